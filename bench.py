@@ -3,7 +3,7 @@
 bench.py — BASELINE.json metric: train-step timesteps*samples/sec, RadLIF 3x1024 on synthetic
 SSC-shaped input (B=256 per GPU, T=250, C=700), fp32, at 1/2/4/8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the training hot path over one resident synthetic batch:
@@ -17,10 +17,14 @@ Other workloads (`--workload`): cfg2 / cfg4 / cfg5 are BASELINE.json configs[1] 
 audio through the HIP mel filterbank inside the step), rnn / mlp / ligru / gru the reference's non-spiking
 baselines at the headline shape (SURVEY f-4).  The driver's default line is cfg3.
 
-Rank 0 prints ONE JSON line with the contract keys plus
-  "roofline":     dominant kernel's achieved algorithmic rate vs the gfx950 peak (HIP events, live)
+Rank 0 prints ONE JSON line with the contract keys.  A plain run measures the headline figure only: set-up,
+warm-up, the timed steps, the outputs (--dump-outputs), the line.  With --full the line also holds
+  "roofline":     dominant kernel's achieved algorithmic rate vs the gfx950 peak (HIP events, live; a captured
+                  graph takes `steps` extra eagerly launched, instrumented steps after the timed region)
+  "kernels_ms_per_step": the HIP-event time of every named call per step
   "cpu_baseline": the CPU oracle (a validated restatement of the reference's eager PyTorch path,
-                  oracle/snn_oracle.py) timed on this host's cores on a bounded sample.
+                  oracle/snn_oracle.py) timed on this host's cores on a bounded sample (cfg3, one GPU).
+Without --full those keys are null.
 """
 import argparse
 import json
@@ -203,6 +207,16 @@ def cpu_baseline(state_dict, x_cpu, y_cpu):
                       f"with flush-to-zero {ftz:.1f} s (footnote; the reference runs with denormals on)"}
 
 
+def dump_outputs(out_dir, arrays):
+    """Writes {name: tensor or None} as out_dir/<name>.npy in float32 (None: not written)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,7 +225,14 @@ def main():
                     help="untimed warm-up steps (default: 3; cfg2 / cfg4: 50 / 20 — a ~1 ms step needs tens of ms "
                          "of work before the clocks have settled: cfg2 reads 1.35 ms per step with 5 + 20 steps and "
                          "1.0 ms with 50 + 200, the headline workload 6.5 ms either way)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP-event times, the "
+                         "roofline object and the CPU oracle baseline (cfg3, one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller (loss.npy, the "
+                         "network output out.npy, the firing rates rates.npy) into DIR, float32.  The step history "
+                         "depends on the launch mode: compare runs with the same --graph")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg3")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N>1: weak = the workload's batch per GPU, strong = that batch split over the GPUs")
@@ -228,6 +249,8 @@ def main():
         args.steps = short_step[0]
     if args.warmup is None:
         args.warmup = short_step[1]
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     global WORKLOAD
     WORKLOAD = WORKLOADS[args.workload]
 
@@ -270,7 +293,8 @@ def main():
         net = sparch_amd.SNN((B, None, C), w["layer_sizes"], neuron_type=w["neuron_type"], dropout=w["pdrop"],
                              normalization="batchnorm", bidirectional=bidir).to(dev)
     net.train()
-    state0 = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}  # for the CPU baseline leg
+    state0 = ({k: v.detach().cpu().clone() for k, v in net.state_dict().items()}  # for the CPU baseline leg
+              if args.full else None)
     opt = sparch_amd.optim.Adam(net.parameters(), 1e-2)  # exp.py:89 (same arithmetic, one launch: SURVEY f-2)
     loss_fn = Fn.CrossEntropyLoss()                 # exp.py:100 (one launch for the loss and its gradient)
     reducer = dp.GradAllReducer(net, rows_per_rank=B) if multi else None
@@ -286,6 +310,9 @@ def main():
     y_cpu = torch.randint(0, w["layer_sizes"][-1], (B,), generator=g)
     x, y = x_cpu.to(dev), y_cpu.to(dev)
     torch.manual_seed(99 + rank)
+    # the eager step's output and firing rates (None for the non-spiking baselines), for --dump-outputs; detached:
+    # a reference to the step's autograd graph would reach into the graph capture that may follow the warm-up
+    last = {}
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -296,6 +323,7 @@ def main():
         if reducer is not None:
             reducer.finish()
         opt.step()
+        last["out"], last["rates"] = out.detach(), (rates.detach() if rates is not None else None)
         return loss
 
     spiking = w["neuron_type"] not in ("RNN", "MLP", "LiGRU", "GRU")
@@ -370,7 +398,8 @@ def main():
 
     def timed_region():
         Fn.timer.reset()
-        Fn.timer.enabled = graphed is None  # HIP events per named call exist only for eagerly launched kernels
+        # HIP events per named call (--full) exist only for eagerly launched kernels
+        Fn.timer.enabled = args.full and graphed is None
         if multi:
             dist.barrier()
         torch.cuda.synchronize()
@@ -390,8 +419,11 @@ def main():
         dt, host_dt, totals, loss = timed_region()
         if not kernels_ok("timed region after the degrade"):
             raise SystemExit("bench.py: persistent-kernel timeouts persist after degrading to per-step launches")
+    if args.dump_outputs and rank == 0:
+        out, rates = (graphed.out, graphed.rates) if graphed is not None else (last["out"], last["rates"])
+        dump_outputs(args.dump_outputs, {"loss": loss, "out": out, "rates": rates})
     roof_note = None
-    if graphed is not None:
+    if graphed is not None and args.full:
         # per-kernel durations for the roofline object: the same kernels launched eagerly (a graph replay has no
         # per-kernel HIP events), `steps` instrumented steps right after the timed region
         graphed.close()
@@ -443,10 +475,11 @@ def main():
                         "frac": ach / PEAK_HBM_GBS, "traffic": traffic, "avg_ms": kern[dom]["avg_ms"]}
                 if traffic_src is not None:
                     roof["traffic_profile"] = traffic_src
-        print(f"[bench] gpu: {value:.0f} ts*samples/s, {ms:.2f} ms/step; dominant {dom}; "
-              f"timing the CPU oracle sample next", file=sys.stderr, flush=True)
+        cpu_leg = args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg3"
+        print(f"[bench] gpu: {value:.0f} ts*samples/s, {ms:.2f} ms/step; dominant {dom}"
+              + ("; timing the CPU oracle sample next" if cpu_leg else ""), file=sys.stderr, flush=True)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg3":
+        if cpu_leg:
             cpu = cpu_baseline(state0, x_cpu, y_cpu)
         titles = {"cfg3": "RadLIF 3x1024 SSC shape", "cfg2": "adLIF 3x512 SHD shape",
                   "cfg4": "RadLIF 3x1024 on SC raw audio through the HIP mel front-end",
@@ -478,7 +511,8 @@ def main():
                                            "window": "all-reduce per layer, in the windows between persistent launches",
                                            "deferred": "one collective after backward"}[reducer.policy])},
             "roofline": roof, "cpu_baseline": cpu,
-            "kernels_ms_per_step": {k: round(v["avg_ms"] * v["launches"] / args.steps, 4) for k, v in kern.items()},
+            "kernels_ms_per_step": ({k: round(v["avg_ms"] * v["launches"] / args.steps, 4) for k, v in kern.items()}
+                                    if args.full else None),
             "final_loss": final_loss,
             # host time to enqueue one step (no synchronisation inside): well below ms_per_step = the GPU is the bound
             "host_enqueue_ms_per_step": round(1e3 * host_dt / args.steps, 3),

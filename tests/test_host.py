@@ -217,3 +217,24 @@ def test_bench_roofline_traffic_comes_from_the_profile_of_the_workload_run():
     assert val is not None and src["file"].endswith("cfg2.json")
     assert bench.pmc_traffic("rec_cell_bwd[RadLIF]", "cfg5", False) == (None, None)  # no fp32 pass of cfg5 is tracked
     assert bench.pmc_traffic("gemm_nn[64000x1024x1024]", "mlp", False) == (None, None)
+
+
+
+def test_bench_dump_outputs_writes_float32_npy(tmp_path):
+    """bench.py --dump-outputs: every array the step returned as <name>.npy in float32, values unchanged; an absent
+    one (the non-spiking baselines have no firing rates) is not written."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor(1.5), "out": torch.randn(4, 3, generator=g),
+              "rates": torch.rand(6, generator=g).to(torch.bfloat16), "none": None}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["loss.npy", "out.npy", "rates.npy"]
+    for k in ("loss", "out", "rates"):
+        a = np.load(tmp_path / "d" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == tuple(arrays[k].shape)
+        assert np.array_equal(a, arrays[k].float().numpy())

@@ -3,8 +3,8 @@
 # gpurun call.   usage: tools/ab_lib.sh OUT_PREFIX VARIANT_NAME [bench args]
 P=$1; V=$2; shift 2
 for rep in 1 2; do
-  SPARCH_HIP_LIB=$PWD/sparch_amd/libsparch_hip_$V.so timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > ${P}_${V}_$rep.json
-  timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > ${P}_new_$rep.json
+  SPARCH_HIP_LIB=$PWD/sparch_amd/libsparch_hip_$V.so timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > ${P}_${V}_$rep.json
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > ${P}_new_$rep.json
 done
 python - <<PY
 import json, glob

@@ -1,7 +1,7 @@
 #!/bin/bash
 # bench.py with the shipped library and with several diagnostic variant libraries, round-robin, in ONE gpurun call.
 # usage: tools/ab_libs.sh "bench args" main variant1 variant2 ...
-ARGS=$1; shift
+ARGS="--full $1"; shift  # --full: the per-kernel times compared below
 for rep in 1 2; do
   for V in "$@"; do
     if [ "$V" = main ]; then F=$PWD/sparch_amd/libsparch_hip.so; else F=$PWD/sparch_amd/libsparch_hip_$V.so; fi
