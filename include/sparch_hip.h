@@ -403,6 +403,16 @@ int sparch_fbank_frames(int n_samples);
 int sparch_fbank_fwd(int n_clips, int n_samples, int n_mels, const float* wave, float* out,
                      void* stream);
 
+/* G9  variable-length clips, padded (the reference's HD / SC collate: kaldi.fbank per clip, then
+ *     pad_sequence(batch_first=True), nonspiking_datasets.py:96,104-111,194,202-209).  Clip i is
+ *     row i of wave (n_clips, ld), in_dtype 0 = fp32 in [-1,1], 1 = int16 PCM (scaled by 2^-15 on
+ *     load: bit-identical to the fp32 path on pcm/32768).  lengths (n_clips) device int32 samples;
+ *     clip i has f_i = sparch_fbank_frames(min(max(lengths[i], 0), ld)) frames.  out (n_clips,
+ *     n_frames_out, n_mels): frames t < f_i as sparch_fbank_fwd gives them for the clip alone (same
+ *     bits), frames f_i <= t < n_frames_out exactly 0.  Nothing past ld or a clip's own end is read.   */
+int sparch_fbank_padded_fwd(int n_clips, int ld, const int* lengths, int n_frames_out, int n_mels,
+                            int in_dtype, const void* wave, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * f-3  SHD/SSC event lists -> dense binned spike counts (replaces SpikingDataset.__getitem__,
  *      spiking_datasets.py:66-78: np.digitize into np.linspace(0, max_time, nb_steps) edges, then a

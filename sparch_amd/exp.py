@@ -7,12 +7,13 @@ checkpointing as a whole-module pickle (456-463, 126-133).
 
 The training step itself (exp.py:352-382) runs on the MI355X path: `sparch_amd.SNN` on a HIP device.
 What this build adds, not replaces:
-  * --synthetic 1: batches of the dataset's shape generated on the fly (no SHD/SSC/HD/SC files exist
-    offline); without it SHD/SSC go through sparch_amd.dataloaders (h5py event lists binned on the device),
-    HD/SC (torchaudio files) are not covered;
-  * hd / sc inputs are raw waveforms turned into 40-bin log-mel features ON THE DEVICE by
-    `sparch_amd.fbank` (the reference calls torchaudio's kaldi.fbank per clip on the CPU,
-    nonspiking_datasets.py:96, 194);
+  * --synthetic 1: batches of the dataset's shape generated on the fly (no dataset files needed);
+    without it SHD/SSC go through sparch_amd.dataloaders.spiking_datasets (h5py event lists binned on the
+    device) and HD/SC through sparch_amd.dataloaders.nonspiking_datasets (audio files decoded on the host);
+  * hd / sc inputs are raw waveforms turned into 40-bin log-mel features ON THE DEVICE (the reference calls
+    torchaudio's kaldi.fbank per clip on the CPU, nonspiking_datasets.py:96, 194): by the file loaders' collate
+    function (`sparch_amd.fbank_padded`: clips of different lengths, zero-padded features as pad_sequence pads
+    them), and for synthetic one-second waves by the trainer (`sparch_amd.fbank`);
   * data parallelism when launched under torch.distributed.run: per-rank batch shard, per-layer
     gradient all-reduce over RCCL (`sparch_amd.dp.GradAllReducer`); rank 0 logs and checkpoints.
 """
@@ -103,6 +104,13 @@ class Experiment:
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
+        # The HD / SC file loaders pad each batch to its own longest clip, so ranks hold different numbers of rows
+        # (B * T); the --sync_bn exchange (functional._Norm) gathers equal-sized statistics from every rank.  Refused
+        # on every rank alike, before the first collective.
+        if self.sync_bn and self.world > 1 and self.dataset_name in _AUDIO_SETS and not self.synthetic:
+            raise ValueError("sparch_amd: --sync_bn needs the same number of time steps on every rank; the hd / sc "
+                             "file loaders give each batch the length of its longest clip. Run without --sync_bn "
+                             "(per-rank BatchNorm statistics) or with --synthetic 1.")
 
         self.init_exp_folders()
         self.init_logging()
@@ -222,18 +230,23 @@ class Experiment:
             raise ValueError(f"batch_size {self.batch_size} must be divisible by the number of GPUs {self.world}")
         per_rank = self.batch_size // self.world
         if not self.synthetic:
-            if kind != "spiking":
-                raise RuntimeError(
-                    "sparch_amd: the file-based HD/SC (torchaudio) loader of the reference is not part of this "
-                    "build (no torchaudio offline); run with --synthetic 1")
-            from .dataloaders.spiking_datasets import load_shd_or_ssc  # exp.py:224-252 (needs h5py + the files)
+            # data-parallel: each rank draws its 1/world share of every epoch
+            if kind == "spiking":
+                from .dataloaders.spiking_datasets import load_shd_or_ssc  # exp.py:224-252 (needs h5py + the files)
 
-            def ld(split, shuffle):  # data-parallel: each rank draws its 1/world share of every epoch
-                return load_shd_or_ssc(self.dataset_name, self.data_folder, split, per_rank, nb_steps=100,
-                                       shuffle=shuffle, device=self.device, rank=self.rank, world=self.world)
+                def ld(split, shuffle):
+                    return load_shd_or_ssc(self.dataset_name, self.data_folder, split, per_rank, nb_steps=100,
+                                           shuffle=shuffle, device=self.device, rank=self.rank, world=self.world)
+            else:
+                from .dataloaders.nonspiking_datasets import load_hd_or_sc  # exp.py:254-288
+
+                def ld(split, shuffle):
+                    return load_hd_or_sc(self.dataset_name, self.data_folder, split, per_rank, shuffle=shuffle,
+                                         use_augm=self.use_augm, device=self.device, rank=self.rank,
+                                         world=self.world)
 
             self.train_loader, self.valid_loader = ld("train", True), ld("valid", False)
-            if self.dataset_name == "ssc":
+            if self.dataset_name in ["sc", "ssc"]:
                 self.test_loader = ld("test", False)
             return
 
@@ -277,7 +290,7 @@ class Experiment:
         y = y.to(self.device, non_blocking=True)
         if x.dtype == torch.uint8:  # spike counts as bytes: expanded on the device
             x = Fn.input_from_counts(x) if self.net.is_snn else x.float()
-        if self.input_kind == "audio":
+        if self.input_kind == "audio" and x.ndim == 2:  # synthetic waves; the file loaders deliver features
             x = fbank(x, num_mel_bins=40)  # (B, 16000) -> (B, 98, 40) on the device
         return x, y
 

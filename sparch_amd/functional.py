@@ -1120,6 +1120,48 @@ def fbank(wave, num_mel_bins=40):
     return out
 
 
+def fbank_padded(wave, lengths, num_mel_bins=40):
+    """Log-mel features of clips of different lengths, padded as the reference's HD / SC collate pads them
+    (kaldi.fbank per clip, then pad_sequence: nonspiking_datasets.py:96-111, 194-209).
+
+    wave: (B, ld) device tensor, fp32 in [-1, 1] or int16 PCM (scaled by 2^-15 in the kernel; the same bits as the
+    fp32 path on pcm / 32768); clip i is wave[i, :lengths[i]].  lengths: B host ints or a tensor (samples).
+    Returns (feats (B, T_max, num_mel_bins) fp32 on the device, frames (B,) int64 on the host): clip i's frames
+    t < frames[i] are fbank(wave[i, :lengths[i]]) bit for bit, the later ones exactly 0; T_max = frames.max().
+    Raises ValueError when a length exceeds ld or when no clip reaches one frame (400 samples)."""
+    _require_device(wave, "waveform")
+    if wave.ndim != 2:
+        raise ValueError(f"fbank_padded: wave must be (clips, samples), got shape {tuple(wave.shape)}")
+    if wave.dtype == torch.int16:
+        in_dtype, wave = 1, wave.contiguous()
+    else:
+        in_dtype, wave = 0, _f32c(wave)
+    n_clips, ld = wave.shape
+    lens = torch.as_tensor(lengths).detach().to("cpu", torch.int64).reshape(-1)
+    if lens.numel() != n_clips:
+        raise ValueError(f"fbank_padded: {lens.numel()} lengths for {n_clips} clips")
+    if n_clips and int(lens.max()) > ld:
+        raise ValueError(f"fbank_padded: a clip length {int(lens.max())} exceeds the row length {ld}")
+    # sparch_fbank_frames over the batch (400-sample frames every 160 samples); the library's own count of the
+    # longest clip is T_max, and the two must agree
+    n = lens.clamp(min=0)
+    frames = torch.where(n < 400, torch.zeros_like(n), 1 + torch.div(n - 400, 160, rounding_mode="floor"))
+    n_frames = lib.sparch_fbank_frames(int(n.max())) if n_clips else 0
+    if n_clips and int(frames.max()) != n_frames:
+        raise RuntimeError(f"fbank_padded: frame count {int(frames.max())} differs from the library's {n_frames}")
+    if n_frames == 0:
+        raise ValueError("fbank_padded: no clip is long enough for one frame (400 samples)")
+    # from pinned memory without blocking the host: the caching host allocator does not hand the block out again
+    # before the copy has completed
+    lens_dev = lens.to(torch.int32).pin_memory().to(wave.device, non_blocking=True)
+    out = torch.empty(n_clips, n_frames, num_mel_bins, dtype=torch.float32, device=wave.device)
+    tok = timer.start(f"fbank_padded[{n_clips}x{ld}]")
+    check(lib.sparch_fbank_padded_fwd(n_clips, ld, ptr(lens_dev), n_frames, num_mel_bins, in_dtype, ptr(wave),
+                                      ptr(out), _stream()), "sparch_fbank_padded_fwd")
+    timer.stop(tok)
+    return out, frames
+
+
 def bin_events(times, units, nb_steps=100, nb_units=700, max_time=1.4, device="cuda"):
     """Batch of event lists -> dense (B, nb_steps, nb_units) float32 spike counts on the device, as the
     reference's SpikingDataset.__getitem__ builds them per sample on the CPU (spiking_datasets.py:66-78).
