@@ -413,6 +413,35 @@ int sparch_fbank_fwd(int n_clips, int n_samples, int n_mels, const float* wave, 
 int sparch_fbank_padded_fwd(int n_clips, int ld, const int* lengths, int n_frames_out, int n_mels,
                             int in_dtype, const void* wave, float* out, void* stream);
 
+/* f-3  FLAC (RFC 9639) decoding into the padded waveform buffer of the HD collate (replaces
+ *     torchaudio.load at nonspiking_datasets.py:90).  bytes (n_bytes, device, n_bytes % 4 == 0) holds
+ *     the files of n_clips clips, each starting at a 4-aligned offset; clips (n_clips,
+ *     SPARCH_FLAC_CLIP_FIELDS) device int64 describes clip i: byte range [begin, end), absolute offset
+ *     of its first frame, STREAMINFO total samples, output row, sample rate, channels (1-8), bits per
+ *     sample (4-24), min / max block size, then its workspace share: slot base and slot count (at least
+ *     ceil(total / min block): one slot per frame) and, for 2 channels, scratch base (int32 elements,
+ *     slots x max block of them).  Slot bases ascend with i.  out (n_rows, ld): out_dtype 0 = fp32
+ *     x * 2^-(bps-1), 1 = int16 (16-bit clips only); channel 0 of clip i goes to samples
+ *     [0, total) of its row, nothing else is written.  err (2, device int64, 8-aligned), written by the
+ *     call: [0] clips in error, [1] (clip << 32) | (frame << 8) | SPARCH_FLAC_E* reason of the lowest
+ *     failing clip (all ones when none).  A clip fails when its table row is inconsistent, a frame
+ *     header or subframe is invalid, a frame runs past the clip's bytes, a CRC-16 differs, or the frames
+ *     do not add up to `total`; no read leaves the clip's bytes, whatever they hold.  Workspace: from
+ *     sparch_flac_workspace_bytes(sum of slot counts, sum of scratch sizes), 16-aligned.  Launches
+ *     only (stream-ordered memsets included): no allocation, no synchronisation.               */
+#define SPARCH_FLAC_CLIP_FIELDS 13
+#define SPARCH_FLAC_ETABLE 1     /* table row inconsistent with the buffers, the workspace or out_dtype */
+#define SPARCH_FLAC_EHEADER 2    /* no valid frame header (with the expected number) where one must be */
+#define SPARCH_FLAC_ESUBFRAME 3  /* reserved or invalid subframe / residual coding                     */
+#define SPARCH_FLAC_ETRUNC 4     /* a frame runs past the clip's last byte                             */
+#define SPARCH_FLAC_ECRC 5       /* frame CRC-16 mismatch                                              */
+#define SPARCH_FLAC_ELENGTH 6    /* the frames do not add up to the STREAMINFO sample count            */
+size_t sparch_flac_workspace_bytes(long long n_slots, long long n_scratch);
+int sparch_flac_decode_padded(int n_clips, const long long* clips, const unsigned char* bytes, long long n_bytes,
+                              long long n_slots, long long n_scratch, int n_rows, int ld, int out_dtype,
+                              void* out, long long* err, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ------------------------------------------------------------------------------------
  * f-3  SHD/SSC event lists -> dense binned spike counts (replaces SpikingDataset.__getitem__,
  *      spiking_datasets.py:66-78: np.digitize into np.linspace(0, max_time, nb_steps) edges, then a

@@ -92,6 +92,9 @@ PROTOTYPES = {
     "sparch_fbank_frames": (c_int, [c_int]),
     "sparch_fbank_fwd": (c_int, [c_int, c_int, c_int, P, P, P]),
     "sparch_fbank_padded_fwd": (c_int, [c_int, c_int, P, c_int, c_int, c_int, P, P, P]),
+    "sparch_flac_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
+    "sparch_flac_decode_padded": (c_int, [c_int, P, P, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
+                                          P, P, P, c_size_t, P]),
     "sparch_bin_events": (c_int, [c_longlong, P, P, P, c_int, c_int, c_int, c_double, P, P, P]),
     "sparch_act_fwd": (c_int, [c_int, c_size_t, c_int, P, P, P, c_float, c_uint64, P, P]),
     "sparch_act_bwd": (c_int, [c_int, c_size_t, c_int, P, P, P, P, c_float, c_uint64, P, P]),

@@ -8,9 +8,17 @@ max_snr=0.9, p_noise=0.1, workers=0)`, whose batches keep the `(xs, xlens, ys)` 
 clip's own frames, xlens the frame counts, ys a LongTensor.
 
 What differs is WHERE the features are made: the reference runs torchaudio's kaldi.fbank per clip on the CPU in
-`__getitem__` and pads in the collate function; here `__getitem__` returns the decoded host samples of a clip
-(`audio.read_audio`), and the collate function packs the batch into one pinned buffer, uploads it (16-bit PCM as
-int16) and makes the padded features with one kernel (`functional.fbank_padded`).
+`__getitem__` and pads in the collate function; here `__getitem__` returns the decoded host samples of a WAV clip,
+or the undecoded bytes and STREAMINFO of a FLAC clip (`audio.read_clip`), and the collate function packs the WAV
+samples into one pinned buffer, uploads it (int16 when every clip is 16-bit mono), decodes the FLAC clips into
+their rows of the same device buffer (`functional.flac_decode_padded`, one pinned upload of their bytes) and makes
+the padded features with one kernel (`functional.fbank_padded`).
+
+FLAC decode errors are found without a per-batch synchronisation: the error record is copied to pinned memory
+behind an event, read when the next batch is collated if the event has completed, and at the end of the epoch at
+the latest (FlacError naming the file).  On a dataset's first batch the decoded samples of every mono FLAC clip
+with a non-zero STREAMINFO MD5 are copied back and hashed (one synchronising copy, once): a decoder that misreads
+the format fails there instead of training on wrong audio.
 
 File lists, their order and the labels are the reference's, with two of its bugs left out:
   * SC labels are the sorted subdirectories of `data_folder` minus the first (`_background_noise_` in the v0.02
@@ -29,8 +37,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..functional import fbank_padded
-from .audio import read_audio
+from ..functional import fbank_padded, flac_decode_padded, flac_error_message
+from .audio import FlacError, FlacStream, flac_md5_ok, read_clip
 
 logger = logging.getLogger(__name__)
 
@@ -52,18 +60,22 @@ def _refuse_augmentation(use_augm):
 
 
 class _AudioClips(Dataset):
-    """Clips `file_list` with class indices `targets`; host decoding per item, features per batch on the device."""
+    """Clips `file_list` with class indices `targets`; host decoding of WAV per item, FLAC decoding and features per
+    batch on the device."""
 
     def __init__(self, file_list, targets, device):
         self.file_list, self.targets, self.device = file_list, targets, device
         self._rate_warned = False
+        self._md5_checked = False
+        self._pending = []  # (event, pinned error record, file names) of batches whose FLAC errors are unread
 
     def __len__(self):
         return len(self.file_list)
 
     def __getitem__(self, index):
-        """(samples of channel 0 on the host: int16 for 16-bit mono PCM, float32 otherwise; label)."""
-        x, rate = read_audio(self.file_list[index])
+        """(clip, label): the samples of channel 0 on the host for WAV (int16 for 16-bit mono PCM, float32
+        otherwise), an audio.FlacStream (file bytes and STREAMINFO, not decoded) for FLAC."""
+        x, rate = read_clip(self.file_list[index])
         if rate != SAMPLE_RATE and not self._rate_warned:
             self._rate_warned = True
             logger.warning(f"{self.file_list[index]}: sample rate {rate} Hz; the features assume {SAMPLE_RATE} Hz "
@@ -73,19 +85,71 @@ class _AudioClips(Dataset):
     def generateBatch(self, batch):
         """(xs (B, T_max, 40) on the device, xlens (B,) frame counts, ys (B,)): nonspiking_datasets.py:104-111 with
         the features made once per batch on the device."""
+        self.check_decode_errors(wait=False)
         clips, ys = zip(*batch)
-        lengths = [len(c) for c in clips]
-        pcm16 = all(c.dtype == np.int16 for c in clips)
+        flac = [i for i, c in enumerate(clips) if isinstance(c, FlacStream)]
+        lengths = [c.info.total_samples if isinstance(c, FlacStream) else len(c) for c in clips]
+        pcm16 = all(c.info.bps == 16 and c.info.channels == 1 if isinstance(c, FlacStream) else c.dtype == np.int16
+                    for c in clips)
         # a fresh pinned buffer per batch: the caching host allocator does not hand it out again before the
         # non-blocking copy from it has completed, and nothing writes to it after the copy is enqueued
         host = torch.empty(len(clips), max(lengths), dtype=torch.int16 if pcm16 else torch.float32,
                            pin_memory=torch.cuda.is_available())
         rows = host.numpy()
         for row, c, n in zip(rows, clips, lengths):  # the kernel reads no sample past a clip's length
-            row[:n] = c if pcm16 or c.dtype == np.float32 else c.astype(np.float32) / np.float32(2 ** 15)
+            if not isinstance(c, FlacStream):
+                row[:n] = c if pcm16 or c.dtype == np.float32 else c.astype(np.float32) / np.float32(2 ** 15)
         wave = host.to(self.device, non_blocking=True)
+        if flac:  # FLAC rows: decoded on the device into the same buffer (their host rows are not read)
+            streams = [clips[i] for i in flac]
+            err = flac_decode_padded([c.data for c in streams], [c.info for c in streams], wave, rows=flac)
+            names = [c.path for c in streams]
+            if not self._md5_checked:
+                self._md5_checked = True
+                self._check_md5(wave, flac, streams, err)
+            else:
+                rec = torch.empty(2, dtype=torch.int64, pin_memory=True)
+                rec.copy_(err, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                self._pending.append((ev, rec, names))
         xs, xlens = fbank_padded(wave, lengths, num_mel_bins=40)
         return xs, xlens, torch.LongTensor(ys)
+
+    def _check_md5(self, wave, flac, streams, err):
+        """First FLAC batch of the dataset: decode errors, then the MD5 of every mono clip that carries one."""
+        msg = flac_error_message(err.cpu(), [c.path for c in streams])
+        if msg:
+            raise FlacError(msg)
+        mono = [(i, c) for i, c in zip(flac, streams) if c.info.channels == 1 and c.info.md5 != bytes(16)]
+        if mono:
+            rows = wave[[i for i, _ in mono]].cpu().numpy()
+            for row, (_, c) in zip(rows, mono):
+                if not flac_md5_ok(row[:c.info.total_samples], c.info):
+                    raise FlacError(f"{c.path}: decoded samples do not match the STREAMINFO MD5")
+
+    def check_decode_errors(self, wait=True):
+        """Raise FlacError for the first failed FLAC file of the batches collated so far whose decoding has completed
+        (wait=True: of all of them, waiting for the device)."""
+        while self._pending:
+            ev, rec, names = self._pending[0]
+            if wait:
+                ev.synchronize()
+            elif not ev.query():
+                return
+            self._pending.pop(0)
+            msg = flac_error_message(rec, names)
+            if msg:
+                self._pending.clear()
+                raise FlacError(msg)
+
+
+class _EpochCheckedLoader(DataLoader):
+    """A DataLoader whose iteration ends by reading the decode error records of the epoch's last batches."""
+
+    def __iter__(self):
+        yield from super().__iter__()
+        self.dataset.check_decode_errors(wait=True)
 
 
 class HeidelbergDigits(_AudioClips):
@@ -154,7 +218,7 @@ def load_hd_or_sc(dataset_name, data_folder, split, batch_size, shuffle=True, us
         from torch.utils.data.distributed import DistributedSampler
 
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed)
-        return DataLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch, sampler=sampler,
-                          num_workers=0, pin_memory=False)
-    return DataLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch, shuffle=shuffle,
-                      num_workers=0, pin_memory=False)
+        return _EpochCheckedLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch,
+                                   sampler=sampler, num_workers=0, pin_memory=False)
+    return _EpochCheckedLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch, shuffle=shuffle,
+                               num_workers=0, pin_memory=False)

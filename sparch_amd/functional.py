@@ -1162,6 +1162,91 @@ def fbank_padded(wave, lengths, num_mel_bins=40):
     return out, frames
 
 
+FLAC_CLIP_FIELDS = 13  # SPARCH_FLAC_CLIP_FIELDS
+FLAC_REASONS = {1: "inconsistent clip table entry", 2: "no valid frame header where the previous frame ended",
+                3: "invalid subframe or residual coding", 4: "truncated: a frame runs past the end of the file",
+                5: "frame CRC-16 mismatch", 6: "the frames do not add up to the STREAMINFO sample count"}
+
+
+def flac_pack(streams, infos, rows, n_rows, ld, int16):
+    """Host half of `flac_decode_padded`: (pinned uint8 tensor of the streams, each at a 4-aligned offset; clip
+    table (n, FLAC_CLIP_FIELDS) int64; slot count; scratch int32 count), checked against an (n_rows, ld) output."""
+    import numpy as np
+
+    n = len(streams)
+    if n == 0 or len(infos) != n or len(rows) != n:
+        raise ValueError("flac_decode_padded: one descriptor and one row per stream, at least one stream")
+    sizes = [len(s) for s in streams]
+    begins = np.zeros(n + 1, np.int64)
+    begins[1:] = np.cumsum([(z + 3) & ~3 for z in sizes])
+    table = np.zeros((n, FLAC_CLIP_FIELDS), np.int64)
+    slot_base = scratch_base = 0
+    for k, (info, row) in enumerate(zip(infos, rows)):
+        if info is None or not 0 <= row < n_rows or info.total_samples > ld:
+            raise ValueError(f"flac_decode_padded: stream {k}: no descriptor, row {row} outside {n_rows} rows, or "
+                             f"{getattr(info, 'total_samples', '?')} samples exceed the row length {ld}")
+        if int16 and info.bps != 16:
+            raise ValueError(f"flac_decode_padded: stream {k} has {info.bps}-bit samples; int16 rows take 16 bits")
+        slots = -(-info.total_samples // info.min_block)                  # frames <= ceil(total / min block)
+        scratch = slots * info.max_block if info.channels == 2 else 0
+        table[k] = (begins[k], begins[k] + sizes[k], begins[k] + info.first_frame, info.total_samples, row,
+                    info.sample_rate, info.channels, info.bps, info.min_block, info.max_block, slot_base, slots,
+                    scratch_base)
+        slot_base += slots
+        scratch_base += scratch
+    host = torch.empty(int(begins[-1]), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    buf = host.numpy()
+    for k, s in enumerate(streams):
+        buf[begins[k]:begins[k] + sizes[k]] = np.frombuffer(s, np.uint8)
+        buf[begins[k] + sizes[k]:begins[k + 1]] = 0
+    return host, table, slot_base, scratch_base
+
+
+def flac_decode_padded(streams, infos, wave, rows=None):
+    """Decode FLAC streams on the device into rows of `wave` (sparch_flac_decode_padded).
+
+    streams: file contents (bytes); infos: their `dataloaders.audio.parse_flac` descriptors; wave: (R, ld) device
+    tensor, fp32 (x * 2^-(bps-1)) or int16 (16-bit streams only); rows: the row of each stream (default 0, 1, ...).
+    Channel 0 of stream k fills wave[rows[k], :total_samples]; nothing else of `wave` is written.  The file bytes go
+    up in one pinned copy.  Returns the device error record (2,) int64 without synchronising: read it with
+    `flac_error_message` once the stream has reached it."""
+    _require_device(wave, "waveform")
+    if wave.ndim != 2 or not wave.is_contiguous() or wave.dtype not in (torch.float32, torch.int16):
+        raise ValueError("flac_decode_padded: wave must be a contiguous (rows, samples) fp32 or int16 tensor")
+    n_rows, ld = wave.shape
+    rows = list(range(len(streams))) if rows is None else [int(r) for r in rows]
+    int16 = wave.dtype == torch.int16
+    host, table, n_slots, n_scratch = flac_pack(streams, infos, rows, n_rows, ld, int16)
+    dev = wave.device
+    # from pinned memory without blocking the host (the caching host allocator keeps both blocks until the copies
+    # are done)
+    bytes_d = host.to(dev, non_blocking=True)
+    table_d = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+    ws_bytes = lib.sparch_flac_workspace_bytes(n_slots, n_scratch)
+    if ws_bytes == 0:
+        raise ValueError(f"flac_decode_padded: workspace of {n_slots} frame slots out of range")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    err = torch.empty(2, dtype=torch.int64, device=dev)
+    tok = timer.start(f"flac_decode_padded[{len(streams)}x{ld}]")
+    check(lib.sparch_flac_decode_padded(len(streams), ptr(table_d), ptr(bytes_d), host.numel(), n_slots, n_scratch,
+                                        n_rows, ld, 1 if int16 else 0, ptr(wave), ptr(err), ptr(ws), ws_bytes,
+                                        _stream()), "sparch_flac_decode_padded")
+    timer.stop(tok)
+    return err
+
+
+def flac_error_message(record, names):
+    """Text of a `flac_decode_padded` error record (a host copy) naming the failing file of `names` (the streams in
+    the order they were passed), or None when every stream decoded."""
+    count, key = (int(v) for v in record)
+    if count == 0:
+        return None
+    key &= (1 << 64) - 1
+    clip, frame, reason = key >> 32, (key >> 8) & 0xFFFFFF, key & 0xFF
+    msg = f"{names[clip]}: FLAC frame {frame}: {FLAC_REASONS.get(reason, f'reason {reason}')}"
+    return msg + (f" ({count - 1} more file(s) of the batch failed)" if count > 1 else "")
+
+
 def bin_events(times, units, nb_steps=100, nb_units=700, max_time=1.4, device="cuda"):
     """Batch of event lists -> dense (B, nb_steps, nb_units) float32 spike counts on the device, as the
     reference's SpikingDataset.__getitem__ builds them per sample on the CPU (spiking_datasets.py:66-78).
