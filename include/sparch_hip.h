@@ -413,6 +413,26 @@ int sparch_fbank_fwd(int n_clips, int n_samples, int n_mels, const float* wave, 
 int sparch_fbank_padded_fwd(int n_clips, int ld, const int* lengths, int n_frames_out, int n_mels,
                             int in_dtype, const void* wave, float* out, void* stream);
 
+/* f-3  Waveform augmentation of HD / SC training clips (replaces torchaudio_augmentations 0.2.4's
+ *     ComposeMany of RandomApply(PolarityInversion, .8), (Noise(min_snr, max_snr), p_noise),
+ *     (Gain, .3), (Reverb(16000), .6) at nonspiking_datasets.py:71-78,93,170-177,191; restated,
+ *     parity unpinned).  Clip i is wave[i, :len_i], len_i = min(max(lengths[i], 0), ld), in_dtype 0 =
+ *     fp32, 1 = int16 scaled by 2^-15; lengths (n_clips) device int32.  params (n_clips,
+ *     SPARCH_AUGM_FIELDS) device fp32, per clip: polarity, noise, gain, reverb flags (0 / 1), the noise
+ *     uniform u, the gain ratio, reverberance, HF damping and room scale in percent (clamped to
+ *     [0, 100]).  Noise: std = unbiased std of the clip (len_i >= 2, else no noise), noise_std =
+ *     a + (b - a) u with a = min_snr std, b = max_snr std (fp32), normal values from a Philox4x32-10
+ *     stream keyed by (noise_seed, i, sample).  Reverb: sox 14.4 `reverb R D S` at sample_rate
+ *     (8000-48000), stereo depth 100 %, then `channels 1`; same length out, no tail.  Writes exactly
+ *     out[i, :len_i] (out (n_clips, ld) fp32, not overlapping wave) and reads nothing past len_i.
+ *     Launch only: no allocation, no synchronisation.  sparch_augment_lds_bytes(sample_rate): the
+ *     dynamic LDS of one workgroup (0 outside 8000-48000).                                          */
+#define SPARCH_AUGM_FIELDS 9
+int sparch_augment_lds_bytes(int sample_rate);
+int sparch_augment_padded(int n_clips, int ld, const int* lengths, int in_dtype, const void* wave,
+                          const float* params, float min_snr, float max_snr, unsigned long long noise_seed,
+                          int sample_rate, float* out, void* stream);
+
 /* f-3  FLAC (RFC 9639) decoding into the padded waveform buffer of the HD collate (replaces
  *     torchaudio.load at nonspiking_datasets.py:90).  bytes (n_bytes, device, n_bytes % 4 == 0) holds
  *     the files of n_clips clips, each starting at a 4-aligned offset; clips (n_clips,

@@ -6,8 +6,8 @@ There is no CPU fallback: importing this package without the built library fails
 """
 from . import _capi  # noqa: F401  (fails loudly when libsparch_hip.so is missing)
 from . import optim  # noqa: F401
-from .functional import (bin_events, check_status, compute_dtype, fbank, fbank_padded,  # noqa: F401
-                         flac_decode_padded, set_compute_dtype)
+from .functional import (augment_padded, bin_events, check_status, compute_dtype, fbank,  # noqa: F401
+                         fbank_padded, flac_decode_padded, set_compute_dtype)
 from .snns import (SNN, LIFLayer, RLIFLayer, RadLIFLayer, ReadoutLayer,  # noqa: F401
                    SpikeFunctionBoxcar, adLIFLayer)
 

@@ -92,6 +92,8 @@ PROTOTYPES = {
     "sparch_fbank_frames": (c_int, [c_int]),
     "sparch_fbank_fwd": (c_int, [c_int, c_int, c_int, P, P, P]),
     "sparch_fbank_padded_fwd": (c_int, [c_int, c_int, P, c_int, c_int, c_int, P, P, P]),
+    "sparch_augment_lds_bytes": (c_int, [c_int]),
+    "sparch_augment_padded": (c_int, [c_int, c_int, P, c_int, P, P, c_float, c_float, c_uint64, c_int, P, P]),
     "sparch_flac_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
     "sparch_flac_decode_padded": (c_int, [c_int, P, P, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
                                           P, P, P, c_size_t, P]),

@@ -26,8 +26,16 @@ File lists, their order and the labels are the reference's, with two of its bugs
   * the SC training split drops the files named in validation_list.txt and testing_list.txt; the reference
     compares path strings, which silently drops nothing when `data_folder` starts with "./".  Here paths are
     compared relative to `data_folder`.
-`use_augm=True` raises NotImplementedError: the reference's augmentation (torchaudio_augmentations, whose Reverb
-is a sox effect) is not available, and training without it while the caller asked for it would be worse.
+Augmentation (`use_augm=True`) is an explicit opt-in.  The reference's transforms (torchaudio_augmentations, whose
+Reverb is a sox effect) are not available, so this build restates them (DESIGN.md §4 "augment", parity UNPINNED
+against the real libraries), and they are used only when the environment variable SPARCH_AUGMENT is "restated" when
+the dataset is constructed.  Unset or empty, `use_augm=True` raises NotImplementedError as before: training without
+augmentation, or with a different one, while the caller asked for the reference's would be worse.  Any other value
+is a ValueError.  With the variable set, the HD `train` and SC `training` splits draw the reference's per-clip
+decisions once per batch in the collate function (`augment.draw_augmentation`: Python's `random` and torch's
+generator in the reference's order) and apply them to the decoded batch on the device (`functional.augment_padded`)
+before the features; the other splits are not augmented, as in the reference.  The first-batch MD5 check reads the
+decoded samples before augmentation.
 """
 import logging
 import os
@@ -37,8 +45,9 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..functional import fbank_padded, flac_decode_padded, flac_error_message
+from ..functional import augment_padded, fbank_padded, flac_decode_padded, flac_error_message
 from .audio import FlacError, FlacStream, flac_md5_ok, read_clip
+from .augment import draw_augmentation
 
 logger = logging.getLogger(__name__)
 
@@ -53,18 +62,31 @@ def hd_label(filename):
     return int(os.path.splitext(name)[0][-1]) + (10 if name[5] == "g" else 0)
 
 
-def _refuse_augmentation(use_augm):
-    if use_augm:
+AUGMENT_ENV = "SPARCH_AUGMENT"
+
+
+def _augmentation(use_augm, augmented_split, min_snr, max_snr, p_noise):
+    """(min_snr, max_snr, p_noise) when this split is augmented, else None.  use_augm needs SPARCH_AUGMENT=restated,
+    read here (at construction) and not at import."""
+    if not use_augm:
+        return None
+    mode = os.environ.get(AUGMENT_ENV, "")
+    if mode == "":
         raise NotImplementedError("sparch_amd.dataloaders: data augmentation of HD / SC (torchaudio_augmentations "
-                                  "in the reference) is not part of this build; run with --use_augm False")
+                                  "in the reference) is not part of this build; run with --use_augm False. "
+                                  f"{AUGMENT_ENV}=restated selects this build's restatement of it (unpinned).")
+    if mode != "restated":
+        raise ValueError(f"{AUGMENT_ENV}={mode!r}: the only value is 'restated'")
+    return (min_snr, max_snr, p_noise) if augmented_split else None
 
 
 class _AudioClips(Dataset):
     """Clips `file_list` with class indices `targets`; host decoding of WAV per item, FLAC decoding and features per
     batch on the device."""
 
-    def __init__(self, file_list, targets, device):
+    def __init__(self, file_list, targets, device, augment=None):
         self.file_list, self.targets, self.device = file_list, targets, device
+        self.augment = augment  # (min_snr, max_snr, p_noise) of an augmented split, else None
         self._rate_warned = False
         self._md5_checked = False
         self._pending = []  # (event, pinned error record, file names) of batches whose FLAC errors are unread
@@ -113,6 +135,10 @@ class _AudioClips(Dataset):
                 ev = torch.cuda.Event()
                 ev.record()
                 self._pending.append((ev, rec, names))
+        if self.augment is not None:  # nonspiking_datasets.py:93, 191, per clip in batch order; sox is told 16 kHz
+            min_snr, max_snr, p_noise = self.augment
+            params, noise_seed = draw_augmentation(len(clips), min_snr, max_snr, p_noise)
+            wave = augment_padded(wave, lengths, params, noise_seed, min_snr, max_snr, sample_rate=SAMPLE_RATE)
         xs, xlens = fbank_padded(wave, lengths, num_mel_bins=40)
         return xs, xlens, torch.LongTensor(ys)
 
@@ -159,12 +185,12 @@ class HeidelbergDigits(_AudioClips):
     def __init__(self, data_folder, split, use_augm, min_snr, max_snr, p_noise, device="cuda"):
         if split not in ["train", "test"]:
             raise ValueError(f"Invalid split {split}")
-        _refuse_augmentation(use_augm)
+        augment = _augmentation(use_augm, split == "train", min_snr, max_snr, p_noise)
         self.data_folder = data_folder
         with open(os.path.join(data_folder, f"{split}_filenames.txt")) as f:
             names = [n for n in f.read().splitlines() if n.strip()]
         super().__init__([os.path.join(data_folder, "audio", n) for n in names], [hd_label(n) for n in names],
-                         device)
+                         device, augment)
 
 
 class SpeechCommands(_AudioClips):
@@ -175,7 +201,7 @@ class SpeechCommands(_AudioClips):
     def __init__(self, data_folder, split, use_augm, min_snr, max_snr, p_noise, device="cuda"):
         if split not in ["training", "validation", "testing"]:
             raise ValueError(f"Invalid split {split}")
-        _refuse_augmentation(use_augm)
+        augment = _augmentation(use_augm, split == "training", min_snr, max_snr, p_noise)
         self.data_folder = data_folder
 
         def load_list(filename):  # paths relative to data_folder, normalised ("./yes/a.wav" -> "yes/a.wav")
@@ -190,7 +216,7 @@ class SpeechCommands(_AudioClips):
             files = load_list(f"{split}_list.txt")
         self.labels = sorted(next(os.walk(data_folder))[1])[1:]
         super().__init__([os.path.join(data_folder, w) for w in files],
-                         [self.labels.index(os.path.dirname(w)) for w in files], device)
+                         [self.labels.index(os.path.dirname(w)) for w in files], device, augment)
 
 
 def load_hd_or_sc(dataset_name, data_folder, split, batch_size, shuffle=True, use_augm=False, min_snr=0.0001,

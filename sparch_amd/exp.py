@@ -248,6 +248,8 @@ class Experiment:
             self.train_loader, self.valid_loader = ld("train", True), ld("valid", False)
             if self.dataset_name in ["sc", "ssc"]:
                 self.test_loader = ld("test", False)
+            if kind == "audio" and self.use_augm:  # exp.py:285-286
+                logging.info("\nData augmentation is used\n")
             return
 
         def mk(seed):

@@ -1162,6 +1162,64 @@ def fbank_padded(wave, lengths, num_mel_bins=40):
     return out, frames
 
 
+AUGM_FIELDS = 9  # SPARCH_AUGM_FIELDS
+
+
+def augment_padded(wave, lengths, params, noise_seed, min_snr, max_snr, sample_rate=16000):
+    """Waveform augmentation of padded clips on the device (sparch_augment_padded): the reference's training-split
+    transforms (torchaudio_augmentations' PolarityInversion, Noise, Gain and sox's reverb, nonspiking_datasets.py:71-78,
+    170-177), restated (DESIGN.md §4 "augment", parity unpinned), with the per-clip decisions and values drawn on the
+    host (`dataloaders.augment.draw_augmentation`).
+
+    wave: (B, ld) device tensor, fp32 or int16 PCM (scaled by 2^-15); clip i is wave[i, :lengths[i]].  lengths: B host
+    ints or a tensor (a negative length counts as 0).  params: (B, AUGM_FIELDS) host table, per clip the polarity,
+    noise, gain and reverb flags (0 / 1), the noise uniform u, the gain ratio, reverberance, HF damping and room scale
+    in [0, 100].  noise_seed: key of the noise stream; min_snr / max_snr: the Noise bounds; sample_rate: what sox is
+    told (the reference passes 16000 for every clip).
+    Returns a fresh fp32 (B, ld) device tensor: row i holds the augmented clip in [:lengths[i]] and is not written
+    after it.  Raises ValueError for a length past ld or a table entry out of range."""
+    _require_device(wave, "waveform")
+    if wave.ndim != 2:
+        raise ValueError(f"augment_padded: wave must be (clips, samples), got shape {tuple(wave.shape)}")
+    if wave.dtype == torch.int16:
+        in_dtype, wave = 1, wave.contiguous()
+    else:
+        in_dtype, wave = 0, _f32c(wave)
+    n_clips, ld = wave.shape
+    lens = torch.as_tensor(lengths).detach().to("cpu", torch.int64).reshape(-1)
+    if lens.numel() != n_clips:
+        raise ValueError(f"augment_padded: {lens.numel()} lengths for {n_clips} clips")
+    if n_clips and int(lens.max()) > ld:
+        raise ValueError(f"augment_padded: a clip length {int(lens.max())} exceeds the row length {ld}")
+    table = torch.as_tensor(params).detach().to("cpu", torch.float32).contiguous()
+    if tuple(table.shape) != (n_clips, AUGM_FIELDS):
+        raise ValueError(f"augment_padded: params must be ({n_clips}, {AUGM_FIELDS}), got {tuple(table.shape)}")
+    flags, u, ratio, rds = table[:, :4], table[:, 4], table[:, 5], table[:, 6:]
+    if not bool(((flags == 0) | (flags == 1)).all()):
+        raise ValueError("augment_padded: stage flags must be 0 or 1")
+    # u in [0, 1): random.random() rounded to fp32, which rounds up to 1.0 for the last 2^-25 of the range
+    if not bool(((u >= 0) & (u <= 1)).all()):
+        raise ValueError("augment_padded: the noise uniform must lie in [0, 1)")
+    if not bool(torch.isfinite(ratio).all()):
+        raise ValueError("augment_padded: the gain ratio must be finite")
+    if not bool(((rds >= 0) & (rds <= 100)).all()):
+        raise ValueError("augment_padded: reverberance, HF damping and room scale must lie in [0, 100]")
+    if not 8000 <= int(sample_rate) <= 48000:
+        raise ValueError(f"augment_padded: sample rate {sample_rate} outside 8000-48000 Hz")
+    dev = wave.device
+    # from pinned memory without blocking the host (the caching host allocator keeps the blocks until the copies
+    # are done)
+    lens_dev = lens.to(torch.int32).pin_memory().to(dev, non_blocking=True)
+    table_dev = table.pin_memory().to(dev, non_blocking=True)
+    out = torch.empty(n_clips, ld, dtype=torch.float32, device=dev)
+    tok = timer.start(f"augment_padded[{n_clips}x{ld}]")
+    check(lib.sparch_augment_padded(n_clips, ld, ptr(lens_dev), in_dtype, ptr(wave), ptr(table_dev), float(min_snr),
+                                    float(max_snr), int(noise_seed) & (2 ** 64 - 1), int(sample_rate), ptr(out),
+                                    _stream()), "sparch_augment_padded")
+    timer.stop(tok)
+    return out
+
+
 FLAC_CLIP_FIELDS = 13  # SPARCH_FLAC_CLIP_FIELDS
 FLAC_REASONS = {1: "inconsistent clip table entry", 2: "no valid frame header where the previous frame ended",
                 3: "invalid subframe or residual coding", 4: "truncated: a frame runs past the end of the file",
