@@ -473,6 +473,33 @@ int sparch_bin_events(long long n_events, const float* times, const int* units,
                       const long long* sample_offsets, int n_samples, int nb_steps, int nb_units,
                       double max_time, float* out, uint32_t* n_dropped, void* stream);
 
+/* f-3  A batch from a device-resident event store (the whole of SHD / SSC uploaded once) and a device
+ *      list of sample indices: gather and bin in one launch, no memset, no global atomic.
+ *      Store: times (n_events; times_dtype 0 = fp32, 1 = fp16), units (n_events, uint16; 0xFFFF marks a
+ *      unit that was negative or did not fit and is dropped like any unit >= nb_units), offsets
+ *      (n_store + 1, int64, non-decreasing from 0 to n_events: checked by the owner, not here), labels
+ *      (n_store, int64; may be NULL when y is).  idx (batch, device int64): sample of each batch row; an
+ *      index outside [0, n_store) gives an empty sample and label -1.  nb_units <= 65535.
+ *      Outputs, each may be NULL, at least one is not:
+ *        plane  (batch * nb_steps, ldp) bf16 bit patterns, ldp = nb_units rounded up to 8, exact zeros
+ *               behind column nb_units: the layout and values of sparch_expand_counts_u8 (16-byte
+ *               aligned; exact while every count is <= 256, the owner of the store sees to that);
+ *        dense  (batch, nb_steps, nb_units) fp32, the tensor sparch_bin_events writes;
+ *        counts (batch, nb_steps, nb_units) uint8, saturating at 255.
+ *      y (batch, int64) = labels[idx], *n_dropped (device uint32) as sparch_bin_events counts it;
+ *      either may be NULL.  n_dropped needs a workspace of sparch_events_gather_bin_workspace_bytes
+ *      (one word per workgroup, summed by a second small launch; no workspace without it).
+ *      Every event gets the bin sparch_bin_events gives it (one shared device function).  sorted != 0
+ *      promises that the times of every sample are non-decreasing (a workgroup then finds the events
+ *      of its time slab by search instead of scanning the sample); a wrong promise loses events but
+ *      reads nothing out of bounds.  Launch only: no allocation, no synchronisation.              */
+size_t sparch_events_gather_bin_workspace_bytes(int batch, int nb_steps, int nb_units);
+int sparch_events_gather_bin(const void* times, int times_dtype, const uint16_t* units,
+                             const long long* offsets, const long long* labels, long long n_store,
+                             const long long* idx, int batch, int nb_steps, int nb_units, double max_time,
+                             int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
+                             uint32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- f-4: non-spiking baselines (anns.py) --------------------------------------------------
  * Element-wise tail of MLPLayer.forward (anns.py:218-227): y = dropout(act(z * scale + shift)) over n
  * elements of an (n/H, H) tensor; scale/shift (H) = the folded BatchNorm affine, NULL for none.

@@ -13,14 +13,23 @@ arithmetic (bit-exact against np.digitize + accumulate, tests/test_hip_parity.py
 
 h5py is imported when a dataset is opened (it is not installed in the offline build image: the class then
 raises ImportError naming the package — there is no other source for the files' contents).
+
+SPARCH_EVENTS=resident (or `load_shd_or_ssc(..., resident="resident")`) keeps the whole split on the device
+instead (`functional.EventStore`): the events are uploaded once, and every batch is built there from the list
+of its sample indices by one kernel (`sparch_events_gather_bin`) — no per-sample reads, no per-batch upload
+but the indices of an epoch.  The index lists come from a torch DataLoader built with the arguments of the
+per-sample loader, so the batches and the draws from torch's global generator are the same.  The events come
+from the `h5_file` hook, else from the pack file `{data_folder}/{dataset}_{split}.events.npz`
+(tools/pack_events.py; readable without h5py), else from the .h5 file.
 """
 import logging
+import os
 
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..functional import bin_events
+from ..functional import EventStore, bin_events
 
 logger = logging.getLogger(__name__)
 
@@ -77,12 +86,90 @@ class SpikingDataset(Dataset):
         return xs, xlens, torch.LongTensor(ys)
 
 
+class _SampleIndices(Dataset):
+    """Sample i is the number i: the DataLoader over it yields the index lists of an epoch's batches."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, index):
+        return index
+
+
+def _index_loader(dataset, batch_size, shuffle, rank, world, seed, collate_fn=None):
+    """The DataLoader of `load_shd_or_ssc`, for both of its loaders: same sampler, same arguments."""
+    if world > 1:
+        from torch.utils.data.distributed import DistributedSampler
+
+        sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed)
+        return DataLoader(dataset, batch_size=batch_size, collate_fn=collate_fn, sampler=sampler,
+                          num_workers=0, pin_memory=False)
+    return DataLoader(dataset, batch_size=batch_size, collate_fn=collate_fn, shuffle=shuffle,
+                      num_workers=0, pin_memory=False)
+
+
+class ResidentEventLoader:
+    """Batches `(x, xlens, y)` of an `EventStore`: x and y on the device, xlens as the per-sample loader gives
+    them.  Iterating draws the epoch's index lists from a DataLoader over the sample numbers (so `len`, the
+    short last batch, `.sampler` / `set_epoch` and the global generator behave as with the per-sample loader),
+    uploads them in one copy and launches one kernel per batch.  `values=True` asks for dense fp32 batches (a
+    non-spiking network reads the values; a spiking one reads the bf16 plane the store serves when it can)."""
+
+    def __init__(self, store, batch_size, nb_steps=100, shuffle=True, rank=0, world=1, seed=0, values=False):
+        self.store, self.batch_size, self.nb_steps, self.values = store, batch_size, nb_steps, values
+        self.index_loader = _index_loader(_SampleIndices(len(store)), batch_size, shuffle, rank, world, seed)
+        self.sampler = self.index_loader.sampler
+        store.prepare(nb_steps)  # the one read-back the plane / fp32 decision needs: now, not in the first epoch
+
+    def __len__(self):
+        return len(self.index_loader)
+
+    def index_lists(self):
+        """The sample indices of every batch of one epoch (host tensors), in order."""
+        return [b.to(torch.int64) for b in self.index_loader]
+
+    def __iter__(self):
+        lists = self.index_lists()
+        if not lists:
+            return
+        flat = torch.cat(lists).to(self.store.device)
+        at = 0
+        for b in lists:
+            n = b.numel()
+            x, y = self.store.batch(flat[at:at + n], self.nb_steps, values=self.values)
+            at += n
+            yield x, torch.tensor([self.nb_steps] * n), y
+
+
+def _event_pack_path(data_folder, dataset_name, split):
+    return f"{data_folder}/{dataset_name}_{split}.events.npz"
+
+
+def _resident_store(dataset_name, data_folder, split, h5_file, device):
+    if h5_file is not None:
+        return EventStore.from_mapping(h5_file, device=device)
+    pack = _event_pack_path(data_folder, dataset_name, split)
+    if os.path.exists(pack):
+        return EventStore.from_pack(pack, device=device)
+    with _open_h5(f"{data_folder}/{dataset_name}_{split}.h5") as f:
+        return EventStore.from_mapping(f, device=device)
+
+
 def load_shd_or_ssc(dataset_name, data_folder, split, batch_size, nb_steps=100, shuffle=True, workers=0,
-                    h5_file=None, device="cuda", rank=0, world=1, seed=0):
+                    h5_file=None, device="cuda", rank=0, world=1, seed=0, resident=None, values=False):
     """spiking_datasets.py:90-140.  rank / world (data-parallel runs; not in the reference, which is single
     device): every rank reads the same file and draws a disjoint 1/world share of each epoch's (shuffled)
     sample order through a DistributedSampler — call `loader.sampler.set_epoch(e)` per epoch; `batch_size`
-    is the PER-RANK batch."""
+    is the PER-RANK batch.  resident: None reads SPARCH_EVENTS; unset or empty = the per-sample loader,
+    "resident" = a `ResidentEventLoader` (`values`: see there); anything else is a ValueError."""
+    if resident is None:
+        resident = os.environ.get("SPARCH_EVENTS", "")
+    if resident not in ("", "resident"):
+        raise ValueError(f"SPARCH_EVENTS / resident: unknown value '{resident}' (unset or empty: per-sample "
+                         "loader; 'resident': the split's events stay on the device)")
     if dataset_name not in ["shd", "ssc"]:
         raise ValueError(f"Invalid dataset name {dataset_name}")
     if split not in ["train", "valid", "test"]:
@@ -93,13 +180,18 @@ def load_shd_or_ssc(dataset_name, data_folder, split, batch_size, nb_steps=100, 
     if workers != 0:
         raise ValueError("sparch_amd.dataloaders: the collate function bins on the GPU; use workers=0 "
                          "(the reference's default)")
+    if resident == "resident":
+        store = _resident_store(dataset_name, data_folder, split, h5_file, device)
+        logging.info(f"Number of examples in {split} set: {len(store)}")
+        loader = ResidentEventLoader(store, batch_size, nb_steps, shuffle, rank, world, seed, values=values)
+        logging.info(f"Events of the {split} set are resident on {store.device}: {store.n_events} events, "
+                     f"{store.nbytes / 2**20:.1f} MiB, times {'sorted' if store.sorted else 'unsorted'}, largest "
+                     f"bin count {store.prepare(nb_steps)} ("
+                     f"{'bf16 plane' if store.serves_plane(nb_steps) and not values else 'dense fp32'} batches)")
+        if store.dropped(nb_steps):
+            logging.warning(f"{store.dropped(nb_steps)} events of the {split} set are outside the {nb_steps} x "
+                            f"{store.nb_units} grid and dropped (the reference's sparse constructor rejects them)")
+        return loader
     dataset = SpikingDataset(dataset_name, data_folder, split, nb_steps, h5_file=h5_file, device=device)
     logging.info(f"Number of examples in {split} set: {len(dataset)}")
-    if world > 1:
-        from torch.utils.data.distributed import DistributedSampler
-
-        sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed)
-        return DataLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch, sampler=sampler,
-                          num_workers=0, pin_memory=False)
-    return DataLoader(dataset, batch_size=batch_size, collate_fn=dataset.generateBatch, shuffle=shuffle,
-                      num_workers=0, pin_memory=False)
+    return _index_loader(dataset, batch_size, shuffle, rank, world, seed, collate_fn=dataset.generateBatch)

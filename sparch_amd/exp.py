@@ -9,7 +9,8 @@ The training step itself (exp.py:352-382) runs on the MI355X path: `sparch_amd.S
 What this build adds, not replaces:
   * --synthetic 1: batches of the dataset's shape generated on the fly (no dataset files needed);
     without it SHD/SSC go through sparch_amd.dataloaders.spiking_datasets (h5py event lists binned on the
-    device) and HD/SC through sparch_amd.dataloaders.nonspiking_datasets (audio files decoded on the host);
+    device; with SPARCH_EVENTS=resident the whole split stays on the device and each batch is one kernel)
+    and HD/SC through sparch_amd.dataloaders.nonspiking_datasets (audio files decoded on the host);
   * hd / sc inputs are raw waveforms turned into 40-bin log-mel features ON THE DEVICE (the reference calls
     torchaudio's kaldi.fbank per clip on the CPU, nonspiking_datasets.py:96, 194): by the file loaders' collate
     function (`sparch_amd.fbank_padded`: clips of different lengths, zero-padded features as pad_sequence pads
@@ -236,7 +237,8 @@ class Experiment:
 
                 def ld(split, shuffle):
                     return load_shd_or_ssc(self.dataset_name, self.data_folder, split, per_rank, nb_steps=100,
-                                           shuffle=shuffle, device=self.device, rank=self.rank, world=self.world)
+                                           shuffle=shuffle, device=self.device, rank=self.rank, world=self.world,
+                                           values=self.model_type in ("MLP", "RNN", "LiGRU", "GRU"))
             else:
                 from .dataloaders.nonspiking_datasets import load_hd_or_sc  # exp.py:254-288
 
@@ -283,13 +285,22 @@ class Experiment:
         if self.world > 1:  # identical initial replicas
             for p in self.net.parameters():
                 torch.distributed.broadcast(p.data, src=0)
+        # a resident event loader (SPARCH_EVENTS=resident) serves the bf16 plane a spiking layer 1 reads; a
+        # non-spiking network reads the values themselves: dense fp32 batches there (asked for when the loaders were
+        # made, from --model_type; a pretrained model says itself what it is)
+        for name in ("train_loader", "valid_loader", "test_loader"):
+            loader = getattr(self, name, None)
+            if hasattr(loader, "store") and hasattr(loader, "values"):
+                loader.values = not self.net.is_snn
         self.nb_params = sum(p.numel() for p in self.net.parameters() if p.requires_grad)
         logging.info(f"Total number of trainable parameters is {self.nb_params}")
 
     # ---------------------------------------------------------------------------------- epochs
     def _to_device(self, x, y):
-        x = x.to(self.device, non_blocking=True)
-        y = y.to(self.device, non_blocking=True)
+        if x.device != self.device:  # (a batch made on the device is passed on as it is, plane tag included)
+            x = x.to(self.device, non_blocking=True)
+        if y.device != self.device:
+            y = y.to(self.device, non_blocking=True)
         if x.dtype == torch.uint8:  # spike counts as bytes: expanded on the device
             x = Fn.input_from_counts(x) if self.net.is_snn else x.float()
         if self.input_kind == "audio" and x.ndim == 2:  # synthetic waves; the file loaders deliver features
@@ -307,6 +318,8 @@ class Experiment:
 
         def put(batch):
             x, xlens, y = batch
+            if x.device == self.device and y.device == self.device:
+                return x, xlens, y, None  # made on the device by kernels of the compute stream: nothing to upload
             with torch.cuda.stream(side):
                 xd = x.to(self.device, non_blocking=True)
                 yd = y.to(self.device, non_blocking=True)
@@ -325,10 +338,11 @@ class Experiment:
                 nxt = put(next(it))
             except StopIteration:
                 nxt = None
-            main.wait_event(ev)
-            for t in (xd, yd):
-                if t.is_cuda:
-                    t.record_stream(main)
+            if ev is not None:
+                main.wait_event(ev)
+                for t in (xd, yd):
+                    if t.is_cuda:
+                        t.record_stream(main)
             yield xd, xlens, yd
 
     def _mean_over_ranks(self, value):

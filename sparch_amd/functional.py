@@ -1331,6 +1331,224 @@ def bin_events(times, units, nb_steps=100, nb_units=700, max_time=1.4, device="c
     return out, dropped[:1]
 
 
+# ----------------------------------------------------------------------------- resident SHD / SSC events
+EVENT_PACK_KEYS = ("times", "units", "offsets", "labels")
+_UNIT_DROPPED = 0xFFFF  # stored for a unit that is negative or does not fit 16 bits: still counted as dropped
+
+
+def event_arrays_from_mapping(h5):
+    """The contents of an SHD / SSC file — any mapping with ["spikes"]["times"], ["spikes"]["units"] (one
+    variable-length row per sample) and ["labels"], an open h5py file included — as the four flat arrays of an
+    event store: times (float16 or float32 as the source had them; anything else, float64 included, rounded to
+    float32 as SpikingDataset.__getitem__ does), units (uint16, 0xFFFF for a unit that is negative or does not
+    fit), offsets (int64, n + 1), labels (int64, n)."""
+    import numpy as np
+
+    labels = np.array(h5["labels"], dtype=np.int64).ravel()
+    rows_t, rows_u = h5["spikes"]["times"], h5["spikes"]["units"]
+    n = len(labels)
+    ts = [np.asarray(rows_t[i]).ravel() for i in range(n)]
+    us = [np.asarray(rows_u[i]).ravel() for i in range(n)]
+    lens = np.array([len(t) for t in ts], dtype=np.int64)
+    if any(len(u) != m for u, m in zip(us, lens)):
+        raise ValueError("event store: a sample has different numbers of times and units")
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    keep16 = n > 0 and all(t.dtype == np.float16 for t in ts)
+    tdt = np.float16 if keep16 else np.float32
+    times = np.concatenate([t.astype(tdt, copy=False) for t in ts]) if n and offsets[-1] else np.zeros(0, tdt)
+    u = np.concatenate([x.astype(np.int64, copy=False) for x in us]) if n and offsets[-1] else np.zeros(0, np.int64)
+    units = np.where((u < 0) | (u >= _UNIT_DROPPED), _UNIT_DROPPED, u).astype(np.uint16)
+    return {"times": times, "units": units, "offsets": offsets, "labels": labels}
+
+
+def check_event_arrays(a, what="event store"):
+    """ValueError unless the four arrays agree (host-side; the kernel trusts the offsets)."""
+    import numpy as np
+
+    for k in EVENT_PACK_KEYS:
+        if k not in a:
+            raise ValueError(f"{what}: array '{k}' is missing")
+    t, u, o, y = (np.asarray(a[k]) for k in EVENT_PACK_KEYS)
+    if t.dtype not in (np.float16, np.float32) or u.dtype != np.uint16 or o.dtype != np.int64 or y.dtype != np.int64:
+        raise ValueError(f"{what}: dtypes must be float16/float32, uint16, int64, int64; got "
+                         f"{t.dtype}, {u.dtype}, {o.dtype}, {y.dtype}")
+    if t.ndim != 1 or u.ndim != 1 or o.ndim != 1 or y.ndim != 1:
+        raise ValueError(f"{what}: the arrays must be one-dimensional")
+    if len(y) == 0:
+        raise ValueError(f"{what}: no samples")
+    if len(o) != len(y) + 1:
+        raise ValueError(f"{what}: {len(y)} labels need {len(y) + 1} offsets, found {len(o)}")
+    if o[0] != 0 or np.any(np.diff(o) < 0):
+        raise ValueError(f"{what}: offsets must start at 0 and never decrease")
+    if len(t) != len(u) or int(o[-1]) != len(t):
+        raise ValueError(f"{what}: the last offset ({int(o[-1])}) is not the number of events "
+                         f"({len(t)} times, {len(u)} units)")
+    return {"times": t, "units": u, "offsets": o, "labels": y}
+
+
+def save_event_pack(path, arrays):
+    """Write the pack file of a split: an uncompressed np.savez of times, units, offsets, labels."""
+    import numpy as np
+
+    a = check_event_arrays(arrays, what=str(path))
+    with open(path, "wb") as f:  # a file object: np.savez would append ".npz" to a name
+        np.savez(f, **a)
+
+
+def load_event_pack(path):
+    import numpy as np
+
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in EVENT_PACK_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not an event pack (no {', '.join(missing)})")
+        return check_event_arrays({k: z[k] for k in EVENT_PACK_KEYS}, what=str(path))
+
+
+def _samples_sorted(times, offsets):
+    """True iff the times of every sample are non-decreasing (NaN counts as unsorted)."""
+    import numpy as np
+
+    if len(times) < 2:
+        return True
+    ok = times[1:] >= times[:-1]
+    starts = offsets[1:-1]                       # pairs (s - 1, s) that straddle two samples do not count
+    starts = starts[(starts > 0) & (starts < len(times))]
+    ok[starts - 1] = True
+    return bool(ok.all())
+
+
+def _require_room(need, free, what):
+    if need > free:
+        raise RuntimeError(f"{what}: the event store needs {need / 2**20:.1f} MiB on the device, only "
+                           f"{free / 2**20:.1f} MiB are free; train without SPARCH_EVENTS=resident")
+
+
+class EventStore:
+    """All events of one SHD / SSC split on the device, uploaded once; `batch(idx)` then builds a batch from a device
+    list of sample indices in one launch (`sparch_events_gather_bin`).
+
+    Built from the four flat arrays (`event_arrays_from_mapping`, `load_event_pack`), or through `from_mapping` /
+    `from_pack`.  `prepare(nb_steps)` bins the whole store once on the device and keeps the largest count of any
+    (sample, bin, unit): up to 255 the store serves the bf16 plane layer 1 reads, wrapped as `input_from_counts`
+    wraps it; above, dense fp32 as the per-sample loader does.  The decision is taken once, on the host."""
+
+    def __init__(self, arrays, device="cuda", nb_units=700, max_time=1.4):
+        import numpy as np
+
+        a = check_event_arrays(arrays)
+        if not 0 < nb_units <= 65535:
+            raise ValueError(f"EventStore: nb_units {nb_units} outside 1..65535 (units are stored in 16 bits)")
+        self.device = torch.device(device)
+        _require_device(torch.empty(0, device=self.device), "EventStore")
+        self.nb_units, self.max_time = int(nb_units), float(max_time)
+        self.n_samples, self.n_events = len(a["labels"]), len(a["times"])
+        self.sorted = _samples_sorted(a["times"], a["offsets"])
+        self.nbytes = sum(int(v.nbytes) for v in a.values())
+        _require_room(self.nbytes, torch.cuda.mem_get_info(self.device)[0], "EventStore")
+        # an empty store array still needs an address for the kernel's argument check
+        pad = {k: (v if len(v) else np.zeros(1, v.dtype)) for k, v in a.items()}
+        self.times = torch.from_numpy(pad["times"]).to(self.device)
+        self.units = torch.from_numpy(pad["units"].view("int16")).to(self.device)  # bits; torch has no uint16 maths
+        self.offsets = torch.from_numpy(pad["offsets"]).to(self.device)
+        self.labels = torch.from_numpy(pad["labels"]).to(self.device)
+        self.times_dtype = 1 if a["times"].dtype.itemsize == 2 else 0
+        self._max_count = {}    # nb_steps -> largest bin count of the store
+        self._dropped = {}      # nb_steps -> events dropped over the whole store
+
+    @classmethod
+    def from_mapping(cls, h5, **kw):
+        return cls(event_arrays_from_mapping(h5), **kw)
+
+    @classmethod
+    def from_pack(cls, path, **kw):
+        return cls(load_event_pack(path), **kw)
+
+    def __len__(self):
+        return self.n_samples
+
+    def _launch(self, idx, nb_steps, plane=None, dense=None, counts=None, y=None, n_dropped=None):
+        B = idx.numel()
+        ws, ws_bytes = None, 0
+        if n_dropped is not None:
+            ws_bytes = lib.sparch_events_gather_bin_workspace_bytes(B, nb_steps, self.nb_units)
+            ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=self.device)
+        tok = timer.start(f"events_gather_bin[{B}x{nb_steps}x{self.nb_units}]")
+        check(lib.sparch_events_gather_bin(ptr(self.times), self.times_dtype, ptr(self.units), ptr(self.offsets),
+                                           ptr(self.labels), self.n_samples, ptr(idx), B, nb_steps, self.nb_units,
+                                           self.max_time, int(self.sorted), ptr(plane), ptr(dense), ptr(counts),
+                                           ptr(y), ptr(n_dropped), ptr(ws), ws_bytes, _stream()),
+              "sparch_events_gather_bin")
+        timer.stop(tok)
+
+    def gather(self, idx, nb_steps, plane=False, dense=False, counts=False, dropped=False):
+        """Raw outputs of the kernel for the device int64 index list `idx`: a dict with 'y' and whichever of
+        'plane' ((B * nb_steps, ldp) bf16), 'dense' ((B, nb_steps, K) fp32), 'counts' ((B, nb_steps, K) uint8,
+        saturating) and 'n_dropped' (device int32, 1 element) were asked for."""
+        _require_device(idx, "idx")
+        if idx.dtype != torch.int64 or idx.ndim != 1 or idx.numel() == 0 or not idx.is_contiguous():
+            raise ValueError("EventStore.gather: idx must be a non-empty contiguous 1-D int64 tensor")
+        if not (plane or dense or counts):
+            raise ValueError("EventStore.gather: ask for at least one of plane, dense, counts")
+        B, K, dev = idx.numel(), self.nb_units, self.device
+        out = {"y": torch.empty(B, dtype=torch.int64, device=dev)}
+        if plane:
+            out["plane"] = torch.empty(B * nb_steps, (K + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)
+        if dense:
+            out["dense"] = torch.empty(B, nb_steps, K, dtype=torch.float32, device=dev)
+        if counts:
+            out["counts"] = torch.empty(B, nb_steps, K, dtype=torch.uint8, device=dev)
+        if dropped:
+            out["n_dropped"] = torch.empty(4, dtype=torch.int32, device=dev)
+        self._launch(idx, nb_steps, out.get("plane"), out.get("dense"), out.get("counts"), out["y"],
+                     out.get("n_dropped"))
+        if dropped:
+            out["n_dropped"] = out["n_dropped"][:1]
+        return out
+
+    def prepare(self, nb_steps, chunk=256):
+        """Largest bin count over the whole store at nb_steps (found on the device, one read-back), cached."""
+        if nb_steps not in self._max_count:
+            top = torch.zeros((), dtype=torch.float32, device=self.device)
+            lost = torch.zeros(1, dtype=torch.int64, device=self.device)
+            for a in range(0, self.n_samples, chunk):
+                idx = torch.arange(a, min(a + chunk, self.n_samples), dtype=torch.int64, device=self.device)
+                got = self.gather(idx, nb_steps, dense=True, dropped=True)
+                top = torch.maximum(top, got["dense"].max())
+                lost += got["n_dropped"]
+            self._max_count[nb_steps] = int(top.item())
+            self._dropped[nb_steps] = int(lost.item())
+        return self._max_count[nb_steps]
+
+    def dropped(self, nb_steps):
+        """Events of the whole store that the binning rejects (t < 0, t >= max_time, unit out of range)."""
+        self.prepare(nb_steps)
+        return self._dropped[nb_steps]
+
+    def serves_plane(self, nb_steps):
+        # the conditions under which layer 1 would read the plane of an fp32 batch (SpikingLayerFn.forward)
+        return (USE_SPIKE_GEMM and USE_SPIKE16 and USE_INPUT_PLANE and DENSE_GEMM == "split6"
+                and self.prepare(nb_steps) <= 255)
+
+    def batch(self, idx, nb_steps, values=False):
+        """(x, y) on the device for the index list: x is the layer-1 input — the tagged placeholder of
+        `input_from_counts` when the store serves the plane, dense fp32 (B, nb_steps, K) otherwise or when
+        `values` asks for a tensor whose elements can be read (non-spiking networks)."""
+        if not values and self.serves_plane(nb_steps):
+            got = self.gather(idx, nb_steps, plane=True)
+            B = idx.numel()
+            key = str(self.device)
+            one = _flag_one.get(key)
+            if one is None:
+                one = _flag_one[key] = torch.ones(4, dtype=torch.int32, device=self.device)
+            x = spike_placeholder(B, nb_steps, self.nb_units, self.device).view(B, nb_steps, self.nb_units)
+            x._sparch_input_plane = (tuple(x.shape), got["plane"], one)
+            return x, got["y"]
+        got = self.gather(idx, nb_steps, dense=True)
+        return got["dense"], got["y"]
+
+
 # ----------------------------------------------------------------------------- f-4: non-spiking baselines
 ACT_KIND = {"sigmoid": 0, "relu": 1, "tanh": 2}
 
