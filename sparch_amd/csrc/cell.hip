@@ -20,10 +20,6 @@
 
 namespace {
 
-// time steps of loads in flight per thread: the small-problem (VEC = 1) variant runs at ~4 waves per CU and
-// needs a deep prefetch to cover HBM latency; the vector variant has 4x the bytes per load
-template <int VEC> struct Depth { static constexpr int U = VEC == 1 ? 16 : 8; };
-
 struct CellArgs {
     int B, dirs, T, H;
     const float* Wx; const float* scale; const float* shift;
@@ -62,20 +58,13 @@ __device__ __forceinline__ void ld_saved(float (&d)[VEC], const float* base, siz
         d[0] = bf16_to_f32(q[0]);
     }
 }
-#ifndef CELL_NT
-#define CELL_NT 1  // saved states (written by the forward, read once by the backward much later) as non-temporal accesses:
-                   // they do not take the infinity cache's room from what the NEXT kernel reads (cfg2 step 0.956 -> 0.937 ms, one call)
-#endif
+// Saved states (written by the forward, read once by the backward much later) are non-temporal accesses: they do not
+// take the infinity cache's room from what the NEXT kernel reads (cfg2 step 0.956 -> 0.937 ms, one call).
 template <int VEC, bool IS_U>
 __device__ __forceinline__ void st_saved(float* base, size_t i, const float (&d)[VEC], bool s16, float theta) {
     if (!s16) {
-#if CELL_NT
         if constexpr (VEC == 4) __builtin_nontemporal_store(f32x4{d[0], d[1], d[2], d[3]}, reinterpret_cast<f32x4*>(base + i));
         else __builtin_nontemporal_store(d[0], base + i);
-#else
-        if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(base + i) = f32x4{d[0], d[1], d[2], d[3]};
-        else base[i] = d[0];
-#endif
         return;
     }
     unsigned short* q = reinterpret_cast<unsigned short*>(base) + i;
@@ -99,245 +88,15 @@ __device__ __forceinline__ void stv(float* p, const float (&d)[VEC]) {
     }
 }
 
-template <bool ADAPT, int VEC, bool S16>
-__global__ __launch_bounds__(256) void cell_fwd_kernel(CellArgs c) {
-    constexpr int U = Depth<VEC>::U;
-    const int HQ = c.H / VEC;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Bp = c.B * c.dirs;
-    if (idx >= (long long)Bp * HQ) return;
-    const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
-    const int d = bp / c.B, b = bp - d * c.B;
-    const int T = c.T, H = c.H, HO = c.H * c.dirs;
-
-    float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], sc[VEC], sh[VEC];
-    float u[VEC], w[VEC], s[VEC];
-    uint32_t cnt[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        al[e] = clampf(c.alpha[h + e], SP_ALPHA_LO, SP_ALPHA_HI);
-        oma[e] = 1.0f - al[e];
-        if (ADAPT) {
-            be[e] = clampf(c.beta[h + e], SP_BETA_LO, SP_BETA_HI);
-            pa[e] = clampf(c.a[h + e], SP_A_LO, SP_A_HI);
-            pb[e] = clampf(c.b[h + e], SP_B_LO, SP_B_HI);
-        }
-        sc[e] = c.scale ? c.scale[h + e] : 1.0f;
-        sh[e] = c.scale ? c.shift[h + e] : 0.0f;
-        cnt[e] = 0;
-    }
-    ldv<VEC>(u, c.u0 + (size_t)bp * H + h);
-    ldv<VEC>(s, c.s0 + (size_t)bp * H + h);
-    if (ADAPT) ldv<VEC>(w, c.w0 + (size_t)bp * H + h);
-    const bool has_norm = c.scale != nullptr;
-    const bool drop = c.p_drop > 0.0f;
-    const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
-
-    for (int t0 = 0; t0 < T; t0 += U) {
-        float x[U][VEC];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int t = t0 + j;
-            if (t < T) {
-                const int tt = d ? (T - 1 - t) : t;
-                ldv<VEC>(x[j], c.Wx + ((size_t)b * T + tt) * H + h);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int t = t0 + j;
-            if (t >= T) break;
-            const int tt = d ? (T - 1 - t) : t;
-            float so[VEC];
-            const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                float xn = x[j][e];
-                if (has_norm) xn = bn_affine(xn, sc[e], sh[e]);
-                float drive = xn;
-                if (ADAPT) {
-                    w[e] = (be[e] * w[e] + pa[e] * u[e]) + pb[e] * s[e];  // snns.py:438
-                    drive = xn - w[e];
-                }
-                u[e] = al[e] * (u[e] - s[e]) + oma[e] * drive;           // snns.py:297 / 439
-                s[e] = (u[e] - c.theta) > 0.0f ? 1.0f : 0.0f;            // snns.py:29
-                const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
-                so[e] = s[e] * k;
-                cnt[e] += (so[e] != 0.0f) ? 1u : 0u;
-            }
-            if (c.s_out) stv<VEC>(c.s_out + o, so);  // the fp32 copy: only for callers that read the layer's output tensor
-            if (c.s16_out) {  // the same spikes as a bf16 plane (0 / 1.0) for the GEMMs that consume them
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) c.s16_out[o + e] = so[e] != 0.0f ? (uint16_t)0x3F80 : (uint16_t)0;
-            }
-            if (c.u_save) st_saved<VEC, true>(c.u_save, ((size_t)bp * T + t) * H + h, u, S16, c.theta);
-            if (ADAPT && c.w_save) st_saved<VEC, false>(c.w_save, ((size_t)bp * T + t) * H + h, w, S16, c.theta);
-        }
-    }
-    if (c.spike_count) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e)
-            if (cnt[e]) atomicAdd(c.spike_count + (size_t)d * H + h + e, cnt[e]);
-    }
-}
-
-template <bool ADAPT, int VEC, bool S16>
-__global__ __launch_bounds__(256) void cell_bwd_kernel(CellArgs c) {
-    constexpr int U = Depth<VEC>::U;
-    const int HQ = c.H / VEC;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Bp = c.B * c.dirs;
-    if (idx >= (long long)Bp * HQ) return;
-    const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
-    const int d = bp / c.B, b = bp - d * c.B;
-    const int T = c.T, H = c.H, HO = c.H * c.dirs;
-
-    float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], gr[VEC];
-    float du_n[VEC], dw_n[VEC], u_t[VEC];
-    float acc_al[VEC], acc_be[VEC], acc_a[VEC], acc_b[VEC];
-    const bool bn = c.bn_x != nullptr;
-    float bn_mu[VEC], bn_is[VEC], acc_dy[VEC], acc_dyx[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        bn_mu[e] = bn ? c.bn_mean[h + e] : 0.f;
-        bn_is[e] = bn ? c.bn_invstd[h + e] : 0.f;
-        acc_dy[e] = acc_dyx[e] = 0.f;
-        al[e] = clampf(c.alpha[h + e], SP_ALPHA_LO, SP_ALPHA_HI);
-        oma[e] = 1.0f - al[e];
-        if (ADAPT) {
-            be[e] = clampf(c.beta[h + e], SP_BETA_LO, SP_BETA_HI);
-            pa[e] = clampf(c.a[h + e], SP_A_LO, SP_A_HI);
-            pb[e] = clampf(c.b[h + e], SP_B_LO, SP_B_HI);
-        }
-        gr[e] = c.g_rate ? c.g_rate[(size_t)d * H + h + e] * c.g_rate_scale : 0.0f;
-        du_n[e] = dw_n[e] = 0.f;
-        acc_al[e] = acc_be[e] = acc_a[e] = acc_b[e] = 0.f;
-    }
-    constexpr bool s16 = S16;  // compile-time: a run-time flag here breaks up the batched prefetch loads
-    ld_saved<VEC>(u_t, c.u_save, ((size_t)bp * T + (T - 1)) * H + h, s16);
-    const bool drop = c.p_drop > 0.0f;
-    const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
-
-    for (int t0 = T - 1; t0 >= 0; t0 -= U) {
-        float g[U][VEC], up[U][VEC], wp[U][VEC], xr[U][VEC];
-        // bf16 saves: the raw words are fetched here and unpacked at their use, so that the U steps' loads stay
-        // one batch (unpacking next to each load made hipcc wait for every load in turn: 2x the kernel time)
-        [[maybe_unused]] unsigned long long upr[U], wpr[U];
-        if constexpr (S16 && VEC == 4) {
-            // branch-free batch (steps below 0 re-read step 0: in range, never used): with the per-step `if (t >= 0)`
-            // the 64-bit raw words crossed basic blocks and hipcc waited for every load in turn
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int t = max(t0 - j, 0);
-                const int tt = d ? (T - 1 - t) : t;
-                ldv<VEC>(g[j], c.g_out + ((size_t)b * T + tt) * HO + (size_t)d * H + h);
-                if (bn) ldv<VEC>(xr[j], c.bn_x + ((size_t)b * T + tt) * H + h);
-                const size_t i = ((size_t)bp * T + (t > 0 ? t - 1 : 0)) * H + h;  // t = 0 reads u0 / w0 below
-                upr[j] = *reinterpret_cast<const unsigned long long*>(reinterpret_cast<const unsigned short*>(c.u_save) + i);
-                if (ADAPT) wpr[j] = *reinterpret_cast<const unsigned long long*>(reinterpret_cast<const unsigned short*>(c.w_save) + i);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int t = t0 - j;
-                if (t >= 0) {
-                    const int tt = d ? (T - 1 - t) : t;
-                    ldv<VEC>(g[j], c.g_out + ((size_t)b * T + tt) * HO + (size_t)d * H + h);
-                    if (bn) ldv<VEC>(xr[j], c.bn_x + ((size_t)b * T + tt) * H + h);
-                    if (t > 0) {
-                        const size_t i = ((size_t)bp * T + (t - 1)) * H + h;
-                        ld_saved<VEC>(up[j], c.u_save, i, s16);
-                        if (ADAPT) ld_saved<VEC>(wp[j], c.w_save, i, s16);
-                    } else {
-                        ldv<VEC>(up[j], c.u0 + (size_t)bp * H + h);
-                        if (ADAPT) ldv<VEC>(wp[j], c.w0 + (size_t)bp * H + h);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int t = t0 - j;
-            if (t < 0) break;
-            const int tt = d ? (T - 1 - t) : t;
-            const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
-            float sp[VEC], dwx[VEC];
-            if constexpr (S16 && VEC == 4) {
-                if (t > 0) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        up[j][e] = bf16_to_f32((unsigned short)(upr[j] >> (16 * e)));
-                        if (ADAPT) wp[j][e] = bf16_to_f32((unsigned short)(wpr[j] >> (16 * e)));
-                    }
-                } else {  // last step of the reverse pass: the exact fp32 initial states
-                    ldv<VEC>(up[j], c.u0 + (size_t)bp * H + h);
-                    if (ADAPT) ldv<VEC>(wp[j], c.w0 + (size_t)bp * H + h);
-                }
-            }
-            if (t > 0) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) sp[e] = (up[j][e] - c.theta) > 0.0f ? 1.0f : 0.0f;
-            } else {
-                ldv<VEC>(sp, c.s0 + (size_t)bp * H + h);
-            }
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
-                const float gs = (g[j][e] + gr[e]) * k;
-                float ds = gs - al[e] * du_n[e];
-                if (ADAPT) ds = ds + pb[e] * dw_n[e];
-                const float xs = u_t[e] - c.theta;
-                float du = boxcar_gate(ds, xs) + al[e] * du_n[e];            // snns.py:33-35
-                if (ADAPT) du = du + pa[e] * dw_n[e];
-                dwx[e] = oma[e] * du;
-                if (bn) {  // BatchNorm backward's column sums (dy = dWx, xhat = (x - mean) * invstd)
-                    acc_dy[e] += dwx[e];
-                    acc_dyx[e] += dwx[e] * ((xr[j][e] - bn_mu[e]) * bn_is[e]);
-                }
-                const float q = up[j][e] - sp[e];
-                acc_al[e] += du * (q - u_t[e]);  // d u_t / d alpha = (q - u_t)/(1-alpha); scaled at the end
-                if (ADAPT) {
-                    const float dw = be[e] * dw_n[e] - dwx[e];
-                    acc_be[e] += dw * wp[j][e];
-                    acc_a[e] += dw * up[j][e];
-                    acc_b[e] += dw * sp[e];
-                    dw_n[e] = dw;
-                }
-                du_n[e] = du;
-                u_t[e] = up[j][e];
-            }
-            stv<VEC>(c.dWx + ((size_t)bp * T + tt) * H + h, dwx);
-        }
-    }
-    const size_t plane = (size_t)Bp * H;
-    float* ws = c.dparam_ws + (size_t)bp * H + h;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc_al[e] = acc_al[e] / oma[e];
-    stv<VEC>(ws, acc_al);
-    if (ADAPT) {
-        stv<VEC>(ws + plane, acc_be);
-        stv<VEC>(ws + 2 * plane, acc_a);
-        stv<VEC>(ws + 3 * plane, acc_b);
-    }
-    if (bn) {
-        stv<VEC>(ws + 4 * plane, acc_dy);
-        stv<VEC>(ws + 5 * plane, acc_dyx);
-    }
-}
-
-// ------------------------------------------------------------------ pipelined variants (round 3)
-// The kernels above fetch U steps, wait for ALL of them (`s_waitcnt vmcnt(0)`), compute U steps, and start over:
-// with one wave per SIMD (65 k neurons at BASELINE configs[1] = 1024 waves on 1024 SIMDs) nothing covers the HBM
-// round trip of each batch, and the nullable outputs put a scalar branch around every load and store.  These
-// variants keep a register ring of the next D steps' inputs: every step issues ONE step's loads (D steps ahead,
+// ------------------------------------------------------------------ the scan kernels: register-ring pipelines (round 3)
+// Fetching a batch of steps, waiting for ALL of them (`s_waitcnt vmcnt(0)`), computing them and starting over leaves
+// the HBM round trip of each batch uncovered at one wave per SIMD (65 k neurons at BASELINE configs[1] = 1024 waves on
+// 1024 SIMDs), and nullable outputs put a scalar branch around every load and store (the first scan kernels, DESIGN.md
+// section 6).  These kernels keep a register ring of the next D steps' inputs: every step issues ONE step's loads (D steps ahead,
 // unconditional, clamped into range at the sequence end) and consumes the oldest slot, so the round trip sits behind
 // D steps of arithmetic and stores; which outputs exist is a template parameter (no branch in the loop).  D is
 // bounded by the wave's 6-bit vmcnt (in order, counts stores): with OPS vector-memory operations per step a load
 // older than 63 / OPS steps is forced complete by any counted wait.  Same arithmetic, same order: bit-identical.
-#ifndef CELL_PIPE
-#define CELL_PIPE 1
-#endif
 typedef unsigned cell_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int pipe_depth(int vec, int ops) { return vec == 4 ? 8 : (63 / ops < 16 ? 63 / ops : 16); }
 
@@ -346,16 +105,12 @@ template <int VEC, bool S16> struct SavedVec;
 template <int VEC> struct SavedVec<VEC, false> {
     float v[VEC];
     __device__ __forceinline__ void load(const float* base, size_t i) {
-#if CELL_NT
         if constexpr (VEC == 4) {
             const f32x4 q = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + i));
             v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
         } else {
             v[0] = __builtin_nontemporal_load(base + i);
         }
-#else
-        ldv<VEC>(v, base + i);
-#endif
     }
     __device__ __forceinline__ void expand(float (&d)[VEC]) const {
 #pragma unroll
@@ -943,23 +698,9 @@ int launch_cell(bool bwd, CellArgs& c, hipStream_t st) {
     const bool vec4 = vec_ok && work >= (long long)256 * 8 * 64 * 4;
     const long long threads = vec4 ? work / 4 : work;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
-#if CELL_PIPE
     const bool drop = c.p_drop > 0.0f;
     if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true>(bwd, c, blocks, st); else launch_cell_pipe<ADAPT, 4, false>(bwd, c, blocks, st); }
     else      { if (drop) launch_cell_pipe<ADAPT, 1, true>(bwd, c, blocks, st); else launch_cell_pipe<ADAPT, 1, false>(bwd, c, blocks, st); }
-#else
-#define SP_CELL_LAUNCH(KERNEL, S16)                                                                     \
-    do {                                                                                                \
-        if (vec4) hipLaunchKernelGGL((KERNEL<ADAPT, 4, S16>), dim3(blocks), dim3(256), 0, st, c);       \
-        else      hipLaunchKernelGGL((KERNEL<ADAPT, 1, S16>), dim3(blocks), dim3(256), 0, st, c);       \
-    } while (0)
-    if (!bwd) {
-        if (c.save16) SP_CELL_LAUNCH(cell_fwd_kernel, true); else SP_CELL_LAUNCH(cell_fwd_kernel, false);
-    } else {
-        if (c.save16) SP_CELL_LAUNCH(cell_bwd_kernel, true); else SP_CELL_LAUNCH(cell_bwd_kernel, false);
-    }
-#undef SP_CELL_LAUNCH
-#endif
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_fwd_kernel(LigruArgs a) {
         float rz[4] = {0.f, 0.f, 0.f, 0.f}, rc[4] = {0.f, 0.f, 0.f, 0.f};
         if (s > 0) {
             const unsigned base = (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < REC_AHEAD ? KGW : REC_AHEAD;
+            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;
             u32x4 raw[KGW][2][2];
 #pragma unroll
             for (int kk = 0; kk < AHEAD; ++kk) issue_tile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_kg);
@@ -224,11 +224,11 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_fwd_kernel(LigruArgs a) {
                 u32x4 rawv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(y[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, AUX_SC1);
             }
             if (s >= 2) {
                 const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, AUX_SC1);
             }
         }
         lds_barrier();
@@ -386,14 +386,14 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_bwd_kernel(LigruArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { rz[e] = __float_as_uint(dzp[e]); rc[e] = __float_as_uint(dcp[e]); }
                 const unsigned so = (unsigned)(s % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(rz, rsrc, so + pz, 0, REC_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(rc, rsrc, so + pc, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(rz, rsrc, so + pz, 0, AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b128(rc, rsrc, so + pc, 0, AUX_SC1);
             }
             if (s >= 2) {
                 const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
                 const unsigned so = (unsigned)((s - 2) % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, REC_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pc, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pc, 0, AUX_SC1);
             }
         }
         lds_barrier();
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
         float rz[4] = {0.f, 0.f, 0.f, 0.f}, rr[4] = {0.f, 0.f, 0.f, 0.f}, rc[4] = {0.f, 0.f, 0.f, 0.f};
         if (s > 0) {
             const unsigned base = (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < REC_AHEAD ? KGW : REC_AHEAD;
+            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;
             u32x4 raw[KGW][2][2];
 #pragma unroll
             for (int kk = 0; kk < AHEAD; ++kk) issue_tile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_kg);
@@ -552,9 +552,9 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
                 u32x4 rawv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(q[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot_bytes + qtile, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot_bytes + qtile, 0, AUX_SC1);
             }
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot_bytes + qtile, 0, REC_ST_AUX);
+            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot_bytes + qtile, 0, AUX_SC1);
         }
         // ---- candidate pre-activation: q V^T on the 16x16x32 MFMA
         if (s > 0) {
@@ -624,9 +624,9 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
                 u32x4 rawv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(y[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, AUX_SC1);
             }
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, REC_ST_AUX);
+            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, AUX_SC1);
         }
         if (valid) {
             const size_t o_st = ((size_t)bp * T + t) * H + unit;
@@ -788,8 +788,8 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_bwd_kernel(LigruArgs a) {
             u32x4 rawv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(dcp[e]);
-            __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot2_bytes + ctile, 0, REC_ST_AUX);
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot2_bytes + ctile, 0, REC_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot2_bytes + ctile, 0, AUX_SC1);
+            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot2_bytes + ctile, 0, AUX_SC1);
         }
         product16(vc, vlo2, std::integral_constant<int, KG1>{}, rsrc2,
                   (unsigned)(s % RING) * slot2_bytes + rt_off2 + (unsigned)lane * 16u, a.n_kg, red2, par);
@@ -823,13 +823,13 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_bwd_kernel(LigruArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { wz[e] = __float_as_uint(dzp[e]); wr[e] = __float_as_uint(drp[e]); }
                 const unsigned so = (unsigned)(s % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(wz, rsrc, so + pz, 0, REC_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(wr, rsrc, so + pr, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(wz, rsrc, so + pz, 0, AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b128(wr, rsrc, so + pr, 0, AUX_SC1);
             }
             if (s >= 2) {
                 const unsigned so = (unsigned)((s - 2) % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, REC_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pr, 0, REC_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pr, 0, AUX_SC1);
             }
         }
         if (valid) {

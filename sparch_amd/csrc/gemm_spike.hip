@@ -29,10 +29,8 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-#ifndef GEMM_TAIL2
-#define GEMM_TAIL2 2
-#endif
 constexpr int BK = 32;
+constexpr int TAIL2 = 2;      // MFMA groups of a six-term K tile that run behind the stage hand-over barrier (see mfma_phase)
 constexpr int KC_ROW = 40;    // bf16 per LDS row of a KC image (32 + 8 pad = 80 B)
 // bf16 per LDS row of a KM image of a ROWS-wide operand tile: ROWS + 32 pad (128 -> 320 B, 256 -> 576 B;
 // both are 16 dwords mod the 64 banks, which is what makes the transposed reads conflict-free)
@@ -42,7 +40,7 @@ template <bool KM, int ROWS> constexpr int plane_elems() { return KM ? BK * km_r
 enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_STATS = 2 };
 
 // Diagnostic build only (-DSPARCH_REC_PROF): s_memtime stamps of the phases of one K-tile iteration
-#if defined(SPARCH_REC_PROF) && !defined(GA_NO_STAMPS)
+#ifdef SPARCH_REC_PROF
 __device__ unsigned long long g_gemm_prof[8 + 8 * 2];  // [8..]: per wave of the sampled workgroup: phase, barrier
 #define GP_DECL                                                                                  \
     unsigned long long gp_t = 0, gp_acc[5] = {0, 0, 0, 0, 0}, gp_c0, gp_r0;                      \
@@ -117,52 +115,21 @@ template <bool KM, int ROWS>
 __device__ __forceinline__ bool tile_is_full(int row0, int rows, int k0, int kend, int vec) {
     return vec && row0 + ROWS <= rows && k0 + BK <= kend;
 }
-// GEMM_NT (bit mask, experiment, OFF): non-temporal hints for what a product touches once — 1: the row-major
-// activation operand of the pipelined kernels, 2: the C tiles of products with a row-major A (the big activations /
-// gradients), 4: both K-major streams of the TN products.  Measured on the cfg3 step in one call (round 3): 0 -> 6.49
-// ms, 1 -> 6.62-6.77, 3 -> 6.56-6.60, 7 -> 6.54-6.65: the products themselves do not change and the kernel BEHIND a
-// hinted product slows down (rec_bwd after dX: 2.09 -> 2.14-2.24 ms) — its input no longer waits in the infinity cache.
-#ifndef GEMM_NT
-#define GEMM_NT 0
-#endif
-// (a weight matrix is never streamed: it is the operand every tile of the product re-reads)
-template <bool A_KM, bool B_KM> constexpr bool stream_a() { return (!A_KM && (GEMM_NT & 1)) || (A_KM && B_KM && (GEMM_NT & 4)); }
-// 8: the spike plane of the TN products whose spikes are the layer's INPUT (dW = dx^T * s_in, MODE 1): written by the
-//    forward pass long ago and read here for the last time, beside a dx that the dX product behind reads again
-template <bool A_KM, bool B_KM, int MODE = 0> constexpr bool stream_b() {
-    return A_KM && B_KM && ((GEMM_NT & 4) || (MODE == 1 && (GEMM_NT & 8)));
-}
-template <bool STREAM>
-__device__ __forceinline__ f32x4 ld16(const void* q) {
-    if constexpr (STREAM) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
-    else return *reinterpret_cast<const f32x4*>(q);
-}
+// (No non-temporal hints here, unlike the time loops: on the activation operand, the C tiles or the K-major streams of
+// the TN products they took the cfg3 step from 6.49 to 6.54-6.77 ms.  The products themselves do not change and the
+// kernel BEHIND a hinted product slows down (rec_bwd after dX: 2.09 -> 2.14-2.24 ms) — its input no longer waits in the
+// infinity cache.  DESIGN.md, "Retired experiment switches".)
+__device__ __forceinline__ f32x4 ld16(const void* q) { return *reinterpret_cast<const f32x4*>(q); }
 // Which 16-byte piece of a ROW-MAJOR (ROWS x 32) operand tile a thread moves (piece index f = tid + NT * p; PPR = 8
-// pieces per row of fp32 source, 4 of a bf16 plane).  Row-major order (row = f / PPR, piece = f % PPR) makes a wave's
-// LDS stores collide: the images' rows are 80 bytes apart (20 banks, the stride that keeps the fragment reads
-// conflict-free), so four CONSECUTIVE rows wrap the 64 banks and the fourth lands on the first — SQ_LDS_BANK_CONFLICT
-// 29 % of the LDS cycles of the NT kernels, 17 % of dX (profiles/r03_pmc_lds.md).  Rows FOUR apart start 16 banks
-// apart, so the lanes that are served together take rows r, r+4, r+8, r+12: each 16 lanes of a 16-byte store and each
-// 32 lanes of an 8-byte store then cover the 64 banks exactly once — and a row's pieces stay on CONSECUTIVE lanes, so
-// the global loads coalesce as before (the first attempt, sixteen rows per piece column, was conflict-free too and
-// 17 % slower: 16-byte requests to 16 different rows per 16 lanes).
-// MEASURED, NOT KEPT (GEMM_RM_MAP=1 selects it): the conflict counter goes to 0 in every kernel and LDS busy from 43 to
-// 30 % (NT) and 39 to 31 % (dX) — and the products do not get faster (tools/gemm_sweep.py, one call: NT with statistics
-// 389 -> 395 us, dX 793 -> 791, dense NN 759 -> 762).  The LDS port is not what these kernels wait for.
-#ifndef GEMM_RM_MAP
-#define GEMM_RM_MAP 0
-#endif
+// pieces per row of fp32 source, 4 of a bf16 plane): row-major order.  A wave's LDS stores collide in this order — the
+// images' rows are 80 bytes apart, so four consecutive rows wrap the 64 banks: SQ_LDS_BANK_CONFLICT 29 % of the LDS cycles
+// of the NT kernels, 17 % of dX (profiles/r03_pmc_lds.md) — but a conflict-free order (lanes served together take rows
+// r, r+4, r+8, r+12) bought nothing: LDS busy 43 -> 30 % (NT), 39 -> 31 % (dX), NT with statistics 389 -> 395 us, dX
+// 793 -> 791, dense NN 759 -> 762.  The LDS port is not what these kernels wait for ("Retired experiment
+// switches").
 template <int PPR>
-__device__ __forceinline__ void rm_piece(int f, int& row, int& kp) {
-#if GEMM_RM_MAP
-    const int l = f & 63;
-    if constexpr (PPR == 4) { row = ((f >> 6) << 4) + (l >> 4) + (((l >> 2) & 3) << 2); kp = l & 3; }
-    else { row = ((f >> 7) << 4) + (((f >> 6) & 1) << 1) + (l >> 5) + (((l >> 3) & 3) << 2); kp = l & 7; }
-#else
-    row = f / PPR; kp = f % PPR;
-#endif
-}
-template <bool KM, int ROWS, int NT, bool STREAM = false>
+__device__ __forceinline__ void rm_piece(int f, int& row, int& kp) { row = f / PPR; kp = f % PPR; }
+template <bool KM, int ROWS, int NT>
 __device__ __forceinline__ void load_piece(f32x4& out, int p, bool fast, const float* __restrict__ P, int ld,
                                            int row0, int rows, int k0, int kend, int vec, int tid) {
     constexpr int RQ = ROWS / 4;  // pieces per k row of a KM tile
@@ -171,8 +138,8 @@ __device__ __forceinline__ void load_piece(f32x4& out, int p, bool fast, const f
     if constexpr (!KM) { int r_, kp_; rm_piece<8>(f, r_, kp_); row = row0 + r_; k = k0 + (kp_ << 2); }
     else               { k = k0 + f / RQ; row = row0 + ((f % RQ) << 2); }
     if (fast) {
-        if constexpr (!KM) out = ld16<STREAM>(P + (size_t)row * ld + k);
-        else               out = ld16<STREAM>(P + (size_t)k * ld + row);
+        if constexpr (!KM) out = ld16(P + (size_t)row * ld + k);
+        else               out = ld16(P + (size_t)k * ld + row);
         return;
     }
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -204,7 +171,7 @@ __device__ __forceinline__ void load_piece(f32x4& out, int p, bool fast, const f
 // ---- the same for a spike operand held as a bf16 plane (0 / 1.0; SURVEY f: the producers write it next to
 // their fp32 output): 8 elements per 16-byte piece, half the bytes through the CU's L1 fill path — which,
 // beside the matrix pipe, is what bounds these kernels.
-template <bool KM, int ROWS, int NT, bool STREAM = false>
+template <bool KM, int ROWS, int NT>
 __device__ __forceinline__ void load_piece16(f32x4& out, int p, bool fast, const unsigned short* __restrict__ P,
                                              int ld, int row0, int rows, int k0, int kend, int vec, int tid) {
     constexpr int RQ = ROWS / 8;  // pieces per k row of a KM tile
@@ -213,7 +180,7 @@ __device__ __forceinline__ void load_piece16(f32x4& out, int p, bool fast, const
     if constexpr (!KM) { int r_, kp_; rm_piece<4>(f, r_, kp_); row = row0 + r_; k = k0 + (kp_ << 3); }
     else               { k = k0 + f / RQ; row = row0 + ((f % RQ) << 3); }
     const unsigned short* q = KM ? P + (size_t)k * ld + row : P + (size_t)row * ld + k;
-    if (fast) { out = ld16<STREAM>(q); return; }
+    if (fast) { out = ld16(q); return; }
     u32x4 v = {0u, 0u, 0u, 0u};
     const bool outer_ok = KM ? (k < kend) : (row < rows);
     const int inner = KM ? row : k, inner_end = KM ? rows : kend;
@@ -321,9 +288,6 @@ __device__ __forceinline__ void store_piece_rne1(const f32x4& r, int p, unsigned
 template <bool KM, int ROWS>
 __device__ __forceinline__ u32x4 frag_read(const unsigned short* __restrict__ S, int idx_base, int lane, int ks) {
     constexpr int KM_ROW = km_row<ROWS>();
-#if defined(SPARCH_REC_PROF) && defined(GA_NO_FRAG)  // ablation: no LDS fragment reads
-    return u32x4{(unsigned)lane, (unsigned)ks, (unsigned)idx_base, 0x3F803F80u};
-#endif
     if constexpr (!KM) {
         const int r = lane & 31, h = lane >> 5;
         return *reinterpret_cast<const u32x4*>(S + (idx_base + r) * KC_ROW + 16 * ks + 8 * h);
@@ -341,15 +305,6 @@ __device__ __forceinline__ u32x4 frag_read(const unsigned short* __restrict__ S,
 }
 
 __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-#if defined(SPARCH_REC_PROF) && defined(GA_NO_MFMA)  // ablation: keep the operands alive, drop the MFMA
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#endif
-#if defined(SPARCH_REC_PROF) && defined(GA_FRAG_UNUSED)  // ablation: reads issued and waited for, MFMA on constants
-    asm volatile("" ::"v"(a), "v"(b));
-    const u32x4 k = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, k), __builtin_bit_cast(bf16x8, k), c, 0, 0, 0);
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
@@ -483,9 +438,6 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
             else if constexpr (NP == 1 && !SPIKE_A) store_piece_rne1<A_KM, BM, NT>(ra[q], q, st, tid);
             else store_piece<A_KM, BM, NT, SPIKE_A, true>(ra[q], q, st, tid, g.e_exact);
         } else if (q < NPA + NPB) {
-#ifdef GEMM_ABL_B
-            if (MODE == 2 || MODE == 0) { asm volatile("" ::"v"(rb[q - NPA])); return; }
-#endif
             if constexpr (BPRE)  // plane (q - NPA) / NPB1 straight into its LDS image: no conversion
                 store_piece16<B_KM, BN, NT>(rb[q - NPA], (q - NPA) % NPB1, st + A_PLANES * PLANE_A + ((q - NPA) / NPB1) * PLANE_B, tid);
             else if constexpr (B16) store_piece16<B_KM, BN, NT>(rb[q - NPA], q - NPA, st + A_PLANES * PLANE_A, tid);
@@ -494,21 +446,20 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
         }
     };
     // global -> registers, full in-range tile at K offset k (FAST only)
-    constexpr bool STR_A = stream_a<A_KM, B_KM>(), STR_B = stream_b<A_KM, B_KM, MODE>();
     auto fetch_piece = [&](auto& ra, auto& rb, int q, int k) __attribute__((always_inline)) {
         if (q < NPA) {
             if constexpr (APRE)
-                load_piece16<A_KM, BM, NT, STR_A>(ra[q], q % NPA1, true, g.Ap + (q / NPA1) * g.ap_stride, g.lda, m0, g.M, k, k_end, 1, tid);
+                load_piece16<A_KM, BM, NT>(ra[q], q % NPA1, true, g.Ap + (q / NPA1) * g.ap_stride, g.lda, m0, g.M, k, k_end, 1, tid);
             else if constexpr (A16)
-                load_piece16<A_KM, BM, NT, STR_A>(ra[q], q, true, reinterpret_cast<const unsigned short*>(g.A), g.lda, m0, g.M, k, k_end, 1, tid);
-            else load_piece<A_KM, BM, NT, STR_A>(ra[q], q, true, g.A, g.lda, m0, g.M, k, k_end, 1, tid);
+                load_piece16<A_KM, BM, NT>(ra[q], q, true, reinterpret_cast<const unsigned short*>(g.A), g.lda, m0, g.M, k, k_end, 1, tid);
+            else load_piece<A_KM, BM, NT>(ra[q], q, true, g.A, g.lda, m0, g.M, k, k_end, 1, tid);
         } else if (q < NPA + NPB) {
             if constexpr (BPRE)
-                load_piece16<B_KM, BN, NT, STR_B>(rb[q - NPA], (q - NPA) % NPB1, true, g.Bp + ((q - NPA) / NPB1) * g.bp_stride, g.ldb, n0,
+                load_piece16<B_KM, BN, NT>(rb[q - NPA], (q - NPA) % NPB1, true, g.Bp + ((q - NPA) / NPB1) * g.bp_stride, g.ldb, n0,
                                            g.N, k, k_end, 1, tid);
             else if constexpr (B16)
-                load_piece16<B_KM, BN, NT, STR_B>(rb[q - NPA], q - NPA, true, reinterpret_cast<const unsigned short*>(g.B), g.ldb, n0, g.N, k, k_end, 1, tid);
-            else load_piece<B_KM, BN, NT, STR_B>(rb[q - NPA], q - NPA, true, g.B, g.ldb, n0, g.N, k, k_end, 1, tid);
+                load_piece16<B_KM, BN, NT>(rb[q - NPA], q - NPA, true, reinterpret_cast<const unsigned short*>(g.B), g.ldb, n0, g.N, k, k_end, 1, tid);
+            else load_piece<B_KM, BN, NT>(rb[q - NPA], q - NPA, true, g.B, g.ldb, n0, g.N, k, k_end, 1, tid);
         }
     };
 
@@ -538,13 +489,6 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
 #pragma unroll
             for (int p = 0; p < NP; ++p)
                 fa[ks][i][p] = frag_read<A_KM, BM>(As + p * PLANE_A, (wm * WI + i) * 32, lane, ks);
-#ifdef GEMM_ABL_B  // timing ablation (wrong results): the weight operand's LDS traffic (staging stores + fragment reads)
-                   // dropped.  Standalone on random operands (tools/gemm_sweep.py, round 3): NT with statistics 383 ->
-                   // 330 us, dX 746 -> 635 us — the bound on what W fragments loaded straight from a fragment-ordered pack
-                   // in L2 could give (-14 %; inside the training step the ablated run reads 0.71 -> 0.54 ms, but there
-                   // its garbage output turns the next steps' operands into NaNs, which draw less power: clocks, not LDS)
-        if (MODE == 2) { asm volatile("" : "+v"(fb[ks][0][0]), "+v"(fb[ks][0][1]), "+v"(fb[ks][0][NP - 1])); return; }
-#endif
 #pragma unroll
         for (int j = 0; j < WJ; ++j)
 #pragma unroll
@@ -562,9 +506,6 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
         }
     };
     auto read_dense = [&](const unsigned short* st, int buf, int ks, int p) __attribute__((always_inline)) {
-#ifdef GEMM_ABL_B  // (the same ablation for the spike x weight products)
-        if (SPIKE_A) { asm volatile("" : "+v"(fd[buf][0])); return; }
-#endif
 #pragma unroll
         for (int j = 0; j < WD; ++j) {
             if constexpr (SPIKE_A)
@@ -582,7 +523,7 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
         constexpr bool HAS_NEXT = decltype(has_next)::value;
         constexpr int NTERM = NP == 3 ? 6 : 1;              // cross terms of a dense x dense product
         constexpr int NG = MODE == 2 ? 2 * NTERM : 2 * NP;  // MFMA groups of WI x WJ per K tile
-        constexpr int TAIL = !HAS_NEXT ? 0 : (MODE == 2 && NP == 3 ? GEMM_TAIL2 : 1);  // groups behind the barrier
+        constexpr int TAIL = !HAS_NEXT ? 0 : (MODE == 2 && NP == 3 ? TAIL2 : 1);  // groups behind the barrier
         constexpr int PPG = (NPA + NPB + NG - TAIL - 1) / (NG - TAIL);
         auto handover = [&]() __attribute__((always_inline)) {
             GP_STAMP(3);  // MFMA groups with the next tile's conversion and the loads after it
@@ -666,12 +607,8 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
                 unsigned short* nxt = lds + ((t + 1) & 1) * STAGE;
                 const int k3 = k_of(t + (AHEAD2 ? 3 : 2));
                 mfma_phase(cur, nxt, with_next, [&](int q) __attribute__((always_inline)) {
-#if !(defined(SPARCH_REC_PROF) && defined(GA_NO_STORE))
                     convert_piece(xa, xb, q, nxt);
-#endif
-#if !(defined(SPARCH_REC_PROF) && defined(GA_NO_GLOAD))
                     fetch_piece(xa, xb, q, k3);
-#endif
                 });
             };
             if constexpr (AHEAD2) {
@@ -737,8 +674,7 @@ __global__ __launch_bounds__((Shape<MODE, FAST>::NT), (Shape<MODE, FAST>::OCC)) 
                 // back to back (a predicated store is its own basic block, and hipcc then waits for the
                 // previous store's acknowledgement, vmcnt(0), in each one)
                 if (FAST || (row < g.M && col < g.N)) {
-                    if constexpr (FAST && !A_KM && (GEMM_NT & 2)) __builtin_nontemporal_store(v, Cz + (size_t)row * g.ldc + col);
-                    else Cz[(size_t)row * g.ldc + col] = v;
+                    Cz[(size_t)row * g.ldc + col] = v;
                     if constexpr (EPI & EPI_STATS) { csum[j] += v; csq[j] += v * v; }
                 }
             }
@@ -1430,7 +1366,7 @@ extern "C" int sparch_gemm_auto16_tn(int M, int N, int K, const float* A, int ld
     return SPARCH_OK;
 }
 
-#if defined(SPARCH_REC_PROF) && !defined(GA_NO_STAMPS)
+#ifdef SPARCH_REC_PROF
 extern "C" int sparch_gemm_prof_read(unsigned long long* host_out, int reset) {
     static unsigned long long zero[8 + 8 * 2];
     if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_gemm_prof), sizeof(zero)) != hipSuccess) return -1;

@@ -163,9 +163,6 @@ __global__ __launch_bounds__(256) void colfinish_kernel(int H, int n_rb, int n_o
 
 // dx = gamma*invstd * (dy - dbeta/M - xhat*dgamma/M) = k1*dy + k2*x + k3 with per-column k1,k2,k3:
 // a thread keeps the coefficients of its 4 columns in registers and strides over rows.
-#ifndef BN_APPLY_NT_X
-#define BN_APPLY_NT_X 1
-#endif
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(int M, int H, float invM, const float* __restrict__ dy,
                                                            const float* __restrict__ x,
                                                            const float* __restrict__ mean,
@@ -197,12 +194,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(int M, int H, float i
             for (int u = 0; u < UR; ++u) {
                 const size_t o = (size_t)(r + u) * H + c;
                 d[u] = *reinterpret_cast<const f32x4*>(dy + o);
-#if BN_APPLY_NT_X  // the raw projection (saved by the forward, read here for the last time) as a streaming load: dx, which the
-                   // two GEMMs behind this pass read, keeps its place in the infinity cache (cfg3 step 6.37-6.47 -> 6.28-6.33 ms)
+                // the raw projection (saved by the forward, read here for the last time) as a streaming load: dx, which the
+                // two GEMMs behind this pass read, keeps its place in the infinity cache (cfg3 step 6.37-6.47 -> 6.28-6.33 ms)
                 xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + o));
-#else
-                xv[u] = *reinterpret_cast<const f32x4*>(x + o);
-#endif
             }
 #pragma unroll
             for (int u = 0; u < UR; ++u) {

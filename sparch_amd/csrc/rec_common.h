@@ -17,54 +17,13 @@ constexpr int RT = 32;       // rows per batch tile
 constexpr int CT = 32;       // columns per workgroup (= one k-group of its consumers)
 constexpr int RED_LD = 33;   // padded row of the cross-wave reduction tiles (read with 4-byte accesses)
 constexpr int RED_LD4 = 32;  // ... of the spiking cells' tiles, read with one 16-byte access per partial tile
-#ifndef REC_RING
-#define REC_RING 4
-#endif
-constexpr int RING = REC_RING;  // depth of the backward hand-off ring (2 suffices, see header)
+constexpr int RING = 4;      // depth of the backward hand-off ring (2 suffices, see header)
 constexpr int TILE_BYTES = RT * CT * 4;  // one fp32 hand-off tile
-// Scope of the hand-off accesses.  Experiment hooks (diagnostic builds only); the shipped values are
-// agent scope / sc1, the only combination that is correct for any placement of the workgroups.
-#ifndef REC_LD_SCOPE
-#define REC_LD_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#endif
-#ifndef REC_ST_SCOPE
-#define REC_ST_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#endif
-#ifndef REC_LD_AUX
-#define REC_LD_AUX 16 /* sc1 */
-#endif
-#ifndef REC_ST_AUX
-#define REC_ST_AUX 16 /* sc1 */
-#endif
-#ifndef REC_XSTORE
-#define REC_XSTORE 0  /* forward: bulk stores issued by the waves without pointwise state (measured: slower, see reccell.hip) */
-#endif
-#ifndef REC_BWD_XSTORE
-#define REC_BWD_XSTORE 1  /* backward: bulk stores issued one step later by the waves without pointwise state */
-#endif
-#ifndef REC_BWD_LATE_PREFETCH
-#define REC_BWD_LATE_PREFETCH 2  /* backward: where the next step's HBM inputs are requested — 0: loop top, in front of the tile loads (1.083 ms per launch); 1: behind the last tile load (1.057); 2: behind the reduction barrier, a pointwise phase and a publish ahead of the next tile loads (1.036; round 3, A/B in one call); 3: behind the publish barrier, with the rec-independent part of the reverse step moved behind the tile loop (1.097); 4: behind the publish stores, in front of the publish barrier (1.049 against 1.031 for 2 at that time) */
-#endif
-#ifndef REC_FWD_UPPER_SLEEP
-#define REC_FWD_UPPER_SLEEP 0  /* forward: s_sleep units (64 cycles) of the waves without pointwise state before they poll again */
-#endif
-#ifndef REC_BWD_UPPER_RESET
-#define REC_BWD_UPPER_RESET 1  /* backward: the ring's sentinels are put back by the waves without pointwise state */
-#endif
-#ifndef REC_BWD_PARK
-#define REC_BWD_PARK 0  /* backward: the step's saved states wait in LDS instead of VGPRs (see reccell.hip; measured 1.056 vs 1.043 ms per launch, and a second k-group of tile loads in flight still spills: off) */
-#endif
-#ifndef REC_BWD_PROBE
-#define REC_BWD_PROBE 0  /* backward: probe one dword per producer sample before issuing a step's tile loads (measured with one k-group ahead: 1.117 vs 1.040 ms per launch — the probe is one more round trip; with two or more ahead the kernel spills) */
-#endif
-#ifndef REC_BWD_UPPER_DELAY
-#define REC_BWD_UPPER_DELAY 0   // s_sleep units (64 cycles) before the upper waves' first tile loads of a backward step.
-                                // Measured (40 launches x 3, one call): 0 -> 1.029 ms per launch, 4 -> 1.040, 8 -> 1.049,
-                                // 14 -> 1.074: the upper waves are the LATE ones at the reduction barrier, not early pollers
-#endif
-#ifndef REC_AHEAD
-#define REC_AHEAD 1  /* k-groups whose tile loads are issued ahead of the one being multiplied */
-#endif
+// Cache-policy operand of the hand-off buffer accesses: sc1.  Every hand-off load and store is agent scope / sc1,
+// the only combination that is correct for any placement of the workgroups (a narrower scope stays in an XCD's L2,
+// invisible to the other XCDs; plain stores are used only where xcd_agree has VERIFIED a shared XCD, see below).
+constexpr int AUX_SC1 = 16;
+constexpr int TILES_AHEAD = 1;  // k-groups whose tile loads are issued ahead of the one being multiplied
 constexpr u64 TIMEOUT_TICKS = 200000000ull;  // 2 s of s_memrealtime (100 MHz)
 // "not written yet" pattern of the backward / dense hand-off ring: a SIGNALLING NaN.  Arithmetic results are
 // never signalling (the hardware quiets every NaN it produces or propagates, IEEE mode), so no tile value
@@ -83,32 +42,14 @@ __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<
 // 1.09 (stores), 1.04 ms (both), step 6.58 -> 6.38 ms.  (The same hints on the split GEMMs' activation operands and
 // C tiles LOSE: 6.49 -> 6.55-6.77 ms — a GEMM's output is the next kernel's input and should stay in the 256 MB
 // infinity cache; `rec_bwd` right behind the dX product slowed down by 3-7 %.)
-#ifndef REC_NT_LOADS
-#define REC_NT_LOADS 1
-#endif
 __device__ __forceinline__ f32x4 ld4s(const float* p) {  // a streaming input: read once
-#if REC_NT_LOADS
     return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-    return *reinterpret_cast<const f32x4*>(p);
-#endif
 }
-#ifndef REC_NT_STORES
-#define REC_NT_STORES 1  /* bulk output stores of the recurrent kernels as non-temporal stores (see REC_NT_LOADS) */
-#endif
-__device__ __forceinline__ void st4(float* p, f32x4 v) {
-#if REC_NT_STORES
+__device__ __forceinline__ void st4(float* p, f32x4 v) {  // a bulk output of the recurrent kernels
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 __device__ __forceinline__ void st2(void* p, u32x2 v) {  // an 8-byte bulk output (bf16 plane quads, bf16 saves)
-#if REC_NT_STORES
     __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(p));
-#else
-    *reinterpret_cast<u32x2*>(p) = v;
-#endif
 }
 // saved states (u, w) as fp32 or bf16 (element index i)
 __device__ __forceinline__ f32x4 ld4_saved(const float* base, size_t i, bool s16) {
@@ -255,7 +196,7 @@ __device__ __forceinline__ void issue_tile(u32x4 (&g)[2][2], __amdgpu_buffer_rsr
             // zeros for out-of-range buffer loads — no branch, and zeros are never "missing"
             const unsigned off = kg < n_ct ? base + (unsigned)kg * TILE_BYTES + (unsigned)((ks * 2 + q) * 1024)
                                            : 0xFFFFFF00u;
-            g[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, REC_LD_AUX);
+            g[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, AUX_SC1);
         }
 }
 
@@ -281,7 +222,7 @@ __device__ __forceinline__ void settle_tile(u32x4 (&g)[2][2], __amdgpu_buffer_rs
 #pragma unroll
                 for (int q = 0; q < 2; ++q)
                     tmp[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tile_base + (unsigned)((ks * 2 + q) * 1024),
-                                                                      0, REC_LD_AUX);
+                                                                      0, AUX_SC1);
             vm_settled();
             unsigned still = 0;
 #pragma unroll
@@ -325,7 +266,7 @@ __device__ __forceinline__ void issue_ptile(u32x4 (&g)[2][NP], __amdgpu_buffer_r
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const unsigned off = kg < n_ct ? base + (unsigned)kg * ptile_bytes<NP>() + (unsigned)((ks * NP + p) * 1024) : 0xFFFFFF00u;
-            g[ks][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, REC_LD_AUX);
+            g[ks][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, AUX_SC1);
         }
 }
 template <int NP = 3>
@@ -344,7 +285,7 @@ __device__ __forceinline__ void settle_ptile(u32x4 (&g)[2][NP], __amdgpu_buffer_
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    tmp[ks][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tile_base + (unsigned)((ks * NP + p) * 1024), 0, REC_LD_AUX);
+                    tmp[ks][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tile_base + (unsigned)((ks * NP + p) * 1024), 0, AUX_SC1);
             vm_settled();
             unsigned still = 0;
 #pragma unroll
@@ -387,7 +328,7 @@ __device__ __forceinline__ void store_planes(const u32x2 (&w)[3], __amdgpu_buffe
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         if (plain) __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, off + (unsigned)(p * 1024), 0, 0);
-        else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, off + (unsigned)(p * 1024), 0, REC_ST_AUX);
+        else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, off + (unsigned)(p * 1024), 0, AUX_SC1);
     }
 }
 

@@ -58,10 +58,6 @@
 
 #include "rec_common.h"
 
-#ifndef REC_ACC_REGS
-#define REC_ACC_REGS 0  /* backward: parameter / BatchNorm partial sums in LDS (1: in registers — measured no faster: 1.37 vs 1.36 ms per launch) */
-#endif
-
 namespace {
 
 struct RecArgs {
@@ -232,17 +228,9 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
     // would put their HBM latency in front of the sweep.  Issued behind it they retire under the MFMA phase.
     f32x4 pend_s = {0.f, 0.f, 0.f, 0.f}, pend_u = pend_s, pend_w = pend_s;
     int pend_t = -1;
-    // XSTORE (build option REC_XSTORE=1, 8-wave kernels; OFF: measured 0.76 -> 0.81 ms per launch, bit-identical
-    // results): the stores issued by the four waves that hold NO pointwise state.  A step's (s, u, w) go through
-    // an LDS staging buffer; after the next step's reduction barrier the upper waves read them and issue the
-    // global stores while the pointwise waves run their update — the stores then sit in THOSE waves' memory
-    // queues, not in front of the pointwise waves' poll (`vmcnt` is in order and counts stores).  But the upper
-    // waves poll too, with LESS lead over their stores (a pointwise phase instead of a whole step), and the
-    // matrix phase waits for its slowest wave: the timing ablation's 0.75 k cycles (no stores at all) cannot be
-    // had by moving the stores between waves of the same workgroup.
-    constexpr bool XSTORE = REC_XSTORE && NW == 8 && !EXT && CW == 1;
-    __shared__ __attribute__((aligned(16))) f32x4 stage[XSTORE ? 2 : 1][3][XSTORE ? 256 : 1];
-    const bool valid_hi = !pw && bp < a.Bp && col < H;  // an upper-wave thread, same (row, columns) as tid - 256
+    // (Handing these stores to the four waves without pointwise state, through an LDS staging buffer, lost:
+    // 0.76 -> 0.81 ms per launch.  Those waves poll too, with less lead over the stores, and the matrix phase waits
+    // for its slowest wave.  DESIGN.md, "Retired experiment switches".)
     auto store_step = [&](int st_t, const f32x4& vs, const f32x4& vu, const f32x4& vw) {
         const int ptt = d ? (T - 1 - st_t) : st_t;
         const size_t o_s = ((size_t)b * T + ptt) * HO + (size_t)d * H + colc;
@@ -257,24 +245,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         if (ADAPT) st4_saved<false>(a.w_save, ((size_t)bp * T + st_t) * H + col, vw, a.save16, a.theta);
     };
     auto flush_pending = [&]() {
-#if defined(SPARCH_REC_PROF) && defined(FA_NO_BULK)  // timing ablation (no outputs): the step's HBM stores dropped
+        if (pend_t >= 0 && valid) store_step(pend_t, pend_s, pend_u, pend_w);
         pend_t = -1;
-        return;
-#endif
-        if (!XSTORE && pend_t >= 0 && valid) store_step(pend_t, pend_s, pend_u, pend_w);
-        pend_t = -1;
-    };
-    auto flush_staged = [&](int st_t) {  // upper waves: the staged step st_t -> HBM
-#if defined(SPARCH_REC_PROF) && defined(FA_NO_BULK)
-        return;
-#endif
-        if (valid_hi) {
-            const int q = tid & 255;
-            const f32x4 vs = stage[st_t & 1][0][q], vu = stage[st_t & 1][1][q];
-            f32x4 vw = vs;
-            if (ADAPT) vw = stage[st_t & 1][2][q];
-            store_step(st_t, vs, vu, vw);
-        }
     };
     PROF_DECL
 
@@ -306,7 +278,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
 #pragma unroll
                 for (int kk = 0; kk < KGW; ++kk) {
                     const int kgc = min(wave + NW * kk, a.n_ct - 1);
-                    gran[kk] = __hip_atomic_load(base + (size_t)kgc * 32 + li, __ATOMIC_RELAXED, REC_LD_SCOPE);
+                    gran[kk] = __hip_atomic_load(base + (size_t)kgc * 32 + li, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 unsigned bad = 0;
 #pragma unroll
@@ -338,14 +310,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
                 // section free of branches lets the scheduler interleave LUT reads with the MFMA chain
                 const unsigned wbits = (wave + NW * kk < a.n_ct) ? (unsigned)gran[kk] : 0u;
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-#if defined(SPARCH_REC_PROF) && defined(FA_NO_LUT)  // timing ablation (wrong results): no LDS table read
-                    const unsigned by = (wbits >> (16 * ks + 8 * hh)) & 0xFFu;
-                    af[kk][ks] = u32x4{by, by ^ 0x3F80u, by, by};
-#else
+                for (int ks = 0; ks < 2; ++ks)
                     af[kk][ks] = lut[(wbits >> (16 * ks + 8 * hh)) & 0xFFu];
-#endif
-                }
             }
             f32x16 acc[CW];
 #pragma unroll
@@ -357,19 +323,9 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-#ifdef REC_FWD_ABL2  // timing ablation (wrong results): two of the three planes
-                    for (int p = NP - 1; p >= (NP == 3 ? 1 : 0); --p)
-#else
                     for (int p = NP - 1; p >= 0; --p)
-#endif
 #pragma unroll
-                        for (int c = 0; c < CW; ++c) {
-#if defined(SPARCH_REC_PROF) && defined(FA_NO_MFMA)  // timing ablation (wrong results): operands kept alive, no MFMA
-                            asm volatile("" ::"v"(af[kk][ks]), "v"(vb[c][kk][ks][p]));
-#else
-                            acc[c] = mfma_bf16(af[kk][ks], vb[c][kk][ks][p], acc[c]);
-#endif
-                        }
+                        for (int c = 0; c < CW; ++c) acc[c] = mfma_bf16(af[kk][ks], vb[c][kk][ks][p], acc[c]);
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
                 float* rd = red[t & 1][wave][c];
@@ -385,19 +341,12 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         lds_barrier();
         PROF_STAMP(2);  // barrier
         if (lds_flag_read(&abort_flag[t & 1])) break;
-        if (XSTORE && t > a.t_begin) flush_staged(t - 1);  // (the barrier above ordered the staging writes)
         // Everything from here to the end of the step belongs to the waves that own pointwise state.  A WAVE-UNIFORM
         // branch (round 3): until then the upper four waves of an 8-wave workgroup ran the whole update on dead
         // values — per-thread `valid` only masked its stores — and took every other vector issue slot of the
         // pointwise waves they share a SIMD with (stamped: 1.44 k cycles of "pointwise" on wave 4 beside 1.54 k on
         // wave 0).  They now go straight on to the next step's poll.
         if (pw_wave) {
-#if defined(SPARCH_REC_PROF) && defined(FA_NO_RED)  // timing ablation (wrong results): one partial tile instead of NW
-        if (t > 0 && !EXT) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rec[e] = red[t & 1][0][CW == 2 ? tid >> 8 : 0][r * RED_LD4 + cq * 4 + e];
-        }
-#else
         if (t > 0 && !EXT) {
             // unpadded 128-byte rows: a thread's four columns are one aligned ds_read_b128 per partial tile, and the
             // b128 lane groups (rows r, r+1 of column quads 0-3 / 4-7) fall on all 64 banks (conflict-free, like the
@@ -413,7 +362,6 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) rec[e] = sum[e];
         }
-#endif
 
         // ---- pointwise membrane update for this thread's 4 neurons
         // (Hoisting the rec-independent part of this update in front of the poll was measured: 0.75 -> 0.81 ms
@@ -455,11 +403,9 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             gu64* slot = (gu64*)a.chan + (((size_t)t * a.n_rt_total + rt) * a.n_ct + ct) * 32 + r;
             const u64 granule = ((u64)(unsigned)(t + 1) << 32) | (u64)word;
             if (xcd_local) __hip_atomic_store(slot, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else __hip_atomic_store(slot, granule, __ATOMIC_RELAXED, REC_ST_SCOPE);
+            else __hip_atomic_store(slot, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#if !REC_FWD_UPPER_SLEEP
         if (NW == 8 && CW == 1) lds_barrier();  // releases the upper waves into the next step's poll (see the else branch)
-#endif
         PROF_STAMP(3);  // pointwise + publish
         if (valid) {
             const int tt = d ? (T - 1 - t) : t;
@@ -471,12 +417,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
                 so[e] = s[e] * k;
                 cnt[e] += (so[e] != 0.0f) ? 1u : 0u;
             }
-            if (XSTORE) {
-                stage[t & 1][0][tid] = so; stage[t & 1][1][tid] = uo;
-                if (ADAPT) stage[t & 1][2][tid] = wo;
-            } else {
-                pend_s = so; pend_u = uo; pend_w = wo;
-            }
+            pend_s = so; pend_u = uo; pend_w = wo;
         }
         } else {
             // ... but not at once: the peers' granules of this step cannot exist before their pointwise phase is
@@ -487,22 +428,12 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             // and LDS cycles from the pointwise waves).  So they park in a second barrier that the pointwise waves
             // join right behind their publish store: no instruction issues while a wave waits there, and the
             // wait adapts to the cell kind and the clock.
-#if REC_FWD_UPPER_SLEEP
-            __builtin_amdgcn_s_sleep(REC_FWD_UPPER_SLEEP);
-#else
             lds_barrier();
-#endif
         }
         pend_t = t;
         PROF_STAMP(4);  // dropout
     }
-    if (XSTORE) {  // the last step of the launch (skipped after an abort: the step is discarded anyway)
-        const bool aborted = (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])) != 0;
-        __syncthreads();
-        if (!aborted && a.t_end > a.t_begin) flush_staged(a.t_end - 1);
-    } else {
-        flush_pending();
-    }
+    flush_pending();
     PROF_FLUSH(0)
 
     // ---- spike counts (post-dropout) -> one integer atomic per (direction, column) per workgroup
@@ -551,22 +482,10 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
     __shared__ __attribute__((aligned(16))) f32x4 first_tile[3][256 * CW];
     // running parameter-gradient partial sums (alpha, beta, a, b) of the thread's 4 columns: touched once per
     // step, off the critical path -> LDS, so that the hot loop's registers do not spill
-#if REC_ACC_REGS
-    f32x4 pacc_r[6] = {};         // the six accumulators in registers (the k-group pipeline freed the room)
-#define PACC(j, i) pacc_r[j]
-#else
+    // (in registers they were measured no faster: 1.37 vs 1.36 ms per launch)
     __shared__ __attribute__((aligned(16))) f32x4 pacc[6][256 * CW];  // + BatchNorm's sum dWx, sum dWx*xhat
-#define PACC(j, i) pacc[j][i]
-#endif
     __shared__ int abort_flag[2];
     __shared__ int xcd_local_flag;
-    // PARK: the saved states of a step (u_{t-1}, w_{t-1}, the raw projection) wait in LDS from the loop top to the
-    // points that use them — the spike of s_{t-1} and the parameter sums behind the publish barrier, u_t in the next
-    // step's box-car gate — instead of in 16 VGPRs across the whole tile phase (the registers a second k-group of
-    // tile loads in flight needs)
-    constexpr bool PARK = REC_BWD_PARK && NW == 8 && CW == 1;
-    __shared__ __attribute__((aligned(16))) f32x4 park_u[PARK ? 2 : 1][PARK ? 256 : 1];
-    __shared__ __attribute__((aligned(16))) f32x4 park_wx[PARK ? 2 : 1][PARK ? 256 : 1];
     // BXS (8-wave kernels): the step's bulk HBM stores (dWx for the GEMMs, the bf16 plane of s_{t-1}) are issued
     // by the four waves that hold NO pointwise state, one step later: the pointwise waves stage the 24 bytes per
     // thread in LDS after the publish barrier, the upper waves pick them up behind the NEXT step's reduction
@@ -574,7 +493,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
     // cycles ahead of their own next tile loads.  On the pointwise waves the stores sat ~0.8 k cycles in front of
     // the next step's tile loads, and `vmcnt` (in order, counts stores) made the first k-group wait for their
     // acknowledgement: timing ablation without the stores 1.29 -> 1.16 ms per launch.
-    constexpr bool BXS = REC_BWD_XSTORE && NW == 8 && !EXT && CW == 1;
+    constexpr bool BXS = NW == 8 && !EXT && CW == 1;
     __shared__ __attribute__((aligned(16))) f32x4 stage_dwx[BXS ? 256 : 1];
     __shared__ __attribute__((aligned(8))) u32x2 stage_sp[BXS ? 256 : 1];
 
@@ -656,16 +575,15 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
                 v = ld4(ws + 5 * plane); dw_n[0] = v.x; dw_n[1] = v.y; dw_n[2] = v.z; dw_n[3] = v.w;
             }
         }
-        PACC(0, tid) = v_al; PACC(1, tid) = v_be; PACC(2, tid) = v_a; PACC(3, tid) = v_b;
+        pacc[0][tid] = v_al; pacc[1][tid] = v_be; pacc[2][tid] = v_a; pacc[3][tid] = v_b;
         if (bn) {
-            PACC(4, tid) = a.t_end < T ? ld4(ws + 6 * plane) : z4;
-            PACC(5, tid) = a.t_end < T ? ld4(ws + 7 * plane) : z4;
+            pacc[4][tid] = a.t_end < T ? ld4(ws + 6 * plane) : z4;
+            pacc[5][tid] = a.t_end < T ? ld4(ws + 7 * plane) : z4;
         }
     }
     {
         const f32x4 v = expand_saved(ld_saved_raw<S16>(a.u_save, ((size_t)bpc * T + (a.t_end - 1)) * H + colc));
         u_t[0] = v.x; u_t[1] = v.y; u_t[2] = v.z; u_t[3] = v.w;
-        if (PARK && pw) park_u[a.t_end & 1][tid] = v;
     }
     if (tid < 2) abort_flag[tid] = 0;
     const unsigned my_xcc = xcc_id();
@@ -716,24 +634,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
             upv = first_tile[0][pt];
             if (ADAPT) wpv = first_tile[1][pt];
         }
-        if (PARK && pw) {
-            park_u[t & 1][pt] = upv;
-            if (ADAPT) park_wx[0][pt] = wpv;
-            if (bn) park_wx[1][pt] = xrv;
-        }
         float rec[4] = {0.f, 0.f, 0.f, 0.f};
         const int par = t & 1;
-        // The next step's inputs (g, u, w, raw projection: HBM loads) are prefetched IN FRONT of this step's tile
-        // loads.  (Build option REC_BWD_LATE_PREFETCH=1 issues them behind the last tile load instead, so that no
-        // HBM round trip sits between the pointwise waves and their first k-group, `vmcnt` being in order —
-        // measured 1.20 -> 1.26 ms per launch: the tiles have not landed at that point anyway, and the late loads
-        // then arrive into the pointwise phase.)
-#if REC_BWD_LATE_PREFETCH == 2
-#elif REC_BWD_LATE_PREFETCH
-        if (!(t + 1 < T && !EXT) && pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#else
-        if (pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#endif
         // Everything of the reverse step that does not depend on the recurrent product — the dropout factor's
         // hash, the incoming gradient, alpha * du_{t+1}, the adaptation terms — is computed BEFORE the reduction
         // barrier, behind the first tile loads' issue (the pointwise waves would only wait there): the chain
@@ -777,50 +679,18 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
             // 3.7 k, and MFMA (3.1 k) + split VALU (2.8 k) add up on the SIMD instead of overlapping.
             // (bf16 operand mode, NP = 1: a third of the bytes — all k-groups are issued at once; one group ahead
             // made that mode's tile phase four sequential L2 round trips, 3.2 k cycles with 16 MFMAs per SIMD)
-            constexpr int AHEAD = NP == 1 ? KGW : (KGW < REC_AHEAD ? KGW : REC_AHEAD);
+            constexpr int AHEAD = NP == 1 ? KGW : (KGW < TILES_AHEAD ? KGW : TILES_AHEAD);
             u32x4 raw[KGW][2][NP];  // [k-group][k16-step][plane]: MFMA A fragments as they come off the wire
-#if REC_BWD_PROBE
-            // PROBE, then burst (round 3).  A tile load issued before its producer's stores have landed returns
-            // sentinels and costs a second, serialized round trip in `settle_ptile` — which is why more than one
-            // k-group in flight at the step's start only lost time (round 2: 10.3 k -> 11.4 k cycles per step with
-            // all loads up front; 1.04 -> 1.34 ms per launch with two groups ahead): the early groups were
-            // speculative.  So a wave first watches ONE dword per sample: lane (kk, j) reads the first word that
-            // producer thread (row 2j+1, column quad j & 7) of tile kk stores into the LAST plane — 16 samples per
-            // tile from all four producer waves, 4 cache lines per probe instruction instead of 6 KiB per k-group —
-            // and issues the tile loads only when every sample has landed.  The full sentinel check of
-            // `settle_ptile` stays: a piece that is still missing then is re-loaded as before.
-            if (pw) pre_pointwise();
-            {
-                const int pk = lane >> 4, pj = lane & 15, prow = 2 * pj + 1, pcq = pj & 7;
-                const int pkg = wave + NW * pk;
-                const unsigned poff = (pk < KGW && pkg < a.n_ct)
-                    ? slot * slot_bytes + rt_off + (unsigned)pkg * PT +
-                      (unsigned)((((pcq >> 2) * NP + (NP - 1)) * 64 + ((pcq >> 1) & 1) * 32 + prow) * 16 + (pcq & 1) * 8)
-                    : 0xFFFFFF00u;  // beyond the buffer resource: reads 0, never "missing"
-                const u64 t_start = __builtin_amdgcn_s_memrealtime();
-                for (unsigned spins = 0;; ++spins) {
-                    const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rsrc, poff, 0, REC_LD_AUX);
-                    if (__all(v != SENTINEL)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((spins & 63u) == 63u && __builtin_amdgcn_s_memrealtime() - t_start > TIMEOUT_TICKS) {
-                        lds_flag_set(&abort_flag[par]);
-                        break;
-                    }
-                }
-            }
-#endif
-#if REC_BWD_UPPER_DELAY
-            // (experiment: the waves without pointwise state reach this point a few hundred cycles before the others;
-            // if their first k-group is requested before the peers' tiles have landed it costs them a second round
-            // trip, and the pointwise waves then wait for them at the reduction barrier)
-            if (NW == 8 && CW == 1 && !pw_wave) __builtin_amdgcn_s_sleep(REC_BWD_UPPER_DELAY);
-#endif
+            // (More than one k-group in flight at the step's start only loses time — a tile load issued before its
+            // producer's stores have landed returns sentinels and costs a second, serialized round trip in
+            // `settle_ptile`: 10.3 k -> 11.4 k cycles per step with all loads up front, 1.04 -> 1.34 ms per launch with
+            // two groups ahead.  Probing one dword per producer sample before the burst is one more round trip: 1.117
+            // vs 1.040 ms.  Delaying the upper waves' first loads loses too — they are the LATE ones at the reduction
+            // barrier.  DESIGN.md, "Retired experiment switches".)
 #pragma unroll
             for (int kk = 0; kk < AHEAD; ++kk) issue_ptile<NW, NP>(raw[kk], rsrc, base, wave + NW * kk, a.n_ct);
             PROF_STAMP(0);  // first tile load issue
-#if !REC_BWD_PROBE && REC_BWD_LATE_PREFETCH != 3
             if (pw) pre_pointwise();
-#endif
             f32x16 acc[CW];
 #pragma unroll
             for (int c = 0; c < CW; ++c)
@@ -848,25 +718,15 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
                     // |x||V|), t2*lo (<= 2^-23) and t3*lo.  Worst-case per product; summed over a row the
                     // dropped part measures 3e-9 of sum|x||V| (7 terms: 1.4e-9; an fp32 sgemm's own
                     // rounding: 1e-7) — the same kind of cut as the dense 6-term GEMM.
-#ifndef REC_BWD_ABL3  // (timing ablation, wrong results: the three largest terms only)
                     acc[0] = mfma_bf16(p2, vb[0][kk][ks][NP == 3], acc[0]);  // t2*mid
                     acc[0] = mfma_bf16(p3, vb[0][kk][ks][0], acc[0]);  // t3*hi
                     acc[0] = mfma_bf16(p1, vl, acc[0]);       // t1*lo
-#else
-                    asm volatile("" ::"v"(p3), "v"(vl));
-#endif
                     acc[0] = mfma_bf16(p2, vb[0][kk][ks][0], acc[0]);  // t2*hi
                     acc[0] = mfma_bf16(p1, vb[0][kk][ks][NP == 3], acc[0]);  // t1*mid
                     acc[0] = mfma_bf16(p1, vb[0][kk][ks][0], acc[0]);  // t1*hi
                     }
                 }
             }
-#if REC_BWD_LATE_PREFETCH == 1
-            if (pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#endif
-#if REC_BWD_LATE_PREFETCH == 3
-            if (pw) pre_pointwise();
-#endif
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
                 float* rd = red[wave][c];
@@ -883,11 +743,13 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         vm_settled();  // tile loads are in, last step's stores and this step's prefetch long complete
         PROF_STAMP(2);  // barrier
         if (lds_flag_read(&abort_flag[par])) { t_stop = t; break; }
-#if REC_BWD_LATE_PREFETCH == 2
+        // The next step's inputs (g, u, w, raw projection: HBM loads) are requested HERE, behind the reduction barrier:
+        // a pointwise phase and a publish ahead of the next tile loads, so that no HBM round trip sits between the
+        // pointwise waves and their first k-group (`vmcnt` is in order).  Measured per launch, A/B in one call: at the
+        // loop top 1.083 ms, behind the last tile load 1.057, here 1.036, behind the publish stores 1.049, behind the
+        // publish barrier 1.097 ("Retired experiment switches").
         if (pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#endif
-#ifndef REC_NO_RESET
-        if (BXS && REC_BWD_UPPER_RESET && !pw) {
+        if (BXS && !pw) {
             // The sentinels go back into this workgroup's tile of step t+2 (every peer has consumed it: see the
             // header) from the waves WITHOUT pointwise state, which idle from here to the publish barrier — as
             // 16-byte stores, one or two per thread, instead of three 8-byte stores per pointwise thread between
@@ -904,10 +766,9 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
                 // plus 16 * piece would wrap around into the ring's first tile)
                 const unsigned o = (t + 2 < T && piece < PIECES) ? so + (unsigned)piece * 16u : 0xFFFFF000u;
                 if (xcd_local) __builtin_amdgcn_raw_buffer_store_b128(sent4, rsrc, o, 0, 0);
-                else __builtin_amdgcn_raw_buffer_store_b128(sent4, rsrc, o, 0, REC_ST_AUX);
+                else __builtin_amdgcn_raw_buffer_store_b128(sent4, rsrc, o, 0, AUX_SC1);
             }
         }
-#endif
         if (BXS && valid_hi && t + 1 < a.t_end) {  // the previous step's staged outputs -> HBM (upper waves)
             const int t1 = t + 1, tt1 = d ? (T - 1 - t1) : t1;
             st4(a.dWx + ((size_t)bp * T + tt1) * H + col, stage_dwx[tid & 255]);
@@ -919,8 +780,9 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         float sp[4] = {0.f, 0.f, 0.f, 0.f}, du_new[4] = {0.f, 0.f, 0.f, 0.f}, dw_new[4] = {0.f, 0.f, 0.f, 0.f};
         f32x4 dwx = {0.f, 0.f, 0.f, 0.f}, spv = dwx;
         PROF_STAMP(6);  // behind the barrier: settle, flag read, prefetch issue, staged stores
+        // (u_{t-1}, u_t — and w_{t-1}, the raw projection below — as separate locals: hipcc's register assignment in the
+        // NP = 1 kernels follows these declarations, and the shipped instruction order is the measured one)
         f32x4 up_use = upv, ut_use = {u_t[0], u_t[1], u_t[2], u_t[3]};
-        if (PARK && pw) { up_use = park_u[t & 1][pt]; ut_use = park_u[(t + 1) & 1][pt]; }
         if (pw_wave) {
         if (t + 1 < T && EXT) {
             const f32x4 v = ld4(a.rec0 + (size_t)bpc * H + colc);
@@ -996,39 +858,25 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, REC_ST_AUX);
+                    else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
                 }
             }
-#ifndef REC_NO_RESET
-            if (!(BXS && REC_BWD_UPPER_RESET)) {  // (8-wave kernels: the upper waves put the sentinels back, see below)
+            if (!BXS) {  // (8-wave kernels: the upper waves put the sentinels back, see above)
                 const u32x2 sent = {SENTINEL, SENTINEL};
                 const unsigned so = t + 2 < T ? (unsigned)((t + 2) % RING) * slot_bytes + tile_off : 0xFFFFF000u;
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, REC_ST_AUX);
+                    else __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
                 }
             }
-#endif
         }
         }
-#if REC_BWD_LATE_PREFETCH == 4
-        if (pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#endif
         PROF_STAMP(3);  // pointwise + tile store issue
-#ifndef REC_NO_PUBLISH_BARRIER
         lds_barrier();  // the non-pointwise waves start polling only once this workgroup's own tile is on its way
-#endif
         PROF_STAMP(4);  // publish barrier
-#if REC_BWD_LATE_PREFETCH == 3
-        if (pw && t - 1 >= a.t_begin) load_step(t - 1, g_nx, up_nx, wp_nx, xr_nx);
-#endif
         // ---- off the critical path: fp32 outputs for the following GEMMs, parameter partial sums
-#if defined(SPARCH_REC_PROF) && defined(BA_NO_BULK)  // timing ablation (no outputs): the step's HBM stores dropped
-        if (false) {
-#else
         if (valid) {
-#endif
             u32x2 h;  // s_{t-1} (binary for t >= 1, zero row at t = 0) as a bf16 plane for the dV product
             h.x = (spv[0] != 0.f ? 0x3F80u : 0u) | (spv[1] != 0.f ? 0x3F800000u : 0u);
             h.y = (spv[2] != 0.f ? 0x3F80u : 0u) | (spv[3] != 0.f ? 0x3F800000u : 0u);
@@ -1041,9 +889,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         }
         if (pw) {
             f32x4 wp_use = wpv, xr_use = xrv;
-            if (PARK) { if (ADAPT) wp_use = park_wx[0][pt]; if (bn) xr_use = park_wx[1][pt]; }
-            f32x4 v_al = PACC(0, pt), v_be, v_a, v_b;
-            if (ADAPT) { v_be = PACC(1, pt); v_a = PACC(2, pt); v_b = PACC(3, pt); }
+            f32x4 v_al = pacc[0][pt], v_be, v_a, v_b;
+            if (ADAPT) { v_be = pacc[1][pt]; v_a = pacc[2][pt]; v_b = pacc[3][pt]; }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float q = up_use[e] - sp[e];
@@ -1054,24 +901,24 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
                     v_b[e] += dw_new[e] * sp[e];
                 }
             }
-            PACC(0, pt) = v_al;
-            if (ADAPT) { PACC(1, pt) = v_be; PACC(2, pt) = v_a; PACC(3, pt) = v_b; }
+            pacc[0][pt] = v_al;
+            if (ADAPT) { pacc[1][pt] = v_be; pacc[2][pt] = v_a; pacc[3][pt] = v_b; }
             if (bn) {  // BatchNorm backward's column sums (dy = dWx, xhat = (x - mean) * invstd)
-                f32x4 v_dy = PACC(4, pt), v_dyx = PACC(5, pt);
+                f32x4 v_dy = pacc[4][pt], v_dyx = pacc[5][pt];
                 const f32x4 mu = pcol[5][d][cqx], is = pcol[6][d][cqx];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v_dy[e] += dwx[e];
                     v_dyx[e] += dwx[e] * ((xr_use[e] - mu[e]) * is[e]);
                 }
-                PACC(4, pt) = v_dy; PACC(5, pt) = v_dyx;
+                pacc[4][pt] = v_dy; pacc[5][pt] = v_dyx;
             }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (ADAPT) dw_n[e] = dw_new[e];
             du_n[e] = du_new[e];
-            u_t[e] = PARK ? 0.f : upv[e];
+            u_t[e] = upv[e];
         }
         PROF_STAMP(5);  // fp32 stores + partial sums
     }
@@ -1079,19 +926,17 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
     if (BXS) {  // the launch's last step is still staged (after an abort the step is discarded anyway)
         const bool aborted = (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])) != 0;
         __syncthreads();
-#if !(defined(SPARCH_REC_PROF) && defined(BA_NO_BULK))
         if (!aborted && valid_hi && a.t_end > a.t_begin) {
             const int t1 = a.t_begin, tt1 = d ? (T - 1 - t1) : t1;
             st4(a.dWx + ((size_t)bp * T + tt1) * H + col, stage_dwx[tid & 255]);
             st2(a.s_prev16 + ((size_t)bp * T + tt1) * H + col, stage_sp[tid & 255]);
         }
-#endif
     }
     if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
         status_raise(a.status, SPARCH_STATUS_REC_BWD, t_stop);
 
     if (valid) {
-        f32x4 v = PACC(0, tid);
+        f32x4 v = pacc[0][tid];
         if (a.t_begin == 0) {  // last chunk of the pass: d u_t / d alpha = (q - u_t) / (1 - alpha)
             const f32x4 al = pcol[0][d][cqx];
 #pragma unroll
@@ -1100,14 +945,14 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         st4(ws, v);
         v.x = du_n[0]; v.y = du_n[1]; v.z = du_n[2]; v.w = du_n[3]; st4(ws + 4 * plane, v);
         if (ADAPT) {
-            st4(ws + plane, PACC(1, tid));
-            st4(ws + 2 * plane, PACC(2, tid));
-            st4(ws + 3 * plane, PACC(3, tid));
+            st4(ws + plane, pacc[1][tid]);
+            st4(ws + 2 * plane, pacc[2][tid]);
+            st4(ws + 3 * plane, pacc[3][tid]);
             v.x = dw_n[0]; v.y = dw_n[1]; v.z = dw_n[2]; v.w = dw_n[3]; st4(ws + 5 * plane, v);
         }
         if (bn) {
-            st4(ws + 6 * plane, PACC(4, tid));
-            st4(ws + 7 * plane, PACC(5, tid));
+            st4(ws + 6 * plane, pacc[4][tid]);
+            st4(ws + 7 * plane, pacc[5][tid]);
         }
     }
 }
@@ -1225,7 +1070,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
         if (s > 0 && !EXT) {
             const unsigned slot = (unsigned)((s - 1) % RING);
             const unsigned base = slot * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < REC_AHEAD ? KGW : REC_AHEAD;  // see rec_bwd_kernel
+            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;  // see rec_bwd_kernel
             u32x4 raw[KGW][2][3];  // [k-group][k16-step][plane]
 #pragma unroll
             for (int kk = 0; kk < AHEAD; ++kk) issue_ptile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_ct);
@@ -1319,7 +1164,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                     if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, REC_ST_AUX);
+                    else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
                 }
             }
             if (s >= 2) {
@@ -1328,7 +1173,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                     if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, REC_ST_AUX);
+                    else __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
                 }
             }
         }
