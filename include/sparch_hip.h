@@ -500,6 +500,32 @@ int sparch_events_gather_bin(const void* times, int times_dtype, const uint16_t*
                              int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
                              uint32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream);
 
+/* f-3  A batch of HD / SC features from a device-resident audio store (every clip of a split in one flat
+ *      sample array, uploaded once) and a device list of clip indices.
+ *      Store: samples (dtype 0 = fp32 in [-1,1], 1 = int16 PCM scaled by 2^-15 on load), starts (n_store,
+ *      int64: first sample of each clip), lengths (n_store, int32 samples; negative counts as 0), labels
+ *      (n_store, int64; may be NULL when y is).  The owner has checked that every clip lies inside samples
+ *      and that clips do not overlap; the kernels trust it.  idx (batch, device int64): clip of each batch
+ *      row; an index outside [0, n_store) gives an empty clip and label -1.  y (batch, int64) = labels[idx],
+ *      may be NULL.  Nothing outside a clip's own samples is read.  Launch only: no allocation, no
+ *      synchronisation.
+ *      sparch_audio_gather_fbank: out (batch, n_frames_out, n_mels); row b holds the frames
+ *      t < sparch_fbank_frames(length) of clip idx[b] exactly as sparch_fbank_padded_fwd gives them (one shared
+ *      device function), the frames behind them exact zeros (a clip with more than n_frames_out frames is cut).
+ *      sparch_audio_gather_augment: out (batch, ld) fp32; row b holds the first min(length, ld) samples of clip
+ *      idx[b] augmented exactly as sparch_augment_padded augments row b of a batch buffer holding those clips
+ *      (one shared device function; params, the noise stream keyed by (noise_seed, b, sample), min_snr,
+ *      max_snr and sample_rate as there) and is not written behind them; out_lengths (batch, device int32)
+ *      receives min(length, ld): the `lengths` of the sparch_fbank_padded_fwd launch that follows.          */
+int sparch_audio_gather_fbank(const void* samples, int dtype, const long long* starts, const int* lengths,
+                              const long long* labels, long long n_store, const long long* idx, int batch,
+                              int n_frames_out, int n_mels, float* out, long long* y, void* stream);
+int sparch_audio_gather_augment(const void* samples, int dtype, const long long* starts, const int* lengths,
+                                const long long* labels, long long n_store, const long long* idx, int batch,
+                                int ld, const float* params, float min_snr, float max_snr,
+                                unsigned long long noise_seed, int sample_rate, float* out, int* out_lengths,
+                                long long* y, void* stream);
+
 /* ---- f-4: non-spiking baselines (anns.py) --------------------------------------------------
  * Element-wise tail of MLPLayer.forward (anns.py:218-227): y = dropout(act(z * scale + shift)) over n
  * elements of an (n/H, H) tensor; scale/shift (H) = the folded BatchNorm affine, NULL for none.

@@ -36,6 +36,14 @@ decisions once per batch in the collate function (`augment.draw_augmentation`: P
 generator in the reference's order) and apply them to the decoded batch on the device (`functional.augment_padded`)
 before the features; the other splits are not augmented, as in the reference.  The first-batch MD5 check reads the
 decoded samples before augmentation.
+
+SPARCH_AUDIO=resident (or `load_hd_or_sc(..., resident="resident")`) keeps the whole split on the device instead
+(`functional.AudioStore`): the clips are read (FLAC: decoded on the device) and uploaded once, and every batch is
+built there from the list of its clip indices — one kernel (`sparch_audio_gather_fbank`), two for an augmented split
+(`sparch_audio_gather_augment`, then the padded fbank).  The index lists come from a torch DataLoader built with the
+arguments of the file loader and the augmentation draws are made per batch where the collate function makes them,
+so with equal seeds the batches are the file loader's bit for bit.  The samples come from the pack file
+`{data_folder}/{dataset}_{split}.audio.npz` when it exists (tools/pack_audio.py), else from the files.
 """
 import logging
 import os
@@ -45,7 +53,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..functional import augment_padded, fbank_padded, flac_decode_padded, flac_error_message
+from ..functional import AudioStore, augment_padded, fbank_padded, flac_decode_padded, flac_error_message
+from ._index import _index_loader, _SampleIndices
 from .audio import FlacError, FlacStream, flac_md5_ok, read_clip
 from .augment import draw_augmentation
 
@@ -219,11 +228,73 @@ class SpeechCommands(_AudioClips):
                          [self.labels.index(os.path.dirname(w)) for w in files], device, augment)
 
 
+class ResidentAudioLoader:
+    """Batches `(xs, xlens, ys)` of an `AudioStore`: xs and ys on the device, xlens on the host as the file loader
+    gives them.  Iterating draws the epoch's index lists from a DataLoader over the clip numbers (so `len`, the short
+    last batch, `.sampler` / `set_epoch` and the global generator behave as with the file loader), uploads them in
+    one copy, and per batch makes the augmentation draws of an augmented split (`augment`: (min_snr, max_snr,
+    p_noise), else None) where the file loader's collate makes them, then launches the kernel(s)."""
+
+    def __init__(self, store, batch_size, shuffle=True, rank=0, world=1, seed=0, augment=None):
+        self.store, self.batch_size, self.augment = store, batch_size, augment
+        self.index_loader = _index_loader(_SampleIndices(len(store)), batch_size, shuffle, rank, world, seed)
+        self.sampler = self.index_loader.sampler
+
+    def __len__(self):
+        return len(self.index_loader)
+
+    def index_lists(self):
+        """The clip indices of every batch of one epoch (host tensors), in order."""
+        return [b.to(torch.int64) for b in self.index_loader]
+
+    def draw(self, n_clips):
+        """The augmentation of one batch, (params, noise_seed, min_snr, max_snr), or None for a plain split."""
+        if self.augment is None:
+            return None
+        min_snr, max_snr, p_noise = self.augment
+        params, noise_seed = draw_augmentation(n_clips, min_snr, max_snr, p_noise)
+        return params, noise_seed, min_snr, max_snr
+
+    def __iter__(self):
+        lists = self.index_lists()
+        if not lists:
+            return
+        flat = torch.cat(lists).to(self.store.device)
+        at = 0
+        for b in lists:
+            n = b.numel()
+            yield self.store.batch(flat[at:at + n], b, augment=self.draw(n), sample_rate=SAMPLE_RATE)
+            at += n
+
+
+def _audio_pack_path(data_folder, dataset_name, split):
+    return f"{data_folder}/{dataset_name}_{split}.audio.npz"
+
+
+def _dataset(dataset_name, data_folder, split, use_augm=False, min_snr=0.0001, max_snr=0.9, p_noise=0.1,
+             device="cuda"):
+    """(dataset, the split's own name): the clips of `split` ("train" / "valid" / "test") of "hd" or "sc"."""
+    if dataset_name == "hd":
+        if split in ["valid", "test"]:
+            split = "test"
+            logging.info("\nHD uses the same split for validation and testing.\n")
+        return HeidelbergDigits(data_folder, split, use_augm, min_snr, max_snr, p_noise, device=device), split
+    split = {"train": "training", "valid": "validation", "test": "testing"}[split]
+    return SpeechCommands(data_folder, split, use_augm, min_snr, max_snr, p_noise, device=device), split
+
+
 def load_hd_or_sc(dataset_name, data_folder, split, batch_size, shuffle=True, use_augm=False, min_snr=0.0001,
-                  max_snr=0.9, p_noise=0.1, workers=0, device="cuda", rank=0, world=1, seed=0):
+                  max_snr=0.9, p_noise=0.1, workers=0, device="cuda", rank=0, world=1, seed=0, resident=None):
     """nonspiking_datasets.py:212-290.  rank / world (data-parallel runs; not in the reference): every rank lists
     the same files and draws a disjoint 1/world share of each epoch's (shuffled) order through a
-    DistributedSampler — call `loader.sampler.set_epoch(e)` per epoch; `batch_size` is the PER-RANK batch."""
+    DistributedSampler — call `loader.sampler.set_epoch(e)` per epoch; `batch_size` is the PER-RANK batch.
+    resident: None reads SPARCH_AUDIO; unset or empty = the file loader, "resident" = a `ResidentAudioLoader` (every
+    rank keeps the whole split on its device); anything else is a ValueError."""
+    if resident is None:
+        resident = os.environ.get("SPARCH_AUDIO", "")
+    if resident not in ("", "resident"):
+        raise ValueError(f"SPARCH_AUDIO / resident: unknown value '{resident}' (unset or empty: file loader; "
+                         "'resident': the split's clips stay on the device)")
     if dataset_name not in ["hd", "sc"]:
         raise ValueError(f"Invalid dataset name {dataset_name}")
     if split not in ["train", "valid", "test"]:
@@ -231,15 +302,22 @@ def load_hd_or_sc(dataset_name, data_folder, split, batch_size, shuffle=True, us
     if workers != 0:
         raise ValueError("sparch_amd.dataloaders: the collate function computes the features on the GPU; use "
                          "workers=0 (the reference's default)")
-    if dataset_name == "hd":
-        if split in ["valid", "test"]:
-            split = "test"
-            logging.info("\nHD uses the same split for validation and testing.\n")
-        dataset = HeidelbergDigits(data_folder, split, use_augm, min_snr, max_snr, p_noise, device=device)
-    else:
-        split = {"train": "training", "valid": "validation", "test": "testing"}[split]
-        dataset = SpeechCommands(data_folder, split, use_augm, min_snr, max_snr, p_noise, device=device)
+    dataset, split = _dataset(dataset_name, data_folder, split, use_augm, min_snr, max_snr, p_noise, device)
     logging.info(f"Number of examples in {dataset_name} {split} set: {len(dataset)}")
+    if resident == "resident":
+        pack = _audio_pack_path(data_folder, dataset_name, split)
+        if os.path.exists(pack):
+            store = AudioStore.from_pack(pack, device=device)
+            if len(store) != len(dataset):
+                raise ValueError(f"{pack}: {len(store)} clips, the {split} set lists {len(dataset)}; write the pack "
+                                 "again (tools/pack_audio.py)")
+        else:
+            store = AudioStore.from_files(dataset.file_list, dataset.targets, device=device, sample_rate=SAMPLE_RATE)
+        logging.info(f"Clips of the {dataset_name} {split} set are resident on {store.device}: {len(store)} clips, "
+                     f"{store.nbytes / 2**20:.1f} MiB, {'int16' if store.int16 else 'fp32'} samples, from the "
+                     f"{'pack ' + pack if store.source == 'pack' else 'files'}"
+                     f"{', augmented per batch on the device' if dataset.augment is not None else ''}")
+        return ResidentAudioLoader(store, batch_size, shuffle, rank, world, seed, augment=dataset.augment)
     if world > 1:
         from torch.utils.data.distributed import DistributedSampler
 

@@ -30,6 +30,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from ..functional import EventStore, bin_events
+from ._index import _index_loader, _SampleIndices  # noqa: F401  (shared with the HD / SC loader)
 
 logger = logging.getLogger(__name__)
 
@@ -84,31 +85,6 @@ class SpikingDataset(Dataset):
         xs, _ = bin_events(times, units, self.nb_steps, self.nb_units, self.max_time, device=self.device)
         xlens = torch.tensor([self.nb_steps] * len(ys))
         return xs, xlens, torch.LongTensor(ys)
-
-
-class _SampleIndices(Dataset):
-    """Sample i is the number i: the DataLoader over it yields the index lists of an epoch's batches."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, index):
-        return index
-
-
-def _index_loader(dataset, batch_size, shuffle, rank, world, seed, collate_fn=None):
-    """The DataLoader of `load_shd_or_ssc`, for both of its loaders: same sampler, same arguments."""
-    if world > 1:
-        from torch.utils.data.distributed import DistributedSampler
-
-        sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed)
-        return DataLoader(dataset, batch_size=batch_size, collate_fn=collate_fn, sampler=sampler,
-                          num_workers=0, pin_memory=False)
-    return DataLoader(dataset, batch_size=batch_size, collate_fn=collate_fn, shuffle=shuffle,
-                      num_workers=0, pin_memory=False)
 
 
 class ResidentEventLoader:

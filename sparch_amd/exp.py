@@ -105,12 +105,12 @@ class Experiment:
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
-        # The HD / SC file loaders pad each batch to its own longest clip, so ranks hold different numbers of rows
+        # The HD / SC loaders (file and resident) pad each batch to its own longest clip, so ranks hold different numbers of rows
         # (B * T); the --sync_bn exchange (functional._Norm) gathers equal-sized statistics from every rank.  Refused
         # on every rank alike, before the first collective.
         if self.sync_bn and self.world > 1 and self.dataset_name in _AUDIO_SETS and not self.synthetic:
             raise ValueError("sparch_amd: --sync_bn needs the same number of time steps on every rank; the hd / sc "
-                             "file loaders give each batch the length of its longest clip. Run without --sync_bn "
+                             "loaders give each batch the length of its longest clip. Run without --sync_bn "
                              "(per-rank BatchNorm statistics) or with --synthetic 1.")
 
         self.init_exp_folders()

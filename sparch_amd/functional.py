@@ -1165,6 +1165,27 @@ def fbank_padded(wave, lengths, num_mel_bins=40):
 AUGM_FIELDS = 9  # SPARCH_AUGM_FIELDS
 
 
+def _augm_table(params, n_clips, sample_rate, what):
+    """The (n_clips, AUGM_FIELDS) table of draws as a contiguous host fp32 tensor, or ValueError for an entry out of
+    range (shared by `augment_padded` and `AudioStore.gather_augment`)."""
+    table = torch.as_tensor(params).detach().to("cpu", torch.float32).contiguous()
+    if tuple(table.shape) != (n_clips, AUGM_FIELDS):
+        raise ValueError(f"{what}: params must be ({n_clips}, {AUGM_FIELDS}), got {tuple(table.shape)}")
+    flags, u, ratio, rds = table[:, :4], table[:, 4], table[:, 5], table[:, 6:]
+    if not bool(((flags == 0) | (flags == 1)).all()):
+        raise ValueError(f"{what}: stage flags must be 0 or 1")
+    # u in [0, 1): random.random() rounded to fp32, which rounds up to 1.0 for the last 2^-25 of the range
+    if not bool(((u >= 0) & (u <= 1)).all()):
+        raise ValueError(f"{what}: the noise uniform must lie in [0, 1)")
+    if not bool(torch.isfinite(ratio).all()):
+        raise ValueError(f"{what}: the gain ratio must be finite")
+    if not bool(((rds >= 0) & (rds <= 100)).all()):
+        raise ValueError(f"{what}: reverberance, HF damping and room scale must lie in [0, 100]")
+    if not 8000 <= int(sample_rate) <= 48000:
+        raise ValueError(f"{what}: sample rate {sample_rate} outside 8000-48000 Hz")
+    return table
+
+
 def augment_padded(wave, lengths, params, noise_seed, min_snr, max_snr, sample_rate=16000):
     """Waveform augmentation of padded clips on the device (sparch_augment_padded): the reference's training-split
     transforms (torchaudio_augmentations' PolarityInversion, Noise, Gain and sox's reverb, nonspiking_datasets.py:71-78,
@@ -1191,21 +1212,7 @@ def augment_padded(wave, lengths, params, noise_seed, min_snr, max_snr, sample_r
         raise ValueError(f"augment_padded: {lens.numel()} lengths for {n_clips} clips")
     if n_clips and int(lens.max()) > ld:
         raise ValueError(f"augment_padded: a clip length {int(lens.max())} exceeds the row length {ld}")
-    table = torch.as_tensor(params).detach().to("cpu", torch.float32).contiguous()
-    if tuple(table.shape) != (n_clips, AUGM_FIELDS):
-        raise ValueError(f"augment_padded: params must be ({n_clips}, {AUGM_FIELDS}), got {tuple(table.shape)}")
-    flags, u, ratio, rds = table[:, :4], table[:, 4], table[:, 5], table[:, 6:]
-    if not bool(((flags == 0) | (flags == 1)).all()):
-        raise ValueError("augment_padded: stage flags must be 0 or 1")
-    # u in [0, 1): random.random() rounded to fp32, which rounds up to 1.0 for the last 2^-25 of the range
-    if not bool(((u >= 0) & (u <= 1)).all()):
-        raise ValueError("augment_padded: the noise uniform must lie in [0, 1)")
-    if not bool(torch.isfinite(ratio).all()):
-        raise ValueError("augment_padded: the gain ratio must be finite")
-    if not bool(((rds >= 0) & (rds <= 100)).all()):
-        raise ValueError("augment_padded: reverberance, HF damping and room scale must lie in [0, 100]")
-    if not 8000 <= int(sample_rate) <= 48000:
-        raise ValueError(f"augment_padded: sample rate {sample_rate} outside 8000-48000 Hz")
+    table = _augm_table(params, n_clips, sample_rate, "augment_padded")
     dev = wave.device
     # from pinned memory without blocking the host (the caching host allocator keeps the blocks until the copies
     # are done)
@@ -1419,10 +1426,10 @@ def _samples_sorted(times, offsets):
     return bool(ok.all())
 
 
-def _require_room(need, free, what):
+def _require_room(need, free, what, kind="event", env="SPARCH_EVENTS"):
     if need > free:
-        raise RuntimeError(f"{what}: the event store needs {need / 2**20:.1f} MiB on the device, only "
-                           f"{free / 2**20:.1f} MiB are free; train without SPARCH_EVENTS=resident")
+        raise RuntimeError(f"{what}: the {kind} store needs {need / 2**20:.1f} MiB on the device, only "
+                           f"{free / 2**20:.1f} MiB are free; train without {env}=resident")
 
 
 class EventStore:
@@ -1547,6 +1554,250 @@ class EventStore:
             return x, got["y"]
         got = self.gather(idx, nb_steps, dense=True)
         return got["dense"], got["y"]
+
+
+# ----------------------------------------------------------------------------- resident HD / SC audio
+AUDIO_PACK_KEYS = ("samples", "starts", "lengths", "labels")
+AUDIO_FLAC_CHUNK = 256  # FLAC clips decoded per launch while the arrays of a split are built
+
+
+def check_audio_arrays(a, what="audio store"):
+    """ValueError unless the four arrays of an audio store agree (host-side; the kernels trust them): samples int16
+    or float32, starts int64, lengths int32, labels int64, one entry per clip in the last three; every clip
+    [start, start + length) lies inside samples, and no two clips overlap."""
+    import numpy as np
+
+    for k in AUDIO_PACK_KEYS:
+        if k not in a:
+            raise ValueError(f"{what}: array '{k}' is missing")
+    x, s, n, y = (np.asarray(a[k]) for k in AUDIO_PACK_KEYS)
+    if x.dtype not in (np.int16, np.float32) or s.dtype != np.int64 or n.dtype != np.int32 or y.dtype != np.int64:
+        raise ValueError(f"{what}: dtypes must be int16/float32, int64, int32, int64; got "
+                         f"{x.dtype}, {s.dtype}, {n.dtype}, {y.dtype}")
+    if x.ndim != 1 or s.ndim != 1 or n.ndim != 1 or y.ndim != 1:
+        raise ValueError(f"{what}: the arrays must be one-dimensional")
+    if len(y) == 0:
+        raise ValueError(f"{what}: no clips")
+    if not len(s) == len(n) == len(y):
+        raise ValueError(f"{what}: starts, lengths and labels must have one length, found {len(s)}, {len(n)}, "
+                         f"{len(y)}")
+    if np.any(s < 0):
+        raise ValueError(f"{what}: clip {int(np.argmax(s < 0))} has a negative start")
+    if np.any(n < 0):
+        raise ValueError(f"{what}: clip {int(np.argmax(n < 0))} has a negative length")
+    end = s + n
+    if np.any(end > len(x)):
+        i = int(np.argmax(end > len(x)))
+        raise ValueError(f"{what}: clip {i} ends at sample {int(end[i])}, past the end of samples ({len(x)})")
+    live = np.flatnonzero(n > 0)                         # an empty clip overlaps nothing
+    live = live[np.argsort(s[live], kind="stable")]
+    clash = end[live][:-1] > s[live][1:]
+    if np.any(clash):
+        k = int(np.argmax(clash))
+        raise ValueError(f"{what}: clips {int(live[k])} and {int(live[k + 1])} overlap")
+    return {"samples": x, "starts": s, "lengths": n, "labels": y}
+
+
+def save_audio_pack(path, arrays):
+    """Write the pack file of a split: an uncompressed np.savez of samples, starts, lengths, labels."""
+    import numpy as np
+
+    a = check_audio_arrays(arrays, what=str(path))
+    with open(path, "wb") as f:  # a file object: np.savez would append ".npz" to a name
+        np.savez(f, **a)
+
+
+def load_audio_pack(path):
+    import numpy as np
+
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in AUDIO_PACK_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not an audio pack (no {', '.join(missing)})")
+        return check_audio_arrays({k: z[k] for k in AUDIO_PACK_KEYS}, what=str(path))
+
+
+def audio_arrays_from_files(file_list, targets, device="cuda", sample_rate=16000, chunk=AUDIO_FLAC_CHUNK):
+    """The clips `file_list` with labels `targets` as the four flat host arrays of an audio store, clip after clip
+    without gaps (the kernels load single samples: nothing to align).  samples is int16 PCM when every clip is
+    16-bit mono, else float32 in [-1, 1] for the whole split, each clip converted as the file loader's collate
+    converts it (`dataloaders.audio`: int16 / 2^15, FLAC x * 2^-(bps-1)).  WAV clips are read on the host; FLAC clips
+    are decoded on `device`, `chunk` clips per launch (`flac_decode_padded`), every chunk's error record and every
+    mono clip's STREAMINFO MD5 checked (FlacError naming the file).  A tree with FLAC clips needs a device: this
+    build decodes FLAC nowhere else (RuntimeError naming the first such file when none is visible).  Warns once when
+    a clip's sample rate is not `sample_rate` (nothing is resampled).  The files are read twice (lengths and sample
+    format first, samples second), so the host holds the flat array and one clip or FLAC chunk, not the split twice."""
+    import logging
+
+    import numpy as np
+
+    from .dataloaders.audio import FlacError, FlacStream, flac_md5_ok, read_clip
+
+    if len(file_list) != len(targets):
+        raise ValueError(f"audio store: {len(file_list)} files, {len(targets)} labels")
+    # two passes over the files, so that the host never holds more than the flat array and one clip (or one chunk of
+    # FLAC files): the first finds every clip's length and whether the split is 16-bit mono throughout
+    n = len(file_list)
+    lengths, flac, pcm16, warned = np.zeros(n, np.int32), [], True, False
+    for i, path in enumerate(file_list):
+        clip, rate = read_clip(path)
+        if rate != sample_rate and not warned:
+            warned = True
+            logging.getLogger(__name__).warning(
+                f"{path}: sample rate {rate} Hz; the features assume {sample_rate} Hz and nothing is resampled (as "
+                "in the reference). Warned once per dataset.")
+        if isinstance(clip, FlacStream):
+            flac.append(i)
+            lengths[i] = clip.info.total_samples
+            pcm16 = pcm16 and clip.info.bps == 16 and clip.info.channels == 1
+        else:
+            lengths[i] = len(clip)
+            pcm16 = pcm16 and clip.dtype == np.int16
+    if flac and (device is None or not torch.cuda.is_available()):
+        raise RuntimeError(f"{file_list[flac[0]]}: FLAC clips are decoded on the device (this build has no host "
+                           "FLAC decoder) and no HIP device is visible; build the audio store or its pack where "
+                           "one is")
+    starts = np.zeros(n, np.int64)
+    np.cumsum(lengths[:-1], dtype=np.int64, out=starts[1:])
+    samples = np.empty(int(lengths.sum(dtype=np.int64)), np.int16 if pcm16 else np.float32)
+
+    def reread(i):
+        clip, _ = read_clip(file_list[i])
+        m = clip.info.total_samples if isinstance(clip, FlacStream) else len(clip)
+        if m != lengths[i] or isinstance(clip, FlacStream) != (i in is_flac):
+            raise ValueError(f"{file_list[i]}: the file changed while the audio store was built")
+        return clip
+
+    is_flac = set(flac)
+    for i in range(n):
+        if i not in is_flac:
+            c = reread(i)
+            samples[starts[i]:starts[i] + lengths[i]] = (
+                c if pcm16 or c.dtype == np.float32 else c.astype(np.float32) / np.float32(2 ** 15))
+    for at in range(0, len(flac), chunk):  # (a FLAC stream this build decodes has at least one sample: ld >= 1)
+        part = flac[at:at + chunk]
+        streams = [reread(i) for i in part]
+        wave = torch.empty(len(part), int(lengths[part].max()), dtype=torch.int16 if pcm16 else torch.float32,
+                           device=device)
+        err = flac_decode_padded([c.data for c in streams], [c.info for c in streams], wave)
+        msg = flac_error_message(err.cpu(), [c.path for c in streams])  # load time: synchronous anyway
+        if msg:
+            raise FlacError(msg)
+        rows = wave.cpu().numpy()
+        for row, i, c in zip(rows, part, streams):
+            x = row[:lengths[i]]
+            if c.info.channels == 1 and not flac_md5_ok(x, c.info):
+                raise FlacError(f"{c.path}: decoded samples do not match the STREAMINFO MD5")
+            samples[starts[i]:starts[i] + lengths[i]] = x
+    return {"samples": samples, "starts": starts, "lengths": lengths, "labels": np.asarray(targets, np.int64)}
+
+
+class AudioStore:
+    """All clips of one HD / SC split on the device, uploaded once; `batch(idx, idx_host)` then builds the padded
+    log-mel batch of the file loader's collate from a device list of clip indices: one launch
+    (`sparch_audio_gather_fbank`), or two for an augmented split (`sparch_audio_gather_augment`, then
+    `sparch_fbank_padded_fwd`).  The lengths stay on the host too: T_max and the frame counts of a batch are computed
+    there, so a batch costs no synchronisation and no device-to-host read.
+
+    Built from the four flat arrays (`audio_arrays_from_files`, `load_audio_pack`), or through `from_files` /
+    `from_pack`; `source` says which, for the log."""
+
+    def __init__(self, arrays, device="cuda", source="arrays"):
+        import numpy as np
+
+        a = check_audio_arrays(arrays)
+        self.device = torch.device(device)
+        _require_device(torch.empty(0, device=self.device), "AudioStore")
+        self.n_clips, self.n_samples = len(a["labels"]), len(a["samples"])
+        self.int16 = a["samples"].dtype == np.int16
+        self.dtype = 1 if self.int16 else 0  # the kernels' `dtype` / `in_dtype`
+        self.source = source
+        self.nbytes = sum(int(v.nbytes) for v in a.values())
+        _require_room(self.nbytes, torch.cuda.mem_get_info(self.device)[0], "AudioStore", "audio", "SPARCH_AUDIO")
+        # an empty sample array still needs an address for the kernels' argument check
+        x = a["samples"] if self.n_samples else np.zeros(1, a["samples"].dtype)
+        self.samples = torch.from_numpy(x).to(self.device)
+        self.starts = torch.from_numpy(a["starts"]).to(self.device)
+        self.lengths = torch.from_numpy(a["lengths"]).to(self.device)
+        self.labels = torch.from_numpy(a["labels"]).to(self.device)
+        self.lengths_host = torch.from_numpy(a["lengths"].astype(np.int64))
+
+    @classmethod
+    def from_files(cls, file_list, targets, device="cuda", **kw):
+        return cls(audio_arrays_from_files(file_list, targets, device=device, **kw), device=device, source="files")
+
+    @classmethod
+    def from_pack(cls, path, device="cuda"):
+        return cls(load_audio_pack(path), device=device, source="pack")
+
+    def __len__(self):
+        return self.n_clips
+
+    def _idx(self, idx, what):
+        _require_device(idx, "idx")
+        if idx.dtype != torch.int64 or idx.ndim != 1 or idx.numel() == 0 or not idx.is_contiguous():
+            raise ValueError(f"AudioStore.{what}: idx must be a non-empty contiguous 1-D int64 tensor")
+        return idx.numel()
+
+    def gather_fbank(self, idx, n_frames, num_mel_bins=40):
+        """(feats (B, n_frames, num_mel_bins) fp32, y (B,) int64) on the device for the device int64 index list
+        `idx`: row b holds the frames of clip idx[b] as `fbank_padded` gives them, then exact zeros; an index outside
+        the store gives a zero row and label -1."""
+        B = self._idx(idx, "gather_fbank")
+        out = torch.empty(B, n_frames, num_mel_bins, dtype=torch.float32, device=self.device)
+        y = torch.empty(B, dtype=torch.int64, device=self.device)
+        tok = timer.start(f"audio_gather_fbank[{B}x{n_frames}]")
+        check(lib.sparch_audio_gather_fbank(ptr(self.samples), self.dtype, ptr(self.starts), ptr(self.lengths),
+                                            ptr(self.labels), self.n_clips, ptr(idx), B, n_frames, num_mel_bins,
+                                            ptr(out), ptr(y), _stream()), "sparch_audio_gather_fbank")
+        timer.stop(tok)
+        return out, y
+
+    def gather_augment(self, idx, ld, params, noise_seed, min_snr, max_snr, sample_rate=16000):
+        """(rows (B, ld) fp32, lengths (B,) int32, y (B,) int64) on the device: row b holds clip idx[b] (its first
+        ld samples) augmented as `augment_padded` augments row b of a batch of those clips, same table, same seed; it
+        is not written behind the clip.  params: the (B, AUGM_FIELDS) host table of `draw_augmentation`."""
+        B = self._idx(idx, "gather_augment")
+        table = _augm_table(params, B, sample_rate, "AudioStore.gather_augment")
+        if not 0 < int(ld) <= 2 ** 31 - 1:
+            raise ValueError(f"AudioStore.gather_augment: row length {ld} out of range")
+        # from pinned memory without blocking the host (the caching host allocator keeps the block until the copy
+        # is done)
+        table_dev = table.pin_memory().to(self.device, non_blocking=True)
+        out = torch.empty(B, ld, dtype=torch.float32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        y = torch.empty(B, dtype=torch.int64, device=self.device)
+        tok = timer.start(f"audio_gather_augment[{B}x{ld}]")
+        check(lib.sparch_audio_gather_augment(ptr(self.samples), self.dtype, ptr(self.starts), ptr(self.lengths),
+                                              ptr(self.labels), self.n_clips, ptr(idx), B, ld, ptr(table_dev),
+                                              float(min_snr), float(max_snr), int(noise_seed) & (2 ** 64 - 1),
+                                              int(sample_rate), ptr(out), ptr(lens), ptr(y), _stream()),
+              "sparch_audio_gather_augment")
+        timer.stop(tok)
+        return out, lens, y
+
+    def batch(self, idx, idx_host, augment=None, num_mel_bins=40, sample_rate=16000):
+        """(xs (B, T_max, num_mel_bins) on the device, xlens (B,) host int64 frame counts, ys (B,) on the device): the
+        batch the file loader's collate makes of the clips `idx_host` (host int64; `idx` is the same list on the
+        device).  augment: None, or (params, noise_seed, min_snr, max_snr) of `draw_augmentation`.  Raises the
+        ValueError of `fbank_padded` when no clip of the batch reaches one frame."""
+        n = self.lengths_host[idx_host]
+        frames = torch.where(n < 400, torch.zeros_like(n), 1 + torch.div(n - 400, 160, rounding_mode="floor"))
+        n_frames = int(frames.max())
+        if n_frames == 0:
+            raise ValueError("fbank_padded: no clip is long enough for one frame (400 samples)")
+        if augment is None:
+            xs, ys = self.gather_fbank(idx, n_frames, num_mel_bins)
+            return xs, frames, ys
+        params, noise_seed, min_snr, max_snr = augment
+        B, ld = idx.numel(), int(n.max())
+        rows, lens, ys = self.gather_augment(idx, ld, params, noise_seed, min_snr, max_snr, sample_rate)
+        xs = torch.empty(B, n_frames, num_mel_bins, dtype=torch.float32, device=self.device)
+        tok = timer.start(f"fbank_padded[{B}x{ld}]")
+        check(lib.sparch_fbank_padded_fwd(B, ld, ptr(lens), n_frames, num_mel_bins, 0, ptr(rows), ptr(xs), _stream()),
+              "sparch_fbank_padded_fwd")
+        timer.stop(tok)
+        return xs, frames, ys
 
 
 # ----------------------------------------------------------------------------- f-4: non-spiking baselines
