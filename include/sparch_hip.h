@@ -256,7 +256,9 @@ int sparch_layernorm_bwd(int M, int H, int Hn, const float* dy, const float* x, 
  *   u_save, w_save (Bp,T,H) in cell time order; needed by the backward (NULL => not saved).
  *   spike_count (H*dirs) uint32: number of spikes surviving dropout per output feature;
  *           firing rate = count * keep_scale / (B*T)  (snns.py:174 after 278).
- *   Dropout: keep iff hash(seed, output element index) >= p; kept values scale by 1/(1-p).
+ *   Dropout: keep iff hash(seed, output element index) >= p; kept values scale by 1/(1-p).  The index is the
+ *   element's position in the (B,T,H*dirs) tensor THIS launch writes: a caller that runs a layer zero-padded to a
+ *   wider H gets the padded tensor's mask (restated in numpy, padding included: tests/dropout_numpy.py).
  *   `seed` (every entry point that takes one): the 63-bit seed itself, or SPARCH_SEED_IN_MEMORY | the device
  *   address of a uint64 holding it — for a step captured in a HIP graph, whose arguments are frozen.
  * ---------------------------------------------------------------------------------- */

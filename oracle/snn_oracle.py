@@ -154,8 +154,10 @@ def hidden_layer(kind, x, p, prefix, init, *, normalization="batchnorm",
     """{LIF,adLIF,RLIF,RadLIF}Layer.forward (snns.py:249-280, 386-417, 521-552,
     663-694).  `init` = dict(u0, s0[, w0]) of shape (B', H) with B' = B*(1+bidir).
     `drop_mask` (B, T, H*(1+bidir)), already scaled by 1/(1-p), stands in for
-    nn.Dropout (278): device RNG streams cannot match, so parity runs use p=0
-    and pass None."""
+    nn.Dropout (278) as a constant.  torch's own RNG stream cannot be matched, but
+    the HIP kernels' mask is a pure function of (seed, output element index):
+    tests/dropout_numpy.py restates it, so a parity run with dropout on passes
+    that mask here (None = no dropout)."""
     if bidirectional:  # 252-254: time-flipped copy stacked on the batch axis
         x = torch.cat([x, x.flip(1)], dim=0)
     Wx = F.linear(x, p[prefix + "W.weight"], p.get(prefix + "W.bias"))  # 261
@@ -190,7 +192,8 @@ def snn_forward(x, p, *, neuron_type, num_layers, init_states, normalization="ba
     (batch, time) of the concatenated post-dropout hidden outputs (171-174).
     `p` is keyed like the reference state_dict ('snn.{i}.alpha', ...);
     `init_states[i]` is dict(u0, s0[, w0]) for hidden layer i and dict(u0) for
-    the readout.  `spikes_out` (a list) receives every hidden layer's output."""
+    the readout.  `spikes_out` (a list) receives every hidden layer's output.
+    `drop_masks[i]` is hidden layer i's dropout mask (see hidden_layer), or None."""
     if x.ndim == 4:  # 160-162
         x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
     elif x.ndim != 3:

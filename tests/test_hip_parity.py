@@ -10,7 +10,9 @@ Stated tolerances (fp32):
     so a membrane potential within 1 ulp of the threshold may flip a spike and the
     trajectories then diverge: spike mismatch fraction <= 2e-3 on the fixtures;
   * gradients: max-abs error <= 2e-4 of the tensor's max-abs (+1e-6) when spikes agree;
-  * GEMM: |err| <= 2e-6 * sum_k |a||b|  (exact fp32 fmaf chain vs fp64 reference).
+  * GEMM: |err| <= 2e-6 * sum_k |a||b|  (exact fp32 fmaf chain vs fp64 reference);
+  * dropout: the in-kernel mask is restated in numpy (tests/dropout_numpy.py) and handed to the oracle as a
+    constant, so runs with dropout on keep the bars above (tests/test_dropout_rate_backward_gpu.py).
 """
 import numpy as np
 import pytest
@@ -1038,8 +1040,8 @@ def test_readout_cell_vs_reference_golden():
 
 
 # ------------------------------------------------------------------------------------ whole SNN
-def _build(sp, cfg, params):
-    net = sp.SNN((cfg["B"], None, cfg["C"]), cfg["layer_sizes"], neuron_type=cfg["neuron_type"], dropout=0.0,
+def _build(sp, cfg, params, dropout=0.0):
+    net = sp.SNN((cfg["B"], None, cfg["C"]), cfg["layer_sizes"], neuron_type=cfg["neuron_type"], dropout=dropout,
                  normalization=cfg["normalization"], use_bias=cfg["use_bias"], bidirectional=cfg["bidirectional"],
                  use_readout_layer=cfg["use_readout_layer"])
     missing = net.load_state_dict(params, strict=True)
@@ -1106,12 +1108,16 @@ def test_snn_train_step_vs_reference_golden(sp, name):
         assert np.abs(rates_e.cpu().numpy() - z["rates_eval"]).mean() <= 0.02
 
 
-def _run_dyadic(sp, name, monkeypatch):
+def _run_dyadic(sp, name, monkeypatch, dropout=0.0, seeds=None, loss_kw=None):
     """One training step of a dyadic fixture's network on the HIP path, fed the fixture's initial states in
-    the reference's draw order.  Returns (cfg, z, per-layer spikes, out, loss, net)."""
+    the reference's draw order.  Returns (cfg, z, per-layer spikes, out, loss, net).  With dropout, `seeds[k]` is
+    the dropout seed hidden layer k hands its kernels; `loss_kw` goes to oracle.train_step_loss (the regulariser)."""
     Fn = _Fn()
     cfg, x, y, params, init, z = snn_case(name)
-    net = _build(sp, cfg, params).train()
+    net = _build(sp, cfg, params, dropout).train()
+    if seeds is not None:
+        for lay, seed in zip(list(net.snn)[:-1], seeds):
+            lay._dropout_seed = lambda device, seed=seed: seed
     order = []
     for st in init:
         order += [st[k] for k in ("u0", "w0", "s0") if k in st]
@@ -1133,7 +1139,7 @@ def _run_dyadic(sp, name, monkeypatch):
         lay.forward_with_rate = wrapped
     out, rates = net(x.to(DEV))
     Fn.check_status()
-    loss = orc.train_step_loss(out, rates, y.to(DEV))
+    loss = orc.train_step_loss(out, rates, y.to(DEV), **(loss_kw or {}))
     loss.backward()
     Fn.check_status()
     return cfg, z, rec, out, loss, net
@@ -1413,6 +1419,35 @@ def test_dropout_statistics_and_backward_mask_consistency(sp):
     assert abs(kept - 0.75) < 0.02, kept
     assert not bool((s_drop > 0)[~fired].any())
     np.testing.assert_allclose(rate.cpu().numpy(), s_drop.mean(dim=(0, 1)).cpu().numpy(), rtol=1e-5, atol=1e-7)
+    # ... and the backward's regenerated mask is the forward's.  With a known seed the mask is the numpy
+    # restatement's (tests/dropout_numpy.py), exactly, in the forward; and since s_drop = s_full * mask, the layer's
+    # backward under dropout must equal the dropout-free backward fed g * mask — bit for bit (the kernels form
+    # (g + 0) * k, then the same launches on the same values), at fired and non-fired elements alike.
+    from tests import dropout_numpy as dn
+    seed = 0x0BADC0DE_12345678
+    mask = torch.from_numpy(dn.keep_mask(seed, (B, T, H), 0.25)).to(DEV)
+    lay._dropout_seed = lambda device: seed
+    g_s = torch.randn(B, T, H, generator=torch.Generator().manual_seed(4)).to(DEV)
+
+    def grads(p_drop, g_up):
+        lay.dropout = p_drop
+        lay.zero_grad()
+        xd = x.clone().requires_grad_(True)
+        torch.manual_seed(10)
+        s, _ = lay.forward_with_rate(xd)
+        (s * g_up).sum().backward()
+        _Fn().check_status()
+        return s.detach(), xd.grad, {k: v.grad.clone() for k, v in lay.named_parameters()}
+
+    s_d, dx_d, g_d = grads(0.25, g_s)
+    s_f, dx_f, g_f = grads(0.0, g_s * mask)
+    assert torch.equal(s_d, s_f * mask) and float(s_d.sum()) > 0
+    assert int(((s_f > 0) & (mask == 0)).sum()) >= 200 and int(((s_f > 0) & (mask > 0)).sum()) >= 200
+    assert torch.equal(dx_d, dx_f), float((dx_d - dx_f).abs().max())
+    for k in g_d:
+        assert torch.equal(g_d[k], g_f[k]), (k, float((g_d[k] - g_f[k]).abs().max()))
+    s_w, dx_w, _ = grads(0.0, g_s * torch.from_numpy(dn.keep_mask(seed + 1, (B, T, H), 0.25)).to(DEV))
+    assert not torch.equal(dx_w, dx_f)  # (the comparison can tell masks apart)
 
 
 # ------------------------------------------------------------------------------------ mel front-end
