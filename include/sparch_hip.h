@@ -36,10 +36,24 @@ extern "C" {
 
 #define SPARCH_OK 0
 #define SPARCH_EINVAL (-1)      /* bad shape / null pointer / unsupported size        */
-#define SPARCH_EALIGN (-2)      /* pointer or leading dimension not 16-byte aligned   */
+#define SPARCH_EALIGN (-2)      /* a pointer that MUST be 16-byte aligned is not (see below) */
 #define SPARCH_EWORKSPACE (-3)  /* workspace too small (see *_workspace_bytes)        */
 #define SPARCH_ELAUNCH (-4)     /* HIP reported a launch error                        */
 #define SPARCH_ETIMEOUT (-5)    /* reported through a status word: in-kernel wait gave up */
+
+/* Alignment and leading dimensions (pinned by tests/test_gemm_layouts_gpu.py).
+ *   - The matrix products of G1 (every sparch_gemm*) take ANY pointer alignment and any leading dimension >= the row
+ *     width (smaller: SPARCH_EINVAL), independently per operand; none of them returns SPARCH_EALIGN.  An operand
+ *     whose base is 16-byte aligned and whose ld is a multiple of 16 bytes (ld % 4 == 0 for fp32, ld % 8 == 0 for a
+ *     uint16 plane) is staged with 16-byte loads — also when its row width is not (the tail of a row is then read
+ *     element by element; nothing behind the row's last element is read) — any other operand with scalar loads: same
+ *     results, slower.  The pipelined kernels additionally need whole tiles and K % 32 == 0; pre-split planes
+ *     (_wp / _pp / _ap) are read only where those kernels apply and share the fp32 operand's ld, plane p of an R-row
+ *     operand starting p * R * ld elements behind the first.  C is written in columns 0..N-1 of each row only.
+ *   - SPARCH_EALIGN is returned (and nothing launched) by sparch_split3 (x, planes), sparch_plane_bf16_exact and
+ *     sparch_expand_counts_u8 (plane; an ldp that is not a multiple of 8 is SPARCH_EINVAL), and by the element-wise /
+ *     scan kernels of G2-G7 and f-4 for their tensor arguments (cell, norm, act, softmax_sum entry points).
+ *   - A workspace smaller than its query: SPARCH_EWORKSPACE, nothing launched. */
 
 /* The status word of a device: FOUR uint32 the caller keeps zeroed.  [0] != 0: an in-kernel wait of a persistent
  * recurrent launch gave up (SPARCH_ETIMEOUT) and the results of that training step are invalid;
@@ -153,7 +167,8 @@ int sparch_gemm6_tn(int M, int N, int K, const float* A, int lda, const float* B
 /* Weight operands pre-split into their bf16 planes.  A spiking layer's W (H x K) is the B operand of its
  * projection (snns.py:261, x W^T) and of backward's dx = dWx W; both kernels would re-convert the same
  * tile of W in every workgroup that stages it (250 row tiles at B*T = 32000).  sparch_split3 writes the
- * exact truncation split x = p0 + p1 + p2 once: planes[p*n + i], bf16 bit patterns, n % 8 == 0.  The _wp
+ * exact truncation split x = p0 + p1 + p2 once: planes[p*n + i], bf16 bit patterns, n % 8 == 0 (else SPARCH_EINVAL),
+ * x and planes 16-byte aligned (else SPARCH_EALIGN).  The _wp
  * entries take B together with those planes (same layout and ldb; B_planes may be NULL) and return the
  * same bits as sparch_gemm_spike16_nt / sparch_gemm6_nn: where the pipelined kernel applies (K % 32 == 0,
  * ldb % 8 == 0, full tiles) it copies the planes into LDS, elsewhere it converts B as before.        */
@@ -166,7 +181,8 @@ int sparch_gemm6_nn_wp(int M, int N, int K, const float* A, int lda, const float
 
 /* First-layer input (snns.py:261 on the network input): SHD/SSC-style binned spike counts are small
  * integers, exactly representable in bf16, but the library cannot know that on the host.
- * sparch_flag_bf16_exact sets *flag (device uint32) to 1 iff every element of x is bf16-exact; the
+ * sparch_flag_bf16_exact sets *flag (device uint32) to 1 iff every element of x is bf16-exact — and x is 16-byte
+ * aligned with n % 4 == 0: otherwise the flag is 0 without looking at x (the safe answer: the six-term kernel) —; the
  * _auto_ GEMMs then enqueue BOTH the single-plane exact kernel and the 6-term kernel, each gated on
  * the device by *flag, so exactly one runs — no host round trip.  nt: A is the flagged operand;
  * tn: B is (dW = dWx^T x).                                                                       */
@@ -179,7 +195,7 @@ int sparch_gemm_auto_tn(int M, int N, int K, const float* A, int lda, const floa
                         const uint32_t* b_exact_flag, void* ws, size_t ws_bytes, void* stream, int precision);
 /* The same with the flagged operand's bf16 plane made by the check itself: sparch_plane_bf16_exact writes
  * plane[m][k] = upper 16 bits of x[m][k] (the exact value whenever the flag stays 1; rows of ldp >= K elements,
- * ldp % 8 == 0, columns K.. zero) in the pass that computes the flag, and the _auto16_ GEMMs read that plane
+ * ldp % 8 == 0, ALL ldp columns of a row are written, K.. with zeros; plane 16-byte aligned, x and ldx >= K free) in the pass that computes the flag, and the _auto16_ GEMMs read that plane
  * (2 bytes per element through the spike-plane kernels) when *flag == 1, the fp32 operand through the six-term
  * kernels otherwise.  One pass over the network input per step instead of three. */
 int sparch_plane_bf16_exact(int M, int K, const float* x, int ldx, uint16_t* plane, int ldp, uint32_t* flag,
