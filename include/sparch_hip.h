@@ -287,6 +287,18 @@ int sparch_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
                     uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
                     int save_bf16, uint32_t* spike_count, void* stream);
 
+/* Streaming inference: the same cells over one CHUNK (B,T,H) of a longer sequence, state in, state out, nothing
+ * saved.  u / w / s (B,H) hold the state the previous chunk ended in (for the first chunk: the initial states) and
+ * are updated in place; s is the last step's raw spikes.  Chunks of any length >= 1, fed in order, give bit for bit
+ * the spikes of one call over the whole sequence: the arithmetic of a step does not know where a chunk ends.
+ * One direction and no dropout (a stream is causal and runs in eval): dirs != 1, p_drop != 0, a NULL state
+ * pointer or a recurrent kind are SPARCH_EINVAL.  spike_count is ADDED to (the caller owns and clears it).     */
+int sparch_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                           const float* scale, const float* shift, const float* alpha,
+                           const float* beta, const float* a, const float* b, float* u, float* w,
+                           float* s, float theta, float p_drop, float* s_out, uint16_t* s16_out,
+                           uint32_t* spike_count, void* stream);
+
 /* save_bf16 (forward and backward alike): u_save / w_save are (Bp,T,H) bf16 instead of fp32 — half the bytes
  * of the two largest tensors a layer keeps for its backward pass.  The stored membrane potential is rounded
  * so that the backward's three discrete decisions (spike u-theta > 0, box-car edges) are EXACTLY the fp32
@@ -344,6 +356,19 @@ int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx
                         uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save,
                         void* w_save, int save_bf16, uint32_t* spike_count, void* chan,
                         size_t chan_bytes, uint32_t* status, int steps_per_launch, void* stream, int precision);
+/* Streaming form of sparch_rec_cell_fwd (see sparch_cell_stream_fwd): one chunk (B,T,H), no save tensors.
+ *   u, w, s (B,H)     state, in place; s = the last step's raw spikes (fp32)
+ *   s16_state (B,H)   the same spikes as a bf16 0/1 plane, written behind the chunk's last step
+ *   rec0 (B,H)        s * Vmasked for the state the chunk starts from, by the caller: a dense product for drawn
+ *                     initial states, the exact spike product on s16_state from the second chunk on
+ *   chan              sparch_rec_chan_bytes(B,T,H) bytes for THIS chunk's T; steps_per_launch as above.          */
+int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                               const float* scale, const float* shift, const float* alpha,
+                               const float* beta, const float* a, const float* b,
+                               const float* vpack, const float* rec0, float* u, float* w, float* s,
+                               uint16_t* s16_state, float theta, float p_drop, float* s_out,
+                               uint16_t* s16_out, uint32_t* spike_count, void* chan, size_t chan_bytes,
+                               uint32_t* status, int steps_per_launch, void* stream, int precision);
 /* Backward: each step's 32x32 dWx tile is handed to the other workgroups through `chan`.
  * s_prev16 (Bp,T,H) receives s_{t-1} as a bf16 plane (binary for t >= 1, a zero row at
  * t = 0: the non-binary s0 term is added by the caller) for dV = s_prev^T * dWx
@@ -375,6 +400,15 @@ int sparch_rec_cell_step_fwd(int kind, int B, int dirs, int T, int H, int t, con
                              float p_drop, uint64_t seed, float* s_out, uint16_t* s16_out,
                              float* u_save, float* w_save, uint32_t* spike_count,
                              uint16_t* s_step16, void* stream);
+/* Streaming form of the forward step (H > 1024): step t of a chunk (B,T,H); u / w / s (B,H) are read and written
+ * in place by every step, s16_state (B,H) receives the step's spikes (the operand of the next product, which for
+ * t = 0 is the caller's product on the state the chunk starts from).  Nothing the size of the stream is kept. */
+int sparch_rec_cell_step_stream_fwd(int kind, int B, int dirs, int T, int H, int t, const float* Wx,
+                                    const float* scale, const float* shift, const float* alpha,
+                                    const float* beta, const float* a, const float* b, const float* rec,
+                                    float* u, float* w, float* s, uint16_t* s16_state, float theta,
+                                    float p_drop, float* s_out, uint16_t* s16_out, uint32_t* spike_count,
+                                    void* stream);
 int sparch_rec_cell_step_bwd(int kind, int B, int dirs, int T, int H, int t, const float* g_out,
                              const float* g_rate, const float* u_save, const float* w_save,
                              const float* alpha, const float* beta, const float* a, const float* b,
@@ -407,6 +441,11 @@ int sparch_colsum(int M, int H, const float* x, float* out, void* ws, size_t ws_
 int sparch_readout_fwd(int B, int T, int C, const float* Wx, const float* scale,
                        const float* shift, const float* alpha, const float* u0, float* out,
                        float* u_save, void* stream);
+/* Streaming form: u (B,C) is the membrane state and out (B,C) the running sum, both in place.  The accumulator is
+ * carried IN, so the one sequential sum over t continues across chunks (adding per-chunk sums rounds differently):
+ * out after the last chunk equals sparch_readout_fwd's over the whole sequence bit for bit.                    */
+int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, const float* scale,
+                              const float* shift, const float* alpha, float* u, float* out, void* stream);
 int sparch_readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x,
                        const float* bn_mean, const float* bn_invstd, const float* u_save,
                        const float* alpha, const float* u0, float* dWx, float* dalpha_ws,

@@ -10,5 +10,6 @@ from .functional import (augment_padded, bin_events, check_status, compute_dtype
                          fbank_padded, flac_decode_padded, set_compute_dtype)
 from .snns import (SNN, LIFLayer, RLIFLayer, RadLIFLayer, ReadoutLayer,  # noqa: F401
                    SpikeFunctionBoxcar, adLIFLayer)
+from .streaming import StreamingFbank, StreamingSNN  # noqa: F401
 
 __version__ = "0.1.0"

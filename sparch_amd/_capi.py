@@ -68,6 +68,8 @@ PROTOTYPES = {
     "sparch_layernorm_bwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "sparch_cell_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P,
                                 c_float, c_float, c_uint64, P, P, P, P, c_int, P, P]),
+    "sparch_cell_stream_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P,
+                                       c_float, c_float, P, P, P, P]),
     "sparch_cell_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
                                 c_float, c_float, c_uint64, P, P, P, P, P, P]),
     "sparch_vpack_bytes": (c_size_t, [c_int]),
@@ -78,16 +80,21 @@ PROTOTYPES = {
     "sparch_rec_chan_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sparch_rec_cell_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P,
                                     c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, c_size_t, P, c_int, P, c_int]),
+    "sparch_rec_cell_stream_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                           c_float, c_float, P, P, P, P, c_size_t, P, c_int, P, c_int]),
     "sparch_rec_cell_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
                                     c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_size_t, P, c_int, P, c_int]),
     "sparch_rec_cell_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                          c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
+    "sparch_rec_cell_step_stream_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P,
+                                                P, P, P, c_float, c_float, P, P, P, P]),
     "sparch_rec_cell_step_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                          P, c_float, c_float, c_uint64, P, P, P, P, P, P, P, P]),
     "sparch_colsum_clamped": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "sparch_add_halves": (c_int, [c_size_t, P, P, P]),
     "sparch_colsum": (c_int, [c_int, c_int, P, P, P, c_size_t, P]),
     "sparch_readout_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
+    "sparch_readout_stream_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "sparch_readout_bwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
     "sparch_fbank_frames": (c_int, [c_int]),
     "sparch_fbank_fwd": (c_int, [c_int, c_int, c_int, P, P, P]),

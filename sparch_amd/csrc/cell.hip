@@ -136,7 +136,9 @@ template <> struct SavedVec<1, true> {
 // SAVE: 0 = no saved states (eval), 1 = fp32, 2 = bf16.  SOUT / S16OUT: the fp32 spike tensor / the bf16 plane.
 // DROP: dropout is on (a template parameter: a scalar branch around the mask's hash inside the loop makes hipcc's
 // wait-count pass fall back to `s_waitcnt vmcnt(0)` at the join, once per trip — the ring would drain every D steps)
-template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP>
+// STATE (streaming, sparch_cell_stream_fwd): u0 / w0 / s0 are the stream's (Bp,H) state buffers — read here as ever,
+// and written back from the registers behind the last step, so that the next chunk's launch continues the sequence.
+template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP, bool STATE = false>
 __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
     constexpr int D = pipe_depth(VEC, 1 + (SOUT ? 1 : 0) + (S16OUT ? 1 : 0) + (SAVE ? 1 + (ADAPT ? 1 : 0) : 0));
     const int HQ = c.H / VEC;
@@ -241,6 +243,12 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
             if (cnt[e]) atomicAdd(c.spike_count + (size_t)d * H + h + e, cnt[e]);
+    }
+    if constexpr (STATE) {  // each thread owns its elements of the state for the whole launch: in place
+        const size_t o = (size_t)bp * H + h;
+        stv<VEC>(const_cast<float*>(c.u0) + o, u);
+        stv<VEC>(const_cast<float*>(c.s0) + o, s);
+        if (ADAPT) stv<VEC>(const_cast<float*>(c.w0) + o, w);
     }
 }
 
@@ -441,12 +449,16 @@ __device__ __forceinline__ float ro_softmax_row(float* row, int C) {  // in plac
     return den;
 }
 
+// STREAM (sparch_readout_stream_fwd): `u_io` (B,C) is the membrane state, read in place of u0 and written back behind
+// the last step, and `out` comes in holding the running sum: the accumulator CONTINUES the one sequential sum over t
+// (per-chunk sums added afterwards would round differently).
+template <bool STREAM>
 __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C, int rows, const float* __restrict__ Wx,
                                                             const float* __restrict__ scale,
                                                             const float* __restrict__ shift,
                                                             const float* __restrict__ alpha,
                                                             const float* __restrict__ u0, float* __restrict__ out,
-                                                            float* __restrict__ u_save) {
+                                                            float* __restrict__ u_save, float* u_io) {
     __shared__ float us[RO_FWD_FLOATS];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -458,7 +470,8 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
     const bool has_bn = scale != nullptr;
     const float sc = has_bn ? scale[cp] : 1.0f, sh = has_bn ? shift[cp] : 0.0f;
-    float u = u0[(size_t)b * C + cp], acc = 0.f;
+    float u = STREAM ? u_io[(size_t)b * C + cp] : u0[(size_t)b * C + cp];
+    float acc = STREAM ? out[(size_t)b * C + cp] : 0.f;
     const __amdgpu_buffer_rsrc_t rx = ro_row(Wx, (size_t)T * C, b), ru = ro_row(u_save, (size_t)T * C, b);
     for (int c0 = 0; c0 < T; c0 += rows) {
         const int len = min(rows, T - c0), n = len * C;
@@ -538,6 +551,7 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
         ro_barrier();
     }
     if (act) out[(size_t)b * C + cc] = acc;
+    if (STREAM && act) u_io[(size_t)b * C + cc] = u;
 }
 
 // Backward of the above.  With p_t = softmax(u_t) and g = dL/dout:
@@ -705,6 +719,29 @@ int launch_cell(bool bwd, CellArgs& c, hipStream_t st) {
     return SPARCH_OK;
 }
 
+// the streaming forward: no saved states, no dropout, the end state written back (same thread mapping as launch_cell)
+template <bool ADAPT>
+int launch_cell_stream(const CellArgs& c, hipStream_t st) {
+    const long long work = (long long)c.B * c.H;
+    const bool vec4 = (c.H % 4 == 0) && work >= (long long)256 * 8 * 64 * 4;
+    const long long threads = vec4 ? work / 4 : work;
+    const unsigned blocks = (unsigned)((threads + 255) / 256);
+    auto go = [&](auto vec, auto sout, auto s16out) {
+        hipLaunchKernelGGL((cell_fwd_pipe_kernel<ADAPT, decltype(vec)::value, 0, decltype(sout)::value,
+                                                 decltype(s16out)::value, false, true>),
+                           dim3(blocks), dim3(256), 0, st, c);
+    };
+    auto outs = [&](auto vec) {
+        if (c.s_out && c.s16_out) go(vec, std::true_type{}, std::true_type{});
+        else if (c.s_out) go(vec, std::true_type{}, std::false_type{});
+        else go(vec, std::false_type{}, std::true_type{});
+    };
+    if (vec4) outs(std::integral_constant<int, 4>{});
+    else outs(std::integral_constant<int, 1>{});
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
 bool ptrs_aligned(std::initializer_list<const void*> ps) {
     for (const void* p : ps)
         if (p && !aligned16(p)) return false;
@@ -739,6 +776,30 @@ extern "C" int sparch_cell_fwd(int kind, int B, int dirs, int T, int H, const fl
     c.save16 = save_bf16 != 0; c.spike_count = spike_count;
     return adapt ? launch_cell<true>(false, c, (hipStream_t)stream)
                  : launch_cell<false>(false, c, (hipStream_t)stream);
+}
+
+extern "C" int sparch_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                      const float* scale, const float* shift, const float* alpha,
+                                      const float* beta, const float* a, const float* b, float* u, float* w,
+                                      float* s, float theta, float p_drop, float* s_out, uint16_t* s16_out,
+                                      uint32_t* spike_count, void* stream) {
+    SPARCH_ENTER();
+    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_ADLIF;
+    // a stream is causal (one direction) and runs in eval (no dropout); the state is mandatory
+    if (dirs != 1 || p_drop != 0.0f || !u || !s || (adapt && !w)) return SPARCH_EINVAL;
+    if (B <= 0 || T <= 0 || H <= 0 || !Wx || !alpha || (!s_out && !s16_out)) return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b)) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!ptrs_aligned({Wx, u, w, s, s_out})) return SPARCH_EALIGN;
+    CellArgs c{};
+    c.B = B; c.dirs = 1; c.T = T; c.H = H;
+    c.Wx = Wx; c.scale = scale; c.shift = shift;
+    c.alpha = alpha; c.beta = beta; c.a = a; c.b = b;
+    c.u0 = u; c.w0 = w; c.s0 = s;
+    c.theta = theta; c.p_drop = 0.0f; c.inv_keep = 1.0f;
+    c.s_out = s_out; c.s16_out = s16_out; c.spike_count = spike_count;
+    return adapt ? launch_cell_stream<true>(c, (hipStream_t)stream) : launch_cell_stream<false>(c, (hipStream_t)stream);
 }
 
 extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
@@ -777,8 +838,21 @@ extern "C" int sparch_readout_fwd(int B, int T, int C, const float* Wx, const fl
     SPARCH_ENTER();
     if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
     if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    hipLaunchKernelGGL(readout_fwd_kernel, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
-                       ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, u0, out, u_save);
+    hipLaunchKernelGGL(readout_fwd_kernel<false>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                       ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+extern "C" int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, const float* scale,
+                                         const float* shift, const float* alpha, float* u, float* out,
+                                         void* stream) {
+    SPARCH_ENTER();
+    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u || !out) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    hipLaunchKernelGGL(readout_fwd_kernel<true>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                       ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, (const float*)nullptr, out,
+                       (float*)nullptr, u);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }

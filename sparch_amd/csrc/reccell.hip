@@ -129,9 +129,14 @@ __device__ u64 g_rec_prof[2][512][12];
 // 16 row tiles x 16 workgroups = ONE persistent launch on 256 CUs instead of two half-filled ones run back to
 // back.  The hand-off format does not change: the workgroup publishes the granules of k-groups 2 ctw and
 // 2 ctw + 1, consumers read k-groups as before.
-template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1>
+// STREAM (streaming inference, sparch_rec_cell_stream_fwd / sparch_rec_cell_step_stream_fwd): no save tensors.  u0 /
+// w0 / s0 are the stream's (Bp,H) state buffers: EVERY launch starts from them (a launch per step included) and
+// writes the state it ended in back behind its last step, each thread its own elements; the last step's raw spikes
+// also go to s_step16 as a bf16 0/1 plane, the operand of the caller's next s @ V product.
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool STREAM = false>
 __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT), "64-column workgroups: the 8-wave persistent kernels");
+    static_assert(!STREAM || CW == 1, "the streaming kernels own 32 columns per workgroup");
     __shared__ __attribute__((aligned(16))) float red[2][NW][CW][RT * RED_LD4];
     __shared__ __attribute__((aligned(16))) u32x4 lut[256];  // byte of 8 spikes -> 8 bf16 (0 / 1.0)
     __shared__ int abort_flag[2];
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
     }
     {
         f32x4 v;
-        if (a.t_begin == 0) {
+        if (a.t_begin == 0 || STREAM) {
             v = ld4(a.u0 + (size_t)bpc * H + colc); u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
             v = ld4(a.s0 + (size_t)bpc * H + colc); s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
             if (ADAPT) { v = ld4(a.w0 + (size_t)bpc * H + colc); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
@@ -241,8 +246,10 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             h.y = (vs[2] != 0.f ? 0x3F80u : 0u) | (vs[3] != 0.f ? 0x3F800000u : 0u);
             st2(a.s16_out + o_s, h);
         }
-        st4_saved<true>(a.u_save, ((size_t)bp * T + st_t) * H + col, vu, a.save16, a.theta);
-        if (ADAPT) st4_saved<false>(a.w_save, ((size_t)bp * T + st_t) * H + col, vw, a.save16, a.theta);
+        if constexpr (!STREAM) {
+            st4_saved<true>(a.u_save, ((size_t)bp * T + st_t) * H + col, vu, a.save16, a.theta);
+            if (ADAPT) st4_saved<false>(a.w_save, ((size_t)bp * T + st_t) * H + col, vw, a.save16, a.theta);
+        }
     };
     auto flush_pending = [&]() {
         if (pend_t >= 0 && valid) store_step(pend_t, pend_s, pend_u, pend_w);
@@ -435,6 +442,20 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
     }
     flush_pending();
     PROF_FLUSH(0)
+    if constexpr (STREAM) {
+        if (valid) {  // the state this launch ended in, in place (nobody else reads or writes these elements)
+            const size_t o = (size_t)bp * H + col;
+            *reinterpret_cast<f32x4*>(const_cast<float*>(a.u0) + o) = f32x4{u[0], u[1], u[2], u[3]};
+            *reinterpret_cast<f32x4*>(const_cast<float*>(a.s0) + o) = f32x4{s[0], s[1], s[2], s[3]};
+            if (ADAPT) *reinterpret_cast<f32x4*>(const_cast<float*>(a.w0) + o) = f32x4{w[0], w[1], w[2], w[3]};
+            if (!EXT) {  // (the step variant has written the plane already)
+                u32x2 h;
+                h.x = (s[0] != 0.f ? 0x3F80u : 0u) | (s[1] != 0.f ? 0x3F800000u : 0u);
+                h.y = (s[2] != 0.f ? 0x3F80u : 0u) | (s[3] != 0.f ? 0x3F800000u : 0u);
+                *reinterpret_cast<u32x2*>(a.s_step16 + o) = h;
+            }
+        }
+    }
 
     // ---- spike counts (post-dropout) -> one integer atomic per (direction, column) per workgroup
     if (a.spike_count) {
@@ -1293,8 +1314,10 @@ bool xcd_local_enabled() {
 }
 
 // NP = 1: the bf16 operand mode (sparch_set_operand_precision) — the V pack then holds one rounded plane
-template <bool BWD, bool ADAPT, int NP = 3>
+// STREAM: the streaming forward's instantiations (state in / out, no saves; 32-column workgroups only)
+template <bool BWD, bool ADAPT, int NP = 3, bool STREAM = false>
 int launch_rec(int kgw, const RecArgs& a, unsigned grid, hipStream_t st, int cw = 1) {
+    static_assert(!(BWD && STREAM), "streaming is forward-only");
     if constexpr (NP == 1) {
         if (cw == 2) {  // 64-column workgroups (bf16 operand mode, 8-wave kernels: kgw >= 2)
 #define SP_LAUNCH2(KB)                                                                                \
@@ -1316,7 +1339,7 @@ int launch_rec(int kgw, const RecArgs& a, unsigned grid, hipStream_t st, int cw 
 #define SP_LAUNCH(K, KB, NWB)                                                                        \
     if (BWD && a.save16) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, NWB, false, NP, true>), dim3(grid), dim3(64 * NWB), 0, st, a); \
     else if (BWD) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, NWB, false, NP, false>), dim3(grid), dim3(64 * NWB), 0, st, a); \
-    else     hipLaunchKernelGGL((rec_fwd_kernel<ADAPT, KB, NWB, false, NP>), dim3(grid), dim3(64 * NWB), 0, st, a);
+    else     hipLaunchKernelGGL((rec_fwd_kernel<ADAPT, KB, NWB, false, NP, 1, STREAM>), dim3(grid), dim3(64 * NWB), 0, st, a);
     switch (kgw) {
         case 1: SP_LAUNCH(1, 1, 4) break;
         case 2: SP_LAUNCH(2, 1, 8) break;
@@ -1329,7 +1352,7 @@ int launch_rec(int kgw, const RecArgs& a, unsigned grid, hipStream_t st, int cw 
     return SPARCH_OK;
 }
 
-template <bool BWD, bool ADAPT, int NP = 3>
+template <bool BWD, bool ADAPT, int NP = 3, bool STREAM = false>
 bool rec_co_resident(int kgw, unsigned grid, int cus, int cw = 1) {
     if constexpr (NP == 1) {
         if (cw == 2) {
@@ -1347,7 +1370,7 @@ bool rec_co_resident(int kgw, unsigned grid, int cus, int cw = 1) {
     }
 #define SP_RES(KB, NWB) \
     return BWD ? grid_is_co_resident<rec_bwd_kernel<ADAPT, KB, NWB, false, NP>>(grid, 64 * NWB, cus) \
-               : grid_is_co_resident<rec_fwd_kernel<ADAPT, KB, NWB, false, NP>>(grid, 64 * NWB, cus);
+               : grid_is_co_resident<rec_fwd_kernel<ADAPT, KB, NWB, false, NP, 1, STREAM>>(grid, 64 * NWB, cus);
     switch (kgw) {
         case 1: SP_RES(1, 4)
         case 2: SP_RES(1, 8)
@@ -1358,7 +1381,7 @@ bool rec_co_resident(int kgw, unsigned grid, int cus, int cw = 1) {
 #undef SP_RES
 }
 
-template <bool BWD>
+template <bool BWD, bool STREAM = false>
 int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
     const bool adapt = kind == SPARCH_KIND_RADLIF;
     const bool low = sparch_operand_bf16() != 0;  // the V pack must have been made in the same mode
@@ -1395,7 +1418,7 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     // over all rows takes about as long as one over half of them.  SPARCH_REC_CW=1 forces the 32-column kernels.
     static const int cw_env = [] { const char* e = getenv("SPARCH_REC_CW"); return e ? atoi(e) : 0; }();
     int cw = 1;
-    if (low && L > 1 && kgw >= 2 && a.n_ct % 2 == 0 && cw_env != 1 &&
+    if (!STREAM && low && L > 1 && kgw >= 2 && a.n_ct % 2 == 0 && cw_env != 1 &&
         (cw_env == 2 || ((long long)a.n_rt_total * a.n_ct > cus && (long long)a.n_rt_total * (a.n_ct / 2) <= cus)))
         cw = 2;
     const int wg_per_rt = a.n_ct / cw;  // workgroups of one row tile
@@ -1407,8 +1430,8 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     }
     if (L > 1) {  // ask the runtime's occupancy calculator instead of assuming one workgroup per CU fits
         const unsigned g = (unsigned)(wg_per_rt * min(rt_per_launch, a.n_rt_total));
-        const bool ok = low ? (adapt ? rec_co_resident<BWD, true, 1>(kgw, g, cus, cw) : rec_co_resident<BWD, false, 1>(kgw, g, cus, cw))
-                            : (adapt ? rec_co_resident<BWD, true>(kgw, g, cus) : rec_co_resident<BWD, false>(kgw, g, cus));
+        const bool ok = low ? (adapt ? rec_co_resident<BWD, true, 1, STREAM>(kgw, g, cus, cw) : rec_co_resident<BWD, false, 1, STREAM>(kgw, g, cus, cw))
+                            : (adapt ? rec_co_resident<BWD, true, 3, STREAM>(kgw, g, cus) : rec_co_resident<BWD, false, 3, STREAM>(kgw, g, cus));
         if (!ok) {
             if (a.save16 && !BWD) return SPARCH_EINVAL;  // bf16 saves need the whole-sequence forward launch
             L = 1; rt_per_launch = a.n_rt_total;
@@ -1423,8 +1446,8 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
         if (!BWD) {
             for (int t0 = 0; t0 < a.T; t0 += L) {
                 a.t_begin = t0; a.t_end = min(a.T, t0 + L);
-                int rc = low ? (adapt ? launch_rec<false, true, 1>(kgw, a, grid, st, cw) : launch_rec<false, false, 1>(kgw, a, grid, st, cw))
-                             : (adapt ? launch_rec<false, true>(kgw, a, grid, st) : launch_rec<false, false>(kgw, a, grid, st));
+                int rc = low ? (adapt ? launch_rec<false, true, 1, STREAM>(kgw, a, grid, st, cw) : launch_rec<false, false, 1, STREAM>(kgw, a, grid, st, cw))
+                             : (adapt ? launch_rec<false, true, 3, STREAM>(kgw, a, grid, st) : launch_rec<false, false, 3, STREAM>(kgw, a, grid, st));
                 if (rc != SPARCH_OK) return rc;
             }
         } else {
@@ -1617,6 +1640,37 @@ extern "C" int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, cons
     return run_rec<false>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
 
+extern "C" int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                          const float* scale, const float* shift, const float* alpha,
+                                          const float* beta, const float* a, const float* b,
+                                          const float* vpack, const float* rec0, float* u, float* w, float* s,
+                                          uint16_t* s16_state, float theta, float p_drop, float* s_out,
+                                          uint16_t* s16_out, uint32_t* spike_count, void* chan, size_t chan_bytes,
+                                          uint32_t* status, int steps_per_launch, void* stream, int precision) {
+    SPARCH_ENTER();
+    PrecisionScope prec_scope_(precision);
+    if (!prec_scope_.ok) return SPARCH_EINVAL;
+    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_RADLIF;
+    // a stream is causal (one direction) and runs in eval (no dropout); the state is mandatory
+    if (dirs != 1 || p_drop != 0.0f || !u || !s || !s16_state || (adapt && !w)) return SPARCH_EINVAL;
+    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0) return SPARCH_EINVAL;
+    if (!Wx || !alpha || !vpack || !rec0 || (!s_out && !s16_out) || !status) return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b)) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!al16({Wx, vpack, rec0, u, w, s, s16_state, s_out, s16_out, chan})) return SPARCH_EALIGN;
+    RecArgs r{};
+    r.B = B; r.dirs = 1; r.T = T; r.H = H; r.Bp = B;
+    r.Wx = Wx; r.scale = scale; r.shift = shift;
+    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b;
+    r.vpack = reinterpret_cast<const u32x4*>(vpack); r.rec0 = rec0; r.u0 = u; r.w0 = w; r.s0 = s;
+    r.s_step16 = s16_state;
+    r.theta = theta; r.p_drop = 0.0f; r.inv_keep = 1.0f;
+    r.s_out = s_out; r.s16_out = s16_out; r.spike_count = spike_count;
+    r.chan = (u64*)chan; r.status = status;
+    return run_rec<false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
+}
+
 extern "C" int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                    const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
                                    const float* alpha, const float* beta, const float* a,
@@ -1721,6 +1775,38 @@ extern "C" int sparch_rec_cell_step_fwd(int kind, int B, int dirs, int T, int H,
     hipStream_t st = (hipStream_t)stream;
     if (adapt) hipLaunchKernelGGL((rec_fwd_kernel<true, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
     else       hipLaunchKernelGGL((rec_fwd_kernel<false, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+extern "C" int sparch_rec_cell_step_stream_fwd(int kind, int B, int dirs, int T, int H, int t, const float* Wx,
+                                               const float* scale, const float* shift, const float* alpha,
+                                               const float* beta, const float* a, const float* b,
+                                               const float* rec, float* u, float* w, float* s,
+                                               uint16_t* s16_state, float theta, float p_drop, float* s_out,
+                                               uint16_t* s16_out, uint32_t* spike_count, void* stream) {
+    SPARCH_ENTER();
+    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_RADLIF;
+    if (dirs != 1 || p_drop != 0.0f || !u || !s || !s16_state || (adapt && !w)) return SPARCH_EINVAL;
+    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || t < 0 || t >= T) return SPARCH_EINVAL;
+    if (!Wx || !alpha || !rec || (!s_out && !s16_out)) return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b)) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!al16({Wx, rec, u, w, s, s16_state, s_out, s16_out})) return SPARCH_EALIGN;
+    RecArgs r{};
+    r.B = B; r.dirs = 1; r.T = T; r.H = H; r.Bp = B;
+    r.n_ct = cdiv(H, CT); r.nkg = 4; r.n_rt_total = cdiv(r.Bp, RT); r.rt_base = 0; r.n_rt_launch = r.n_rt_total;
+    r.t_begin = t; r.t_end = t + 1;
+    r.Wx = Wx; r.scale = scale; r.shift = shift;
+    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b; r.rec0 = rec; r.u0 = u; r.w0 = w; r.s0 = s;
+    r.theta = theta; r.p_drop = 0.0f; r.inv_keep = 1.0f;
+    r.s_out = s_out; r.s16_out = s16_out; r.spike_count = spike_count;
+    r.s_step16 = s16_state;
+    const unsigned grid = (unsigned)(r.n_ct * r.n_rt_total);
+    hipStream_t st = (hipStream_t)stream;
+    if (adapt) hipLaunchKernelGGL((rec_fwd_kernel<true, 1, 4, true, 3, 1, true>), dim3(grid), dim3(256), 0, st, r);
+    else       hipLaunchKernelGGL((rec_fwd_kernel<false, 1, 4, true, 3, 1, true>), dim3(grid), dim3(256), 0, st, r);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }

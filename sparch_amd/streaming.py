@@ -1,0 +1,445 @@
+"""
+Streaming inference: a trained spiking network classifies a stream chunk by chunk, carrying every neuron's state
+from one chunk to the next.
+
+    st = StreamingSNN(net, batch_size)          # net.eval(), unidirectional
+    st.reset()                                  # the draws one SNN.forward would make, same generator, same order
+    out = st.step(x_chunk)                      # (B,Tc,C), any Tc >= 1 -> running softmax-sum (B,classes)
+
+What is carried per hidden layer is (u, [w,] s) after the chunk's last step, per readout (u, out): a step of the cell
+recurrences needs nothing else, and the arithmetic of a step does not know where a chunk ends — so the spikes of a
+chunked stream are those of one forward over the whole sequence, bit for bit wherever the matrix products are exact
+(dyadic weights), and the readout's running sum continues ONE sequential sum over t (the accumulator goes into the
+kernel; adding per-chunk sums would round differently).  The kernels are the `*_stream_fwd` entry points of the
+library: state in, state out, in place, no (B,T,H) save tensors.
+
+Everything a forward call derives from the parameters alone — the split planes of W, the packed and masked V, the
+eval-mode BatchNorm fold — is made once (`refresh()` after the parameters change); a chunk step launches the
+projection, the boundary product s @ V of a recurrent layer and the cell, nothing else.
+"""
+import numpy as np
+import torch
+
+from . import functional as Fn
+from ._capi import KIND, check, lib, ptr
+
+
+def _pad_cols(t, H4):
+    return None if t is None else torch.nn.functional.pad(t, (0, H4 - t.shape[-1]))
+
+
+class _Layer:
+    """One layer's cached operands and its state buffers (plain attribute bag)."""
+
+
+class StreamingSNN:
+    """Chunked forward of a `sparch_amd.SNN` in eval mode with carried state.
+
+    step(x_chunk) returns, with a readout layer, the running softmax-sum (B,classes) after all steps seen so far
+    (with graph=True a static tensor that the next step overwrites), without one the chunk's spikes (B,Tc,H).
+    firing_rates() is spike count / (B * steps_seen) per hidden unit, concatenated over the layers as SNN.forward
+    does; the integer counts add exactly across chunks.  The spike counters are per layer, NOT per row:
+    reset(rows=...) restarts the state, the running output and the step count of those rows and leaves the counters
+    (and steps_seen) alone.  Nothing here synchronises with the device.
+
+    A recurrent kernel whose in-kernel wait times out raises the status word (`functional.check_status`) as in the
+    whole-sequence path; the stream kernels have by then written a half-advanced state over the carried one, so after
+    such a report the stream can only be continued from a reset() (or a set_state() of a state saved earlier)."""
+
+    def __init__(self, net, batch_size, graph=False):
+        if not getattr(net, "is_snn", False):
+            raise ValueError("StreamingSNN: a sparch_amd.SNN (the non-spiking baselines do not stream)")
+        if net.bidirectional:
+            raise ValueError("StreamingSNN: a bidirectional network is not causal — its backward direction needs "
+                             "the end of the sequence before the first output")
+        if net.training:
+            raise ValueError("StreamingSNN: the network is in training mode — BatchNorm's batch statistics and "
+                             "dropout have no streaming meaning; call net.eval() first")
+        self.net = net
+        self.batch_size = int(batch_size)
+        self.graph = bool(graph)
+        self.steps_seen = 0
+        self.row_steps = np.zeros(self.batch_size, dtype=np.int64)
+        self._layers = None
+        self._prec = None
+        self._g = None            # dict(Tc, x, out, graph) once the step is captured
+        self._g_Tc = None         # the chunk length the graph is (to be) captured for: the first one seen
+        self._g_warm = 0
+        self._g_replays = 0
+        # inspection hook of the tests, not part of the interface: callable(layer_index, spikes (B,Tc,H)) called behind every chunk step for every hidden
+        # layer with the chunk's spikes as they travel to the next layer (the bf16 0/1 plane, or fp32); the tensor
+        # is only valid during the call (graph=True: a static buffer the next replay overwrites)
+        self._spike_tap = None
+
+    # ------------------------------------------------------------------ caches
+    def refresh(self):
+        """(Re)build everything derived from the parameters and the running statistics: call after changing them.
+        The state of the stream is kept."""
+        net, B = self.net, self.batch_size
+        dev = next(net.parameters()).device
+        Fn._require_device(next(net.parameters()), "the network")
+        old = self._layers
+        layers = []
+        last = net.num_layers - 1
+        with torch.no_grad():
+            for i, mod in enumerate(net.snn):
+                L = _Layer()
+                L.readout = bool(net.use_readout_layer and i == last)
+                L.kind = None if L.readout else mod.kind
+                L.recurrent = L.kind in ("RLIF", "RadLIF")
+                L.adaptive = L.kind in ("adLIF", "RadLIF")
+                L.H, L.K = mod.hidden_size, mod.input_size
+                L.W = Fn._f32c(mod.W.weight.detach())
+                L.Wb = None if mod.W.bias is None else Fn._f32c(mod.W.bias.detach())
+                L.w_planes = Fn.split_planes(L.W) if (L.K % 32 == 0 and L.H >= 128) else None
+                L.norm = mod.normalization if mod.normalize else "none"
+                L.scale = L.shift = L.nw = L.nb = None
+                if L.norm == "batchnorm":  # eval: the running statistics folded into one affine map per column
+                    _, L.scale, L.shift, _ = Fn._Norm.forward(
+                        "batchnorm", torch.empty(1, L.H, dtype=torch.float32, device=dev), None, mod.norm.weight,
+                        mod.norm.bias, mod.norm.running_mean, mod.norm.running_var, False, 1)
+                elif L.norm == "layernorm":
+                    L.nw, L.nb = mod.norm.weight.detach(), mod.norm.bias.detach()
+                L.theta = None if L.readout else float(mod.threshold)
+                # the recurrent kernels own 4 columns per thread: other widths run zero-padded (as cell_forward does),
+                # and the padded state stays padded
+                L.Hs = (L.H + 3) // 4 * 4 if L.recurrent else L.H
+                pad = (lambda t: _pad_cols(t, L.Hs)) if L.Hs != L.H else (lambda t: t)
+                L.p = {"alpha": pad(mod.alpha.detach())}
+                if L.adaptive:
+                    L.p.update(beta=pad(mod.beta.detach()), a=pad(mod.a.detach()), b=pad(mod.b.detach()))
+                if L.Hs != L.H:
+                    L.scale, L.shift = pad(L.scale), pad(L.shift)
+                if L.recurrent:
+                    V = Fn._f32c(mod.V.weight.detach())
+                    if L.Hs != L.H:
+                        V = torch.nn.functional.pad(V, (0, L.Hs - L.H, 0, L.Hs - L.H))
+                    L.step_path = Fn.rec_step_path(L.Hs)
+                    L.vmask = torch.empty(L.Hs, L.Hs, dtype=torch.float32, device=dev)
+                    if L.step_path:
+                        L.vpack = None
+                        check(lib.sparch_vmask(L.Hs, ptr(V), ptr(L.vmask), Fn._stream()), "sparch_vmask")
+                    else:
+                        L.vpack = torch.empty(lib.sparch_vpack_bytes(L.Hs) // 4, dtype=torch.float32, device=dev)
+                        check(lib.sparch_vpack(L.Hs, ptr(V), 0, ptr(L.vpack), ptr(L.vmask), Fn._stream(), Fn._prec()),
+                              "sparch_vpack")
+                    L.vmask_t = L.vmask.t().contiguous()  # (H_out, H_in): the NT operand of the exact spike product
+                # state buffers: kept across refresh()
+                if old is not None:
+                    for k in ("u", "w", "s", "s16", "count", "out", "binary"):
+                        setattr(L, k, getattr(old[i], k, None))
+                elif L.readout:
+                    L.u = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
+                    L.out = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
+                else:
+                    L.u = torch.zeros(B, L.Hs, dtype=torch.float32, device=dev)
+                    L.w = torch.zeros(B, L.Hs, dtype=torch.float32, device=dev) if L.adaptive else None
+                    L.s = torch.zeros(B, L.Hs, dtype=torch.float32, device=dev)
+                    L.s16 = torch.zeros(B, L.Hs, dtype=torch.bfloat16, device=dev) if L.recurrent else None
+                    L.count = torch.zeros(L.Hs, dtype=torch.int32, device=dev)
+                    L.binary = False  # s holds 0/1 only AND s16 mirrors it (true behind every chunk step)
+                layers.append(L)
+        self._layers, self._prec, self._dev = layers, Fn._prec(), dev
+        self._g, self._g_warm = None, 0  # a captured step holds the old operands
+
+    def _ensure(self):
+        if self._layers is None or self._prec != Fn._prec():  # (the V pack is made for one operand mode)
+            self.refresh()
+
+    # ------------------------------------------------------------------ state
+    @staticmethod
+    def _entry(st, readout):
+        """One layer's entry of a state list -> (u, w, s[, out]) tensors or None."""
+        if readout:
+            if torch.is_tensor(st):
+                return st, None, None, None
+            return st.get("u0", st.get("u")), None, None, st.get("out")
+        if isinstance(st, dict):
+            return st.get("u0", st.get("u")), st.get("w0", st.get("w")), st.get("s0", st.get("s")), None
+        u, w, s = st
+        return u, w, s, None
+
+    def _load(self, states, rows):
+        idx = None if rows is None else torch.as_tensor(list(rows), dtype=torch.long, device=self._dev)
+        n = self.batch_size if rows is None else len(idx)
+        if len(states) != len(self._layers):
+            raise ValueError(f"StreamingSNN: {len(self._layers)} layers, {len(states)} state entries")
+
+        def put(dst, src, what, H):
+            if src is None:
+                raise ValueError(f"StreamingSNN: the state has no {what}")
+            src = torch.as_tensor(src, dtype=torch.float32).to(self._dev)
+            if src.ndim != 2 or src.shape[0] != n or src.shape[1] not in (H, dst.shape[1]):
+                raise ValueError(f"StreamingSNN: {what} has shape {tuple(src.shape)}, expected ({n}, {H})")
+            src = _pad_cols(src, dst.shape[1])
+            if idx is None:
+                dst.copy_(src)
+            else:
+                dst.index_copy_(0, idx, src)
+
+        for L, st in zip(self._layers, states):
+            u, w, s, out = self._entry(st, L.readout)
+            put(L.u, u, "u", L.H)
+            if L.readout:
+                if out is not None:
+                    put(L.out, out, "out", L.H)
+                continue
+            if L.adaptive:
+                put(L.w, w, "w", L.H)
+            put(L.s, s, "s", L.H)
+            L.binary = False  # drawn states are uniform noise; a caller's are whatever they are
+
+    def reset(self, states=None, rows=None):
+        """Start (the given rows of) the stream anew.  states=None draws u0, [w0,] s0 per hidden layer and the
+        readout's u0 from torch's global CPU generator in exactly the order one SNN.forward draws them
+        (`SNN.draw_states`): under the same torch.manual_seed the first chunk equals the beginning of net(x).
+        states: a list with one entry per layer — (u0, w0, s0) or a dict with u0 / w0 / s0 (or u / w / s), for the
+        readout a tensor or a dict with u0 — of batch_size rows, or of len(rows) rows.
+        rows: reinitialise state, running output and step count of these rows only (independent streams that end at
+        different times); the spike counters are per layer, not per row, and keep counting."""
+        self._ensure()
+        n = self.batch_size if rows is None else len(list(rows))
+        if states is None:
+            states = self.net.draw_states(n, self._dev)
+            states.wait_ready()
+        self._load(states, rows)
+        ro = self._layers[-1] if self._layers[-1].readout else None
+        if rows is None:
+            for L in self._layers:
+                if not L.readout:
+                    L.count.zero_()
+            if ro is not None:
+                ro.out.zero_()
+            self.steps_seen = 0
+            self.row_steps[:] = 0
+        else:
+            rows = list(rows)
+            if ro is not None:
+                ro.out.index_fill_(0, torch.as_tensor(rows, dtype=torch.long, device=self._dev), 0.0)
+            self.row_steps[rows] = 0
+
+    def set_state(self, states):
+        """Load a state (the format of get_state(), or of reset(states=...)) without touching counters."""
+        self._ensure()
+        self._load(states, None)
+
+    def get_state(self):
+        """A copy of the carried state: per hidden layer {"u", ["w",] "s"}, for the readout {"u", "out"} (unpadded)."""
+        self._ensure()
+        res = []
+        for L in self._layers:
+            if L.readout:
+                res.append({"u": L.u.clone(), "out": L.out.clone()})
+            else:
+                d = {"u": L.u[:, :L.H].clone(), "s": L.s[:, :L.H].clone()}
+                if L.adaptive:
+                    d["w"] = L.w[:, :L.H].clone()
+                res.append(d)
+        return res
+
+    def firing_rates(self):
+        """Spikes per hidden unit / (B * steps_seen), the layers concatenated as SNN.forward concatenates them."""
+        self._ensure()
+        if self.steps_seen == 0:
+            raise ValueError("StreamingSNN.firing_rates: no step seen yet")
+        counts = [L.count[:L.H] for L in self._layers if not L.readout]
+        c = torch.cat(counts) if len(counts) > 1 else counts[0]
+        return c * (1.0 / float(self.batch_size * self.steps_seen))
+
+    # ------------------------------------------------------------------ the chunk step
+    def _rec_drive(self, L):
+        """s @ Vmasked for the state the next step starts from: the exact spike product on the bf16 plane once the
+        state is binary (every chunk but the first after a reset), the dense six-term product on drawn states."""
+        B = self.batch_size
+        if L.binary and Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16:
+            return Fn.gemm_nt(Fn.spike_placeholder(1, B, L.Hs, self._dev).view(B, L.Hs), L.vmask_t, spike_scale=1.0,
+                              a16=L.s16)[0]
+        if L.step_path:
+            return Fn.gemm_nn(L.s, L.vmask)
+        return Fn._gemm_small(L.s, L.vmask, nn=True)
+
+    def _cell(self, L, Wx, Tc, want_fp32):
+        """Wx (B*Tc, H) normalised projection (or raw + scale / shift) -> (s fp32 or None, s16 or None), (B,Tc,H)."""
+        B, H, Hs, dev = self.batch_size, L.H, L.Hs, self._dev
+        plane = Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16
+        if Hs != H:
+            Wx = _pad_cols(Wx, Hs)
+        s16 = torch.empty(B, Tc, Hs, dtype=torch.bfloat16, device=dev) if plane else None
+        s_out = torch.empty(B, Tc, Hs, dtype=torch.float32, device=dev) if (want_fp32 or not plane) else None
+        k, p = KIND[L.kind], L.p
+        if not L.recurrent:
+            check(lib.sparch_cell_stream_fwd(k, B, 1, Tc, Hs, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(p["alpha"]),
+                                             ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(L.u), ptr(L.w),
+                                             ptr(L.s), L.theta, 0.0, ptr(s_out), ptr(s16), ptr(L.count), Fn._stream()),
+                  "sparch_cell_stream_fwd")
+        elif L.step_path:
+            for t in range(Tc):
+                rec = self._rec_drive(L)
+                check(lib.sparch_rec_cell_step_stream_fwd(k, B, 1, Tc, Hs, t, ptr(Wx), ptr(L.scale), ptr(L.shift),
+                                                          ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
+                                                          ptr(p.get("b")), ptr(rec), ptr(L.u), ptr(L.w), ptr(L.s),
+                                                          ptr(L.s16), L.theta, 0.0, ptr(s_out), ptr(s16), ptr(L.count),
+                                                          Fn._stream()), "sparch_rec_cell_step_stream_fwd")
+                L.binary = True
+        else:
+            rec0 = self._rec_drive(L)
+            nbytes = lib.sparch_rec_chan_bytes(B, Tc, Hs)
+            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            with Fn._persistent_launch():
+                check(lib.sparch_rec_cell_stream_fwd(k, B, 1, Tc, Hs, ptr(Wx), ptr(L.scale), ptr(L.shift),
+                                                     ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
+                                                     ptr(p.get("b")), ptr(L.vpack), ptr(rec0), ptr(L.u), ptr(L.w),
+                                                     ptr(L.s), ptr(L.s16), L.theta, 0.0, ptr(s_out), ptr(s16),
+                                                     ptr(L.count), ptr(chan), nbytes, ptr(Fn.status_word(dev)),
+                                                     Fn.rec_steps_per_launch(Tc), Fn._stream(), Fn._prec()),
+                      "sparch_rec_cell_stream_fwd")
+            L.binary = True
+        if Hs != H:  # the next layer's operand at the layer's own width (the state stays padded)
+            s16 = None if s16 is None else s16[..., :H].contiguous()
+            s_out = None if s_out is None else s_out[..., :H].contiguous()
+        return s_out, s16
+
+    def _norm(self, L, Wx_raw):
+        if L.norm == "layernorm":
+            return Fn._Norm.forward("layernorm", Wx_raw, None, L.nw, L.nb, None, None, False, 1)[0]
+        return Wx_raw  # batchnorm: folded into the cell's scale / shift
+
+    def _body(self, x):
+        """One chunk through every layer (eager launches, or the region a graph captures)."""
+        B = self.batch_size
+        Tc = x.shape[1]
+        M = B * Tc
+        dev = self._dev
+        layers = self._layers
+        s = s16 = None
+        taps = []
+        for i, L in enumerate(layers):
+            if i == 0:
+                # the network input, as SpikingLayerFn.forward takes it: its bf16 plane when every value is bf16-exact
+                # (binned spike counts are; decided on the device), the fp32 values otherwise
+                tag = Fn.input_plane_of(x)
+                x2 = x.view(M, L.K)
+                xplane = xflag = None
+                if tag is not None:
+                    xplane, xflag = tag
+                elif Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16 and Fn.USE_INPUT_PLANE and Fn.DENSE_GEMM == "split6":
+                    xplane, xflag = Fn.plane_bf16_exact(x2)
+                elif Fn.USE_SPIKE_GEMM:
+                    xflag = Fn.flag_bf16_exact(x2)
+                Wx_raw, _ = Fn.gemm_nt(x2, L.W, L.Wb, a_exact_flag=xflag, a_plane=xplane)
+            else:
+                x2 = (s if s16 is None else Fn.spike_placeholder(B, Tc, L.K, dev)).view(M, L.K)
+                Wx_raw, _ = Fn.gemm_nt(x2, L.W, L.Wb, spike_scale=1.0, a16=None if s16 is None else s16.view(M, L.K),
+                                       b_planes=L.w_planes)
+            Wx = self._norm(L, Wx_raw)
+            if L.readout:
+                check(lib.sparch_readout_stream_fwd(B, Tc, L.H, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(L.p["alpha"]),
+                                                    ptr(L.u), ptr(L.out), Fn._stream()), "sparch_readout_stream_fwd")
+                return L.out, taps
+            s, s16 = self._cell(L, Wx, Tc, want_fp32=(i + 1 == len(layers)))
+            taps.append(s if s16 is None else s16)
+        return s, taps
+
+    def _emit(self, taps):
+        if self._spike_tap is not None:
+            for i, t in enumerate(taps):
+                self._spike_tap(i, t)
+
+    def step(self, x_chunk):
+        """x_chunk (B,Tc,C) float32, or uint8 spike counts, on the device; any Tc >= 1."""
+        self._ensure()
+        net = self.net
+        x = x_chunk
+        if net.reshape and x.ndim == 4:
+            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
+        Fn._require_device(x, "input")
+        if x.ndim != 3 or x.shape[0] != self.batch_size or x.shape[1] < 1 or x.shape[2] != self._layers[0].K:
+            raise ValueError(f"StreamingSNN.step: a ({self.batch_size}, Tc >= 1, {self._layers[0].K}) chunk, got "
+                             f"{tuple(x.shape)}")
+        if x.dtype != torch.uint8:
+            x = Fn._f32c(x)
+        Tc = x.shape[1]
+        out = None
+        with torch.no_grad():
+            if self.graph:
+                out = self._graph_step(x, Tc)
+            if out is None:
+                xin = Fn.input_from_counts(x) if x.dtype == torch.uint8 else x
+                out, taps = self._body(xin)
+                self._emit(taps)
+                if self._layers[-1].readout:
+                    out = out.clone()  # (the buffer itself is the accumulator of the next step)
+        self.steps_seen += Tc
+        self.row_steps += Tc
+        return out
+
+    def _graph_step(self, x, Tc):
+        """Replay (after capturing it once) the step for the first (B,Tc) seen; None = take the eager path: another
+        Tc, a state that is not binary yet (the first chunk after a reset runs the dense boundary product), or the
+        one eager pass that warms the kernels up before the capture."""
+        if self._g_Tc is None:
+            self._g_Tc = (Tc, x.dtype)
+        if (Tc, x.dtype) != self._g_Tc or not all(L.binary for L in self._layers if L.recurrent):
+            return None
+        if self._g is None:
+            if self._g_warm < 1:
+                self._g_warm += 1
+                return None
+            g = {"x": x.clone(), "graph": torch.cuda.CUDAGraph()}
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g["graph"]):
+                xin = Fn.input_from_counts(g["x"]) if x.dtype == torch.uint8 else g["x"]
+                out, g["taps"] = self._body(xin)
+                g["out"] = out.clone()
+            self._g = g
+        self._g["x"].copy_(x, non_blocking=True)
+        self._g["graph"].replay()
+        self._g_replays += 1
+        self._emit(self._g["taps"])
+        return self._g["out"]
+
+
+# ---------------------------------------------------------------------------------------- raw audio
+FBANK_WINDOW, FBANK_SHIFT = 400, 160  # 25 ms frames every 10 ms at 16 kHz (csrc/fbank_frame.h)
+
+
+def fbank_stream_plan(tail, n_new):
+    """Frame arithmetic of a streamed Kaldi filterbank with snip_edges=True (pure host): with `tail` unconsumed
+    samples kept and `n_new` arriving, returns (frames that are complete now, samples to keep afterwards).  Frame j
+    covers samples [160 j, 160 j + 400) of the stream and depends on nothing else, so the frames of tail + chunk are
+    the stream's next frames; what is kept starts at the first frame that is not complete yet: at most 399 samples,
+    and 240 .. 399 once a frame has been made."""
+    total = int(tail) + int(n_new)
+    if total < FBANK_WINDOW:
+        return 0, total
+    frames = 1 + (total - FBANK_WINDOW) // FBANK_SHIFT
+    return frames, total - frames * FBANK_SHIFT
+
+
+class StreamingFbank:
+    """push(wave_chunk (B,n)) -> (B, new_frames, num_mel_bins): the log-mel frames that became complete, from the
+    library's fbank kernel run on the kept tail + the chunk (per-frame DC removal and pre-emphasis are per frame, so
+    they equal the frames of the whole clip bit for bit)."""
+
+    def __init__(self, batch_size, num_mel_bins=40):
+        self.batch_size, self.num_mel_bins = int(batch_size), int(num_mel_bins)
+        self.tail = None
+        self.frames_seen = 0
+
+    def reset(self):
+        self.tail, self.frames_seen = None, 0
+
+    def push(self, wave_chunk):
+        Fn._require_device(wave_chunk, "waveform")
+        w = Fn._f32c(wave_chunk)
+        if w.ndim != 2 or w.shape[0] != self.batch_size:
+            raise ValueError(f"StreamingFbank.push: a ({self.batch_size}, n) chunk, got {tuple(w.shape)}")
+        buf = w if self.tail is None else torch.cat([self.tail, w], dim=1)
+        frames, keep = fbank_stream_plan(0 if self.tail is None else self.tail.shape[1], w.shape[1])
+        if frames == 0:
+            self.tail = buf.clone() if buf is w else buf  # never keep the caller's own buffer
+            return torch.empty(self.batch_size, 0, self.num_mel_bins, dtype=torch.float32, device=w.device)
+        out = Fn.fbank(buf, self.num_mel_bins)
+        self.tail = buf[:, buf.shape[1] - keep:].clone()
+        self.frames_seen += frames
+        return out
