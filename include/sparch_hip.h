@@ -224,6 +224,8 @@ int sparch_gemm_spike_tn(int M, int N, int K, const float* A, int lda, const flo
  * num_batches_tracked (nullable, ABI v5): BatchNorm1d's int64 counter, incremented by the same launch under the
  * same guard (the reference's `norm(...)` call does it, snns.py:264; a separate host-side `+= 1` was one more
  * kernel per layer and advanced on skipped steps too).
+ * Training needs dup*M >= 2 values per column (the unbiased variance divides by n - 1; nn.BatchNorm1d raises for a
+ * single value per channel): dup*M < 2 is SPARCH_EINVAL, nothing launched.
  * Eval (training = 0): scale/shift from running stats; colstat_ws ignored.           */
 int sparch_bn_finalize(int H, int M, int n_tiles, int dup, const float* colstat_ws,
                        const float* gamma, const float* beta, float* running_mean,

@@ -405,6 +405,8 @@ extern "C" int sparch_bn_finalize(int H, int M, int n_tiles, int dup, const floa
     SPARCH_ENTER();
     if (H <= 0 || !gamma || !beta || !running_mean || !running_var || !scale || !shift) return SPARCH_EINVAL;
     if (training && (M <= 0 || n_tiles <= 0 || dup < 1 || !colstat_ws)) return SPARCH_EINVAL;
+    // one value per column has no unbiased variance (n - 1 = 0; nn.BatchNorm1d raises for it)
+    if (training && (long long)M * dup < 2) return SPARCH_EINVAL;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(H, CS_COLS)), dim3(256), 0, (hipStream_t)stream, H, M,
                        n_tiles, dup, colstat_ws, gamma, beta, running_mean, running_var, momentum, eps,
                        training, scale, shift, save_mean, save_invstd, skip_if_nonzero,

@@ -522,6 +522,8 @@ class _Norm:
                 dist.all_gather(parts, colstat, group=SYNC_BN["group"])
                 colstat = torch.stack([q.view(2, n_tiles, H) for q in parts], dim=1).reshape(-1)  # (2, world*tiles, H)
                 n_tiles, rows = n_tiles * world, M * world
+            if training and rows * dup < 2:  # nn.BatchNorm1d's own refusal (the unbiased variance divides by n - 1)
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {(M, H)}")
             check(lib.sparch_bn_finalize(H, rows, n_tiles, dup, ptr(colstat), ptr(weight), ptr(bias),
                                          ptr(running_mean), ptr(running_var), BN_MOMENTUM, NORM_EPS,
                                          int(training), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),

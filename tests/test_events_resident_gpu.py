@@ -254,7 +254,10 @@ def test_run_exp_on_packs(tmp_path, model_type, served):
 
     data = tmp_path / "shd"
     data.mkdir()
-    pack_events.pack_mapping(_fake_h5(n=21, seed=1, tdtype=np.float16), str(data / "shd_train.events.npz"))
+    # 22 samples in batches of 4: a ragged last batch of TWO.  (A last batch of one sample gives the MLP's readout
+    # BatchNorm a single value per channel, which nn.BatchNorm1d refuses in training and sparch_bn_finalize now refuses
+    # as well; it used to write a non-finite running variance, and the evaluation behind it printed NaN.)
+    pack_events.pack_mapping(_fake_h5(n=22, seed=1, tdtype=np.float16), str(data / "shd_train.events.npz"))
     pack_events.pack_mapping(_fake_h5(n=9, seed=2, tdtype=np.float16), str(data / "shd_test.events.npz"))
     exp = tmp_path / "exp"
     env = dict(os.environ, SPARCH_EVENTS="resident")
@@ -269,6 +272,5 @@ def test_run_exp_on_packs(tmp_path, model_type, served):
         assert line in log, line
     train = [float(v) for v in re.findall(r"Epoch \d+: train loss=(\S+)", log)]
     assert len(train) == 2 and all(np.isfinite(train))
-    # (the MLP's EVALUATION on this toy set gives NaN with the per-sample loader as well: same batches, same losses)
-    assert model_type == "MLP" or "nan" not in log.lower()
+    assert "nan" not in log.lower()
     assert ("bf16 plane" in log) == (served == "bf16 plane")
