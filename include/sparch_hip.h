@@ -589,7 +589,10 @@ int sparch_audio_gather_augment(const void* samples, int dtype, const long long*
  * Element-wise tail of MLPLayer.forward (anns.py:218-227): y = dropout(act(z * scale + shift)) over n
  * elements of an (n/H, H) tensor; scale/shift (H) = the folded BatchNorm affine, NULL for none.
  * Backward: dz = dy * keep * act'(z * scale + shift) — the gradient w.r.t. the NORMALISED
- * pre-activation (feed it to the norm's backward).  H % 4 == 0.                                   */
+ * pre-activation (feed it to the norm's backward).  H % 4 == 0.
+ * relu PROPAGATES NaN, as torch.relu / nn.ReLU do (v <= 0 ? +0 : v; -0.0 gives +0.0), here and in every kernel of
+ * the baselines that applies it (the RNN cell, LiGRU's candidate on both of its paths): a network whose
+ * pre-activations have gone non-finite shows it in its loss.                                      */
 #define SPARCH_ACT_SIGMOID 0
 #define SPARCH_ACT_RELU 1
 #define SPARCH_ACT_TANH 2
@@ -708,8 +711,9 @@ int sparch_gate_step(int mode, int B, int dirs, int T, int H, int t, const float
  * step captured in a HIP graph, whose kernel arguments are frozen at capture time.
  * skip_if_nonzero (nullable): a device word, e.g. the recurrent kernels' status word — when it is non-zero
  * the step leaves parameters and moments untouched (a timed-out step must not be applied; no host sync) and
- * adds 1 to skip_if_nonzero[1] (hence not const: the caller learns how many steps to take back from its
- * bias-correction counter when it reads the word). */
+ * adds 1 to skip_if_nonzero[1] — ONCE PER CALL, however many launches the tensor table needs (24 tensors each), and
+ * not at all when no tensor is non-empty — hence not const: the caller learns how many steps to take back from its
+ * bias-correction counter when it reads the word.  Empty tensors (numel 0) are passed over and may be NULL. */
 int sparch_adam_step(int n_tensors, float* const* params, const float* const* grads,
                      float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                      float step_size, float beta1, float beta2, float bc2_sqrt, float eps,
@@ -751,8 +755,11 @@ int sparch_expand_counts_u8(long long M, int K, const uint8_t* counts, uint16_t*
 
 /* ---- a11: the train step's loss (exp.py:100, 362: nn.CrossEntropyLoss()(output, y), mean over the batch) and its
  * gradient with respect to the logits, one launch: loss[0] = mean_b(logsumexp(x_b) - x_b[y_b]),
- * dlogits = (softmax(x) - onehot(y)) / B.  logits (B,C) fp32, labels (B) int64 (a label outside [0,C) contributes
- * nothing), loss (1) fp32, dlogits (B,C) fp32. */
+ * dlogits = (softmax(x) - onehot(y)) / B.  logits (B,C) fp32, labels (B) int64, loss (1) fp32, dlogits (B,C) fp32.
+ * A row whose label lies outside [0,C) (compared as 64 bits) is IGNORED: it adds nothing to the loss and its row of
+ * dlogits is zero, so loss and gradient agree; the divisor stays B.  This is not torch's ignore_index, which divides
+ * by the number of rows it counted; the reference never passes such a label (its datasets number their classes
+ * 0..C-1), so the two cannot be told apart there. */
 int sparch_ce_loss(int B, int C, const float* logits, const int64_t* labels, float* loss, float* dlogits,
                    void* stream);
 

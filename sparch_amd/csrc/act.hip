@@ -11,7 +11,7 @@ namespace {
 
 __device__ __forceinline__ float act_f(int kind, float v) {
     if (kind == SPARCH_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    if (kind == SPARCH_ACT_RELU) return fmaxf(v, 0.0f);
+    if (kind == SPARCH_ACT_RELU) return v <= 0.0f ? 0.0f : v;  // a NaN stays a NaN (torch.relu); fmaxf would return 0
     return tanhf(v);
 }
 // derivative expressed through the activation's OUTPUT a = act(v)
@@ -200,7 +200,8 @@ extern "C" int sparch_softmax_sum_bwd(int B, int T, int K, const float* x, const
 //      gradient with respect to the logits in ONE launch: eager torch spends seven small kernels on it per step
 //      (cat, log-softmax, nll forward, two fills, nll backward, log-softmax backward).  One workgroup; a thread
 //      owns batch rows b, b + 256, ...: max, sum of exponentials, loss_b = log(sum) + max - x[label] and
-//      dlogits = (softmax - onehot) / B; the B row losses are summed in a fixed order (deterministic).
+//      dlogits = (softmax - onehot) / B; the B row losses are summed in a fixed order (deterministic).  A row whose
+//      label lies outside [0, C) adds nothing to the loss and gets a zero gradient row; the divisor stays B.
 namespace {
 __global__ __launch_bounds__(256) void ce_loss_kernel(int B, int C, const float* __restrict__ x,
                                                       const long long* __restrict__ y, float* __restrict__ loss,
@@ -216,12 +217,13 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(int B, int C, const float*
         float s = 0.0f;
         for (int c = 0; c < C; ++c) s += expf(row[c] - m);
         const float lse = logf(s);
-        const int lab = (int)y[b];
+        const long long lab = y[b];  // compared as 64 bits: 2^32 is out of range, not class 0
         const bool lab_ok = lab >= 0 && lab < C;
         if (lab_ok) acc += (lse + m) - row[lab];
         for (int c = 0; c < C; ++c) {
             const float p = expf((row[c] - m) - lse);  // softmax through log-softmax, as torch's backward does
-            dx[(size_t)b * C + c] = (p - ((lab_ok && c == lab) ? 1.0f : 0.0f)) * inv_b;
+            // a row whose label is outside [0, C) is not part of the loss: its gradient is zero
+            dx[(size_t)b * C + c] = lab_ok ? (p - (c == lab ? 1.0f : 0.0f)) * inv_b : 0.0f;
         }
     }
     part[tid] = acc;

@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256) void gate_kernel(GateArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             z[e] = sigm(xz[e] + rz[e]);                                   // anns.py:457
-            c[e] = fmaxf(xc[e] + rc[e], 0.0f);                            // anns.py:458 (ReLU, line 388)
+            const float pc = xc[e] + rc[e];
+            c[e] = pc <= 0.0f ? 0.0f : pc;                                // anns.py:458 (ReLU, line 388): NaN stays NaN
             y[e] = z[e] * yp[e] + (1.0f - z[e]) * c[e];                   // anns.py:459
             const float k = a.p_drop > 0.f ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
             yo[e] = y[e] * k;

@@ -209,7 +209,8 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_fwd_kernel(LigruArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             z[e] = sigm(xz[e] + rz[e]);
-            c[e] = fmaxf(xc[e] + rc[e], 0.0f);
+            const float pc = xc[e] + rc[e];
+            c[e] = pc <= 0.0f ? 0.0f : pc;      // ReLU that keeps a NaN, as nn.ReLU does (fmaxf would return 0)
             y[e] = z[e] * yp[e] + (1.0f - z[e]) * c[e];
             const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
             yo[e] = y[e] * k;

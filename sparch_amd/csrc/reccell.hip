@@ -1007,7 +1007,7 @@ struct AnnArgs {
 
 __device__ __forceinline__ float ann_act(int kind, float v) {
     if (kind == SPARCH_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    if (kind == SPARCH_ACT_RELU) return fmaxf(v, 0.0f);
+    if (kind == SPARCH_ACT_RELU) return v <= 0.0f ? 0.0f : v;  // a NaN stays a NaN (torch.relu); fmaxf would return 0
     return tanhf(v);
 }
 __device__ __forceinline__ float ann_dact(int kind, float a) {  // through the activation's output

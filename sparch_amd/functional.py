@@ -1076,6 +1076,7 @@ class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels):
         _require_device(logits, "logits")
+        _require_device(labels, "labels")
         logits = _f32c(logits)
         B, C = logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=logits.device)
