@@ -643,7 +643,8 @@ int sparch_ann_rec_step_bwd(int act, int B, int dirs, int T, int H, int s, const
  * forward outputs: y_out (B,T,H*dirs) = dropout(y), y_state / z_save / c_save (Bp,T,H) in cell time order;
  * backward outputs (Bp,T,H at the ORIGINAL time index): dz_all, dc_all = gradients w.r.t. the two normalised
  * projections, yprev_all = y_{t-1} (dVz = dz_all^T yprev_all, dV = dc_all^T yprev_all); carry (Bp,H): scratch
- * carried between chunked launches.  chan: sparch_ligru_chan_bytes(Bp, H) of scratch.                  */
+ * carried between chunked launches.  chan: sparch_ligru_chan_bytes(Bp, H) of scratch — one size for both passes;
+ * fewer bytes are SPARCH_EWORKSPACE in either (sparch_gru_chan_bytes likewise for the GRU).                    */
 size_t sparch_ligru_vpack_bytes(int H, int backward);
 int sparch_ligru_vpack(int H, const float* Vz, const float* V, int backward, float* vpack, void* stream, int precision);
 size_t sparch_ligru_chan_bytes(int Bp, int H);

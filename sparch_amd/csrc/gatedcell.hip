@@ -946,7 +946,8 @@ int run_ligru(LigruArgs& a, void* chan, size_t chan_bytes, int steps_per_launch,
     a.n_kg = a.H / 32;
     a.n_rt_total = cdiv(a.Bp, RT);
     const size_t rb = BWD ? ring_bytes_bwd(a.Bp, a.H) : ring_bytes_fwd(a.Bp, a.H);
-    if (!chan || chan_bytes < rb) return SPARCH_EWORKSPACE;
+    // the documented size (the larger of the two passes' rings), as sparch_ann_rec_* hold callers to theirs
+    if (!chan || chan_bytes < sparch_ligru_chan_bytes(a.Bp, a.H)) return SPARCH_EWORKSPACE;
     if (rb >= ((size_t)1 << 31)) return SPARCH_EINVAL;  // 32-bit buffer offsets
     if (hipMemsetD32Async((hipDeviceptr_t)chan, (int)SENTINEL, rb / 4, st) != hipSuccess) return SPARCH_ELAUNCH;
     a.ring = reinterpret_cast<char*>(chan);
@@ -995,7 +996,7 @@ int run_gru(LigruArgs& a, void* chan, size_t chan_bytes, int steps_per_launch, h
     a.n_kg = a.H / 32;
     a.n_rt_total = cdiv(a.Bp, RT);
     const size_t r1 = BWD ? ring_bytes_bwd(a.Bp, a.H) : ring_bytes_fwd(a.Bp, a.H), r2 = ring_bytes_fwd(a.Bp, a.H);
-    if (!chan || chan_bytes < r1 + r2) return SPARCH_EWORKSPACE;
+    if (!chan || chan_bytes < sparch_gru_chan_bytes(a.Bp, a.H)) return SPARCH_EWORKSPACE;  // the documented size
     if (r1 >= ((size_t)1 << 31)) return SPARCH_EINVAL;  // 32-bit buffer offsets
     if (hipMemsetD32Async((hipDeviceptr_t)chan, (int)SENTINEL, (r1 + r2) / 4, st) != hipSuccess) return SPARCH_ELAUNCH;
     a.ring = reinterpret_cast<char*>(chan);

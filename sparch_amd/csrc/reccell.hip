@@ -1715,6 +1715,7 @@ extern "C" int sparch_ann_rec_fwd(int act, int B, int dirs, int T, int H, const 
                                   int steps_per_launch, void* stream) {
     SPARCH_ENTER();
     if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
+    if (act != SPARCH_ACT_SIGMOID && act != SPARCH_ACT_RELU && act != SPARCH_ACT_TANH) return SPARCH_EINVAL;  // before chan is touched
     if (!Wx || !vpack || !y_out || !y_state || !status) return SPARCH_EINVAL;
     if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
     if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
@@ -1733,6 +1734,7 @@ extern "C" int sparch_ann_rec_bwd(int act, int B, int dirs, int T, int H, const 
                                   void* stream) {
     SPARCH_ENTER();
     if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
+    if (act != SPARCH_ACT_SIGMOID && act != SPARCH_ACT_RELU && act != SPARCH_ACT_TANH) return SPARCH_EINVAL;  // before chan is touched
     if (!g_out || !y_state || !vpack || !dpre || !y_prev || !status) return SPARCH_EINVAL;
     if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
     if (!al16({g_out, y_state, vpack, dpre, y_prev, chan})) return SPARCH_EALIGN;

@@ -2479,8 +2479,10 @@ def test_timeout_degrades_to_one_launch_per_step_and_guards_the_optimizer(sp, mo
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,H,bidir", [(3, 7, 32, False), (33, 11, 96, True), (70, 5, 160, False), (9, 6, 1024, True)])
 def test_ligru_persistent_shape_sweep(B, T, H, bidir, monkeypatch):
-    """Ragged batches (row tiles with padding rows, several row-tile groups), hidden sizes with partial k-group
-    coverage per wave, the largest supported size, both directions: persistent LiGRU == launch-per-step LiGRU."""
+    """Ragged batches (up to three row tiles, the last with padding rows; on a 256-CU device every shape here fits ONE
+    row-tile group — a second group, rt_base > 0, is reached by tests/test_gated_kernels_gpu.py), hidden sizes with
+    partial k-group coverage per wave, the largest supported size, both directions: persistent LiGRU == launch-per-step
+    LiGRU."""
     from sparch_amd.anns import LiGRULayer
 
     C = 20
