@@ -938,103 +938,63 @@ int kgw_bwd(int H) {  // producer tiles (16 units each) per wave, 8 waves
 size_t ring_bytes_fwd(int Bp, int H) { return (size_t)RING * cdiv(Bp, RT) * cdiv(H, 32) * TILE_BYTES; }
 size_t ring_bytes_bwd(int Bp, int H) { return (size_t)RING * cdiv(Bp, RT) * cdiv(H, UT) * TILE_BYTES; }
 
-template <bool BWD>
-int run_ligru(LigruArgs& a, void* chan, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
-    const int kgw = BWD ? kgw_bwd(a.H) : kgw_fwd(a.H);
-    if (kgw == 0) return SPARCH_EINVAL;
+// ---- the kernel table: (cell, direction, kgw) -> instantiation; always 8 waves.  (The forward's kgw stops at 4.)
+using GatedKernel = KernelRef<LigruArgs>;
+template <bool GRU, bool BWD>
+GatedKernel gated_kernel(int kgw) {
+    return rec_plan::with_kgw(kgw, [](auto k) -> GatedKernel {
+        constexpr int K = decltype(k)::value, KF = K > 4 ? 4 : K;
+        if constexpr (GRU) { if constexpr (BWD) return {gru_bwd_kernel<K, 8>, 512}; else return {gru_fwd_kernel<KF, 8>, 512}; }
+        else { if constexpr (BWD) return {ligru_bwd_kernel<K, 8>, 512}; else return {ligru_fwd_kernel<KF, 8>, 512}; }
+    });
+}
+
+// One pass: size and check the workspace, clear it, plan and walk (rec_plan.h).
+// LiGRU: one ring.  GRU: two rings (a step has two hand-offs) and launches that are always co-resident — where a row
+// tile's workgroups cannot be, the call is refused and the host takes the launch-per-step path of annstep.hip.
+template <bool GRU, bool BWD>
+int run_gated(LigruArgs& a, void* chan, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
+    const GatedKernel k = gated_kernel<GRU, BWD>(BWD ? kgw_bwd(a.H) : kgw_fwd(a.H));
+    if (!k.fn) return SPARCH_EINVAL;
     a.n_ct = a.H / UT;
     a.n_kg = a.H / 32;
     a.n_rt_total = cdiv(a.Bp, RT);
-    const size_t rb = BWD ? ring_bytes_bwd(a.Bp, a.H) : ring_bytes_fwd(a.Bp, a.H);
+    const size_t r1 = BWD ? ring_bytes_bwd(a.Bp, a.H) : ring_bytes_fwd(a.Bp, a.H), r2 = GRU ? ring_bytes_fwd(a.Bp, a.H) : 0;
     // the documented size (the larger of the two passes' rings), as sparch_ann_rec_* hold callers to theirs
-    if (!chan || chan_bytes < sparch_ligru_chan_bytes(a.Bp, a.H)) return SPARCH_EWORKSPACE;
-    if (rb >= ((size_t)1 << 31)) return SPARCH_EINVAL;  // 32-bit buffer offsets
-    if (hipMemsetD32Async((hipDeviceptr_t)chan, (int)SENTINEL, rb / 4, st) != hipSuccess) return SPARCH_ELAUNCH;
-    a.ring = reinterpret_cast<char*>(chan);
-    int L = steps_per_launch;
-    if (L < 1) L = 1;
-    if (L > a.T) L = a.T;
-    int cus = sparch_device_cus();
-    if (cus <= 0) cus = 256;
-    int rt_per_launch;
-    if (L == 1) {
-        rt_per_launch = a.n_rt_total;
-    } else {
-        rt_per_launch = cus / a.n_ct;  // one workgroup per CU must be co-resident
-        if (rt_per_launch < 1) { L = 1; rt_per_launch = a.n_rt_total; }
-    }
-    for (int rt0 = 0; rt0 < a.n_rt_total; rt0 += rt_per_launch) {
-        a.rt_base = rt0;
-        a.n_rt_launch = min(rt_per_launch, a.n_rt_total - rt0);
-        const unsigned grid = (unsigned)(a.n_ct * a.n_rt_launch);
-        for (int s0 = 0; s0 < a.T; s0 += L) {
-            a.s_begin = s0; a.s_end = min(a.T, s0 + L);
-#define SP_LIGRU(K)                                                                                      \
-    if (BWD) hipLaunchKernelGGL((ligru_bwd_kernel<K, 8>), dim3(grid), dim3(512), 0, st, a);              \
-    else     hipLaunchKernelGGL((ligru_fwd_kernel<(K > 4 ? 4 : K), 8>), dim3(grid), dim3(512), 0, st, a);
-            switch (kgw) {
-                case 1: SP_LIGRU(1) break;
-                case 2: SP_LIGRU(2) break;
-                case 4: SP_LIGRU(4) break;
-                case 8: SP_LIGRU(8) break;
-                default: return SPARCH_EINVAL;
-            }
-#undef SP_LIGRU
-            SPARCH_CHECK_LAUNCH();
-        }
-    }
-    return SPARCH_OK;
-}
-
-
-// GRU launches: always co-resident (two hand-offs per step), the row-tile groups one after the other
-template <bool BWD>
-int run_gru(LigruArgs& a, void* chan, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
-    const int kgw = BWD ? kgw_bwd(a.H) : kgw_fwd(a.H);
-    if (kgw == 0) return SPARCH_EINVAL;
-    a.n_ct = a.H / UT;
-    a.n_kg = a.H / 32;
-    a.n_rt_total = cdiv(a.Bp, RT);
-    const size_t r1 = BWD ? ring_bytes_bwd(a.Bp, a.H) : ring_bytes_fwd(a.Bp, a.H), r2 = ring_bytes_fwd(a.Bp, a.H);
-    if (!chan || chan_bytes < sparch_gru_chan_bytes(a.Bp, a.H)) return SPARCH_EWORKSPACE;  // the documented size
+    if (!chan || chan_bytes < (GRU ? sparch_gru_chan_bytes(a.Bp, a.H) : sparch_ligru_chan_bytes(a.Bp, a.H))) return SPARCH_EWORKSPACE;
     if (r1 >= ((size_t)1 << 31)) return SPARCH_EINVAL;  // 32-bit buffer offsets
-    if (hipMemsetD32Async((hipDeviceptr_t)chan, (int)SENTINEL, (r1 + r2) / 4, st) != hipSuccess) return SPARCH_ELAUNCH;
+    if (int rc = clear_handoff(chan, SENTINEL, r1 + r2, st)) return rc;
     a.ring = reinterpret_cast<char*>(chan);
-    a.ring2 = a.ring + r1;
-    int L = steps_per_launch;
-    if (L < 1) L = 1;
-    if (L > a.T) L = a.T;
-    int cus = sparch_device_cus();
-    if (cus <= 0) cus = 256;
-    const int rt_per_launch = cus / a.n_ct;
-    if (rt_per_launch < 1) return SPARCH_EINVAL;  // a row tile's workgroups cannot all be resident: per-step path
-    for (int rt0 = 0; rt0 < a.n_rt_total; rt0 += rt_per_launch) {
-        a.rt_base = rt0;
-        a.n_rt_launch = min(rt_per_launch, a.n_rt_total - rt0);
-        const unsigned grid = (unsigned)(a.n_ct * a.n_rt_launch);
-        for (int s0 = 0; s0 < a.T; s0 += L) {
-            a.s_begin = s0; a.s_end = min(a.T, s0 + L);
-#define SP_GRU(K)                                                                                        \
-    if (BWD) hipLaunchKernelGGL((gru_bwd_kernel<K, 8>), dim3(grid), dim3(512), 0, st, a);                \
-    else     hipLaunchKernelGGL((gru_fwd_kernel<(K > 4 ? 4 : K), 8>), dim3(grid), dim3(512), 0, st, a);
-            switch (kgw) {
-                case 1: SP_GRU(1) break;
-                case 2: SP_GRU(2) break;
-                case 4: SP_GRU(4) break;
-                case 8: SP_GRU(8) break;
-                default: return SPARCH_EINVAL;
-            }
-#undef SP_GRU
-            SPARCH_CHECK_LAUNCH();
-        }
-    }
-    return SPARCH_OK;
+    if (GRU) a.ring2 = a.ring + r1;
+    rec_plan::Policy pol;
+    pol.always_resident = GRU;
+    const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, sparch_device_cus(), pol);
+    if (!q.ok) return SPARCH_EINVAL;  // a row tile's workgroups cannot all be resident: per-step path
+    return rec_plan::walk(q, false, [&](int rt0, int n_rt, int s0, int s1) {
+        a.rt_base = rt0; a.n_rt_launch = n_rt; a.s_begin = s0; a.s_end = s1;
+        return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), a, st);
+    });
 }
 
-bool al16g(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (p && !aligned16(p)) return false;
-    return true;
+// what the four entries share: shape (H % 32: a consumer k-group is two workgroups' units) and dropout
+bool gated_ok(int B, int dirs, int T, int H, float p_drop) { return shape_ok(B, dirs, T, H, 32) && p_drop_ok(p_drop); }
+LigruArgs gated_fwd_args(int B, int dirs, int T, int H, float p_drop, uint64_t seed, const float* Wx, const float* sc,
+                         const float* sh, const float* Wzx, const float* scz, const float* shz, const float* vpack,
+                         float* y_out, float* y_state, float* z_save, float* c_save, uint32_t* status) {
+    LigruArgs a = base_args<LigruArgs>(B, dirs, T, H, p_drop, seed);
+    a.Wx = Wx; a.sc = sc; a.sh = sh; a.Wzx = Wzx; a.scz = scz; a.shz = shz;
+    a.vpack = reinterpret_cast<const u32x4*>(vpack);
+    a.y_out = y_out; a.y_state = y_state; a.z_save = z_save; a.c_save = c_save; a.status = status;
+    return a;
+}
+LigruArgs gated_bwd_args(int B, int dirs, int T, int H, float p_drop, uint64_t seed, const float* g_out,
+                         const float* y_state, const float* z_save, const float* c_save, const float* vpack_b,
+                         float* dz_all, float* dc_all, float* yprev_all, float* carry, uint32_t* status) {
+    LigruArgs a = base_args<LigruArgs>(B, dirs, T, H, p_drop, seed);
+    a.g_out = g_out; a.y_state = const_cast<float*>(y_state); a.z_save = const_cast<float*>(z_save);
+    a.c_save = const_cast<float*>(c_save); a.vpack = reinterpret_cast<const u32x4*>(vpack_b);
+    a.dz_all = dz_all; a.dc_all = dc_all; a.yprev_all = yprev_all; a.carry = carry; a.status = status;
+    return a;
 }
 
 }  // namespace
@@ -1082,18 +1042,13 @@ extern "C" int sparch_ligru_fwd(int B, int dirs, int T, int H, const float* Wx, 
                                 float* c_save, void* chan, size_t chan_bytes, uint32_t* status,
                                 int steps_per_launch, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 32 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!Wx || !Wzx || !vpack || !y_out || !y_state || !z_save || !c_save || !status) return SPARCH_EINVAL;
-    if ((sc == nullptr) != (sh == nullptr) || (scz == nullptr) != (shz == nullptr)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
-    if (!al16g({Wx, sc, sh, Wzx, scz, shz, vpack, y_out, y_state, z_save, c_save, chan})) return SPARCH_EALIGN;
-    LigruArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.Wx = Wx; a.sc = sc; a.sh = sh; a.Wzx = Wzx; a.scz = scz; a.shz = shz;
-    a.vpack = reinterpret_cast<const u32x4*>(vpack);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.y_out = y_out; a.y_state = y_state; a.z_save = z_save; a.c_save = c_save; a.status = status;
-    return run_ligru<false>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
+    if (!gated_ok(B, dirs, T, H, p_drop) || !all_set({Wx, Wzx, vpack, y_out, y_state, z_save, c_save, status}) ||
+        !paired(sc, sh) || !paired(scz, shz))
+        return SPARCH_EINVAL;
+    if (!al16({Wx, sc, sh, Wzx, scz, shz, vpack, y_out, y_state, z_save, c_save, chan})) return SPARCH_EALIGN;
+    LigruArgs a = gated_fwd_args(B, dirs, T, H, p_drop, seed, Wx, sc, sh, Wzx, scz, shz, vpack, y_out, y_state, z_save,
+                                 c_save, status);
+    return run_gated<false, false>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
 
 extern "C" int sparch_ligru_bwd(int B, int dirs, int T, int H, const float* g_out, const float* y_state,
@@ -1102,18 +1057,13 @@ extern "C" int sparch_ligru_bwd(int B, int dirs, int T, int H, const float* g_ou
                                 void* chan, size_t chan_bytes, uint32_t* status, int steps_per_launch,
                                 void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 32 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!g_out || !y_state || !z_save || !c_save || !vpack_b || !dz_all || !dc_all || !yprev_all || !carry || !status)
+    if (!gated_ok(B, dirs, T, H, p_drop) ||
+        !all_set({g_out, y_state, z_save, c_save, vpack_b, dz_all, dc_all, yprev_all, carry, status}))
         return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
-    if (!al16g({g_out, y_state, z_save, c_save, vpack_b, dz_all, dc_all, yprev_all, carry, chan})) return SPARCH_EALIGN;
-    LigruArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.g_out = g_out; a.y_state = const_cast<float*>(y_state); a.z_save = const_cast<float*>(z_save);
-    a.c_save = const_cast<float*>(c_save); a.vpack = reinterpret_cast<const u32x4*>(vpack_b);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.dz_all = dz_all; a.dc_all = dc_all; a.yprev_all = yprev_all; a.carry = carry; a.status = status;
-    return run_ligru<true>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
+    if (!al16({g_out, y_state, z_save, c_save, vpack_b, dz_all, dc_all, yprev_all, carry, chan})) return SPARCH_EALIGN;
+    LigruArgs a = gated_bwd_args(B, dirs, T, H, p_drop, seed, g_out, y_state, z_save, c_save, vpack_b, dz_all, dc_all,
+                                 yprev_all, carry, status);
+    return run_gated<false, true>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
 
 // ---- GRU (sparch_amd/functional.py GatedLayerFn): two fragment buffers per direction of time
@@ -1157,21 +1107,16 @@ extern "C" int sparch_gru_fwd(int B, int dirs, int T, int H, const float* Wx, co
                               uint64_t seed, float* y_out, float* y_state, float* z_save, float* r_save, float* c_save,
                               void* chan, size_t chan_bytes, uint32_t* status, int steps_per_launch, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 32 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!Wx || !Wzx || !Wrx || !vpack_gate || !vpack_cand || !y_out || !y_state || !z_save || !r_save || !c_save || !status)
+    if (!gated_ok(B, dirs, T, H, p_drop) ||
+        !all_set({Wx, Wzx, Wrx, vpack_gate, vpack_cand, y_out, y_state, z_save, r_save, c_save, status}) ||
+        !paired(sc, sh) || !paired(scz, shz) || !paired(scr, shr))
         return SPARCH_EINVAL;
-    if ((sc == nullptr) != (sh == nullptr) || (scz == nullptr) != (shz == nullptr) || (scr == nullptr) != (shr == nullptr))
-        return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
-    if (!al16g({Wx, sc, sh, Wzx, scz, shz, Wrx, scr, shr, vpack_gate, vpack_cand, y_out, y_state, z_save, r_save, c_save, chan}))
+    if (!al16({Wx, sc, sh, Wzx, scz, shz, Wrx, scr, shr, vpack_gate, vpack_cand, y_out, y_state, z_save, r_save, c_save, chan}))
         return SPARCH_EALIGN;
-    LigruArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.Wx = Wx; a.sc = sc; a.sh = sh; a.Wzx = Wzx; a.scz = scz; a.shz = shz; a.Wrx = Wrx; a.scr = scr; a.shr = shr;
-    a.vpack = reinterpret_cast<const u32x4*>(vpack_gate); a.vpack2 = reinterpret_cast<const u32x4*>(vpack_cand);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.y_out = y_out; a.y_state = y_state; a.z_save = z_save; a.r_save = r_save; a.c_save = c_save; a.status = status;
-    return run_gru<false>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
+    LigruArgs a = gated_fwd_args(B, dirs, T, H, p_drop, seed, Wx, sc, sh, Wzx, scz, shz, vpack_gate, y_out, y_state,
+                                 z_save, c_save, status);
+    a.Wrx = Wrx; a.scr = scr; a.shr = shr; a.r_save = r_save; a.vpack2 = reinterpret_cast<const u32x4*>(vpack_cand);
+    return run_gated<true, false>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
 
 extern "C" int sparch_gru_bwd(int B, int dirs, int T, int H, const float* g_out, const float* y_state, const float* z_save,
@@ -1180,21 +1125,16 @@ extern "C" int sparch_gru_bwd(int B, int dirs, int T, int H, const float* g_out,
                               float* dc_all, float* yprev_all, float* ry_all, float* carry, void* chan, size_t chan_bytes,
                               uint32_t* status, int steps_per_launch, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 32 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!g_out || !y_state || !z_save || !r_save || !c_save || !vpack_gate_b || !vpack_cand_b || !dz_all || !dr_all ||
-        !dc_all || !yprev_all || !ry_all || !carry || !status)
+    if (!gated_ok(B, dirs, T, H, p_drop) ||
+        !all_set({g_out, y_state, z_save, r_save, c_save, vpack_gate_b, vpack_cand_b, dz_all, dr_all, dc_all, yprev_all,
+                  ry_all, carry, status}))
         return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
-    if (!al16g({g_out, y_state, z_save, r_save, c_save, vpack_gate_b, vpack_cand_b, dz_all, dr_all, dc_all, yprev_all, ry_all,
+    if (!al16({g_out, y_state, z_save, r_save, c_save, vpack_gate_b, vpack_cand_b, dz_all, dr_all, dc_all, yprev_all, ry_all,
                 carry, chan}))
         return SPARCH_EALIGN;
-    LigruArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.g_out = g_out; a.y_state = const_cast<float*>(y_state); a.z_save = const_cast<float*>(z_save);
-    a.r_save = const_cast<float*>(r_save); a.c_save = const_cast<float*>(c_save);
-    a.vpack = reinterpret_cast<const u32x4*>(vpack_gate_b); a.vpack2 = reinterpret_cast<const u32x4*>(vpack_cand_b);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.dz_all = dz_all; a.dr_all = dr_all; a.dc_all = dc_all; a.yprev_all = yprev_all; a.ry_all = ry_all;
-    a.carry = carry; a.status = status;
-    return run_gru<true>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
+    LigruArgs a = gated_bwd_args(B, dirs, T, H, p_drop, seed, g_out, y_state, z_save, c_save, vpack_gate_b, dz_all, dc_all,
+                                 yprev_all, carry, status);
+    a.r_save = const_cast<float*>(r_save); a.vpack2 = reinterpret_cast<const u32x4*>(vpack_cand_b);
+    a.dr_all = dr_all; a.ry_all = ry_all;
+    return run_gated<true, true>(a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }

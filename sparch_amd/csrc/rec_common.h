@@ -1,8 +1,12 @@
 // Shared device helpers of the persistent recurrent kernels (reccell.hip, gatedcell.hip): types, the hand-off
 // ring constants, bare LDS barriers, exact-split MFMA wrapper, tile issue / settle of the sentinel protocol.
-// See the header comment of reccell.hip for the design.
+// At the end, the host side the two files share: kernel-table rows, launch and clear helpers, the entry points'
+// argument checks.  The launch policy is rec_plan.h.  See the header comment of reccell.hip for the design.
 #pragma once
 #include "common.h"
+#include "rec_plan.h"
+
+#include <initializer_list>
 
 namespace {
 
@@ -393,19 +397,84 @@ __device__ __forceinline__ void xcd_agree(gu32* tab, unsigned empty, int n_ct, i
     if (tid == 0) *lds_flag = all ? 1 : 0;
 }
 
-// Host side: can `grid` workgroups of this kernel be resident at once?  (The persistent launches wait for each
-// other inside the kernel.)  Occupancy as the runtime computes it for this kernel's registers / LDS, times the CU
-// count; cached per kernel.  The in-kernel spins are bounded anyway — this keeps a foreseeable miss (fewer CUs
-// than assumed, a build with more registers) from costing a 2 s timeout before the per-step fallback takes over.
-template <auto Kernel>
-bool grid_is_co_resident(unsigned grid, int threads, int cus) {
-    static const int per_cu = [threads] {
+// ---- host side: what the entry points and the launch code of reccell.hip and gatedcell.hip share.  The launch
+// policy itself (groups of row tiles x chunks of steps, the kgw -> kernel shape rule) is rec_plan.h.
+
+// One row of a kernel family's table: what is launched and with how many threads; per_cu (the kinds that ask the
+// occupancy calculator only) answers how many workgroups of THIS kernel the runtime fits on a CU.
+template <class Args>
+struct KernelRef {
+    void (*fn)(Args) = nullptr;
+    int threads = 0;
+    int (*per_cu)() = nullptr;
+};
+// Occupancy as the runtime computes it for this kernel's registers / LDS; asked once per kernel and process (host time
+// per launch is inside every training step).  A failed query counts as 1.
+template <auto Kernel, int THREADS>
+int occupancy_per_cu() {
+    static const int per_cu = [] {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, threads, 0) != hipSuccess) n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, THREADS, 0) != hipSuccess) n = 1;
         (void)hipGetLastError();
         return n;
     }();
-    return (long long)per_cu * cus >= (long long)grid;
+    return per_cu;
+}
+template <class Args, void (*Kernel)(Args), int THREADS>
+constexpr KernelRef<Args> kernel_with_occupancy() { return {Kernel, THREADS, &occupancy_per_cu<Kernel, THREADS>}; }
+// Can `grid` workgroups of this kernel be resident at once?  (The persistent launches wait for each other inside the
+// kernel.)  The in-kernel spins are bounded anyway — this keeps a foreseeable miss (fewer CUs than assumed, a build
+// with more registers) from costing a 2 s timeout before the per-step fallback takes over.
+template <class Args>
+bool co_resident(const KernelRef<Args>& k, unsigned grid, int cus) {
+    return (long long)k.per_cu() * rec_plan::cus_or_default(cus) >= (long long)grid;
+}
+template <class Args>
+int launch_kernel(const KernelRef<Args>& k, unsigned grid, const Args& a, hipStream_t st) {
+    if (!k.fn) return SPARCH_EINVAL;
+    hipLaunchKernelGGL(k.fn, dim3(grid), dim3((unsigned)k.threads), 0, st, a);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+// Hand-off buffers before a pass: `bytes` of 32-bit `pattern` — 0 for the forward granules ("tag 0"), SENTINEL for the
+// rings ("not written yet"); the agreement table behind either is cleared with them, its "empty" being that word.
+inline int clear_handoff(void* p, unsigned pattern, size_t bytes, hipStream_t st) {
+    const hipError_t e = pattern == 0 ? hipMemsetAsync(p, 0, bytes, st)
+                                      : hipMemsetD32Async((hipDeviceptr_t)p, (int)pattern, bytes / 4, st);
+    return e == hipSuccess ? SPARCH_OK : SPARCH_ELAUNCH;
+}
+
+// argument checks of the entry points
+inline bool all_set(std::initializer_list<const void*> ps) {  // mandatory pointers
+    for (const void* p : ps)
+        if (!p) return false;
+    return true;
+}
+inline bool al16(std::initializer_list<const void*> ps) {  // pointers the kernels access 16 bytes at a time (or NULL)
+    for (const void* p : ps)
+        if (p && !aligned16(p)) return false;
+    return true;
+}
+inline bool paired(const void* scale, const void* shift) { return (scale == nullptr) == (shift == nullptr); }
+inline bool p_drop_ok(float p) { return p >= 0.0f && p < 1.0f; }  // false for a NaN
+inline bool shape_ok(int B, int dirs, int T, int H, int h_multiple) {
+    return B > 0 && T > 0 && H > 0 && H % h_multiple == 0 && (dirs == 1 || dirs == 2);
+}
+// the fields every Args struct starts from
+template <class Args>
+Args base_args(int B, int dirs, int T, int H, float p_drop, uint64_t seed) {
+    Args a{};
+    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
+    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
+    return a;
+}
+// geometry of a step entry (RecArgs / AnnArgs): one launch over all row tiles, the recurrent product supplied by the
+// caller (one k-group class)
+template <class Args>
+unsigned step_geometry(Args& a) {
+    a.n_ct = cdiv(a.H, CT); a.nkg = 4; a.n_rt_total = cdiv(a.Bp, RT); a.rt_base = 0; a.n_rt_launch = a.n_rt_total;
+    return (unsigned)(a.n_ct * a.n_rt_total);
 }
 
 }  // namespace

@@ -54,6 +54,12 @@
 //   * steps_per_launch = T gives one persistent launch; = 1 degenerates to one launch per
 //     time step, where every wait is already satisfied at launch (safe fallback, and the
 //     path for shapes whose grid cannot be co-resident).
+//   * host side: how a pass is cut into launches (groups of row tiles x chunks of steps, the
+//     fallbacks, 32- or 64-column workgroups) is decided in ONE place for these cells and for
+//     gatedcell.hip's: rec_plan.h (plain C++, no HIP).  What differs between the kinds is a
+//     rec_plan::Policy; run_rec / run_ann below size, check and clear the workspace, plan, walk.
+//     Which instantiation runs a call is one table per family (rec_kernel, ann_kernel), used
+//     for launching and for the occupancy question alike.
 #include "common.h"
 
 #include "rec_common.h"
@@ -1313,74 +1319,65 @@ bool xcd_local_enabled() {
     return g_xcd_local < 0 ? env_on : g_xcd_local != 0;
 }
 
+// ---- the kernel tables: the ONE mapping from what a call asks for to the instantiation that runs it.  Launching and
+// the co-residency question both go through it, so the question is asked of the kernel that is launched.
+using RecKernel = KernelRef<RecArgs>;
+using AnnKernel = KernelRef<AnnArgs>;
+using rec_plan::rec_kb;
+using rec_plan::rec_nw;
+
 // NP = 1: the bf16 operand mode (sparch_set_operand_precision) — the V pack then holds one rounded plane
 // STREAM: the streaming forward's instantiations (state in / out, no saves; 32-column workgroups only)
-template <bool BWD, bool ADAPT, int NP = 3, bool STREAM = false>
-int launch_rec(int kgw, const RecArgs& a, unsigned grid, hipStream_t st, int cw = 1) {
+// CW = 2: 64-column workgroups (bf16 operand mode, not streaming, the 8-wave kernels: kgw >= 2)
+// S16: the backward that reads bf16 saved states (the forward takes a.save16 at run time)
+template <bool BWD, bool ADAPT, int NP, bool STREAM, int K, int CW, bool S16>
+constexpr RecKernel rec_kernel_of() {
+    constexpr int KB = rec_kb(K), NW = rec_nw(K);
+    if constexpr (BWD) return kernel_with_occupancy<RecArgs, rec_bwd_kernel<ADAPT, KB, NW, false, NP, S16, CW>, 64 * NW>();
+    else return kernel_with_occupancy<RecArgs, rec_fwd_kernel<ADAPT, KB, NW, false, NP, CW, STREAM>, 64 * NW>();
+}
+template <bool BWD, bool STREAM = false>
+RecKernel rec_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
     static_assert(!(BWD && STREAM), "streaming is forward-only");
-    if constexpr (NP == 1) {
-        if (cw == 2) {  // 64-column workgroups (bf16 operand mode, 8-wave kernels: kgw >= 2)
-#define SP_LAUNCH2(KB)                                                                                \
-    if (BWD && a.save16) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, 8, false, 1, true, 2>), dim3(grid), dim3(512), 0, st, a); \
-    else if (BWD) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, 8, false, 1, false, 2>), dim3(grid), dim3(512), 0, st, a); \
-    else     hipLaunchKernelGGL((rec_fwd_kernel<ADAPT, KB, 8, false, 1, 2>), dim3(grid), dim3(512), 0, st, a);
-            switch (kgw) {
-                case 2: SP_LAUNCH2(1) break;
-                case 4: SP_LAUNCH2(2) break;
-                case 8: SP_LAUNCH2(4) break;
-                default: return SPARCH_EINVAL;
-            }
-#undef SP_LAUNCH2
-            SPARCH_CHECK_LAUNCH();
-            return SPARCH_OK;
+    return rec_plan::with_kgw(kgw, [&](auto k) {
+        return rec_plan::with_bool(adapt, [&](auto ad) {
+            return rec_plan::with_bool(BWD && save16, [&](auto s16) -> RecKernel {
+                constexpr int K = decltype(k)::value;
+                constexpr bool A = decltype(ad)::value, S16 = BWD && decltype(s16)::value;
+                if (!low) return rec_kernel_of<BWD, A, 3, STREAM, K, 1, S16>();
+                if constexpr (!STREAM && K >= 2)
+                    if (cw == 2) return rec_kernel_of<BWD, A, 1, false, K, 2, S16>();
+                return rec_kernel_of<BWD, A, 1, STREAM, K, 1, S16>();
+            });
+        });
+    });
+}
+// the step variants (EXT): the recurrent product comes from the caller, one k-group class, no hand-off
+template <bool BWD, bool STREAM = false>
+RecKernel rec_step_kernel(bool adapt) {
+    constexpr int KB = rec_kb(1), NW = rec_nw(1);
+    return rec_plan::with_bool(adapt, [](auto ad) -> RecKernel {
+        constexpr bool A = decltype(ad)::value;
+        if constexpr (BWD) return {rec_bwd_kernel<A, KB, NW, true>, 64 * NW};
+        else return {rec_fwd_kernel<A, KB, NW, true, 3, 1, STREAM>, 64 * NW};
+    });
+}
+// dense cell; EXT: its step variant (kgw = 1 only).  An unknown activation or kgw has no kernel.
+template <bool BWD, bool EXT = false>
+AnnKernel ann_kernel(int act, int kgw) {
+    return rec_plan::with_kgw(kgw, [&](auto k) -> AnnKernel {
+        constexpr int K = decltype(k)::value, KB = rec_kb(K), NW = rec_nw(K);
+        if constexpr (EXT && K != 1) return {};
+        else switch (act) {
+            case SPARCH_ACT_SIGMOID: return {ann_rec_kernel<SPARCH_ACT_SIGMOID, BWD, KB, NW, EXT>, 64 * NW};
+            case SPARCH_ACT_RELU: return {ann_rec_kernel<SPARCH_ACT_RELU, BWD, KB, NW, EXT>, 64 * NW};
+            case SPARCH_ACT_TANH: return {ann_rec_kernel<SPARCH_ACT_TANH, BWD, KB, NW, EXT>, 64 * NW};
+            default: return {};
         }
-    }
-    // 8 waves of K/2 k-groups each once there are at least 8 k-groups, else 4 waves
-#define SP_LAUNCH(K, KB, NWB)                                                                        \
-    if (BWD && a.save16) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, NWB, false, NP, true>), dim3(grid), dim3(64 * NWB), 0, st, a); \
-    else if (BWD) hipLaunchKernelGGL((rec_bwd_kernel<ADAPT, KB, NWB, false, NP, false>), dim3(grid), dim3(64 * NWB), 0, st, a); \
-    else     hipLaunchKernelGGL((rec_fwd_kernel<ADAPT, KB, NWB, false, NP, 1, STREAM>), dim3(grid), dim3(64 * NWB), 0, st, a);
-    switch (kgw) {
-        case 1: SP_LAUNCH(1, 1, 4) break;
-        case 2: SP_LAUNCH(2, 1, 8) break;
-        case 4: SP_LAUNCH(4, 2, 8) break;
-        case 8: SP_LAUNCH(8, 4, 8) break;
-        default: return SPARCH_EINVAL;
-    }
-#undef SP_LAUNCH
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    });
 }
 
-template <bool BWD, bool ADAPT, int NP = 3, bool STREAM = false>
-bool rec_co_resident(int kgw, unsigned grid, int cus, int cw = 1) {
-    if constexpr (NP == 1) {
-        if (cw == 2) {
-#define SP_RES2(KB) \
-    return BWD ? grid_is_co_resident<rec_bwd_kernel<ADAPT, KB, 8, false, 1, false, 2>>(grid, 512, cus) \
-               : grid_is_co_resident<rec_fwd_kernel<ADAPT, KB, 8, false, 1, 2>>(grid, 512, cus);
-            switch (kgw) {
-                case 2: SP_RES2(1)
-                case 4: SP_RES2(2)
-                case 8: SP_RES2(4)
-                default: return false;
-            }
-#undef SP_RES2
-        }
-    }
-#define SP_RES(KB, NWB) \
-    return BWD ? grid_is_co_resident<rec_bwd_kernel<ADAPT, KB, NWB, false, NP>>(grid, 64 * NWB, cus) \
-               : grid_is_co_resident<rec_fwd_kernel<ADAPT, KB, NWB, false, NP, 1, STREAM>>(grid, 64 * NWB, cus);
-    switch (kgw) {
-        case 1: SP_RES(1, 4)
-        case 2: SP_RES(1, 8)
-        case 4: SP_RES(2, 8)
-        case 8: SP_RES(4, 8)
-        default: return false;
-    }
-#undef SP_RES
-}
-
+// ---- one pass of the persistent kernels: size and check the workspace, clear it, plan and walk (rec_plan.h)
 template <bool BWD, bool STREAM = false>
 int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
     const bool adapt = kind == SPARCH_KIND_RADLIF;
@@ -1391,142 +1388,97 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     a.nkg = 4 * kgw;
     a.n_rt_total = cdiv(a.Bp, RT);
     if (!a.chan || chan_bytes < sparch_rec_chan_bytes(a.Bp, a.T, a.H)) return SPARCH_EWORKSPACE;
-    // (the agreement table of the XCD-local stores sits behind the granules / the ring and is cleared with them:
-    // "empty" is 0 in the forward's zeroed buffer, the sentinel word in the backward's)
-    const size_t tabb = xcd_tab_bytes(a.Bp, a.H);
-    if (!BWD) {
-        const size_t fb = fwd_chan_bytes(a.Bp, a.T, a.H);
-        if (hipMemsetAsync(a.chan, 0, fb + tabb, st) != hipSuccess) return SPARCH_ELAUNCH;
-        a.xcd_tab = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.chan) + fb);
-    } else {  // every ring piece reads "not written yet" until its producer's store lands
-        const size_t rb = bwd_pring_bytes(a.Bp, a.H);
-        if (hipMemsetD32Async((hipDeviceptr_t)a.chan, (int)SENTINEL, (rb + tabb) / 4, st) != hipSuccess)
-            return SPARCH_ELAUNCH;
-        a.ring = reinterpret_cast<char*>(a.chan);
-        a.xcd_tab = reinterpret_cast<unsigned*>(a.ring + rb);
-    }
+    // forward: zeroed granules; backward: every ring piece reads "not written yet" until its producer's store lands.
+    // The agreement table of the XCD-local stores sits behind either and is cleared with it.
+    const size_t hb = BWD ? bwd_pring_bytes(a.Bp, a.H) : fwd_chan_bytes(a.Bp, a.T, a.H);
+    if (int rc = clear_handoff(a.chan, BWD ? SENTINEL : 0u, hb + xcd_tab_bytes(a.Bp, a.H), st)) return rc;
+    if (BWD) a.ring = reinterpret_cast<char*>(a.chan);
 
-    int L = steps_per_launch;
-    if (L < 1) L = 1;
-    if (L > a.T) L = a.T;
-    int cus = sparch_device_cus();
-    if (cus <= 0) cus = 256;
-    int rt_per_launch;
-    // 64-column workgroups (bf16 operand mode): when the row tiles do not fit one persistent launch at 32 columns
-    // per workgroup (512 virtual rows at H = 1024: 16 x 32 workgroups) but do at 64 (16 x 16), the whole batch runs
-    // as ONE launch instead of two half-machine launches back to back — the steps are latency chains, so a launch
-    // over all rows takes about as long as one over half of them.  SPARCH_REC_CW=1 forces the 32-column kernels.
     static const int cw_env = [] { const char* e = getenv("SPARCH_REC_CW"); return e ? atoi(e) : 0; }();
-    int cw = 1;
-    if (!STREAM && low && L > 1 && kgw >= 2 && a.n_ct % 2 == 0 && cw_env != 1 &&
-        (cw_env == 2 || ((long long)a.n_rt_total * a.n_ct > cus && (long long)a.n_rt_total * (a.n_ct / 2) <= cus)))
-        cw = 2;
-    const int wg_per_rt = a.n_ct / cw;  // workgroups of one row tile
-    if (L == 1) {
-        rt_per_launch = a.n_rt_total;  // nothing waits inside a launch: any grid size is fine
-    } else {
-        rt_per_launch = cus / wg_per_rt;  // one workgroup per CU must be co-resident
-        if (rt_per_launch < 1) { L = 1; rt_per_launch = a.n_rt_total; }
-    }
-    if (L > 1) {  // ask the runtime's occupancy calculator instead of assuming one workgroup per CU fits
-        const unsigned g = (unsigned)(wg_per_rt * min(rt_per_launch, a.n_rt_total));
-        const bool ok = low ? (adapt ? rec_co_resident<BWD, true, 1, STREAM>(kgw, g, cus, cw) : rec_co_resident<BWD, false, 1, STREAM>(kgw, g, cus, cw))
-                            : (adapt ? rec_co_resident<BWD, true, 3, STREAM>(kgw, g, cus) : rec_co_resident<BWD, false, 3, STREAM>(kgw, g, cus));
-        if (!ok) {
-            if (a.save16 && !BWD) return SPARCH_EINVAL;  // bf16 saves need the whole-sequence forward launch
-            L = 1; rt_per_launch = a.n_rt_total;
-        }
-    }
-    if (L == 1) cw = 1;
-    if (L < a.T || !xcd_local_enabled()) a.xcd_tab = nullptr;  // whole-sequence launches only (one agreement per launch)
-    for (int rt0 = 0; rt0 < a.n_rt_total; rt0 += rt_per_launch) {
-        a.rt_base = rt0;
-        a.n_rt_launch = min(rt_per_launch, a.n_rt_total - rt0);
-        const unsigned grid = (unsigned)((a.n_ct / cw) * a.n_rt_launch);
-        if (!BWD) {
-            for (int t0 = 0; t0 < a.T; t0 += L) {
-                a.t_begin = t0; a.t_end = min(a.T, t0 + L);
-                int rc = low ? (adapt ? launch_rec<false, true, 1, STREAM>(kgw, a, grid, st, cw) : launch_rec<false, false, 1, STREAM>(kgw, a, grid, st, cw))
-                             : (adapt ? launch_rec<false, true, 3, STREAM>(kgw, a, grid, st) : launch_rec<false, false, 3, STREAM>(kgw, a, grid, st));
-                if (rc != SPARCH_OK) return rc;
-            }
-        } else {
-            for (int t1 = a.T; t1 > 0; t1 -= L) {
-                a.t_end = t1; a.t_begin = max(0, t1 - L);
-                int rc = low ? (adapt ? launch_rec<true, true, 1>(kgw, a, grid, st, cw) : launch_rec<true, false, 1>(kgw, a, grid, st, cw))
-                             : (adapt ? launch_rec<true, true>(kgw, a, grid, st) : launch_rec<true, false>(kgw, a, grid, st));
-                if (rc != SPARCH_OK) return rc;
-            }
-        }
-    }
-    return SPARCH_OK;
-}
-
-template <int ACT, bool BWD>
-int launch_ann(int kgw, const AnnArgs& a, unsigned grid, hipStream_t st) {
-#define SP_LAUNCH_ANN(KB, NWB) \
-    hipLaunchKernelGGL((ann_rec_kernel<ACT, BWD, KB, NWB>), dim3(grid), dim3(64 * NWB), 0, st, a);
-    switch (kgw) {
-        case 1: SP_LAUNCH_ANN(1, 4) break;
-        case 2: SP_LAUNCH_ANN(1, 8) break;
-        case 4: SP_LAUNCH_ANN(2, 8) break;
-        case 8: SP_LAUNCH_ANN(4, 8) break;
-        default: return SPARCH_EINVAL;
-    }
-#undef SP_LAUNCH_ANN
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    rec_plan::Policy pol;
+    pol.ask_occupancy = true;
+    pol.refuse_degrade = a.save16 && !BWD;  // bf16 saves need the whole-sequence forward launch
+    pol.has_cw2 = !STREAM && low && kgw >= 2;
+    pol.cw_override = cw_env;
+    const int cus = sparch_device_cus();
+    const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, cus, pol, [&](unsigned grid, int cw) {
+        return co_resident(rec_kernel<BWD, STREAM>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
+    });
+    if (!q.ok) return SPARCH_EINVAL;
+    // whole-sequence launches only (one agreement per launch)
+    a.xcd_tab = q.whole && xcd_local_enabled() ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.chan) + hb) : nullptr;
+    const RecKernel k = rec_kernel<BWD, STREAM>(adapt, low, kgw, q.cw, a.save16 != 0);
+    return rec_plan::walk(q, BWD, [&](int rt0, int n_rt, int t0, int t1) {
+        a.rt_base = rt0; a.n_rt_launch = n_rt; a.t_begin = t0; a.t_end = t1;
+        return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), a, st);
+    });
 }
 
 template <bool BWD>
 int run_ann(int act, AnnArgs& a, void* chan, size_t chan_bytes, int steps_per_launch, hipStream_t st) {
     const int kgw = pick_kgw(a.H);
-    if (kgw == 0) return SPARCH_EINVAL;
+    const AnnKernel k = ann_kernel<BWD>(act, kgw);
+    if (!k.fn) return SPARCH_EINVAL;
     a.n_ct = cdiv(a.H, CT);
     a.nkg = 4 * kgw;
     a.n_rt_total = cdiv(a.Bp, RT);
     if (!chan || chan_bytes < sparch_rec_chan_bytes(a.Bp, a.T, a.H)) return SPARCH_EWORKSPACE;
-    const size_t rb = bwd_pring_bytes(a.Bp, a.H), tabb = xcd_tab_bytes(a.Bp, a.H);  // plane tiles + agreement table
-    if (hipMemsetD32Async((hipDeviceptr_t)chan, (int)SENTINEL, (rb + tabb) / 4, st) != hipSuccess)
-        return SPARCH_ELAUNCH;
+    const size_t rb = bwd_pring_bytes(a.Bp, a.H);  // plane tiles, the agreement table behind them
+    if (int rc = clear_handoff(chan, SENTINEL, rb + xcd_tab_bytes(a.Bp, a.H), st)) return rc;
     a.ring = reinterpret_cast<char*>(chan);
-    a.xcd_tab = reinterpret_cast<unsigned*>(a.ring + rb);
-    int L = steps_per_launch;
-    if (L < 1) L = 1;
-    if (L > a.T) L = a.T;
-    if (L < a.T || !xcd_local_enabled()) a.xcd_tab = nullptr;  // whole-sequence launches only
-    int cus = sparch_device_cus();
-    if (cus <= 0) cus = 256;
-    int rt_per_launch;
-    if (L == 1) {
-        rt_per_launch = a.n_rt_total;
-    } else {
-        rt_per_launch = cus / a.n_ct;  // one workgroup per CU must be co-resident
-        if (rt_per_launch < 1) { L = 1; rt_per_launch = a.n_rt_total; }
-    }
-    for (int rt0 = 0; rt0 < a.n_rt_total; rt0 += rt_per_launch) {
-        a.rt_base = rt0;
-        a.n_rt_launch = min(rt_per_launch, a.n_rt_total - rt0);
-        const unsigned grid = (unsigned)(a.n_ct * a.n_rt_launch);
-        for (int s0 = 0; s0 < a.T; s0 += L) {
-            a.s_begin = s0; a.s_end = min(a.T, s0 + L);
-            int rc;
-            switch (act) {
-                case SPARCH_ACT_SIGMOID: rc = launch_ann<SPARCH_ACT_SIGMOID, BWD>(kgw, a, grid, st); break;
-                case SPARCH_ACT_RELU: rc = launch_ann<SPARCH_ACT_RELU, BWD>(kgw, a, grid, st); break;
-                case SPARCH_ACT_TANH: rc = launch_ann<SPARCH_ACT_TANH, BWD>(kgw, a, grid, st); break;
-                default: return SPARCH_EINVAL;
-            }
-            if (rc != SPARCH_OK) return rc;
-        }
-    }
-    return SPARCH_OK;
+    rec_plan::Policy pol;
+    pol.whole_before_degrade = true;
+    const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, sparch_device_cus(), pol);
+    a.xcd_tab = q.whole && xcd_local_enabled() ? reinterpret_cast<unsigned*>(a.ring + rb) : nullptr;  // whole-sequence launches only
+    return rec_plan::walk(q, false, [&](int rt0, int n_rt, int s0, int s1) {
+        a.rt_base = rt0; a.n_rt_launch = n_rt; a.s_begin = s0; a.s_end = s1;
+        return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), a, st);
+    });
 }
 
-bool al16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (p && !aligned16(p)) return false;
-    return true;
+// ---- what the entry points share.  Every SPARCH_EINVAL check of an entry comes before its SPARCH_EALIGN check.
+bool rec_shape_ok(int kind, int B, int dirs, int T, int H, int t = 0) {  // H % 4: the kernels move four columns at a time
+    return (kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF) && shape_ok(B, dirs, T, H, 4) && t >= 0 && t < T;
+}
+// a stream is causal (one direction) and runs in eval (no dropout)
+bool stream_ok(int dirs, float p_drop) { return dirs == 1 && p_drop == 0.0f; }
+// what only the adaptive kind reads
+bool adapt_set(int kind, std::initializer_list<const void*> ps) { return kind != SPARCH_KIND_RADLIF || all_set(ps); }
+// BatchNorm backward folded in: all three or none, and 16-byte aligned (a misaligned one is refused like a missing one)
+bool bn_ok(const float* bn_x, const float* bn_mean, const float* bn_invstd) {
+    return !bn_x || (bn_mean && bn_invstd && al16({bn_x, bn_mean, bn_invstd}));
+}
+bool act_ok(int act) { return act == SPARCH_ACT_SIGMOID || act == SPARCH_ACT_RELU || act == SPARCH_ACT_TANH; }
+
+// shape, neuron parameters and the state a pass starts from
+RecArgs rec_args(int B, int dirs, int T, int H, const float* alpha, const float* beta, const float* a, const float* b,
+                 const float* u0, const float* w0, const float* s0, float theta, float p_drop, uint64_t seed) {
+    RecArgs r = base_args<RecArgs>(B, dirs, T, H, p_drop, seed);
+    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b; r.u0 = u0; r.w0 = w0; r.s0 = s0; r.theta = theta;
+    return r;
+}
+void rec_fwd_io(RecArgs& r, const float* Wx, const float* scale, const float* shift, const float* rec0, float* s_out,
+                uint16_t* s16_out, uint32_t* spike_count) {
+    r.Wx = Wx; r.scale = scale; r.shift = shift; r.rec0 = rec0;
+    r.s_out = s_out; r.s16_out = s16_out; r.spike_count = spike_count;
+}
+void rec_bwd_io(RecArgs& r, const float* g_out, const float* g_rate, const void* u_save, const void* w_save, float* dWx,
+                uint16_t* s_prev16, float* dparam_ws, const float* bn_x, const float* bn_mean, const float* bn_invstd) {
+    r.g_out = g_out; r.g_rate = g_rate; r.g_rate_scale = 1.0f / ((float)r.B * (float)r.T);
+    r.u_save = (float*)const_cast<void*>(u_save); r.w_save = (float*)const_cast<void*>(w_save);
+    r.dWx = dWx; r.s_prev16 = s_prev16; r.dparam_ws = dparam_ws;
+    r.bn_x = bn_x; r.bn_mean = bn_mean; r.bn_invstd = bn_invstd; r.bn_src = bn_x ? bn_x : g_out;
+}
+// one step [t, t + 1) over all row tiles
+int rec_step_launch(const RecKernel& k, RecArgs& r, int t, void* stream) {
+    const unsigned grid = step_geometry(r);
+    r.t_begin = t; r.t_end = t + 1;
+    return launch_kernel(k, grid, r, (hipStream_t)stream);
+}
+int ann_step_launch(const AnnKernel& k, AnnArgs& a, int s, const float* rec, float* step_out, void* stream) {
+    const unsigned grid = step_geometry(a);
+    a.s_begin = s; a.s_end = s + 1; a.rec_ext = rec; a.step_out = step_out;
+    return launch_kernel(k, grid, a, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1620,22 +1572,14 @@ extern "C" int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, cons
     if (!prec_scope_.ok) return SPARCH_EINVAL;
     // bf16 saved states cannot carry the exact state from one launch of a chunked forward to the next
     if (save_bf16 && steps_per_launch < T) return SPARCH_EINVAL;
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!Wx || !alpha || !vpack || !rec0 || !u0 || !s0 || (!s_out && !s16_out) || !u_save || !status) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!rec_shape_ok(kind, B, dirs, T, H) || !all_set({Wx, alpha, vpack, rec0, u0, s0, u_save, status}) ||
+        (!s_out && !s16_out) || !adapt_set(kind, {beta, a, b, w0, w_save}) || !paired(scale, shift) || !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({Wx, vpack, rec0, u0, w0, s0, s_out, s16_out, u_save, w_save, chan})) return SPARCH_EALIGN;
-    RecArgs r{};
-    r.B = B; r.dirs = dirs; r.T = T; r.H = H; r.Bp = B * dirs;
-    r.Wx = Wx; r.scale = scale; r.shift = shift;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b;
-    r.vpack = reinterpret_cast<const u32x4*>(vpack); r.rec0 = rec0; r.u0 = u0; r.w0 = w0; r.s0 = s0;
-    r.theta = theta; r.p_drop = p_drop; r.inv_keep = 1.0f / (1.0f - p_drop); r.seed = seed;
-    r.s_out = s_out; r.s16_out = s16_out; r.u_save = (float*)u_save; r.w_save = (float*)w_save;
-    r.save16 = save_bf16 != 0; r.spike_count = spike_count;
+    RecArgs r = rec_args(B, dirs, T, H, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed);
+    rec_fwd_io(r, Wx, scale, shift, rec0, s_out, s16_out, spike_count);
+    r.vpack = reinterpret_cast<const u32x4*>(vpack);
+    r.u_save = (float*)u_save; r.w_save = (float*)w_save; r.save16 = save_bf16 != 0;
     r.chan = (u64*)chan; r.status = status;
     return run_rec<false>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1650,23 +1594,15 @@ extern "C" int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int 
     SPARCH_ENTER();
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    // a stream is causal (one direction) and runs in eval (no dropout); the state is mandatory
-    if (dirs != 1 || p_drop != 0.0f || !u || !s || !s16_state || (adapt && !w)) return SPARCH_EINVAL;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0) return SPARCH_EINVAL;
-    if (!Wx || !alpha || !vpack || !rec0 || (!s_out && !s16_out) || !status) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b)) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    // the state is mandatory
+    if (!rec_shape_ok(kind, B, dirs, T, H) || !stream_ok(dirs, p_drop) || !all_set({u, s, s16_state, Wx, alpha, vpack, rec0, status}) ||
+        (!s_out && !s16_out) || !adapt_set(kind, {w, beta, a, b}) || !paired(scale, shift))
+        return SPARCH_EINVAL;
     if (!al16({Wx, vpack, rec0, u, w, s, s16_state, s_out, s16_out, chan})) return SPARCH_EALIGN;
-    RecArgs r{};
-    r.B = B; r.dirs = 1; r.T = T; r.H = H; r.Bp = B;
-    r.Wx = Wx; r.scale = scale; r.shift = shift;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b;
-    r.vpack = reinterpret_cast<const u32x4*>(vpack); r.rec0 = rec0; r.u0 = u; r.w0 = w; r.s0 = s;
+    RecArgs r = rec_args(B, 1, T, H, alpha, beta, a, b, u, w, s, theta, 0.0f, 0);
+    rec_fwd_io(r, Wx, scale, shift, rec0, s_out, s16_out, spike_count);
+    r.vpack = reinterpret_cast<const u32x4*>(vpack);
     r.s_step16 = s16_state;
-    r.theta = theta; r.p_drop = 0.0f; r.inv_keep = 1.0f;
-    r.s_out = s_out; r.s16_out = s16_out; r.spike_count = spike_count;
     r.chan = (u64*)chan; r.status = status;
     return run_rec<false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1683,27 +1619,16 @@ extern "C" int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, cons
     SPARCH_ENTER();
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x) || !aligned16(bn_mean) || !aligned16(bn_invstd)))
+    if (!bn_ok(bn_x, bn_mean, bn_invstd) || !rec_shape_ok(kind, B, dirs, T, H) ||
+        !all_set({g_out, u_save, alpha, vpack_t, u0, s0, dWx, s_prev16, dparam_ws, status}) ||
+        !adapt_set(kind, {beta, a, b, w0, w_save}) || !p_drop_ok(p_drop))
         return SPARCH_EINVAL;
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (!g_out || !u_save || !alpha || !vpack_t || !u0 || !s0 || !dWx || !s_prev16 || !dparam_ws || !status)
-        return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
     if (!al16({g_out, u_save, w_save, vpack_t, u0, w0, s0, dWx, s_prev16, dparam_ws, chan})) return SPARCH_EALIGN;
     if (bwd_pring_bytes(B * dirs, H) >= ((size_t)1 << 31)) return SPARCH_EINVAL;  // 32-bit buffer offsets
-    RecArgs r{};
-    r.B = B; r.dirs = dirs; r.T = T; r.H = H; r.Bp = B * dirs;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b;
-    r.vpack = reinterpret_cast<const u32x4*>(vpack_t); r.u0 = u0; r.w0 = w0; r.s0 = s0;
-    r.theta = theta; r.p_drop = p_drop; r.inv_keep = 1.0f / (1.0f - p_drop); r.seed = seed;
-    r.u_save = (float*)const_cast<void*>(u_save); r.w_save = (float*)const_cast<void*>(w_save);
+    RecArgs r = rec_args(B, dirs, T, H, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed);
+    rec_bwd_io(r, g_out, g_rate, u_save, w_save, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd);
+    r.vpack = reinterpret_cast<const u32x4*>(vpack_t);
     r.save16 = save_bf16 != 0;
-    r.g_out = g_out; r.g_rate = g_rate; r.g_rate_scale = 1.0f / ((float)B * (float)T);
-    r.dWx = dWx; r.s_prev16 = s_prev16; r.dparam_ws = dparam_ws;
-    r.bn_x = bn_x; r.bn_mean = bn_mean; r.bn_invstd = bn_invstd; r.bn_src = bn_x ? bn_x : g_out;
     r.chan = (u64*)chan; r.status = status;
     return run_rec<true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1714,16 +1639,13 @@ extern "C" int sparch_ann_rec_fwd(int act, int B, int dirs, int T, int H, const 
                                   float* y_out, float* y_state, void* chan, size_t chan_bytes, uint32_t* status,
                                   int steps_per_launch, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (act != SPARCH_ACT_SIGMOID && act != SPARCH_ACT_RELU && act != SPARCH_ACT_TANH) return SPARCH_EINVAL;  // before chan is touched
-    if (!Wx || !vpack || !y_out || !y_state || !status) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    // (an unknown act is refused here, before chan is touched)
+    if (!shape_ok(B, dirs, T, H, 4) || !act_ok(act) || !all_set({Wx, vpack, y_out, y_state, status}) ||
+        !paired(scale, shift) || !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({Wx, scale, shift, vpack, y_out, y_state, chan})) return SPARCH_EALIGN;
-    AnnArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
+    AnnArgs a = base_args<AnnArgs>(B, dirs, T, H, p_drop, seed);
     a.Wx = Wx; a.scale = scale; a.shift = shift; a.vpack = reinterpret_cast<const u32x4*>(vpack);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
     a.y_state = y_state; a.y_out = y_out; a.status = status;
     return run_ann<false>(act, a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1733,15 +1655,13 @@ extern "C" int sparch_ann_rec_bwd(int act, int B, int dirs, int T, int H, const 
                                   void* chan, size_t chan_bytes, uint32_t* status, int steps_per_launch,
                                   void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2)) return SPARCH_EINVAL;
-    if (act != SPARCH_ACT_SIGMOID && act != SPARCH_ACT_RELU && act != SPARCH_ACT_TANH) return SPARCH_EINVAL;  // before chan is touched
-    if (!g_out || !y_state || !vpack || !dpre || !y_prev || !status) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    // (an unknown act is refused here, before chan is touched)
+    if (!shape_ok(B, dirs, T, H, 4) || !act_ok(act) || !all_set({g_out, y_state, vpack, dpre, y_prev, status}) ||
+        !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({g_out, y_state, vpack, dpre, y_prev, chan})) return SPARCH_EALIGN;
-    AnnArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
+    AnnArgs a = base_args<AnnArgs>(B, dirs, T, H, p_drop, seed);
     a.g_out = g_out; a.y_in = y_state; a.vpack = reinterpret_cast<const u32x4*>(vpack);
-    a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
     a.dpre = dpre; a.y_prev = y_prev; a.status = status;
     return run_ann<true>(act, a, chan, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1756,29 +1676,14 @@ extern "C" int sparch_rec_cell_step_fwd(int kind, int B, int dirs, int T, int H,
                                         float* u_save, float* w_save, uint32_t* spike_count,
                                         uint16_t* s_step16, void* stream) {
     SPARCH_ENTER();
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || (dirs != 1 && dirs != 2) || t < 0 || t >= T) return SPARCH_EINVAL;
-    if (!Wx || !alpha || !rec || !u0 || !s0 || (!s_out && !s16_out) || !u_save || !s_step16) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!rec_shape_ok(kind, B, dirs, T, H, t) || !all_set({Wx, alpha, rec, u0, s0, u_save, s_step16}) ||
+        (!s_out && !s16_out) || !adapt_set(kind, {beta, a, b, w0, w_save}) || !paired(scale, shift) || !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({Wx, rec, u0, w0, s0, s_out, s16_out, u_save, w_save, s_step16})) return SPARCH_EALIGN;
-    RecArgs r{};
-    r.B = B; r.dirs = dirs; r.T = T; r.H = H; r.Bp = B * dirs;
-    r.n_ct = cdiv(H, CT); r.nkg = 4; r.n_rt_total = cdiv(r.Bp, RT); r.rt_base = 0; r.n_rt_launch = r.n_rt_total;
-    r.t_begin = t; r.t_end = t + 1;
-    r.Wx = Wx; r.scale = scale; r.shift = shift;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b; r.rec0 = rec; r.u0 = u0; r.w0 = w0; r.s0 = s0;
-    r.theta = theta; r.p_drop = p_drop; r.inv_keep = 1.0f / (1.0f - p_drop); r.seed = seed;
-    r.s_out = s_out; r.s16_out = s16_out; r.u_save = u_save; r.w_save = w_save; r.spike_count = spike_count;
-    r.s_step16 = s_step16;
-    const unsigned grid = (unsigned)(r.n_ct * r.n_rt_total);
-    hipStream_t st = (hipStream_t)stream;
-    if (adapt) hipLaunchKernelGGL((rec_fwd_kernel<true, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
-    else       hipLaunchKernelGGL((rec_fwd_kernel<false, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    RecArgs r = rec_args(B, dirs, T, H, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed);
+    rec_fwd_io(r, Wx, scale, shift, rec, s_out, s16_out, spike_count);
+    r.u_save = u_save; r.w_save = w_save; r.s_step16 = s_step16;
+    return rec_step_launch(rec_step_kernel<false>(kind == SPARCH_KIND_RADLIF), r, t, stream);
 }
 
 extern "C" int sparch_rec_cell_step_stream_fwd(int kind, int B, int dirs, int T, int H, int t, const float* Wx,
@@ -1788,29 +1693,14 @@ extern "C" int sparch_rec_cell_step_stream_fwd(int kind, int B, int dirs, int T,
                                                uint16_t* s16_state, float theta, float p_drop, float* s_out,
                                                uint16_t* s16_out, uint32_t* spike_count, void* stream) {
     SPARCH_ENTER();
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    if (dirs != 1 || p_drop != 0.0f || !u || !s || !s16_state || (adapt && !w)) return SPARCH_EINVAL;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || t < 0 || t >= T) return SPARCH_EINVAL;
-    if (!Wx || !alpha || !rec || (!s_out && !s16_out)) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b)) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!rec_shape_ok(kind, B, dirs, T, H, t) || !stream_ok(dirs, p_drop) || !all_set({u, s, s16_state, Wx, alpha, rec}) ||
+        (!s_out && !s16_out) || !adapt_set(kind, {w, beta, a, b}) || !paired(scale, shift))
+        return SPARCH_EINVAL;
     if (!al16({Wx, rec, u, w, s, s16_state, s_out, s16_out})) return SPARCH_EALIGN;
-    RecArgs r{};
-    r.B = B; r.dirs = 1; r.T = T; r.H = H; r.Bp = B;
-    r.n_ct = cdiv(H, CT); r.nkg = 4; r.n_rt_total = cdiv(r.Bp, RT); r.rt_base = 0; r.n_rt_launch = r.n_rt_total;
-    r.t_begin = t; r.t_end = t + 1;
-    r.Wx = Wx; r.scale = scale; r.shift = shift;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b; r.rec0 = rec; r.u0 = u; r.w0 = w; r.s0 = s;
-    r.theta = theta; r.p_drop = 0.0f; r.inv_keep = 1.0f;
-    r.s_out = s_out; r.s16_out = s16_out; r.spike_count = spike_count;
+    RecArgs r = rec_args(B, 1, T, H, alpha, beta, a, b, u, w, s, theta, 0.0f, 0);
+    rec_fwd_io(r, Wx, scale, shift, rec, s_out, s16_out, spike_count);
     r.s_step16 = s16_state;
-    const unsigned grid = (unsigned)(r.n_ct * r.n_rt_total);
-    hipStream_t st = (hipStream_t)stream;
-    if (adapt) hipLaunchKernelGGL((rec_fwd_kernel<true, 1, 4, true, 3, 1, true>), dim3(grid), dim3(256), 0, st, r);
-    else       hipLaunchKernelGGL((rec_fwd_kernel<false, 1, 4, true, 3, 1, true>), dim3(grid), dim3(256), 0, st, r);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return rec_step_launch(rec_step_kernel<false, true>(kind == SPARCH_KIND_RADLIF), r, t, stream);
 }
 
 extern "C" int sparch_rec_cell_step_bwd(int kind, int B, int dirs, int T, int H, int t, const float* g_out,
@@ -1822,85 +1712,42 @@ extern "C" int sparch_rec_cell_step_bwd(int kind, int B, int dirs, int T, int H,
                                         const float* bn_mean, const float* bn_invstd, float* dwx_step,
                                         void* stream) {
     SPARCH_ENTER();
-    if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x) || !aligned16(bn_mean) || !aligned16(bn_invstd)))
+    if (!bn_ok(bn_x, bn_mean, bn_invstd) || !rec_shape_ok(kind, B, dirs, T, H, t) ||
+        !all_set({g_out, u_save, alpha, u0, s0, dWx, s_prev16, dparam_ws, dwx_step}) || (t + 1 < T && !rec) ||
+        !adapt_set(kind, {beta, a, b, w0, w_save}) || !p_drop_ok(p_drop))
         return SPARCH_EINVAL;
-    if (kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_RADLIF;
-    if (B <= 0 || T <= 0 || H < 4 || (H % 4) != 0 || (dirs != 1 && dirs != 2) || t < 0 || t >= T) return SPARCH_EINVAL;
-    if (!g_out || !u_save || !alpha || !u0 || !s0 || !dWx || !s_prev16 || !dparam_ws || !dwx_step) return SPARCH_EINVAL;
-    if (t + 1 < T && !rec) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
     if (!al16({g_out, u_save, w_save, rec, u0, w0, s0, dWx, s_prev16, dparam_ws, dwx_step})) return SPARCH_EALIGN;
-    RecArgs r{};
-    r.B = B; r.dirs = dirs; r.T = T; r.H = H; r.Bp = B * dirs;
-    r.n_ct = cdiv(H, CT); r.nkg = 4; r.n_rt_total = cdiv(r.Bp, RT); r.rt_base = 0; r.n_rt_launch = r.n_rt_total;
-    r.t_begin = t; r.t_end = t + 1;
-    r.alpha = alpha; r.beta = beta; r.a = a; r.b = b; r.rec0 = rec; r.u0 = u0; r.w0 = w0; r.s0 = s0;
-    r.theta = theta; r.p_drop = p_drop; r.inv_keep = 1.0f / (1.0f - p_drop); r.seed = seed;
-    r.u_save = const_cast<float*>(u_save); r.w_save = const_cast<float*>(w_save);
-    r.g_out = g_out; r.g_rate = g_rate; r.g_rate_scale = 1.0f / ((float)B * (float)T);
-    r.dWx = dWx; r.s_prev16 = s_prev16; r.dparam_ws = dparam_ws; r.dwx_step = dwx_step;
-    r.bn_x = bn_x; r.bn_mean = bn_mean; r.bn_invstd = bn_invstd; r.bn_src = bn_x ? bn_x : g_out;
-    const unsigned grid = (unsigned)(r.n_ct * r.n_rt_total);
-    hipStream_t st = (hipStream_t)stream;
-    if (adapt) hipLaunchKernelGGL((rec_bwd_kernel<true, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
-    else       hipLaunchKernelGGL((rec_bwd_kernel<false, 1, 4, true>), dim3(grid), dim3(256), 0, st, r);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    RecArgs r = rec_args(B, dirs, T, H, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed);
+    rec_bwd_io(r, g_out, g_rate, u_save, w_save, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd);
+    r.rec0 = rec; r.dwx_step = dwx_step;
+    return rec_step_launch(rec_step_kernel<true>(kind == SPARCH_KIND_RADLIF), r, t, stream);
 }
-
-namespace {
-template <bool BWD>
-int launch_ann_step(int act, const AnnArgs& a, hipStream_t st) {
-    const unsigned grid = (unsigned)(a.n_ct * a.n_rt_total);
-    switch (act) {
-        case SPARCH_ACT_SIGMOID:
-            hipLaunchKernelGGL((ann_rec_kernel<SPARCH_ACT_SIGMOID, BWD, 1, 4, true>), dim3(grid), dim3(256), 0, st, a); break;
-        case SPARCH_ACT_RELU:
-            hipLaunchKernelGGL((ann_rec_kernel<SPARCH_ACT_RELU, BWD, 1, 4, true>), dim3(grid), dim3(256), 0, st, a); break;
-        case SPARCH_ACT_TANH:
-            hipLaunchKernelGGL((ann_rec_kernel<SPARCH_ACT_TANH, BWD, 1, 4, true>), dim3(grid), dim3(256), 0, st, a); break;
-        default: return SPARCH_EINVAL;
-    }
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
-}
-}  // namespace
 
 /* `s` counts steps in processing order (forward: t = s; backward: t = T-1-s); rec = y_{t-1} V^T (forward) /
- * dpre_{t+1} V (backward), ignored at s = 0. */
+ * dpre_{t+1} V (backward), ignored at s = 0.  (An unknown act is refused where the kernel is picked, behind the
+ * alignment check.) */
 extern "C" int sparch_ann_rec_step_fwd(int act, int B, int dirs, int T, int H, int s, const float* Wx,
                                        const float* scale, const float* shift, const float* rec, float p_drop,
                                        uint64_t seed, float* y_out, float* y_state, float* y_step, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2) || s < 0 || s >= T) return SPARCH_EINVAL;
-    if (!Wx || !y_out || !y_state || !y_step || (s > 0 && !rec)) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!shape_ok(B, dirs, T, H, 4) || s < 0 || s >= T || !all_set({Wx, y_out, y_state, y_step}) || (s > 0 && !rec) ||
+        !paired(scale, shift) || !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({Wx, scale, shift, rec, y_out, y_state, y_step})) return SPARCH_EALIGN;
-    AnnArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.n_ct = cdiv(H, CT); a.nkg = 4; a.n_rt_total = cdiv(a.Bp, RT); a.rt_base = 0; a.n_rt_launch = a.n_rt_total;
-    a.s_begin = s; a.s_end = s + 1;
-    a.Wx = Wx; a.scale = scale; a.shift = shift; a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.y_state = y_state; a.y_out = y_out; a.rec_ext = rec; a.step_out = y_step;
-    return launch_ann_step<false>(act, a, (hipStream_t)stream);
+    AnnArgs a = base_args<AnnArgs>(B, dirs, T, H, p_drop, seed);
+    a.Wx = Wx; a.scale = scale; a.shift = shift; a.y_state = y_state; a.y_out = y_out;
+    return ann_step_launch(ann_kernel<false, true>(act, 1), a, s, rec, y_step, stream);
 }
 
 extern "C" int sparch_ann_rec_step_bwd(int act, int B, int dirs, int T, int H, int s, const float* g_out,
                                        const float* y_state, const float* rec, float p_drop, uint64_t seed,
                                        float* dpre, float* y_prev, float* dpre_step, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || (dirs != 1 && dirs != 2) || s < 0 || s >= T) return SPARCH_EINVAL;
-    if (!g_out || !y_state || !dpre || !y_prev || !dpre_step || (s > 0 && !rec)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!shape_ok(B, dirs, T, H, 4) || s < 0 || s >= T || !all_set({g_out, y_state, dpre, y_prev, dpre_step}) ||
+        (s > 0 && !rec) || !p_drop_ok(p_drop))
+        return SPARCH_EINVAL;
     if (!al16({g_out, y_state, rec, dpre, y_prev, dpre_step})) return SPARCH_EALIGN;
-    AnnArgs a{};
-    a.B = B; a.dirs = dirs; a.T = T; a.H = H; a.Bp = B * dirs;
-    a.n_ct = cdiv(H, CT); a.nkg = 4; a.n_rt_total = cdiv(a.Bp, RT); a.rt_base = 0; a.n_rt_launch = a.n_rt_total;
-    a.s_begin = s; a.s_end = s + 1;
-    a.g_out = g_out; a.y_in = y_state; a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
-    a.dpre = dpre; a.y_prev = y_prev; a.rec_ext = rec; a.step_out = dpre_step;
-    return launch_ann_step<true>(act, a, (hipStream_t)stream);
+    AnnArgs a = base_args<AnnArgs>(B, dirs, T, H, p_drop, seed);
+    a.g_out = g_out; a.y_in = y_state; a.dpre = dpre; a.y_prev = y_prev;
+    return ann_step_launch(ann_kernel<true, true>(act, 1), a, s, rec, dpre_step, stream);
 }
