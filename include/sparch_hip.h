@@ -448,6 +448,33 @@ int sparch_readout_fwd(int B, int T, int C, const float* Wx, const float* scale,
  * out after the last chunk equals sparch_readout_fwd's over the whole sequence bit for bit.                    */
 int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, const float* scale,
                               const float* shift, const float* alpha, float* u, float* out, void* stream);
+/* Streaming, chunks of ONE time step: the projection and the cell of a layer in one launch (csrc/streamstep.hip),
+ * one launch per layer and step instead of the chain of projection, boundary product and cell launches.
+ * sparch_stream_step_fwd — one hidden layer, all B rows, any K, H, B >= 1 (rows in tiles over grid.y):
+ *   x (B,K), row stride ldx   the step's input: in_dtype 0 fp32 — the network input, or the previous layer's fresh
+ *                             spike state — or 1 uint8 spike counts, read as they are
+ *   W (H,K), bias (H) or NULL the projection as stored; scale / shift (H) the folded eval BatchNorm, both or neither
+ *   vmask_t (H,H), row stride ld   row h = column h of V with its diagonal zeroed (RLIF / RadLIF; else NULL)
+ *   u, w (B,H), row stride ld      membrane / adaptation state, in place
+ *   s_in (B,H)  the previous step's spikes (or a drawn real-valued s0: one code path), s_out (B,H) the new ones,
+ *               both fp32 with row stride ld; s16_out (B,H) the new spikes as a bf16 0/1 plane (NULL: not wanted),
+ *               so the chunk entry points above can continue from the same state.  Every workgroup of a recurrent
+ *               layer reads ALL of s_in: s_out must be another buffer there (equal pointers: SPARCH_EINVAL); for
+ *               LIF / adLIF they may be one.  Columns >= H of a row are never written.
+ *   spike_count (H) is ADDED to (integer atomics; NULL: not counted).
+ * The membrane update is the expression tree of the chunk kernels: a stream stepped here equals the chunked stream bit
+ * for bit wherever the projection sums are exact (fp32 FMA chains here, in another order than the MFMA products).
+ * Nothing waits inside a launch.  W, vmask_t, u, w, s_in, s_out, s16_out 16-byte aligned (else SPARCH_EALIGN).
+ * sparch_stream_step_readout — Wx = x W^T (+ bias), affine, u = alpha u + (1 - alpha) Wx, out += softmax(u); u and
+ * out (B,C) in place as in sparch_readout_stream_fwd, and out equal to its bit for bit on the same Wx; C <= 256.  */
+int sparch_stream_step_fwd(int kind, int B, int K, int H, int ld, int in_dtype, const void* x, int ldx,
+                           const float* W, const float* bias, const float* scale, const float* shift,
+                           const float* alpha, const float* beta, const float* a, const float* b,
+                           const float* vmask_t, float* u, float* w, const float* s_in, float* s_out,
+                           uint16_t* s16_out, float theta, uint32_t* spike_count, void* stream);
+int sparch_stream_step_readout(int B, int K, int C, const float* x, int ldx, const float* W, const float* bias,
+                               const float* scale, const float* shift, const float* alpha, float* u, float* out,
+                               void* stream);
 int sparch_readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x,
                        const float* bn_mean, const float* bn_invstd, const float* u_save,
                        const float* alpha, const float* u0, float* dWx, float* dalpha_ws,

@@ -96,6 +96,9 @@ PROTOTYPES = {
     "sparch_readout_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "sparch_readout_stream_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "sparch_readout_bwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
+    "sparch_stream_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P,
+                                       P, P, P, P, P, c_float, P, P]),
+    "sparch_stream_step_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),
     "sparch_fbank_frames": (c_int, [c_int]),
     "sparch_fbank_fwd": (c_int, [c_int, c_int, c_int, P, P, P]),
     "sparch_fbank_padded_fwd": (c_int, [c_int, c_int, P, c_int, c_int, c_int, P, P, P]),

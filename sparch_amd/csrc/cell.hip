@@ -437,17 +437,7 @@ struct RoCursor {
         if (c >= C) { c -= C; ++t; }
     }
 };
-__device__ __forceinline__ float ro_softmax_row(float* row, int C) {  // in place; returns nothing useful
-    float m = row[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) {
-        const float e = expf(row[c] - m);
-        row[c] = e;
-        den += e;
-    }
-    return den;
-}
+// (ro_softmax_row: common.h — the streaming step's readout kernel, streamstep.hip, shares it)
 
 // STREAM (sparch_readout_stream_fwd): `u_io` (B,C) is the membrane state, read in place of u0 and written back behind
 // the last step, and `out` comes in holding the running sum: the accumulator CONTINUES the one sequential sum over t

@@ -86,6 +86,22 @@ __device__ __forceinline__ float clampf(float x, float lo, float hi) {
     return fminf(fmaxf(x, lo), hi);
 }
 
+// The readout's softmax over one row of class potentials, by ONE thread, in place: row[c] <- exp(row[c] - max), the
+// sum of those returned (the caller divides).  One definition for readout_fwd_kernel / readout_bwd_kernel (cell.hip)
+// and the streaming step's readout (streamstep.hip): the running sum `out` of a stream must not depend on which of
+// them made a step.
+__device__ __forceinline__ float ro_softmax_row(float* row, int C) {
+    float m = row[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float e = expf(row[c] - m);
+        row[c] = e;
+        den += e;
+    }
+    return den;
+}
+
 // Dropout decision for output element `idx` of a layer: a counter-based hash of (seed, idx) built
 // from two rounds of a 32-bit integer finaliser (lowbias32); keep iff uniform >= p.  Forward and
 // backward regenerate the same mask from (seed, idx), nothing is stored.

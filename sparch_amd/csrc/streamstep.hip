@@ -1,0 +1,375 @@
+// Streaming inference, chunks of ONE time step: projection + cell in one launch per layer.
+//
+// sparch_stream_step_fwd   one hidden layer, one step, all rows:  Wx = x_t W^T (+ bias), the eval BatchNorm affine,
+//                          rec = s_in Vmasked for the recurrent kinds, the membrane update, the new state.
+// sparch_stream_step_readout  the readout layer's step: Wx, affine, u = alpha u + (1 - alpha) Wx, out += softmax(u).
+//
+// A chunk of one step is 1 .. a few hundred rows: the MFMA projection kernels (built for 64 000 rows) and the
+// boundary product run a dozen dependent launches on it, and the step costs the length of that chain.  Here a step
+// costs one kernel boundary per layer.  Nothing waits inside a launch: every workgroup reads the WHOLE previous spike
+// state s_in and writes its own columns of s_out, a different buffer, so the only ordering is the kernel boundary.
+//
+// Shape (hidden layer): a workgroup is 4 waves and owns 4 adjacent columns of the layer (one per wave) for one tile
+// of RT <= 16 batch rows (grid.y walks the row tiles: no batch cap).  A wave's column is one row of W (H,K) and one
+// row of vmask_t: both are streamed ONCE per row tile, straight into registers (16-byte loads issued before the tile
+// of x_t is staged, so their latency overlaps the staging), lanes striding over K; the row tile of x_t / s_in sits
+// in LDS in K-pieces and is read by all four waves.  The weights of a layer (<= 8 MB) are read again every step and a
+// column always lands on the same workgroup index, so they are loaded with the default cache policy and stay in L2.
+// The dot products are fp32 FMA chains, 64 lane partials per (row, column) added by a butterfly: exact wherever the
+// sums are exact in any order (dyadic weights on 0/1 spikes), otherwise within a few ulp of any other fp32 order.
+// The pointwise update restates the expression trees of rec_fwd_kernel (reccell.hip) and cell_fwd_pipe_kernel
+// (cell.hip); the file is built with -ffp-contract=off like them, so the same expressions give the same bits.
+#include <initializer_list>
+
+#include "common.h"
+
+namespace {
+
+constexpr int SS_NT = 256;   // 4 waves
+constexpr int SS_COLS = 4;   // columns per workgroup: one per wave
+// floats of one staged row piece: the tile is RT x KP floats of LDS (<= 32 KB)
+__host__ __device__ constexpr int ss_piece(int RT) { return RT <= 8 ? 1024 : 512; }
+
+struct StepArgs {
+    int B, K, H, ld, ldx, in_u8;
+    const void* x;
+    const float *W, *bias, *scale, *shift, *alpha, *beta, *a, *b, *vmask_t;
+    float *u, *w;
+    const float* s_in;
+    float* s_out;
+    uint16_t* s16_out;
+    float theta;
+    uint32_t* spike_count;
+};
+
+// acc[r] += sum_k src[r0 + r][k] * wrow[k], k < K.  All 256 threads stage; the calling wave's lanes stride over k.
+// A wave without a column is given any valid row (it stages, keeps the barriers, and its sums are never read).
+// VEC: rows of the weight matrix are 16-byte aligned (base aligned, row stride a multiple of 4) — 16-byte loads up to
+// K & ~3, the <= 3 left over by the first lanes; otherwise scalar loads throughout (a compile-time choice: as a
+// run-time one hipcc issues the loads of both forms).
+// Every global load is UNCONDITIONAL on a clamped address and masked where it is used: a load under a branch makes
+// hipcc wait for it at the join, one round trip per load instead of one per piece.
+template <int RT, bool U8, bool VEC>
+__device__ __forceinline__ void ss_dot(float* xs, const void* src, int ld_src, const float* wrow, int K, int r0, int B,
+                                       float (&acc)[RT]) {
+    constexpr int KP = ss_piece(RT), NV = KP / 256, NS = KP / 64, NI = KP / SS_NT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int Kv = VEC ? (K & ~3) : 0;
+    for (int k0 = 0; k0 < K; k0 += KP) {
+        const int klen = min(KP, K - k0);
+        // ---- this wave's weights of the piece -> registers (in flight while the tile is staged)
+        f32x4 wv[VEC ? NV : 1];
+        float ws[VEC ? 1 : NS];
+        float wt = 0.f;
+        if (VEC) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)  // (a row of a vec matrix holds (K + 3) & ~3 floats: the clamp stays inside)
+                wv[i] = *reinterpret_cast<const f32x4*>(wrow + min(k0 + (i * 64 + lane) * 4, max(Kv - 4, 0)));
+            wt = wrow[min(Kv + lane, K - 1)];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NS; ++i) ws[i] = wrow[min(k0 + i * 64 + lane, K - 1)];
+        }
+        // ---- the row tile's piece -> LDS (rows past B as zeros): all loads first, then the stores
+        float xv[RT][NI];
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const size_t o = (size_t)min(r0 + r, B - 1) * ld_src;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const size_t oo = o + min(k0 + tid + i * SS_NT, K - 1);
+                xv[r][i] = U8 ? (float)static_cast<const uint8_t*>(src)[oo] : static_cast<const float*>(src)[oo];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int kk = tid + i * SS_NT;
+                if (kk < klen) xs[r * KP + kk] = (r0 + r < B) ? xv[r][i] : 0.f;
+            }
+        }
+        __syncthreads();
+        if (VEC) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int kk = (i * 64 + lane) * 4;
+                if (k0 + kk < Kv) {
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) {
+                        const f32x4 x4 = *reinterpret_cast<const f32x4*>(&xs[r * KP + kk]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[r] = __builtin_fmaf(wv[i][e], x4[e], acc[r]);
+                    }
+                }
+            }
+            if (Kv >= k0 && Kv < k0 + KP && Kv + lane < K) {  // the <= 3 columns behind the last 16 bytes
+#pragma unroll
+                for (int r = 0; r < RT; ++r) acc[r] = __builtin_fmaf(wt, xs[r * KP + (Kv - k0) + lane], acc[r]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                const int kk = i * 64 + lane;
+                if (kk < klen) {
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) acc[r] = __builtin_fmaf(ws[i], xs[r * KP + kk], acc[r]);
+                }
+            }
+        }
+        __syncthreads();  // the piece is consumed: the next one (or the next operand) may be staged
+    }
+}
+
+__device__ __forceinline__ float ss_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <int RT, bool ADAPT, bool REC, bool VEC>
+__global__ __launch_bounds__(SS_NT) void stream_step_kernel(StepArgs a) {
+    constexpr int KP = ss_piece(RT);
+    __shared__ __attribute__((aligned(16))) float xs[RT * KP];
+    __shared__ float red[2][RT][SS_COLS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h0 = blockIdx.x * SS_COLS, r0 = blockIdx.y * RT;
+    const int hw = min(h0 + wave, a.H - 1);  // this wave's column (a wave past H: any valid one, never read)
+    // ---- the pointwise phase's operands, asked for now (thread = (row, column), the tile's 4 columns of a row
+    //      adjacent in memory): they arrive while the dot products run
+    const int r = tid >> 2, c = tid & 3;
+    const int row = r0 + r, h = h0 + c;
+    const bool valid = r < RT && row < a.B && h < a.H;
+    const int hc = min(h, a.H - 1);
+    const size_t o = (size_t)min(row, a.B - 1) * a.ld + hc;
+    const float p_al = a.alpha[hc];
+    const float p_bias = a.bias ? a.bias[hc] : 0.f;
+    const float p_sc = a.scale ? a.scale[hc] : 1.f, p_sh = a.scale ? a.shift[hc] : 0.f;
+    const float p_be = ADAPT ? a.beta[hc] : 0.f, p_a = ADAPT ? a.a[hc] : 0.f, p_b = ADAPT ? a.b[hc] : 0.f;
+    float u = a.u[o];
+    const float w_prev = ADAPT ? a.w[o] : 0.f;
+    const float s = a.s_in[o];
+
+    float accx[RT], accr[RT];
+#pragma unroll
+    for (int i = 0; i < RT; ++i) accx[i] = accr[i] = 0.f;
+    if (a.in_u8)
+        ss_dot<RT, true, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
+    else
+        ss_dot<RT, false, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
+    if (REC) ss_dot<RT, false, VEC>(xs, a.s_in, a.ld, a.vmask_t + (size_t)hw * a.ld, a.H, r0, a.B, accr);
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+        const float sx = ss_wave_sum(accx[i]);
+        const float sr = REC ? ss_wave_sum(accr[i]) : 0.f;
+        if (lane == 0) {
+            red[0][i][wave] = sx;
+            red[1][i][wave] = sr;
+        }
+    }
+    __syncthreads();
+    if (!valid) return;
+    const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
+    float wx = red[0][r][c];
+    if (a.bias) wx = wx + p_bias;
+    const float xn = a.scale ? bn_affine(wx, p_sc, p_sh) : wx;
+    float drive = REC ? xn + red[1][r][c] : xn;                              // snns.py:572 / 720
+    if (ADAPT) {
+        const float be = clampf(p_be, SP_BETA_LO, SP_BETA_HI), pa = clampf(p_a, SP_A_LO, SP_A_HI),
+                    pb = clampf(p_b, SP_B_LO, SP_B_HI);
+        const float w = (be * w_prev + pa * u) + pb * s;                     // snns.py:718 / 438
+        drive = drive - w;
+        a.w[o] = w;
+    }
+    u = al * (u - s) + oma * drive;                                          // snns.py:572 / 719 / 297 / 439
+    const bool spike = (u - a.theta) > 0.0f;                                 // snns.py:29
+    a.u[o] = u;
+    a.s_out[o] = spike ? 1.0f : 0.0f;
+    if (a.s16_out) a.s16_out[o] = spike ? (uint16_t)0x3F80u : (uint16_t)0u;  // bf16 1.0 / 0.0
+    if (spike && a.spike_count) atomicAdd(a.spike_count + h, 1u);
+}
+
+// ---- readout: one workgroup per batch row, 16 waves; a wave takes groups of RO_CG classes, lanes stride over K
+constexpr int RO_NT = 1024;
+constexpr int RO_KP = 1024;  // floats of x_t staged per piece: 16 weight floats per lane, class and piece
+// classes whose weight loads are in flight together: 3 with 16-byte loads (35 classes: one group per wave), 1 with
+// scalar ones (16 loads and their addresses per class: more would spill)
+__host__ __device__ constexpr int ro_group(bool VEC) { return VEC ? 3 : 1; }
+
+template <bool VEC>
+struct RoWeights {
+    f32x4 v[ro_group(VEC)][VEC ? RO_KP / 256 : 1];
+    float s[ro_group(VEC)][VEC ? 1 : RO_KP / 64];
+};
+// the weights of classes c0 .. c0 + ro_group(VEC) - 1 for the piece at k0: loads on clamped addresses, masked at their use
+// (see ss_dot)
+template <bool VEC>
+__device__ __forceinline__ void ro_load_group(RoWeights<VEC>& w, const float* __restrict__ W, int K, int C, int c0,
+                                              int k0, int lane) {
+#pragma unroll
+    for (int j = 0; j < ro_group(VEC); ++j) {
+        const float* wr = W + (size_t)min(c0 + j, C - 1) * K;
+        if (VEC) {
+#pragma unroll
+            for (int i = 0; i < RO_KP / 256; ++i)
+                w.v[j][i] = *reinterpret_cast<const f32x4*>(wr + min(k0 + (i * 64 + lane) * 4, K - 4));
+        } else {
+#pragma unroll
+            for (int i = 0; i < RO_KP / 64; ++i) w.s[j][i] = wr[min(k0 + i * 64 + lane, K - 1)];
+        }
+    }
+}
+
+template <bool VEC>  // 16-byte weight loads (K a multiple of 4) or scalar ones
+__global__ __launch_bounds__(RO_NT) void stream_step_readout_kernel(int K, int C, const float* __restrict__ x, int ldx,
+                                                                    const float* __restrict__ W,
+                                                                    const float* __restrict__ bias,
+                                                                    const float* __restrict__ scale,
+                                                                    const float* __restrict__ shift,
+                                                                    const float* __restrict__ alpha, float* u_io,
+                                                                    float* out) {
+    __shared__ __attribute__((aligned(16))) float xs[RO_KP];
+    __shared__ float row[256];  // Wx, then u, then softmax(u) of the classes
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    const float* xr = x + (size_t)b * ldx;
+    // thread = class operands, asked for now
+    const bool act = tid < C;
+    const int cc = act ? tid : 0;
+    const float p_al = alpha[cc], p_bias = bias ? bias[cc] : 0.f;
+    const float p_sc = scale ? scale[cc] : 1.f, p_sh = scale ? shift[cc] : 0.f;
+    const float u_prev = u_io[(size_t)b * C + cc], out_prev = out[(size_t)b * C + cc];
+    if (act) row[tid] = 0.f;
+    constexpr int RO_CG = ro_group(VEC), C_STEP = (RO_NT / 64) * RO_CG;
+    for (int k0 = 0; k0 < K; k0 += RO_KP) {
+        const int klen = min(RO_KP, K - k0);
+        const float xv = xr[min(k0 + tid, K - 1)];
+        RoWeights<VEC> w;
+        ro_load_group<VEC>(w, W, K, C, wave * RO_CG, k0, lane);  // the first group, in flight while x_t is staged
+        if (tid < klen) xs[tid] = xv;
+        __syncthreads();
+        for (int c0 = wave * RO_CG; c0 < C; c0 += C_STEP) {  // (a class belongs to one wave: no race on row[c])
+            if (c0 != wave * RO_CG) ro_load_group<VEC>(w, W, K, C, c0, k0, lane);
+#pragma unroll
+            for (int j = 0; j < RO_CG; ++j) {
+                float acc = 0.f;
+                if (VEC) {
+#pragma unroll
+                    for (int i = 0; i < RO_KP / 256; ++i) {
+                        const int kk = (i * 64 + lane) * 4;
+                        if (kk < klen) {
+                            const f32x4 x4 = *reinterpret_cast<const f32x4*>(&xs[kk]);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) acc = __builtin_fmaf(w.v[j][i][e], x4[e], acc);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < RO_KP / 64; ++i)
+                        if (i * 64 + lane < klen) acc = __builtin_fmaf(w.s[j][i], xs[i * 64 + lane], acc);
+                }
+                acc = ss_wave_sum(acc);
+                if (lane == 0 && c0 + j < C) row[c0 + j] = row[c0 + j] + acc;
+            }
+        }
+        __syncthreads();
+    }
+    // thread = class: the recurrence of readout_fwd_kernel (cell.hip)
+    if (act) {
+        const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
+        float wx = row[tid];
+        if (bias) wx = wx + p_bias;
+        const float xn = scale ? bn_affine(wx, p_sc, p_sh) : wx;
+        const float u = al * u_prev + oma * xn;                              // snns.py:822
+        u_io[(size_t)b * C + tid] = u;
+        row[tid] = u;
+    }
+    __syncthreads();
+    // one thread: the softmax in the arithmetic (and the order) of the whole-sequence kernel's thread = time phase
+    if (tid == 0) {
+        const float den = ro_softmax_row(row, C);
+        for (int c = 0; c < C; ++c) row[c] = row[c] / den;
+    }
+    __syncthreads();
+    if (act) out[(size_t)b * C + tid] = out_prev + row[tid];                 // snns.py:823
+}
+
+template <int RT, bool VEC>
+void launch_step(int kind, const StepArgs& a, dim3 grid, hipStream_t st) {
+    switch (kind) {
+        case SPARCH_KIND_LIF: hipLaunchKernelGGL((stream_step_kernel<RT, false, false, VEC>), grid, dim3(SS_NT), 0, st, a); break;
+        case SPARCH_KIND_ADLIF: hipLaunchKernelGGL((stream_step_kernel<RT, true, false, VEC>), grid, dim3(SS_NT), 0, st, a); break;
+        case SPARCH_KIND_RLIF: hipLaunchKernelGGL((stream_step_kernel<RT, false, true, VEC>), grid, dim3(SS_NT), 0, st, a); break;
+        default: hipLaunchKernelGGL((stream_step_kernel<RT, true, true, VEC>), grid, dim3(SS_NT), 0, st, a); break;
+    }
+}
+template <bool VEC>
+void launch_step_rows(int RT, int kind, const StepArgs& a, dim3 grid, hipStream_t st) {
+    switch (RT) {
+        case 1: launch_step<1, VEC>(kind, a, grid, st); break;
+        case 2: launch_step<2, VEC>(kind, a, grid, st); break;
+        case 4: launch_step<4, VEC>(kind, a, grid, st); break;
+        case 8: launch_step<8, VEC>(kind, a, grid, st); break;
+        default: launch_step<16, VEC>(kind, a, grid, st); break;
+    }
+}
+
+bool all16(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (p && !aligned16(p)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int sparch_stream_step_fwd(int kind, int B, int K, int H, int ld, int in_dtype, const void* x, int ldx,
+                                      const float* W, const float* bias, const float* scale, const float* shift,
+                                      const float* alpha, const float* beta, const float* a, const float* b,
+                                      const float* vmask_t, float* u, float* w, const float* s_in, float* s_out,
+                                      uint16_t* s16_out, float theta, uint32_t* spike_count, void* stream) {
+    SPARCH_ENTER();
+    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF && kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF)
+        return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_ADLIF || kind == SPARCH_KIND_RADLIF;
+    const bool rec = kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF;
+    if (in_dtype != 0 && in_dtype != 1) return SPARCH_EINVAL;
+    if (B <= 0 || K <= 0 || H <= 0 || ld < H || ldx < K) return SPARCH_EINVAL;
+    if (!x || !W || !alpha || !u || !s_in || !s_out) return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b || !w)) return SPARCH_EINVAL;
+    if (rec && (!vmask_t || s_in == s_out)) return SPARCH_EINVAL;  // every workgroup reads all of s_in
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!all16({W, vmask_t, u, w, s_in, s_out, s16_out})) return SPARCH_EALIGN;
+    StepArgs g{};
+    g.B = B; g.K = K; g.H = H; g.ld = ld; g.ldx = ldx; g.in_u8 = in_dtype;
+    g.x = x; g.W = W; g.bias = bias; g.scale = scale; g.shift = shift;
+    g.alpha = alpha; g.beta = beta; g.a = a; g.b = b; g.vmask_t = vmask_t;
+    g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out;
+    g.theta = theta; g.spike_count = spike_count;
+    // the smallest row tile that holds the batch: fewer accumulators and LDS reads for the few-row stream
+    const int RT = B >= 9 ? 16 : B >= 5 ? 8 : B >= 3 ? 4 : B;
+    const dim3 grid(cdiv(H, SS_COLS), cdiv(B, RT));
+    if (grid.y > 65535u) return SPARCH_EINVAL;
+    // 16-byte weight loads where every row of W and of vmask_t is aligned, scalar ones otherwise
+    if ((K & 3) == 0 && (!rec || (ld & 3) == 0)) launch_step_rows<true>(RT, kind, g, grid, (hipStream_t)stream);
+    else launch_step_rows<false>(RT, kind, g, grid, (hipStream_t)stream);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+extern "C" int sparch_stream_step_readout(int B, int K, int C, const float* x, int ldx, const float* W,
+                                          const float* bias, const float* scale, const float* shift,
+                                          const float* alpha, float* u, float* out, void* stream) {
+    SPARCH_ENTER();
+    if (B <= 0 || K <= 0 || C <= 0 || C > 256 || ldx < K) return SPARCH_EINVAL;
+    if (!x || !W || !alpha || !u || !out) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (!aligned16(W)) return SPARCH_EALIGN;
+    if ((K & 3) == 0)
+        hipLaunchKernelGGL(stream_step_readout_kernel<true>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, K, C, x, ldx,
+                           W, bias, scale, shift, alpha, u, out);
+    else
+        hipLaunchKernelGGL(stream_step_readout_kernel<false>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, K, C, x,
+                           ldx, W, bias, scale, shift, alpha, u, out);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}

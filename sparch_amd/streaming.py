@@ -16,6 +16,14 @@ library: state in, state out, in place, no (B,T,H) save tensors.
 Everything a forward call derives from the parameters alone — the split planes of W, the packed and masked V, the
 eval-mode BatchNorm fold — is made once (`refresh()` after the parameters change); a chunk step launches the
 projection, the boundary product s @ V of a recurrent layer and the cell, nothing else.
+
+    st = StreamingSNN(net, batch_size, fused=True)
+
+serves the chunk of ONE time step (a live stream) with one launch per layer: `sparch_stream_step_fwd` does the
+projection, the BatchNorm affine, s @ V and the cell for a hidden layer, `sparch_stream_step_readout` the readout
+(csrc/streamstep.hip).  Every workgroup of a recurrent layer reads all of the previous spikes, so those layers keep
+their spike state twice and the host swaps which copy is current after each fused step.  Longer chunks take the
+path above on the same state.
 """
 import numpy as np
 import torch
@@ -46,7 +54,7 @@ class StreamingSNN:
     whole-sequence path; the stream kernels have by then written a half-advanced state over the carried one, so after
     such a report the stream can only be continued from a reset() (or a set_state() of a state saved earlier)."""
 
-    def __init__(self, net, batch_size, graph=False):
+    def __init__(self, net, batch_size, graph=False, fused=False):
         if not getattr(net, "is_snn", False):
             raise ValueError("StreamingSNN: a sparch_amd.SNN (the non-spiking baselines do not stream)")
         if net.bidirectional:
@@ -55,9 +63,18 @@ class StreamingSNN:
         if net.training:
             raise ValueError("StreamingSNN: the network is in training mode — BatchNorm's batch statistics and "
                              "dropout have no streaming meaning; call net.eval() first")
+        if fused and any(mod.normalize and mod.normalization == "layernorm" for mod in net.snn):
+            raise ValueError("StreamingSNN: fused=True does not take LayerNorm layers (a row statistic across the "
+                             "workgroups of a step); use fused=False")
         self.net = net
         self.batch_size = int(batch_size)
         self.graph = bool(graph)
+        self.fused = bool(fused)
+        self._fused_active = self.fused and Fn._prec() == 0
+        self._fg = {}             # fused step, graph=True: {current spike buffers: dict(graph, replays)}, one per parity
+        self._fg_x = self._fg_out = None   # the static input and output both parities share
+        self._fg_dtype = None
+        self._fg_warm = 0
         self.steps_seen = 0
         self.row_steps = np.zeros(self.batch_size, dtype=np.int64)
         self._layers = None
@@ -126,7 +143,7 @@ class StreamingSNN:
                     L.vmask_t = L.vmask.t().contiguous()  # (H_out, H_in): the NT operand of the exact spike product
                 # state buffers: kept across refresh()
                 if old is not None:
-                    for k in ("u", "w", "s", "s16", "count", "out", "binary"):
+                    for k in ("u", "w", "s", "s16", "count", "out", "binary", "s_alt", "s16_alt", "s_first"):
                         setattr(L, k, getattr(old[i], k, None))
                 elif L.readout:
                     L.u = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
@@ -138,9 +155,23 @@ class StreamingSNN:
                     L.s16 = torch.zeros(B, L.Hs, dtype=torch.bfloat16, device=dev) if L.recurrent else None
                     L.count = torch.zeros(L.Hs, dtype=torch.int32, device=dev)
                     L.binary = False  # s holds 0/1 only AND s16 mirrors it (true behind every chunk step)
+                    L.s_alt = L.s16_alt = L.s_first = None
+                if self.fused and L.recurrent and L.s_alt is None:
+                    # the other copy of the spike state: a fused step reads s / writes s_alt, then the host swaps the
+                    # names (its padded columns are never written: they stay zero like those of s)
+                    L.s_alt, L.s16_alt, L.s_first = torch.zeros_like(L.s), torch.zeros_like(L.s16), L.s
                 layers.append(L)
         self._layers, self._prec, self._dev = layers, Fn._prec(), dev
         self._g, self._g_warm = None, 0  # a captured step holds the old operands
+        self._fg, self._fg_x, self._fg_out, self._fg_warm = {}, None, None, 0
+        self._fused_active = self.fused and self._prec == 0  # (the bf16 operand mode takes the chunk path)
+
+    @property
+    def fused_active(self):
+        """True when a step of Tc == 1 takes the fused one-launch-per-layer path (fused=True and fp32 operands)."""
+        if self._layers is not None and self._prec != Fn._prec():
+            return self.fused and Fn._prec() == 0  # (the next use refreshes)
+        return self._fused_active
 
     def _ensure(self):
         if self._layers is None or self._prec != Fn._prec():  # (the V pack is made for one operand mode)
@@ -356,9 +387,18 @@ class StreamingSNN:
         if x.ndim != 3 or x.shape[0] != self.batch_size or x.shape[1] < 1 or x.shape[2] != self._layers[0].K:
             raise ValueError(f"StreamingSNN.step: a ({self.batch_size}, Tc >= 1, {self._layers[0].K}) chunk, got "
                              f"{tuple(x.shape)}")
+        Tc = x.shape[1]
+        if self._fused_active:
+            if Tc == 1:
+                with torch.no_grad():
+                    out = self._fused_step(x)
+                self.steps_seen += 1
+                self.row_steps += 1
+                return out
+            if self.graph:
+                self._primary_spikes()
         if x.dtype != torch.uint8:
             x = Fn._f32c(x)
-        Tc = x.shape[1]
         out = None
         with torch.no_grad():
             if self.graph:
@@ -397,6 +437,99 @@ class StreamingSNN:
         self._g_replays += 1
         self._emit(self._g["taps"])
         return self._g["out"]
+
+    # ------------------------------------------------------------------ the fused step (Tc == 1)
+    def _spike_key(self):
+        return tuple(L.s.data_ptr() for L in self._layers if L.recurrent)
+
+    def _primary_spikes(self):
+        """Make the first spike buffer of every recurrent layer the current one (a copy after an odd number of fused
+        steps): the captured chunk step of `_graph_step` holds the pointers it was captured with."""
+        for L in self._layers:
+            if L.recurrent and L.s is not L.s_first:
+                L.s_alt.copy_(L.s)
+                L.s16_alt.copy_(L.s16)
+                L.s, L.s_alt, L.s16, L.s16_alt = L.s_alt, L.s, L.s16_alt, L.s16
+
+    def _fused_launch(self, x, ldx):
+        """The step's launches on the current buffers: one per layer.  x (B,1,K) fp32 or uint8 with unit stride
+        along K and row stride ldx.  Returns the readout's accumulator, or the last layer's fresh spike buffer."""
+        B = self.batch_size
+        src, dt = x, int(x.dtype == torch.uint8)
+        for L in self._layers:
+            if L.readout:
+                check(lib.sparch_stream_step_readout(B, L.K, L.H, ptr(src), ldx, ptr(L.W), ptr(L.Wb), ptr(L.scale),
+                                                     ptr(L.shift), ptr(L.p["alpha"]), ptr(L.u), ptr(L.out),
+                                                     Fn._stream()), "sparch_stream_step_readout")
+                return L.out
+            p = L.p
+            s_out, s16_out = (L.s_alt, L.s16_alt) if L.recurrent else (L.s, None)
+            check(lib.sparch_stream_step_fwd(KIND[L.kind], B, L.K, L.H, L.Hs, dt, ptr(src), ldx, ptr(L.W), ptr(L.Wb),
+                                             ptr(L.scale), ptr(L.shift), ptr(p["alpha"]), ptr(p.get("beta")),
+                                             ptr(p.get("a")), ptr(p.get("b")), ptr(L.vmask_t) if L.recurrent else None,
+                                             ptr(L.u), ptr(L.w), ptr(L.s), ptr(s_out), ptr(s16_out), L.theta,
+                                             ptr(L.count), Fn._stream()), "sparch_stream_step_fwd")
+            src, ldx, dt = s_out, L.Hs, 0
+        return src
+
+    def _fused_swap(self):
+        """Behind a fused step (launched or replayed): the written spike buffers become the current ones."""
+        for L in self._layers:
+            if L.readout:
+                continue
+            if L.recurrent:
+                L.s, L.s_alt, L.s16, L.s16_alt = L.s_alt, L.s, L.s16_alt, L.s16
+            L.binary = True
+
+    def _fused_step(self, x):
+        layers = self._layers
+        if x.dtype not in (torch.uint8, torch.float32) or x.stride(2) != 1:
+            x = x.contiguous() if x.dtype == torch.uint8 else Fn._f32c(x)
+        ldx = max(int(x.stride(0)), layers[0].K)  # a (B,1,K) slice of a longer sequence is read where it lies
+        ro = layers[-1].readout
+        hidden = [L for L in layers if not L.readout]
+        g = self._fused_graph(x) if self.graph else None
+        if g is None:
+            out = self._fused_launch(x, ldx)
+            self._fused_swap()
+            out = out.clone() if ro else out[:, :hidden[-1].H].unsqueeze(1).clone()
+        else:
+            self._fg_x.copy_(x, non_blocking=True)
+            g["graph"].replay()
+            g["replays"] += 1
+            self._fused_swap()
+            out = self._fg_out
+        if self._spike_tap is not None:
+            for i, L in enumerate(hidden):
+                self._spike_tap(i, L.s[:, :L.H].unsqueeze(1))
+        return out
+
+    def _fused_graph(self, x):
+        """The captured three-launch chain for the current parity (captured on first need, after one eager fused
+        step, for the first input dtype seen); None = launch eagerly."""
+        if self._fg_dtype is None:
+            self._fg_dtype = x.dtype
+        if x.dtype != self._fg_dtype:
+            return None
+        if self._fg_warm < 1:
+            self._fg_warm += 1
+            return None
+        key = self._spike_key()
+        g = self._fg.get(key)
+        if g is None:
+            layers = self._layers
+            last = layers[-1]
+            if self._fg_x is None:
+                self._fg_x = torch.empty(x.shape, dtype=x.dtype, device=self._dev)
+                self._fg_out = (torch.empty_like(last.out) if last.readout else
+                                torch.empty(self.batch_size, 1, last.H, dtype=torch.float32, device=self._dev))
+            g = {"graph": torch.cuda.CUDAGraph(), "replays": 0}
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g["graph"]):
+                out = self._fused_launch(self._fg_x, layers[0].K)
+                self._fg_out.copy_(out if last.readout else out[:, :last.H].unsqueeze(1))
+            self._fg[key] = g
+        return g
 
 
 # ---------------------------------------------------------------------------------------- raw audio

@@ -16,6 +16,12 @@ recurrent kernels), repeated `--rounds` times — its own min / max over the rou
 exceed to mean anything.
 
 One JSON object per line goes to --out (default profiles/stream_bench.jsonl) and to stdout.
+
+--fused: the chunk of one step also through `StreamingSNN(fused=True)` (one launch per layer, csrc/streamstep.hip).  At
+Tc = 1 the four modes eager / graph / fused / fused+graph are then timed stream by stream in turn (eager, graph, fused,
+fused+graph, eager, ...), `--streams` streams each, and every row carries its own min and max over those streams;
+a `fused_vs_unfused` line per B says whether both fused modes lie below the unfused rows' minimum by more than the
+unfused rows' own min-max spread.  Defaults then: --batches 1 8 32 256, --out profiles/stream_bench_fused.jsonl.
 """
 import argparse
 import json
@@ -29,8 +35,9 @@ if ROOT not in sys.path:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bench.jsonl"))
-    ap.add_argument("--batches", type=int, nargs="+", default=[1, 32, 256])
+    ap.add_argument("--fused", action="store_true", help="add the fused one-step path at Tc = 1 (see above)")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batches", type=int, nargs="+", default=None)
     ap.add_argument("--chunks", type=int, nargs="+", default=[1, 10, 50, 250])
     ap.add_argument("--T", type=int, default=250)
     ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of whole forward / Tc = T stream")
@@ -38,6 +45,10 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 1024, 35])
     ap.add_argument("--channels", type=int, default=700)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "stream_bench_fused.jsonl" if args.fused else "stream_bench.jsonl")
+    if args.batches is None:
+        args.batches = [1, 8, 32, 256] if args.fused else [1, 32, 256]
 
     import torch
 
@@ -89,6 +100,44 @@ def main():
                 setattr(_capi.lib, name, f)
         return n_calls[0]
 
+    def fused_rows(B, chunks):
+        """Tc = 1: the four modes, one stream each in turn, `--streams` times."""
+        modes = {"eager": (False, False), "graph": (True, False), "fused": (False, True), "fused+graph": (True, True)}
+        sts, calls, ms = {}, {}, {m: [] for m in modes}
+
+        def stream(st):
+            out = None
+            for c in chunks:
+                out = st.step(c)
+            return out
+
+        for mode, (graph, fused) in modes.items():
+            st = sts[mode] = sparch_amd.StreamingSNN(net, B, graph=graph, fused=fused)
+            st.reset()
+            stream(st)                        # warm-up (graph: the eager pass, then the captures)
+            stream(st)
+            Fn.check_status(dev)
+            calls[mode] = None if graph else count_calls(lambda: st.step(chunks[0]))
+        for _ in range(args.streams):
+            for mode in modes:
+                ms[mode].append(timed(lambda: stream(sts[mode]), 1) / len(chunks))
+        Fn.check_status(dev)
+        for mode, (graph, fused) in modes.items():
+            st, v = sts[mode], ms[mode]
+            replayed = None if not graph else (bool(st._fg) and all(g["replays"] > 0 for g in st._fg.values())
+                                               if fused else bool(st._g is not None))
+            emit({"what": "stream", "B": B, "Tc": 1, "mode": mode, "ms_per_chunk": sum(v) / len(v),
+                  "ms_per_chunk_min": min(v), "ms_per_chunk_max": max(v), "ms_per_chunk_streams": v,
+                  "us_per_step": 1e3 * sum(v) / len(v), "lib_calls_per_chunk": calls[mode], "graph_replayed": replayed})
+        unf = ms["eager"] + ms["graph"]
+        lo, spread = min(unf), max(max(ms["eager"]) - min(ms["eager"]), max(ms["graph"]) - min(ms["graph"]))
+        emit({"what": "fused_vs_unfused", "B": B, "Tc": 1, "unfused_min_ms": lo, "unfused_spread_ms": spread,
+              "fused_max_ms": max(ms["fused"]), "fused_graph_max_ms": max(ms["fused+graph"]),
+              "unfused_min_over_fused": lo / (sum(ms["fused"]) / len(ms["fused"])),
+              "unfused_min_over_fused_graph": lo / (sum(ms["fused+graph"]) / len(ms["fused+graph"])),
+              "fused_clears_margin": bool(max(ms["fused"]) < lo - spread),
+              "fused_graph_clears_margin": bool(max(ms["fused+graph"]) < lo - spread)})
+
     for B in args.batches:
         g = torch.Generator().manual_seed(4321 + B)
         x = (torch.rand(B, T, C, generator=g) < 0.05).float().to(dev)
@@ -99,6 +148,9 @@ def main():
 
         for Tc in args.chunks:
             chunks = [x[:, t0:t0 + Tc].contiguous() for t0 in range(0, T, Tc)]
+            if args.fused and Tc == 1:
+                fused_rows(B, chunks)
+                continue
             for mode in ("eager", "graph"):
                 st = sparch_amd.StreamingSNN(net, B, graph=(mode == "graph"))
 
