@@ -17,6 +17,7 @@
 // KC fragments are single 16-byte LDS reads with no transpose anywhere.
 // fp32 MFMA is an exact k-ordered fmaf chain (one rounding per product).
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -236,15 +237,6 @@ __global__ void zero_diag_kernel(float* __restrict__ C, int n, int ldc) {
     if (i < n) C[(size_t)i * ldc + i] = 0.f;
 }
 
-int choose_splits(int M, int N, int K) {
-    const int tiles = cdiv(M, BM) * cdiv(N, BN);
-    const int kt = cdiv(K, BK);
-    int s = 1;
-    // aim for ~1024 workgroups (4 per CU), at least 8 K-tiles per split
-    while (tiles * s < 1024 && kt / (s * 2) >= 8) s *= 2;
-    return s;
-}
-
 template <bool A_KM, bool B_KM, int EPI>
 int launch(GemmArgs& g, int splits, hipStream_t st) {
     const int tiles = cdiv(g.M, BM) * cdiv(g.N, BN);
@@ -254,19 +246,28 @@ int launch(GemmArgs& g, int splits, hipStream_t st) {
     return SPARCH_OK;
 }
 
+using gemm_plan::Form;
+
+// a direct product into C (sparch_gemm_tn re-points it at the slabs)
+GemmArgs direct_args(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc) {
+    GemmArgs g{};
+    g.A = A; g.B = B; g.C = C;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.k_per_split = gemm_plan::k_per_split(K, BK); g.c_split_stride = 0;
+    g.a_vec = aligned16(A) && (lda % 4 == 0);
+    g.b_vec = aligned16(B) && (ldb % 4 == 0);
+    return g;
+}
+
 }  // namespace
 
 extern "C" int sparch_gemm_nt(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                               float* C, int ldc, const float* bias, float* colstat_ws, void* stream) {
     SPARCH_ENTER();
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    GemmArgs g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
+    if (!gemm_plan::dims_ok(Form::NT, M, N, K, lda, ldb, ldc) || !A || !B || !C) return SPARCH_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    GemmArgs g = direct_args(M, N, K, A, lda, B, ldb, C, ldc);
+    g.bias = bias; g.colstat = colstat_ws;
     if (colstat_ws) return launch<false, false, EPI_BIAS | EPI_STATS>(g, 1, st);
     if (bias) return launch<false, false, EPI_BIAS>(g, 1, st);
     return launch<false, false, EPI_NONE>(g, 1, st);
@@ -275,35 +276,26 @@ extern "C" int sparch_gemm_nt(int M, int N, int K, const float* A, int lda, cons
 extern "C" int sparch_gemm_nn(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                               float* C, int ldc, void* stream) {
     SPARCH_ENTER();
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < N || ldc < N) return SPARCH_EINVAL;
-    GemmArgs g{};
-    g.A = A; g.B = B; g.C = C;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    return launch<false, true, EPI_NONE>(g, 1, (hipStream_t)stream);
+    if (!gemm_plan::dims_ok(Form::NN, M, N, K, lda, ldb, ldc) || !A || !B || !C) return SPARCH_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs g = direct_args(M, N, K, A, lda, B, ldb, C, ldc);
+    return launch<false, true, EPI_NONE>(g, 1, st);
 }
 
 extern "C" size_t sparch_gemm_tn_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    return (size_t)choose_splits(M, N, K) * M * N * sizeof(float);
+    return gemm_plan::slab_bytes(gemm_plan::splits_doubling(M, N, K, BM, BN, BK), M, N);
 }
 
 extern "C" int sparch_gemm_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                               float* C, int ldc, int zero_diag, int accumulate, void* ws, size_t ws_bytes,
                               void* stream) {
     SPARCH_ENTER();
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < M || ldb < N || ldc < N) return SPARCH_EINVAL;
+    if (!gemm_plan::dims_ok(Form::TN, M, N, K, lda, ldb, ldc) || !A || !B || !C) return SPARCH_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int splits = choose_splits(M, N, K);
-    GemmArgs g{};
-    g.A = A; g.B = B;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
+    const int splits = gemm_plan::splits_doubling(M, N, K, BM, BN, BK);
+    GemmArgs g = direct_args(M, N, K, A, lda, B, ldb, C, ldc);
     if (splits == 1 && !accumulate) {
-        g.C = C; g.ldc = ldc; g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0;
         int rc = launch<true, true, EPI_NONE>(g, 1, st);
         if (rc != SPARCH_OK || !zero_diag) return rc;
         const int n = M < N ? M : N;
@@ -311,10 +303,9 @@ extern "C" int sparch_gemm_tn(int M, int N, int K, const float* A, int lda, cons
         SPARCH_CHECK_LAUNCH();
         return SPARCH_OK;
     }
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
+    if (!ws || ws_bytes < gemm_plan::slab_bytes(splits, M, N)) return SPARCH_EWORKSPACE;
     g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
+    g.k_per_split = gemm_plan::k_per_split(K, BK, splits);
     int rc = launch<true, true, EPI_NONE>(g, splits, st);
     if (rc != SPARCH_OK) return rc;
     const size_t total = (size_t)M * N;

@@ -17,9 +17,11 @@
 //       -> MFMA fragment = one ds_read_b128 (conflict-free);
 //   KM operand (element (k,col) at p[k*ld+col]): LDS image [k][128 col] bf16, 320-byte rows
 //       -> MFMA fragment = two ds_read_b64_tr_b16 (hardware transpose read, conflict-free).
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -750,19 +752,10 @@ int target_wgs(int occ) {
 }
 template <int MODE>
 int choose_splits(int M, int N, int K) {  // TN products only
-    if (sparch_operand_bf16()) {  // every pipelined kernel of that mode works on 256 x 256 tiles
-        using SB = Shape<MODE, true, true>;
-        const int tiles_b = cdiv(M, SB::BM) * cdiv(N, SB::BN);
-        int sb = target_wgs(1) / tiles_b;
-        if (sb > cdiv(K, BK) / 8) sb = cdiv(K, BK) / 8;
-        return sb < 1 ? 1 : sb;
-    }
+    using SB = Shape<MODE, true, true>;   // bf16 operand mode: every pipelined kernel works on 256 x 256 tiles
     using S = Shape<MODE, true, MODE != 2>;
-    const int tiles = cdiv(M, S::BM) * cdiv(N, S::BN);
-    const int kt = cdiv(K, BK);
-    int s = target_wgs(1) / tiles;  // the pipelined kernel runs one workgroup per CU
-    if (s > kt / 8) s = kt / 8;
-    return s < 1 ? 1 : s;
+    const bool b = sparch_operand_bf16();
+    return gemm_plan::splits_for(M, N, K, b ? SB::BM : S::BM, b ? SB::BN : S::BN, BK, target_wgs(1));
 }
 
 template <bool A_KM, bool B_KM, int MODE, int EPI, bool S16, int NP = 3>
@@ -870,51 +863,127 @@ extern "C" int sparch_split3(size_t n, const float* x, uint16_t* planes, void* s
     return SPARCH_OK;
 }
 
+// ---- The matrix products' entry points.  Each is GEMM_ENTER, the kernel arguments (make_args: a direct product into
+// C), what is particular to it, and one of two tails: the launch, or cut_product (the product cut into K ranges: slabs
+// in the workspace, the launch, the reduction into C).  Refusals, in this order: an unknown precision, bad sizes /
+// leading dimensions / NULLs (SPARCH_EINVAL, all in GEMM_ENTER), what the entry itself refuses (SPARCH_EINVAL), then
+// a missing or short workspace (SPARCH_EWORKSPACE, cut_product).  No entry refuses for alignment: a misaligned base or
+// an odd leading dimension only clears a_vec / b_vec.  The arithmetic is gemm_plan.h's.
+namespace {
+using gemm_plan::Form;
+
+#define GEMM_ENTER(form, pointers_set)            \
+    SPARCH_ENTER();                               \
+    PrecisionScope prec_scope_(precision);        \
+    hipStream_t st = (hipStream_t)stream;         \
+    if (!prec_scope_.ok || !gemm_plan::dims_ok(form, M, N, K, lda, ldb, ldc) || !(pointers_set)) return SPARCH_EINVAL
+
+// An operand as a kernel reads it; q = its elements per 16 bytes (4 fp32, 8 bf16).  (A NULL base — an operand given
+// by its planes alone — counts as aligned.)
+struct Operand {
+    const void* p; int ld, q;
+    bool vec() const { return aligned16(p) && ld % q == 0; }
+};
+void set_a(SArgs& g, Operand a) { g.A = static_cast<const float*>(a.p); g.lda = a.ld; g.a_vec = a.vec(); }
+void set_b(SArgs& g, Operand b) { g.B = static_cast<const float*>(b.p); g.ldb = b.ld; g.b_vec = b.vec(); }
+// a direct product into C; cut_product re-points it at the slabs
+SArgs make_args(int M, int N, int K, Operand a, Operand b, float* C, int ldc, float scale = 1.0f,
+                const float* bias = nullptr, float* colstat = nullptr) {
+    SArgs g{};
+    g.M = M; g.N = N; g.K = K; g.scale = scale;
+    set_a(g, a); set_b(g, b);
+    g.C = C; g.ldc = ldc; g.c_split_stride = 0; g.k_per_split = gemm_plan::k_per_split(K, BK);
+    g.bias = bias; g.colstat = colstat;
+    return g;
+}
+// The epilogue a call asks for: column statistics (with the bias), else the bias, else none — but never less than
+// MIN_EPI (the gated pairs exist with a bias epilogue only).  WP: B's planes may be at hand (launch_wp).
+template <bool WP, bool A_KM, bool B_KM, int MODE, bool S16 = false, int MIN_EPI = EPI_NONE>
+int launch_epi(SArgs& g, hipStream_t st) {
+    auto go = [&](auto epi) {
+        if constexpr (WP) return launch_wp<A_KM, B_KM, MODE, decltype(epi)::value, S16>(g, 1, st);
+        else return launch<A_KM, B_KM, MODE, decltype(epi)::value, S16>(g, 1, st);
+    };
+    if (g.colstat) return go(std::integral_constant<int, EPI_BIAS | EPI_STATS>{});
+    if constexpr (MIN_EPI == EPI_NONE)
+        if (!g.bias) return go(std::integral_constant<int, EPI_NONE>{});
+    return go(std::integral_constant<int, EPI_BIAS>{});
+}
+
+// The product cut into `splits` K ranges: each range's partial product goes to its slab in the workspace (run(): the
+// launch, or the gated pair of them, which must leave g.N at C's width), then one kernel adds the slabs up into C in
+// fixed order.  slab_width: row stride of the slabs where it is not N (sparch_gemm_auto16_tn).
+struct Cut {
+    int zero_diag, accumulate;
+    void* ws; size_t ws_bytes;
+    int slab_width = 0;
+};
+template <class Run>
+int cut_product(SArgs& g, int splits, const Cut& c, hipStream_t st, Run run) {
+    float* const C = g.C;
+    const int ldc = g.ldc, width = c.slab_width ? c.slab_width : g.N;
+    if (!c.ws || c.ws_bytes < gemm_plan::slab_bytes(splits, g.M, width)) return SPARCH_EWORKSPACE;
+    g.C = (float*)c.ws; g.ldc = width; g.c_split_stride = (size_t)g.M * width;
+    g.k_per_split = gemm_plan::k_per_split(g.K, BK, splits);
+    if (int rc = run()) return rc;
+    const size_t total = (size_t)g.M * g.N;
+    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)c.ws,
+                       C, g.M, g.N, ldc, splits, c.zero_diag, c.accumulate, c.slab_width);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+// An operand whose exactness in bf16 is known only on the device (*flag): both kernels are enqueued, the single-plane
+// one for the exact case first and the six-term one second; each returns at once unless the flag is what it wants.
+template <class Exact, class Six>
+int gated(SArgs& g, const uint32_t* flag, Exact exact, Six six) {
+    g.gate = flag; g.e_exact = 1; g.gate_want = 1;
+    if (int rc = exact()) return rc;
+    g.gate_want = 0;
+    return six();
+}
+
+// K ranges of the dense NT / NN products with a SMALL M*N and a long K (the per-step recurrent products of the gated
+// baselines: 256 x 2048 x 1024 is 16 tiles on 256 CUs)
+int small_splits(int M, int N, int K) {
+    using S = Shape<2, true>;
+    return gemm_plan::splits_for(M, N, K, S::BM, S::BN, BK, target_wgs(1));
+}
+
+// spike_side 0 / 1: A / B is the spike operand (s16: given as a bf16 plane)
+int spike_tn(SArgs g, int spike_side, bool s16, const Cut& c, hipStream_t st) {
+    if (spike_side != 0 && spike_side != 1) return SPARCH_EINVAL;
+    const int splits = spike_side == 0 ? choose_splits<0>(g.M, g.N, g.K) : choose_splits<1>(g.M, g.N, g.K);
+    return cut_product(g, splits, c, st, [&] {
+        if (s16) return spike_side == 0 ? launch<true, true, 0, EPI_NONE, true>(g, splits, st)
+                                        : launch<true, true, 1, EPI_NONE, true>(g, splits, st);
+        return spike_side == 0 ? launch<true, true, 0, EPI_NONE>(g, splits, st)
+                               : launch<true, true, 1, EPI_NONE>(g, splits, st);
+    });
+}
+// no bias / statistics epilogue; no workspace is needed when one range suffices
+template <bool B_KM>
+int gemm6_splitk(SArgs g, const Cut& c, hipStream_t st) {
+    const int splits = small_splits(g.M, g.N, g.K);
+    auto run = [&] { return launch<false, B_KM, 2, EPI_NONE>(g, splits, st); };
+    return splits > 1 ? cut_product(g, splits, c, st, run) : run();
+}
+}  // namespace
+
 extern "C" int sparch_gemm_spike_nt(int M, int N, int K, const float* A_spk, int lda, float scale, const float* B,
                                     int ldb, float* C, int ldc, const float* bias, float* colstat_ws,
                                     void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A_spk || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A_spk; g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = scale;
-    g.a_vec = aligned16(A_spk) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (colstat_ws) return launch<false, false, 0, EPI_BIAS | EPI_STATS>(g, 1, st);
-    if (bias) return launch<false, false, 0, EPI_BIAS>(g, 1, st);
-    return launch<false, false, 0, EPI_NONE>(g, 1, st);
+    GEMM_ENTER(Form::NT, A_spk && B && C);
+    SArgs g = make_args(M, N, K, {A_spk, lda, 4}, {B, ldb, 4}, C, ldc, scale, bias, colstat_ws);
+    return launch_epi<false, false, false, 0>(g, st);
 }
 
 extern "C" int sparch_gemm_spike_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                     int spike_side, float scale, float* C, int ldc, int zero_diag,
                                     int accumulate, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < M || ldb < N || ldc < N) return SPARCH_EINVAL;
-    if (spike_side != 0 && spike_side != 1) return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int splits = spike_side == 0 ? choose_splits<0>(M, N, K) : choose_splits<1>(M, N, K);
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = scale;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    int rc = spike_side == 0 ? launch<true, true, 0, EPI_NONE>(g, splits, st)
-                             : launch<true, true, 1, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    GEMM_ENTER(Form::TN, A && B && C);
+    return spike_tn(make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc, scale), spike_side, false,
+                    {zero_diag, accumulate, ws, ws_bytes}, st);
 }
 
 // ---- the spike operand as a bf16 plane (entries 0 / 1.0, written by the cell kernels next to their fp32
@@ -922,84 +991,34 @@ extern "C" int sparch_gemm_spike_tn(int M, int N, int K, const float* A, int lda
 extern "C" int sparch_gemm_spike16_nt(int M, int N, int K, const uint16_t* A_spk16, int lda, float scale,
                                       const float* B, int ldb, float* C, int ldc, const float* bias,
                                       float* colstat_ws, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A_spk16 || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = reinterpret_cast<const float*>(A_spk16); g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = scale;
-    g.a_vec = aligned16(A_spk16) && (lda % 8 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (colstat_ws) return launch<false, false, 0, EPI_BIAS | EPI_STATS, true>(g, 1, st);
-    if (bias) return launch<false, false, 0, EPI_BIAS, true>(g, 1, st);
-    return launch<false, false, 0, EPI_NONE, true>(g, 1, st);
+    GEMM_ENTER(Form::NT, A_spk16 && B && C);
+    SArgs g = make_args(M, N, K, {A_spk16, lda, 8}, {B, ldb, 4}, C, ldc, scale, bias, colstat_ws);
+    return launch_epi<false, false, false, 0, true>(g, st);
 }
 
 extern "C" int sparch_gemm_spike16_nt_wp(int M, int N, int K, const uint16_t* A_spk16, int lda, float scale,
                                          const float* B, const uint16_t* B_planes, int ldb, float* C, int ldc,
                                          const float* bias, float* colstat_ws, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A_spk16 || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = reinterpret_cast<const float*>(A_spk16); g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
+    GEMM_ENTER(Form::NT, A_spk16 && B && C);
+    SArgs g = make_args(M, N, K, {A_spk16, lda, 8}, {B, ldb, 4}, C, ldc, scale, bias, colstat_ws);
     g.Bp = B_planes; g.bp_stride = (size_t)N * ldb;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = scale;
-    g.a_vec = aligned16(A_spk16) && (lda % 8 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (colstat_ws) return launch_wp<false, false, 0, EPI_BIAS | EPI_STATS, true>(g, 1, st);
-    if (bias) return launch_wp<false, false, 0, EPI_BIAS, true>(g, 1, st);
-    return launch_wp<false, false, 0, EPI_NONE, true>(g, 1, st);
+    return launch_epi<true, false, false, 0, true>(g, st);
 }
 
 extern "C" int sparch_gemm6_nn_wp(int M, int N, int K, const float* A, int lda, const float* B,
                                   const uint16_t* B_planes, int ldb, float* C, int ldc, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < N || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A; g.B = B; g.C = C; g.Bp = B_planes; g.bp_stride = (size_t)K * ldb;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    return launch_wp<false, true, 2, EPI_NONE>(g, 1, (hipStream_t)stream);
+    GEMM_ENTER(Form::NN, A && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc);
+    g.Bp = B_planes; g.bp_stride = (size_t)K * ldb;
+    return launch_wp<false, true, 2, EPI_NONE>(g, 1, st);
 }
 
 extern "C" int sparch_gemm_spike16_tn(int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                                       int spike_side, float scale, float* C, int ldc, int zero_diag,
                                       int accumulate, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < M || ldb < N || ldc < N) return SPARCH_EINVAL;
-    if (spike_side != 0 && spike_side != 1) return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int splits = spike_side == 0 ? choose_splits<0>(M, N, K) : choose_splits<1>(M, N, K);
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = static_cast<const float*>(A); g.B = static_cast<const float*>(B);
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = scale;
-    g.a_vec = aligned16(A) && (lda % (spike_side == 0 ? 8 : 4) == 0);
-    g.b_vec = aligned16(B) && (ldb % (spike_side == 1 ? 8 : 4) == 0);
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    int rc = spike_side == 0 ? launch<true, true, 0, EPI_NONE, true>(g, splits, st)
-                             : launch<true, true, 1, EPI_NONE, true>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    GEMM_ENTER(Form::TN, A && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, spike_side == 0 ? 8 : 4}, {B, ldb, spike_side == 1 ? 8 : 4}, C, ldc, scale);
+    return spike_tn(g, spike_side, true, {zero_diag, accumulate, ws, ws_bytes}, st);
 }
 
 // C[M,N] = A[M,K] * B[K,N], BOTH operands given as their three exact bf16 planes (A_planes: 3 x M x lda,
@@ -1007,18 +1026,11 @@ extern "C" int sparch_gemm_spike16_tn(int M, int N, int K, const void* A, int ld
 // does not apply — A may be NULL when the caller knows it does (sparch_gemm6_nn_pp_applies).
 extern "C" int sparch_gemm6_nn_pp(int M, int N, int K, const float* A, const uint16_t* A_planes, int lda, const float* B,
                                   const uint16_t* B_planes, int ldb, float* C, int ldc, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || (!A && !A_planes) || !B || !C || lda < K || ldb < N || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A; g.B = B; g.C = C; g.Bp = B_planes; g.bp_stride = (size_t)K * ldb;
+    GEMM_ENTER(Form::NN, (A || A_planes) && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc);
     g.Ap = A_planes; g.ap_stride = (size_t)M * lda;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.a_vec = (A ? aligned16(A) : true) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    return launch_ap<false, true, 2, EPI_NONE, false, true>(g, 1, (hipStream_t)stream);
+    g.Bp = B_planes; g.bp_stride = (size_t)K * ldb;
+    return launch_ap<false, true, 2, EPI_NONE, false, true>(g, 1, st);
 }
 
 // C[M,N] (+)= A[K,M]^T * B[K,N] with B a bf16 spike plane (as sparch_gemm_spike16_tn, spike_side = 1) and the dense A
@@ -1026,149 +1038,55 @@ extern "C" int sparch_gemm6_nn_pp(int M, int N, int K, const float* A, const uin
 extern "C" int sparch_gemm_spike16_tn_ap(int M, int N, int K, const float* A, const uint16_t* A_planes, int lda,
                                          const uint16_t* B16, int ldb, float scale, float* C, int ldc, int zero_diag,
                                          int accumulate, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || (!A && !A_planes) || !B16 || !C || lda < M || ldb < N || ldc < N) return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int splits = choose_splits<1>(M, N, K);
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = A; g.B = reinterpret_cast<const float*>(B16);
+    GEMM_ENTER(Form::TN, (A || A_planes) && B16 && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B16, ldb, 8}, C, ldc, scale);
     g.Ap = A_planes; g.ap_stride = (size_t)K * lda;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = scale;
-    g.a_vec = (A ? aligned16(A) : true) && (lda % 4 == 0);
-    g.b_vec = aligned16(B16) && (ldb % 8 == 0);
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    int rc = launch_ap<true, true, 1, EPI_NONE, true, false>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    const int splits = choose_splits<1>(M, N, K);
+    return cut_product(g, splits, {zero_diag, accumulate, ws, ws_bytes}, st,
+                       [&] { return launch_ap<true, true, 1, EPI_NONE, true, false>(g, splits, st); });
 }
 
 // ---- dense x dense on the exact 6-term split (same signatures as the fp32-MFMA entry points in gemm.hip)
 extern "C" int sparch_gemm6_nt(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                                int ldc, const float* bias, float* colstat_ws, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (colstat_ws) return launch<false, false, 2, EPI_BIAS | EPI_STATS>(g, 1, st);
-    if (bias) return launch<false, false, 2, EPI_BIAS>(g, 1, st);
-    return launch<false, false, 2, EPI_NONE>(g, 1, st);
+    GEMM_ENTER(Form::NT, A && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc, 1.0f, bias, colstat_ws);
+    return launch_epi<false, false, false, 2>(g, st);
 }
 
 extern "C" int sparch_gemm6_nn(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                                int ldc, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < N || ldc < N) return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A; g.B = B; g.C = C;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    return launch<false, true, 2, EPI_NONE>(g, 1, (hipStream_t)stream);
+    GEMM_ENTER(Form::NN, A && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc);
+    return launch<false, true, 2, EPI_NONE>(g, 1, st);
 }
 
-// Split-K forms of the dense NT / NN products for SMALL M*N with a long K (the per-step recurrent products of
-// the gated baselines: 256 x 2048 x 1024 is 16 tiles on 256 CUs).  splits = sparch_gemm6_splitk_count(M,N,K)
-// slabs of M*N floats in `ws`, reduced in fixed order; no bias / statistics epilogue.
-namespace {
-int small_splits(int M, int N, int K) {
-    using S = Shape<2, true>;
-    const int tiles = cdiv(M, S::BM) * cdiv(N, S::BN);
-    const int kt = cdiv(K, BK);
-    int s = target_wgs(1) / tiles;
-    if (s > kt / 8) s = kt / 8;      // at least 8 K tiles per workgroup: the pipelined kernel's minimum
-    return s < 1 ? 1 : s;
-}
-template <bool B_KM>
-int gemm6_splitk(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, void* ws,
-                 size_t ws_bytes, hipStream_t st) {
-    const int splits = small_splits(M, N, K);
-    SArgs g{};
-    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    if (splits == 1) {
-        g.C = C; g.ldc = ldc; g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0;
-        return launch<false, B_KM, 2, EPI_NONE>(g, 1, st);
-    }
-    if (!ws || ws_bytes < (size_t)splits * M * N * sizeof(float)) return SPARCH_EWORKSPACE;
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    int rc = launch<false, B_KM, 2, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, 0, 0);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
-}
-}  // namespace
-
+// Split-K forms of the dense NT / NN products (small_splits): sparch_gemm6_splitk_workspace_bytes(M, N, K) bytes of
+// slabs in `ws`, reduced in fixed order.
 extern "C" size_t sparch_gemm6_splitk_workspace_bytes(int M, int N, int K, int precision) {
     PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return 0;
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    if (!prec_scope_.ok || M <= 0 || N <= 0 || K <= 0) return 0;
     const int s = small_splits(M, N, K);
-    return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
+    return s > 1 ? gemm_plan::slab_bytes(s, M, N) : 0;
 }
 extern "C" int sparch_gemm6_nt_splitk(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                       float* C, int ldc, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < K || ldc < N) return SPARCH_EINVAL;
-    return gemm6_splitk<false>(M, N, K, A, lda, B, ldb, C, ldc, ws, ws_bytes, (hipStream_t)stream);
+    GEMM_ENTER(Form::NT, A && B && C);
+    return gemm6_splitk<false>(make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc), {0, 0, ws, ws_bytes}, st);
 }
 extern "C" int sparch_gemm6_nn_splitk(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                       float* C, int ldc, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < N || ldc < N) return SPARCH_EINVAL;
-    return gemm6_splitk<true>(M, N, K, A, lda, B, ldb, C, ldc, ws, ws_bytes, (hipStream_t)stream);
+    GEMM_ENTER(Form::NN, A && B && C);
+    return gemm6_splitk<true>(make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc), {0, 0, ws, ws_bytes}, st);
 }
 
 extern "C" int sparch_gemm6_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                                int ldc, int zero_diag, int accumulate, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < M || ldb < N || ldc < N) return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    GEMM_ENTER(Form::TN, A && B && C);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc);
     const int splits = choose_splits<2>(M, N, K);
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    int rc = launch<true, true, 2, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return cut_product(g, splits, {zero_diag, accumulate, ws, ws_bytes}, st,
+                       [&] { return launch<true, true, 2, EPI_NONE>(g, splits, st); });
 }
 
 // ---- operand whose exactness in bf16 is known only on the device
@@ -1201,60 +1119,24 @@ extern "C" int sparch_flag_bf16_exact(size_t n, const float* x, uint32_t* flag, 
 extern "C" int sparch_gemm_auto_nt(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                    float* C, int ldc, const float* bias, float* colstat_ws,
                                    const uint32_t* a_exact_flag, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < K || ldb < K || ldc < N || !a_exact_flag)
-        return SPARCH_EINVAL;
-    SArgs g{};
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.gate = a_exact_flag; g.e_exact = 1;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    g.gate_want = 1;  // A is bf16-exact: single plane for A, three for B
-    if (colstat_ws) rc = launch<false, false, 0, EPI_BIAS | EPI_STATS>(g, 1, st);
-    else rc = launch<false, false, 0, EPI_BIAS>(g, 1, st);
-    if (rc != SPARCH_OK) return rc;
-    g.gate_want = 0;  // otherwise: both operands split, six cross terms
-    if (colstat_ws) return launch<false, false, 2, EPI_BIAS | EPI_STATS>(g, 1, st);
-    return launch<false, false, 2, EPI_BIAS>(g, 1, st);
+    GEMM_ENTER(Form::NT, A && B && C && a_exact_flag);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc, 1.0f, bias, colstat_ws);
+    return gated(g, a_exact_flag,  // A is bf16-exact: single plane for A, three for B; otherwise six cross terms
+                 [&] { return launch_epi<false, false, false, 0, false, EPI_BIAS>(g, st); },
+                 [&] { return launch_epi<false, false, false, 2, false, EPI_BIAS>(g, st); });
 }
 
 extern "C" int sparch_gemm_auto_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                    float* C, int ldc, int zero_diag, int accumulate,
                                    const uint32_t* b_exact_flag, void* ws, size_t ws_bytes, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || lda < M || ldb < N || ldc < N || !b_exact_flag)
-        return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    GEMM_ENTER(Form::TN, A && B && C && b_exact_flag);
+    SArgs g = make_args(M, N, K, {A, lda, 4}, {B, ldb, 4}, C, ldc);
     // one split count for both gated kernels: only one of them runs, and the reduction needs one number
     const int splits = choose_splits<1>(M, N, K);
-    const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.C = (float*)ws; g.ldc = N; g.c_split_stride = (size_t)M * N;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    g.gate = b_exact_flag; g.e_exact = 1;
-    g.gate_want = 1;
-    int rc = launch<true, true, 1, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    g.gate_want = 0;
-    rc = launch<true, true, 2, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return cut_product(g, splits, {zero_diag, accumulate, ws, ws_bytes}, st, [&] {
+        return gated(g, b_exact_flag, [&] { return launch<true, true, 1, EPI_NONE>(g, splits, st); },
+                     [&] { return launch<true, true, 2, EPI_NONE>(g, splits, st); });
+    });
 }
 
 // ---- the same check that ALSO writes the bf16 plane of x (upper halves; the exact values when the flag stays 1):
@@ -1299,71 +1181,33 @@ extern "C" int sparch_plane_bf16_exact(int M, int K, const float* x, int ldx, ui
 extern "C" int sparch_gemm_auto16_nt(int M, int N, int K, const float* A, int lda, const uint16_t* A16, int lda16,
                                      const float* B, int ldb, float* C, int ldc, const float* bias,
                                      float* colstat_ws, const uint32_t* a_exact_flag, void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !A16 || !B || !C || lda < K || lda16 < K || ldb < K || ldc < N ||
-        !a_exact_flag)
-        return SPARCH_EINVAL;
-    SArgs g{};
-    g.B = B; g.C = C; g.bias = bias; g.colstat = colstat_ws;
-    g.M = M; g.N = N; g.K = K; g.ldb = ldb; g.ldc = ldc;
-    g.k_per_split = cdiv(K, BK) * BK; g.c_split_stride = 0; g.scale = 1.0f;
-    g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.gate = a_exact_flag; g.e_exact = 1;
-    hipStream_t st = (hipStream_t)stream;
-    g.A = reinterpret_cast<const float*>(A16); g.lda = lda16;
-    g.a_vec = aligned16(A16) && (lda16 % 8 == 0);
-    g.gate_want = 1;
-    int rc = colstat_ws ? launch<false, false, 0, EPI_BIAS | EPI_STATS, true>(g, 1, st)
-                        : launch<false, false, 0, EPI_BIAS, true>(g, 1, st);
-    if (rc != SPARCH_OK) return rc;
-    g.A = A; g.lda = lda; g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.gate_want = 0;
-    if (colstat_ws) return launch<false, false, 2, EPI_BIAS | EPI_STATS>(g, 1, st);
-    return launch<false, false, 2, EPI_BIAS>(g, 1, st);
+    GEMM_ENTER(Form::NT, A && A16 && B && C && a_exact_flag && lda16 >= K);
+    SArgs g = make_args(M, N, K, {A16, lda16, 8}, {B, ldb, 4}, C, ldc, 1.0f, bias, colstat_ws);
+    return gated(g, a_exact_flag, [&] { return launch_epi<false, false, false, 0, true, EPI_BIAS>(g, st); }, [&] {
+        set_a(g, {A, lda, 4});
+        return launch_epi<false, false, false, 2, false, EPI_BIAS>(g, st);
+    });
 }
 
 extern "C" int sparch_gemm_auto16_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                      const uint16_t* B16, int ldb16, float* C, int ldc, int zero_diag,
                                      int accumulate, const uint32_t* b_exact_flag, void* ws, size_t ws_bytes,
                                      void* stream, int precision) {
-    SPARCH_ENTER();
-    PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return SPARCH_EINVAL;
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !B16 || !C || lda < M || ldb < N || ldb16 < N || ldc < N ||
-        !b_exact_flag)
-        return SPARCH_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    GEMM_ENTER(Form::TN, A && B && B16 && C && b_exact_flag && ldb16 >= N);
     // A ragged width (N % 8 != 0, e.g. 700 input channels): the plane kernel's transposed 16-byte loads want whole
     // groups of 8 columns, and the plane has them — its rows are padded with zeros to ldb16.  The product is then
     // taken at the padded width N8 (the extra columns are zeros and are never reduced), with the slabs N8 wide.
     const int N8 = (N + 7) & ~7;
     if (N8 > ldb16) return SPARCH_EINVAL;
+    SArgs g = make_args(M, N8, K, {A, lda, 4}, {B16, ldb16, 8}, C, ldc);
     const int splits = choose_splits<1>(M, N8, K);
-    const size_t need = (size_t)splits * M * N8 * sizeof(float);
-    if (!ws || ws_bytes < need) return SPARCH_EWORKSPACE;
-    SArgs g{};
-    g.A = A; g.M = M; g.N = N8; g.K = K; g.lda = lda; g.scale = 1.0f;
-    g.a_vec = aligned16(A) && (lda % 4 == 0);
-    g.C = (float*)ws; g.ldc = N8; g.c_split_stride = (size_t)M * N8;
-    g.k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-    g.gate = b_exact_flag; g.e_exact = 1;
-    g.B = reinterpret_cast<const float*>(B16); g.ldb = ldb16;
-    g.b_vec = aligned16(B16) && (ldb16 % 8 == 0);
-    g.gate_want = 1;
-    int rc = launch<true, true, 1, EPI_NONE, true>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    g.N = N;  // the fp32 operand has exactly N columns
-    g.B = B; g.ldb = ldb; g.b_vec = aligned16(B) && (ldb % 4 == 0);
-    g.gate_want = 0;
-    rc = launch<true, true, 2, EPI_NONE>(g, splits, st);
-    if (rc != SPARCH_OK) return rc;
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, C, M, N, ldc, splits, zero_diag, accumulate, N8);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return cut_product(g, splits, {zero_diag, accumulate, ws, ws_bytes, N8}, st, [&] {
+        return gated(g, b_exact_flag, [&] { return launch<true, true, 1, EPI_NONE, true>(g, splits, st); }, [&] {
+            g.N = N;  // the fp32 operand has exactly N columns, as has C
+            set_b(g, {B, ldb, 4});
+            return launch<true, true, 2, EPI_NONE>(g, splits, st);
+        });
+    });
 }
 
 #ifdef SPARCH_REC_PROF
@@ -1377,9 +1221,7 @@ extern "C" int sparch_gemm_prof_read(unsigned long long* host_out, int reset) {
 
 extern "C" size_t sparch_gemm_spike_tn_workspace_bytes(int M, int N, int K, int precision) {
     PrecisionScope prec_scope_(precision);
-    if (!prec_scope_.ok) return 0;
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int s0 = choose_splits<0>(M, N, K), s1 = choose_splits<1>(M, N, K), s2 = choose_splits<2>(M, N, K);
-    const int smax = s0 > s1 ? (s0 > s2 ? s0 : s2) : (s1 > s2 ? s1 : s2);
-    return (size_t)smax * M * N * sizeof(float);
+    if (!prec_scope_.ok || M <= 0 || N <= 0 || K <= 0) return 0;
+    const int smax = std::max(std::max(choose_splits<0>(M, N, K), choose_splits<1>(M, N, K)), choose_splits<2>(M, N, K));
+    return gemm_plan::slab_bytes(smax, M, N);
 }

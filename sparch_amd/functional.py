@@ -419,6 +419,13 @@ def gemm_nn(A, B, b_planes=None):
     return C
 
 
+def _tn_workspace(device, M, N, K, split6=True):
+    """(workspace, its byte count as the entry point is told it) for the K-range slabs of a TN product."""
+    nbytes = (lib.sparch_gemm_spike_tn_workspace_bytes(M, N, K, _prec()) if split6
+              else lib.sparch_gemm_tn_workspace_bytes(M, N, K))
+    return torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=device), nbytes
+
+
 def gemm_tn(A, B, zero_diag=False, spike_side=None, spike_scale=1.0, out=None, b_exact_flag=None, spike16=False,
             b_plane=None):
     """A (K,M)^T @ B (K,N) -> (M,N); contraction over the long leading axis.
@@ -432,29 +439,25 @@ def gemm_tn(A, B, zero_diag=False, spike_side=None, spike_scale=1.0, out=None, b
     if spike16 and not (spike_side is not None and USE_SPIKE_GEMM):
         raise RuntimeError("internal: a bf16 spike plane needs the spike GEMM path")
     if spike_side is not None and USE_SPIKE_GEMM and spike16:
-        nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(M, N, K, _prec())
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=A.device)
+        ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_spike_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike16_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), int(spike_side),
                                          float(spike_scale), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                          ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_spike16_tn")
     elif spike_side is not None and USE_SPIKE_GEMM:
-        nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(M, N, K, _prec())
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=A.device)
+        ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_spike_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), int(spike_side),
                                        float(spike_scale), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                        ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_spike_tn")
     elif b_exact_flag is not None and b_plane is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
-        nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(M, (N + 7) // 8 * 8, K, _prec())  # slabs at the plane's padded width
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=A.device)
+        ws, nbytes = _tn_workspace(A.device, M, (N + 7) // 8 * 8, K)  # slabs at the plane's padded width
         tok = timer.start(f"gemm_auto_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_auto16_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0) or N, ptr(b_plane),
                                         b_plane.stride(0), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                         ptr(b_exact_flag), ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_auto16_tn")
     elif b_exact_flag is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
-        nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(M, N, K, _prec())
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=A.device)
+        ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_auto_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_auto_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0),
                                       int(zero_diag), int(accumulate), ptr(b_exact_flag), ptr(ws), nbytes,
@@ -463,9 +466,7 @@ def gemm_tn(A, B, zero_diag=False, spike_side=None, spike_scale=1.0, out=None, b
         if spike_side is not None and spike_scale != 1.0:
             raise RuntimeError("internal: fp32 gemm_tn fallback expects unscaled operands")
         split6 = DENSE_GEMM == "split6"
-        nbytes = (lib.sparch_gemm_spike_tn_workspace_bytes(M, N, K, _prec()) if split6
-                  else lib.sparch_gemm_tn_workspace_bytes(M, N, K))
-        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=A.device)
+        ws, nbytes = _tn_workspace(A.device, M, N, K, split6)
         fn = lib.sparch_gemm6_tn if split6 else lib.sparch_gemm_tn
         tok = timer.start(f"gemm_tn[{M}x{N}x{K}]")
         check(fn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0), int(zero_diag),
