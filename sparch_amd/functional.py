@@ -11,18 +11,12 @@ No CPU fallback: CPU tensors raise.
 """
 import ctypes
 import os
+import typing
 
 import torch
 
 from . import _capi
 from ._capi import KIND, check, lib, ptr
-
-# Exact bf16-split MFMA GEMMs for spike operands (SPARCH_SPIKE_GEMM=0 forces the fp32 MFMA everywhere).
-USE_SPIKE_GEMM = os.environ.get("SPARCH_SPIKE_GEMM", "1") != "0"
-# spike operands travel between layers as bf16 0/1 planes next to the fp32 tensors (half the GEMM operand bytes)
-USE_SPIKE16 = os.environ.get("SPARCH_SPIKE16", "1") != "0"
-USE_PRESPLIT = os.environ.get("SPARCH_PRESPLIT", "1") != "0"  # weights split into bf16 planes once per step
-PRESPLIT_NT = os.environ.get("SPARCH_PRESPLIT_NT", "0") == "1"  # ... also for the forward projection (see SpikingLayerFn)
 
 # Dense GEMMs: "split6" = exact 6-term bf16 split on the bf16 MFMA (default), "fp32" = fp32-input MFMA.
 DENSE_GEMM = os.environ.get("SPARCH_DENSE_GEMM", "split6")
@@ -35,10 +29,6 @@ DENSE_GEMM = os.environ.get("SPARCH_DENSE_GEMM", "split6")
 # same pass also adds the two directions' gradients (no separate sparch_add_halves pass): cfg5 76.1 -> 74.7 ms.
 # Hence "auto" = bidirectional layers only; SPARCH_DX_PLANES=1 / 0 forces it on / off.
 USE_DX_PLANES = {"1": True, "0": False}.get(os.environ.get("SPARCH_DX_PLANES", "auto"), "auto")
-
-# BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel instead of a
-# separate pass over dy and x (SPARCH_FUSE_BN_SUMS=0: the separate sparch_bn_bwd_reduce pass, for comparison).
-FUSE_BN_SUMS = os.environ.get("SPARCH_FUSE_BN_SUMS", "1") != "0"
 
 # Saved states (u, w) of the spiking layers in bf16 instead of fp32 (SPARCH_SAVE_DTYPE=bf16; BASELINE configs[4]
 # is the long-sequence bf16 case: at T=1000 the fp32 saves are 4.2 GB per layer and direction pair).  Every
@@ -294,9 +284,6 @@ def flag_bf16_exact(x):
     return flag
 
 
-USE_INPUT_PLANE = os.environ.get("SPARCH_INPUT_PLANE", "1") != "0"
-
-
 def plane_bf16_exact(x2):
     """(plane, flag) of a (M, K) fp32 network input: the bf16 plane of x (rows padded to a multiple of 8 elements,
     zeros behind column K) and the device flag "every element is bf16-exact", made in ONE pass — the first
@@ -349,8 +336,8 @@ def input_plane_of(x):
 def split_planes(W):
     """The three exact bf16 planes of a weight matrix, (3, *W.shape) bf16 (W = p0 + p1 + p2 exactly, the
     truncation split the GEMM kernels otherwise redo in every workgroup that stages a tile of W); None where
-    the pre-split kernels do not apply (SPARCH_PRESPLIT=0, or a layout they do not take)."""
-    if not USE_PRESPLIT or W.dtype != torch.float32 or not W.is_contiguous() or W.numel() % 8 or W.shape[-1] % 8:
+    the pre-split kernels do not apply (a layout they do not take)."""
+    if W.dtype != torch.float32 or not W.is_contiguous() or W.numel() % 8 or W.shape[-1] % 8:
         return None
     planes = torch.empty((3,) + tuple(W.shape), dtype=torch.bfloat16, device=W.device)
     check(lib.sparch_split3(W.numel(), ptr(W), ptr(planes), _stream()), "sparch_split3")
@@ -369,25 +356,25 @@ def gemm_nt(A, B, bias=None, colstat=False, spike_scale=None, a_exact_flag=None,
     ws = None
     if colstat:
         ws = torch.empty(2 * ((M + 127) // 128) * N, dtype=torch.float32, device=A.device)
-    if spike_scale is not None and USE_SPIKE_GEMM and a16 is not None and USE_SPIKE16 and b_planes is not None:
+    if spike_scale is not None and a16 is not None and b_planes is not None:
         tok = timer.start(f"gemm_spike_nt[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike16_nt_wp(M, N, K, ptr(a16), a16.stride(0), float(spike_scale), ptr(B),
                                             ptr(b_planes), B.stride(0), ptr(C), N, ptr(bias), ptr(ws), _stream(), _prec()),
               "sparch_gemm_spike16_nt_wp")
-    elif spike_scale is not None and USE_SPIKE_GEMM and a16 is not None and USE_SPIKE16:
+    elif spike_scale is not None and a16 is not None:
         tok = timer.start(f"gemm_spike_nt[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike16_nt(M, N, K, ptr(a16), a16.stride(0), float(spike_scale), ptr(B), B.stride(0),
                                          ptr(C), N, ptr(bias), ptr(ws), _stream(), _prec()), "sparch_gemm_spike16_nt")
-    elif spike_scale is not None and USE_SPIKE_GEMM:
+    elif spike_scale is not None:
         tok = timer.start(f"gemm_spike_nt[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike_nt(M, N, K, ptr(A), A.stride(0), float(spike_scale), ptr(B), B.stride(0),
                                        ptr(C), N, ptr(bias), ptr(ws), _stream(), _prec()), "sparch_gemm_spike_nt")
-    elif a_exact_flag is not None and a_plane is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
+    elif a_exact_flag is not None and a_plane is not None and DENSE_GEMM == "split6":
         tok = timer.start(f"gemm_auto_nt[{M}x{N}x{K}]")  # a_plane: plane_bf16_exact(A)[0], read when the flag is 1
         check(lib.sparch_gemm_auto16_nt(M, N, K, ptr(A), A.stride(0) or K, ptr(a_plane), a_plane.stride(0), ptr(B),
                                         B.stride(0), ptr(C), N, ptr(bias), ptr(ws), ptr(a_exact_flag), _stream(), _prec()),
               "sparch_gemm_auto16_nt")
-    elif a_exact_flag is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
+    elif a_exact_flag is not None and DENSE_GEMM == "split6":
         tok = timer.start(f"gemm_auto_nt[{M}x{N}x{K}]")
         check(lib.sparch_gemm_auto_nt(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), N, ptr(bias),
                                       ptr(ws), ptr(a_exact_flag), _stream(), _prec()), "sparch_gemm_auto_nt")
@@ -436,35 +423,33 @@ def gemm_tn(A, B, zero_diag=False, spike_side=None, spike_scale=1.0, out=None, b
     N = B.shape[1]
     accumulate = out is not None
     C = out if accumulate else torch.empty(M, N, dtype=torch.float32, device=A.device)
-    if spike16 and not (spike_side is not None and USE_SPIKE_GEMM):
+    if spike16 and spike_side is None:
         raise RuntimeError("internal: a bf16 spike plane needs the spike GEMM path")
-    if spike_side is not None and USE_SPIKE_GEMM and spike16:
+    if spike_side is not None and spike16:
         ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_spike_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike16_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), int(spike_side),
                                          float(spike_scale), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                          ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_spike16_tn")
-    elif spike_side is not None and USE_SPIKE_GEMM:
+    elif spike_side is not None:
         ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_spike_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_spike_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), int(spike_side),
                                        float(spike_scale), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                        ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_spike_tn")
-    elif b_exact_flag is not None and b_plane is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
+    elif b_exact_flag is not None and b_plane is not None and DENSE_GEMM == "split6":
         ws, nbytes = _tn_workspace(A.device, M, (N + 7) // 8 * 8, K)  # slabs at the plane's padded width
         tok = timer.start(f"gemm_auto_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_auto16_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0) or N, ptr(b_plane),
                                         b_plane.stride(0), ptr(C), C.stride(0), int(zero_diag), int(accumulate),
                                         ptr(b_exact_flag), ptr(ws), nbytes, _stream(), _prec()), "sparch_gemm_auto16_tn")
-    elif b_exact_flag is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6":
+    elif b_exact_flag is not None and DENSE_GEMM == "split6":
         ws, nbytes = _tn_workspace(A.device, M, N, K)
         tok = timer.start(f"gemm_auto_tn[{M}x{N}x{K}]")
         check(lib.sparch_gemm_auto_tn(M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0),
                                       int(zero_diag), int(accumulate), ptr(b_exact_flag), ptr(ws), nbytes,
                                       _stream(), _prec()), "sparch_gemm_auto_tn")
     else:
-        if spike_side is not None and spike_scale != 1.0:
-            raise RuntimeError("internal: fp32 gemm_tn fallback expects unscaled operands")
         split6 = DENSE_GEMM == "split6"
         ws, nbytes = _tn_workspace(A.device, M, N, K, split6)
         fn = lib.sparch_gemm6_tn if split6 else lib.sparch_gemm_tn
@@ -598,6 +583,118 @@ class _Norm:
         return dy, None, None
 
 
+# ----------------------------------------------------------------------------- the projection of a layer
+class _LayerInput(typing.NamedTuple):
+    """How a layer's GEMMs read its (M,K) input: x2 itself (scale, x16, flag, plane all None); a spike train of ours
+    with entries 0 or `scale`, read through its bf16 0/1 plane x16 (x2 may then be a placeholder without values);
+    or a network input whose bf16 `plane` is read when the device `flag` says every value is bf16-exact, x2 otherwise.
+    The forward product and the weight gradient take the same description, so they cannot disagree."""
+    x2: torch.Tensor
+    scale: typing.Optional[float] = None
+    x16: typing.Optional[torch.Tensor] = None
+    flag: typing.Optional[torch.Tensor] = None
+    plane: typing.Optional[torch.Tensor] = None
+
+    def project(self, W, Wb, colstat, b_planes=None):
+        """x W^T (+ Wb) -> ((M,H), BatchNorm column-stat partials or None)."""
+        return gemm_nt(self.x2, W, Wb, colstat=colstat, spike_scale=self.scale, a_exact_flag=self.flag, a16=self.x16,
+                       b_planes=b_planes, a_plane=self.plane)
+
+    def weight_grad(self, dx_raw):
+        """dx_raw^T x -> (H,K)."""
+        if self.scale is None:
+            return gemm_tn(dx_raw, self.x2, b_exact_flag=self.flag, b_plane=self.plane)
+        if self.x16 is None:
+            return gemm_tn(dx_raw, self.x2, spike_side=1, spike_scale=self.scale)
+        return gemm_tn(dx_raw, self.x16, spike_side=1, spike_scale=self.scale, spike16=True)
+
+
+def _layer_input(cfg, x, gated=True):
+    """The _LayerInput of x (B,T,K) under cfg's in_spike_scale / in_spike16 (x came out of a spiking layer of ours)
+    and in_plane (x was made by input_from_counts).  gated: for any other input let the device decide whether it is
+    bf16-exact (binned spike counts are) — one pass that also makes the plane the GEMMs then read."""
+    B, T, K = x.shape
+    scale, x16, tag = cfg.get("in_spike_scale"), cfg.get("in_spike16"), cfg.get("in_plane") if gated else None
+    if scale is not None and x16 is not None:
+        return _LayerInput(x.view(B * T, K), scale, x16.view(B * T, K))  # (x may be a placeholder: never touch it)
+    if tag is not None:
+        return _LayerInput(x.view(B * T, K), None, None, tag[1], tag[0])
+    x2 = _f32c(x).view(B * T, K)
+    if scale is not None or not gated:
+        return _LayerInput(x2, scale)
+    if DENSE_GEMM == "split6":
+        plane, flag = plane_bf16_exact(x2)
+        return _LayerInput(x2, None, None, flag, plane)
+    return _LayerInput(x2, None, None, flag_bf16_exact(x2))
+
+
+def _project(inp, W, Wb, nw, nb, cfg, dup, ln_width=None):
+    """norm(x W^T + Wb) of a layer -> (Wx_in, scale, shift, nsaved, Wx_raw): what the cell reads (BatchNorm stays
+    folded into scale / shift), what _Norm.backward needs, and the raw projection where backward needs it (else
+    None).  dup: how many directions share the rows (BatchNorm's sample count)."""
+    norm, training = cfg["normalization"], cfg["training"]
+    Wx_raw, colstat = inp.project(W, Wb, colstat=(norm == "batchnorm" and training))
+    Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
+                                                cfg.get("running_var"), training, dup,
+                                                nbt=cfg.get("num_batches_tracked"), ln_width=ln_width)
+    return Wx_in, scale, shift, nsaved, Wx_raw if norm in ("batchnorm", "layernorm") else None
+
+
+def _use_dx_planes(inp, norm, dirs, M, K, H):
+    """dx as bf16 planes (made once by the BatchNorm pass) for the dW and dX products: a hidden layer fed by a spike
+    plane, exact mode, shapes the pipelined plane kernels take (whole tiles, 32-deep K tiles)."""
+    return ((USE_DX_PLANES is True or (USE_DX_PLANES == "auto" and dirs == 2))
+            and norm == "batchnorm" and inp.x16 is not None and DENSE_GEMM == "split6"
+            and _precision == 0 and H % 32 == 0 and K % 32 == 0 and H >= 256 and K >= 256 and M >= 256
+            and M % 32 == 0)
+
+
+def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, need_bias, sums=None, ln_width=None,
+                      w_planes=None, dx_planes=False, raw_dx=False):
+    """Backward of _project.  dy: the gradient of the normalised projection, (M,H) or the (B*dirs,T,H) halves of
+    `dirs` directions that share the projection rows (snns.py:252-254); may be overwritten.  sums: BatchNorm's column
+    sums where the cell's backward kernel made them.  w_planes: split_planes(W) for the dx product.  dx_planes: the
+    layer may take the plane kernels (_use_dx_planes decides).  Returns (dx (M,K) or None, dW, dWb or None, dnw, dnb);
+    raw_dx: the first entry is dx_raw (M,H) instead — the caller forms dx itself."""
+    norm = cfg["normalization"]
+    H, K = W.shape
+    M = dy.numel() // (H * dirs)
+    dxp = None
+    if dx_planes and _use_dx_planes(inp, norm, dirs, M, K, H) and (not need_dx or w_planes is not None):
+        B = dy.shape[0] // dirs
+        dy2 = dy[B:].view(M, H) if dirs == 2 else None  # second direction: added by the same pass
+        dx_raw, dnw, dnb, dxp = _Norm.backward(norm, dy[:B].view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
+                                               planes=True, dy2=dy2, keep_fp32=need_bias)
+        nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(H, K, M, _prec())
+        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=W.device)
+        dW = torch.empty(H, K, dtype=torch.float32, device=W.device)
+        tok = timer.start(f"gemm_spike_tn[{H}x{K}x{M}]")
+        check(lib.sparch_gemm_spike16_tn_ap(H, K, M, ptr(dx_raw), ptr(dxp), H, ptr(inp.x16), inp.x16.stride(0),
+                                            float(inp.scale), ptr(dW), K, 0, 0, ptr(ws), nbytes, _stream(), _prec()),
+              "sparch_gemm_spike16_tn_ap")
+        timer.stop(tok)
+    else:
+        if dirs == 2:
+            halves, dy = dy, torch.empty(dy.shape[0] // 2, dy.shape[1], H, dtype=torch.float32, device=W.device)
+            check(lib.sparch_add_halves(M * H, ptr(halves), ptr(dy), _stream()), "sparch_add_halves")
+        dx_raw, dnw, dnb = _Norm.backward(norm, dy.view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
+                                          ln_width=ln_width)
+        dW = inp.weight_grad(dx_raw)
+    dWb = _colsum(dx_raw) if need_bias else None
+    if raw_dx:
+        return dx_raw, dW, dWb, dnw, dnb
+    dx = None
+    if need_dx and dxp is not None:
+        dx = torch.empty(M, K, dtype=torch.float32, device=W.device)
+        tok = timer.start(f"gemm_nn[{M}x{K}x{H}]")
+        check(lib.sparch_gemm6_nn_pp(M, K, H, ptr(dx_raw), ptr(dxp), H, ptr(W), ptr(w_planes), K, ptr(dx), K, _stream(),
+                                     _prec()), "sparch_gemm6_nn_pp")
+        timer.stop(tok)
+    elif need_dx:
+        dx = gemm_nn(dx_raw, W, b_planes=w_planes)
+    return dx, dW, dWb, dnw, dnb
+
+
 # ----------------------------------------------------------------------------- cells (given Wx)
 _placeholder_zero = {}  # one element per device (a fresh torch.zeros(1) per layer and step was a fill kernel each)
 
@@ -612,14 +709,33 @@ def spike_placeholder(B, T, F, device):
     return z.expand(B, T, F)
 
 
+def _persistent(label, entry, lead, nbytes, dev, L, *tail):
+    """One persistent recurrent launch (a kernel whose workgroups wait for each other): `entry`(*lead, channel buffer
+    of `nbytes`, its size, status word, L time steps per launch, stream, *tail) inside `_persistent_launch()`, timed
+    under `label` (None: not timed)."""
+    chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
+    tok = timer.start(label) if label is not None else None
+    with _persistent_launch():
+        check(getattr(lib, entry)(*lead, ptr(chan), nbytes, ptr(status_word(dev)), L, _stream(), *tail), entry)
+    timer.stop(tok)
+
+
+def _vpack(H, V, flags, vmask=None):
+    """V (H,H) packed into the MFMA fragments of the persistent kernels (flags: 1 = transposed, 2 = dense, i.e. no
+    zeroed diagonal); vmask: also write the masked fp32 copy there."""
+    vpack = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=V.device)
+    check(lib.sparch_vpack(H, ptr(V), flags, ptr(vpack), ptr(vmask), _stream(), _prec()), "sparch_vpack")
+    return vpack
+
+
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
                  want_s_out=True, want_saves=True):
     """Run one spiking cell over the whole sequence on the device.
 
     Wx (B,T,H) raw projection (+ optional per-column scale/shift); u0/w0/s0 (B*dirs,H).
     Returns (s_out (B,T,H*dirs), count (H*dirs) int32, saved, s16) where saved feeds cell_backward and s16 is
-    s_out != 0 as a bf16 plane (or None).  want_s_out=False (round 3): the fp32 tensor is not written — s_out is
-    None — when the bf16 plane exists, i.e. for a layer whose output only feeds the next layer's spike GEMMs
+    s_out != 0 as a bf16 plane.  want_s_out=False (round 3): the fp32 tensor is not written — s_out is
+    None — for a layer whose output only feeds the next layer's spike GEMMs
     (the reference materialises it because its next op is a dense nn.Linear, snns.py:261; here it was 4 of the
     14 bytes a recurrent forward step stores per element).  want_saves=False (LIF / adLIF, nothing will be
     differentiated — validation and test forwards, exp.py:405-518): u / w are not saved either (8 of an adLIF step's
@@ -630,8 +746,7 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
     # the same spikes as a bf16 0/1 plane for the GEMMs of the next layer (rows must stay 16-byte aligned)
-    s16 = torch.empty(B, T, H * dirs, dtype=torch.bfloat16, device=dev) if (USE_SPIKE_GEMM and USE_SPIKE16) else None
-    want_s_out = want_s_out or s16 is None
+    s16 = torch.empty(B, T, H * dirs, dtype=torch.bfloat16, device=dev)
     s_out = torch.empty(B, T, H * dirs, dtype=torch.float32, device=dev) if want_s_out else None
     L = steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T)
     # bf16 saves: the recurrent kernels take them for whole-sequence launches only (a chunked forward resumes
@@ -690,16 +805,11 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
         # t = 0 drive: s0 is uniform noise, not binary (snns.py:559/702): a (B', H, H) dense product, split-K so
         # that its 16 output tiles become a full grid (38 -> ~15 us at B' = 256, H = 1024)
         rec0 = _gemm_small(s0, vmask, nn=True)
-        nbytes = lib.sparch_rec_chan_bytes(Bp, T, H)
-        chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-        tok = timer.start(f"rec_cell_fwd[{kind}]")
-        with _persistent_launch():
-            check(lib.sparch_rec_cell_fwd(k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]),
-                                          ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack),
-                                          ptr(rec0), ptr(u0), ptr(w0), ptr(s0), theta, p_drop, seed, ptr(s_out),
-                                          ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count), ptr(chan),
-                                          nbytes, ptr(status_word(dev)), L, _stream(), _prec()), "sparch_rec_cell_fwd")
-        timer.stop(tok)
+        _persistent(f"rec_cell_fwd[{kind}]", "sparch_rec_cell_fwd",
+                    (k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]), ptr(p.get("beta")),
+                     ptr(p.get("a")), ptr(p.get("b")), ptr(vpack), ptr(rec0), ptr(u0), ptr(w0), ptr(s0), theta, p_drop,
+                     seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count)),
+                    lib.sparch_rec_chan_bytes(Bp, T, H), dev, L, _prec())
         return s_out, count, (u_save, w_save, vpack_t), s16
     return s_out, count, (u_save, w_save), s16
 
@@ -759,30 +869,19 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                                                    _stream()), "sparch_rec_cell_step_bwd")
             timer.stop(tok)
         else:
-            if vpack_fwd_made is not None:
-                vpack_t = vpack_fwd_made
-            else:
-                vpack_t = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=dev)
-                check(lib.sparch_vpack(H, ptr(V), 1, ptr(vpack_t), None, _stream(), _prec()), "sparch_vpack")
-            nbytes = lib.sparch_rec_chan_bytes(Bp, T, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-            L = steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T)
-            tok = timer.start(f"rec_cell_bwd[{kind}]")
-            with _persistent_launch():
-                check(lib.sparch_rec_cell_bwd(k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save),
-                                              int(save16), ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")),
-                                              ptr(vpack_t), ptr(u0), ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx),
-                                              ptr(s_prev), ptr(ws), ptr(bn_x), ptr(bn_mean), ptr(bn_invstd), ptr(chan),
-                                              nbytes, ptr(status_word(dev)), L, _stream(), _prec()), "sparch_rec_cell_bwd")
-            timer.stop(tok)
+            vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
+            _persistent(f"rec_cell_bwd[{kind}]", "sparch_rec_cell_bwd",
+                        (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
+                         ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack_t), ptr(u0),
+                         ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws), ptr(bn_x), ptr(bn_mean),
+                         ptr(bn_invstd)),
+                        lib.sparch_rec_chan_bytes(Bp, T, H), dev,
+                        steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec())
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
-        if USE_SPIKE_GEMM:
-            dV = gemm_tn(s_prev.view(Bp * T, H), dWx.view(Bp * T, H), zero_diag=True, spike_side=0, spike16=True)
-        else:  # fp32-MFMA comparison path (tests)
-            dV = gemm_tn(s_prev.view(Bp * T, H).float(), dWx.view(Bp * T, H), zero_diag=True)
-        for dd in range(dirs):  # s_prev rows of cell step 0 are zero on both paths: add the s0 term
+        dV = gemm_tn(s_prev.view(Bp * T, H), dWx.view(Bp * T, H), zero_diag=True, spike_side=0, spike16=True)
+        for dd in range(dirs):  # s_prev rows of cell step 0 are zero: add the s0 term
             rows = slice(dd * B, (dd + 1) * B)
             gemm_tn(s0[rows], dWx[rows, (T - 1) if dd else 0, :], zero_diag=True, out=dV)
         grads["V"] = dV
@@ -809,42 +908,15 @@ class SpikingLayerFn(torch.autograd.Function):
     def forward(ctx, cfg, x, W, Wb, nw, nb, alpha, beta, a, b, V, u0, w0, s0):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
-        kind, norm, dirs = cfg["kind"], cfg["normalization"], cfg["dirs"]
-        training, theta, p_drop, seed = cfg["training"], cfg["theta"], cfg["p_drop"], cfg["seed"]
-        in_scale = cfg.get("in_spike_scale")  # input is a spike train of ours: entries 0 or in_scale
-        plane_in = ((in_scale is not None and cfg.get("in_spike16") is not None and USE_SPIKE_GEMM and USE_SPIKE16)
-                    or cfg.get("in_plane") is not None)
-        if not plane_in:  # (an input read through its bf16 plane may be a placeholder: never touch its values)
-            x = _f32c(x)
+        kind, dirs, theta, p_drop, seed = cfg["kind"], cfg["dirs"], cfg["theta"], cfg["p_drop"], cfg["seed"]
+        inp = _layer_input(cfg, x)
         B, T, K = x.shape
         H = W.shape[0]
-        M = B * T
-        x2 = x.view(M, K)
-        use_bn_stats = norm == "batchnorm" and training
-        # otherwise (network input): let the device decide whether x is bf16-exact (binned spike counts are)
-        xplane = None
-        if cfg.get("in_plane") is not None:
-            xplane, xflag = cfg["in_plane"]  # the input came as bytes (input_from_counts): plane made, flag = 1
-        elif in_scale is None and USE_SPIKE_GEMM and USE_SPIKE16 and USE_INPUT_PLANE and DENSE_GEMM == "split6":
-            xplane, xflag = plane_bf16_exact(x2)  # one pass: the flag AND the plane the two GEMMs read when it is 1
-        else:
-            xflag = flag_bf16_exact(x2) if (in_scale is None and USE_SPIKE_GEMM) else None
-        ctx.xflag, ctx.xplane = xflag, xplane
-        x16 = cfg.get("in_spike16") if in_scale is not None else None
-        x16 = x16.view(M, K) if x16 is not None else None
         # the weights' bf16 planes, split once here for backward's dx GEMM (775 -> 732 us).  The projection itself
-        # converts W on the fly by default: every workgroup streams all of W, and 4 MB of fp32 stay resident in
-        # the XCD's 4 MB L2 where 6 MB of planes do not (0.42 against 0.61 GB of L2 misses per launch, 1.8 % faster;
-        # SPARCH_PRESPLIT_NT=1 hands it the planes too)
-        need_dx = ctx.needs_input_grad[1]
-        planes_ok = K % 32 == 0 and H >= 128
-        w_planes = split_planes(W) if planes_ok and (need_dx or (PRESPLIT_NT and x16 is not None)) else None
-        ctx.w_planes = w_planes if need_dx else None
-        Wx_raw, colstat = gemm_nt(x2, W, Wb, colstat=use_bn_stats, spike_scale=in_scale, a_exact_flag=xflag, a16=x16,
-                                  b_planes=w_planes if PRESPLIT_NT else None, a_plane=xplane)  # snns.py:261
-        Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
-                                                    cfg.get("running_var"), training, dirs,
-                                                    nbt=cfg.get("num_batches_tracked"))  # 264-266
+        # converts W on the fly: every workgroup streams all of W, and 4 MB of fp32 stay resident in the XCD's 4 MB
+        # L2 where 6 MB of planes do not (0.42 against 0.61 GB of L2 misses per launch, 1.8 % faster)
+        ctx.w_planes = split_planes(W) if (ctx.needs_input_grad[1] and K % 32 == 0 and H >= 128) else None
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, dirs)  # snns.py:261, 264-266
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
         if cfg.get("states_ready") is not None:  # initial states uploaded on a side stream (snns._rand_batch)
@@ -857,15 +929,12 @@ class SpikingLayerFn(torch.autograd.Function):
             s_out = spike_placeholder(B, T, H * dirs, x.device)
         inv_keep = 1.0 / (1.0 - p_drop)
         rate = count * (inv_keep / float(B * T))  # snns.py:174 on post-dropout spikes (int32 * float -> fp32, one kernel)
-        ctx.cfg = cfg
+        ctx.cfg, ctx.inp = cfg, inp
         ctx.shape = (B, T, K, H)
         ctx.nsaved = nsaved
         ctx.cell_saved = saved
         ctx.set_materialize_grads(False)  # no zero tensors for unused outputs (s16 is as large as s in bf16)
-        ctx.save_for_backward(x2, W, nw, alpha, beta, a, b, V, u0, w0, s0,
-                              Wx_raw if norm in ("batchnorm", "layernorm") else None)
-        if s16 is None:  # keep the output arity fixed
-            s16 = torch.empty(0, dtype=torch.bfloat16, device=x.device)
+        ctx.save_for_backward(inp.x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw)
         ctx.mark_non_differentiable(s16)
         return s_out, rate, s16
 
@@ -875,7 +944,6 @@ class SpikingLayerFn(torch.autograd.Function):
         kind, norm, dirs = cfg["kind"], cfg["normalization"], cfg["dirs"]
         B, T, K, H = ctx.shape
         x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw = ctx.saved_tensors
-        M = B * T
         dev = x2.device
         if g_s is None:
             g_s = torch.zeros(B, T, H * dirs, dtype=torch.float32, device=dev)
@@ -884,58 +952,16 @@ class SpikingLayerFn(torch.autograd.Function):
             g_rate = _f32c(g_rate)
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
-        bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and FUSE_BN_SUMS and H % 4 == 0) else None
+        # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
+        bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
                                 theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn)
         ctx.cell_saved = None
-        in_scale = cfg.get("in_spike_scale")
-        x16 = cfg.get("in_spike16") if (in_scale is not None and USE_SPIKE16) else None
-        # dx as bf16 planes (made once by the BatchNorm pass) for the dW and dX products: a hidden layer fed by a spike
-        # plane, exact mode, shapes the pipelined plane kernels take (whole tiles, 32-deep K tiles)
-        use_planes = ((USE_DX_PLANES is True or (USE_DX_PLANES == "auto" and dirs == 2))
-                      and norm == "batchnorm" and x16 is not None and USE_SPIKE_GEMM and DENSE_GEMM == "split6"
-                      and _precision == 0 and H % 32 == 0 and K % 32 == 0 and H >= 256 and K >= 256 and M >= 256
-                      and M % 32 == 0 and (not ctx.needs_input_grad[1] or ctx.w_planes is not None))
-        need_bias = ctx.needs_input_grad[3]
-        if use_planes:
-            dy2 = dWx[B:].view(M, H) if dirs == 2 else None  # second direction: added by the same pass
-            dx_raw, dnw, dnb, dxp = _Norm.backward(norm, dWx[:B].view(M, H), Wx_raw, nw, ctx.nsaved, cfg["training"],
-                                                   sums=pg.get("bn_sums"), planes=True, dy2=dy2, keep_fp32=need_bias)
-            nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(H, K, M, _prec())
-            ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
-            dW = torch.empty(H, K, dtype=torch.float32, device=dev)
-            x16m = x16.view(M, K)
-            tok = timer.start(f"gemm_spike_tn[{H}x{K}x{M}]")
-            check(lib.sparch_gemm_spike16_tn_ap(H, K, M, ptr(dx_raw), ptr(dxp), H, ptr(x16m), x16m.stride(0), float(in_scale),
-                                                ptr(dW), K, 0, 0, ptr(ws), nbytes, _stream(), _prec()),
-                  "sparch_gemm_spike16_tn_ap")
-            timer.stop(tok)
-            dWb = _colsum(dx_raw) if need_bias else None
-            dx = None
-            if ctx.needs_input_grad[1]:
-                dx = torch.empty(M, K, dtype=torch.float32, device=dev)
-                tok = timer.start(f"gemm_nn[{M}x{K}x{H}]")
-                check(lib.sparch_gemm6_nn_pp(M, K, H, ptr(dx_raw), ptr(dxp), H, ptr(W), ptr(ctx.w_planes), K, ptr(dx), K,
-                                             _stream(), _prec()), "sparch_gemm6_nn_pp")
-                timer.stop(tok)
-                dx = dx.view(B, T, K)
-        else:
-            if dirs == 2:  # both directions share the projection rows (snns.py:252-254)
-                dy = torch.empty(B, T, H, dtype=torch.float32, device=dev)
-                check(lib.sparch_add_halves(M * H, ptr(dWx), ptr(dy), _stream()), "sparch_add_halves")
-            else:
-                dy = dWx
-            dy = dy.view(M, H)
-            dx_raw, dnw, dnb = _Norm.backward(norm, dy, Wx_raw, nw, ctx.nsaved, cfg["training"], sums=pg.get("bn_sums"))
-            if x16 is not None and USE_SPIKE_GEMM:
-                dW = gemm_tn(dx_raw, x16.view(M, K), spike_side=1, spike_scale=in_scale, spike16=True)
-            elif in_scale is not None and USE_SPIKE_GEMM:
-                dW = gemm_tn(dx_raw, x2, spike_side=1, spike_scale=in_scale)  # (H,K) = dx_raw^T x, x spikes
-            else:
-                dW = gemm_tn(dx_raw, x2, b_exact_flag=ctx.xflag, b_plane=ctx.xplane)
-            dWb = _colsum(dx_raw) if need_bias else None
-            dx = gemm_nn(dx_raw, W, b_planes=ctx.w_planes).view(B, T, K) if ctx.needs_input_grad[1] else None
-        ctx.w_planes = ctx.xplane = None
+        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
+                                                  need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                  sums=pg.get("bn_sums"), w_planes=ctx.w_planes, dx_planes=True)
+        dx = None if dx is None else dx.view(B, T, K)
+        ctx.w_planes = ctx.inp = None
         return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
                 pg.get("V"), None, None, None)
 
@@ -947,33 +973,20 @@ class ReadoutLayerFn(torch.autograd.Function):
     def forward(ctx, cfg, x, W, Wb, nw, nb, alpha, u0):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
-        norm, training = cfg["normalization"], cfg["training"]
-        plane_in = (cfg.get("in_spike_scale") is not None and cfg.get("in_spike16") is not None
-                    and USE_SPIKE_GEMM and USE_SPIKE16)
-        if not plane_in:
-            x = _f32c(x)
         B, T, K = x.shape
         C = W.shape[0]
         if C > 256:
             raise ValueError(f"sparch_amd: the readout kernels handle at most 256 classes (got {C})")
-        M = B * T
-        x2 = x.view(M, K)
-        x16 = cfg.get("in_spike16") if cfg.get("in_spike_scale") is not None else None
-        Wx_raw, colstat = gemm_nt(x2, W, Wb, colstat=(norm == "batchnorm" and training),
-                                  spike_scale=cfg.get("in_spike_scale"),
-                                  a16=x16.view(M, K) if x16 is not None else None)  # snns.py:796
-        Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
-                                                    cfg.get("running_var"), training, 1,
-                                                    nbt=cfg.get("num_batches_tracked"))  # 799-801
+        inp = _layer_input(cfg, x, gated=False)
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1)  # snns.py:796, 799-801
         out = torch.empty(B, C, dtype=torch.float32, device=x.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
         check(lib.sparch_readout_fwd(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
                                      ptr(u_save), _stream()), "sparch_readout_fwd")
-        ctx.cfg = cfg
+        ctx.cfg, ctx.inp = cfg, inp
         ctx.shape = (B, T, K, C)
         ctx.nsaved = nsaved
-        ctx.save_for_backward(x2, W, nw, alpha, u0, u_save,
-                              Wx_raw if norm in ("batchnorm", "layernorm") else None)
+        ctx.save_for_backward(inp.x2, W, nw, alpha, u0, u_save, Wx_raw)
         return out
 
     @staticmethod
@@ -986,7 +999,7 @@ class ReadoutLayerFn(torch.autograd.Function):
         dev = x2.device
         g_out = _f32c(g_out)
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=dev)
-        fuse = norm == "batchnorm" and FUSE_BN_SUMS
+        fuse = norm == "batchnorm"
         ws = torch.empty(3 if fuse else 1, B, C, dtype=torch.float32, device=dev)
         check(lib.sparch_readout_bwd(B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None,
                                      ptr(ctx.nsaved[0]) if fuse else None, ptr(ctx.nsaved[1]) if fuse else None,
@@ -998,18 +1011,11 @@ class ReadoutLayerFn(torch.autograd.Function):
         else:
             (dalpha,) = _finish_param_grads(ws, B, C, [alpha], [ALPHA_LIM])
             sums = None
-        dy = dWx.view(M, C)
-        dx_raw, dnw, dnb = _Norm.backward(norm, dy, Wx_raw, nw, ctx.nsaved, cfg["training"], sums=sums)
-        in_scale = cfg.get("in_spike_scale")
-        x16 = cfg.get("in_spike16") if (in_scale is not None and USE_SPIKE16) else None
-        if x16 is not None and USE_SPIKE_GEMM:
-            dW = gemm_tn(dx_raw, x16.view(M, K), spike_side=1, spike_scale=in_scale, spike16=True)
-        elif in_scale is not None and USE_SPIKE_GEMM:
-            dW = gemm_tn(dx_raw, x2, spike_side=1, spike_scale=in_scale)
-        else:
-            dW = gemm_tn(dx_raw, x2)
-        dWb = _colsum(dx_raw) if ctx.needs_input_grad[3] else None
-        dx = gemm_nn(dx_raw, W).view(B, T, K) if ctx.needs_input_grad[1] else None
+        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx.view(M, C),
+                                                  need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                  sums=sums)
+        dx = None if dx is None else dx.view(B, T, K)
+        ctx.inp = None
         return None, dx, dW, dWb, dnw, dnb, dalpha, None
 
 
@@ -1539,8 +1545,7 @@ class EventStore:
 
     def serves_plane(self, nb_steps):
         # the conditions under which layer 1 would read the plane of an fp32 batch (SpikingLayerFn.forward)
-        return (USE_SPIKE_GEMM and USE_SPIKE16 and USE_INPUT_PLANE and DENSE_GEMM == "split6"
-                and self.prepare(nb_steps) <= 255)
+        return DENSE_GEMM == "split6" and self.prepare(nb_steps) <= 255
 
     def batch(self, idx, nb_steps, values=False):
         """(x, y) on the device for the index list: x is the layer-1 input — the tagged placeholder of
@@ -1815,30 +1820,24 @@ class MLPLayerFn(torch.autograd.Function):
     def forward(ctx, cfg, x, W, Wb, nw, nb):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
-        norm, training = cfg["normalization"], cfg["training"]
-        x = _f32c(x)
         B, T, K = x.shape
         H = W.shape[0]
         if H % 4 != 0:
             raise ValueError("sparch_amd: MLP layers need hidden_size % 4 == 0")
         M = B * T
-        x2 = x.view(M, K)
-        Wx_raw, colstat = gemm_nt(x2, W, Wb, colstat=(norm == "batchnorm" and training))          # anns.py:218
-        Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
-                                                    cfg.get("running_var"), training, 1,          # 221-223
-                                                    ln_width=cfg.get("ln_width"))
+        inp = _LayerInput(_f32c(x).view(M, K))
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1, cfg.get("ln_width"))  # anns.py:218-223
         y = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
         check(lib.sparch_act_fwd(ACT_KIND[cfg["act"]], M * H, H, ptr(Wx_in), ptr(scale), ptr(shift),
                                  cfg["p_drop"], cfg["seed"], ptr(y), _stream()), "sparch_act_fwd")  # 226
         ctx.cfg, ctx.shape, ctx.nsaved = cfg, (B, T, K, H), nsaved
-        ctx.save_for_backward(x2, W, nw, Wx_raw if norm in ("batchnorm", "layernorm") else None,
-                              Wx_in if norm != "batchnorm" else None, scale, shift)
+        ctx.save_for_backward(inp.x2, W, nw, Wx_raw, Wx_in if cfg["normalization"] != "batchnorm" else None, scale,
+                              shift)
         return y
 
     @staticmethod
     def backward(ctx, g_y):
         cfg = ctx.cfg
-        norm = cfg["normalization"]
         B, T, K, H = ctx.shape
         x2, W, nw, Wx_raw, Wx_in, scale, shift = ctx.saved_tensors
         M = B * T
@@ -1846,12 +1845,10 @@ class MLPLayerFn(torch.autograd.Function):
         dz = torch.empty(M, H, dtype=torch.float32, device=x2.device)
         check(lib.sparch_act_bwd(ACT_KIND[cfg["act"]], M * H, H, ptr(z), ptr(scale), ptr(shift), ptr(_f32c(g_y)),
                                  cfg["p_drop"], cfg["seed"], ptr(dz), _stream()), "sparch_act_bwd")
-        dx_raw, dnw, dnb = _Norm.backward(norm, dz, Wx_raw, nw, ctx.nsaved, cfg["training"],
-                                          ln_width=cfg.get("ln_width"))
-        dW = gemm_tn(dx_raw, x2)
-        dWb = _colsum(dx_raw) if ctx.needs_input_grad[3] else None
-        dx = gemm_nn(dx_raw, W).view(B, T, K) if ctx.needs_input_grad[1] else None
-        return None, dx, dW, dWb, dnw, dnb
+        dx, dW, dWb, dnw, dnb = _project_backward(_LayerInput(x2), W, nw, cfg, ctx.nsaved, Wx_raw, dz,
+                                                  need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                  ln_width=cfg.get("ln_width"))
+        return None, None if dx is None else dx.view(B, T, K), dW, dWb, dnw, dnb
 
 
 class ReadoutANNFn(torch.autograd.Function):
@@ -1861,7 +1858,6 @@ class ReadoutANNFn(torch.autograd.Function):
     def forward(ctx, cfg, x, W, Wb, nw, nb):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
-        norm, training = cfg["normalization"], cfg["training"]
         x = _f32c(x)
         B, T, K = x.shape
         C = W.shape[0]
@@ -1869,27 +1865,22 @@ class ReadoutANNFn(torch.autograd.Function):
             raise ValueError("sparch_amd: ANN readout needs input features % 4 == 0 and <= 4096")
         y = torch.empty(B, K, dtype=torch.float32, device=x.device)
         check(lib.sparch_softmax_sum_fwd(B, T, K, ptr(x), ptr(y), _stream()), "sparch_softmax_sum_fwd")  # 658-663
-        Wy_raw, colstat = gemm_nt(y, W, Wb, colstat=(norm == "batchnorm" and training))                  # 650
-        Wy_in, scale, shift, nsaved = _Norm.forward(norm, Wy_raw, colstat, nw, nb, cfg.get("running_mean"),
-                                                    cfg.get("running_var"), training, 1)                 # 653-654
+        Wy_in, scale, shift, nsaved, Wy_raw = _project(_LayerInput(y), W, Wb, nw, nb, cfg, 1)           # 650, 653-654
         out = Wy_in if scale is None else Wy_in * scale + shift  # (B,C): tiny
         ctx.cfg, ctx.shape, ctx.nsaved = cfg, (B, T, K, C), nsaved
-        ctx.save_for_backward(x, y, W, nw, Wy_raw if norm in ("batchnorm", "layernorm") else None, scale)
+        ctx.save_for_backward(x, y, W, nw, Wy_raw, scale)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
         cfg = ctx.cfg
-        norm = cfg["normalization"]
-        B, T, K, C = ctx.shape
-        x, y, W, nw, Wy_raw, scale = ctx.saved_tensors
+        B, T, K, _ = ctx.shape
+        x, y, W, nw, Wy_raw, _ = ctx.saved_tensors
         dz = _f32c(g_out).clone()
-        dx_raw, dnw, dnb = _Norm.backward(norm, dz, Wy_raw, nw, ctx.nsaved, cfg["training"])
-        dW = gemm_tn(dx_raw, y)
-        dWb = _colsum(dx_raw) if ctx.needs_input_grad[3] else None
+        gy, dW, dWb, dnw, dnb = _project_backward(_LayerInput(y), W, nw, cfg, ctx.nsaved, Wy_raw, dz,
+                                                  need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3])
         dx = None
-        if ctx.needs_input_grad[1]:
-            gy = gemm_nn(dx_raw, W)  # (B,K)
+        if gy is not None:  # (B,K)
             dx = torch.empty(B, T, K, dtype=torch.float32, device=x.device)
             check(lib.sparch_softmax_sum_bwd(B, T, K, ptr(x), ptr(gy), ptr(dx), _stream()), "sparch_softmax_sum_bwd")
         return None, dx, dW, dWb, dnw, dnb
@@ -1904,19 +1895,14 @@ class RNNLayerFn(torch.autograd.Function):
     def forward(ctx, cfg, x, W, Wb, nw, nb, V):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
-        norm, training, dirs = cfg["normalization"], cfg["training"], cfg["dirs"]
-        x = _f32c(x)
+        dirs = cfg["dirs"]
         B, T, K = x.shape
         H = W.shape[0]
         if H % 4 != 0:
             raise ValueError("sparch_amd: recurrent layers need hidden_size % 4 == 0")
-        M = B * T
         dev = x.device
-        x2 = x.view(M, K)
-        Wx_raw, colstat = gemm_nt(x2, W, Wb, colstat=(norm == "batchnorm" and training))             # anns.py:306
-        Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
-                                                    cfg.get("running_var"), training, dirs,          # 309-311
-                                                    ln_width=cfg.get("ln_width"))
+        inp = _LayerInput(_f32c(x).view(B * T, K))
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, dirs, cfg.get("ln_width"))  # anns.py:306-311
         Bp = B * dirs
         y_out = torch.empty(B, T, H * dirs, dtype=torch.float32, device=dev)
         y_state = torch.empty(Bp, T, H, dtype=torch.float32, device=dev)
@@ -1932,28 +1918,22 @@ class RNNLayerFn(torch.autograd.Function):
                                                   ptr(y_state), ptr(y_step), _stream()), "sparch_ann_rec_step_fwd")
             timer.stop(tok)
         else:
-            vpack = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=dev)
-            check(lib.sparch_vpack(H, ptr(V), 1 | 2, ptr(vpack), None, _stream(), _prec()), "sparch_vpack")   # y V^T, dense
-            nbytes = lib.sparch_rec_chan_bytes(Bp, T, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-            tok = timer.start("ann_rec_fwd[RNN]")
-            with _persistent_launch():
-                check(lib.sparch_ann_rec_fwd(ACT_KIND[cfg["act"]], B, dirs, T, H, ptr(Wx_in), ptr(scale), ptr(shift),
-                                             ptr(vpack), cfg["p_drop"], cfg["seed"], ptr(y_out), ptr(y_state),
-                                             ptr(chan), nbytes, ptr(status_word(dev)), rec_steps_per_launch(T),
-                                             _stream()), "sparch_ann_rec_fwd")
-            timer.stop(tok)
+            vpack = _vpack(H, V, 1 | 2)  # y V^T, dense
+            _persistent("ann_rec_fwd[RNN]", "sparch_ann_rec_fwd",
+                        (ACT_KIND[cfg["act"]], B, dirs, T, H, ptr(Wx_in), ptr(scale), ptr(shift), ptr(vpack),
+                         cfg["p_drop"], cfg["seed"], ptr(y_out), ptr(y_state)),
+                        lib.sparch_rec_chan_bytes(Bp, T, H), dev, rec_steps_per_launch(T))
         ctx.cfg, ctx.shape, ctx.nsaved = cfg, (B, T, K, H), nsaved
-        ctx.save_for_backward(x2, W, nw, V, y_state, Wx_raw if norm in ("batchnorm", "layernorm") else None)
+        ctx.save_for_backward(inp.x2, W, nw, V, y_state, Wx_raw)
         return y_out
 
     @staticmethod
     def backward(ctx, g_y):
         cfg = ctx.cfg
-        norm, dirs = cfg["normalization"], cfg["dirs"]
+        dirs = cfg["dirs"]
         B, T, K, H = ctx.shape
         x2, W, nw, V, y_state, Wx_raw = ctx.saved_tensors
-        M, Bp = B * T, B * dirs
+        Bp = B * dirs
         dev = x2.device
         dpre = torch.empty(Bp, T, H, dtype=torch.float32, device=dev)
         y_prev = torch.empty(Bp, T, H, dtype=torch.float32, device=dev)
@@ -1970,30 +1950,17 @@ class RNNLayerFn(torch.autograd.Function):
                                                   ptr(dpre_step), _stream()), "sparch_ann_rec_step_bwd")
             timer.stop(tok)
         else:
-            vpack = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=dev)
-            check(lib.sparch_vpack(H, ptr(V), 0 | 2, ptr(vpack), None, _stream(), _prec()), "sparch_vpack")   # dpre V, dense
-            nbytes = lib.sparch_rec_chan_bytes(Bp, T, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-            tok = timer.start("ann_rec_bwd[RNN]")
-            with _persistent_launch():
-                check(lib.sparch_ann_rec_bwd(ACT_KIND[cfg["act"]], B, dirs, T, H, ptr(g_y), ptr(y_state), ptr(vpack),
-                                             cfg["p_drop"], cfg["seed"], ptr(dpre), ptr(y_prev), ptr(chan), nbytes,
-                                             ptr(status_word(dev)), rec_steps_per_launch(T), _stream()),
-                      "sparch_ann_rec_bwd")
-            timer.stop(tok)
+            vpack = _vpack(H, V, 0 | 2)  # dpre V, dense
+            _persistent("ann_rec_bwd[RNN]", "sparch_ann_rec_bwd",
+                        (ACT_KIND[cfg["act"]], B, dirs, T, H, ptr(g_y), ptr(y_state), ptr(vpack), cfg["p_drop"],
+                         cfg["seed"], ptr(dpre), ptr(y_prev)),
+                        lib.sparch_rec_chan_bytes(Bp, T, H), dev, rec_steps_per_launch(T))
         # dV[i][j] = sum over rows and steps of dpre[.,i] * y_{t-1}[.,j]   (V(y) = y V^T, anns.py:336)
         dV = gemm_tn(dpre.view(Bp * T, H), y_prev.view(Bp * T, H))
-        if dirs == 2:  # both directions share the projection rows (anns.py:298-300)
-            dy = torch.empty(B, T, H, dtype=torch.float32, device=dev)
-            check(lib.sparch_add_halves(M * H, ptr(dpre), ptr(dy), _stream()), "sparch_add_halves")
-        else:
-            dy = dpre
-        dx_raw, dnw, dnb = _Norm.backward(norm, dy.view(M, H), Wx_raw, nw, ctx.nsaved, cfg["training"],
-                                          ln_width=cfg.get("ln_width"))
-        dW = gemm_tn(dx_raw, x2)
-        dWb = _colsum(dx_raw) if ctx.needs_input_grad[3] else None
-        dx = gemm_nn(dx_raw, W).view(B, T, K) if ctx.needs_input_grad[1] else None
-        return None, dx, dW, dWb, dnw, dnb, dV
+        dx, dW, dWb, dnw, dnb = _project_backward(_LayerInput(x2), W, nw, cfg, ctx.nsaved, Wx_raw, dpre, dirs,
+                                                  need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                  ln_width=cfg.get("ln_width"))  # (anns.py:298-300: shared rows)
+        return None, None if dx is None else dx.view(B, T, K), dW, dWb, dnw, dnb, dV
 
 
 def _gemm_small(A, B, nn):
@@ -2031,21 +1998,20 @@ class GatedLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, x, *params):
         _require_device(x, "input")
-        kind, norm, training, dirs = cfg["kind"], cfg["normalization"], cfg["training"], cfg["dirs"]
+        kind, dirs = cfg["kind"], cfg["dirs"]
         mats = ("c", "z", "r") if kind == "GRU" else ("c", "z")
         P = {m: dict(zip(("W", "Wb", "nw", "nb", "V"), params[5 * i:5 * i + 5])) for i, m in enumerate(mats)}
-        x = _f32c(x)
         B, T, K = x.shape
         H = P["c"]["W"].shape[0]
         if H % 4 != 0:
             raise ValueError("sparch_amd: recurrent layers need hidden_size % 4 == 0")
-        M, Bp, dev = B * T, B * dirs, x.device
-        x2 = x.view(M, K)
+        Bp, dev = B * dirs, x.device
+        inp = _LayerInput(_f32c(x).view(B * T, K))
         proj = {}
         for m in mats:
-            raw, colstat = gemm_nt(x2, P[m]["W"], P[m]["Wb"], colstat=(norm == "batchnorm" and training))
-            z_in, sc, sh, nsaved = _Norm.forward(norm, raw, colstat, P[m]["nw"], P[m]["nb"], cfg["running"][m][0],
-                                                 cfg["running"][m][1], training, dirs, ln_width=cfg.get("ln_width"))
+            rm, rv = cfg["running"][m]
+            z_in, sc, sh, nsaved, raw = _project(inp, P[m]["W"], P[m]["Wb"], P[m]["nw"], P[m]["nb"],
+                                                 dict(cfg, running_mean=rm, running_var=rv), dirs, cfg.get("ln_width"))
             proj[m] = dict(raw=raw, z_in=z_in, sc=sc, sh=sh, nsaved=nsaved)
         Vgate = torch.cat([P["z"]["V"], P["r"]["V"] if kind == "GRU" else P["c"]["V"]], dim=0).contiguous()  # (2H,H)
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
@@ -2067,31 +2033,21 @@ class GatedLayerFn(torch.autograd.Function):
             vc = torch.empty(lib.sparch_gru_vpack_bytes(H, 0, 1) // 4, dtype=torch.float32, device=dev)
             check(lib.sparch_gru_vpack(H, ptr(P["z"]["V"]), ptr(P["r"]["V"]), ptr(P["c"]["V"]), 0, ptr(vg), ptr(vc),
                                        _stream(), _prec()), "sparch_gru_vpack")
-            nbytes = lib.sparch_gru_chan_bytes(Bp, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-            tok = timer.start("gru_fwd")
-            with _persistent_launch():
-                check(lib.sparch_gru_fwd(B, dirs, T, H, ptr(proj["c"]["z_in"]), ptr(proj["c"]["sc"]), ptr(proj["c"]["sh"]),
-                                         ptr(proj["z"]["z_in"]), ptr(proj["z"]["sc"]), ptr(proj["z"]["sh"]),
-                                         ptr(proj["r"]["z_in"]), ptr(proj["r"]["sc"]), ptr(proj["r"]["sh"]), ptr(vg), ptr(vc),
-                                         p_drop, seed, ptr(y_out), ptr(y_state), ptr(z_save), ptr(r_save), ptr(c_save),
-                                         ptr(chan), nbytes, ptr(status_word(dev)), rec_steps_per_launch(T), _stream()),
-                      "sparch_gru_fwd")
-            timer.stop(tok)
+            _persistent("gru_fwd", "sparch_gru_fwd",
+                        (B, dirs, T, H, ptr(proj["c"]["z_in"]), ptr(proj["c"]["sc"]), ptr(proj["c"]["sh"]),
+                         ptr(proj["z"]["z_in"]), ptr(proj["z"]["sc"]), ptr(proj["z"]["sh"]), ptr(proj["r"]["z_in"]),
+                         ptr(proj["r"]["sc"]), ptr(proj["r"]["sh"]), ptr(vg), ptr(vc), p_drop, seed, ptr(y_out),
+                         ptr(y_state), ptr(z_save), ptr(r_save), ptr(c_save)),
+                        lib.sparch_gru_chan_bytes(Bp, H), dev, rec_steps_per_launch(T))
         elif persistent:
             # the whole time loop in one persistent launch per row-tile group (gatedcell.hip)
             vp = torch.empty(lib.sparch_ligru_vpack_bytes(H, 0) // 4, dtype=torch.float32, device=dev)
             check(lib.sparch_ligru_vpack(H, ptr(P["z"]["V"]), ptr(P["c"]["V"]), 0, ptr(vp), _stream(), _prec()), "sparch_ligru_vpack")
-            nbytes = lib.sparch_ligru_chan_bytes(Bp, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
-            tok = timer.start("ligru_fwd")
-            with _persistent_launch():
-                check(lib.sparch_ligru_fwd(B, dirs, T, H, ptr(proj["c"]["z_in"]), ptr(proj["c"]["sc"]), ptr(proj["c"]["sh"]),
-                                           ptr(proj["z"]["z_in"]), ptr(proj["z"]["sc"]), ptr(proj["z"]["sh"]), ptr(vp),
-                                           p_drop, seed, ptr(y_out), ptr(y_state), ptr(z_save), ptr(c_save), ptr(chan),
-                                           nbytes, ptr(status_word(dev)), rec_steps_per_launch(T), _stream()),
-                      "sparch_ligru_fwd")
-            timer.stop(tok)
+            _persistent("ligru_fwd", "sparch_ligru_fwd",
+                        (B, dirs, T, H, ptr(proj["c"]["z_in"]), ptr(proj["c"]["sc"]), ptr(proj["c"]["sh"]),
+                         ptr(proj["z"]["z_in"]), ptr(proj["z"]["sc"]), ptr(proj["z"]["sh"]), ptr(vp), p_drop, seed,
+                         ptr(y_out), ptr(y_state), ptr(z_save), ptr(c_save)),
+                        lib.sparch_ligru_chan_bytes(Bp, H), dev, rec_steps_per_launch(T))
         else:
             tok = timer.start(f"gated_fwd[{kind}]")
             for t in range(T):
@@ -2106,21 +2062,21 @@ class GatedLayerFn(torch.autograd.Function):
         ctx.cfg, ctx.shape, ctx.mats = cfg, (B, T, K, H), mats
         ctx.nsaved = {m: proj[m]["nsaved"] for m in mats}
         ctx.needs_b = {m: P[m]["Wb"] is not None for m in mats}
-        saved = [x2, y_state, z_save, c_save, r_save, Vgate]
+        saved = [inp.x2, y_state, z_save, c_save, r_save, Vgate]
         for m in mats:
-            saved += [P[m]["W"], P[m]["nw"], P[m]["V"], proj[m]["raw"] if norm in ("batchnorm", "layernorm") else None]
+            saved += [P[m]["W"], P[m]["nw"], P[m]["V"], proj[m]["raw"]]
         ctx.save_for_backward(*saved)
         return y_out
 
     @staticmethod
     def backward(ctx, g_y):
         cfg, mats = ctx.cfg, ctx.mats
-        kind, norm, dirs = cfg["kind"], cfg["normalization"], cfg["dirs"]
+        kind, dirs = cfg["kind"], cfg["dirs"]
         B, T, K, H = ctx.shape
         sv = ctx.saved_tensors
         x2, y_state, z_save, c_save, r_save, Vgate = sv[:6]
         Pm = {m: dict(zip(("W", "nw", "V", "raw"), sv[6 + 4 * i:10 + 4 * i])) for i, m in enumerate(mats)}
-        M, Bp, dev = B * T, B * dirs, x2.device
+        Bp, dev = B * dirs, x2.device
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         d_all = {"z": new(Bp, T, H), "c": new(Bp, T, H)}
         yprev_all = new(Bp, T, H)
@@ -2139,29 +2095,20 @@ class GatedLayerFn(torch.autograd.Function):
             vc = torch.empty(lib.sparch_gru_vpack_bytes(H, 1, 1) // 4, dtype=torch.float32, device=dev)
             check(lib.sparch_gru_vpack(H, ptr(Pm["z"]["V"]), ptr(Pm["r"]["V"]), ptr(Pm["c"]["V"]), 1, ptr(vg), ptr(vc),
                                        _stream(), _prec()), "sparch_gru_vpack")
-            nbytes = lib.sparch_gru_chan_bytes(Bp, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
             carry = new(Bp, H)
-            tok = timer.start("gru_bwd")
-            with _persistent_launch():
-                check(lib.sparch_gru_bwd(B, dirs, T, H, ptr(_f32c(g_y)), ptr(y_state), ptr(z_save), ptr(r_save), ptr(c_save),
-                                         ptr(vg), ptr(vc), p_drop, seed, ptr(d_all["z"]), ptr(d_all["r"]), ptr(d_all["c"]),
-                                         ptr(yprev_all), ptr(ry_all), ptr(carry), ptr(chan), nbytes, ptr(status_word(dev)),
-                                         rec_steps_per_launch(T), _stream()), "sparch_gru_bwd")
-            timer.stop(tok)
+            _persistent("gru_bwd", "sparch_gru_bwd",
+                        (B, dirs, T, H, ptr(_f32c(g_y)), ptr(y_state), ptr(z_save), ptr(r_save), ptr(c_save), ptr(vg),
+                         ptr(vc), p_drop, seed, ptr(d_all["z"]), ptr(d_all["r"]), ptr(d_all["c"]), ptr(yprev_all),
+                         ptr(ry_all), ptr(carry)),
+                        lib.sparch_gru_chan_bytes(Bp, H), dev, rec_steps_per_launch(T))
         elif kind == "LiGRU" and ligru_persistent_ok(H):
             vpb = torch.empty(lib.sparch_ligru_vpack_bytes(H, 1) // 4, dtype=torch.float32, device=dev)
             check(lib.sparch_ligru_vpack(H, ptr(Pm["z"]["V"]), ptr(Pm["c"]["V"]), 1, ptr(vpb), _stream(), _prec()), "sparch_ligru_vpack")
-            nbytes = lib.sparch_ligru_chan_bytes(Bp, H)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
             carry = new(Bp, H)
-            tok = timer.start("ligru_bwd")
-            with _persistent_launch():
-                check(lib.sparch_ligru_bwd(B, dirs, T, H, ptr(_f32c(g_y)), ptr(y_state), ptr(z_save), ptr(c_save), ptr(vpb),
-                                           p_drop, seed, ptr(d_all["z"]), ptr(d_all["c"]), ptr(yprev_all), ptr(carry),
-                                           ptr(chan), nbytes, ptr(status_word(dev)), rec_steps_per_launch(T), _stream()),
-                      "sparch_ligru_bwd")
-            timer.stop(tok)
+            _persistent("ligru_bwd", "sparch_ligru_bwd",
+                        (B, dirs, T, H, ptr(_f32c(g_y)), ptr(y_state), ptr(z_save), ptr(c_save), ptr(vpb), p_drop, seed,
+                         ptr(d_all["z"]), ptr(d_all["c"]), ptr(yprev_all), ptr(carry)),
+                        lib.sparch_ligru_chan_bytes(Bp, H), dev, rec_steps_per_launch(T))
         else:
             carry_mv = carry_dir = None
             tok = timer.start(f"gated_bwd[{kind}]")
@@ -2185,17 +2132,13 @@ class GatedLayerFn(torch.autograd.Function):
             dV["c"] = gemm_tn(flat(d_all["c"]), flat(ry_all))
         else:
             dV["c"] = gemm_tn(flat(d_all["c"]), flat(yprev_all))
-        grads, dx_raws = {}, []
-        for m in mats:
-            if dirs == 2:  # both directions share the projection rows
-                dy = new(B, T, H)
-                check(lib.sparch_add_halves(M * H, ptr(d_all[m]), ptr(dy), _stream()), "sparch_add_halves")
-            else:
-                dy = d_all[m]
-            dx_raw, dnw, dnb = _Norm.backward(norm, dy.view(M, H), Pm[m]["raw"], Pm[m]["nw"], ctx.nsaved[m],
-                                              cfg["training"], ln_width=cfg.get("ln_width"))
+        grads, dx_raws, inp = {}, [], _LayerInput(x2)
+        for m in mats:  # per gate matrix; dx below is one product over the concatenated dx_raw
+            dx_raw, dW, dWb, dnw, dnb = _project_backward(inp, Pm[m]["W"], Pm[m]["nw"], cfg, ctx.nsaved[m], Pm[m]["raw"],
+                                                          d_all[m], dirs, need_dx=False, need_bias=ctx.needs_b[m],
+                                                          ln_width=cfg.get("ln_width"), raw_dx=True)
             dx_raws.append(dx_raw)
-            grads[m] = (gemm_tn(dx_raw, x2), _colsum(dx_raw) if ctx.needs_b[m] else None, dnw, dnb, dV[m])
+            grads[m] = (dW, dWb, dnw, dnb, dV[m])
         dx = None
         if ctx.needs_input_grad[1]:
             dx = gemm_nn(torch.cat(dx_raws, dim=1), torch.cat([Pm[m]["W"] for m in mats], dim=0)).view(B, T, K)

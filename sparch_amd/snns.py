@@ -435,9 +435,7 @@ class _SpikingLayer(nn.Module):
             getattr(self, "beta", None), getattr(self, "a", None), getattr(self, "b", None),
             self.V.weight if hasattr(self, "V") else None, u0, w0, s0)
         # lets the next layer take the exact bf16-split GEMMs and read the spikes as a bf16 plane (half the bytes)
-        has_plane = s16.numel() > 0
-        _tag_spikes(s, 1.0 / (1.0 - p_drop), s16 if has_plane else None,
-                    placeholder=has_plane and not fp32_out and not s.is_contiguous())
+        _tag_spikes(s, 1.0 / (1.0 - p_drop), s16, placeholder=not fp32_out and not s.is_contiguous())
         return s, rate
 
     def forward(self, x):
@@ -679,8 +677,7 @@ class SNN(nn.Module):
             else:
                 # between two layers of ours the spikes travel as a bf16 plane: no fp32 copy (unless somebody
                 # else may look at the layer's output: forward hooks, the network's own output)
-                inner = (i + 1 < len(self.snn) and Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16
-                         and not layer._forward_hooks and not _global_forward_hooks())
+                inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
                 x, r = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
                                                fp32_out=not inner)
                 if wait is not None:

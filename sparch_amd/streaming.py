@@ -84,7 +84,7 @@ class StreamingSNN:
         self._g_warm = 0
         self._g_replays = 0
         # inspection hook of the tests, not part of the interface: callable(layer_index, spikes (B,Tc,H)) called behind every chunk step for every hidden
-        # layer with the chunk's spikes as they travel to the next layer (the bf16 0/1 plane, or fp32); the tensor
+        # layer with the chunk's spikes as they travel to the next layer (the bf16 0/1 plane); the tensor
         # is only valid during the call (graph=True: a static buffer the next replay overwrites)
         self._spike_tap = None
 
@@ -137,9 +137,7 @@ class StreamingSNN:
                         L.vpack = None
                         check(lib.sparch_vmask(L.Hs, ptr(V), ptr(L.vmask), Fn._stream()), "sparch_vmask")
                     else:
-                        L.vpack = torch.empty(lib.sparch_vpack_bytes(L.Hs) // 4, dtype=torch.float32, device=dev)
-                        check(lib.sparch_vpack(L.Hs, ptr(V), 0, ptr(L.vpack), ptr(L.vmask), Fn._stream(), Fn._prec()),
-                              "sparch_vpack")
+                        L.vpack = Fn._vpack(L.Hs, V, 0, vmask=L.vmask)
                     L.vmask_t = L.vmask.t().contiguous()  # (H_out, H_in): the NT operand of the exact spike product
                 # state buffers: kept across refresh()
                 if old is not None:
@@ -282,7 +280,7 @@ class StreamingSNN:
         """s @ Vmasked for the state the next step starts from: the exact spike product on the bf16 plane once the
         state is binary (every chunk but the first after a reset), the dense six-term product on drawn states."""
         B = self.batch_size
-        if L.binary and Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16:
+        if L.binary:
             return Fn.gemm_nt(Fn.spike_placeholder(1, B, L.Hs, self._dev).view(B, L.Hs), L.vmask_t, spike_scale=1.0,
                               a16=L.s16)[0]
         if L.step_path:
@@ -290,13 +288,12 @@ class StreamingSNN:
         return Fn._gemm_small(L.s, L.vmask, nn=True)
 
     def _cell(self, L, Wx, Tc, want_fp32):
-        """Wx (B*Tc, H) normalised projection (or raw + scale / shift) -> (s fp32 or None, s16 or None), (B,Tc,H)."""
+        """Wx (B*Tc, H) normalised projection (or raw + scale / shift) -> (s fp32 or None, s16), (B,Tc,H)."""
         B, H, Hs, dev = self.batch_size, L.H, L.Hs, self._dev
-        plane = Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16
         if Hs != H:
             Wx = _pad_cols(Wx, Hs)
-        s16 = torch.empty(B, Tc, Hs, dtype=torch.bfloat16, device=dev) if plane else None
-        s_out = torch.empty(B, Tc, Hs, dtype=torch.float32, device=dev) if (want_fp32 or not plane) else None
+        s16 = torch.empty(B, Tc, Hs, dtype=torch.bfloat16, device=dev)
+        s_out = torch.empty(B, Tc, Hs, dtype=torch.float32, device=dev) if want_fp32 else None
         k, p = KIND[L.kind], L.p
         if not L.recurrent:
             check(lib.sparch_cell_stream_fwd(k, B, 1, Tc, Hs, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(p["alpha"]),
@@ -314,19 +311,14 @@ class StreamingSNN:
                 L.binary = True
         else:
             rec0 = self._rec_drive(L)
-            nbytes = lib.sparch_rec_chan_bytes(B, Tc, Hs)
-            chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-            with Fn._persistent_launch():
-                check(lib.sparch_rec_cell_stream_fwd(k, B, 1, Tc, Hs, ptr(Wx), ptr(L.scale), ptr(L.shift),
-                                                     ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
-                                                     ptr(p.get("b")), ptr(L.vpack), ptr(rec0), ptr(L.u), ptr(L.w),
-                                                     ptr(L.s), ptr(L.s16), L.theta, 0.0, ptr(s_out), ptr(s16),
-                                                     ptr(L.count), ptr(chan), nbytes, ptr(Fn.status_word(dev)),
-                                                     Fn.rec_steps_per_launch(Tc), Fn._stream(), Fn._prec()),
-                      "sparch_rec_cell_stream_fwd")
+            Fn._persistent(None, "sparch_rec_cell_stream_fwd",
+                           (k, B, 1, Tc, Hs, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(p["alpha"]), ptr(p.get("beta")),
+                            ptr(p.get("a")), ptr(p.get("b")), ptr(L.vpack), ptr(rec0), ptr(L.u), ptr(L.w), ptr(L.s),
+                            ptr(L.s16), L.theta, 0.0, ptr(s_out), ptr(s16), ptr(L.count)),
+                           lib.sparch_rec_chan_bytes(B, Tc, Hs), dev, Fn.rec_steps_per_launch(Tc), Fn._prec())
             L.binary = True
         if Hs != H:  # the next layer's operand at the layer's own width (the state stays padded)
-            s16 = None if s16 is None else s16[..., :H].contiguous()
+            s16 = s16[..., :H].contiguous()
             s_out = None if s_out is None else s_out[..., :H].contiguous()
         return s_out, s16
 
@@ -339,8 +331,6 @@ class StreamingSNN:
         """One chunk through every layer (eager launches, or the region a graph captures)."""
         B = self.batch_size
         Tc = x.shape[1]
-        M = B * Tc
-        dev = self._dev
         layers = self._layers
         s = s16 = None
         taps = []
@@ -348,27 +338,19 @@ class StreamingSNN:
             if i == 0:
                 # the network input, as SpikingLayerFn.forward takes it: its bf16 plane when every value is bf16-exact
                 # (binned spike counts are; decided on the device), the fp32 values otherwise
-                tag = Fn.input_plane_of(x)
-                x2 = x.view(M, L.K)
-                xplane = xflag = None
-                if tag is not None:
-                    xplane, xflag = tag
-                elif Fn.USE_SPIKE_GEMM and Fn.USE_SPIKE16 and Fn.USE_INPUT_PLANE and Fn.DENSE_GEMM == "split6":
-                    xplane, xflag = Fn.plane_bf16_exact(x2)
-                elif Fn.USE_SPIKE_GEMM:
-                    xflag = Fn.flag_bf16_exact(x2)
-                Wx_raw, _ = Fn.gemm_nt(x2, L.W, L.Wb, a_exact_flag=xflag, a_plane=xplane)
-            else:
-                x2 = (s if s16 is None else Fn.spike_placeholder(B, Tc, L.K, dev)).view(M, L.K)
-                Wx_raw, _ = Fn.gemm_nt(x2, L.W, L.Wb, spike_scale=1.0, a16=None if s16 is None else s16.view(M, L.K),
-                                       b_planes=L.w_planes)
+                inp = Fn._layer_input({"in_plane": Fn.input_plane_of(x)}, x)
+                Wx_raw, _ = inp.project(L.W, L.Wb, False)
+            else:  # the previous layer's spikes: their bf16 plane, beside a placeholder nobody reads
+                inp = Fn._layer_input({"in_spike_scale": 1.0, "in_spike16": s16},
+                                      Fn.spike_placeholder(B, Tc, L.K, self._dev))
+                Wx_raw, _ = inp.project(L.W, L.Wb, False, b_planes=L.w_planes)
             Wx = self._norm(L, Wx_raw)
             if L.readout:
                 check(lib.sparch_readout_stream_fwd(B, Tc, L.H, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(L.p["alpha"]),
                                                     ptr(L.u), ptr(L.out), Fn._stream()), "sparch_readout_stream_fwd")
                 return L.out, taps
             s, s16 = self._cell(L, Wx, Tc, want_fp32=(i + 1 == len(layers)))
-            taps.append(s if s16 is None else s16)
+            taps.append(s16)
         return s, taps
 
     def _emit(self, taps):
