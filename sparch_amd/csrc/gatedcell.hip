@@ -31,8 +31,6 @@
 // cannot be co-resident (or after a timeout) the host takes the launch-per-step path of annstep.hip.
 #include "rec_common.h"
 
-#include <type_traits>
-
 namespace {
 
 constexpr int UT = 16;  // hidden units per workgroup
@@ -69,23 +67,36 @@ __device__ __forceinline__ f32x4 affine4(const float* W, const float* sc, const 
     return v;
 }
 
-// exact truncation split of 8 fp32 values (two 16-byte pieces) into three bf16 fragments
-__device__ __forceinline__ void split_pieces(const u32x4& lo4, const u32x4& hi4, u32x4& p1, u32x4& p2, u32x4& p3) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            const unsigned x0 = (q ? hi4 : lo4)[2 * pr], x1 = (q ? hi4 : lo4)[2 * pr + 1];
-            const float r0 = __uint_as_float(x0) - __uint_as_float(x0 & 0xFFFF0000u);
-            const float r1 = __uint_as_float(x1) - __uint_as_float(x1 & 0xFFFF0000u);
-            const unsigned y0 = __float_as_uint(r0), y1 = __float_as_uint(r1);
-            const float q0 = r0 - __uint_as_float(y0 & 0xFFFF0000u);
-            const float q1 = r1 - __uint_as_float(y1 & 0xFFFF0000u);
-            p1[2 * q + pr] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);
-            p2[2 * q + pr] = __builtin_amdgcn_perm(y1, y0, 0x07060302u);
-            p3[2 * q + pr] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-        }
-}
+// Who a thread is, in all four kernels: 8 waves multiply; the first 128 threads also own the pointwise work, row r
+// (of the 32 of row tile rt) x 4 consecutive units (of the 16 of column tile ct).
+struct Geo {
+    int tid, lane, wave, rt, ct;
+    bool pw, valid;           // a pointwise thread; ... whose row and units exist
+    int r, uq, bp, unit;      // row in the tile, unit quad; padded batch row, first unit
+    int bpc, uc, d, b;        // the two clamped (for loads of threads that are not valid); direction, batch row
+    int p16;                  // 16x16x32 A-fragment order: piece of row r, k-quarter 0, k-half uq & 1 (see the backward)
+    __device__ __forceinline__ explicit Geo(const LigruArgs& a) {
+        tid = threadIdx.x;
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
+        ct = (int)(blockIdx.x / a.n_rt_launch);
+        pw = tid < 128;
+        r = (tid & 127) >> 2; uq = tid & 3;
+        bp = rt * RT + r; unit = ct * UT + uq * 4;
+        valid = pw && bp < a.Bp && unit < a.H;
+        bpc = min(bp, a.Bp - 1); uc = min(unit, a.H - 4);
+        d = bpc / a.B; b = bpc - d * a.B;
+        p16 = (((r >> 4) * 2 + (uq & 1)) * 64 + (r & 15)) * 16;
+    }
+    // forward tile order (32x32x16 A fragments): this thread's 4 units are one 16-byte piece of k16-step (ct & 1) of
+    // ring tile ct >> 1 — the byte offset of that piece in a row tile's part of a slot
+    __device__ __forceinline__ unsigned piece32() const {
+        return (unsigned)(ct >> 1) * TILE_BYTES + (unsigned)(((((ct & 1) * 2 + (uq & 1)) * 64) + (uq >> 1) * 32 + r) * 16);
+    }
+    // 16x16x32 A-fragment order, k-quarter kq of a tile
+    __device__ __forceinline__ unsigned piece16(int kq) const { return (unsigned)(p16 + kq * 16 * 16); }
+};
 
 // ------------------------------------------------------------------------------ forward
 // vpack[ct][kg][ks][p][lane] = 8 bf16 of plane p: rows k = kg*32 + 16*ks + 8*(lane>>5) + j of column
@@ -96,115 +107,55 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_fwd_kernel(LigruArgs a) {
     __shared__ __attribute__((aligned(16))) u32x4 vlo[NW][KGW][2][64];
     __shared__ int abort_flag[2];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, hh = lane >> 5;
-    const int rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
-    const int ct = (int)(blockIdx.x / a.n_rt_launch);
+    const Geo g(a);
     const int T = a.T, H = a.H, HO = a.H * a.dirs;
 
-    // pointwise ownership: 128 threads, row r, 4 consecutive units
-    const bool pw = tid < 128;
-    const int r = (tid & 127) >> 2, uq = tid & 3;
-    const int bp = rt * RT + r, unit = ct * UT + uq * 4;
-    const bool valid = pw && bp < a.Bp && unit < H;
-    const int bpc = min(bp, a.Bp - 1), uc = min(unit, H - 4);
-    const int d = bpc / a.B, b = bpc - d * a.B;
-
     u32x4 vb[KGW][2][2];
-#pragma unroll
-    for (int kk = 0; kk < KGW; ++kk) {
-        const int kg = wave + NW * kk;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const u32x4* src = a.vpack + ((((size_t)ct * (NW * KGW) + kg) * 2 + ks) * 3) * 64 + lane;
-            vb[kk][ks][0] = src[0];
-            vb[kk][ks][1] = src[64];
-            vlo[wave][kk][ks][lane] = src[128];
-        }
-    }
-    if (tid < 2) abort_flag[tid] = 0;
+    load_slice32<KGW, NW>(vb, vlo[g.wave], a.vpack, g.ct, NW * KGW, g.wave, g.lane);
+    if (g.tid < 2) abort_flag[g.tid] = 0;
     __syncthreads();
 
     const unsigned slot_bytes = (unsigned)((size_t)a.n_rt_total * a.n_kg * TILE_BYTES);
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, (int)(RING * slot_bytes), 0x00020000);
-    const unsigned rt_off = (unsigned)((size_t)rt * a.n_kg * TILE_BYTES);
+    const unsigned rt_off = (unsigned)((size_t)g.rt * a.n_kg * TILE_BYTES);
     const bool drop = a.p_drop > 0.0f;
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     f32x4 yp = zero4;  // y_{t-1} of this thread's 4 units (zeros at t = 0, anns.py:452)
-    if (pw && a.s_begin > 0) yp = ld4(a.y_state + ((size_t)bpc * T + (a.s_begin - 1)) * H + uc);
+    if (g.pw && a.s_begin > 0) yp = ld4(a.y_state + ((size_t)g.bpc * T + (a.s_begin - 1)) * H + g.uc);
     auto load_x = [&](int t, f32x4& xz, f32x4& xc) {
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o = ((size_t)b * T + tt) * H + uc;
-        xz = affine4(a.Wzx, a.scz, a.shz, o, uc);
-        xc = affine4(a.Wx, a.sc, a.sh, o, uc);
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o = ((size_t)g.b * T + tt) * H + g.uc;
+        xz = affine4(a.Wzx, a.scz, a.shz, o, g.uc);
+        xc = affine4(a.Wx, a.sc, a.sh, o, g.uc);
     };
     f32x4 xz_n = zero4, xc_n = zero4;
-    if (pw) load_x(a.s_begin, xz_n, xc_n);
+    if (g.pw) load_x(a.s_begin, xz_n, xc_n);
 
     for (int s = a.s_begin; s < a.s_end; ++s) {
         const f32x4 xz = xz_n, xc = xc_n;
         const int par = s & 1;
-        if (pw && s + 1 < a.s_end) load_x(s + 1, xz_n, xc_n);
+        if (g.pw && s + 1 < a.s_end) load_x(s + 1, xz_n, xc_n);
+        // ---- [z | c] pre-activations: y_{t-1} [Vz | V]^T
         float rz[4] = {0.f, 0.f, 0.f, 0.f}, rc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (s > 0) {
-            const unsigned base = (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;
-            u32x4 raw[KGW][2][2];
-#pragma unroll
-            for (int kk = 0; kk < AHEAD; ++kk) issue_tile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_kg);
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KGW; ++kk) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (wave + NW * kk < a.n_kg)
-                    settle_tile(raw[kk], rsrc, base + (unsigned)(wave + NW * kk) * TILE_BYTES, &abort_flag[par]);
-                if (kk + AHEAD < KGW) issue_tile<NW>(raw[kk + AHEAD], rsrc, base, wave + NW * (kk + AHEAD), a.n_kg);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    u32x4 p1, p2, p3;
-                    split_pieces(raw[kk][ks][0], raw[kk][ks][1], p1, p2, p3);
-                    const u32x4 vl = vlo[wave][kk][ks][lane];
-                    acc = mfma_bf16(p2, vb[kk][ks][1], acc);  // t2*mid
-                    acc = mfma_bf16(p3, vb[kk][ks][0], acc);  // t3*hi
-                    acc = mfma_bf16(p1, vl, acc);             // t1*lo
-                    acc = mfma_bf16(p2, vb[kk][ks][0], acc);  // t2*hi
-                    acc = mfma_bf16(p1, vb[kk][ks][1], acc);  // t1*mid
-                    acc = mfma_bf16(p1, vb[kk][ks][0], acc);  // t1*hi
-                }
-            }
-            float* rd = red[wave];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
-                rd[row * RED_LD + li] = acc[i];
-            }
-        }
+        if (s > 0)
+            ring_product32<KGW, NW, 2>(vb, vlo[g.wave], rsrc, (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)g.lane * 16u,
+                                       a.n_kg, g.wave, g.lane, &abort_flag[par], red[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (s > 0 && pw) {
+        if (s > 0 && g.pw) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float sz = red[0][r * RED_LD + uq * 4 + e], sc_ = red[0][r * RED_LD + UT + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) {
-                    sz = sz + red[w][r * RED_LD + uq * 4 + e];
-                    sc_ = sc_ + red[w][r * RED_LD + UT + uq * 4 + e];
-                }
-                rz[e] = sz; rc[e] = sc_;
+                rz[e] = wave_sum(red, g.r * RED_LD + g.uq * 4 + e);
+                rc[e] = wave_sum(red, g.r * RED_LD + UT + g.uq * 4 + e);
             }
         }
         // ---- gates (anns.py:457-459)
         const int t = s;
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o_out = ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc;
         f32x4 z, c, y, yo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -214,158 +165,83 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_fwd_kernel(LigruArgs a) {
             y[e] = z[e] * yp[e] + (1.0f - z[e]) * c[e];
             const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
             yo[e] = y[e] * k;
-            if (!valid) y[e] = 0.0f;
+            if (!g.valid) y[e] = 0.0f;
         }
-        // ---- publish y_t: this thread's 4 units are one 16-byte piece of k16-step (ct & 1) of ring tile ct >> 1
-        if (pw) {
-            const int ksp = ct & 1, hq = uq >> 1, qq = uq & 1;
-            const unsigned piece = (unsigned)((((ksp * 2 + qq) * 64) + hq * 32 + r) * 16);
-            const unsigned tile_off = rt_off + (unsigned)(ct >> 1) * TILE_BYTES + piece;
-            if (s + 1 < T) {
-                u32x4 rawv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(y[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, AUX_SC1);
-            }
-            if (s >= 2) {
-                const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, AUX_SC1);
-            }
-        }
+        // ---- publish y_t (the last step's has no reader)
+        if (g.pw) publish_piece(rsrc, slot_bytes, rt_off + g.piece32(), s, s + 1 < T, y);
         lds_barrier();
-        if (valid) {
-            const size_t o_st = ((size_t)bp * T + t) * H + unit;
+        if (g.valid) {
+            const size_t o_st = ((size_t)g.bp * T + t) * H + g.unit;
             st4(a.y_state + o_st, y); st4(a.z_save + o_st, z); st4(a.c_save + o_st, c);
-            st4(a.y_out + ((size_t)b * T + tt) * HO + (size_t)d * H + unit, yo);
+            st4(a.y_out + ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.unit, yo);
         }
         yp = y;
     }
-    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
-        status_raise(a.status, SPARCH_STATUS_LIGRU_FWD, -1);
+    raise_if_aborted(abort_flag, a.status, SPARCH_STATUS_LIGRU_FWD, g.tid);
 }
 
 // ------------------------------------------------------------------------------ backward
-// v_mfma_f32_16x16x32_bf16: A fragment = lane (row lane & 15, k-quarter lane >> 4) holds k = 8*(lane>>4) .. +7;
-// B fragment = lane (column lane & 15, same k-quarter); C = 4 rows (4*(lane>>4) .. +3) of column lane & 15.
+// On the 16x16x32 MFMA (fragment layout: mfma16, rec_common.h).
 // A producer's tile: 32 rows x 32 k, k < 16 = dz_pre of its unit k, k >= 16 = dc_pre of unit k - 16, stored as
 // 16-byte pieces ((mb*2 + half)*64 + kq*16 + row16): row = 16*mb + row16, k = 8*kq + 4*half .. +3 — the four
-// 1 KiB wave-loads of a tile are (mb, half) = (0,0), (0,1), (1,0), (1,1).
+// 1 KiB wave-loads of a tile are (mb, half) = (0,0), (0,1), (1,0), (1,1).  A thread's dz_pre quad is k-quarter
+// uq >> 1, its dc_pre quad k-quarter 2 + (uq >> 1), both k-half uq & 1 (Geo::piece16).
 // vpack[ct][kg][p][lane] = 8 bf16 of plane p: k = 8*(lane>>4) + j of k-group kg (= producer tile kg), column
 // lane & 15 = unit ct*16 + (lane & 15):  k < 16: Vz[kg*16 + k][unit],  k >= 16: V[kg*16 + k - 16][unit].
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-constexpr int RED16 = 17;
-
 template <int KGW, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void ligru_bwd_kernel(LigruArgs a) {
     __shared__ __attribute__((aligned(16))) float red[NW][RT * RED16];
     __shared__ __attribute__((aligned(16))) u32x4 vlo[NW][KGW][64];
     __shared__ int abort_flag[2];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
-    const int ct = (int)(blockIdx.x / a.n_rt_launch);
+    const Geo g(a);
     const int T = a.T, H = a.H, HO = a.H * a.dirs;
 
-    const bool pw = tid < 128;
-    const int r = (tid & 127) >> 2, uq = tid & 3;
-    const int bp = rt * RT + r, unit = ct * UT + uq * 4;
-    const bool valid = pw && bp < a.Bp && unit < H;
-    const int bpc = min(bp, a.Bp - 1), uc = min(unit, H - 4);
-    const int d = bpc / a.B, b = bpc - d * a.B;
-
     u32x4 vb[KGW][2];
-#pragma unroll
-    for (int kk = 0; kk < KGW; ++kk) {
-        const int kg = wave + NW * kk;
-        const u32x4* src = a.vpack + (((size_t)ct * (NW * KGW) + kg) * 3) * 64 + lane;
-        vb[kk][0] = src[0];
-        vb[kk][1] = src[64];
-        vlo[wave][kk][lane] = src[128];
-    }
-    if (tid < 2) abort_flag[tid] = 0;
+    load_slice16<KGW, NW>(vb, vlo[g.wave], a.vpack, g.ct, g.wave, g.lane);
+    if (g.tid < 2) abort_flag[g.tid] = 0;
     __syncthreads();
 
     const unsigned slot_bytes = (unsigned)((size_t)a.n_rt_total * a.n_ct * TILE_BYTES);
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, (int)(RING * slot_bytes), 0x00020000);
-    const unsigned rt_off = (unsigned)((size_t)rt * a.n_ct * TILE_BYTES);
+    const unsigned rt_off = (unsigned)((size_t)g.rt * a.n_ct * TILE_BYTES);
     const bool drop = a.p_drop > 0.0f;
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     f32x4 cdir = zero4;  // dy_{t+1} z_{t+1}
-    if (pw && a.s_begin > 0) cdir = ld4(a.carry + (size_t)bpc * H + uc);
-    auto load_step = [&](int s, f32x4& g, f32x4& z, f32x4& c, f32x4& ypv) {
+    if (g.pw && a.s_begin > 0) cdir = ld4(a.carry + (size_t)g.bpc * H + g.uc);
+    auto load_step = [&](int s, f32x4& gv, f32x4& z, f32x4& c, f32x4& ypv) {
         const int t = T - 1 - s;
-        const int tt = d ? (T - 1 - t) : t;
-        g = ld4(a.g_out + ((size_t)b * T + tt) * HO + (size_t)d * H + uc);
-        const size_t o_st = ((size_t)bpc * T + t) * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        gv = ld4(a.g_out + ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc);
+        const size_t o_st = ((size_t)g.bpc * T + t) * H + g.uc;
         z = ld4(a.z_save + o_st); c = ld4(a.c_save + o_st);
         ypv = t > 0 ? ld4(a.y_state + o_st - H) : zero4;
     };
     f32x4 g_n = zero4, z_n = zero4, c_n = zero4, yp_n = zero4;
-    if (pw) load_step(a.s_begin, g_n, z_n, c_n, yp_n);
+    if (g.pw) load_step(a.s_begin, g_n, z_n, c_n, yp_n);
 
     for (int s = a.s_begin; s < a.s_end; ++s) {
         const f32x4 gv = g_n, zv = z_n, cv = c_n, ypv = yp_n;
         const int par = s & 1;
-        if (pw && s + 1 < a.s_end) load_step(s + 1, g_n, z_n, c_n, yp_n);
+        if (g.pw && s + 1 < a.s_end) load_step(s + 1, g_n, z_n, c_n, yp_n);
+        // ---- [dz_pre | dc_pre]_{t+1} [Vz ; V]
         float cmv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (s > 0) {
-            const unsigned base = (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            u32x4 raw[2][2][2];  // [parity of kk][mb][half]: one tile ahead
-            auto issue = [&](int kk) {
-                const int kg = wave + NW * kk;
-                issue_tile<NW>(raw[kk & 1], rsrc, base, kg, a.n_ct);  // pieces (mb*2 + half)*1024: same offsets
-            };
-            issue(0);
-            f32x4 acc[2] = {zero4, zero4};
-#pragma unroll
-            for (int kk = 0; kk < KGW; ++kk) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (wave + NW * kk < a.n_ct)
-                    settle_tile(raw[kk & 1], rsrc, base + (unsigned)(wave + NW * kk) * TILE_BYTES, &abort_flag[par]);
-                if (kk + 1 < KGW) issue(kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                const u32x4 vl = vlo[wave][kk][lane];
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    u32x4 p1, p2, p3;
-                    split_pieces(raw[kk & 1][mb][0], raw[kk & 1][mb][1], p1, p2, p3);
-                    acc[mb] = mfma16(p2, vb[kk][1], acc[mb]);  // t2*mid
-                    acc[mb] = mfma16(p3, vb[kk][0], acc[mb]);  // t3*hi
-                    acc[mb] = mfma16(p1, vl, acc[mb]);         // t1*lo
-                    acc[mb] = mfma16(p2, vb[kk][0], acc[mb]);  // t2*hi
-                    acc[mb] = mfma16(p1, vb[kk][1], acc[mb]);  // t1*mid
-                    acc[mb] = mfma16(p1, vb[kk][0], acc[mb]);  // t1*hi
-                }
-            }
-            float* rd = red[wave];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    rd[(16 * mb + 4 * (lane >> 4) + i) * RED16 + (lane & 15)] = acc[mb][i];
-        }
+        if (s > 0)
+            ring_product16<KGW, NW>(vb, vlo[g.wave], rsrc, (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)g.lane * 16u,
+                                    a.n_ct, g.wave, g.lane, &abort_flag[par], red[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (s > 0 && pw) {
+        if (s > 0 && g.pw) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sum = red[0][r * RED16 + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) sum = sum + red[w][r * RED16 + uq * 4 + e];
-                cmv[e] = sum;
-            }
+            for (int e = 0; e < 4; ++e) cmv[e] = wave_sum(red, g.r * RED16 + g.uq * 4 + e);
         }
         // ---- gate gradients (annstep.hip mode 3)
         const int t = T - 1 - s;
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o_out = ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc;
         f32x4 dzp, dcp, cdo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -374,39 +250,23 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_bwd_kernel(LigruArgs a) {
             dzp[e] = (dy * (ypv[e] - cv[e])) * (zv[e] * (1.0f - zv[e]));
             dcp[e] = cv[e] > 0.0f ? dy * (1.0f - zv[e]) : 0.0f;
             cdo[e] = dy * zv[e];
-            if (!valid) { dzp[e] = 0.0f; dcp[e] = 0.0f; }
+            if (!g.valid) { dzp[e] = 0.0f; dcp[e] = 0.0f; }
         }
-        // ---- publish [dz_pre | dc_pre]: two 16-byte pieces of this workgroup's tile, in A-fragment order
-        if (pw) {
-            const int mb = r >> 4, row16 = r & 15, half = uq & 1;
-            const unsigned pz = (unsigned)((((mb * 2 + half) * 64) + (uq >> 1) * 16 + row16) * 16);
-            const unsigned pc = (unsigned)((((mb * 2 + half) * 64) + (2 + (uq >> 1)) * 16 + row16) * 16);
-            const unsigned tile_off = rt_off + (unsigned)ct * TILE_BYTES;
-            if (s + 1 < T) {
-                u32x4 rz, rc;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { rz[e] = __float_as_uint(dzp[e]); rc[e] = __float_as_uint(dcp[e]); }
-                const unsigned so = (unsigned)(s % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(rz, rsrc, so + pz, 0, AUX_SC1);
-                __builtin_amdgcn_raw_buffer_store_b128(rc, rsrc, so + pc, 0, AUX_SC1);
-            }
-            if (s >= 2) {
-                const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
-                const unsigned so = (unsigned)((s - 2) % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, AUX_SC1);
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pc, 0, AUX_SC1);
-            }
+        // ---- publish [dz_pre | dc_pre]: two 16-byte pieces of this workgroup's tile
+        if (g.pw) {
+            const unsigned tile_off = rt_off + (unsigned)g.ct * TILE_BYTES;
+            publish_piece(rsrc, slot_bytes, tile_off + g.piece16(g.uq >> 1), s, s + 1 < T, dzp);
+            publish_piece(rsrc, slot_bytes, tile_off + g.piece16(2 + (g.uq >> 1)), s, s + 1 < T, dcp);
         }
         lds_barrier();
-        if (valid) {
-            const size_t o_or = ((size_t)bp * T + tt) * H + unit;
+        if (g.valid) {
+            const size_t o_or = ((size_t)g.bp * T + tt) * H + g.unit;
             st4(a.dz_all + o_or, dzp); st4(a.dc_all + o_or, dcp); st4(a.yprev_all + o_or, ypv);
         }
         cdir = cdo;
     }
-    if (valid) st4(a.carry + (size_t)bp * H + unit, cdir);
-    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
-        status_raise(a.status, SPARCH_STATUS_LIGRU_BWD, -1);
+    if (g.valid) st4(a.carry + (size_t)g.bp * H + g.unit, cdir);
+    raise_if_aborted(abort_flag, a.status, SPARCH_STATUS_LIGRU_BWD, g.tid);
 }
 
 
@@ -415,7 +275,8 @@ __global__ __launch_bounds__(64 * NW, 1) void ligru_bwd_kernel(LigruArgs a) {
 // vpack2[ct][kg][p][lane] = 8 bf16 of plane p of V: column lane & 15 = unit ct*16 + (lane & 15),
 // k = kg*32 + 8*(lane>>4) + j  (B fragment of the 16x16x32 MFMA for (r y) V^T).
 // Ring 1 carries y (forward tile order), ring 2 carries q = r y: 32 rows x 32 k per tile in the 16x16x32
-// A-fragment order (see the LiGRU backward), producer ct = k 16*(ct & 1) .. +15 of tile ct >> 1.
+// A-fragment order (see the LiGRU backward), producer ct = k 16*(ct & 1) .. +15 of tile ct >> 1, i.e. its units'
+// k-quarters are 2*(ct & 1) + (uq >> 1).
 template <int KGW, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
     __shared__ __attribute__((aligned(16))) float red[NW][RT * RED_LD];
@@ -424,116 +285,52 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
     __shared__ __attribute__((aligned(16))) u32x4 vlo2[NW][KGW][64];
     __shared__ int abort_flag[2];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, hh = lane >> 5;
-    const int rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
-    const int ct = (int)(blockIdx.x / a.n_rt_launch);
+    const Geo g(a);
     const int T = a.T, H = a.H, HO = a.H * a.dirs;
 
-    const bool pw = tid < 128;
-    const int r = (tid & 127) >> 2, uq = tid & 3;
-    const int bp = rt * RT + r, unit = ct * UT + uq * 4;
-    const bool valid = pw && bp < a.Bp && unit < H;
-    const int bpc = min(bp, a.Bp - 1), uc = min(unit, H - 4);
-    const int d = bpc / a.B, b = bpc - d * a.B;
-
     u32x4 vb[KGW][2][2], vc[KGW][2];
-#pragma unroll
-    for (int kk = 0; kk < KGW; ++kk) {
-        const int kg = wave + NW * kk;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const u32x4* src = a.vpack + ((((size_t)ct * (NW * KGW) + kg) * 2 + ks) * 3) * 64 + lane;
-            vb[kk][ks][0] = src[0];
-            vb[kk][ks][1] = src[64];
-            vlo[wave][kk][ks][lane] = src[128];
-        }
-        const u32x4* src2 = a.vpack2 + (((size_t)ct * (NW * KGW) + kg) * 3) * 64 + lane;
-        vc[kk][0] = src2[0];
-        vc[kk][1] = src2[64];
-        vlo2[wave][kk][lane] = src2[128];
-    }
-    if (tid < 2) abort_flag[tid] = 0;
+    load_slice32<KGW, NW>(vb, vlo[g.wave], a.vpack, g.ct, NW * KGW, g.wave, g.lane);
+    load_slice16<KGW, NW>(vc, vlo2[g.wave], a.vpack2, g.ct, g.wave, g.lane);
+    if (g.tid < 2) abort_flag[g.tid] = 0;
     __syncthreads();
 
     const unsigned slot_bytes = (unsigned)((size_t)a.n_rt_total * a.n_kg * TILE_BYTES);  // both rings
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, (int)(RING * slot_bytes), 0x00020000);
     __amdgpu_buffer_rsrc_t rsrc2 = __builtin_amdgcn_make_buffer_rsrc(a.ring2, 0, (int)(RING * slot_bytes), 0x00020000);
-    const unsigned rt_off = (unsigned)((size_t)rt * a.n_kg * TILE_BYTES);
+    const unsigned rt_off = (unsigned)((size_t)g.rt * a.n_kg * TILE_BYTES);
     const bool drop = a.p_drop > 0.0f;
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
 
     f32x4 yp = zero4;  // y_{t-1} of this thread's 4 units (zeros at t = 0, anns.py:584)
-    if (pw && a.s_begin > 0) yp = ld4(a.y_state + ((size_t)bpc * T + (a.s_begin - 1)) * H + uc);
+    if (g.pw && a.s_begin > 0) yp = ld4(a.y_state + ((size_t)g.bpc * T + (a.s_begin - 1)) * H + g.uc);
     auto load_x = [&](int t, f32x4& xz, f32x4& xr, f32x4& xc) {
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o = ((size_t)b * T + tt) * H + uc;
-        xz = affine4(a.Wzx, a.scz, a.shz, o, uc);
-        xr = affine4(a.Wrx, a.scr, a.shr, o, uc);
-        xc = affine4(a.Wx, a.sc, a.sh, o, uc);
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o = ((size_t)g.b * T + tt) * H + g.uc;
+        xz = affine4(a.Wzx, a.scz, a.shz, o, g.uc);
+        xr = affine4(a.Wrx, a.scr, a.shr, o, g.uc);
+        xc = affine4(a.Wx, a.sc, a.sh, o, g.uc);
     };
     f32x4 xz_n = zero4, xr_n = zero4, xc_n = zero4;
-    if (pw) load_x(a.s_begin, xz_n, xr_n, xc_n);
+    if (g.pw) load_x(a.s_begin, xz_n, xr_n, xc_n);
 
     for (int s = a.s_begin; s < a.s_end; ++s) {
         const f32x4 xz = xz_n, xr = xr_n, xc = xc_n;
         const int par = s & 1;
-        if (pw && s + 1 < a.s_end) load_x(s + 1, xz_n, xr_n, xc_n);
+        if (g.pw && s + 1 < a.s_end) load_x(s + 1, xz_n, xr_n, xc_n);
         // ---- [z | r] pre-activations: y_{t-1} [Vz | Vr]^T
         float rz[4] = {0.f, 0.f, 0.f, 0.f}, rr[4] = {0.f, 0.f, 0.f, 0.f}, rc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (s > 0) {
-            const unsigned base = (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;
-            u32x4 raw[KGW][2][2];
-#pragma unroll
-            for (int kk = 0; kk < AHEAD; ++kk) issue_tile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_kg);
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KGW; ++kk) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (wave + NW * kk < a.n_kg)
-                    settle_tile(raw[kk], rsrc, base + (unsigned)(wave + NW * kk) * TILE_BYTES, &abort_flag[par]);
-                if (kk + AHEAD < KGW) issue_tile<NW>(raw[kk + AHEAD], rsrc, base, wave + NW * (kk + AHEAD), a.n_kg);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    u32x4 p1, p2, p3;
-                    split_pieces(raw[kk][ks][0], raw[kk][ks][1], p1, p2, p3);
-                    const u32x4 vl = vlo[wave][kk][ks][lane];
-                    acc = mfma_bf16(p2, vb[kk][ks][1], acc);  // t2*mid
-                    acc = mfma_bf16(p3, vb[kk][ks][0], acc);  // t3*hi
-                    acc = mfma_bf16(p1, vl, acc);             // t1*lo
-                    acc = mfma_bf16(p2, vb[kk][ks][0], acc);  // t2*hi
-                    acc = mfma_bf16(p1, vb[kk][ks][1], acc);  // t1*mid
-                    acc = mfma_bf16(p1, vb[kk][ks][0], acc);  // t1*hi
-                }
-            }
-            float* rd = red[wave];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
-                rd[row * RED_LD + li] = acc[i];
-            }
-        }
+        if (s > 0)
+            ring_product32<KGW, NW, 2>(vb, vlo[g.wave], rsrc, (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)g.lane * 16u,
+                                       a.n_kg, g.wave, g.lane, &abort_flag[par], red[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (s > 0 && pw) {
+        if (s > 0 && g.pw) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float sz = red[0][r * RED_LD + uq * 4 + e], sr = red[0][r * RED_LD + UT + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) {
-                    sz = sz + red[w][r * RED_LD + uq * 4 + e];
-                    sr = sr + red[w][r * RED_LD + UT + uq * 4 + e];
-                }
-                rz[e] = sz; rr[e] = sr;
+                rz[e] = wave_sum(red, g.r * RED_LD + g.uq * 4 + e);
+                rr[e] = wave_sum(red, g.r * RED_LD + UT + g.uq * 4 + e);
             }
         }
         // ---- gates (anns.py:589-590) and q = r y_{t-1}
@@ -542,71 +339,27 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
         for (int e = 0; e < 4; ++e) {
             z[e] = sigm(xz[e] + rz[e]);
             rg[e] = sigm(xr[e] + rr[e]);
-            q[e] = valid ? rg[e] * yp[e] : 0.0f;
+            q[e] = g.valid ? rg[e] * yp[e] : 0.0f;
         }
         // ---- publish q (steps > 0: y_{-1} = 0 makes step 0's product zero, nobody reads a step-0 tile)
-        const int mbp = r >> 4, row16 = r & 15;
-        const unsigned qpiece = (unsigned)((((mbp * 2 + (uq & 1)) * 64) + ((ct & 1) * 2 + (uq >> 1)) * 16 + row16) * 16);
-        const unsigned qtile = rt_off + (unsigned)(ct >> 1) * TILE_BYTES + qpiece;
-        if (pw) {
-            if (s > 0) {
-                u32x4 rawv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(q[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot_bytes + qtile, 0, AUX_SC1);
-            }
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot_bytes + qtile, 0, AUX_SC1);
-        }
-        // ---- candidate pre-activation: q V^T on the 16x16x32 MFMA
-        if (s > 0) {
-            const unsigned base = (unsigned)(s % RING) * slot_bytes + rt_off + (unsigned)lane * 16u;
-            u32x4 raw[2][2][2];  // [parity of kk][mb][half]: one tile ahead
-            auto issue = [&](int kk) { issue_tile<NW>(raw[kk & 1], rsrc2, base, wave + NW * kk, a.n_kg); };
-            issue(0);
-            f32x4 acc[2] = {zero4, zero4};
-#pragma unroll
-            for (int kk = 0; kk < KGW; ++kk) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (wave + NW * kk < a.n_kg)
-                    settle_tile(raw[kk & 1], rsrc2, base + (unsigned)(wave + NW * kk) * TILE_BYTES, &abort_flag[par]);
-                if (kk + 1 < KGW) issue(kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                const u32x4 vl = vlo2[wave][kk][lane];
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    u32x4 p1, p2, p3;
-                    split_pieces(raw[kk & 1][mb][0], raw[kk & 1][mb][1], p1, p2, p3);
-                    acc[mb] = mfma16(p2, vc[kk][1], acc[mb]);  // t2*mid
-                    acc[mb] = mfma16(p3, vc[kk][0], acc[mb]);  // t3*hi
-                    acc[mb] = mfma16(p1, vl, acc[mb]);         // t1*lo
-                    acc[mb] = mfma16(p2, vc[kk][0], acc[mb]);  // t2*hi
-                    acc[mb] = mfma16(p1, vc[kk][1], acc[mb]);  // t1*mid
-                    acc[mb] = mfma16(p1, vc[kk][0], acc[mb]);  // t1*hi
-                }
-            }
-            float* rd = red16[wave];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    rd[(16 * mb + 4 * (lane >> 4) + i) * RED16 + (lane & 15)] = acc[mb][i];
-        }
+        if (g.pw)
+            publish_piece(rsrc2, slot_bytes, rt_off + (unsigned)(g.ct >> 1) * TILE_BYTES + g.piece16((g.ct & 1) * 2 + (g.uq >> 1)),
+                          s, s > 0, q);
+        // ---- candidate pre-activation: q V^T
+        if (s > 0)
+            ring_product16<KGW, NW>(vc, vlo2[g.wave], rsrc2, (unsigned)(s % RING) * slot_bytes + rt_off + (unsigned)g.lane * 16u,
+                                    a.n_kg, g.wave, g.lane, &abort_flag[par], red16[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (s > 0 && pw) {
+        if (s > 0 && g.pw) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sum = red16[0][r * RED16 + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) sum = sum + red16[w][r * RED16 + uq * 4 + e];
-                rc[e] = sum;
-            }
+            for (int e = 0; e < 4; ++e) rc[e] = wave_sum(red16, g.r * RED16 + g.uq * 4 + e);
         }
         // ---- candidate and state (anns.py:591-592)
         const int t = s;
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o_out = ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc;
         f32x4 c, y, yo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -614,30 +367,18 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_fwd_kernel(LigruArgs a) {
             y[e] = z[e] * yp[e] + (1.0f - z[e]) * c[e];
             const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
             yo[e] = y[e] * k;
-            if (!valid) y[e] = 0.0f;
+            if (!g.valid) y[e] = 0.0f;
         }
         // ---- publish y_t (forward tile order, as the LiGRU)
-        if (pw) {
-            const int ksp = ct & 1, hq = uq >> 1, qq = uq & 1;
-            const unsigned piece = (unsigned)((((ksp * 2 + qq) * 64) + hq * 32 + r) * 16);
-            const unsigned tile_off = rt_off + (unsigned)(ct >> 1) * TILE_BYTES + piece;
-            if (s + 1 < T) {
-                u32x4 rawv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(y[e]);
-                __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc, (unsigned)(s % RING) * slot_bytes + tile_off, 0, AUX_SC1);
-            }
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + tile_off, 0, AUX_SC1);
-        }
-        if (valid) {
-            const size_t o_st = ((size_t)bp * T + t) * H + unit;
+        if (g.pw) publish_piece(rsrc, slot_bytes, rt_off + g.piece32(), s, s + 1 < T, y);
+        if (g.valid) {
+            const size_t o_st = ((size_t)g.bp * T + t) * H + g.unit;
             st4(a.y_state + o_st, y); st4(a.z_save + o_st, z); st4(a.r_save + o_st, rg); st4(a.c_save + o_st, c);
-            st4(a.y_out + ((size_t)b * T + tt) * HO + (size_t)d * H + unit, yo);
+            st4(a.y_out + ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.unit, yo);
         }
         yp = y;
     }
-    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
-        status_raise(a.status, SPARCH_STATUS_GRU_FWD, -1);
+    raise_if_aborted(abort_flag, a.status, SPARCH_STATUS_GRU_FWD, g.tid);
 }
 
 // backward: vpack = ligru backward layout with [Vz ; Vr] (K = 2H: producer tile kg = 32 rows x (16 dz_pre +
@@ -653,123 +394,58 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_bwd_kernel(LigruArgs a) {
     __shared__ __attribute__((aligned(16))) u32x4 vlo2[NW][KG1][64];
     __shared__ int abort_flag[2];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
-    const int ct = (int)(blockIdx.x / a.n_rt_launch);
+    const Geo g(a);
     const int T = a.T, H = a.H, HO = a.H * a.dirs;
 
-    const bool pw = tid < 128;
-    const int r = (tid & 127) >> 2, uq = tid & 3;
-    const int bp = rt * RT + r, unit = ct * UT + uq * 4;
-    const bool valid = pw && bp < a.Bp && unit < H;
-    const int bpc = min(bp, a.Bp - 1), uc = min(unit, H - 4);
-    const int d = bpc / a.B, b = bpc - d * a.B;
-
     u32x4 vb[KGW][2], vc[KG1][2];
-#pragma unroll
-    for (int kk = 0; kk < KGW; ++kk) {
-        const u32x4* src = a.vpack + (((size_t)ct * (NW * KGW) + wave + NW * kk) * 3) * 64 + lane;
-        vb[kk][0] = src[0];
-        vb[kk][1] = src[64];
-        vlo[wave][kk][lane] = src[128];
-    }
-#pragma unroll
-    for (int kk = 0; kk < KG1; ++kk) {
-        const u32x4* src = a.vpack2 + (((size_t)ct * (NW * KG1) + wave + NW * kk) * 3) * 64 + lane;
-        vc[kk][0] = src[0];
-        vc[kk][1] = src[64];
-        vlo2[wave][kk][lane] = src[128];
-    }
-    if (tid < 2) abort_flag[tid] = 0;
+    load_slice16<KGW, NW>(vb, vlo[g.wave], a.vpack, g.ct, g.wave, g.lane);
+    load_slice16<KG1, NW>(vc, vlo2[g.wave], a.vpack2, g.ct, g.wave, g.lane);
+    if (g.tid < 2) abort_flag[g.tid] = 0;
     __syncthreads();
 
     const unsigned slot_bytes = (unsigned)((size_t)a.n_rt_total * a.n_ct * TILE_BYTES);    // ring 1: one tile per producer
     const unsigned slot2_bytes = (unsigned)((size_t)a.n_rt_total * a.n_kg * TILE_BYTES);   // ring 2: two producers per tile
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, (int)(RING * slot_bytes), 0x00020000);
     __amdgpu_buffer_rsrc_t rsrc2 = __builtin_amdgcn_make_buffer_rsrc(a.ring2, 0, (int)(RING * slot2_bytes), 0x00020000);
-    const unsigned rt_off = (unsigned)((size_t)rt * a.n_ct * TILE_BYTES);
-    const unsigned rt_off2 = (unsigned)((size_t)rt * a.n_kg * TILE_BYTES);
+    const unsigned rt_off = (unsigned)((size_t)g.rt * a.n_ct * TILE_BYTES);
+    const unsigned rt_off2 = (unsigned)((size_t)g.rt * a.n_kg * TILE_BYTES);
     const bool drop = a.p_drop > 0.0f;
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
 
     f32x4 cdir = zero4;  // (dq r + dy z)_{t+1}
-    if (pw && a.s_begin > 0) cdir = ld4(a.carry + (size_t)bpc * H + uc);
-    auto load_step = [&](int s, f32x4& g, f32x4& z, f32x4& rg, f32x4& c, f32x4& ypv) {
+    if (g.pw && a.s_begin > 0) cdir = ld4(a.carry + (size_t)g.bpc * H + g.uc);
+    auto load_step = [&](int s, f32x4& gv, f32x4& z, f32x4& rg, f32x4& c, f32x4& ypv) {
         const int t = T - 1 - s;
-        const int tt = d ? (T - 1 - t) : t;
-        g = ld4(a.g_out + ((size_t)b * T + tt) * HO + (size_t)d * H + uc);
-        const size_t o_st = ((size_t)bpc * T + t) * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        gv = ld4(a.g_out + ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc);
+        const size_t o_st = ((size_t)g.bpc * T + t) * H + g.uc;
         z = ld4(a.z_save + o_st); rg = ld4(a.r_save + o_st); c = ld4(a.c_save + o_st);
         ypv = t > 0 ? ld4(a.y_state + o_st - H) : zero4;
     };
     f32x4 g_n = zero4, z_n = zero4, r_n = zero4, c_n = zero4, yp_n = zero4;
-    if (pw) load_step(a.s_begin, g_n, z_n, r_n, c_n, yp_n);
-
-    // one 16-column product over `ntiles` tiles of 32 k from ring slot `base`: partial tiles -> rdst[wave]
-    auto product16 = [&](auto& vreg, auto& vl_lds, auto ktiles, __amdgpu_buffer_rsrc_t rs, unsigned base, int ntiles,
-                         float (*rdst)[RT * RED16], int par) __attribute__((always_inline)) {
-        constexpr int KT = decltype(ktiles)::value;
-        u32x4 raw[2][2][2];  // [parity of kk][mb][half]: one tile ahead
-        auto issue = [&](int kk) { issue_tile<NW>(raw[kk & 1], rs, base, wave + NW * kk, ntiles); };
-        issue(0);
-        f32x4 acc[2] = {zero4, zero4};
-#pragma unroll
-        for (int kk = 0; kk < KT; ++kk) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (wave + NW * kk < ntiles)
-                settle_tile(raw[kk & 1], rs, base + (unsigned)(wave + NW * kk) * TILE_BYTES, &abort_flag[par]);
-            if (kk + 1 < KT) issue(kk + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 vl = vl_lds[wave][kk][lane];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                u32x4 p1, p2, p3;
-                split_pieces(raw[kk & 1][mb][0], raw[kk & 1][mb][1], p1, p2, p3);
-                acc[mb] = mfma16(p2, vreg[kk][1], acc[mb]);  // t2*mid
-                acc[mb] = mfma16(p3, vreg[kk][0], acc[mb]);  // t3*hi
-                acc[mb] = mfma16(p1, vl, acc[mb]);           // t1*lo
-                acc[mb] = mfma16(p2, vreg[kk][0], acc[mb]);  // t2*hi
-                acc[mb] = mfma16(p1, vreg[kk][1], acc[mb]);  // t1*mid
-                acc[mb] = mfma16(p1, vreg[kk][0], acc[mb]);  // t1*hi
-            }
-        }
-        float* rd = rdst[wave];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                rd[(16 * mb + 4 * (lane >> 4) + i) * RED16 + (lane & 15)] = acc[mb][i];
-    };
+    if (g.pw) load_step(a.s_begin, g_n, z_n, r_n, c_n, yp_n);
 
     for (int s = a.s_begin; s < a.s_end; ++s) {
         const f32x4 gv = g_n, zv = z_n, rv = r_n, cv = c_n, ypv = yp_n;
         const int par = s & 1;
-        if (pw && s + 1 < a.s_end) load_step(s + 1, g_n, z_n, r_n, c_n, yp_n);
+        if (g.pw && s + 1 < a.s_end) load_step(s + 1, g_n, z_n, r_n, c_n, yp_n);
         // ---- [dz_pre | dr_pre]_{t+1} [Vz ; Vr]
         float cmv[4] = {0.f, 0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
         if (s > 0)
-            product16(vb, vlo, std::integral_constant<int, KGW>{}, rsrc,
-                      (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u, a.n_ct, red, par);
+            ring_product16<KGW, NW>(vb, vlo[g.wave], rsrc, (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)g.lane * 16u,
+                                    a.n_ct, g.wave, g.lane, &abort_flag[par], red[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (s > 0 && pw) {
+        if (s > 0 && g.pw) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sum = red[0][r * RED16 + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) sum = sum + red[w][r * RED16 + uq * 4 + e];
-                cmv[e] = sum;
-            }
+            for (int e = 0; e < 4; ++e) cmv[e] = wave_sum(red, g.r * RED16 + g.uq * 4 + e);
         }
         // ---- gate gradients, first half (annstep.hip mode 4)
         const int t = T - 1 - s;
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + uc;
+        const int tt = g.d ? (T - 1 - t) : t;
+        const size_t o_out = ((size_t)g.b * T + tt) * HO + (size_t)g.d * H + g.uc;
         f32x4 dzp, dcp, cdo, ry;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -779,32 +455,20 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_bwd_kernel(LigruArgs a) {
             dcp[e] = (dy * (1.0f - zv[e])) * (1.0f - cv[e] * cv[e]);
             cdo[e] = dy * zv[e];
             ry[e] = rv[e] * ypv[e];
-            if (!valid) { dzp[e] = 0.0f; dcp[e] = 0.0f; }
+            if (!g.valid) { dzp[e] = 0.0f; dcp[e] = 0.0f; }
         }
-        // ---- publish dc_pre, then dq = dc_pre V
-        const int mbp = r >> 4, row16 = r & 15, half = uq & 1;
-        if (pw) {
-            const unsigned cpiece = (unsigned)((((mbp * 2 + half) * 64) + ((ct & 1) * 2 + (uq >> 1)) * 16 + row16) * 16);
-            const unsigned ctile = rt_off2 + (unsigned)(ct >> 1) * TILE_BYTES + cpiece;
-            u32x4 rawv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rawv[e] = __float_as_uint(dcp[e]);
-            __builtin_amdgcn_raw_buffer_store_b128(rawv, rsrc2, (unsigned)(s % RING) * slot2_bytes + ctile, 0, AUX_SC1);
-            if (s >= 2) __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc2, (unsigned)((s - 2) % RING) * slot2_bytes + ctile, 0, AUX_SC1);
-        }
-        product16(vc, vlo2, std::integral_constant<int, KG1>{}, rsrc2,
-                  (unsigned)(s % RING) * slot2_bytes + rt_off2 + (unsigned)lane * 16u, a.n_kg, red2, par);
+        // ---- publish dc_pre (read in this very step, by every step), then dq = dc_pre V
+        if (g.pw)
+            publish_piece(rsrc2, slot2_bytes, rt_off2 + (unsigned)(g.ct >> 1) * TILE_BYTES + g.piece16((g.ct & 1) * 2 + (g.uq >> 1)),
+                          s, true, dcp);
+        ring_product16<KG1, NW>(vc, vlo2[g.wave], rsrc2, (unsigned)(s % RING) * slot2_bytes + rt_off2 + (unsigned)g.lane * 16u,
+                                a.n_kg, g.wave, g.lane, &abort_flag[par], red2[g.wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
-        if (pw) {
+        if (g.pw) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sum = red2[0][r * RED16 + uq * 4 + e];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) sum = sum + red2[w][r * RED16 + uq * 4 + e];
-                dq[e] = sum;
-            }
+            for (int e = 0; e < 4; ++e) dq[e] = wave_sum(red2, g.r * RED16 + g.uq * 4 + e);
         }
         // ---- second half (annstep.hip mode 5)
         f32x4 drp;
@@ -812,37 +476,23 @@ __global__ __launch_bounds__(64 * NW, 1) void gru_bwd_kernel(LigruArgs a) {
         for (int e = 0; e < 4; ++e) {
             drp[e] = (dq[e] * ypv[e]) * (rv[e] * (1.0f - rv[e]));
             cdo[e] = cdo[e] + dq[e] * rv[e];
-            if (!valid) drp[e] = 0.0f;
+            if (!g.valid) drp[e] = 0.0f;
         }
-        // ---- publish [dz_pre | dr_pre]: two 16-byte pieces of this workgroup's tile, in A-fragment order
-        if (pw) {
-            const unsigned pz = (unsigned)((((mbp * 2 + half) * 64) + (uq >> 1) * 16 + row16) * 16);
-            const unsigned pr = (unsigned)((((mbp * 2 + half) * 64) + (2 + (uq >> 1)) * 16 + row16) * 16);
-            const unsigned tile_off = rt_off + (unsigned)ct * TILE_BYTES;
-            if (s + 1 < T) {
-                u32x4 wz, wr;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { wz[e] = __float_as_uint(dzp[e]); wr[e] = __float_as_uint(drp[e]); }
-                const unsigned so = (unsigned)(s % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(wz, rsrc, so + pz, 0, AUX_SC1);
-                __builtin_amdgcn_raw_buffer_store_b128(wr, rsrc, so + pr, 0, AUX_SC1);
-            }
-            if (s >= 2) {
-                const unsigned so = (unsigned)((s - 2) % RING) * slot_bytes + tile_off;
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pz, 0, AUX_SC1);
-                __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, so + pr, 0, AUX_SC1);
-            }
+        // ---- publish [dz_pre | dr_pre]: two 16-byte pieces of this workgroup's tile
+        if (g.pw) {
+            const unsigned tile_off = rt_off + (unsigned)g.ct * TILE_BYTES;
+            publish_piece(rsrc, slot_bytes, tile_off + g.piece16(g.uq >> 1), s, s + 1 < T, dzp);
+            publish_piece(rsrc, slot_bytes, tile_off + g.piece16(2 + (g.uq >> 1)), s, s + 1 < T, drp);
         }
-        if (valid) {
-            const size_t o_or = ((size_t)bp * T + tt) * H + unit;
+        if (g.valid) {
+            const size_t o_or = ((size_t)g.bp * T + tt) * H + g.unit;
             st4(a.dz_all + o_or, dzp); st4(a.dr_all + o_or, drp); st4(a.dc_all + o_or, dcp);
             st4(a.yprev_all + o_or, ypv); st4(a.ry_all + o_or, ry);
         }
         cdir = cdo;
     }
-    if (valid) st4(a.carry + (size_t)bp * H + unit, cdir);
-    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
-        status_raise(a.status, SPARCH_STATUS_GRU_BWD, -1);
+    if (g.valid) st4(a.carry + (size_t)g.bp * H + g.unit, cdir);
+    raise_if_aborted(abort_flag, a.status, SPARCH_STATUS_GRU_BWD, g.tid);
 }
 
 // fragments of ONE matrix for a 16-column product on the 16x16x32 MFMA: column lane & 15 = unit ct*16 + (lane & 15),

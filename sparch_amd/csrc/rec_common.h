@@ -1,5 +1,6 @@
 // Shared device helpers of the persistent recurrent kernels (reccell.hip, gatedcell.hip): types, the hand-off
-// ring constants, bare LDS barriers, exact-split MFMA wrapper, tile issue / settle of the sentinel protocol.
+// ring constants, bare LDS barriers, exact-split MFMA wrappers, and the sentinel ring's machinery — tile issue /
+// settle, the truncation split, the six-term ring product, the cross-wave sum, the publish, the abort epilogue.
 // At the end, the host side the two files share: kernel-table rows, launch and clear helpers, the entry points'
 // argument checks.  The launch policy is rec_plan.h.  See the header comment of reccell.hip for the design.
 #pragma once
@@ -20,9 +21,10 @@ typedef __attribute__((address_space(1))) unsigned gu32;
 constexpr int RT = 32;       // rows per batch tile
 constexpr int CT = 32;       // columns per workgroup (= one k-group of its consumers)
 constexpr int RED_LD = 33;   // padded row of the cross-wave reduction tiles (read with 4-byte accesses)
+constexpr int RED16 = 17;    // ... of the 16-column products' tiles
 constexpr int RED_LD4 = 32;  // ... of the spiking cells' tiles, read with one 16-byte access per partial tile
 constexpr int RING = 4;      // depth of the backward hand-off ring (2 suffices, see header)
-constexpr int TILE_BYTES = RT * CT * 4;  // one fp32 hand-off tile
+constexpr int TILE_BYTES = RT * CT * 4;  // one fp32 hand-off tile (= ptile_bytes<2>(), see issue_ptile)
 // Cache-policy operand of the hand-off buffer accesses: sc1.  Every hand-off load and store is agent scope / sc1,
 // the only combination that is correct for any placement of the workgroups (a narrower scope stays in an XCD's L2,
 // invisible to the other XCDs; plain stores are used only where xcd_agree has VERIFIED a shared XCD, see below).
@@ -144,6 +146,11 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
                                                    c, 0, 0, 0);
 }
+// v_mfma_f32_16x16x32_bf16: A fragment = lane (row lane & 15, k-quarter lane >> 4) holds k = 8*(lane>>4) .. +7;
+// B fragment = lane (column lane & 15, same k-quarter); C = 4 rows (4*(lane>>4) .. +3) of column lane & 15.
+__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
 
 // exact 3-way bf16 split of an fp32 value: x == hi + mid + lo (round-to-nearest-even at each step)
 __device__ __forceinline__ void split3(float x, unsigned short& hi, unsigned short& mid, unsigned short& lo) {
@@ -182,72 +189,8 @@ __device__ __forceinline__ void load_vslice(u32x4 (&vb)[KGW][2][NP], const u32x4
 }
 
 
-// Load this wave's k-groups of a row tile's fp32 hand-off tiles (fragment order) from ring slot `base`,
-// re-loading every 16-byte piece that still holds the sentinel until all have landed (bounded spin).
-// lane (row li, k-half hh) of k16-step ks needs k = 16*ks + 8*hh + 4q + 0..3 of producer tile kg:
-// piece (ks*2+q)*64 + lane of that tile -> each wave-load is 1 KiB contiguous.
+// A 16-byte piece of a hand-off tile that still holds the sentinel has not been written yet.
 __device__ __forceinline__ bool piece_missing(const u32x4& v) { return v[0] == SENTINEL || v[3] == SENTINEL; }
-
-// issue the four 1 KiB wave-loads of ONE k-group
-template <int NW>
-__device__ __forceinline__ void issue_tile(u32x4 (&g)[2][2], __amdgpu_buffer_rsrc_t rsrc, unsigned base, int kg,
-                                           int n_ct) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            // padding k-groups (beyond H) read past the end of the buffer resource: the hardware returns
-            // zeros for out-of-range buffer loads — no branch, and zeros are never "missing"
-            const unsigned off = kg < n_ct ? base + (unsigned)kg * TILE_BYTES + (unsigned)((ks * 2 + q) * 1024)
-                                           : 0xFFFFFF00u;
-            g[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, AUX_SC1);
-        }
-}
-
-// the four pieces of ONE k-group: wait for them (the others stay in flight), re-load what still reads as the
-// sentinel until it has landed (bounded spin).  Fast path: four compares and one wave-uniform branch.
-__device__ __forceinline__ void settle_tile(u32x4 (&g)[2][2], __amdgpu_buffer_rsrc_t rsrc, unsigned tile_base,
-                                            int* abort_slot) {
-    unsigned miss = 0;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) miss |= piece_missing(g[ks][q]) ? (1u << (ks * 2 + q)) : 0u;
-    if (__any(miss != 0)) {
-        // slow path.  Re-loads go to temporaries and are waited for right here (builtin wait: the compiler's
-        // scoreboard stays exact), then merged by select: the pending loads of the later k-groups are not
-        // touched, so the fast path keeps its precise vmcnt(N) waits after the join.
-        const u64 t_start = __builtin_amdgcn_s_memrealtime();
-        for (unsigned spins = 0;; ++spins) {
-            __builtin_amdgcn_s_sleep(1);
-            u32x4 tmp[2][2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    tmp[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tile_base + (unsigned)((ks * 2 + q) * 1024),
-                                                                      0, AUX_SC1);
-            vm_settled();
-            unsigned still = 0;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const unsigned bit = 1u << (ks * 2 + q);
-                    const bool m = (miss & bit) != 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) g[ks][q][e] = m ? tmp[ks][q][e] : g[ks][q][e];
-                    if (m && piece_missing(tmp[ks][q])) still |= bit;
-                }
-            miss = still;
-            if (!__any(miss != 0)) break;
-            if ((spins & 63u) == 63u && __builtin_amdgcn_s_memrealtime() - t_start > TIMEOUT_TICKS) {
-                lds_flag_set(abort_slot);  // the status word is raised at the kernel's exit
-                break;
-            }
-        }
-    }
-}
 
 // ---- hand-off tiles as PRE-SPLIT bf16 planes (round 2, with the XCD-local stores).  The producer
 // splits its dWx values once (x = t1 + t2 + t3, truncation split) and publishes the three planes; a consumer
@@ -261,6 +204,18 @@ __device__ __forceinline__ void settle_tile(u32x4 (&g)[2][2], __amdgpu_buffer_rs
 // NP planes per tile: 3 = the exact split, 1 = the bf16 operand mode (one nearest-even rounding by the producer,
 // 2 KB per tile; the same layout with NP in place of 3).  A rounded plane word cannot equal the sentinel either:
 // v_cvt_pk_bf16_f32 quiets every NaN it converts.
+// A dense fp32 tile (the gated kernels' rings, 4 KB) is, as far as LOADING goes, a tile of NP = 2 "planes": lane
+// (row li, k-half hh) of k16-step ks needs k = 16*ks + 8*hh + 4q + 0..3, which its producers store as piece
+// (ks*2 + q)*64 + lane — the same four contiguous 1 KiB wave-loads, the same sentinel check per piece; the consumer
+// splits the two pieces of a k16-step into the three fragments (split_pieces).
+// issue_ptile: the 2 NP wave-loads of ONE k-group.  Padding k-groups (beyond n_ct) read past the end of the buffer
+// resource: the hardware returns zeros for out-of-range buffer loads — no branch, and zeros are never "missing".
+// settle_ptile: wait for the pieces of ONE k-group (the others stay in flight) and re-load what still reads as the
+// sentinel until it has landed (bounded spin; on a timeout the abort flag is set and the status word is raised at the
+// kernel's exit).  Fast path: 2 NP compares and one wave-uniform branch.  Slow path: re-loads go to temporaries and
+// are waited for right there (builtin wait: the compiler's scoreboard stays exact), then merged by select — the
+// pending loads of the later k-groups are not touched, so the fast path keeps its precise vmcnt(N) waits after the
+// join.
 constexpr int PTILE_BYTES = RT * CT * 6;  // what the host sizes the ring for (three planes)
 template <int NP> constexpr int ptile_bytes() { return RT * CT * 2 * NP; }
 template <int NW, int NP = 3>
@@ -280,7 +235,7 @@ __device__ __forceinline__ void settle_ptile(u32x4 (&g)[2][NP], __amdgpu_buffer_
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int p = 0; p < NP; ++p) miss |= piece_missing(g[ks][p]) ? (1u << (ks * NP + p)) : 0u;
-    if (__any(miss != 0)) {  // slow path as settle_tile: temporaries, builtin wait, merge by select
+    if (__any(miss != 0)) {  // slow path: temporaries, builtin wait, merge by select
         const u64 t_start = __builtin_amdgcn_s_memrealtime();
         for (unsigned spins = 0;; ++spins) {
             __builtin_amdgcn_s_sleep(1);
@@ -312,19 +267,36 @@ __device__ __forceinline__ void settle_ptile(u32x4 (&g)[2][NP], __amdgpu_buffer_
     }
 }
 
-// exact truncation split of a thread's 4 fp32 values into three words-pairs of bf16 (plane p: w[p] = 4 bf16)
+// THE exact truncation split, two values at a time: x = t1 + t2 + t3 with t1 the upper half of x, t2 the upper half of
+// the residual, t3 of what remains; w[0..2] = the bf16 pairs t1, t2, t3 (x1's in the upper half).  v_perm for the
+// packing, AND + SUB for the residuals: ~5.5 VALU instructions per value.
+struct SplitPair { unsigned w[3]; };
+__device__ __forceinline__ SplitPair split_pair(unsigned x0, unsigned x1) {
+    const float r0 = __uint_as_float(x0) - __uint_as_float(x0 & 0xFFFF0000u);
+    const float r1 = __uint_as_float(x1) - __uint_as_float(x1 & 0xFFFF0000u);
+    const unsigned y0 = __float_as_uint(r0), y1 = __float_as_uint(r1);
+    const float q0 = r0 - __uint_as_float(y0 & 0xFFFF0000u);
+    const float q1 = r1 - __uint_as_float(y1 & 0xFFFF0000u);
+    return {{__builtin_amdgcn_perm(x1, x0, 0x07060302u), __builtin_amdgcn_perm(y1, y0, 0x07060302u),
+             __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u)}};
+}
+// consumer side: 8 fp32 values (the two 16-byte pieces of a fragment's k range) -> the three bf16 fragments
+__device__ __forceinline__ void split_pieces(const u32x4& lo4, const u32x4& hi4, u32x4& p1, u32x4& p2, u32x4& p3) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+            const SplitPair t = split_pair((q ? hi4 : lo4)[2 * pr], (q ? hi4 : lo4)[2 * pr + 1]);
+            p1[2 * q + pr] = t.w[0]; p2[2 * q + pr] = t.w[1]; p3[2 * q + pr] = t.w[2];
+        }
+}
+// producer side: a thread's 4 fp32 values -> one word pair (4 bf16) per plane
 __device__ __forceinline__ void split4_planes(const f32x4& v, u32x2 (&w)[3]) {
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
-        const unsigned x0 = __float_as_uint(v[2 * pr]), x1 = __float_as_uint(v[2 * pr + 1]);
-        const float r0 = v[2 * pr] - __uint_as_float(x0 & 0xFFFF0000u);
-        const float r1 = v[2 * pr + 1] - __uint_as_float(x1 & 0xFFFF0000u);
-        const unsigned y0 = __float_as_uint(r0), y1 = __float_as_uint(r1);
-        const float q0 = r0 - __uint_as_float(y0 & 0xFFFF0000u);
-        const float q1 = r1 - __uint_as_float(y1 & 0xFFFF0000u);
-        w[0][pr] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);
-        w[1][pr] = __builtin_amdgcn_perm(y1, y0, 0x07060302u);
-        w[2][pr] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
+        const SplitPair t = split_pair(__float_as_uint(v[2 * pr]), __float_as_uint(v[2 * pr + 1]));
+#pragma unroll
+        for (int p = 0; p < 3; ++p) w[p][pr] = t.w[p];
     }
 }
 // one plane-tile half piece per plane (8 bytes each, 1 KiB apart) at byte offset `off`; `plain`: XCD-local stores
@@ -336,26 +308,158 @@ __device__ __forceinline__ void store_planes(const u32x2 (&w)[3], __amdgpu_buffe
     }
 }
 
-// exact truncation split of one k-group's tile (2 k16-steps x 8 fp32 values per lane) into the three bf16
-// fragments per k16-step: P[ks][0..2] = t1, t2, t3 with x = t1 + t2 + t3 (v_perm for the packing, AND + SUB for
-// the residuals: ~5.5 VALU instructions per value)
-__device__ __forceinline__ void split_tile(const u32x4 (&g)[2][2], u32x4 (&P)[2][3]) {
+// ---- the ring product: one step's recurrent product of a workgroup, written once.
+// The six cross terms of (t1 + t2 + t3) x (hi + mid + lo) that matter, smallest first.  THIS ORDER IS PART OF THE
+// RESULT'S BITS (tests/golden/baseline_rec_bits.json).  MFMA: mfma_bf16 (32x32x16, f32x16) or mfma16 (16x16x32, f32x4).
+template <auto MFMA, class Acc>
+__device__ __forceinline__ Acc six_terms(const u32x4& p1, const u32x4& p2, const u32x4& p3, const u32x4& hi,
+                                         const u32x4& mid, const u32x4& lo, Acc acc) {
+    acc = MFMA(p2, mid, acc);  // t2*mid
+    acc = MFMA(p3, hi, acc);   // t3*hi
+    acc = MFMA(p1, lo, acc);   // t1*lo
+    acc = MFMA(p2, hi, acc);   // t2*hi
+    acc = MFMA(p1, mid, acc);  // t1*mid
+    acc = MFMA(p1, hi, acc);   // t1*hi
+    return acc;
+}
+
+// This wave's KGW tiles (k-groups wave, wave + NW, ...) of a row tile, from the ring slot at `base` (slot + row tile +
+// lane * 16), handed to body(kk, tile) one after the other with the next tile's loads in flight (TILES_AHEAD; more
+// loses, see rec_bwd_kernel).  The sched_barrier pair keeps hipcc from moving the issue above the settle's wait or the
+// MFMAs into the pair.  Everything is unrolled: kk is a constant where body indexes registers with it.
+template <int KGW, int NW, int NP, class Body>
+__device__ __forceinline__ void ring_tiles(__amdgpu_buffer_rsrc_t rsrc, unsigned base, int ntiles, int wave,
+                                           int* abort_slot, Body&& body) {
+    constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;
+    u32x4 raw[KGW][2][NP];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int kk = 0; kk < AHEAD; ++kk) issue_ptile<NW, NP>(raw[kk], rsrc, base, wave + NW * kk, ntiles);
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
+    for (int kk = 0; kk < KGW; ++kk) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (wave + NW * kk < ntiles)
+            settle_ptile<NP>(raw[kk], rsrc, base + (unsigned)(wave + NW * kk) * ptile_bytes<NP>(), abort_slot);
+        if (kk + AHEAD < KGW) issue_ptile<NW, NP>(raw[kk + AHEAD], rsrc, base, wave + NW * (kk + AHEAD), ntiles);
+        __builtin_amdgcn_sched_barrier(0);
+        body(kk, raw[kk]);
+    }
+}
+
+// 32 columns (32x32x16 MFMA): a tile is two k16-steps of one 32 x 32 product.  vb[kk][ks] = hi, mid fragments of the
+// slice, vlo_w[kk][ks][lane] = its lo fragment (LDS); NP = 3: the tile arrives as planes, NP = 2: as fp32 to split.
+// The wave's partial tile goes to red_w (RT x RED_LD).
+template <int KGW, int NW, int NP>
+__device__ __forceinline__ void ring_product32(const u32x4 (&vb)[KGW][2][2], const u32x4 (&vlo_w)[KGW][2][64],
+                                               __amdgpu_buffer_rsrc_t rsrc, unsigned base, int ntiles, int wave, int lane,
+                                               int* abort_slot, float* red_w) {
+    f32x16 acc;
 #pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const unsigned x0 = g[ks][q][2 * pr], x1 = g[ks][q][2 * pr + 1];
-                const float r0 = __uint_as_float(x0) - __uint_as_float(x0 & 0xFFFF0000u);
-                const float r1 = __uint_as_float(x1) - __uint_as_float(x1 & 0xFFFF0000u);
-                const unsigned y0 = __float_as_uint(r0), y1 = __float_as_uint(r1);
-                const float q0 = r0 - __uint_as_float(y0 & 0xFFFF0000u);
-                const float q1 = r1 - __uint_as_float(y1 & 0xFFFF0000u);
-                P[ks][0][2 * q + pr] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);
-                P[ks][1][2 * q + pr] = __builtin_amdgcn_perm(y1, y0, 0x07060302u);
-                P[ks][2][2 * q + pr] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-            }
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    ring_tiles<KGW, NW, NP>(rsrc, base, ntiles, wave, abort_slot, [&](int kk, const u32x4 (&g)[2][NP]) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            u32x4 p1, p2, p3;
+            if constexpr (NP == 3) { p1 = g[ks][0]; p2 = g[ks][1]; p3 = g[ks][2]; }
+            else split_pieces(g[ks][0], g[ks][1], p1, p2, p3);
+            acc = six_terms<mfma_bf16>(p1, p2, p3, vb[kk][ks][0], vb[kk][ks][1], vlo_w[kk][ks][lane], acc);
+        }
+    });
+    const int li = lane & 31, hh = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
+        red_w[row * RED_LD + li] = acc[i];
+    }
+}
+
+// 16 columns (16x16x32 MFMA, nothing of the matrix pipe spent on padding columns): a tile is one 32-deep k step of
+// two 16-row blocks, fp32, pieces ((mb*2 + half)*64 + lane) — the ptile offsets with (mb, half) for (ks, q).
+// vb[kk] = hi, mid, vlo_w[kk][lane] = lo.  The wave's two partial 16 x 16 tiles go to red_w (RT x RED16).
+template <int KGW, int NW>
+__device__ __forceinline__ void ring_product16(const u32x4 (&vb)[KGW][2], const u32x4 (&vlo_w)[KGW][64],
+                                               __amdgpu_buffer_rsrc_t rsrc, unsigned base, int ntiles, int wave, int lane,
+                                               int* abort_slot, float* red_w) {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2] = {zero4, zero4};
+    ring_tiles<KGW, NW, 2>(rsrc, base, ntiles, wave, abort_slot, [&](int kk, const u32x4 (&g)[2][2]) {
+        const u32x4 vl = vlo_w[kk][lane];
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            u32x4 p1, p2, p3;
+            split_pieces(g[mb][0], g[mb][1], p1, p2, p3);
+            acc[mb] = six_terms<mfma16>(p1, p2, p3, vb[kk][0], vb[kk][1], vl, acc[mb]);
+        }
+    });
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red_w[(16 * mb + 4 * (lane >> 4) + i) * RED16 + (lane & 15)] = acc[mb][i];
+}
+
+// the resident slice of a ring product: hi and mid fragments in registers, lo in LDS (vlo_w = this wave's part)
+template <int KGW, int NW>
+__device__ __forceinline__ void load_slice32(u32x4 (&vb)[KGW][2][2], u32x4 (&vlo_w)[KGW][2][64], const u32x4* vpack,
+                                             int ct, int nkg, int wave, int lane) {
+#pragma unroll
+    for (int kk = 0; kk < KGW; ++kk)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const u32x4* src = vpack + ((((size_t)ct * nkg + wave + NW * kk) * 2 + ks) * 3) * 64 + lane;
+            vb[kk][ks][0] = src[0];
+            vb[kk][ks][1] = src[64];
+            vlo_w[kk][ks][lane] = src[128];
+        }
+}
+template <int KGW, int NW>
+__device__ __forceinline__ void load_slice16(u32x4 (&vb)[KGW][2], u32x4 (&vlo_w)[KGW][64], const u32x4* vpack, int ct,
+                                             int wave, int lane) {
+#pragma unroll
+    for (int kk = 0; kk < KGW; ++kk) {
+        const u32x4* src = vpack + (((size_t)ct * (NW * KGW) + wave + NW * kk) * 3) * 64 + lane;
+        vb[kk][0] = src[0];
+        vb[kk][1] = src[64];
+        vlo_w[kk][lane] = src[128];
+    }
+}
+
+// element o of the product: the waves' partial tiles summed in wave order 0 .. NW-1 (part of the result's bits)
+template <int NW, int N>
+__device__ __forceinline__ float wave_sum(const float (&red)[NW][N], int o) {
+    float sum = red[0][o];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) sum = sum + red[w][o];
+    return sum;
+}
+
+// Publish a thread's part of step s at byte offset `off` of a ring slot (row tile + tile + piece): the data into slot
+// s % RING where someone will read it (`live`), and the sentinel back into the slot of step s-2 — every peer has
+// consumed that one: they have all published step s-1 since.  Write-through (sc1) stores.
+__device__ __forceinline__ void publish_piece(__amdgpu_buffer_rsrc_t rsrc, unsigned slot_bytes, unsigned off, int s,
+                                              bool live, const f32x4& v) {
+    if (live)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (unsigned)(s % RING) * slot_bytes + off, 0, AUX_SC1);
+    if (s >= 2) {
+        const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
+        __builtin_amdgcn_raw_buffer_store_b128(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + off, 0, AUX_SC1);
+    }
+}
+// ... of a plane tile: the 4 values split here, once, for all consumers; `plain`: XCD-local stores
+__device__ __forceinline__ void publish_planes(__amdgpu_buffer_rsrc_t rsrc, unsigned slot_bytes, unsigned off, int s,
+                                               bool live, const f32x4& v, bool plain) {
+    if (live) {
+        u32x2 w[3];
+        split4_planes(v, w);
+        store_planes(w, rsrc, (unsigned)(s % RING) * slot_bytes + off, plain);
+    }
+    if (s >= 2) {
+        const u32x2 sent[3] = {{SENTINEL, SENTINEL}, {SENTINEL, SENTINEL}, {SENTINEL, SENTINEL}};
+        store_planes(sent, rsrc, (unsigned)((s - 2) % RING) * slot_bytes + off, plain);
+    }
+}
+
+// the end of a ring kernel: a settle that timed out (either parity) raises the device's status word
+__device__ __forceinline__ void raise_if_aborted(const int (&abort_flag)[2], unsigned* status, unsigned kernel_id, int tid) {
+    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1]))) status_raise(status, kernel_id, -1);
 }
 
 // ---- XCD-local hand-off stores (speed option, VERIFIED at run time).

@@ -1032,7 +1032,6 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, hh = lane >> 5;
     const int rt = a.rt_base + (int)(blockIdx.x % a.n_rt_launch);
     const int ct = (int)(blockIdx.x / a.n_rt_launch);
     const int T = a.T, H = a.H, HO = a.H * a.dirs;
@@ -1045,17 +1044,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
     const int d = bpc / a.B, b = bpc - d * a.B;
 
     u32x4 vb[KGW][2][2];
-#pragma unroll
-    for (int kk = 0; kk < (EXT ? 0 : KGW); ++kk) {
-        const int kg = wave + NW * kk;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const u32x4* src = a.vpack + ((((size_t)ct * a.nkg + kg) * 2 + ks) * 3) * 64 + lane;
-            vb[kk][ks][0] = src[0];
-            vb[kk][ks][1] = src[64];
-            vlo[wave][kk][ks][lane] = src[128];
-        }
-    }
+    if (!EXT) load_slice32<KGW, NW>(vb, vlo[wave], a.vpack, ct, a.nkg, wave, lane);
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
     if (!BWD && a.scale) { sc = ld4(a.scale + colc); sh = ld4(a.shift + colc); }
     if (tid < 2) abort_flag[tid] = 0;
@@ -1094,41 +1083,9 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
         const int par = s & 1;
         if (pw && s + 1 < a.s_end) load_step(s + 1, n0, n1, n2);
 
-        if (s > 0 && !EXT) {
-            const unsigned slot = (unsigned)((s - 1) % RING);
-            const unsigned base = slot * slot_bytes + rt_off + (unsigned)lane * 16u;
-            constexpr int AHEAD = KGW < TILES_AHEAD ? KGW : TILES_AHEAD;  // see rec_bwd_kernel
-            u32x4 raw[KGW][2][3];  // [k-group][k16-step][plane]
-#pragma unroll
-            for (int kk = 0; kk < AHEAD; ++kk) issue_ptile<NW>(raw[kk], rsrc, base, wave + NW * kk, a.n_ct);
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KGW; ++kk) {
-                __builtin_amdgcn_sched_barrier(0);
-                settle_ptile(raw[kk], rsrc, base + (unsigned)(wave + NW * kk) * PTILE_BYTES, &abort_flag[par]);
-                if (kk + AHEAD < KGW) issue_ptile<NW>(raw[kk + AHEAD], rsrc, base, wave + NW * (kk + AHEAD), a.n_ct);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const u32x4 p1 = raw[kk][ks][0], p2 = raw[kk][ks][1], p3 = raw[kk][ks][2];
-                    const u32x4 vl = vlo[wave][kk][ks][lane];
-                    acc = mfma_bf16(p2, vb[kk][ks][1], acc);  // t2*mid
-                    acc = mfma_bf16(p3, vb[kk][ks][0], acc);  // t3*hi
-                    acc = mfma_bf16(p1, vl, acc);             // t1*lo
-                    acc = mfma_bf16(p2, vb[kk][ks][0], acc);  // t2*hi
-                    acc = mfma_bf16(p1, vb[kk][ks][1], acc);  // t1*mid
-                    acc = mfma_bf16(p1, vb[kk][ks][0], acc);  // t1*hi
-                }
-            }
-            float* rd = red[par][wave];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
-                rd[row * RED_LD + li] = acc[i];
-            }
-        }
+        if (s > 0 && !EXT)
+            ring_product32<KGW, NW, 3>(vb, vlo[wave], rsrc, (unsigned)((s - 1) % RING) * slot_bytes + rt_off + (unsigned)lane * 16u,
+                                       a.n_ct, wave, lane, &abort_flag[par], red[par][wave]);
         lds_barrier();
         vm_settled();
         if (lds_flag_read(&abort_flag[par])) break;
@@ -1137,13 +1094,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
             rec[0] = v.x; rec[1] = v.y; rec[2] = v.z; rec[3] = v.w;
         } else if (s > 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = r * RED_LD + cq * 4 + e;
-                float sum = red[par][0][o];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) sum = sum + red[par][w][o];
-                rec[e] = sum;
-            }
+            for (int e = 0; e < 4; ++e) rec[e] = wave_sum(red[par], r * RED_LD + cq * 4 + e);
         }
 
         // ---- pointwise rule
@@ -1166,43 +1117,13 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
                 aux[e] = c2[e];
             }
         }
-        // ---- publish this step's tile (fragment order, write-through); put the sentinel back into the slot
-        //      of step s-2 (every peer has consumed it: they have all published step s-1 since)
+        // ---- publish this step's tile as planes (fragment order; the last step's has no reader): a thread's 4
+        //      columns are half a 16-byte piece per plane
         if (EXT) {
             if (valid) st4(a.step_out + (size_t)bp * H + col, val);
         } else if (pw) {
             const unsigned piece = (unsigned)(((cq >> 2) * 3 * 64 + ((cq >> 1) & 1) * 32 + r) * 16 + (cq & 1) * 8);
-            const unsigned tile_off = rt_off + (unsigned)ct * PTILE_BYTES + piece;
-            if (s + 1 < T) {
-                u32x2 w[3];
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    const unsigned x0 = __float_as_uint(val[2 * pr]), x1 = __float_as_uint(val[2 * pr + 1]);
-                    const float r0 = val[2 * pr] - __uint_as_float(x0 & 0xFFFF0000u);
-                    const float r1 = val[2 * pr + 1] - __uint_as_float(x1 & 0xFFFF0000u);
-                    const unsigned y0 = __float_as_uint(r0), y1 = __float_as_uint(r1);
-                    const float q0 = r0 - __uint_as_float(y0 & 0xFFFF0000u);
-                    const float q1 = r1 - __uint_as_float(y1 & 0xFFFF0000u);
-                    w[0][pr] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);
-                    w[1][pr] = __builtin_amdgcn_perm(y1, y0, 0x07060302u);
-                    w[2][pr] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-                }
-                const unsigned so = (unsigned)(s % RING) * slot_bytes + tile_off;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(w[p], rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
-                }
-            }
-            if (s >= 2) {
-                const u32x2 sent = {SENTINEL, SENTINEL};
-                const unsigned so = (unsigned)((s - 2) % RING) * slot_bytes + tile_off;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, AUX_SC1);
-                }
-            }
+            publish_planes(rsrc, slot_bytes, rt_off + (unsigned)ct * PTILE_BYTES + piece, s, s + 1 < T, val, xcd_local);
         }
         lds_barrier();
         // ---- off the critical path: outputs
@@ -1216,8 +1137,7 @@ __global__ __launch_bounds__(64 * NW, 1) void ann_rec_kernel(AnnArgs a) {
             }
         }
     }
-    if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))
-        status_raise(a.status, BWD ? SPARCH_STATUS_ANN_REC_BWD : SPARCH_STATUS_ANN_REC_FWD, -1);
+    raise_if_aborted(abort_flag, a.status, BWD ? SPARCH_STATUS_ANN_REC_BWD : SPARCH_STATUS_ANN_REC_FWD, tid);
 }
 
 // ------------------------------------------------------------------------------ V prepack

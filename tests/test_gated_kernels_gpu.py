@@ -16,6 +16,9 @@ oracle and to torch autograd by tests/test_gated_numpy_host.py):
                                 inside a row tile; a full machine of co-resident RNN workgroups; H = 512 with 9 row
                                 tiles.  The batch sizes follow from sparch_device_cus()
   c  error codes                refused on the host, nothing launched or written
+  d  the same bits              SHA-256 of every output of the whole-sequence persistent launches against
+                                tests/golden/baseline_rec_bits.json: what the fp64 bounds cannot see (a reordered MFMA
+                                term, another reduction order) changes a hash
 
 Inputs: standard-normal projections and upstream gradients, scale in [0.7, 1.3], shift in [-0.2, 0.2], recurrent
 matrices of standard deviation 0.5 / sqrt(H).  The backward kernels get the fp64 reference's saves rounded to fp32 (not
@@ -35,6 +38,9 @@ Every shape and pointer a kernel receives is valid.
 """
 import ctypes
 import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -518,3 +524,64 @@ def test_error_codes_are_refused_before_any_launch():
     worst = {}                                                         # ... and the same buffers are taken when valid
     check_fwd(rnn, rnn_fwd(rnn, 2), "persistent", worst)
     check_bwd(rnn, rnn_bwd(rnn, 2), "persistent", worst)
+
+
+# ====================================================================================================== d. the same bits
+BITS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "baseline_rec_bits.json")
+BITS_B, BITS_T = 33, 6
+BITS_H = {96: (2, 0.25), 256: (1, 0.0), 512: (1, 0.0), 1024: (2, 0.25)}        # H -> (dirs, p_drop)
+
+
+def sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def baseline_bits(cell, kind, H):
+    """{"inputs": hash of everything the kernels are given, "fwd.<output>" / "bwd.<output>": hash of that tensor}."""
+    dirs, p = BITS_H[H]
+    c = case(cell, kind, BITS_B, BITS_T, H, dirs, p)
+    bits = {"inputs": sha(*[a for m in sorted(c.X) for a in c.X[m]], *[c.V[m] for m in sorted(c.V)], c.g_out,
+                          *[c.saves[k] for k in SAVES[cell]])}
+    for name, got in (("fwd", fwd_whole(c, c.T)), ("bwd", bwd_whole(c, c.T))):
+        bits.update({f"{name}.{k}": sha(a) for k, a in got.items()})
+    return bits
+
+
+@functools.lru_cache(maxsize=1)
+def recorded_bits():
+    with open(BITS_FILE) as f:
+        return json.load(f)["bits"]
+
+
+@pytest.mark.parametrize("H", sorted(BITS_H))
+@pytest.mark.parametrize("cell,kind", CELLS, ids=CELL_IDS)
+def test_whole_launch_outputs_have_the_recorded_bits(cell, kind, H):
+    """Forward and backward, one persistent launch over the whole sequence, B = 33 (two row tiles, the second ragged),
+    T = 6 (with a ring of 4 slots, slot 0 is reused and the sentinel is put back twice); two directions and p_drop 0.25
+    at H = 96 and 1024, one direction without dropout at 256 and 512.  The four H select every instantiation: the gated
+    forward with 1, 1, 2, 4 k-groups per wave, the gated backward with 1, 2, 4, 8, the RNN with 4 waves x 1, then
+    8 waves x 1, 2, 4.  The kernels fix their reduction order (MFMA terms, k-groups of a wave, waves 0 .. NW-1), the
+    dropout mask is a hash of the element index and the inputs come from numpy, so the outputs are reproducible to
+    the bit; the fp64 tests above have tolerances and would pass a reordered sum.
+
+    The file was recorded with the build of the commit BEFORE the kernels were rewritten on shared ring helpers, never
+    from the code under test.  Re-record it (python -m tests.test_gated_kernels_gpu > the file, on the last commit
+    whose bits are trusted) only for a new toolchain or a deliberate change of arithmetic, such as fp16 planes, and
+    say which in the commit message.  A differing "inputs" hash means that the host-side numpy inputs moved, not a
+    kernel."""
+    want = recorded_bits()[f"{CELL_IDS[CELLS.index((cell, kind))]}-H{H}"]
+    got = baseline_bits(cell, kind, H)
+    assert got["inputs"] == want["inputs"], "the numpy inputs differ from the recorded ones (not a kernel's doing)"
+    assert sorted(got) == sorted(want)
+    differ = [k for k in sorted(got) if got[k] != want[k]]
+    assert not differ, f"{cell} {kind or ''} H {H}: other bits than recorded in {differ}"
+
+
+if __name__ == "__main__":
+    print(json.dumps({"recorded_with": {"torch": torch.__version__, "hip": torch.version.hip, "numpy": np.__version__,
+                                        "device": torch.cuda.get_device_name(0)},
+                      "bits": {f"{i}-H{H}": baseline_bits(cell, kind, H) for (cell, kind), i in zip(CELLS, CELL_IDS)
+                               for H in sorted(BITS_H)}}, indent=1, sort_keys=True))

@@ -13,7 +13,7 @@ out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = {}
 rows = []
 for line in out.splitlines():
-    m = re.search(r"remark: +([A-Za-z ]+?)(?: \[bytes/\w+\])?: (.+?) \[-Rpass", line)
+    m = re.search(r"remark: +([A-Za-z ]+?)(?: \[\w+/\w+\])?: (.+?) \[-Rpass", line)
     if not m:
         continue
     k, v = m.group(1).strip(), m.group(2).strip()
@@ -27,5 +27,5 @@ for r in rows:
     name = re.sub(r"\(anonymous namespace\)::", "", name).split("(")[0]
     if flt and flt not in name:
         continue
-    print(f"{name:48s} vgpr {r.get('VGPRs', '?'):>4} agpr {r.get('AGPRs', '?'):>3} sgpr {r.get('SGPRs', '?'):>3} "
+    print(f"{name:48s} vgpr {r.get('VGPRs', '?'):>4} agpr {r.get('AGPRs', '?'):>3} sgpr {r.get('TotalSGPRs', r.get('SGPRs', '?')):>3} "
           f"scratch {r.get('ScratchSize', '?'):>4} lds {r.get('LDS Size', '?'):>6} occ {r.get('Occupancy', '?')}")
