@@ -475,6 +475,28 @@ int sparch_stream_step_fwd(int kind, int B, int K, int H, int ld, int in_dtype, 
 int sparch_stream_step_readout(int B, int K, int C, const float* x, int ldx, const float* W, const float* bias,
                                const float* scale, const float* shift, const float* alpha, float* u, float* out,
                                void* stream);
+/* The same step, EVENT-DRIVEN (csrc/streamsparse.hip): only the weights of the ACTIVE inputs (value != 0) are read,
+ * about nnz * H * 4 bytes per operand and row tile instead of all of W and V.  The contracts, state buffers, strides,
+ * in_dtype, error codes and alignment refusals are those of the two entry points above; the weight operands differ, so
+ * that everything one input position contributes is one contiguous row:
+ *   Wt (K, ldw)       W TRANSPOSED, fp32; ldw >= H (readout: ldc >= C) a multiple of 4 (else SPARCH_EINVAL), the base
+ *                     16-byte aligned (else SPARCH_EALIGN)
+ *   vmask (H, ld)     the masked V as sparch_vmask writes it, NOT transposed: row k = what spike k of s_in feeds
+ * Per row the (k, value) pairs with value != 0 are listed in ascending k (values are kept: counts above 1, real-valued
+ * features and a drawn s0 take the same path; any density up to 100 % is correct).  Hidden layer: entry p of a row's
+ * list goes to partial sum p mod 4, each an fp32 FMA chain acc = fma(value, wt, acc) in ascending p, combined as
+ * (p0 + p1) + (p2 + p3); readout: one chain per class over the whole list.  Leaving out a zero input removes an exact
+ * +-0 from a sum that starts at +0, so only the ORDER of the non-zero terms differs from the dense step: results are
+ * bit-equal to it wherever the sums are exact in any order (dyadic weights on 0/1 spikes, counts, dyadic states), and
+ * within the last bits of any other fp32 order otherwise.  No float atomics: a pure function of the inputs.       */
+int sparch_stream_step_sparse_fwd(int kind, int B, int K, int H, int ld, int in_dtype, const void* x, int ldx,
+                                  const float* Wt, int ldw, const float* bias, const float* scale, const float* shift,
+                                  const float* alpha, const float* beta, const float* a, const float* b,
+                                  const float* vmask, float* u, float* w, const float* s_in, float* s_out,
+                                  uint16_t* s16_out, float theta, uint32_t* spike_count, void* stream);
+int sparch_stream_step_sparse_readout(int B, int K, int C, const float* x, int ldx, const float* Wt, int ldc,
+                                      const float* bias, const float* scale, const float* shift, const float* alpha,
+                                      float* u, float* out, void* stream);
 int sparch_readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x,
                        const float* bn_mean, const float* bn_invstd, const float* u_save,
                        const float* alpha, const float* u0, float* dWx, float* dalpha_ws,

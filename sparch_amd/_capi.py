@@ -99,6 +99,9 @@ PROTOTYPES = {
     "sparch_stream_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P,
                                        P, P, P, P, P, c_float, P, P]),
     "sparch_stream_step_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),
+    "sparch_stream_step_sparse_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, P,
+                                              P, P, P, P, P, P, P, P, P, c_float, P, P]),
+    "sparch_stream_step_sparse_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
     "sparch_fbank_frames": (c_int, [c_int]),
     "sparch_fbank_fwd": (c_int, [c_int, c_int, c_int, P, P, P]),
     "sparch_fbank_padded_fwd": (c_int, [c_int, c_int, P, c_int, c_int, c_int, P, P, P]),

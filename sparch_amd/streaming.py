@@ -24,12 +24,26 @@ projection, the BatchNorm affine, s @ V and the cell for a hidden layer, `sparch
 (csrc/streamstep.hip).  Every workgroup of a recurrent layer reads all of the previous spikes, so those layers keep
 their spike state twice and the host swaps which copy is current after each fused step.  Longer chunks take the
 path above on the same state.
+
+    st = StreamingSNN(net, batch_size, fused=True, sparse=True)
+
+makes the fused step event-driven: `sparch_stream_step_sparse_fwd` / `sparch_stream_step_sparse_readout`
+(csrc/streamsparse.hip) list the non-zero inputs of every row and read only their rows of the transposed weights
+(`W.t()` and the un-transposed masked V, cached by `refresh()`), about nnz * H * 4 bytes per operand instead of all of
+W and V.  Same state, same buffer swap, same launches per step; leaving out zero inputs changes no sum, only the order
+of the non-zero terms differs from the dense fused step.
 """
 import numpy as np
 import torch
 
 from . import functional as Fn
 from ._capi import KIND, check, lib, ptr
+
+
+def _transposed(W):
+    """W (H,K) -> W^T (K, ldw) fp32, ldw = H rounded up to a multiple of 4 (zero-padded): one contiguous row per input."""
+    H = W.shape[0]
+    return _pad_cols(W.t(), (H + 3) // 4 * 4).contiguous()
 
 
 def _pad_cols(t, H4):
@@ -54,7 +68,7 @@ class StreamingSNN:
     whole-sequence path; the stream kernels have by then written a half-advanced state over the carried one, so after
     such a report the stream can only be continued from a reset() (or a set_state() of a state saved earlier)."""
 
-    def __init__(self, net, batch_size, graph=False, fused=False):
+    def __init__(self, net, batch_size, graph=False, fused=False, sparse=False):
         if not getattr(net, "is_snn", False):
             raise ValueError("StreamingSNN: a sparch_amd.SNN (the non-spiking baselines do not stream)")
         if net.bidirectional:
@@ -63,6 +77,8 @@ class StreamingSNN:
         if net.training:
             raise ValueError("StreamingSNN: the network is in training mode — BatchNorm's batch statistics and "
                              "dropout have no streaming meaning; call net.eval() first")
+        if sparse and not fused:
+            raise ValueError("StreamingSNN: sparse=True is a form of the fused one-step path — pass fused=True too")
         if fused and any(mod.normalize and mod.normalization == "layernorm" for mod in net.snn):
             raise ValueError("StreamingSNN: fused=True does not take LayerNorm layers (a row statistic across the "
                              "workgroups of a step); use fused=False")
@@ -70,6 +86,7 @@ class StreamingSNN:
         self.batch_size = int(batch_size)
         self.graph = bool(graph)
         self.fused = bool(fused)
+        self.sparse = bool(sparse)
         self._fused_active = self.fused and Fn._prec() == 0
         self._fg = {}             # fused step, graph=True: {current spike buffers: dict(graph, replays)}, one per parity
         self._fg_x = self._fg_out = None   # the static input and output both parities share
@@ -109,6 +126,7 @@ class StreamingSNN:
                 L.W = Fn._f32c(mod.W.weight.detach())
                 L.Wb = None if mod.W.bias is None else Fn._f32c(mod.W.bias.detach())
                 L.w_planes = Fn.split_planes(L.W) if (L.K % 32 == 0 and L.H >= 128) else None
+                L.Wt = _transposed(L.W) if self.sparse else None  # the event-driven step's operand: row k = input k
                 L.norm = mod.normalization if mod.normalize else "none"
                 L.scale = L.shift = L.nw = L.nb = None
                 if L.norm == "batchnorm":  # eval: the running statistics folded into one affine map per column
@@ -170,6 +188,11 @@ class StreamingSNN:
         if self._layers is not None and self._prec != Fn._prec():
             return self.fused and Fn._prec() == 0  # (the next use refreshes)
         return self._fused_active
+
+    @property
+    def sparse_active(self):
+        """True when a step of Tc == 1 takes the event-driven fused path (sparse=True and fused_active)."""
+        return self.sparse and self.fused_active
 
     def _ensure(self):
         if self._layers is None or self._prec != Fn._prec():  # (the V pack is made for one operand mode)
@@ -438,14 +461,30 @@ class StreamingSNN:
         along K and row stride ldx.  Returns the readout's accumulator, or the last layer's fresh spike buffer."""
         B = self.batch_size
         src, dt = x, int(x.dtype == torch.uint8)
+        sparse = self.sparse_active
         for L in self._layers:
             if L.readout:
+                if sparse:
+                    check(lib.sparch_stream_step_sparse_readout(B, L.K, L.H, ptr(src), ldx, ptr(L.Wt), L.Wt.shape[1],
+                                                                ptr(L.Wb), ptr(L.scale), ptr(L.shift), ptr(L.p["alpha"]),
+                                                                ptr(L.u), ptr(L.out), Fn._stream()),
+                          "sparch_stream_step_sparse_readout")
+                    return L.out
                 check(lib.sparch_stream_step_readout(B, L.K, L.H, ptr(src), ldx, ptr(L.W), ptr(L.Wb), ptr(L.scale),
                                                      ptr(L.shift), ptr(L.p["alpha"]), ptr(L.u), ptr(L.out),
                                                      Fn._stream()), "sparch_stream_step_readout")
                 return L.out
             p = L.p
             s_out, s16_out = (L.s_alt, L.s16_alt) if L.recurrent else (L.s, None)
+            if sparse:
+                check(lib.sparch_stream_step_sparse_fwd(KIND[L.kind], B, L.K, L.H, L.Hs, dt, ptr(src), ldx, ptr(L.Wt),
+                                                        L.Wt.shape[1], ptr(L.Wb), ptr(L.scale), ptr(L.shift),
+                                                        ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
+                                                        ptr(p.get("b")), ptr(L.vmask) if L.recurrent else None, ptr(L.u),
+                                                        ptr(L.w), ptr(L.s), ptr(s_out), ptr(s16_out), L.theta,
+                                                        ptr(L.count), Fn._stream()), "sparch_stream_step_sparse_fwd")
+                src, ldx, dt = s_out, L.Hs, 0
+                continue
             check(lib.sparch_stream_step_fwd(KIND[L.kind], B, L.K, L.H, L.Hs, dt, ptr(src), ldx, ptr(L.W), ptr(L.Wb),
                                              ptr(L.scale), ptr(L.shift), ptr(p["alpha"]), ptr(p.get("beta")),
                                              ptr(p.get("a")), ptr(p.get("b")), ptr(L.vmask_t) if L.recurrent else None,

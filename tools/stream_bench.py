@@ -22,6 +22,11 @@ Tc = 1 the four modes eager / graph / fused / fused+graph are then timed stream 
 fused+graph, eager, ...), `--streams` streams each, and every row carries its own min and max over those streams;
 a `fused_vs_unfused` line per B says whether both fused modes lie below the unfused rows' minimum by more than the
 unfused rows' own min-max spread.  Defaults then: --batches 1 8 32 256, --out profiles/stream_bench_fused.jsonl.
+Beside them, in the same turn-taking, the event-driven fused step `StreamingSNN(fused=True, sparse=True)`
+(csrc/streamsparse.hip) as the modes sparse / sparse+graph, and the whole Tc = 1 block once per input density in
+--densities (default 0.02 0.05 0.15; the hidden layers fire what the network at its initial parameters fires: every
+row carries the measured firing rate per layer).  A `sparse_vs_fused` line per (B, density) claims a win only where the
+sparse rows' MAX over the streams lies below the dense fused rows' MIN of the same call.
 """
 import argparse
 import json
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--streams", type=int, default=3, help="timed streams of T steps per (B, Tc, mode)")
     ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 1024, 35])
     ap.add_argument("--channels", type=int, default=700)
+    ap.add_argument("--densities", type=float, nargs="+", default=[0.02, 0.05, 0.15],
+                    help="--fused: input densities of the Tc = 1 block (the other rows run at 0.05)")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "stream_bench_fused.jsonl" if args.fused else "stream_bench.jsonl")
@@ -100,9 +107,14 @@ def main():
                 setattr(_capi.lib, name, f)
         return n_calls[0]
 
-    def fused_rows(B, chunks):
-        """Tc = 1: the four modes, one stream each in turn, `--streams` times."""
-        modes = {"eager": (False, False), "graph": (True, False), "fused": (False, True), "fused+graph": (True, True)}
+    def layer_rates(st):
+        """Measured firing rate per hidden layer over all steps the stream has seen."""
+        return [float(L.count[:L.H].sum()) / (st.batch_size * st.steps_seen * L.H) for L in st._layers if not L.readout]
+
+    def fused_rows(B, chunks, density):
+        """Tc = 1: the six modes, one stream each in turn, `--streams` times."""
+        modes = {"eager": (False, False, False), "graph": (True, False, False), "fused": (False, True, False),
+                 "fused+graph": (True, True, False), "sparse": (False, True, True), "sparse+graph": (True, True, True)}
         sts, calls, ms = {}, {}, {m: [] for m in modes}
 
         def stream(st):
@@ -111,8 +123,8 @@ def main():
                 out = st.step(c)
             return out
 
-        for mode, (graph, fused) in modes.items():
-            st = sts[mode] = sparch_amd.StreamingSNN(net, B, graph=graph, fused=fused)
+        for mode, (graph, fused, sparse) in modes.items():
+            st = sts[mode] = sparch_amd.StreamingSNN(net, B, graph=graph, fused=fused, sparse=sparse)
             st.reset()
             stream(st)                        # warm-up (graph: the eager pass, then the captures)
             stream(st)
@@ -122,21 +134,32 @@ def main():
             for mode in modes:
                 ms[mode].append(timed(lambda: stream(sts[mode]), 1) / len(chunks))
         Fn.check_status(dev)
-        for mode, (graph, fused) in modes.items():
+        for mode, (graph, fused, sparse) in modes.items():
             st, v = sts[mode], ms[mode]
             replayed = None if not graph else (bool(st._fg) and all(g["replays"] > 0 for g in st._fg.values())
                                                if fused else bool(st._g is not None))
-            emit({"what": "stream", "B": B, "Tc": 1, "mode": mode, "ms_per_chunk": sum(v) / len(v),
+            emit({"what": "stream", "B": B, "Tc": 1, "density": density, "mode": mode, "ms_per_chunk": sum(v) / len(v),
                   "ms_per_chunk_min": min(v), "ms_per_chunk_max": max(v), "ms_per_chunk_streams": v,
-                  "us_per_step": 1e3 * sum(v) / len(v), "lib_calls_per_chunk": calls[mode], "graph_replayed": replayed})
+                  "us_per_step": 1e3 * sum(v) / len(v), "lib_calls_per_chunk": calls[mode], "graph_replayed": replayed,
+                  "layer_firing_rates": layer_rates(st)})
         unf = ms["eager"] + ms["graph"]
         lo, spread = min(unf), max(max(ms["eager"]) - min(ms["eager"]), max(ms["graph"]) - min(ms["graph"]))
-        emit({"what": "fused_vs_unfused", "B": B, "Tc": 1, "unfused_min_ms": lo, "unfused_spread_ms": spread,
+        emit({"what": "fused_vs_unfused", "B": B, "Tc": 1, "density": density, "unfused_min_ms": lo, "unfused_spread_ms": spread,
               "fused_max_ms": max(ms["fused"]), "fused_graph_max_ms": max(ms["fused+graph"]),
               "unfused_min_over_fused": lo / (sum(ms["fused"]) / len(ms["fused"])),
               "unfused_min_over_fused_graph": lo / (sum(ms["fused+graph"]) / len(ms["fused+graph"])),
               "fused_clears_margin": bool(max(ms["fused"]) < lo - spread),
               "fused_graph_clears_margin": bool(max(ms["fused+graph"]) < lo - spread)})
+        emit({"what": "sparse_vs_fused", "B": B, "Tc": 1, "density": density,
+              "fused_min_ms": min(ms["fused"]), "sparse_max_ms": max(ms["sparse"]),
+              "fused_graph_min_ms": min(ms["fused+graph"]), "sparse_graph_max_ms": max(ms["sparse+graph"]),
+              "fused_over_sparse": (sum(ms["fused"]) / len(ms["fused"])) / (sum(ms["sparse"]) / len(ms["sparse"])),
+              "fused_graph_over_sparse_graph": (sum(ms["fused+graph"]) / len(ms["fused+graph"])) /
+                                               (sum(ms["sparse+graph"]) / len(ms["sparse+graph"])),
+              "sparse_wins": bool(max(ms["sparse"]) < min(ms["fused"])),
+              "sparse_graph_wins": bool(max(ms["sparse+graph"]) < min(ms["fused+graph"])),
+              "sparse_loses": bool(min(ms["sparse"]) > max(ms["fused"])),
+              "sparse_graph_loses": bool(min(ms["sparse+graph"]) > max(ms["fused+graph"]))})
 
     for B in args.batches:
         g = torch.Generator().manual_seed(4321 + B)
@@ -149,7 +172,10 @@ def main():
         for Tc in args.chunks:
             chunks = [x[:, t0:t0 + Tc].contiguous() for t0 in range(0, T, Tc)]
             if args.fused and Tc == 1:
-                fused_rows(B, chunks)
+                for density in args.densities:
+                    gd = torch.Generator().manual_seed(4321 + B + int(round(1000 * density)))
+                    xd = (torch.rand(B, T, C, generator=gd) < density).float().to(dev)
+                    fused_rows(B, [xd[:, t0:t0 + 1].contiguous() for t0 in range(T)], density)
                 continue
             for mode in ("eager", "graph"):
                 st = sparch_amd.StreamingSNN(net, B, graph=(mode == "graph"))
