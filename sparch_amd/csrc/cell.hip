@@ -15,7 +15,7 @@
 // Arithmetic keeps the reference's operation order with -ffp-contract=off, so given
 // identical inputs the spikes are bit-identical to the eager CPU path.
 // HBM-bound: 12H (LIF) / 16H (adLIF) bytes per sample-step forward, the same backward.
-#include "common.h"
+#include "neuron.h"
 #include <type_traits>
 
 namespace {
@@ -97,7 +97,6 @@ __device__ __forceinline__ void stv(float* p, const float (&d)[VEC]) {
 // D steps of arithmetic and stores; which outputs exist is a template parameter (no branch in the loop).  D is
 // bounded by the wave's 6-bit vmcnt (in order, counts stores): with OPS vector-memory operations per step a load
 // older than 63 / OPS steps is forced complete by any counted wait.  Same arithmetic, same order: bit-identical.
-typedef unsigned cell_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int pipe_depth(int vec, int ops) { return vec == 4 ? 8 : (63 / ops < 16 ? 63 / ops : 16); }
 
 // one saved state (u or w) of VEC neurons as it comes off the wire: fp32, or bf16 words unpacked at the use
@@ -149,18 +148,13 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
     const int d = bp / c.B, b = bp - d * c.B;
     const int T = c.T, H = c.H, HO = c.H * c.dirs;
 
-    float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], sc[VEC], sh[VEC];
+    Neuron<ADAPT> p[VEC];
+    float sc[VEC], sh[VEC];
     float u[VEC], w[VEC], s[VEC];
     uint32_t cnt[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-        al[e] = clampf(c.alpha[h + e], SP_ALPHA_LO, SP_ALPHA_HI);
-        oma[e] = 1.0f - al[e];
-        if (ADAPT) {
-            be[e] = clampf(c.beta[h + e], SP_BETA_LO, SP_BETA_HI);
-            pa[e] = clampf(c.a[h + e], SP_A_LO, SP_A_HI);
-            pb[e] = clampf(c.b[h + e], SP_B_LO, SP_B_HI);
-        }
+        p[e] = neuron_load<ADAPT>(c.alpha, c.beta, c.a, c.b, h + e);
         sc[e] = c.scale ? c.scale[h + e] : 1.0f;
         sh[e] = c.scale ? c.shift[h + e] : 0.0f;
         cnt[e] = 0;
@@ -183,29 +177,16 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
         const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            float xn = x[e];
-            if (has_norm) xn = bn_affine(xn, sc[e], sh[e]);
-            float drive = xn;
-            if (ADAPT) {
-                w[e] = (be[e] * w[e] + pa[e] * u[e]) + pb[e] * s[e];  // snns.py:438
-                drive = xn - w[e];
-            }
-            u[e] = al[e] * (u[e] - s[e]) + oma[e] * drive;           // snns.py:297 / 439
-            s[e] = (u[e] - c.theta) > 0.0f ? 1.0f : 0.0f;            // snns.py:29
+            const float xn = neuron_input(x[e], false, 0.f, has_norm, sc[e], sh[e]);
+            neuron_step<ADAPT, false>(u[e], w[e], s[e], xn, 0.f, p[e], c.theta);
             const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
             so[e] = s[e] * k;
             cnt[e] += (so[e] != 0.0f) ? 1u : 0u;
         }
         if (SOUT) stv<VEC>(c.s_out + o, so);
         if (S16OUT) {
-            if constexpr (VEC == 4) {
-                cell_u32x2 pk;
-                pk.x = (so[0] != 0.0f ? 0x3F80u : 0u) | (so[1] != 0.0f ? 0x3F800000u : 0u);
-                pk.y = (so[2] != 0.0f ? 0x3F80u : 0u) | (so[3] != 0.0f ? 0x3F800000u : 0u);
-                *reinterpret_cast<cell_u32x2*>(c.s16_out + o) = pk;
-            } else {
-                c.s16_out[o] = so[0] != 0.0f ? (uint16_t)0x3F80 : (uint16_t)0;
-            }
+            if constexpr (VEC == 4) *reinterpret_cast<u32x2*>(c.s16_out + o) = spike_quad16(so);
+            else c.s16_out[o] = spike_bf16(so[0] != 0.0f);
         }
         if (SAVE) {
             st_saved<VEC, true>(c.u_save, ((size_t)bp * T + t) * H + h, u, SAVE == 2, c.theta);
@@ -272,13 +253,8 @@ __global__ __launch_bounds__(256) void cell_bwd_pipe_kernel(CellArgs c) {
         bn_mu[e] = BN ? c.bn_mean[h + e] : 0.f;
         bn_is[e] = BN ? c.bn_invstd[h + e] : 0.f;
         acc_dy[e] = acc_dyx[e] = 0.f;
-        al[e] = clampf(c.alpha[h + e], SP_ALPHA_LO, SP_ALPHA_HI);
-        oma[e] = 1.0f - al[e];
-        if (ADAPT) {
-            be[e] = clampf(c.beta[h + e], SP_BETA_LO, SP_BETA_HI);
-            pa[e] = clampf(c.a[h + e], SP_A_LO, SP_A_HI);
-            pb[e] = clampf(c.b[h + e], SP_B_LO, SP_B_HI);
-        }
+        const Neuron<ADAPT> p = neuron_load<ADAPT>(c.alpha, c.beta, c.a, c.b, h + e);
+        al[e] = p.al; oma[e] = p.oma; be[e] = p.be; pa[e] = p.pa; pb[e] = p.pb;
         gr[e] = c.g_rate ? c.g_rate[(size_t)d * H + h + e] * c.g_rate_scale : 0.0f;
         du_n[e] = dw_n[e] = 0.f;
         acc_al[e] = acc_be[e] = acc_a[e] = acc_b[e] = 0.f;
@@ -317,7 +293,7 @@ __global__ __launch_bounds__(256) void cell_bwd_pipe_kernel(CellArgs c) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             if (t0) { up[e] = u0v[e]; if (ADAPT) wp[e] = w0v[e]; }
-            sp[e] = t0 ? s0v[e] : ((up[e] - c.theta) > 0.0f ? 1.0f : 0.0f);
+            sp[e] = t0 ? s0v[e] : (spike_of(up[e], c.theta) ? 1.0f : 0.0f);
         }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
@@ -457,7 +433,7 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     const bool wave_has_class = (tid & ~63) < C;  // wave-uniform: waves past the classes skip the class phases
     const int cc = act ? tid : C;
     const int cp = act ? tid : 0;
-    const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
+    const Neuron<false> p = neuron_load<false>(alpha, nullptr, nullptr, nullptr, cp);
     const bool has_bn = scale != nullptr;
     const float sc = has_bn ? scale[cp] : 1.0f, sh = has_bn ? shift[cp] : 0.0f;
     float u = STREAM ? u_io[(size_t)b * C + cp] : u0[(size_t)b * C + cp];
@@ -488,31 +464,28 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
         // running LDS / row offsets (the step is a handful of instructions: its issue time is the phase);
         // the ragged tail goes step by step.
         if (wave_has_class) {
-            float* p = us + cc;                                                      // -> us[t][cc]
+            float* q = us + cc;                                                      // -> us[t][cc]
             unsigned go = act ? (unsigned)(((size_t)c0 * C + tid) * sizeof(float)) : RO_OOB;  // -> u_save[c0 + t][tid]
             const unsigned gstep = act ? (unsigned)(C * sizeof(float)) : 0u;
             int t0 = 0;
             for (; t0 + 8 <= len; t0 += 8) {
                 float x[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) x[j] = p[j * CS];
+                for (int j = 0; j < 8; ++j) x[j] = q[j * CS];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float xn = has_bn ? bn_affine(x[j], sc, sh) : x[j];
-                    u = al * u + oma * xn;                               // snns.py:822
-                    p[j * CS] = u;
+                    u = readout_step(u, neuron_input(x[j], false, 0.f, has_bn, sc, sh), p.al, p.oma);
+                    q[j * CS] = u;
                     ro_store(u, ru, go + j * gstep);
                 }
-                p += 8 * CS;
+                q += 8 * CS;
                 go += 8 * gstep;
             }
             for (; t0 < len; ++t0) {
-                const float x = *p;
-                const float xn = has_bn ? bn_affine(x, sc, sh) : x;
-                u = al * u + oma * xn;
-                *p = u;
+                u = readout_step(u, neuron_input(*q, false, 0.f, has_bn, sc, sh), p.al, p.oma);
+                *q = u;
                 ro_store(u, ru, go);
-                p += CS;
+                q += CS;
                 go += gstep;
             }
         }
@@ -569,7 +542,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     const bool wave_has_class = (tid & ~63) < C;
     const int cc = act ? tid : C;
     const int cp = act ? tid : 0;
-    const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
+    const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;  // (neuron.h: this copy stays)
     gs[tid] = act ? g_out[(size_t)b * C + cp] : 0.f;
     float du = 0.f, acc = 0.f;
     // BatchNorm backward's column sums folded in (nullable): sum_t dWx and sum_t dWx*xhat per (row, class)

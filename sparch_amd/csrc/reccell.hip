@@ -60,7 +60,7 @@
 //     rec_plan::Policy; run_rec / run_ann below size, check and clear the workspace, plan, walk.
 //     Which instantiation runs a call is one table per family (rec_kernel, ann_kernel), used
 //     for launching and for the occupancy question alike.
-#include "common.h"
+#include "neuron.h"
 
 #include "rec_common.h"
 
@@ -176,19 +176,16 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         u32x4 e;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            e[j] = (((unsigned)tid >> (2 * j)) & 1u ? 0x3F80u : 0u) | (((unsigned)tid >> (2 * j + 1)) & 1u ? 0x3F800000u : 0u);
+            e[j] = spike_pair16(((unsigned)tid >> (2 * j)) & 1u, ((unsigned)tid >> (2 * j + 1)) & 1u);
         lut[tid] = e;
     }
 
-    float al[4], oma[4], be[4], pa[4], pb[4], sc[4], sh[4], u[4], w[4], s[4];
+    Neuron<ADAPT> p[4];
+    float sc[4], sh[4], u[4], w[4], s[4];
     uint32_t cnt[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        al[e] = clampf(a.alpha[colc + e], SP_ALPHA_LO, SP_ALPHA_HI);
-        oma[e] = 1.0f - al[e];
-        be[e] = ADAPT ? clampf(a.beta[colc + e], SP_BETA_LO, SP_BETA_HI) : 0.f;
-        pa[e] = ADAPT ? clampf(a.a[colc + e], SP_A_LO, SP_A_HI) : 0.f;
-        pb[e] = ADAPT ? clampf(a.b[colc + e], SP_B_LO, SP_B_HI) : 0.f;
+        p[e] = neuron_load<ADAPT>(a.alpha, a.beta, a.a, a.b, colc + e);
         sc[e] = a.scale ? a.scale[colc + e] : 1.0f;
         sh[e] = a.scale ? a.shift[colc + e] : 0.0f;
         w[e] = 0.f;
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             const size_t o = ((size_t)bpc * T + (a.t_begin - 1)) * H + colc;
             v = ld4(a.u_save + o); u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) s[e] = (u[e] - a.theta) > 0.0f ? 1.0f : 0.0f;
+            for (int e = 0; e < 4; ++e) s[e] = spike_of(u[e], a.theta) ? 1.0f : 0.0f;
             if (ADAPT) { v = ld4(a.w_save + o); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
         }
     }
@@ -247,10 +244,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         const size_t o_s = ((size_t)b * T + ptt) * HO + (size_t)d * H + colc;
         if (a.s_out) st4(a.s_out + o_s, vs);  // the fp32 copy: only for callers that read the layer's output tensor
         if (a.s16_out) {  // the same spikes as a bf16 plane (0 / 1.0) for the GEMMs that consume them
-            u32x2 h;
-            h.x = (vs[0] != 0.f ? 0x3F80u : 0u) | (vs[1] != 0.f ? 0x3F800000u : 0u);
-            h.y = (vs[2] != 0.f ? 0x3F80u : 0u) | (vs[3] != 0.f ? 0x3F800000u : 0u);
-            st2(a.s16_out + o_s, h);
+            st2(a.s16_out + o_s, spike_quad16(vs));
         }
         if constexpr (!STREAM) {
             st4_saved<true>(a.u_save, ((size_t)bp * T + st_t) * H + col, vu, a.save16, a.theta);
@@ -384,15 +378,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         unsigned nib = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float xn = xs[e];
-            if (has_norm) xn = bn_affine(xn, sc[e], sh[e]);
-            float drive = xn + rec[e];                                      // snns.py:572 / 720
-            if (ADAPT) {
-                w[e] = (be[e] * w[e] + pa[e] * u[e]) + pb[e] * s[e];        // snns.py:718
-                drive = drive - w[e];
-            }
-            u[e] = al[e] * (u[e] - s[e]) + oma[e] * drive;                  // snns.py:572 / 719
-            s[e] = (u[e] - a.theta) > 0.0f ? 1.0f : 0.0f;                   // snns.py:29
+            const float xn = neuron_input(xs[e], false, 0.f, has_norm, sc[e], sh[e]);
+            neuron_step<ADAPT, true>(u[e], w[e], s[e], xn, rec[e], p[e], a.theta);
             uo[e] = u[e];
             wo[e] = w[e];
             if (valid) nib |= (s[e] != 0.0f ? 1u : 0u) << e;
@@ -407,10 +394,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
         word |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)word, 0x141, 0xF, 0xF, true);  // row_half_mirror
         if (EXT) {
             if (valid) {  // the step's raw (pre-dropout) spikes: operand of the caller's s_t @ V product
-                u32x2 h;
-                h.x = (s[0] != 0.f ? 0x3F80u : 0u) | (s[1] != 0.f ? 0x3F800000u : 0u);
-                h.y = (s[2] != 0.f ? 0x3F80u : 0u) | (s[3] != 0.f ? 0x3F800000u : 0u);
-                *reinterpret_cast<u32x2*>(a.s_step16 + (size_t)bp * H + col) = h;
+                *reinterpret_cast<u32x2*>(a.s_step16 + (size_t)bp * H + col) = spike_quad16(s);
             }
         } else if (pw && cq == 0 && t + 1 < T) {
             gu64* slot = (gu64*)a.chan + (((size_t)t * a.n_rt_total + rt) * a.n_ct + ct) * 32 + r;
@@ -455,10 +439,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             *reinterpret_cast<f32x4*>(const_cast<float*>(a.s0) + o) = f32x4{s[0], s[1], s[2], s[3]};
             if (ADAPT) *reinterpret_cast<f32x4*>(const_cast<float*>(a.w0) + o) = f32x4{w[0], w[1], w[2], w[3]};
             if (!EXT) {  // (the step variant has written the plane already)
-                u32x2 h;
-                h.x = (s[0] != 0.f ? 0x3F80u : 0u) | (s[1] != 0.f ? 0x3F800000u : 0u);
-                h.y = (s[2] != 0.f ? 0x3F80u : 0u) | (s[3] != 0.f ? 0x3F800000u : 0u);
-                *reinterpret_cast<u32x2*>(a.s_step16 + o) = h;
+                *reinterpret_cast<u32x2*>(a.s_step16 + o) = spike_quad16(s);
             }
         }
     }
@@ -568,7 +549,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         f32x4 c_al, c_be, c_a, c_b, c_gr;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            c_al[e] = clampf(a.alpha[cc + e], SP_ALPHA_LO, SP_ALPHA_HI);
+            c_al[e] = clampf(a.alpha[cc + e], SP_ALPHA_LO, SP_ALPHA_HI);  // (neuron.h: these four copies stay)
             c_be[e] = ADAPT ? clampf(a.beta[cc + e], SP_BETA_LO, SP_BETA_HI) : 0.f;
             c_a[e] = ADAPT ? clampf(a.a[cc + e], SP_A_LO, SP_A_HI) : 0.f;
             c_b[e] = ADAPT ? clampf(a.b[cc + e], SP_B_LO, SP_B_HI) : 0.f;
@@ -830,7 +811,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         // ---- pointwise reverse step (its rec-independent part: pre_pointwise above)
         if (t > 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sp[e] = (up_use[e] - a.theta) > 0.0f ? 1.0f : 0.0f;
+            for (int e = 0; e < 4; ++e) sp[e] = spike_of(up_use[e], a.theta) ? 1.0f : 0.0f;
         } else {
             const f32x4 v = first_tile[2][pt];
             sp[0] = v.x; sp[1] = v.y; sp[2] = v.z; sp[3] = v.w;
@@ -904,7 +885,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a) {
         PROF_STAMP(4);  // publish barrier
         // ---- off the critical path: fp32 outputs for the following GEMMs, parameter partial sums
         if (valid) {
-            u32x2 h;  // s_{t-1} (binary for t >= 1, zero row at t = 0) as a bf16 plane for the dV product
+            u32x2 h;  // s_{t-1} (binary; a zero row at t = 0) as a bf16 plane for dV (this copy stays: neuron.h)
             h.x = (spv[0] != 0.f ? 0x3F80u : 0u) | (spv[1] != 0.f ? 0x3F800000u : 0u);
             h.y = (spv[2] != 0.f ? 0x3F80u : 0u) | (spv[3] != 0.f ? 0x3F800000u : 0u);
             if (BXS) {

@@ -21,9 +21,10 @@
 //                   a wave load is 64 adjacent floats of weight row k (two 128-byte lines), SP_U of them in flight (the
 //                   addresses come from LDS and are known ahead), acc = fma(value, wt, acc) in ascending p.
 // then the four waves' partial sums of a (row, column) meet in LDS and are added as (p0 + p1) + (p2 + p3), Wx and s V
-// apart, and the pointwise update — the expression trees of stream_step_kernel, restated — writes the new state.
+// apart, and the pointwise update — stream_pointwise (stream_common.h), the dense step's own — writes the new state.
 // The readout is one workgroup per batch row: the same compaction, thread = class runs over the whole list in
-// ascending k (one chain), then exactly the tail of stream_step_readout_kernel.
+// ascending k (one chain), then stream_readout_tail, the dense readout step's own.  What is here: sp_compact, sp_dot,
+// the geometry of the two kernels, the entry points.
 //
 // Why it is exact: leaving out a term whose input is 0 removes an exact +-0 from an fp32 sum that starts at +0; for
 // finite weights no partial sum changes.  What differs from the dense fused kernel is only the ORDER and grouping of the
@@ -34,9 +35,7 @@
 //
 // Weight loads keep the default cache policy: a column tile always lands on the same workgroup index, hence on the same
 // XCD's L2, and the weights are read again every step.
-#include <initializer_list>
-
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
 
@@ -46,18 +45,6 @@ constexpr int SP_COLS = 64;  // columns per workgroup: one per lane
 constexpr int SP_U = 8;      // weight rows in flight per wave
 // input positions compacted per piece: the lists are RT x piece (position, value) pairs of LDS, 6 bytes each (<= 24 KB)
 __host__ __device__ constexpr int sp_piece(int RT) { return RT <= 2 ? 1024 : RT <= 8 ? 512 : 256; }
-
-struct SparseArgs {
-    int B, K, H, ld, ldx, ldw, in_u8;
-    const void* x;
-    const float *Wt, *bias, *scale, *shift, *alpha, *beta, *a, *b, *vmask;
-    float *u, *w;
-    const float* s_in;
-    float* s_out;
-    uint16_t* s16_out;
-    float theta;
-    uint32_t* spike_count;
-};
 
 // One piece [k0, k0 + KP) of the row tile of src -> per row the ascending list of its non-zero (k - k0, value) pairs:
 // lk / lv [r * KP + j], j < pcnt[r]; pbase[r] = the number of entries the row's earlier pieces held.  `tot` is the
@@ -165,7 +152,7 @@ __device__ __forceinline__ void sp_dot(float* lv, uint16_t* lk, int* wcnt, int* 
 }
 
 template <int RT, bool ADAPT, bool REC>
-__global__ __launch_bounds__(SP_NT) void stream_step_sparse_kernel(SparseArgs a) {
+__global__ __launch_bounds__(SP_NT) void stream_step_sparse_kernel(StreamArgs a) {
     constexpr int RPT = (RT + SP_WAVES - 1) / SP_WAVES;  // rows of the pointwise phase per thread
     __shared__ float lv[RT * sp_piece(RT)];
     __shared__ uint16_t lk[RT * sp_piece(RT)];
@@ -177,10 +164,7 @@ __global__ __launch_bounds__(SP_NT) void stream_step_sparse_kernel(SparseArgs a)
     const int h = h0 + lane, hc = min(h, a.H - 1);  // (a lane past H: any valid column, never written)
     // ---- the pointwise phase's operands, asked for now (thread = column, rows wave, wave + 4, ...): they arrive
     //      while the lists are made
-    const float p_al = a.alpha[hc];
-    const float p_bias = a.bias ? a.bias[hc] : 0.f;
-    const float p_sc = a.scale ? a.scale[hc] : 1.f, p_sh = a.scale ? a.shift[hc] : 0.f;
-    const float p_be = ADAPT ? a.beta[hc] : 0.f, p_a = ADAPT ? a.a[hc] : 0.f, p_b = ADAPT ? a.b[hc] : 0.f;
+    const StreamColumn<ADAPT> pc = stream_column<ADAPT>(a.alpha, a.beta, a.a, a.b, a.bias, a.scale, a.shift, hc);
     float u_prev[RPT], w_prev[RPT], s_prev[RPT];
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
@@ -193,10 +177,10 @@ __global__ __launch_bounds__(SP_NT) void stream_step_sparse_kernel(SparseArgs a)
 #pragma unroll
     for (int r = 0; r < RT; ++r) red[0][wave][r][lane] = red[1][wave][r][lane] = 0.f;  // (this thread's own slots)
     if (a.in_u8)
-        sp_dot<RT, true>(lv, lk, wcnt, pcnt, pbase, a.x, a.ldx, a.Wt, a.ldw, a.K, r0, a.B, hc, red[0][wave]);
+        sp_dot<RT, true>(lv, lk, wcnt, pcnt, pbase, a.x, a.ldx, a.W, a.ldw, a.K, r0, a.B, hc, red[0][wave]);
     else
-        sp_dot<RT, false>(lv, lk, wcnt, pcnt, pbase, a.x, a.ldx, a.Wt, a.ldw, a.K, r0, a.B, hc, red[0][wave]);
-    if (REC) sp_dot<RT, false>(lv, lk, wcnt, pcnt, pbase, a.s_in, a.ld, a.vmask, a.ld, a.H, r0, a.B, hc, red[1][wave]);
+        sp_dot<RT, false>(lv, lk, wcnt, pcnt, pbase, a.x, a.ldx, a.W, a.ldw, a.K, r0, a.B, hc, red[0][wave]);
+    if (REC) sp_dot<RT, false>(lv, lk, wcnt, pcnt, pbase, a.s_in, a.ld, a.V, a.ld, a.H, r0, a.B, hc, red[1][wave]);
     // ---- the four waves' partial sums of a (row, column) in one fixed tree (sp_dot ends in a barrier)
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
@@ -205,27 +189,7 @@ __global__ __launch_bounds__(SP_NT) void stream_step_sparse_kernel(SparseArgs a)
         const size_t o = (size_t)row * a.ld + h;
         const float sx = (red[0][0][r][lane] + red[0][1][r][lane]) + (red[0][2][r][lane] + red[0][3][r][lane]);
         const float sr = REC ? (red[1][0][r][lane] + red[1][1][r][lane]) + (red[1][2][r][lane] + red[1][3][r][lane]) : 0.f;
-        float u = u_prev[i];
-        const float s = s_prev[i];
-        // the expression trees of stream_step_kernel (streamstep.hip)
-        const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
-        float wx = sx;
-        if (a.bias) wx = wx + p_bias;
-        const float xn = a.scale ? bn_affine(wx, p_sc, p_sh) : wx;
-        float drive = REC ? xn + sr : xn;                                        // snns.py:572 / 720
-        if (ADAPT) {
-            const float be = clampf(p_be, SP_BETA_LO, SP_BETA_HI), pa = clampf(p_a, SP_A_LO, SP_A_HI),
-                        pb = clampf(p_b, SP_B_LO, SP_B_HI);
-            const float w = (be * w_prev[i] + pa * u) + pb * s;                  // snns.py:718 / 438
-            drive = drive - w;
-            a.w[o] = w;
-        }
-        u = al * (u - s) + oma * drive;                                          // snns.py:572 / 719 / 297 / 439
-        const bool spike = (u - a.theta) > 0.0f;                                 // snns.py:29
-        a.u[o] = u;
-        a.s_out[o] = spike ? 1.0f : 0.0f;
-        if (a.s16_out) a.s16_out[o] = spike ? (uint16_t)0x3F80u : (uint16_t)0u;  // bf16 1.0 / 0.0
-        if (spike && a.spike_count) atomicAdd(a.spike_count + h, 1u);
+        stream_pointwise<ADAPT, REC>(a, pc, sx, sr, u_prev[i], w_prev[i], s_prev[i], o, h);
     }
 }
 
@@ -250,8 +214,7 @@ __global__ __launch_bounds__(SP_NT) void stream_step_sparse_readout_kernel(int K
     // thread = class operands, asked for now
     const bool act = tid < C;
     const int cc = act ? tid : C - 1;
-    const float p_al = alpha[cc], p_bias = bias ? bias[cc] : 0.f;
-    const float p_sc = scale ? scale[cc] : 1.f, p_sh = scale ? shift[cc] : 0.f;
+    const StreamColumn<false> pc = stream_column<false>(alpha, nullptr, nullptr, nullptr, bias, scale, shift, cc);
     const float u_prev = u_io[(size_t)b * C + cc], out_prev = out[(size_t)b * C + cc];
     float acc = 0.f;
     int tot = 0;
@@ -275,40 +238,8 @@ __global__ __launch_bounds__(SP_NT) void stream_step_sparse_readout_kernel(int K
         }
         __syncthreads();
     }
-    // thread = class: the recurrence of readout_fwd_kernel (cell.hip), as in stream_step_readout_kernel
-    if (act) {
-        const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
-        float wx = acc;
-        if (bias) wx = wx + p_bias;
-        const float xn = scale ? bn_affine(wx, p_sc, p_sh) : wx;
-        const float u = al * u_prev + oma * xn;                              // snns.py:822
-        u_io[(size_t)b * C + tid] = u;
-        row[tid] = u;
-    }
-    __syncthreads();
-    // one thread: the softmax in the arithmetic (and the order) of the whole-sequence kernel's thread = time phase
-    if (tid == 0) {
-        const float den = ro_softmax_row(row, C);
-        for (int c = 0; c < C; ++c) row[c] = row[c] / den;
-    }
-    __syncthreads();
-    if (act) out[(size_t)b * C + tid] = out_prev + row[tid];                 // snns.py:823
-}
-
-template <int RT>
-void launch_sparse(int kind, const SparseArgs& a, dim3 grid, hipStream_t st) {
-    switch (kind) {
-        case SPARCH_KIND_LIF: hipLaunchKernelGGL((stream_step_sparse_kernel<RT, false, false>), grid, dim3(SP_NT), 0, st, a); break;
-        case SPARCH_KIND_ADLIF: hipLaunchKernelGGL((stream_step_sparse_kernel<RT, true, false>), grid, dim3(SP_NT), 0, st, a); break;
-        case SPARCH_KIND_RLIF: hipLaunchKernelGGL((stream_step_sparse_kernel<RT, false, true>), grid, dim3(SP_NT), 0, st, a); break;
-        default: hipLaunchKernelGGL((stream_step_sparse_kernel<RT, true, true>), grid, dim3(SP_NT), 0, st, a); break;
-    }
-}
-
-bool all16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (p && !aligned16(p)) return false;
-    return true;
+    stream_readout_tail(row, act, b, C, acc, pc, bias != nullptr, scale != nullptr, u_prev, out_prev, u_io,
+                        out);
 }
 
 }  // namespace
@@ -320,34 +251,18 @@ extern "C" int sparch_stream_step_sparse_fwd(int kind, int B, int K, int H, int 
                                              float* s_out, uint16_t* s16_out, float theta, uint32_t* spike_count,
                                              void* stream) {
     SPARCH_ENTER();
-    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF && kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF)
-        return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_ADLIF || kind == SPARCH_KIND_RADLIF;
-    const bool rec = kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF;
-    if (in_dtype != 0 && in_dtype != 1) return SPARCH_EINVAL;
-    if (B <= 0 || K <= 0 || H <= 0 || ld < H || ldx < K || ldw < H || (ldw & 3) != 0) return SPARCH_EINVAL;
-    if (!x || !Wt || !alpha || !u || !s_in || !s_out) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w)) return SPARCH_EINVAL;
-    if (rec && (!vmask || s_in == s_out)) return SPARCH_EINVAL;  // every workgroup reads all of s_in
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!all16({Wt, vmask, u, w, s_in, s_out, s16_out})) return SPARCH_EALIGN;
-    SparseArgs g{};
+    StreamArgs g{};
     g.B = B; g.K = K; g.H = H; g.ld = ld; g.ldx = ldx; g.ldw = ldw; g.in_u8 = in_dtype;
-    g.x = x; g.Wt = Wt; g.bias = bias; g.scale = scale; g.shift = shift;
-    g.alpha = alpha; g.beta = beta; g.a = a; g.b = b; g.vmask = vmask;
-    g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out;
-    g.theta = theta; g.spike_count = spike_count;
-    // the smallest row tile that holds the batch, as the dense step chooses it
-    const int RT = B >= 9 ? 16 : B >= 5 ? 8 : B >= 3 ? 4 : B;
+    g.x = x; g.W = Wt; g.bias = bias; g.scale = scale; g.shift = shift;
+    g.alpha = alpha; g.beta = beta; g.a = a; g.b = b; g.V = vmask;
+    g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out; g.theta = theta; g.spike_count = spike_count;
+    if (const int rc = stream_step_check(kind, in_dtype, g, true)) return rc;
+    const int RT = stream_row_tile(B);  // the smallest row tile that holds the batch, as the dense step chooses it
     const dim3 grid(cdiv(H, SP_COLS), cdiv(B, RT));
-    if (grid.y > 65535u) return SPARCH_EINVAL;
-    switch (RT) {
-        case 1: launch_sparse<1>(kind, g, grid, (hipStream_t)stream); break;
-        case 2: launch_sparse<2>(kind, g, grid, (hipStream_t)stream); break;
-        case 4: launch_sparse<4>(kind, g, grid, (hipStream_t)stream); break;
-        case 8: launch_sparse<8>(kind, g, grid, (hipStream_t)stream); break;
-        default: launch_sparse<16>(kind, g, grid, (hipStream_t)stream); break;
-    }
+    stream_dispatch(RT, kind, [&](auto rt, auto adapt, auto rec) {
+        hipLaunchKernelGGL((stream_step_sparse_kernel<decltype(rt)::value, decltype(adapt)::value, decltype(rec)::value>), grid,
+                           dim3(SP_NT), 0, (hipStream_t)stream, g);
+    });
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -356,10 +271,7 @@ extern "C" int sparch_stream_step_sparse_readout(int B, int K, int C, const floa
                                                  const float* bias, const float* scale, const float* shift,
                                                  const float* alpha, float* u, float* out, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || K <= 0 || C <= 0 || C > 256 || ldx < K || ldc < C || (ldc & 3) != 0) return SPARCH_EINVAL;
-    if (!x || !Wt || !alpha || !u || !out) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!aligned16(Wt)) return SPARCH_EALIGN;
+    if (const int rc = stream_readout_check(B, K, C, x, ldx, Wt, true, ldc, scale, shift, alpha, u, out)) return rc;
     hipLaunchKernelGGL(stream_step_sparse_readout_kernel, dim3(B), dim3(SP_NT), 0, (hipStream_t)stream, K, C, x, ldx, Wt,
                        ldc, bias, scale, shift, alpha, u, out);
     SPARCH_CHECK_LAUNCH();

@@ -17,11 +17,9 @@
 // column always lands on the same workgroup index, so they are loaded with the default cache policy and stay in L2.
 // The dot products are fp32 FMA chains, 64 lane partials per (row, column) added by a butterfly: exact wherever the
 // sums are exact in any order (dyadic weights on 0/1 spikes), otherwise within a few ulp of any other fp32 order.
-// The pointwise update restates the expression trees of rec_fwd_kernel (reccell.hip) and cell_fwd_pipe_kernel
-// (cell.hip); the file is built with -ffp-contract=off like them, so the same expressions give the same bits.
-#include <initializer_list>
-
-#include "common.h"
+// The pointwise update is the one of rec_fwd_kernel (reccell.hip) and cell_fwd_pipe_kernel (cell.hip): neuron.h, through
+// the tails of stream_common.h.  What is here: ss_dot, the geometry of the two kernels, the entry points.
+#include "stream_common.h"
 
 namespace {
 
@@ -29,18 +27,6 @@ constexpr int SS_NT = 256;   // 4 waves
 constexpr int SS_COLS = 4;   // columns per workgroup: one per wave
 // floats of one staged row piece: the tile is RT x KP floats of LDS (<= 32 KB)
 __host__ __device__ constexpr int ss_piece(int RT) { return RT <= 8 ? 1024 : 512; }
-
-struct StepArgs {
-    int B, K, H, ld, ldx, in_u8;
-    const void* x;
-    const float *W, *bias, *scale, *shift, *alpha, *beta, *a, *b, *vmask_t;
-    float *u, *w;
-    const float* s_in;
-    float* s_out;
-    uint16_t* s16_out;
-    float theta;
-    uint32_t* spike_count;
-};
 
 // acc[r] += sum_k src[r0 + r][k] * wrow[k], k < K.  All 256 threads stage; the calling wave's lanes stride over k.
 // A wave without a column is given any valid row (it stages, keeps the barriers, and its sums are never read).
@@ -128,7 +114,7 @@ __device__ __forceinline__ float ss_wave_sum(float v) {
 }
 
 template <int RT, bool ADAPT, bool REC, bool VEC>
-__global__ __launch_bounds__(SS_NT) void stream_step_kernel(StepArgs a) {
+__global__ __launch_bounds__(SS_NT) void stream_step_kernel(StreamArgs a) {
     constexpr int KP = ss_piece(RT);
     __shared__ __attribute__((aligned(16))) float xs[RT * KP];
     __shared__ float red[2][RT][SS_COLS];
@@ -142,13 +128,8 @@ __global__ __launch_bounds__(SS_NT) void stream_step_kernel(StepArgs a) {
     const bool valid = r < RT && row < a.B && h < a.H;
     const int hc = min(h, a.H - 1);
     const size_t o = (size_t)min(row, a.B - 1) * a.ld + hc;
-    const float p_al = a.alpha[hc];
-    const float p_bias = a.bias ? a.bias[hc] : 0.f;
-    const float p_sc = a.scale ? a.scale[hc] : 1.f, p_sh = a.scale ? a.shift[hc] : 0.f;
-    const float p_be = ADAPT ? a.beta[hc] : 0.f, p_a = ADAPT ? a.a[hc] : 0.f, p_b = ADAPT ? a.b[hc] : 0.f;
-    float u = a.u[o];
-    const float w_prev = ADAPT ? a.w[o] : 0.f;
-    const float s = a.s_in[o];
+    const StreamColumn<ADAPT> pc = stream_column<ADAPT>(a.alpha, a.beta, a.a, a.b, a.bias, a.scale, a.shift, hc);
+    const float u = a.u[o], w = ADAPT ? a.w[o] : 0.f, s = a.s_in[o];
 
     float accx[RT], accr[RT];
 #pragma unroll
@@ -157,7 +138,7 @@ __global__ __launch_bounds__(SS_NT) void stream_step_kernel(StepArgs a) {
         ss_dot<RT, true, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
     else
         ss_dot<RT, false, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
-    if (REC) ss_dot<RT, false, VEC>(xs, a.s_in, a.ld, a.vmask_t + (size_t)hw * a.ld, a.H, r0, a.B, accr);
+    if (REC) ss_dot<RT, false, VEC>(xs, a.s_in, a.ld, a.V + (size_t)hw * a.ld, a.H, r0, a.B, accr);
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
         const float sx = ss_wave_sum(accx[i]);
@@ -168,25 +149,7 @@ __global__ __launch_bounds__(SS_NT) void stream_step_kernel(StepArgs a) {
         }
     }
     __syncthreads();
-    if (!valid) return;
-    const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
-    float wx = red[0][r][c];
-    if (a.bias) wx = wx + p_bias;
-    const float xn = a.scale ? bn_affine(wx, p_sc, p_sh) : wx;
-    float drive = REC ? xn + red[1][r][c] : xn;                              // snns.py:572 / 720
-    if (ADAPT) {
-        const float be = clampf(p_be, SP_BETA_LO, SP_BETA_HI), pa = clampf(p_a, SP_A_LO, SP_A_HI),
-                    pb = clampf(p_b, SP_B_LO, SP_B_HI);
-        const float w = (be * w_prev + pa * u) + pb * s;                     // snns.py:718 / 438
-        drive = drive - w;
-        a.w[o] = w;
-    }
-    u = al * (u - s) + oma * drive;                                          // snns.py:572 / 719 / 297 / 439
-    const bool spike = (u - a.theta) > 0.0f;                                 // snns.py:29
-    a.u[o] = u;
-    a.s_out[o] = spike ? 1.0f : 0.0f;
-    if (a.s16_out) a.s16_out[o] = spike ? (uint16_t)0x3F80u : (uint16_t)0u;  // bf16 1.0 / 0.0
-    if (spike && a.spike_count) atomicAdd(a.spike_count + h, 1u);
+    if (valid) stream_pointwise<ADAPT, REC>(a, pc, red[0][r][c], red[1][r][c], u, w, s, o, h);
 }
 
 // ---- readout: one workgroup per batch row, 16 waves; a wave takes groups of RO_CG classes, lanes stride over K
@@ -236,8 +199,7 @@ __global__ __launch_bounds__(RO_NT) void stream_step_readout_kernel(int K, int C
     // thread = class operands, asked for now
     const bool act = tid < C;
     const int cc = act ? tid : 0;
-    const float p_al = alpha[cc], p_bias = bias ? bias[cc] : 0.f;
-    const float p_sc = scale ? scale[cc] : 1.f, p_sh = scale ? shift[cc] : 0.f;
+    const StreamColumn<false> pc = stream_column<false>(alpha, nullptr, nullptr, nullptr, bias, scale, shift, cc);
     const float u_prev = u_io[(size_t)b * C + cc], out_prev = out[(size_t)b * C + cc];
     if (act) row[tid] = 0.f;
     constexpr int RO_CG = ro_group(VEC), C_STEP = (RO_NT / 64) * RO_CG;
@@ -274,50 +236,16 @@ __global__ __launch_bounds__(RO_NT) void stream_step_readout_kernel(int K, int C
         }
         __syncthreads();
     }
-    // thread = class: the recurrence of readout_fwd_kernel (cell.hip)
-    if (act) {
-        const float al = clampf(p_al, SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;
-        float wx = row[tid];
-        if (bias) wx = wx + p_bias;
-        const float xn = scale ? bn_affine(wx, p_sc, p_sh) : wx;
-        const float u = al * u_prev + oma * xn;                              // snns.py:822
-        u_io[(size_t)b * C + tid] = u;
-        row[tid] = u;
-    }
-    __syncthreads();
-    // one thread: the softmax in the arithmetic (and the order) of the whole-sequence kernel's thread = time phase
-    if (tid == 0) {
-        const float den = ro_softmax_row(row, C);
-        for (int c = 0; c < C; ++c) row[c] = row[c] / den;
-    }
-    __syncthreads();
-    if (act) out[(size_t)b * C + tid] = out_prev + row[tid];                 // snns.py:823
+    stream_readout_tail(row, act, b, C, row[cc], pc, bias != nullptr, scale != nullptr, u_prev, out_prev,
+                        u_io, out);
 }
 
-template <int RT, bool VEC>
-void launch_step(int kind, const StepArgs& a, dim3 grid, hipStream_t st) {
-    switch (kind) {
-        case SPARCH_KIND_LIF: hipLaunchKernelGGL((stream_step_kernel<RT, false, false, VEC>), grid, dim3(SS_NT), 0, st, a); break;
-        case SPARCH_KIND_ADLIF: hipLaunchKernelGGL((stream_step_kernel<RT, true, false, VEC>), grid, dim3(SS_NT), 0, st, a); break;
-        case SPARCH_KIND_RLIF: hipLaunchKernelGGL((stream_step_kernel<RT, false, true, VEC>), grid, dim3(SS_NT), 0, st, a); break;
-        default: hipLaunchKernelGGL((stream_step_kernel<RT, true, true, VEC>), grid, dim3(SS_NT), 0, st, a); break;
-    }
-}
 template <bool VEC>
-void launch_step_rows(int RT, int kind, const StepArgs& a, dim3 grid, hipStream_t st) {
-    switch (RT) {
-        case 1: launch_step<1, VEC>(kind, a, grid, st); break;
-        case 2: launch_step<2, VEC>(kind, a, grid, st); break;
-        case 4: launch_step<4, VEC>(kind, a, grid, st); break;
-        case 8: launch_step<8, VEC>(kind, a, grid, st); break;
-        default: launch_step<16, VEC>(kind, a, grid, st); break;
-    }
-}
-
-bool all16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (p && !aligned16(p)) return false;
-    return true;
+void launch_step(int RT, int kind, const StreamArgs& a, dim3 grid, hipStream_t st) {
+    stream_dispatch(RT, kind, [&](auto rt, auto adapt, auto rec) {
+        hipLaunchKernelGGL((stream_step_kernel<decltype(rt)::value, decltype(adapt)::value, decltype(rec)::value, VEC>), grid,
+                           dim3(SS_NT), 0, st, a);
+    });
 }
 
 }  // namespace
@@ -328,30 +256,18 @@ extern "C" int sparch_stream_step_fwd(int kind, int B, int K, int H, int ld, int
                                       const float* vmask_t, float* u, float* w, const float* s_in, float* s_out,
                                       uint16_t* s16_out, float theta, uint32_t* spike_count, void* stream) {
     SPARCH_ENTER();
-    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF && kind != SPARCH_KIND_RLIF && kind != SPARCH_KIND_RADLIF)
-        return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_ADLIF || kind == SPARCH_KIND_RADLIF;
-    const bool rec = kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF;
-    if (in_dtype != 0 && in_dtype != 1) return SPARCH_EINVAL;
-    if (B <= 0 || K <= 0 || H <= 0 || ld < H || ldx < K) return SPARCH_EINVAL;
-    if (!x || !W || !alpha || !u || !s_in || !s_out) return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w)) return SPARCH_EINVAL;
-    if (rec && (!vmask_t || s_in == s_out)) return SPARCH_EINVAL;  // every workgroup reads all of s_in
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!all16({W, vmask_t, u, w, s_in, s_out, s16_out})) return SPARCH_EALIGN;
-    StepArgs g{};
+    StreamArgs g{};
     g.B = B; g.K = K; g.H = H; g.ld = ld; g.ldx = ldx; g.in_u8 = in_dtype;
     g.x = x; g.W = W; g.bias = bias; g.scale = scale; g.shift = shift;
-    g.alpha = alpha; g.beta = beta; g.a = a; g.b = b; g.vmask_t = vmask_t;
-    g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out;
-    g.theta = theta; g.spike_count = spike_count;
-    // the smallest row tile that holds the batch: fewer accumulators and LDS reads for the few-row stream
-    const int RT = B >= 9 ? 16 : B >= 5 ? 8 : B >= 3 ? 4 : B;
+    g.alpha = alpha; g.beta = beta; g.a = a; g.b = b; g.V = vmask_t;
+    g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out; g.theta = theta; g.spike_count = spike_count;
+    if (const int rc = stream_step_check(kind, in_dtype, g, false)) return rc;
+    const int RT = stream_row_tile(B);
     const dim3 grid(cdiv(H, SS_COLS), cdiv(B, RT));
-    if (grid.y > 65535u) return SPARCH_EINVAL;
     // 16-byte weight loads where every row of W and of vmask_t is aligned, scalar ones otherwise
-    if ((K & 3) == 0 && (!rec || (ld & 3) == 0)) launch_step_rows<true>(RT, kind, g, grid, (hipStream_t)stream);
-    else launch_step_rows<false>(RT, kind, g, grid, (hipStream_t)stream);
+    const bool rec = kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF;
+    if ((K & 3) == 0 && (!rec || (ld & 3) == 0)) launch_step<true>(RT, kind, g, grid, (hipStream_t)stream);
+    else launch_step<false>(RT, kind, g, grid, (hipStream_t)stream);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -360,10 +276,7 @@ extern "C" int sparch_stream_step_readout(int B, int K, int C, const float* x, i
                                           const float* bias, const float* scale, const float* shift,
                                           const float* alpha, float* u, float* out, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || K <= 0 || C <= 0 || C > 256 || ldx < K) return SPARCH_EINVAL;
-    if (!x || !W || !alpha || !u || !out) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    if (!aligned16(W)) return SPARCH_EALIGN;
+    if (const int rc = stream_readout_check(B, K, C, x, ldx, W, false, 0, scale, shift, alpha, u, out)) return rc;
     if ((K & 3) == 0)
         hipLaunchKernelGGL(stream_step_readout_kernel<true>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, K, C, x, ldx,
                            W, bias, scale, shift, alpha, u, out);
