@@ -752,6 +752,53 @@ int sparch_gru_bwd(int B, int dirs, int T, int H, const float* g_out, const floa
 int sparch_gate_step(int mode, int B, int dirs, int T, int H, int t, const float* const* in,
                      float* const* out, float p_drop, uint64_t seed, void* stream);
 
+/* Streaming, ONE time step of a baseline layer with the state carried by the caller (csrc/streamann.hip): the
+ * projection(s), the recurrent product(s) and the cell in one launch, two for a GRU layer.  The whole-sequence entry
+ * points above start from y = 0 and return no state; a stream stepped here from a zero state computes what they do.
+ * sparch_ann_stream_step — one hidden layer, all B rows, any B, K, H >= 1 (rows in tiles over grid.y):
+ *   cell, phase   SPARCH_CELL_MLP / _RNN / _LIGRU with phase 0; SPARCH_CELL_GRU with phase 1 (z, r, r * y) then 2
+ *   act           SPARCH_ACT_* of the MLP and RNN cells (the gated cells have their own; ignored there)
+ *   x (B,K), row stride ldx >= K   the step's input, fp32, read where it lies; or NULL: the projections are `pre`
+ *   W, bias, scale, shift, pre, V   HOST arrays of 3 device pointers each, one slot per gate: 0 the candidate (W, V;
+ *               the only one of MLP and RNN), 1 the update gate (Wz, Vz), 2 the reset gate (Wr, Vr).  A NULL array
+ *               means three NULL slots.  W? (H,K) and V? (H,H) contiguous AS STORED by the modules (row h of V? is
+ *               what y V?^T needs: no transpose, no mask); bias (H) or NULL; scale / shift (H) the folded eval
+ *               BatchNorm, both or neither; pre? (B,H) contiguous, the already normalised projection (LayerNorm
+ *               layers: GEMM, sparch_layernorm_fwd, then this call with x == NULL).  A launch reads the slots of its
+ *               gates only: MLP, RNN, GRU phase 2 slot 0; LiGRU slots 0, 1; GRU phase 1 slots 1, 2.
+ *   y_in (B,H)  the previous state, y_out (B,H) the new one, z and ry (B,H) the GRU's update gate and r * y between
+ *               its phases (phase 1 writes, phase 2 reads them); all fp32 with row stride ld >= H.  Columns >= H of a
+ *               row are never written.  MLP: y_in is not read.
+ *   MLP y = act(p)   RNN y' = act(p + y V^T)   LiGRU z = sigm(pz + y Vz^T), c = relu(p + y V^T), y' = z y + (1 - z) c
+ *   GRU 1: z = sigm(pz + y Vz^T), r = sigm(pr + y Vr^T), ry = r y      2: c = tanh(p + ry V^T), y' = z y + (1 - z) c
+ *   with p? = (x W?^T + bias) * scale + shift, or pre?.  Dot products are fp32 FMA chains (64 lane partials, butterfly).
+ * Every workgroup of a recurrent launch reads ALL of y_in (GRU phase 2: all of ry), so what the launch writes must be
+ * another buffer: y_out == y_in (RNN, LiGRU), z or ry == y_in or each other (GRU 1), y_out == ry or z (GRU 2) are
+ * SPARCH_EINVAL, as are an unknown cell / phase / act, a non-positive size, ld < H, ldx < K, a missing operand of the
+ * launch's gates, scale without shift, more than 65535 row tiles.  After those: W?, V?, y_in, y_out, z, ry 16-byte
+ * aligned (else SPARCH_EALIGN).  Nothing waits inside a launch; nothing is launched by a refused call.
+ * sparch_ann_stream_readout — the readout's step (ReadoutLayerANN, anns.py:644-665), one workgroup per batch row:
+ *   acc[b,:] += softmax(y[b,:]) over the K <= 4096 features (y (B,K) row stride ldy; acc (B,K) contiguous, in place:
+ *   ONE sequential sum over the steps, in time order), then out[b,:] = norm(acc[b,:] W^T + bias) for C <= 256 classes:
+ *   the network's answer as if the sequence ended here.  W (C,K); norm SPARCH_RO_NORM_NONE, _AFFINE (p0 = scale, p1 =
+ *   shift: the folded eval BatchNorm) or _LAYERNORM over the C outputs (p0 = gamma, p1 = beta, eps).  SPARCH_EINVAL: a
+ *   non-positive size, K > 4096, C > 256, ldy < K, a NULL y / acc / W / out, an unknown norm, a norm without both of
+ *   p0 and p1; then W, acc 16-byte aligned (else SPARCH_EALIGN).                                                  */
+#define SPARCH_CELL_MLP 0
+#define SPARCH_CELL_RNN 1
+#define SPARCH_CELL_LIGRU 2
+#define SPARCH_CELL_GRU 3
+#define SPARCH_RO_NORM_NONE 0
+#define SPARCH_RO_NORM_AFFINE 1
+#define SPARCH_RO_NORM_LAYERNORM 2
+int sparch_ann_stream_step(int cell, int phase, int act, int B, int K, int H, int ld, const float* x, int ldx,
+                           const float* const* W, const float* const* bias, const float* const* scale,
+                           const float* const* shift, const float* const* pre, const float* const* V,
+                           const float* y_in, float* y_out, float* z, float* ry, void* stream);
+int sparch_ann_stream_readout(int B, int K, int C, const float* y, int ldy, float* acc, const float* W,
+                              const float* bias, int norm, const float* p0, const float* p1, float eps, float* out,
+                              void* stream);
+
 /* ---- f-2: optimizer step on the device (replaces torch.optim.Adam.step, exp.py:89, 377) ----------
  * One launch for the whole parameter list; arithmetic identical, operation by operation, to
  * torch.optim.Adam's default path (see optim.hip).  `params`, `grads`, `exp_avg`, `exp_avg_sq` are HOST

@@ -11,5 +11,6 @@ from .functional import (augment_padded, bin_events, check_status, compute_dtype
 from .snns import (SNN, LIFLayer, RLIFLayer, RadLIFLayer, ReadoutLayer,  # noqa: F401
                    SpikeFunctionBoxcar, adLIFLayer)
 from .streaming import StreamingFbank, StreamingSNN  # noqa: F401
+from .streaming_ann import StreamingANN  # noqa: F401
 
 __version__ = "0.1.0"

@@ -145,6 +145,9 @@ PROTOTYPES = {
     "sparch_gru_bwd": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_float, c_uint64, P, P, P, P, P, P,
                                P, c_size_t, P, c_int, P]),
     "sparch_gate_step": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_float, c_uint64, P]),
+    "sparch_ann_stream_step": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P,
+                                       P, P, P, P, P]),
+    "sparch_ann_stream_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, c_int, P, P, c_float, P, P]),
     "sparch_bn_bwd_apply_planes": (c_int, [c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
     "sparch_gemm6_nn_pp": (c_int, [c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int, P, c_int]),
     "sparch_gemm_spike16_tn_ap": (c_int, [c_int, c_int, c_int, P, P, c_int, P, c_int, c_float, P, c_int, c_int, c_int,

@@ -27,6 +27,13 @@ Beside them, in the same turn-taking, the event-driven fused step `StreamingSNN(
 --densities (default 0.02 0.05 0.15; the hidden layers fire what the network at its initial parameters fires: every
 row carries the measured firing rate per layer).  A `sparse_vs_fused` line per (B, density) claims a win only where the
 sparse rows' MAX over the streams lies below the dense fused rows' MIN of the same call.
+
+--ann: the non-spiking baselines of the same shape (MLP, RNN, LiGRU, GRU [1024, 1024, 35] on 700 channels, BatchNorm)
+through `StreamingANN` (csrc/streamann.hip) at Tc = 1, eager and replayed, --batches 1 8 32 256.  Per (cell, B), taken
+stream by stream in turn in one call: the two StreamingANN modes, the fused RadLIF stream eager and replayed, and the
+whole-sequence eval forward `net(x)` at T = 250 of the same baseline — what a live stream had to re-run per step before
+StreamingANN.  us per step as mean (min - max) over `--streams` streams after two warm-up streams; `lib_calls_per_step`
+counted on the host as above.  No pass mark.  --out defaults to profiles/stream_bench_ann.jsonl.
 """
 import argparse
 import json
@@ -51,11 +58,13 @@ def main():
     ap.add_argument("--channels", type=int, default=700)
     ap.add_argument("--densities", type=float, nargs="+", default=[0.02, 0.05, 0.15],
                     help="--fused: input densities of the Tc = 1 block (the other rows run at 0.05)")
+    ap.add_argument("--ann", action="store_true", help="the non-spiking baselines through StreamingANN (see above)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "stream_bench_fused.jsonl" if args.fused else "stream_bench.jsonl")
+        name = "stream_bench_ann.jsonl" if args.ann else "stream_bench_fused.jsonl" if args.fused else "stream_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.batches is None:
-        args.batches = [1, 8, 32, 256] if args.fused else [1, 32, 256]
+        args.batches = [1, 8, 32, 256] if (args.fused or args.ann) else [1, 32, 256]
 
     import torch
 
@@ -160,6 +169,60 @@ def main():
               "sparse_graph_wins": bool(max(ms["sparse+graph"]) < min(ms["fused+graph"])),
               "sparse_loses": bool(min(ms["sparse"]) > max(ms["fused"])),
               "sparse_graph_loses": bool(min(ms["sparse+graph"]) > max(ms["fused+graph"]))})
+
+    def ann_rows(kind, B, x):
+        """Tc = 1 on the `kind` baseline of the same shape: StreamingANN eager and replayed, the fused RadLIF stream
+        eager and replayed, and the whole-sequence eval forward net(x) of the baseline (what there was before
+        StreamingANN), one stream / forward each in turn, `--streams` times after two warm-up turns."""
+        from sparch_amd.anns import ANN
+        torch.manual_seed(1234)
+        ann = ANN((B, None, C), args.sizes, ann_type=kind, normalization="batchnorm").to(dev).eval()
+        chunks = [x[:, t0:t0 + 1] for t0 in range(T)]        # read where they lie
+        sts = {"eager": sparch_amd.StreamingANN(ann, B), "graph": sparch_amd.StreamingANN(ann, B, graph=True),
+               "radlif_fused": sparch_amd.StreamingSNN(net, B, fused=True),
+               "radlif_fused+graph": sparch_amd.StreamingSNN(net, B, graph=True, fused=True)}
+
+        def stream(st):
+            out = None
+            for c in chunks:
+                out = st.step(c)
+            return out
+
+        def whole():
+            with torch.no_grad():
+                return ann(x)
+
+        for st in sts.values():
+            st.reset()
+            stream(st)
+            stream(st)
+        whole(), whole()
+        Fn.check_status(dev)
+        calls = {m: count_calls(lambda st=st: st.step(chunks[0])) for m, st in sts.items() if not st.graph}
+        us, whole_ms = {m: [] for m in sts}, []
+        for _ in range(args.streams):
+            for m, st in sts.items():
+                us[m].append(1e3 * timed(lambda st=st: stream(st), 1) / T)
+            whole_ms.append(timed(whole, 1))
+        Fn.check_status(dev)
+        for m, st in sts.items():
+            v = us[m]
+            graphs = getattr(st, "_fg", None) if m.startswith("radlif") else st._g
+            emit({"what": "ann_stream" if not m.startswith("radlif") else "radlif_stream", "cell": kind, "B": B, "Tc": 1,
+                  "mode": m, "us_per_step": sum(v) / len(v), "us_per_step_min": min(v), "us_per_step_max": max(v),
+                  "us_per_step_streams": v, "lib_calls_per_step": calls.get(m),
+                  "graph_replayed": (bool(graphs) and all(g["replays"] > 0 for g in graphs.values())) if st.graph else None})
+        emit({"what": "ann_whole_forward", "cell": kind, "B": B, "T": T, "ms_per_forward": sum(whole_ms) / len(whole_ms),
+              "ms_per_forward_min": min(whole_ms), "ms_per_forward_max": max(whole_ms), "ms_per_forward_calls": whole_ms,
+              "us_per_step_equivalent": 1e3 * sum(whole_ms) / len(whole_ms) / T,
+              "whole_forward_over_eager_step": sum(whole_ms) / len(whole_ms) * 1e3 / (sum(us["eager"]) / len(us["eager"]))})
+
+    if args.ann:
+        for kind in ("MLP", "RNN", "LiGRU", "GRU"):
+            for B in args.batches:
+                g = torch.Generator().manual_seed(4321 + B)
+                ann_rows(kind, B, (torch.rand(B, T, C, generator=g) < 0.05).float().to(dev))
+        args.batches = []
 
     for B in args.batches:
         g = torch.Generator().manual_seed(4321 + B)
