@@ -608,6 +608,35 @@ int sparch_events_gather_bin(const void* times, int times_dtype, const uint16_t*
                              int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
                              uint32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream);
 
+/* f-3  sparch_events_gather_bin with a per-sample augmentation of the events in front of the bin: same
+ *      store, outputs, workspace (sparch_events_gather_bin_workspace_bytes) and return codes.  aug is a
+ *      device table (batch, SPARCH_EVAUG_FIELDS) fp32, row b for batch row b:
+ *        0     unit shift d (integer-valued, |d| <= 65535)
+ *        1, 2  time scale a (finite, > 0) and offset c (seconds, finite)
+ *        3     drop probability p in [0, 1)
+ *        4, 5  time mask [m0, m1) in transformed seconds, empty when m1 <= m0
+ *        6, 7  unit band [k0, k1) in shifted units (integer-valued), empty when k1 <= k0
+ *      Event i of sample s = idx[b] sits at position j = i - offsets[s] of its sample.  In this order:
+ *        1. u = units[i]; the stored marker 0xFFFF is never placed, whatever the shift;
+ *        2. r = the 24-bit uniform of the dropout hash (see "Dropout") of (seed, ((uint64)b << 32) | (uint32)j);
+ *           the event is removed when r < p, compared in fp32 (b enters, so a sample drawn twice into a
+ *           batch gets two masks);
+ *        3. t' = fp32(fp32(a * t) + c), two roundings and no FMA, t widened exactly; u' = u + d;
+ *        4. the event is removed when m0 <= t' < m1 or k0 <= u' < k1;
+ *        5. bin and drop rule of sparch_events_gather_bin (the one shared device function) on (t', u');
+ *        6. otherwise 1 is added at (bin, u').
+ *      *n_dropped counts every event of the batch that was read and not placed (steps 1, 2, 4 and 5), once.
+ *      With a > 0, t' is non-decreasing in t, so `sorted` keeps its meaning.  The table is device data: the
+ *      caller validates it.  A row with a <= 0 is a wrong `sorted` promise (events may be lost); no row, however
+ *      wrong, makes the kernel read or write out of bounds.  seed is used as given (no SPARCH_SEED_IN_MEMORY). */
+#define SPARCH_EVAUG_FIELDS 8
+int sparch_events_gather_bin_aug(const void* times, int times_dtype, const uint16_t* units,
+                                 const long long* offsets, const long long* labels, long long n_store,
+                                 const long long* idx, int batch, int nb_steps, int nb_units, double max_time,
+                                 int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
+                                 uint32_t* n_dropped, void* workspace, size_t workspace_bytes,
+                                 const float* aug, uint64_t seed, void* stream);
+
 /* f-3  A batch of HD / SC features from a device-resident audio store (every clip of a split in one flat
  *      sample array, uploaded once) and a device list of clip indices.
  *      Store: samples (dtype 0 = fp32 in [-1,1], 1 = int16 PCM scaled by 2^-15 on load), starts (n_store,

@@ -114,6 +114,8 @@ PROTOTYPES = {
     "sparch_events_gather_bin_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sparch_events_gather_bin": (c_int, [P, c_int, P, P, P, c_longlong, P, c_int, c_int, c_int, c_double, c_int,
                                          P, P, P, P, P, P, c_size_t, P]),
+    "sparch_events_gather_bin_aug": (c_int, [P, c_int, P, P, P, c_longlong, P, c_int, c_int, c_int, c_double, c_int,
+                                             P, P, P, P, P, P, c_size_t, P, c_uint64, P]),
     "sparch_audio_gather_fbank": (c_int, [P, c_int, P, P, P, c_longlong, P, c_int, c_int, c_int, P, P, P]),
     "sparch_audio_gather_augment": (c_int, [P, c_int, P, P, P, c_longlong, P, c_int, c_int, P, c_float, c_float,
                                             c_uint64, c_int, P, P, P, P]),

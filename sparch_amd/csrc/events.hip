@@ -9,7 +9,10 @@
 // events (and negative times / out-of-range units) are counted in *n_dropped and skipped.
 // Edges are evaluated in fp64 exactly as np.linspace does (start + j*step, last edge = stop).
 // sparch_bin_events accumulates with global float atomics of integer values: exact and order-independent.
-// sparch_events_gather_bin (below) builds a batch from a device-resident store with counters in LDS instead.
+// sparch_events_gather_bin (below) builds a batch from a device-resident store with counters in LDS instead;
+// sparch_events_gather_bin_aug is the same kernel with a per-sample transform of (t, u) in front of the bin.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -164,13 +167,46 @@ __device__ __forceinline__ void gb_store_segment(const unsigned* tile, int cw, i
     }
 }
 
-template <typename TT>
+// ---- per-sample augmentation of the events in front of event_bin (sparch_events_gather_bin_aug).  GbPlain is the
+// unaugmented kernel: every `if constexpr (kAug)` below falls away and its code is what it was.  GbAugment carries
+// the table; a workgroup reads the row of its batch row once.  With a > 0 the transformed time is a non-decreasing
+// function of t (one fp32 product, one fp32 sum: both monotone), so a sorted sample stays sorted and the search
+// keeps working on the transformed times.
+struct GbPlain {};
+struct GbAugment {
+    const float* table;   // (batch, SPARCH_EVAUG_FIELDS) fp32
+    uint64_t seed;
+};
+struct GbAugRow {
+    int d;
+    float a, c, p, m0, m1, k0, k1;
+    uint64_t seed, row;
+    __device__ __forceinline__ GbAugRow(const GbAugment& g, int b) : seed(g.seed), row((uint64_t)(uint32_t)b << 32) {
+        const float* r = g.table + (size_t)b * SPARCH_EVAUG_FIELDS;
+        d = (int)fminf(fmaxf(r[0], -65536.0f), 65536.0f);   // the host checks |d| <= 65535; a bad row stays harmless
+        a = r[1]; c = r[2]; p = r[3]; m0 = r[4]; m1 = r[5]; k0 = r[6]; k1 = r[7];
+    }
+    // two roundings, never an FMA: restatable with any fp32 arithmetic
+    __device__ __forceinline__ float time(float t) const { return __fadd_rn(__fmul_rn(a, t), c); }
+    // event j of the sample, stored unit u, transformed time tp: is it removed before binning?  The stored marker
+    // 0xFFFF, the drop draw (the dropout hash of common.h on (seed, row b : position j), removed iff uniform < p),
+    // the time mask on tp and the unit band on u + d (|u + d| < 2^18: exact as a float).
+    __device__ __forceinline__ bool removed(int u, uint32_t j, float tp) const {
+        const float up = (float)(u + d);
+        // (p is the same for the whole workgroup: no draw is computed for a row that drops nothing)
+        return u == 0xFFFF || (p > 0.0f && keep_scale(seed, row | j, p, 1.0f) == 0.0f) || (tp >= m0 && tp < m1) ||
+               (up >= k0 && up < k1);
+    }
+};
+
+template <typename TT, typename AUG>
 __global__ __launch_bounds__(GB_NT) void gather_bin_kernel(
     const TT* __restrict__ times, const uint16_t* __restrict__ units, const long long* __restrict__ offsets,
     const long long* __restrict__ labels, long long n_store, const long long* __restrict__ idx, int nb_steps,
     int nb_units, int ldp, double max_time, int sorted, GbTile g, uint16_t* __restrict__ plane,
     float* __restrict__ dense, uint8_t* __restrict__ counts, long long* __restrict__ y,
-    unsigned* __restrict__ partial) {
+    unsigned* __restrict__ partial, AUG aug) {
+    constexpr bool kAug = !std::is_same<AUG, GbPlain>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned gb_lds[];
     unsigned* const tile = gb_lds + GB_HDR / 4;
     const int tid = threadIdx.x;
@@ -188,6 +224,10 @@ __global__ __launch_bounds__(GB_NT) void gather_bin_kernel(
     const bool valid = s >= 0 && s < n_store;    // an index outside the store: an empty sample, label -1
     const long long e0 = valid ? offsets[s] : 0, e1 = valid ? offsets[s + 1] : 0;
     if (y && rem == 0 && tid == 0) y[b] = valid ? labels[s] : -1;
+    const auto xf = [&] { if constexpr (kAug) return GbAugRow(aug, b); else return GbPlain(); }();
+    auto time_at = [&](long long i) {
+        if constexpr (kAug) return xf.time(gb_time(times, i)); else return gb_time(times, i);
+    };
 
     {   // zero the header and the tile
         const int n4 = (GB_HDR + (r1 - r0) * cw * 4) / 16;   // cw % 8 == 0
@@ -209,7 +249,7 @@ __global__ __launch_bounds__(GB_NT) void gather_bin_kernel(
                 const long long n = hi[q] - lo[q];
                 stride[q] = (n + GB_NT - 1) / GB_NT;
                 const long long p = lo[q] + (long long)(tid + 1) * stride[q] - 1;
-                below[q] = n > 0 && p < hi[q] && event_bin(gb_time(times, p), edges) < target[q];
+                below[q] = n > 0 && p < hi[q] && event_bin(time_at(p), edges) < target[q];
             }
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
@@ -235,7 +275,7 @@ __global__ __launch_bounds__(GB_NT) void gather_bin_kernel(
 #pragma unroll
         for (int j = 0; j < GB_UNROLL; ++j) {
             const long long i = base + j * GB_NT + tid;
-            t[j] = i < eb ? gb_time(times, i) : -1.0f;
+            t[j] = i < eb ? time_at(i) : -1.0f;
             u[j] = i < eb ? (int)units[i] : -1;
         }
 #pragma unroll
@@ -243,7 +283,12 @@ __global__ __launch_bounds__(GB_NT) void gather_bin_kernel(
             if (base + j * GB_NT + tid >= eb) continue;
             const int bin = event_bin(t[j], edges);
             if (bin < r0 || (bin >= r1 && !last)) continue;   // another row slab's event
-            if (event_dropped(t[j], bin, u[j], nb_steps, nb_units)) {
+            bool gone = false;
+            if constexpr (kAug) {
+                gone = xf.removed(u[j], (uint32_t)(base + j * GB_NT + tid - e0), t[j]);
+                u[j] += xf.d;
+            }
+            if (gone || event_dropped(t[j], bin, u[j], nb_steps, nb_units)) {
                 dropped += cs == 0 ? 1u : 0u;
                 continue;
             }
@@ -292,19 +337,19 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const unsigned* __res
     if (threadIdx.x == 0) *total = acc;
 }
 
-template <typename TT>
+template <typename TT, typename AUG>
 int gb_launch(const void* times, const uint16_t* units, const long long* offsets, const long long* labels,
               long long n_store, const long long* idx, int batch, int nb_steps, int nb_units, int ldp, double max_time,
               int sorted, const GbTile& g, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
-              unsigned* partial, hipStream_t st) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_bin_kernel<TT>),
+              unsigned* partial, AUG aug, hipStream_t st) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_bin_kernel<TT, AUG>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS_BUDGET);
     if (attr != hipSuccess) { sparch_note_hip_error((int)attr); return SPARCH_ELAUNCH; }
     const size_t lds = (size_t)GB_HDR + (size_t)g.rows * g.cw * 4;
     const unsigned grid = (unsigned)batch * (unsigned)(g.n_rslabs * g.n_cslabs);
-    hipLaunchKernelGGL(gather_bin_kernel<TT>, dim3(grid), dim3(GB_NT), lds, st, static_cast<const TT*>(times), units,
+    hipLaunchKernelGGL((gather_bin_kernel<TT, AUG>), dim3(grid), dim3(GB_NT), lds, st, static_cast<const TT*>(times), units,
                        offsets, labels, n_store, idx, nb_steps, nb_units, ldp, max_time, sorted, g, plane, dense,
-                       counts, y, partial);
+                       counts, y, partial, aug);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -352,12 +397,12 @@ extern "C" size_t sparch_events_gather_bin_workspace_bytes(int batch, int nb_ste
     return (size_t)batch * g.n_rslabs * g.n_cslabs * sizeof(uint32_t);
 }
 
-extern "C" int sparch_events_gather_bin(const void* times, int times_dtype, const uint16_t* units,
-                                        const long long* offsets, const long long* labels, long long n_store,
-                                        const long long* idx, int batch, int nb_steps, int nb_units, double max_time,
-                                        int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
-                                        uint32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream) {
-    SPARCH_ENTER();
+template <typename AUG>
+static int gb_entry(const void* times, int times_dtype, const uint16_t* units, const long long* offsets,
+                    const long long* labels, long long n_store, const long long* idx, int batch, int nb_steps,
+                    int nb_units, double max_time, int sorted, uint16_t* plane, float* dense, uint8_t* counts,
+                    long long* y, uint32_t* n_dropped, void* workspace, size_t workspace_bytes, AUG aug,
+                    void* stream) {
     if (!gb_shape_ok(batch, nb_steps, nb_units) || !(max_time > 0.0) || (times_dtype != 0 && times_dtype != 1) ||
         n_store <= 0 || !times || !units || !offsets || !idx || (y && !labels) || (!plane && !dense && !counts))
         return SPARCH_EINVAL;
@@ -372,13 +417,36 @@ extern "C" int sparch_events_gather_bin(const void* times, int times_dtype, cons
     hipStream_t st = (hipStream_t)stream;
     const int rc = times_dtype == 0
         ? gb_launch<float>(times, units, offsets, labels, n_store, idx, batch, nb_steps, nb_units, ldp, max_time,
-                           sorted, g, plane, dense, counts, y, partial, st)
+                           sorted, g, plane, dense, counts, y, partial, aug, st)
         : gb_launch<_Float16>(times, units, offsets, labels, n_store, idx, batch, nb_steps, nb_units, ldp, max_time,
-                              sorted, g, plane, dense, counts, y, partial, st);
+                              sorted, g, plane, dense, counts, y, partial, aug, st);
     if (rc != SPARCH_OK) return rc;
     if (n_dropped) {
         hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, (int)n_wg, n_dropped);
         SPARCH_CHECK_LAUNCH();
     }
     return SPARCH_OK;
+}
+
+extern "C" int sparch_events_gather_bin(const void* times, int times_dtype, const uint16_t* units,
+                                        const long long* offsets, const long long* labels, long long n_store,
+                                        const long long* idx, int batch, int nb_steps, int nb_units, double max_time,
+                                        int sorted, uint16_t* plane, float* dense, uint8_t* counts, long long* y,
+                                        uint32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream) {
+    SPARCH_ENTER();
+    return gb_entry(times, times_dtype, units, offsets, labels, n_store, idx, batch, nb_steps, nb_units, max_time,
+                    sorted, plane, dense, counts, y, n_dropped, workspace, workspace_bytes, GbPlain(), stream);
+}
+
+extern "C" int sparch_events_gather_bin_aug(const void* times, int times_dtype, const uint16_t* units,
+                                            const long long* offsets, const long long* labels, long long n_store,
+                                            const long long* idx, int batch, int nb_steps, int nb_units,
+                                            double max_time, int sorted, uint16_t* plane, float* dense,
+                                            uint8_t* counts, long long* y, uint32_t* n_dropped, void* workspace,
+                                            size_t workspace_bytes, const float* aug, uint64_t seed, void* stream) {
+    SPARCH_ENTER();
+    if (!aug) return SPARCH_EINVAL;
+    return gb_entry(times, times_dtype, units, offsets, labels, n_store, idx, batch, nb_steps, nb_units, max_time,
+                    sorted, plane, dense, counts, y, n_dropped, workspace, workspace_bytes, GbAugment{aug, seed},
+                    stream);
 }

@@ -21,6 +21,11 @@ but the indices of an epoch.  The index lists come from a torch DataLoader built
 per-sample loader, so the batches and the draws from torch's global generator are the same.  The events come
 from the `h5_file` hook, else from the pack file `{data_folder}/{dataset}_{split}.events.npz`
 (tools/pack_events.py; readable without h5py), else from the .h5 file.
+
+`augment=SPEC` (resident loader only; `event_augment.py`): every epoch draws one table row per sample — channel
+shift, time stretch and offset, event / window / band dropping — from a numpy generator seeded with
+(augment_seed, rank, epoch number), uploads the table beside the index lists, and the batch kernel applies row b to
+the events of batch row b while it bins them (`sparch_events_gather_bin_aug`).
 """
 import logging
 import os
@@ -31,6 +36,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from ..functional import EventStore, bin_events
 from ._index import _index_loader, _SampleIndices  # noqa: F401  (shared with the HD / SC loader)
+from .event_augment import draw_event_augmentation, parse_event_augment
 
 logger = logging.getLogger(__name__)
 
@@ -92,10 +98,17 @@ class ResidentEventLoader:
     them.  Iterating draws the epoch's index lists from a DataLoader over the sample numbers (so `len`, the
     short last batch, `.sampler` / `set_epoch` and the global generator behave as with the per-sample loader),
     uploads them in one copy and launches one kernel per batch.  `values=True` asks for dense fp32 batches (a
-    non-spiking network reads the values; a spiking one reads the bf16 plane the store serves when it can)."""
+    non-spiking network reads the values; a spiking one reads the bf16 plane the store serves when it can).
+    `augment` (a spec of `event_augment.parse_event_augment`, text or parsed): every `__iter__` draws the whole
+    epoch's table, one row per sample in the order the epoch serves them, from
+    `np.random.default_rng([augment_seed, rank, epoch_index])`, epoch_index counting the iterations from 0; the
+    table travels in one copy and each batch gets its slice.  Torch's global generator is not touched by it."""
 
-    def __init__(self, store, batch_size, nb_steps=100, shuffle=True, rank=0, world=1, seed=0, values=False):
+    def __init__(self, store, batch_size, nb_steps=100, shuffle=True, rank=0, world=1, seed=0, values=False,
+                 augment=None, augment_seed=0):
         self.store, self.batch_size, self.nb_steps, self.values = store, batch_size, nb_steps, values
+        self.augment = parse_event_augment(augment) if augment is not None else None
+        self.augment_seed, self.rank, self.epoch_index = int(augment_seed), int(rank), 0
         self.index_loader = _index_loader(_SampleIndices(len(store)), batch_size, shuffle, rank, world, seed)
         self.sampler = self.index_loader.sampler
         store.prepare(nb_steps)  # the one read-back the plane / fp32 decision needs: now, not in the first epoch
@@ -112,10 +125,21 @@ class ResidentEventLoader:
         if not lists:
             return
         flat = torch.cat(lists).to(self.store.device)
+        table = seed = scale = None
+        if self.augment is not None:
+            rng = np.random.default_rng([self.augment_seed, self.rank, self.epoch_index])
+            self.epoch_index += 1
+            table, seed = draw_event_augmentation(flat.numel(), self.augment, rng, self.store.nb_units,
+                                                  self.store.max_time)
+            table, scale = self.store.upload_augmentation(table), self.augment["scale"]
         at = 0
         for b in lists:
             n = b.numel()
-            x, y = self.store.batch(flat[at:at + n], self.nb_steps, values=self.values)
+            if table is None:
+                x, y = self.store.batch(flat[at:at + n], self.nb_steps, values=self.values)
+            else:
+                x, y = self.store.batch(flat[at:at + n], self.nb_steps, values=self.values,
+                                        augment=(table[at:at + n], seed), augment_scale=scale)
             at += n
             yield x, torch.tensor([self.nb_steps] * n), y
 
@@ -135,17 +159,24 @@ def _resident_store(dataset_name, data_folder, split, h5_file, device):
 
 
 def load_shd_or_ssc(dataset_name, data_folder, split, batch_size, nb_steps=100, shuffle=True, workers=0,
-                    h5_file=None, device="cuda", rank=0, world=1, seed=0, resident=None, values=False):
+                    h5_file=None, device="cuda", rank=0, world=1, seed=0, resident=None, values=False, augment=None,
+                    augment_seed=0):
     """spiking_datasets.py:90-140.  rank / world (data-parallel runs; not in the reference, which is single
     device): every rank reads the same file and draws a disjoint 1/world share of each epoch's (shuffled)
     sample order through a DistributedSampler — call `loader.sampler.set_epoch(e)` per epoch; `batch_size`
     is the PER-RANK batch.  resident: None reads SPARCH_EVENTS; unset or empty = the per-sample loader,
-    "resident" = a `ResidentEventLoader` (`values`: see there); anything else is a ValueError."""
+    "resident" = a `ResidentEventLoader` (`values`, `augment`, `augment_seed`: see there); anything else is a
+    ValueError, and so is `augment` with the per-sample loader."""
     if resident is None:
         resident = os.environ.get("SPARCH_EVENTS", "")
     if resident not in ("", "resident"):
         raise ValueError(f"SPARCH_EVENTS / resident: unknown value '{resident}' (unset or empty: per-sample "
                          "loader; 'resident': the split's events stay on the device)")
+    if augment is not None:
+        if resident != "resident":
+            raise ValueError("augment: events are augmented inside the resident store's batch kernel; it needs "
+                             "SPARCH_EVENTS=resident / resident='resident'")
+        augment = parse_event_augment(augment)
     if dataset_name not in ["shd", "ssc"]:
         raise ValueError(f"Invalid dataset name {dataset_name}")
     if split not in ["train", "valid", "test"]:
@@ -159,11 +190,16 @@ def load_shd_or_ssc(dataset_name, data_folder, split, batch_size, nb_steps=100, 
     if resident == "resident":
         store = _resident_store(dataset_name, data_folder, split, h5_file, device)
         logging.info(f"Number of examples in {split} set: {len(store)}")
-        loader = ResidentEventLoader(store, batch_size, nb_steps, shuffle, rank, world, seed, values=values)
+        loader = ResidentEventLoader(store, batch_size, nb_steps, shuffle, rank, world, seed, values=values,
+                                     augment=augment, augment_seed=augment_seed)
+        plane = store.serves_plane(nb_steps, augment["scale"] if augment is not None else None) and not values
         logging.info(f"Events of the {split} set are resident on {store.device}: {store.n_events} events, "
                      f"{store.nbytes / 2**20:.1f} MiB, times {'sorted' if store.sorted else 'unsorted'}, largest "
                      f"bin count {store.prepare(nb_steps)} ("
-                     f"{'bf16 plane' if store.serves_plane(nb_steps) and not values else 'dense fp32'} batches)")
+                     f"{'bf16 plane' if plane else 'dense fp32'} batches)")
+        if augment is not None:
+            logging.info(f"Events of the {split} set are augmented on the device: "
+                         + ", ".join(f"{k}={v}" for k, v in augment.items() if v))
         if store.dropped(nb_steps):
             logging.warning(f"{store.dropped(nb_steps)} events of the {split} set are outside the {nb_steps} x "
                             f"{store.nb_units} grid and dropped (the reference's sparse constructor rejects them)")

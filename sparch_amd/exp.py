@@ -9,7 +9,8 @@ The training step itself (exp.py:352-382) runs on the MI355X path: `sparch_amd.S
 What this build adds, not replaces:
   * --synthetic 1: batches of the dataset's shape generated on the fly (no dataset files needed);
     without it SHD/SSC go through sparch_amd.dataloaders.spiking_datasets (h5py event lists binned on the
-    device; with SPARCH_EVENTS=resident the whole split stays on the device and each batch is one kernel)
+    device; with SPARCH_EVENTS=resident the whole split stays on the device and each batch is one kernel;
+    --use_augm 1 with SPARCH_EVENTS_AUGMENT=SPEC then augments the training events inside that kernel)
     and HD/SC through sparch_amd.dataloaders.nonspiking_datasets (audio files decoded on the host);
   * hd / sc inputs are raw waveforms turned into 40-bin log-mel features ON THE DEVICE (the reference calls
     torchaudio's kaldi.fbank per clip on the CPU, nonspiking_datasets.py:96, 194): by the file loaders' collate
@@ -218,10 +219,15 @@ class Experiment:
             logging.basicConfig(level=level, format="%(message)s")
 
     def init_dataset(self):
+        events_augm = ""   # SHD / SSC with --use_augm: the spec of SPARCH_EVENTS_AUGMENT (dataloaders/event_augment.py)
         if self.dataset_name in _SPIKING_SETS:
             self.nb_inputs, self.nb_outputs, kind = 700, _SPIKING_SETS[self.dataset_name], "spiking"
-            if self.use_augm:
+            events_augm = os.environ.get("SPARCH_EVENTS_AUGMENT", "") if self.use_augm else ""
+            if self.use_augm and not events_augm:
                 logging.warning("\nWarning: Data augmentation not implemented for SHD and SSC.\n")
+            if events_augm and (self.synthetic or os.environ.get("SPARCH_EVENTS", "") != "resident"):
+                raise ValueError("--use_augm with SPARCH_EVENTS_AUGMENT set augments the events inside the resident "
+                                 "store's batch kernel: it needs SPARCH_EVENTS=resident and no --synthetic")
         elif self.dataset_name in _AUDIO_SETS:
             self.nb_inputs, self.nb_outputs, kind = 40, _AUDIO_SETS[self.dataset_name], "audio"
         else:
@@ -238,7 +244,8 @@ class Experiment:
                 def ld(split, shuffle):
                     return load_shd_or_ssc(self.dataset_name, self.data_folder, split, per_rank, nb_steps=100,
                                            shuffle=shuffle, device=self.device, rank=self.rank, world=self.world,
-                                           values=self.model_type in ("MLP", "RNN", "LiGRU", "GRU"))
+                                           values=self.model_type in ("MLP", "RNN", "LiGRU", "GRU"),
+                                           augment=events_augm if events_augm and split == "train" else None)
             else:
                 from .dataloaders.nonspiking_datasets import load_hd_or_sc  # exp.py:254-288
 
@@ -250,7 +257,7 @@ class Experiment:
             self.train_loader, self.valid_loader = ld("train", True), ld("valid", False)
             if self.dataset_name in ["sc", "ssc"]:
                 self.test_loader = ld("test", False)
-            if kind == "audio" and self.use_augm:  # exp.py:285-286
+            if self.use_augm and (kind == "audio" or events_augm):  # exp.py:285-286
                 logging.info("\nData augmentation is used\n")
             return
 

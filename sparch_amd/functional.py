@@ -1485,30 +1485,68 @@ class EventStore:
     def __len__(self):
         return self.n_samples
 
-    def _launch(self, idx, nb_steps, plane=None, dense=None, counts=None, y=None, n_dropped=None):
+    def upload_augmentation(self, table):
+        """A host augmentation table ((n, 8): `dataloaders.event_augment`) checked and copied to the store's device in
+        one copy; row slices of the result are what `gather(..., augment=(rows, seed))` takes without another check.
+        ValueError for a table the kernel's contract does not allow."""
+        from .dataloaders.event_augment import check_event_augmentation
+
+        if isinstance(table, torch.Tensor):
+            table = table.detach().cpu().numpy()
+        return torch.from_numpy(check_event_augmentation(table)).to(self.device)
+
+    def _augment_rows(self, augment, B):
+        """(device (B, 8) fp32 rows, seed) of a gather's `augment` argument.  A host table (numpy array, list, CPU
+        tensor) is validated and uploaded; a device tensor is one `upload_augmentation` has checked."""
+        from .dataloaders.event_augment import EVAUG_FIELDS
+
+        try:
+            table, seed = augment
+            seed = int(seed)
+        except (TypeError, ValueError):
+            raise ValueError("EventStore: augment must be a pair (table, seed)") from None
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"EventStore: augmentation seed {seed} outside 0..2^64-1")
+        if not (isinstance(table, torch.Tensor) and table.is_cuda):
+            table = self.upload_augmentation(table)
+        if (table.dtype != torch.float32 or tuple(table.shape) != (B, EVAUG_FIELDS) or not table.is_contiguous()):
+            raise ValueError(f"EventStore: the augmentation table must be contiguous float32 of shape ({B}, "
+                             f"{EVAUG_FIELDS}), found {table.dtype} {tuple(table.shape)}")
+        return table, seed
+
+    def _launch(self, idx, nb_steps, plane=None, dense=None, counts=None, y=None, n_dropped=None, augment=None):
         B = idx.numel()
         ws, ws_bytes = None, 0
         if n_dropped is not None:
             ws_bytes = lib.sparch_events_gather_bin_workspace_bytes(B, nb_steps, self.nb_units)
             ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=self.device)
-        tok = timer.start(f"events_gather_bin[{B}x{nb_steps}x{self.nb_units}]")
-        check(lib.sparch_events_gather_bin(ptr(self.times), self.times_dtype, ptr(self.units), ptr(self.offsets),
-                                           ptr(self.labels), self.n_samples, ptr(idx), B, nb_steps, self.nb_units,
-                                           self.max_time, int(self.sorted), ptr(plane), ptr(dense), ptr(counts),
-                                           ptr(y), ptr(n_dropped), ptr(ws), ws_bytes, _stream()),
-              "sparch_events_gather_bin")
+        args = (ptr(self.times), self.times_dtype, ptr(self.units), ptr(self.offsets), ptr(self.labels),
+                self.n_samples, ptr(idx), B, nb_steps, self.nb_units, self.max_time, int(self.sorted), ptr(plane),
+                ptr(dense), ptr(counts), ptr(y), ptr(n_dropped), ptr(ws), ws_bytes)
+        if augment is None:
+            tok = timer.start(f"events_gather_bin[{B}x{nb_steps}x{self.nb_units}]")
+            check(lib.sparch_events_gather_bin(*args, _stream()), "sparch_events_gather_bin")
+        else:
+            tok = timer.start(f"events_gather_bin_aug[{B}x{nb_steps}x{self.nb_units}]")
+            check(lib.sparch_events_gather_bin_aug(*args, ptr(augment[0]), augment[1], _stream()),
+                  "sparch_events_gather_bin_aug")
         timer.stop(tok)
 
-    def gather(self, idx, nb_steps, plane=False, dense=False, counts=False, dropped=False):
+    def gather(self, idx, nb_steps, plane=False, dense=False, counts=False, dropped=False, augment=None):
         """Raw outputs of the kernel for the device int64 index list `idx`: a dict with 'y' and whichever of
         'plane' ((B * nb_steps, ldp) bf16), 'dense' ((B, nb_steps, K) fp32), 'counts' ((B, nb_steps, K) uint8,
-        saturating) and 'n_dropped' (device int32, 1 element) were asked for."""
+        saturating) and 'n_dropped' (device int32, 1 element) were asked for.  augment = (table, seed): row b of
+        the (B, 8) table transforms the events of batch row b inside the kernel (`sparch_events_gather_bin_aug`;
+        `dataloaders.event_augment` draws such tables); a host table is validated here, before anything is
+        launched (ValueError)."""
         _require_device(idx, "idx")
         if idx.dtype != torch.int64 or idx.ndim != 1 or idx.numel() == 0 or not idx.is_contiguous():
             raise ValueError("EventStore.gather: idx must be a non-empty contiguous 1-D int64 tensor")
         if not (plane or dense or counts):
             raise ValueError("EventStore.gather: ask for at least one of plane, dense, counts")
         B, K, dev = idx.numel(), self.nb_units, self.device
+        if augment is not None:
+            augment = self._augment_rows(augment, B)
         out = {"y": torch.empty(B, dtype=torch.int64, device=dev)}
         if plane:
             out["plane"] = torch.empty(B * nb_steps, (K + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)
@@ -1519,7 +1557,7 @@ class EventStore:
         if dropped:
             out["n_dropped"] = torch.empty(4, dtype=torch.int32, device=dev)
         self._launch(idx, nb_steps, out.get("plane"), out.get("dense"), out.get("counts"), out["y"],
-                     out.get("n_dropped"))
+                     out.get("n_dropped"), augment)
         if dropped:
             out["n_dropped"] = out["n_dropped"][:1]
         return out
@@ -1543,16 +1581,28 @@ class EventStore:
         self.prepare(nb_steps)
         return self._dropped[nb_steps]
 
-    def serves_plane(self, nb_steps):
+    def serves_plane(self, nb_steps, augment_scale=None):
         # the conditions under which layer 1 would read the plane of an fp32 batch (SpikingLayerFn.forward)
-        return DENSE_GEMM == "split6" and self.prepare(nb_steps) <= 255
+        if augment_scale is None:
+            return DENSE_GEMM == "split6" and self.prepare(nb_steps) <= 255
+        # augmented batches: time compression merges bins, so the store's largest count is no bound any more.  A bin
+        # of t' = a * t + c covers at most ceil(1 / a) + 1 bins of t, a >= 1 - augment_scale, one more for the edges
+        from .dataloaders.event_augment import plane_count_factor
 
-    def batch(self, idx, nb_steps, values=False):
+        return DENSE_GEMM == "split6" and self.prepare(nb_steps) * plane_count_factor(augment_scale) <= 255
+
+    def batch(self, idx, nb_steps, values=False, augment=None, augment_scale=None):
         """(x, y) on the device for the index list: x is the layer-1 input — the tagged placeholder of
         `input_from_counts` when the store serves the plane, dense fp32 (B, nb_steps, K) otherwise or when
-        `values` asks for a tensor whose elements can be read (non-spiking networks)."""
-        if not values and self.serves_plane(nb_steps):
-            got = self.gather(idx, nb_steps, plane=True)
+        `values` asks for a tensor whose elements can be read (non-spiking networks).  augment: as `gather` takes
+        it; `augment_scale` < 1 is then a bound of the table's time compression, a >= 1 - augment_scale (None: read
+        from the table), which decides whether the counts still fit the plane."""
+        if augment is not None:
+            augment = self._augment_rows(augment, idx.numel())      # validated (and uploaded) before anything else
+            if augment_scale is None:   # one read-back; a loader passes the bound of its spec instead
+                augment_scale = max(0.0, 1.0 - float(augment[0][:, 1].min()))
+        if not values and self.serves_plane(nb_steps, augment_scale if augment is not None else None):
+            got = self.gather(idx, nb_steps, plane=True, augment=augment)
             B = idx.numel()
             key = str(self.device)
             one = _flag_one.get(key)
@@ -1561,7 +1611,7 @@ class EventStore:
             x = spike_placeholder(B, nb_steps, self.nb_units, self.device).view(B, nb_steps, self.nb_units)
             x._sparch_input_plane = (tuple(x.shape), got["plane"], one)
             return x, got["y"]
-        got = self.gather(idx, nb_steps, dense=True)
+        got = self.gather(idx, nb_steps, dense=True, augment=augment)
         return got["dense"], got["y"]
 
 

@@ -51,7 +51,7 @@ TRAINING_FLAGS = [
     ("reg_factor", float, 0.5, None, "Weight of the firing-rate penalty."),
     ("reg_fmin", float, 0.01, None, "Lowest unpenalised firing rate."),
     ("reg_fmax", float, 0.5, None, "Highest unpenalised firing rate."),
-    ("use_augm", strtobool, False, None, "Data augmentation (non-spiking datasets only)."),
+    ("use_augm", strtobool, False, None, "Data augmentation (shd / ssc: with SPARCH_EVENTS_AUGMENT only)."),
 ]
 
 EXTRA_FLAGS = [

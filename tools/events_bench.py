@@ -19,6 +19,11 @@ Reports (every pair alternates inside one process; medians and quartiles)
     alternating, the first epoch of each is a warm-up.
 
     python tools/events_bench.py [--samples 4096] [--events 8000] [--out result.json]
+
+--augment SPEC (dataloaders/event_augment.py, e.g. shift=40,scale=0.2,offset=0.1,drop=0.1,tmask=0.15,umask=70) reports
+instead, and only, the kernel time of `sparch_events_gather_bin_aug` with rows drawn from SPEC alternating with
+`sparch_events_gather_bin` on the same batches (B = --batch at 100 x 700 and 250 x 700, bf16 plane; the table is on
+the device before the clock starts, as the loader uploads an epoch's table once).
 """
 import argparse
 import json
@@ -122,6 +127,48 @@ def kernel_times(mapping, batch, nb_steps, reps, warmup):
                 gather_bin_plane_write_GBps=plane_bytes / (np.median(new_b2b) * 1e-3) / 1e9)
 
 
+def augment_kernel_times(mapping, batch, nb_steps, reps, warmup, spec):
+    """Augmented and plain gather-and-bin on the same index list, alternating; both write the bf16 plane."""
+    import torch
+
+    from sparch_amd import functional as Fn
+    from sparch_amd.dataloaders.event_augment import draw_event_augmentation
+
+    store = Fn.EventStore.from_mapping(mapping, device="cuda")
+    g = torch.Generator().manual_seed(1)
+    idx = torch.randperm(len(store), generator=g)[:batch].to("cuda")
+    table, seed = draw_event_augmentation(batch, spec, np.random.default_rng(1), NB_UNITS, MAX_TIME)
+    table_d = store.upload_augmentation(table)
+    lost = {}
+
+    def augmented():
+        store.gather(idx, nb_steps, plane=True, augment=(table_d, seed))
+
+    def plain():
+        store.gather(idx, nb_steps, plane=True)
+
+    for _ in range(warmup):
+        augmented()
+        plain()
+    for name, aug in (("augmented", (table_d, seed)), ("plain", None)):
+        lost[name] = int(store.gather(idx, nb_steps, plane=True, dropped=True, augment=aug)["n_dropped"].item())
+    new, old = [], []
+    for _ in range(reps):
+        new.append(_timed(augmented))
+        old.append(_timed(plain))
+
+    def train_of(fn, k=50):
+        return _timed(lambda: [fn() for _ in range(k)]) / k
+
+    new_b2b = [train_of(augmented) for _ in range(5)]
+    old_b2b = [train_of(plain) for _ in range(5)]
+    n = int((store.offsets[idx + 1] - store.offsets[idx]).sum().item())
+    return dict(events_in_batch=n, events_not_placed=lost, gather_bin_aug_ms=_quartiles(new),
+                gather_bin_ms=_quartiles(old), gather_bin_aug_back_to_back_ms=float(np.median(new_b2b)),
+                gather_bin_back_to_back_ms=float(np.median(old_b2b)),
+                aug_over_plain=float(np.median(new) / np.median(old)))
+
+
 def host_times(mapping, batch, epochs):
     import torch
 
@@ -201,6 +248,8 @@ def main(argv=None):
     ap.add_argument("--host-epochs", type=int, default=3)
     ap.add_argument("--train-epochs", type=int, default=5)
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--augment", default=None, metavar="SPEC",
+                    help="time only the augmenting kernel against the plain one on the same batches")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     import torch
@@ -208,6 +257,25 @@ def main(argv=None):
     assert torch.cuda.is_available(), "events_bench needs a HIP device"
     res = dict(samples=a.samples, events_per_sample_assumed=a.events, batch=a.batch)
     mapping = synth_mapping(a.samples, a.events)
+    if a.augment is not None:
+        from sparch_amd.dataloaders.event_augment import parse_event_augment
+
+        res["augment"] = {k: v for k, v in parse_event_augment(a.augment).items() if v}
+        for nb_steps in (100, 250):
+            r = augment_kernel_times(mapping, a.batch, nb_steps, a.reps, a.warmup, a.augment)
+            res[f"augment_kernel_{a.events}ev_{nb_steps}x{NB_UNITS}"] = r
+            print(f"kernel B={a.batch} {nb_steps}x{NB_UNITS}, {r['events_in_batch']} events: gather_bin_aug "
+                  f"{r['gather_bin_aug_ms']['median']:.4f} ms [{r['gather_bin_aug_ms']['p25']:.4f}, "
+                  f"{r['gather_bin_aug_ms']['p75']:.4f}] (back to back {r['gather_bin_aug_back_to_back_ms']:.4f} ms), "
+                  f"gather_bin {r['gather_bin_ms']['median']:.4f} ms [{r['gather_bin_ms']['p25']:.4f}, "
+                  f"{r['gather_bin_ms']['p75']:.4f}] (back to back {r['gather_bin_back_to_back_ms']:.4f} ms)",
+                  flush=True)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     for events in (a.events // 4, a.events, a.events * 2):
         m = mapping if events == a.events else synth_mapping(max(a.batch, 512), events, seed=events)
         for nb_steps in (100, 250):
