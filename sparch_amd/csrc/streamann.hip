@@ -17,18 +17,15 @@
 // transpose, no mask —, streamed once per row tile straight into registers (16-byte loads where K and H are multiples
 // of 4, scalar loads otherwise; issued before the tile is staged); the row tile of x_t, then of y, sits in LDS in
 // K-pieces, staged ONCE for all gates of the phase and read by all four waves.  Dot products are fp32 FMA chains, 64
-// lane partials per (row, column, gate) added by a butterfly.  ann_dot restates ss_dot (streamstep.hip) with a gate
-// dimension; that file is left as it is.
+// lane partials per (row, column, gate) added by a butterfly.  The dot product is stream_dot of stream_common.h, the one
+// of the spiking step, here with the phase's gates, fp32 input and the column tail off; the workgroup's geometry and
+// the row-tile switch are that header's too.
 //
 // The arithmetic is the expression trees of annstep.hip / gatedcell.hip / act.hip (this file is built with
 // -ffp-contract=off): sigm(v) = 1 / (1 + expf(-v)), ReLU keeps a NaN, tanhf, the projection through neuron_input.
 #include "stream_common.h"
 
 namespace {
-
-constexpr int SA_NT = 256;   // 4 waves
-constexpr int SA_COLS = 4;   // columns per workgroup: one per wave
-__host__ __device__ constexpr int sa_piece(int RT) { return RT <= 8 ? 1024 : 512; }  // floats of a staged row piece
 
 // what a launch computes; the gate slots of AnnArgs it uses
 enum { SA_MLP = 0, SA_RNN = 1, SA_LIGRU = 2, SA_GRU1 = 3, SA_GRU2 = 4 };
@@ -52,96 +49,15 @@ __device__ __forceinline__ float sa_act(int kind, float v) {
     if (kind == SPARCH_ACT_RELU) return v <= 0.0f ? 0.0f : v;  // a NaN stays a NaN
     return tanhf(v);
 }
-__device__ __forceinline__ float sa_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// acc[g][r] += sum_k src[r0 + r][k] * wrow[g][k], k < K.  All 256 threads stage the tile's piece once for the G gates;
-// the calling wave's lanes stride over k.  A wave without a column is given any valid rows (it stages, keeps the
-// barriers, and its sums are never read).  VEC: every weight row is 16-byte aligned and K is a multiple of 4.  Every
-// global load is UNCONDITIONAL on a clamped address and masked where it is used (see ss_dot).
-template <int RT, int G, bool VEC>
-__device__ __forceinline__ void ann_dot(float* xs, const float* src, int ld_src, const float* const (&wrow)[G], int K,
-                                        int r0, int B, float (&acc)[G][RT]) {
-    constexpr int KP = sa_piece(RT), NV = KP / 256, NS = KP / 64, NI = KP / SA_NT;
-    const int tid = threadIdx.x, lane = tid & 63;
-    for (int k0 = 0; k0 < K; k0 += KP) {
-        const int klen = min(KP, K - k0);
-        // ---- this wave's weights of the piece -> registers (in flight while the tile is staged)
-        f32x4 wv[G][VEC ? NV : 1];
-        float ws[G][VEC ? 1 : NS];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            if (VEC) {
-#pragma unroll
-                for (int i = 0; i < NV; ++i)
-                    wv[g][i] = *reinterpret_cast<const f32x4*>(wrow[g] + min(k0 + (i * 64 + lane) * 4, K - 4));
-            } else {
-#pragma unroll
-                for (int i = 0; i < NS; ++i) ws[g][i] = wrow[g][min(k0 + i * 64 + lane, K - 1)];
-            }
-        }
-        // ---- the row tile's piece -> LDS (rows past B as zeros): all loads first, then the stores
-        float xv[RT][NI];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const size_t o = (size_t)min(r0 + r, B - 1) * ld_src;
-#pragma unroll
-            for (int i = 0; i < NI; ++i) xv[r][i] = src[o + min(k0 + tid + i * SA_NT, K - 1)];
-        }
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int kk = tid + i * SA_NT;
-                if (kk < klen) xs[r * KP + kk] = (r0 + r < B) ? xv[r][i] : 0.f;
-            }
-        }
-        __syncthreads();
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int kk = (i * 64 + lane) * 4;
-                if (kk < klen) {
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) {
-                        const f32x4 x4 = *reinterpret_cast<const f32x4*>(&xs[r * KP + kk]);
-#pragma unroll
-                        for (int g = 0; g < G; ++g) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[g][r] = __builtin_fmaf(wv[g][i][e], x4[e], acc[g][r]);
-                        }
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int kk = i * 64 + lane;
-                if (kk < klen) {
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) {
-                        const float xk = xs[r * KP + kk];
-#pragma unroll
-                        for (int g = 0; g < G; ++g) acc[g][r] = __builtin_fmaf(ws[g][i], xk, acc[g][r]);
-                    }
-                }
-            }
-        }
-        __syncthreads();  // the piece is consumed: the next one (or the next operand) may be staged
-    }
-}
 
 template <int RT, int MODE, bool VEC>
-__global__ __launch_bounds__(SA_NT) void ann_stream_step_kernel(AnnArgs a) {
-    constexpr int G = sa_gates(MODE), KP = sa_piece(RT);
+__global__ __launch_bounds__(STREAM_NT) void ann_stream_step_kernel(AnnArgs a) {
+    constexpr int G = sa_gates(MODE), KP = stream_piece(RT);
     constexpr bool REC = MODE != SA_MLP;
     __shared__ __attribute__((aligned(16))) float xs[RT * KP];
-    __shared__ float red[2][G][RT][SA_COLS];
+    __shared__ float red[2][G][RT][STREAM_COLS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h0 = blockIdx.x * SA_COLS, r0 = blockIdx.y * RT;
+    const int h0 = blockIdx.x * STREAM_COLS, r0 = blockIdx.y * RT;
     const int hw = min(h0 + wave, a.H - 1);  // this wave's column (a wave past H: any valid one, never read)
     // ---- the pointwise phase's operands, asked for now (thread = (row, column)): they arrive while the dot products run
     const int r = tid >> 2, c = tid & 3;
@@ -171,20 +87,20 @@ __global__ __launch_bounds__(SA_NT) void ann_stream_step_kernel(AnnArgs a) {
         const float* wr[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) wr[g] = a.W[g] + (size_t)hw * a.K;
-        ann_dot<RT, G, VEC>(xs, a.x, a.ldx, wr, a.K, r0, a.B, accx);
+        stream_dot<RT, G, false, VEC, false>(xs, a.x, a.ldx, wr, a.K, r0, a.B, accx);
     }
     if (REC) {
         const float* vr[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) vr[g] = a.V[g] + (size_t)hw * a.H;
-        ann_dot<RT, G, VEC>(xs, a.rec, a.ld, vr, a.H, r0, a.B, accr);
+        stream_dot<RT, G, false, VEC, false>(xs, a.rec, a.ld, vr, a.H, r0, a.B, accr);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
         for (int i = 0; i < RT; ++i) {
-            const float sx = sa_wave_sum(accx[g][i]);
-            const float sr = REC ? sa_wave_sum(accr[g][i]) : 0.f;
+            const float sx = stream_wave_sum(accx[g][i]);
+            const float sr = REC ? stream_wave_sum(accr[g][i]) : 0.f;
             if (lane == 0) {
                 red[0][g][i][wave] = sx;
                 red[1][g][i][wave] = sr;
@@ -307,7 +223,7 @@ __global__ __launch_bounds__(AR_NT) void ann_stream_readout_kernel(int K, int C,
         } else {
             for (int k = lane; k < K; k += 64) d = __builtin_fmaf(wr[k], as[k], d);
         }
-        d = sa_wave_sum(d);
+        d = stream_wave_sum(d);
         if (lane == 0) row[c] = d;
     }
     __syncthreads();
@@ -320,13 +236,13 @@ __global__ __launch_bounds__(AR_NT) void ann_stream_readout_kernel(int K, int C,
         if (wave == 0) {
             float sm = 0.f;
             for (int c = lane; c < C; c += 64) sm += row[c];
-            const float mean = sa_wave_sum(sm) / (float)C;
+            const float mean = stream_wave_sum(sm) / (float)C;
             float sq = 0.f;
             for (int c = lane; c < C; c += 64) {
                 const float dv = row[c] - mean;
                 sq += dv * dv;
             }
-            const float var = sa_wave_sum(sq) / (float)C;
+            const float var = stream_wave_sum(sq) / (float)C;
             if (lane == 0) {
                 stat[0] = mean;
                 stat[1] = 1.0f / sqrtf(var + eps);
@@ -339,25 +255,20 @@ __global__ __launch_bounds__(AR_NT) void ann_stream_readout_kernel(int K, int C,
     }
 }
 
-template <int MODE, bool VEC>
-void launch_ann_rt(int RT, const AnnArgs& a, dim3 grid, hipStream_t st) {
-    switch (RT) {
-        case 1: hipLaunchKernelGGL((ann_stream_step_kernel<1, MODE, VEC>), grid, dim3(SA_NT), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((ann_stream_step_kernel<2, MODE, VEC>), grid, dim3(SA_NT), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((ann_stream_step_kernel<4, MODE, VEC>), grid, dim3(SA_NT), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((ann_stream_step_kernel<8, MODE, VEC>), grid, dim3(SA_NT), 0, st, a); break;
-        default: hipLaunchKernelGGL((ann_stream_step_kernel<16, MODE, VEC>), grid, dim3(SA_NT), 0, st, a); break;
-    }
-}
-
 template <bool VEC>
 void launch_ann(int mode, int RT, const AnnArgs& a, dim3 grid, hipStream_t st) {
+    auto tiles = [&](auto m) {
+        stream_row_tiles(RT, [&](auto rt) {
+            hipLaunchKernelGGL((ann_stream_step_kernel<decltype(rt)::value, decltype(m)::value, VEC>), grid,
+                               dim3(STREAM_NT), 0, st, a);
+        });
+    };
     switch (mode) {
-        case SA_MLP: launch_ann_rt<SA_MLP, VEC>(RT, a, grid, st); break;
-        case SA_RNN: launch_ann_rt<SA_RNN, VEC>(RT, a, grid, st); break;
-        case SA_LIGRU: launch_ann_rt<SA_LIGRU, VEC>(RT, a, grid, st); break;
-        case SA_GRU1: launch_ann_rt<SA_GRU1, VEC>(RT, a, grid, st); break;
-        default: launch_ann_rt<SA_GRU2, VEC>(RT, a, grid, st); break;
+        case SA_MLP: tiles(std::integral_constant<int, SA_MLP>{}); break;
+        case SA_RNN: tiles(std::integral_constant<int, SA_RNN>{}); break;
+        case SA_LIGRU: tiles(std::integral_constant<int, SA_LIGRU>{}); break;
+        case SA_GRU1: tiles(std::integral_constant<int, SA_GRU1>{}); break;
+        default: tiles(std::integral_constant<int, SA_GRU2>{}); break;
     }
 }
 
@@ -411,7 +322,7 @@ extern "C" int sparch_ann_stream_step(int cell, int phase, int act, int B, int K
     if (cdiv(B, RT) > 65535) return SPARCH_EINVAL;  // grid.y walks the row tiles
     const bool gru = cell == SPARCH_CELL_GRU;
     if (!all16({a.W[0], a.W[1], a.V[0], a.V[1], y_in, y_out, gru ? z : nullptr, gru ? ry : nullptr})) return SPARCH_EALIGN;
-    const dim3 grid(cdiv(H, SA_COLS), cdiv(B, RT));
+    const dim3 grid(cdiv(H, STREAM_COLS), cdiv(B, RT));
     // 16-byte weight loads where every row of every weight matrix read is aligned, scalar ones otherwise
     if ((!x || (K & 3) == 0) && (!rec || (H & 3) == 0)) launch_ann<true>(mode, RT, a, grid, (hipStream_t)stream);
     else launch_ann<false>(mode, RT, a, grid, (hipStream_t)stream);

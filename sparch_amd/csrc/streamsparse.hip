@@ -50,7 +50,7 @@ __host__ __device__ constexpr int sp_piece(int RT) { return RT <= 2 ? 1024 : RT 
 // lk / lv [r * KP + j], j < pcnt[r]; pbase[r] = the number of entries the row's earlier pieces held.  `tot` is the
 // running length of row tid's list (threads tid < RT; carried by the caller from piece to piece).  All SP_NT threads
 // call; the lists may be read behind the call (it ends in a barrier) and must be consumed before the next one.
-// Every global load is UNCONDITIONAL on a clamped address and masked where it is used (see ss_dot, streamstep.hip).
+// Every global load is UNCONDITIONAL on a clamped address and masked where it is used (see stream_dot, stream_common.h).
 template <int RT, bool U8>
 __device__ __forceinline__ void sp_compact(float* lv, uint16_t* lk, int* wcnt, int* pcnt, int* pbase, int& tot,
                                            const void* src, int ld_src, int K, int k0, int r0, int B) {

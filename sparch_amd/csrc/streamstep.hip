@@ -18,108 +18,19 @@
 // The dot products are fp32 FMA chains, 64 lane partials per (row, column) added by a butterfly: exact wherever the
 // sums are exact in any order (dyadic weights on 0/1 spikes), otherwise within a few ulp of any other fp32 order.
 // The pointwise update is the one of rec_fwd_kernel (reccell.hip) and cell_fwd_pipe_kernel (cell.hip): neuron.h, through
-// the tails of stream_common.h.  What is here: ss_dot, the geometry of the two kernels, the entry points.
+// the tails of stream_common.h.  The dot product is stream_dot of stream_common.h (one gate, the column tail on), which
+// the baselines' step shares.  What is here: the two kernels and the readout's geometry, the entry points.
 #include "stream_common.h"
 
 namespace {
 
-constexpr int SS_NT = 256;   // 4 waves
-constexpr int SS_COLS = 4;   // columns per workgroup: one per wave
-// floats of one staged row piece: the tile is RT x KP floats of LDS (<= 32 KB)
-__host__ __device__ constexpr int ss_piece(int RT) { return RT <= 8 ? 1024 : 512; }
-
-// acc[r] += sum_k src[r0 + r][k] * wrow[k], k < K.  All 256 threads stage; the calling wave's lanes stride over k.
-// A wave without a column is given any valid row (it stages, keeps the barriers, and its sums are never read).
-// VEC: rows of the weight matrix are 16-byte aligned (base aligned, row stride a multiple of 4) — 16-byte loads up to
-// K & ~3, the <= 3 left over by the first lanes; otherwise scalar loads throughout (a compile-time choice: as a
-// run-time one hipcc issues the loads of both forms).
-// Every global load is UNCONDITIONAL on a clamped address and masked where it is used: a load under a branch makes
-// hipcc wait for it at the join, one round trip per load instead of one per piece.
-template <int RT, bool U8, bool VEC>
-__device__ __forceinline__ void ss_dot(float* xs, const void* src, int ld_src, const float* wrow, int K, int r0, int B,
-                                       float (&acc)[RT]) {
-    constexpr int KP = ss_piece(RT), NV = KP / 256, NS = KP / 64, NI = KP / SS_NT;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int Kv = VEC ? (K & ~3) : 0;
-    for (int k0 = 0; k0 < K; k0 += KP) {
-        const int klen = min(KP, K - k0);
-        // ---- this wave's weights of the piece -> registers (in flight while the tile is staged)
-        f32x4 wv[VEC ? NV : 1];
-        float ws[VEC ? 1 : NS];
-        float wt = 0.f;
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i)  // (a row of a vec matrix holds (K + 3) & ~3 floats: the clamp stays inside)
-                wv[i] = *reinterpret_cast<const f32x4*>(wrow + min(k0 + (i * 64 + lane) * 4, max(Kv - 4, 0)));
-            wt = wrow[min(Kv + lane, K - 1)];
-        } else {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) ws[i] = wrow[min(k0 + i * 64 + lane, K - 1)];
-        }
-        // ---- the row tile's piece -> LDS (rows past B as zeros): all loads first, then the stores
-        float xv[RT][NI];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const size_t o = (size_t)min(r0 + r, B - 1) * ld_src;
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const size_t oo = o + min(k0 + tid + i * SS_NT, K - 1);
-                xv[r][i] = U8 ? (float)static_cast<const uint8_t*>(src)[oo] : static_cast<const float*>(src)[oo];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int kk = tid + i * SS_NT;
-                if (kk < klen) xs[r * KP + kk] = (r0 + r < B) ? xv[r][i] : 0.f;
-            }
-        }
-        __syncthreads();
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int kk = (i * 64 + lane) * 4;
-                if (k0 + kk < Kv) {
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) {
-                        const f32x4 x4 = *reinterpret_cast<const f32x4*>(&xs[r * KP + kk]);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[r] = __builtin_fmaf(wv[i][e], x4[e], acc[r]);
-                    }
-                }
-            }
-            if (Kv >= k0 && Kv < k0 + KP && Kv + lane < K) {  // the <= 3 columns behind the last 16 bytes
-#pragma unroll
-                for (int r = 0; r < RT; ++r) acc[r] = __builtin_fmaf(wt, xs[r * KP + (Kv - k0) + lane], acc[r]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const int kk = i * 64 + lane;
-                if (kk < klen) {
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) acc[r] = __builtin_fmaf(ws[i], xs[r * KP + kk], acc[r]);
-                }
-            }
-        }
-        __syncthreads();  // the piece is consumed: the next one (or the next operand) may be staged
-    }
-}
-
-__device__ __forceinline__ float ss_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <int RT, bool ADAPT, bool REC, bool VEC>
-__global__ __launch_bounds__(SS_NT) void stream_step_kernel(StreamArgs a) {
-    constexpr int KP = ss_piece(RT);
+__global__ __launch_bounds__(STREAM_NT) void stream_step_kernel(StreamArgs a) {
+    constexpr int KP = stream_piece(RT);
     __shared__ __attribute__((aligned(16))) float xs[RT * KP];
-    __shared__ float red[2][RT][SS_COLS];
+    __shared__ float red[2][RT][STREAM_COLS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h0 = blockIdx.x * SS_COLS, r0 = blockIdx.y * RT;
+    const int h0 = blockIdx.x * STREAM_COLS, r0 = blockIdx.y * RT;
     const int hw = min(h0 + wave, a.H - 1);  // this wave's column (a wave past H: any valid one, never read)
     // ---- the pointwise phase's operands, asked for now (thread = (row, column), the tile's 4 columns of a row
     //      adjacent in memory): they arrive while the dot products run
@@ -131,18 +42,19 @@ __global__ __launch_bounds__(SS_NT) void stream_step_kernel(StreamArgs a) {
     const StreamColumn<ADAPT> pc = stream_column<ADAPT>(a.alpha, a.beta, a.a, a.b, a.bias, a.scale, a.shift, hc);
     const float u = a.u[o], w = ADAPT ? a.w[o] : 0.f, s = a.s_in[o];
 
-    float accx[RT], accr[RT];
+    float accx[1][RT], accr[1][RT];
 #pragma unroll
-    for (int i = 0; i < RT; ++i) accx[i] = accr[i] = 0.f;
+    for (int i = 0; i < RT; ++i) accx[0][i] = accr[0][i] = 0.f;
+    // (one gate; the tail switch on: V has H columns in rows of ld floats)
     if (a.in_u8)
-        ss_dot<RT, true, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
+        stream_dot<RT, 1, true, VEC, true>(xs, a.x, a.ldx, {a.W + (size_t)hw * a.K}, a.K, r0, a.B, accx);
     else
-        ss_dot<RT, false, VEC>(xs, a.x, a.ldx, a.W + (size_t)hw * a.K, a.K, r0, a.B, accx);
-    if (REC) ss_dot<RT, false, VEC>(xs, a.s_in, a.ld, a.V + (size_t)hw * a.ld, a.H, r0, a.B, accr);
+        stream_dot<RT, 1, false, VEC, true>(xs, a.x, a.ldx, {a.W + (size_t)hw * a.K}, a.K, r0, a.B, accx);
+    if (REC) stream_dot<RT, 1, false, VEC, true>(xs, a.s_in, a.ld, {a.V + (size_t)hw * a.ld}, a.H, r0, a.B, accr);
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
-        const float sx = ss_wave_sum(accx[i]);
-        const float sr = REC ? ss_wave_sum(accr[i]) : 0.f;
+        const float sx = stream_wave_sum(accx[0][i]);
+        const float sr = REC ? stream_wave_sum(accr[0][i]) : 0.f;
         if (lane == 0) {
             red[0][i][wave] = sx;
             red[1][i][wave] = sr;
@@ -165,7 +77,7 @@ struct RoWeights {
     float s[ro_group(VEC)][VEC ? 1 : RO_KP / 64];
 };
 // the weights of classes c0 .. c0 + ro_group(VEC) - 1 for the piece at k0: loads on clamped addresses, masked at their use
-// (see ss_dot)
+// (see stream_dot, stream_common.h)
 template <bool VEC>
 __device__ __forceinline__ void ro_load_group(RoWeights<VEC>& w, const float* __restrict__ W, int K, int C, int c0,
                                               int k0, int lane) {
@@ -230,7 +142,7 @@ __global__ __launch_bounds__(RO_NT) void stream_step_readout_kernel(int K, int C
                     for (int i = 0; i < RO_KP / 64; ++i)
                         if (i * 64 + lane < klen) acc = __builtin_fmaf(w.s[j][i], xs[i * 64 + lane], acc);
                 }
-                acc = ss_wave_sum(acc);
+                acc = stream_wave_sum(acc);
                 if (lane == 0 && c0 + j < C) row[c0 + j] = row[c0 + j] + acc;
             }
         }
@@ -244,7 +156,7 @@ template <bool VEC>
 void launch_step(int RT, int kind, const StreamArgs& a, dim3 grid, hipStream_t st) {
     stream_dispatch(RT, kind, [&](auto rt, auto adapt, auto rec) {
         hipLaunchKernelGGL((stream_step_kernel<decltype(rt)::value, decltype(adapt)::value, decltype(rec)::value, VEC>), grid,
-                           dim3(SS_NT), 0, st, a);
+                           dim3(STREAM_NT), 0, st, a);
     });
 }
 
@@ -263,7 +175,7 @@ extern "C" int sparch_stream_step_fwd(int kind, int B, int K, int H, int ld, int
     g.u = u; g.w = w; g.s_in = s_in; g.s_out = s_out; g.s16_out = s16_out; g.theta = theta; g.spike_count = spike_count;
     if (const int rc = stream_step_check(kind, in_dtype, g, false)) return rc;
     const int RT = stream_row_tile(B);
-    const dim3 grid(cdiv(H, SS_COLS), cdiv(B, RT));
+    const dim3 grid(cdiv(H, STREAM_COLS), cdiv(B, RT));
     // 16-byte weight loads where every row of W and of vmask_t is aligned, scalar ones otherwise
     const bool rec = kind == SPARCH_KIND_RLIF || kind == SPARCH_KIND_RADLIF;
     if ((K & 3) == 0 && (!rec || (ld & 3) == 0)) launch_step<true>(RT, kind, g, grid, (hipStream_t)stream);

@@ -54,7 +54,121 @@ class _Layer:
     """One layer's cached operands and its state buffers (plain attribute bag)."""
 
 
-class StreamingSNN:
+class _ParityGraphs(dict):
+    """graph=True, steps of one time step: {what identifies the current copy of the state: dict(graph, replays)}, one
+    captured chain of launches per parity, with the static input and output they share."""
+
+    def __init__(self):
+        super().__init__()
+        self.x = self.out = self.dtype = None
+        self.warm = 0
+
+
+class _Stream:
+    """What StreamingSNN and StreamingANN share: the refusals, the step counts, the chunk check, the checked load of a
+    state tensor, the BatchNorm fold and the replayed single step on two copies of the state.  A subclass refuses the
+    wrong kind of network first, sets `_layers` and `_dev` in refresh(), and for graph=True provides `_state_key()` and
+    `_static_step(x)`."""
+
+    def __init__(self, net, batch_size, graph):
+        name = type(self).__name__
+        if net.bidirectional:
+            raise ValueError(f"{name}: a bidirectional network is not causal — its backward direction needs "
+                             "the end of the sequence before the first output")
+        if net.training:
+            raise ValueError(f"{name}: the network is in training mode — BatchNorm's batch statistics and "
+                             "dropout have no streaming meaning; call net.eval() first")
+        self.net = net
+        self.batch_size = int(batch_size)
+        self.graph = bool(graph)
+        self.steps_seen = 0
+        self.row_steps = np.zeros(self.batch_size, dtype=np.int64)
+        self._layers = None
+
+    def _restart(self, rows):
+        if rows is None:
+            self.steps_seen = 0
+            self.row_steps[:] = 0
+        else:
+            self.row_steps[list(rows)] = 0
+
+    def _chunk(self, x):
+        """The checked chunk (B,Tc,K) on the device, a 4-D one flattened when net.reshape."""
+        if self.net.reshape and x.ndim == 4:
+            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
+        Fn._require_device(x, "input")
+        K = self._layers[0].K
+        if x.ndim != 3 or x.shape[0] != self.batch_size or x.shape[1] < 1 or x.shape[2] != K:
+            raise ValueError(f"{type(self).__name__}.step: a ({self.batch_size}, Tc >= 1, {K}) chunk, got "
+                             f"{tuple(x.shape)}")
+        return x
+
+    def _rows(self, rows):
+        return None if rows is None else torch.as_tensor(list(rows), dtype=torch.long, device=self._dev)
+
+    def _entries(self, states):
+        if len(states) != len(self._layers):
+            raise ValueError(f"{type(self).__name__}: {len(self._layers)} layers, {len(states)} state entries")
+        return zip(self._layers, states)
+
+    def _put(self, dst, src, what, idx, H=None):
+        """src (all rows, or the rows idx) -> the state tensor dst; H: the layer's own width where dst is padded."""
+        name, H = type(self).__name__, dst.shape[1] if H is None else H
+        n = self.batch_size if idx is None else len(idx)
+        if src is None:
+            raise ValueError(f"{name}: the state has no {what}")
+        src = torch.as_tensor(src, dtype=torch.float32).to(self._dev)
+        if src.ndim != 2 or src.shape[0] != n or src.shape[1] not in (H, dst.shape[1]):
+            raise ValueError(f"{name}: {what} has shape {tuple(src.shape)}, expected ({n}, {H})")
+        src = _pad_cols(src, dst.shape[1])
+        if idx is None:
+            dst.copy_(src)
+        else:
+            dst.index_copy_(0, idx, src)
+
+    def set_state(self, states):
+        """Load a state (the format of get_state(), or of reset(states=...)) without touching the counters."""
+        self._ensure()
+        self._load(states, None)
+
+    def _bn_fold(self, H, norm):
+        """Eval BatchNorm: the running statistics folded into one affine map (scale, shift) per column."""
+        _, scale, shift, _ = Fn._Norm.forward(
+            "batchnorm", torch.empty(1, H, dtype=torch.float32, device=self._dev), None, norm.weight, norm.bias,
+            norm.running_mean, norm.running_var, False, 1)
+        return scale, shift
+
+    def _replayed_step(self, graphs, x):
+        """Replay the captured chain of launches for the current copy of the state (captured on first need, after one
+        eager step, for the first input dtype seen) on x -> the static output; None = launch eagerly.  The caller
+        swaps the copies behind it."""
+        if graphs.dtype is None:
+            graphs.dtype = x.dtype
+        if x.dtype != graphs.dtype:
+            return None
+        if graphs.warm < 1:
+            graphs.warm += 1
+            return None
+        key = self._state_key()
+        g = graphs.get(key)
+        if g is None:
+            if graphs.x is None:
+                last = self._layers[-1]
+                graphs.x = torch.empty(x.shape, dtype=x.dtype, device=self._dev)
+                graphs.out = torch.empty((self.batch_size, last.H) if last.readout else (self.batch_size, 1, last.H),
+                                         dtype=torch.float32, device=self._dev)
+            g = {"graph": torch.cuda.CUDAGraph(), "replays": 0}
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g["graph"]):
+                graphs.out.copy_(self._static_step(graphs.x))
+            graphs[key] = g
+        graphs.x.copy_(x, non_blocking=True)
+        g["graph"].replay()
+        g["replays"] += 1
+        return graphs.out
+
+
+class StreamingSNN(_Stream):
     """Chunked forward of a `sparch_amd.SNN` in eval mode with carried state.
 
     step(x_chunk) returns, with a readout layer, the running softmax-sum (B,classes) after all steps seen so far
@@ -71,30 +185,16 @@ class StreamingSNN:
     def __init__(self, net, batch_size, graph=False, fused=False, sparse=False):
         if not getattr(net, "is_snn", False):
             raise ValueError("StreamingSNN: a sparch_amd.SNN (the non-spiking baselines do not stream)")
-        if net.bidirectional:
-            raise ValueError("StreamingSNN: a bidirectional network is not causal — its backward direction needs "
-                             "the end of the sequence before the first output")
-        if net.training:
-            raise ValueError("StreamingSNN: the network is in training mode — BatchNorm's batch statistics and "
-                             "dropout have no streaming meaning; call net.eval() first")
+        super().__init__(net, batch_size, graph)
         if sparse and not fused:
             raise ValueError("StreamingSNN: sparse=True is a form of the fused one-step path — pass fused=True too")
         if fused and any(mod.normalize and mod.normalization == "layernorm" for mod in net.snn):
             raise ValueError("StreamingSNN: fused=True does not take LayerNorm layers (a row statistic across the "
                              "workgroups of a step); use fused=False")
-        self.net = net
-        self.batch_size = int(batch_size)
-        self.graph = bool(graph)
         self.fused = bool(fused)
         self.sparse = bool(sparse)
         self._fused_active = self.fused and Fn._prec() == 0
-        self._fg = {}             # fused step, graph=True: {current spike buffers: dict(graph, replays)}, one per parity
-        self._fg_x = self._fg_out = None   # the static input and output both parities share
-        self._fg_dtype = None
-        self._fg_warm = 0
-        self.steps_seen = 0
-        self.row_steps = np.zeros(self.batch_size, dtype=np.int64)
-        self._layers = None
+        self._fg = _ParityGraphs()  # fused step, graph=True: keyed by the current spike buffers
         self._prec = None
         self._g = None            # dict(Tc, x, out, graph) once the step is captured
         self._g_Tc = None         # the chunk length the graph is (to be) captured for: the first one seen
@@ -110,7 +210,7 @@ class StreamingSNN:
         """(Re)build everything derived from the parameters and the running statistics: call after changing them.
         The state of the stream is kept."""
         net, B = self.net, self.batch_size
-        dev = next(net.parameters()).device
+        dev = self._dev = next(net.parameters()).device
         Fn._require_device(next(net.parameters()), "the network")
         old = self._layers
         layers = []
@@ -129,10 +229,8 @@ class StreamingSNN:
                 L.Wt = _transposed(L.W) if self.sparse else None  # the event-driven step's operand: row k = input k
                 L.norm = mod.normalization if mod.normalize else "none"
                 L.scale = L.shift = L.nw = L.nb = None
-                if L.norm == "batchnorm":  # eval: the running statistics folded into one affine map per column
-                    _, L.scale, L.shift, _ = Fn._Norm.forward(
-                        "batchnorm", torch.empty(1, L.H, dtype=torch.float32, device=dev), None, mod.norm.weight,
-                        mod.norm.bias, mod.norm.running_mean, mod.norm.running_var, False, 1)
+                if L.norm == "batchnorm":
+                    L.scale, L.shift = self._bn_fold(L.H, mod.norm)
                 elif L.norm == "layernorm":
                     L.nw, L.nb = mod.norm.weight.detach(), mod.norm.bias.detach()
                 L.theta = None if L.readout else float(mod.threshold)
@@ -177,9 +275,9 @@ class StreamingSNN:
                     # names (its padded columns are never written: they stay zero like those of s)
                     L.s_alt, L.s16_alt, L.s_first = torch.zeros_like(L.s), torch.zeros_like(L.s16), L.s
                 layers.append(L)
-        self._layers, self._prec, self._dev = layers, Fn._prec(), dev
+        self._layers, self._prec = layers, Fn._prec()
         self._g, self._g_warm = None, 0  # a captured step holds the old operands
-        self._fg, self._fg_x, self._fg_out, self._fg_warm = {}, None, None, 0
+        self._fg = _ParityGraphs()
         self._fused_active = self.fused and self._prec == 0  # (the bf16 operand mode takes the chunk path)
 
     @property
@@ -212,33 +310,17 @@ class StreamingSNN:
         return u, w, s, None
 
     def _load(self, states, rows):
-        idx = None if rows is None else torch.as_tensor(list(rows), dtype=torch.long, device=self._dev)
-        n = self.batch_size if rows is None else len(idx)
-        if len(states) != len(self._layers):
-            raise ValueError(f"StreamingSNN: {len(self._layers)} layers, {len(states)} state entries")
-
-        def put(dst, src, what, H):
-            if src is None:
-                raise ValueError(f"StreamingSNN: the state has no {what}")
-            src = torch.as_tensor(src, dtype=torch.float32).to(self._dev)
-            if src.ndim != 2 or src.shape[0] != n or src.shape[1] not in (H, dst.shape[1]):
-                raise ValueError(f"StreamingSNN: {what} has shape {tuple(src.shape)}, expected ({n}, {H})")
-            src = _pad_cols(src, dst.shape[1])
-            if idx is None:
-                dst.copy_(src)
-            else:
-                dst.index_copy_(0, idx, src)
-
-        for L, st in zip(self._layers, states):
+        idx = self._rows(rows)
+        for L, st in self._entries(states):
             u, w, s, out = self._entry(st, L.readout)
-            put(L.u, u, "u", L.H)
+            self._put(L.u, u, "u", idx, L.H)
             if L.readout:
                 if out is not None:
-                    put(L.out, out, "out", L.H)
+                    self._put(L.out, out, "out", idx)
                 continue
             if L.adaptive:
-                put(L.w, w, "w", L.H)
-            put(L.s, s, "s", L.H)
+                self._put(L.w, w, "w", idx, L.H)
+            self._put(L.s, s, "s", idx, L.H)
             L.binary = False  # drawn states are uniform noise; a caller's are whatever they are
 
     def reset(self, states=None, rows=None):
@@ -262,18 +344,9 @@ class StreamingSNN:
                     L.count.zero_()
             if ro is not None:
                 ro.out.zero_()
-            self.steps_seen = 0
-            self.row_steps[:] = 0
-        else:
-            rows = list(rows)
-            if ro is not None:
-                ro.out.index_fill_(0, torch.as_tensor(rows, dtype=torch.long, device=self._dev), 0.0)
-            self.row_steps[rows] = 0
-
-    def set_state(self, states):
-        """Load a state (the format of get_state(), or of reset(states=...)) without touching counters."""
-        self._ensure()
-        self._load(states, None)
+        elif ro is not None:
+            ro.out.index_fill_(0, self._rows(rows), 0.0)
+        self._restart(rows)
 
     def get_state(self):
         """A copy of the carried state: per hidden layer {"u", ["w",] "s"}, for the readout {"u", "out"} (unpadded)."""
@@ -384,14 +457,7 @@ class StreamingSNN:
     def step(self, x_chunk):
         """x_chunk (B,Tc,C) float32, or uint8 spike counts, on the device; any Tc >= 1."""
         self._ensure()
-        net = self.net
-        x = x_chunk
-        if net.reshape and x.ndim == 4:
-            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
-        Fn._require_device(x, "input")
-        if x.ndim != 3 or x.shape[0] != self.batch_size or x.shape[1] < 1 or x.shape[2] != self._layers[0].K:
-            raise ValueError(f"StreamingSNN.step: a ({self.batch_size}, Tc >= 1, {self._layers[0].K}) chunk, got "
-                             f"{tuple(x.shape)}")
+        x = self._chunk(x_chunk)
         Tc = x.shape[1]
         if self._fused_active:
             if Tc == 1:
@@ -444,7 +510,7 @@ class StreamingSNN:
         return self._g["out"]
 
     # ------------------------------------------------------------------ the fused step (Tc == 1)
-    def _spike_key(self):
+    def _state_key(self):
         return tuple(L.s.data_ptr() for L in self._layers if L.recurrent)
 
     def _primary_spikes(self):
@@ -509,48 +575,20 @@ class StreamingSNN:
         ldx = max(int(x.stride(0)), layers[0].K)  # a (B,1,K) slice of a longer sequence is read where it lies
         ro = layers[-1].readout
         hidden = [L for L in layers if not L.readout]
-        g = self._fused_graph(x) if self.graph else None
-        if g is None:
+        out = self._replayed_step(self._fg, x) if self.graph else None
+        if out is None:
             out = self._fused_launch(x, ldx)
-            self._fused_swap()
             out = out.clone() if ro else out[:, :hidden[-1].H].unsqueeze(1).clone()
-        else:
-            self._fg_x.copy_(x, non_blocking=True)
-            g["graph"].replay()
-            g["replays"] += 1
-            self._fused_swap()
-            out = self._fg_out
+        self._fused_swap()
         if self._spike_tap is not None:
             for i, L in enumerate(hidden):
                 self._spike_tap(i, L.s[:, :L.H].unsqueeze(1))
         return out
 
-    def _fused_graph(self, x):
-        """The captured three-launch chain for the current parity (captured on first need, after one eager fused
-        step, for the first input dtype seen); None = launch eagerly."""
-        if self._fg_dtype is None:
-            self._fg_dtype = x.dtype
-        if x.dtype != self._fg_dtype:
-            return None
-        if self._fg_warm < 1:
-            self._fg_warm += 1
-            return None
-        key = self._spike_key()
-        g = self._fg.get(key)
-        if g is None:
-            layers = self._layers
-            last = layers[-1]
-            if self._fg_x is None:
-                self._fg_x = torch.empty(x.shape, dtype=x.dtype, device=self._dev)
-                self._fg_out = (torch.empty_like(last.out) if last.readout else
-                                torch.empty(self.batch_size, 1, last.H, dtype=torch.float32, device=self._dev))
-            g = {"graph": torch.cuda.CUDAGraph(), "replays": 0}
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g["graph"]):
-                out = self._fused_launch(self._fg_x, layers[0].K)
-                self._fg_out.copy_(out if last.readout else out[:, :last.H].unsqueeze(1))
-            self._fg[key] = g
-        return g
+    def _static_step(self, x):
+        """The three-launch chain on the static input, as a graph captures it."""
+        out, last = self._fused_launch(x, self._layers[0].K), self._layers[-1]
+        return out if last.readout else out[:, :last.H].unsqueeze(1)
 
 
 # ---------------------------------------------------------------------------------------- raw audio

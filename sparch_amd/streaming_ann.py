@@ -21,11 +21,11 @@ refusal of compute dtype bf16.
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import functional as Fn
 from ._capi import check, lib, ptr
+from .streaming import _Layer, _ParityGraphs, _Stream
 
 CELL = {"MLP": 0, "RNN": 1, "LiGRU": 2, "GRU": 3}          # SPARCH_CELL_*
 RO_NORM = {"none": 0, "batchnorm": 1, "layernorm": 2}      # SPARCH_RO_NORM_*
@@ -40,11 +40,7 @@ def _slots(tensors):
     return _Slots(*[ptr(t) for t in tensors])
 
 
-class _Layer:
-    """One layer's cached operands and its state buffers (plain attribute bag)."""
-
-
-class StreamingANN:
+class StreamingANN(_Stream):
     """Step-by-step forward of a `sparch_amd.anns.ANN` in eval mode with carried state.
 
     step(x_chunk) returns, with a readout layer, the readout's output (B,classes) after all steps seen so far,
@@ -56,23 +52,10 @@ class StreamingANN:
             raise ValueError("StreamingANN: a sparch_amd.anns.ANN (a spiking network streams through StreamingSNN)")
         if not hasattr(net, "ann"):
             raise ValueError("StreamingANN: a sparch_amd.anns.ANN")
-        if net.bidirectional:
-            raise ValueError("StreamingANN: a bidirectional network is not causal — its backward direction needs "
-                             "the end of the sequence before the first output")
-        if net.training:
-            raise ValueError("StreamingANN: the network is in training mode — BatchNorm's batch statistics and "
-                             "dropout have no streaming meaning; call net.eval() first")
+        super().__init__(net, batch_size, graph)
         self._require_fp32()
-        self.net = net
-        self.batch_size = int(batch_size)
-        self.graph = bool(graph)
-        self.steps_seen = 0
-        self.row_steps = np.zeros(self.batch_size, dtype=np.int64)
-        self._layers = None
         self._parity = 0          # which copy of the recurrent states is current
-        self._g = {}              # graph=True: {parity: dict(graph, replays)}
-        self._g_x = self._g_out = None   # the static input and output both parities share
-        self._g_warm = 0
+        self._g = _ParityGraphs()  # graph=True: keyed by the parity
 
     @staticmethod
     def _require_fp32():
@@ -85,7 +68,7 @@ class StreamingANN:
         """(Re)build everything derived from the parameters and the running statistics: call after changing them.
         The state of the stream is kept."""
         net, B = self.net, self.batch_size
-        dev = next(net.parameters()).device
+        dev = self._dev = next(net.parameters()).device
         Fn._require_device(next(net.parameters()), "the network")
         old = self._layers
         layers = []
@@ -95,10 +78,7 @@ class StreamingANN:
         def fold(L, norm):
             """The eval form of one normalisation: (scale, shift) of BatchNorm's running statistics, or (gamma, beta)."""
             if L.norm == "batchnorm":
-                _, scale, shift, _ = Fn._Norm.forward(
-                    "batchnorm", torch.empty(1, L.H, dtype=torch.float32, device=dev), None, norm.weight, norm.bias,
-                    norm.running_mean, norm.running_var, False, 1)
-                return scale, shift
+                return self._bn_fold(L.H, norm)
             if L.norm == "layernorm":
                 return Fn._f32c(norm.weight.detach()), Fn._f32c(norm.bias.detach())
             return None, None
@@ -143,8 +123,8 @@ class StreamingANN:
                     L.y_alt = zeros(L.H) if L.recurrent else None     # the other copy: a step reads y, writes y_alt
                     L.z, L.ry = (zeros(L.H), zeros(L.H)) if L.kind == "GRU" else (None, None)
                 layers.append(L)
-        self._layers, self._dev = layers, dev
-        self._g, self._g_x, self._g_out, self._g_warm = {}, None, None, 0  # a captured step holds the old operands
+        self._layers = layers
+        self._g = _ParityGraphs()  # a captured step holds the old operands
 
     def _ensure(self):
         self._require_fp32()
@@ -152,28 +132,12 @@ class StreamingANN:
             self.refresh()
 
     # ------------------------------------------------------------------ state
-    def _rows(self, rows):
-        return None if rows is None else torch.as_tensor(list(rows), dtype=torch.long, device=self._dev)
-
     def _load(self, states, idx):
-        n = self.batch_size if idx is None else len(idx)
-        if len(states) != len(self._layers):
-            raise ValueError(f"StreamingANN: {len(self._layers)} layers, {len(states)} state entries")
-        for L, st in zip(self._layers, states):
-            key = "acc" if L.readout else "y"
-            dst = L.acc if L.readout else L.y
+        for L, st in self._entries(states):
             if not L.readout and not L.recurrent:
                 continue  # an MLP layer carries nothing
-            src = st.get(key) if isinstance(st, dict) else st
-            if src is None:
-                raise ValueError(f"StreamingANN: the state has no {key}")
-            src = torch.as_tensor(src, dtype=torch.float32).to(self._dev)
-            if tuple(src.shape) != (n, dst.shape[1]):
-                raise ValueError(f"StreamingANN: {key} has shape {tuple(src.shape)}, expected ({n}, {dst.shape[1]})")
-            if idx is None:
-                dst.copy_(src)
-            else:
-                dst.index_copy_(0, idx, src)
+            key = "acc" if L.readout else "y"
+            self._put(L.acc if L.readout else L.y, st.get(key) if isinstance(st, dict) else st, key, idx)
 
     def reset(self, states=None, rows=None):
         """Start (the given rows of) the stream anew: y = 0 and an empty accumulator, as the reference's forward
@@ -190,16 +154,7 @@ class StreamingANN:
                     buf.index_fill_(0, idx, 0.0)
         if states is not None:
             self._load(states, idx)
-        if rows is None:
-            self.steps_seen = 0
-            self.row_steps[:] = 0
-        else:
-            self.row_steps[list(rows)] = 0
-
-    def set_state(self, states):
-        """Load a state (the format of get_state()) without touching the step counters."""
-        self._ensure()
-        self._load(states, None)
+        self._restart(rows)
 
     def get_state(self):
         """A copy of the carried state: per hidden layer {"y"} ({} for an MLP layer), for the readout {"acc"}."""
@@ -254,25 +209,15 @@ class StreamingANN:
     def step(self, x_chunk):
         """x_chunk (B,Tc,C) float32 (or uint8 counts, converted here) on the device, 4-D when net.reshape; Tc >= 1."""
         self._ensure()
-        x = x_chunk
-        if self.net.reshape and x.ndim == 4:
-            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
-        Fn._require_device(x, "input")
-        K = self._layers[0].K
-        if x.ndim != 3 or x.shape[0] != self.batch_size or x.shape[1] < 1 or x.shape[2] != K:
-            raise ValueError(f"StreamingANN.step: a ({self.batch_size}, Tc >= 1, {K}) chunk, got {tuple(x.shape)}")
+        x = self._chunk(x_chunk)
         if x.dtype != torch.float32 or x.stride(2) != 1:
             x = Fn._f32c(x)
         Tc = x.shape[1]
         ro = self._layers[-1].readout
         with torch.no_grad():
-            g = self._graph_for(x) if (self.graph and Tc == 1) else None
-            if g is not None:
-                self._g_x.copy_(x, non_blocking=True)
-                g["graph"].replay()
-                g["replays"] += 1
+            out = self._replayed_step(self._g, x) if (self.graph and Tc == 1) else None
+            if out is not None:
                 self._swap()
-                out = self._g_out
             else:
                 outs = None if ro else torch.empty(self.batch_size, Tc, self._layers[-1].H, dtype=torch.float32,
                                                    device=self._dev)
@@ -286,23 +231,10 @@ class StreamingANN:
         self.row_steps += Tc
         return out
 
-    def _graph_for(self, x):
-        """The captured chain of launches for the current parity (captured on first need, after one eager step);
-        None = launch eagerly."""
-        if self._g_warm < 1:
-            self._g_warm += 1
-            return None
-        g = self._g.get(self._parity)
-        if g is None:
-            last = self._layers[-1]
-            if self._g_x is None:
-                self._g_x = torch.empty(x.shape, dtype=torch.float32, device=self._dev)
-                self._g_out = torch.empty((self.batch_size, last.H) if last.readout else (self.batch_size, 1, last.H),
-                                          dtype=torch.float32, device=self._dev)
-            g = {"graph": torch.cuda.CUDAGraph(), "replays": 0}
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g["graph"]):
-                y = self._launch(self._g_x[:, 0])
-                self._g_out.copy_(y if last.readout else y.unsqueeze(1))
-            self._g[self._parity] = g
-        return g
+    def _state_key(self):
+        return self._parity
+
+    def _static_step(self, x):
+        """The chain of launches on the static input, as a graph captures it."""
+        y = self._launch(x[:, 0])
+        return y if self._layers[-1].readout else y.unsqueeze(1)
