@@ -4,6 +4,9 @@ sparch_amd.functional.cell_forward / cell_backward.  It shares no code with the 
 float64 is the reference of tests/test_rec_cell_real_V_gpu.py, float32 (the recurrent products accumulated over 32-wide
 k blocks, ascending and descending) is the yardstick its bounds are made from.  tests/test_spiking_numpy_host.py pins it
 to oracle.bptt_numpy (bit for bit, fp32) and to torch autograd of oracle.snn_oracle.spiking_cell (float64).
+tests/test_scan_kernels_fp64_gpu.py (LIF / adLIF: dropout's keep multiplier, sums over the rows ascending and
+descending, the bf16 save words save_u16 / bf16_words) and tests/test_readout_kernels_fp64_gpu.py (readout_forward /
+readout_backward, further down) stand on it too, and share their cases and conditions from here.
 
 Geometry (the header's): B batch rows, dirs = 1 | 2, Bp = B * dirs virtual rows.  Virtual row b + B * d reads the
 projection of batch row b, for d = 1 at time T - 1 - t.  "Cell time order" indexes a (Bp,T,H) tensor by the step t the
@@ -19,9 +22,11 @@ alpha, beta, a, b are the raw parameters clamped to the float32 limits the kerne
 step is s0, real-valued.  In reverse, on SAVED u / w only (the backward kernels never see the projection), with
 du_{T} = dw_{T} = 0 and s_{t-1} = [u_{t-1} - theta > 0] (s0 at t = 0):
 
-    g_t   = g_out_t + g_rate / (B T)
+    g_t   = (g_out_t + g_rate / (B T)) keep_t                    keep: dropout's multiplier, 0 or 1 / (1 - p); else 1
     ds_t  = g_t - alpha du_{t+1} [+ b dw_{t+1}] [+ dWx_{t+1} Vm^T]
     du_t  = box(ds_t, u_t - theta) + alpha du_{t+1} [+ a dw_{t+1}]        box: ds where -0.5 < x <= 0.5, else 0
+                                       (x = u_t - theta in the SAVE's own type, like the spike: the kernels decide all
+                                        three on the fp32 difference, and a value on an edge in fp32 need not be in fp64)
     dWx_t = (1 - alpha) du_t              dw_t = beta dw_{t+1} - dWx_t
     per virtual row:  ws_alpha = (sum_t du_t ((u_{t-1} - s_{t-1}) - u_t)) / (1 - alpha)
                       ws_beta = sum_t dw_t w_{t-1}    ws_a = sum_t dw_t u_{t-1}    ws_b = sum_t dw_t s_{t-1}
@@ -90,6 +95,36 @@ def bf16_round(x):
     return r.astype(x.dtype if x.dtype in (F32, F64) else F32)
 
 
+def bf16_words(x):
+    """The bf16 words (uint16) of an fp32 array rounded to nearest-even (common.h f32_to_bf16_rne; finite values)."""
+    b = np.ascontiguousarray(x, dtype=F32).view(np.uint32)
+    return ((b + (np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+
+
+def bf16_to_f32(words):
+    """bf16 words (uint16) widened to fp32, exactly."""
+    return (np.asarray(words, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(F32)
+
+
+def decisions_of(u, theta):
+    """The three decisions the backward takes from a saved membrane potential (common.h decisions_of), on the fp32
+    difference: bit 0 the spike u - theta > 0, bits 1 / 2 the box-car edges u - theta <= -0.5, u - theta > 0.5."""
+    x = np.asarray(u, dtype=F32) - F32(theta)
+    return (x > 0).astype(np.uint8) | ((x <= F32(-0.5)).astype(np.uint8) << 1) | ((x > F32(0.5)).astype(np.uint8) << 2)
+
+
+def save_u16(u, theta):
+    """common.h save_u16 in numpy: u (fp32) rounded to nearest-even bf16; where that changed one of the three
+    decisions and the word is not +-0, one bf16 ulp back towards u.  Returns the uint16 words."""
+    u = np.ascontiguousarray(u, dtype=F32)
+    b = bf16_words(u)
+    v = bf16_to_f32(b)
+    moved = (decisions_of(v, theta) != decisions_of(u, theta)) & ((b & np.uint16(0x7FFF)) != 0)
+    up, neg = v < u, (b & np.uint16(0x8000)) != 0
+    step = np.where(up != neg, 1, -1).astype(np.int32)
+    return np.where(moved, (b.astype(np.int32) + step).astype(np.uint16), b)
+
+
 def split3(x):
     """The exact TRUNCATION split x = t1 + t2 + t3 of an fp32 array as three fp32 arrays (what the backward kernels do
     to dWx; tests/test_gemm_layouts_gpu.split3_host, not a second restatement)."""
@@ -142,6 +177,19 @@ def matmul_blocks(a, b, k_order=None):
     for kb in order:
         acc = acc + a[:, kb * KB:(kb + 1) * KB] @ b[kb * KB:(kb + 1) * KB]
     return acc
+
+
+def ordered_sum(a, axis, order=None):
+    """Sum along `axis`.  order None: numpy's (pairwise); "asc" / "desc": one running sum in a's dtype, first to last
+    or last to first."""
+    if order is None:
+        return a.sum(axis)
+    a = a if order == "asc" else np.flip(a, axis)
+    return np.take(np.cumsum(a, axis=axis, dtype=a.dtype), -1, axis=axis)
+
+
+# the mutated backward passes of tests/test_spiking_numpy_host.py (sharpness of the scan kernels' bound)
+SCAN_MUTANTS = ("rate_over_dirs", "keep_not_on_rate", "step0_reads_u_save", "xhat_without_mean_last_column")
 
 
 class Params:
@@ -246,21 +294,35 @@ def teacher_forced_forward(kind, dtype, Wx, scale, shift, p, u0, w0, s0, u_save,
 
 # ------------------------------------------------------------------------------------------------ backward
 def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, dirs, theta=1.0, k_order=None,
-             operand=None, rec_operand=None, rec_product=None, bn=None):
+             operand=None, rec_operand=None, rec_product=None, bn=None, keep=None, row_order=None, mutant=None):
     """The reverse recurrences on supplied saves (module docstring).  g_out (B,T,H*dirs); g_rate (H*dirs) or None;
     u_save / w_save (Bp,T,H) in cell time order.  rec_operand: (Bp,T,H) at the original time index, the dWx values
     the dense products read; rec_product(dwx, VmT, k_order) replaces dWx @ Vm^T (the host test's mutant).
+    keep: the dropout multiplier (B,T,H*dirs) on the output layout, 0 or inv_keep (dropout_numpy.keep_mask at the
+    output element index), applied as the kernels apply it: g = (g_out + g_rate / (B T)) * keep.
+    row_order None: the sums over the virtual rows (parameter gradients, bn_sums) are numpy's; "asc" / "desc": added
+    up row by row in that order, in `dtype` (bn_sums: first over the steps of a row in reverse cell time, as the
+    kernels accumulate them).  mutant (tests/test_spiking_numpy_host.py only): one of SCAN_MUTANTS.
     Returns dWx (Bp,T,H) at the original time index, the per-row partials ws_alpha [ws_beta, ws_a, ws_b] (Bp,H), the
     gradients alpha [beta, a, b] [V] and, with bn, bn_sums = (sum dWx, sum dWx xhat)."""
+    assert mutant is None or mutant in SCAN_MUTANTS, mutant
     P = Params(kind, dtype, p, theta, operand)
     Bp, T, H = u_save.shape
-    g = from_out_layout(np.asarray(g_out, dtype=dtype), dirs)
+    go = np.asarray(g_out, dtype=dtype)
+    if keep is not None and mutant == "keep_not_on_rate":
+        go = go * np.asarray(keep, dtype=dtype)
     if g_rate is not None:
-        gr = np.asarray(g_rate, dtype=dtype).reshape(dirs, H) * (dtype(1) / (dtype(B) * dtype(T)))
-        g = g + np.repeat(gr, B, axis=0)[:, None, :]
+        n_rate = dtype(B) * dtype(T) * (dtype(dirs) if mutant == "rate_over_dirs" else dtype(1))
+        go = go + (np.asarray(g_rate, dtype=dtype) * (dtype(1) / n_rate))[None, None, :]
+    if keep is not None and mutant != "keep_not_on_rate":
+        go = go * np.asarray(keep, dtype=dtype)
+    g = from_out_layout(go, dirs)
     us = np.asarray(u_save)
     U = us.astype(dtype)
-    S = ((us - us.dtype.type(theta)) > 0).astype(dtype)  # the decision as the kernels take it: in the save's own type
+    # the three decisions as the kernels take them: on the difference in the save's own type (common.h decisions_of)
+    XS = us - us.dtype.type(theta)
+    S = (XS > 0).astype(dtype)
+    SHUT = (XS <= us.dtype.type(-0.5)) | (XS > us.dtype.type(0.5))
     W = np.asarray(w_save, dtype=dtype) if P.adaptive else None
     u0, s0 = np.asarray(u0, dtype=dtype), np.asarray(s0, dtype=dtype)
     w0 = np.asarray(w0, dtype=dtype) if P.adaptive else None
@@ -272,6 +334,7 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
     dwx_next = None
     for t in range(T - 1, -1, -1):
         u_prev, s_prev = (U[:, t - 1], S[:, t - 1]) if t > 0 else (u0, s0)
+        u_prev_al = U[:, 0] if (t == 0 and mutant == "step0_reads_u_save") else u_prev
         aldu = P.alpha * du_n
         ds = g[:, t] - aldu
         if P.adaptive:
@@ -279,13 +342,12 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
         if P.recurrent and t + 1 < T:
             x_op = P.op(dwx_next if rec_op is None else rec_op[:, t + 1])
             ds = ds + (rec_product or matmul_blocks)(x_op, P.VmT, k_order)
-        xs = U[:, t] - P.theta
-        du = np.where((xs <= -0.5) | (xs > 0.5), dtype(0), ds) + aldu
+        du = np.where(SHUT[:, t], dtype(0), ds) + aldu
         if P.adaptive:
             du = du + P.a * dw_n
         dwx = P.oma * du
         dWx[:, t] = dwx
-        acc["alpha"] = acc["alpha"] + du * ((u_prev - s_prev) - U[:, t])
+        acc["alpha"] = acc["alpha"] + du * ((u_prev_al - s_prev) - U[:, t])
         if P.adaptive:
             dw = P.beta * dw_n - dwx
             acc["beta"] = acc["beta"] + dw * (W[:, t - 1] if t > 0 else w0)
@@ -300,15 +362,95 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
     out = {"dWx": to_original(dWx, B, dirs)}
     for k in ("alpha",) + (("beta", "a", "b") if P.adaptive else ()):
         out["ws_" + k] = acc[k]
-        out[k] = np.where(inside(P.raw[k], LIMS[k]), acc[k].sum(0), dtype(0))
+        out[k] = np.where(inside(P.raw[k], LIMS[k]), ordered_sum(acc[k], 0, row_order), dtype(0))
     if P.recurrent:
         np.fill_diagonal(dV, 0)
         out["V"] = dV
     if bn is not None:
         x_raw, mean, invstd = (np.asarray(v, dtype=dtype) for v in bn)
         xhat = (x_raw - mean) * invstd                                  # (B,T,H) at the original time index
+        if mutant == "xhat_without_mean_last_column":
+            xhat[..., -1] = x_raw[..., -1] * invstd[-1]
         dy = out["dWx"].reshape(dirs, B, T, H)
-        out["bn_sums"] = (dy.sum((0, 1, 2)), (dy * xhat[None]).sum((0, 1, 2)))
+        if row_order is None:
+            out["bn_sums"] = (dy.sum((0, 1, 2)), (dy * xhat[None]).sum((0, 1, 2)))
+        else:       # per virtual row over its steps in reverse cell time, then over the rows
+            rev = lambda q: to_original(q.reshape(Bp, T, H), B, dirs)[:, ::-1]  # noqa: E731
+            out["bn_sums"] = tuple(ordered_sum(ordered_sum(rev(q), 1, "asc"), 0, row_order)
+                                   for q in (dy, dy * xhat[None]))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ readout
+# The readout cell (cell.hip readout_fwd_kernel / readout_bwd_kernel), generic in dtype:
+#     x_t = Wx_t * scale + shift (both optional);   u_t = al u + (1 - al) x_t,  al = alpha clamped to LIMS["alpha"]
+#     p_t = softmax_c(u_t) with the row's maximum subtracted;   out = sum_t p_t, added up in time order
+# and in reverse, on SAVED u only, with g = dL/dout (B,C), the form the kernel's header documents:
+#     e_t = p_t (g - <p_t, g>);  du_t = al du_{t+1} + e_t;  dWx_t = (1 - al) du_t
+#     ws_alpha = (sum_t du_t (u_{t-1} - u_t)) / (1 - al)      (u_{-1} = u0);  alpha = its sum over the rows, clamp-gated
+#     with bn = (Wx_raw, mean, invstd):  bn_dy = sum dWx,  bn_dyx = sum dWx (Wx_raw - mean) invstd
+# class_order None: numpy's sums; "asc" / "desc": the softmax denominator and the dot are running sums over the
+# classes in that order, the sums over the batch rows run in the same order (two fp32 runs make the bound).
+READOUT_MUTANTS = ("u0_ignored", "dot_without_last_class", "ragged_sweep_tail_zero")
+RO_BWD_SWEEP = 256 * 18     # elements of one staging sweep of readout_bwd_kernel (the mutant's geometry only)
+
+
+def _softmax(U, class_order):
+    e = np.exp(U - U.max(-1, keepdims=True))
+    return e / ordered_sum(e, -1, class_order)[..., None]
+
+
+def readout_forward(dtype, Wx, scale, shift, alpha, u0, class_order=None):
+    """Free-running.  Wx (B,T,C); scale / shift (C) or None; alpha (C) raw; u0 (B,C).  Returns u_save (B,T,C), out (B,C)."""
+    x = np.asarray(Wx, dtype=dtype)
+    if scale is not None:
+        x = x * np.asarray(scale, dtype=dtype) + np.asarray(shift, dtype=dtype)
+    lo, hi = LIMS["alpha"]
+    al = np.minimum(np.maximum(np.asarray(alpha, dtype=F32).astype(dtype), dtype(lo)), dtype(hi))
+    oma = dtype(1) - al
+    u = np.asarray(u0, dtype=dtype)
+    U = np.empty(x.shape, dtype)
+    for t in range(x.shape[1]):
+        u = al * u + oma * x[:, t]
+        U[:, t] = u
+    return U, ordered_sum(_softmax(U, class_order), 1, "asc")
+
+
+def readout_backward(dtype, g_out, u_save, alpha, u0, bn=None, class_order=None, mutant=None):
+    """On supplied saves.  Returns a dict: dWx (B,T,C), ws_alpha (B,C), alpha (C) and, with bn, bn_dy, bn_dyx (C)."""
+    assert mutant is None or mutant in READOUT_MUTANTS, mutant
+    U = np.asarray(u_save).astype(dtype)
+    if mutant == "ragged_sweep_tail_zero":      # the last element a ragged last sweep of the (one-chunk) row stages
+        n = U.shape[1] * U.shape[2]
+        assert n % RO_BWD_SWEEP != 0
+        U = U.copy()
+        U.reshape(U.shape[0], n)[:, -1] = 0
+    B, T, C = U.shape
+    g = np.asarray(g_out, dtype=dtype)
+    raw = np.asarray(alpha, dtype=F32)
+    lo, hi = LIMS["alpha"]
+    al = np.minimum(np.maximum(raw.astype(dtype), dtype(lo)), dtype(hi))
+    oma = dtype(1) - al
+    p = _softmax(U, class_order)
+    pg = p * g[:, None, :]
+    dot = ordered_sum(pg[..., :-1] if mutant == "dot_without_last_class" else pg, -1, class_order)
+    e = p * (g[:, None, :] - dot[..., None])
+    u_first = np.zeros((B, C), dtype) if mutant == "u0_ignored" else np.asarray(u0, dtype=dtype)
+    du, acc = np.zeros((B, C), dtype), np.zeros((B, C), dtype)
+    dWx = np.empty((B, T, C), dtype)
+    for t in range(T - 1, -1, -1):
+        du = al * du + e[:, t]
+        dWx[:, t] = oma * du
+        acc = acc + du * ((U[:, t - 1] if t > 0 else u_first) - U[:, t])
+    ws = acc / oma
+    out = {"dWx": dWx, "ws_alpha": ws,
+           "alpha": np.where(inside(raw, LIMS["alpha"]), ordered_sum(ws, 0, class_order), dtype(0))}
+    if bn is not None:
+        x_raw, mean, invstd = (np.asarray(v, dtype=dtype) for v in bn)
+        xhat = (x_raw - mean) * invstd
+        rows = lambda q: q if class_order is None else ordered_sum(q[:, ::-1], 1, "asc")  # noqa: E731
+        tot = (lambda q: q.sum((0, 1))) if class_order is None else (lambda q: ordered_sum(rows(q), 0, class_order))
+        out["bn_dy"], out["bn_dyx"] = tot(dWx), tot(dWx * xhat)
     return out
 
 
@@ -362,6 +504,87 @@ BIDIR_SHAPES = [(k, 17, 2, 6, 132) for k in ("RLIF", "RadLIF")]
 
 def case_seed(kind, B, dirs, T, H):
     return 1000003 * B + 1009 * T + 31 * H + 7 * dirs + len(kind)
+
+
+# ---- the cases of tests/test_scan_kernels_fp64_gpu.py (LIF / adLIF scan kernels of cell.hip), (B, dirs, H):
+# V4     524 304 neurons: four neurons per thread (B dirs H >= 524 288, H % 4 == 0); H / 4 = 1986 threads per row,
+#        so waves straddle rows;   V1BIG  524 040 neurons, H % 4 == 0: just under the threshold, one neuron per thread;
+# V1     one neuron per thread;    V1ODD  a width that is no multiple of 4.
+V4, V1BIG, V1, V1ODD = (33, 2, 7944), (33, 2, 7940), (33, 2, 100), (33, 1, 99)
+T_V4, T_V1 = 9, 17          # ring depth 8: one main trip and a one-step tail; depths 16 / 15 / 15 / 12 at V1
+SCAN_KINDS = ("LIF", "adLIF")
+SCAN_SHAPES = [(k,) + g[:2] + (T, g[2]) for k in SCAN_KINDS for g, T in ((V4, T_V4), (V1, T_V1), (V1BIG, T_V4), (V1ODD, T_V1))]
+SCAN_SALT = {}              # (kind, B, dirs, T, H) -> added to the seed where the first one broke a condition of the GPU file
+P_DROP = 0.25
+
+
+def scan_case(kind, B, dirs, T, H):
+    """make_inputs(..., "drive", affine_in=True) with g_rate scaled by B T (as drawn the rate term is 0.3 % of g_out),
+    parameter 0 of every neuron parameter below its clamp range and parameter 1 above it, and BatchNorm operands
+    bn = (raw projection 0.8 Wx + 0.3, mean ~ U(0.2, 0.6), invstd ~ U(0.5, 1.5))."""
+    from tests.test_spiking_bits_gpu import OUTSIDE
+    seed = case_seed(kind, B, dirs, T, H) + SCAN_SALT.get((kind, B, dirs, T, H), 0)
+    c = make_inputs(kind, B, dirs, T, H, seed, "drive", affine_in=True)
+    c["g_rate"] = c["g_rate"] * F32(B * T)
+    for k in c["p"]:
+        c["p"][k][0], c["p"][k][1] = OUTSIDE[k]
+    rng = np.random.default_rng(seed + 1)
+    c["bn"] = ((c["Wx"] * F32(0.8) + F32(0.3)).astype(F32), rng.uniform(0.2, 0.6, H).astype(F32),
+               rng.uniform(0.5, 1.5, H).astype(F32))
+    return c
+
+
+def scan_keep(c, seed, p_drop=P_DROP):
+    """The keep multiplier of a scan case on the output layout (the kernels run LIF / adLIF at the layer's own width)."""
+    from tests.dropout_numpy import keep_mask
+    return keep_mask(seed, (c["B"], c["T"], c["H"] * c["dirs"]), p_drop)
+
+
+def scan_conditions(c, u_save, keep=None):
+    """The non-vacuity conditions of the scan cases, on fp32 saves: 2 .. 50 % spikes, the box-car open on 5 .. 95 %
+    and, with dropout, kept AND dropped elements among the non-fired ones inside the box-car, 0.75 +- 0.02 kept."""
+    x = np.asarray(u_save, dtype=F32) - F32(c["theta"])
+    spikes, box = x > 0, (x > F32(-0.5)) & (x <= F32(0.5))
+    assert 0.02 <= spikes.mean() <= 0.5, ("spike fraction", float(spikes.mean()))
+    assert 0.05 <= box.mean() <= 0.95, ("box-car open share", float(box.mean()))
+    if keep is not None:
+        k = from_out_layout(keep, c["dirs"])[box & ~spikes] != 0
+        assert k.any() and not k.all() and abs(k.mean() - (1 - P_DROP)) <= 0.02, ("kept share", float(k.mean()))
+    return float(spikes.mean()), float(box.mean())
+
+
+# ---- the cases of tests/test_readout_kernels_fp64_gpu.py, (B, T, C)
+READOUT_SHAPES = [(3, 1, 5), (2, 133, 35), (2, 250, 37), (3, 300, 64), (3, 270, 65), (2, 123, 256), (2, 513, 1), (2, 40, 2)]
+READOUT_SALT = {}
+
+
+def readout_case(B, T, C):
+    """Wx ~ 1.5 N(0,1); u0 ~ U[0,1); alpha inside the clamp range except class 0 below and class 1 above it where
+    C >= 3; g_out ~ N(0,1); scale ~ U(0.7, 1.3), shift ~ U(-0.2, 0.2) for the forward's affine; for the backward's
+    sums bn = (raw projection 0.8 Wx + 0.3, mean ~ U(0.2, 0.6), invstd ~ U(0.5, 1.5))."""
+    rng = np.random.default_rng(1000003 * B + 1009 * T + 31 * C + READOUT_SALT.get((B, T, C), 0))
+    c = {"B": B, "T": T, "C": C, "Wx": (1.5 * rng.standard_normal((B, T, C))).astype(F32),
+         "u0": rng.uniform(0, 1, (B, C)).astype(F32), "alpha": rng.uniform(0.83, 0.95, C).astype(F32),
+         "g_out": rng.standard_normal((B, C)).astype(F32), "scale": rng.uniform(0.7, 1.3, C).astype(F32),
+         "shift": rng.uniform(-0.2, 0.2, C).astype(F32)}
+    if C >= 3:
+        c["alpha"][0], c["alpha"][1] = 0.5, 1.2
+    c["bn"] = ((c["Wx"] * F32(0.8) + F32(0.3)).astype(F32), rng.uniform(0.2, 0.6, C).astype(F32),
+               rng.uniform(0.5, 1.5, C).astype(F32))
+    return c
+
+
+READOUT_BWD_TENSORS = {False: ("dWx", "alpha"), True: ("dWx", "alpha", "bn_dy", "bn_dyx")}
+BOUND_CAP = 1e-5        # every bound of the scan and readout files is at most this share of its reference's max-abs
+
+
+def capped(bound, ref, names):
+    """Asserts that no bound exceeds BOUND_CAP of its reference tensor's max-abs (a tie, or any other discontinuity
+    between the fp32 and fp64 runs, would otherwise hide a failure behind a wide bound)."""
+    for k in names:
+        top = float(np.abs(ref[k]).max())
+        assert bound[k] <= BOUND_CAP * top, f"{k}: bound {bound[k]:.3e} is {bound[k] / max(top, 1e-300):.2e} of max-abs {top:.3e}"
+    return bound
 
 
 FWD_TENSORS = {False: ("u_save",), True: ("u_save", "w_save")}
