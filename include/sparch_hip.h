@@ -74,6 +74,19 @@ extern "C" {
 #define SPARCH_KIND_RLIF 2
 #define SPARCH_KIND_RADLIF 3
 
+/* The surrogate gradient of the spike function, gate(ds, x) with x = u_t - theta in fp32 (the difference the spike
+ * decision uses) and a scale k > 0.  The forward pass does not depend on it.
+ *   BOXCAR        the reference's (snns.py:31-36): ds where -0.5 < x <= 0.5, else 0 (assignment); takes no scale
+ *   TRIANGLE      ds * max(0, 1 - k*|x|)              area 1/k
+ *   FAST_SIGMOID  ds / ((1 + k*|x|) * (1 + k*|x|))    area 2/k
+ *   ATAN          ds / (1 + (k*x)*(k*x))              area pi/k
+ * The smooth forms are plain fp32 products and correctly rounded quotients in this operation order; a NaN in ds or x
+ * propagates.  They read u continuously and therefore need fp32 saves (save_bf16 = 0).                            */
+#define SPARCH_SURROGATE_BOXCAR 0
+#define SPARCH_SURROGATE_TRIANGLE 1
+#define SPARCH_SURROGATE_FAST_SIGMOID 2
+#define SPARCH_SURROGATE_ATAN 3
+
 int sparch_abi_version(void);
 const char* sparch_strerror(int code);
 /* Text of the HIP error behind the calling thread's most recent SPARCH_ELAUNCH. */
@@ -322,6 +335,16 @@ int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                     const float* u0, const float* w0, const float* s0, float theta,
                     float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
                     const float* bn_mean, const float* bn_invstd, void* stream);
+/* The same with a selectable surrogate (SPARCH_SURROGATE_*); sparch_cell_bwd is surrogate = BOXCAR.  SPARCH_EINVAL,
+ * before any device work, for an unknown id, for a smooth form with a scale that is not finite and > 0, and for a
+ * smooth form with save_bf16 != 0.  The scale is ignored for BOXCAR.                                           */
+int sparch_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_out,
+                       const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                       const float* alpha, const float* beta, const float* a, const float* b,
+                       const float* u0, const float* w0, const float* s0, float theta,
+                       float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                       const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
+                       void* stream);
 
 /* Recurrent kinds (RLIF, RadLIF).  V (H,H) = V.weight; the diagonal is masked inside
  * (snns.py:566/712).  The recurrent product s_{t-1}*V runs on MFMA with the V slice of
@@ -386,6 +409,17 @@ int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_
                         const float* bn_x, const float* bn_mean, const float* bn_invstd,
                         void* chan, size_t chan_bytes, uint32_t* status,
                         int steps_per_launch, void* stream, int precision);
+/* The same with a selectable surrogate (see sparch_cell_bwd_sg for the refusals); chunked launches carry du / dw
+ * through dparam_ws exactly as the box-car's do.                                                              */
+int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_out,
+                           const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                           const float* alpha, const float* beta, const float* a,
+                           const float* b, const float* vpack_t, const float* u0,
+                           const float* w0, const float* s0, float theta, float p_drop,
+                           uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                           const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                           void* chan, size_t chan_bytes, uint32_t* status,
+                           int steps_per_launch, int surrogate, float surrogate_scale, void* stream, int precision);
 /* ONE time step t of the same cells with the recurrent product supplied by the caller — the path for hidden
  * sizes whose V slice does not fit the persistent kernels' register-resident layout (H > 1024; the reference
  * accepts any nb_hiddens, snns.py:608-661): any grid size, nothing waits inside a launch.
@@ -418,6 +452,15 @@ int sparch_rec_cell_step_bwd(int kind, int B, int dirs, int T, int H, int t, con
                              float theta, float p_drop, uint64_t seed, float* dWx,
                              uint16_t* s_prev16, float* dparam_ws, const float* bn_x,
                              const float* bn_mean, const float* bn_invstd, float* dwx_step, void* stream);
+/* The backward step with a selectable surrogate (fp32 saves, as the step path always has). */
+int sparch_rec_cell_step_bwd_sg(int kind, int B, int dirs, int T, int H, int t, const float* g_out,
+                                const float* g_rate, const float* u_save, const float* w_save,
+                                const float* alpha, const float* beta, const float* a, const float* b,
+                                const float* rec, const float* u0, const float* w0, const float* s0,
+                                float theta, float p_drop, uint64_t seed, float* dWx,
+                                uint16_t* s_prev16, float* dparam_ws, const float* bn_x,
+                                const float* bn_mean, const float* bn_invstd, float* dwx_step,
+                                int surrogate, float surrogate_scale, void* stream);
 
 /* Finish per-row partials: out[j][h] = sum_r ws[j][r][h], zeroed where the raw parameter
  * lies outside [lo_j, hi_j] (torch.clamp's gradient gate).  n_params <= 8; raw[j]/lim may

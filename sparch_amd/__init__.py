@@ -9,7 +9,7 @@ from . import optim  # noqa: F401
 from .functional import (augment_padded, bin_events, check_status, compute_dtype, fbank,  # noqa: F401
                          fbank_padded, flac_decode_padded, set_compute_dtype)
 from .snns import (SNN, LIFLayer, RLIFLayer, RadLIFLayer, ReadoutLayer,  # noqa: F401
-                   SpikeFunctionBoxcar, adLIFLayer)
+                   SpikeFunctionBoxcar, SpikeFunctionSurrogate, adLIFLayer)
 from .streaming import StreamingFbank, StreamingSNN  # noqa: F401
 from .streaming_ann import StreamingANN  # noqa: F401
 

@@ -72,6 +72,8 @@ PROTOTYPES = {
                                        c_float, c_float, P, P, P, P]),
     "sparch_cell_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
                                 c_float, c_float, c_uint64, P, P, P, P, P, P]),
+    "sparch_cell_bwd_sg": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
+                                   c_float, c_float, c_uint64, P, P, P, P, P, c_int, c_float, P]),
     "sparch_vpack_bytes": (c_size_t, [c_int]),
     "sparch_set_xcd_local": (c_int, [c_int]),
     "sparch_vpack": (c_int, [c_int, P, c_int, P, P, P, c_int]),
@@ -84,12 +86,17 @@ PROTOTYPES = {
                                            c_float, c_float, P, P, P, P, c_size_t, P, c_int, P, c_int]),
     "sparch_rec_cell_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
                                     c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_size_t, P, c_int, P, c_int]),
+    "sparch_rec_cell_bwd_sg": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
+                                       c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_size_t, P, c_int,
+                                       c_int, c_float, P, c_int]),
     "sparch_rec_cell_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                          c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
     "sparch_rec_cell_step_stream_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P,
                                                 P, P, P, c_float, c_float, P, P, P, P]),
     "sparch_rec_cell_step_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                          P, c_float, c_float, c_uint64, P, P, P, P, P, P, P, P]),
+    "sparch_rec_cell_step_bwd_sg": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
+                                            P, c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_int, c_float, P]),
     "sparch_colsum_clamped": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "sparch_add_halves": (c_int, [c_size_t, P, P, P]),
     "sparch_colsum": (c_int, [c_int, c_int, P, P, P, c_size_t, P]),

@@ -233,133 +233,19 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
     }
 }
 
+// The reverse pass exists as two kernel families with ONE body (cell_bwd_body.inc): cell_bwd_pipe_kernel gates with
+// the reference's box-car, cell_bwd_pipe_sg_kernel with one of the smooth surrogates, chosen by a wave-uniform switch
+// on its second argument (fp32 saves only: S16 is never set there).
 template <bool ADAPT, int VEC, bool S16, bool BN, bool DROP>
-__global__ __launch_bounds__(256) void cell_bwd_pipe_kernel(CellArgs c) {
-    constexpr int D = pipe_depth(VEC, 3 + (ADAPT ? 1 : 0) + (BN ? 1 : 0));
-    const int HQ = c.H / VEC;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Bp = c.B * c.dirs;
-    if (idx >= (long long)Bp * HQ) return;
-    const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
-    const int d = bp / c.B, b = bp - d * c.B;
-    const int T = c.T, H = c.H, HO = c.H * c.dirs;
-
-    float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], gr[VEC];
-    float du_n[VEC], dw_n[VEC], u_t[VEC];
-    float acc_al[VEC], acc_be[VEC], acc_a[VEC], acc_b[VEC];
-    float bn_mu[VEC], bn_is[VEC], acc_dy[VEC], acc_dyx[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        bn_mu[e] = BN ? c.bn_mean[h + e] : 0.f;
-        bn_is[e] = BN ? c.bn_invstd[h + e] : 0.f;
-        acc_dy[e] = acc_dyx[e] = 0.f;
-        const Neuron<ADAPT> p = neuron_load<ADAPT>(c.alpha, c.beta, c.a, c.b, h + e);
-        al[e] = p.al; oma[e] = p.oma; be[e] = p.be; pa[e] = p.pa; pb[e] = p.pb;
-        gr[e] = c.g_rate ? c.g_rate[(size_t)d * H + h + e] * c.g_rate_scale : 0.0f;
-        du_n[e] = dw_n[e] = 0.f;
-        acc_al[e] = acc_be[e] = acc_a[e] = acc_b[e] = 0.f;
-    }
-    ld_saved<VEC>(u_t, c.u_save, ((size_t)bp * T + (T - 1)) * H + h, S16);
-    // the initial states: read by cell step 0 (the last of the reverse pass) only; fetched here, off the loop
-    float u0v[VEC], w0v[VEC], s0v[VEC];
-    ldv<VEC>(u0v, c.u0 + (size_t)bp * H + h);
-    ldv<VEC>(s0v, c.s0 + (size_t)bp * H + h);
-    if (ADAPT) ldv<VEC>(w0v, c.w0 + (size_t)bp * H + h);
-    constexpr bool drop = DROP;
-    const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
-
-    struct Slot { float g[VEC]; float xr[BN ? VEC : 1]; SavedVec<VEC, S16> up; SavedVec<VEC, S16> wp; };
-    const float* grow = c.g_out + (size_t)b * T * HO + (size_t)d * H + h;
-    const float* xrow = BN ? c.bn_x + (size_t)b * T * H + h : nullptr;
-    const size_t srow = (size_t)bp * T * H + h;
-    auto fetch = [&](Slot& q, int t) __attribute__((always_inline)) {
-        const int tc = max(t, 0);  // before the start: a step that is in range and never used
-        const int tt = d ? (T - 1 - tc) : tc;
-        ldv<VEC>(q.g, grow + (size_t)tt * HO);
-        if constexpr (BN) ldv<VEC>(q.xr, xrow + (size_t)tt * H);
-        const size_t i = srow + (size_t)max(tc - 1, 0) * H;  // cell step 0 reads row 0 (unused: u0 / w0 below)
-        q.up.load(c.u_save, i);
-        if (ADAPT) q.wp.load(c.w_save, i);
-    };
-    // FIRST: the step may be cell step 0 (tail of the reverse pass only — the main loop stops before it)
-    auto step = [&](int t, const Slot& q, auto first_tag) __attribute__((always_inline)) {
-        constexpr bool FIRST = decltype(first_tag)::value;
-        const int tt = d ? (T - 1 - t) : t;
-        const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
-        float up[VEC], wp[VEC], sp[VEC], dwx[VEC];
-        q.up.expand(up);
-        if (ADAPT) q.wp.expand(wp);
-        const bool t0 = FIRST && t == 0;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            if (t0) { up[e] = u0v[e]; if (ADAPT) wp[e] = w0v[e]; }
-            sp[e] = t0 ? s0v[e] : (spike_of(up[e], c.theta) ? 1.0f : 0.0f);
-        }
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
-            const float gs = (q.g[e] + gr[e]) * k;
-            float ds = gs - al[e] * du_n[e];
-            if (ADAPT) ds = ds + pb[e] * dw_n[e];
-            const float xs = u_t[e] - c.theta;
-            float du = boxcar_gate(ds, xs) + al[e] * du_n[e];            // snns.py:33-35
-            if (ADAPT) du = du + pa[e] * dw_n[e];
-            dwx[e] = oma[e] * du;
-            if (BN) {  // BatchNorm backward's column sums (dy = dWx, xhat = (x - mean) * invstd)
-                acc_dy[e] += dwx[e];
-                acc_dyx[e] += dwx[e] * ((q.xr[BN ? e : 0] - bn_mu[e]) * bn_is[e]);
-            }
-            const float qq = up[e] - sp[e];
-            acc_al[e] += du * (qq - u_t[e]);  // d u_t / d alpha = (q - u_t)/(1-alpha); scaled at the end
-            if (ADAPT) {
-                const float dw = be[e] * dw_n[e] - dwx[e];
-                acc_be[e] += dw * wp[e];
-                acc_a[e] += dw * up[e];
-                acc_b[e] += dw * sp[e];
-                dw_n[e] = dw;
-            }
-            du_n[e] = du;
-            // carried into the next step as a COPY made here: kept in the slot's own register the value outlives the
-            // slot's refill, the refill needs another register, and hipcc shuffles the whole ring through `v_mov`s in
-            // mid-loop — each of which waits for a load issued a few operations earlier
-            asm volatile("v_mov_b32 %0, %1" : "=&v"(u_t[e]) : "v"(up[e]));
-        }
-        stv<VEC>(c.dWx + ((size_t)bp * T + tt) * H + h, dwx);
-    };
-
-    Slot ring[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) fetch(ring[j], T - 1 - j);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // see the forward kernel
-    int i0 = 0;  // reverse index: step t = T - 1 - i
-    for (; i0 + D <= T - 1; i0 += D) {  // steps t >= 1 only
-#pragma unroll
-        for (int j = 0; j < D; ++j) {  // consume, then refill (see the forward kernel)
-            step(T - 1 - (i0 + j), ring[j], std::false_type{});
-            fetch(ring[j], T - 1 - (i0 + j + D));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        if (i0 + j >= T) break;
-        step(T - 1 - (i0 + j), ring[j], std::true_type{});
-    }
-    const size_t plane = (size_t)Bp * H;
-    float* ws = c.dparam_ws + (size_t)bp * H + h;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc_al[e] = acc_al[e] / oma[e];
-    stv<VEC>(ws, acc_al);
-    if (ADAPT) {
-        stv<VEC>(ws + plane, acc_be);
-        stv<VEC>(ws + 2 * plane, acc_a);
-        stv<VEC>(ws + 3 * plane, acc_b);
-    }
-    if (BN) {
-        stv<VEC>(ws + 4 * plane, acc_dy);
-        stv<VEC>(ws + 5 * plane, acc_dyx);
-    }
-}
+__global__ __launch_bounds__(256) void cell_bwd_pipe_kernel(CellArgs c)
+#define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+template <bool ADAPT, int VEC, bool BN, bool DROP, bool S16 = false>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_sg_kernel(CellArgs c, SurrogateArgs sg)
+#define SURROGATE_GATE(ds, x) smooth_gate(sg.id, sg.k, ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
 
 // ------------------------------------------------------------------ readout cell
 // Readout layer (snns.py:815-825): u_t = alpha u_{t-1} + (1-alpha) x_t, out = sum_t softmax_c(u_t).
@@ -642,7 +528,15 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
 }
 
 template <bool ADAPT, int VEC, bool DROP>
-void launch_cell_pipe(bool bwd, const CellArgs& c, unsigned blocks, hipStream_t st) {
+void launch_cell_pipe(bool bwd, const CellArgs& c, const SurrogateArgs& sg, unsigned blocks, hipStream_t st) {
+    if (bwd && sg.id != SPARCH_SURROGATE_BOXCAR) {  // (fp32 saves: the entry point has refused bf16 ones)
+        auto go = [&](auto bn) {
+            hipLaunchKernelGGL((cell_bwd_pipe_sg_kernel<ADAPT, VEC, decltype(bn)::value, DROP>), dim3(blocks), dim3(256), 0,
+                               st, c, sg);
+        };
+        if (c.bn_x) go(std::true_type{}); else go(std::false_type{});
+        return;
+    }
     if (bwd) {
         auto go = [&](auto s16, auto bn) {
             hipLaunchKernelGGL((cell_bwd_pipe_kernel<ADAPT, VEC, decltype(s16)::value, decltype(bn)::value, DROP>),
@@ -668,7 +562,7 @@ void launch_cell_pipe(bool bwd, const CellArgs& c, unsigned blocks, hipStream_t 
 }
 
 template <bool ADAPT>
-int launch_cell(bool bwd, CellArgs& c, hipStream_t st) {
+int launch_cell(bool bwd, CellArgs& c, hipStream_t st, const SurrogateArgs sg = {}) {
     const long long work = (long long)c.B * c.dirs * c.H;
     const bool vec_ok = (c.H % 4 == 0);
     // VEC=4 only when it still leaves >= 8 waves per CU; small problems favour more threads
@@ -676,8 +570,8 @@ int launch_cell(bool bwd, CellArgs& c, hipStream_t st) {
     const long long threads = vec4 ? work / 4 : work;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
     const bool drop = c.p_drop > 0.0f;
-    if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true>(bwd, c, blocks, st); else launch_cell_pipe<ADAPT, 4, false>(bwd, c, blocks, st); }
-    else      { if (drop) launch_cell_pipe<ADAPT, 1, true>(bwd, c, blocks, st); else launch_cell_pipe<ADAPT, 1, false>(bwd, c, blocks, st); }
+    if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 4, false>(bwd, c, sg, blocks, st); }
+    else      { if (drop) launch_cell_pipe<ADAPT, 1, true>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 1, false>(bwd, c, sg, blocks, st); }
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -765,13 +659,15 @@ extern "C" int sparch_cell_stream_fwd(int kind, int B, int dirs, int T, int H, c
     return adapt ? launch_cell_stream<true>(c, (hipStream_t)stream) : launch_cell_stream<false>(c, (hipStream_t)stream);
 }
 
-extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
-                               const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
-                               const float* alpha, const float* beta, const float* a, const float* b,
-                               const float* u0, const float* w0, const float* s0, float theta,
-                               float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
-                               const float* bn_mean, const float* bn_invstd, void* stream) {
+extern "C" int sparch_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                  const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                  const float* alpha, const float* beta, const float* a, const float* b,
+                                  const float* u0, const float* w0, const float* s0, float theta,
+                                  float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                                  const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
+                                  void* stream) {
     SPARCH_ENTER();
+    if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
     if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
     if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x))) return SPARCH_EINVAL;
     const bool adapt = kind == SPARCH_KIND_ADLIF;
@@ -791,8 +687,20 @@ extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const fl
     c.g_out = g_out; c.g_rate = g_rate; c.g_rate_scale = 1.0f / ((float)B * (float)T);
     c.dWx = dWx; c.dparam_ws = dparam_ws;
     c.bn_x = bn_x; c.bn_mean = bn_mean; c.bn_invstd = bn_invstd;
-    return adapt ? launch_cell<true>(true, c, (hipStream_t)stream)
-                 : launch_cell<false>(true, c, (hipStream_t)stream);
+    const SurrogateArgs sg{surrogate, surrogate_scale};
+    return adapt ? launch_cell<true>(true, c, (hipStream_t)stream, sg)
+                 : launch_cell<false>(true, c, (hipStream_t)stream, sg);
+}
+
+extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
+                               const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                               const float* alpha, const float* beta, const float* a, const float* b,
+                               const float* u0, const float* w0, const float* s0, float theta,
+                               float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                               const float* bn_mean, const float* bn_invstd, void* stream) {
+    return sparch_cell_bwd_sg(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, u0, w0,
+                              s0, theta, p_drop, seed, dWx, dparam_ws, bn_x, bn_mean, bn_invstd,
+                              SPARCH_SURROGATE_BOXCAR, 0.0f, stream);
 }
 
 extern "C" int sparch_readout_fwd(int B, int T, int C, const float* Wx, const float* scale,

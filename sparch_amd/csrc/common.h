@@ -56,6 +56,31 @@ __device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return
 // outside the box and a NaN x (both comparisons false) passes the gradient through.
 __device__ __forceinline__ float boxcar_gate(float g, float x) { return (x <= -0.5f || x > 0.5f) ? 0.0f : g; }
 
+// The selectable smooth surrogates (SPARCH_SURROGATE_TRIANGLE / FAST_SIGMOID / ATAN): plain
+// products and correctly rounded quotients in exactly this operation order (-ffp-contract=off; the tests restate it in
+// fp32), peak 1 at x = 0, a NaN in g or x propagates.  `id` and `k` are kernel arguments: the switch is wave-uniform.
+// They travel to the kernels that have a smooth gate only, beside CellArgs / RecArgs (which do not grow).
+struct SurrogateArgs { int id; float k; };
+__device__ __forceinline__ float smooth_gate(int id, float k, float g, float x) {
+    if (id == SPARCH_SURROGATE_TRIANGLE) {
+        const float m = 1.0f - k * fabsf(x);
+        return g * (m < 0.0f ? 0.0f : m);  // max(0, m) that keeps a NaN (fmaxf would return 0)
+    }
+    if (id == SPARCH_SURROGATE_FAST_SIGMOID) {
+        const float d = 1.0f + k * fabsf(x);
+        return g / (d * d);
+    }
+    const float kx = k * x;
+    return g / (1.0f + kx * kx);
+}
+// what the _sg entry points check before any device work: a known id, a finite scale > 0 for the smooth forms, and
+// fp32 saves with them (bf16 saves keep the box-car's three decisions, not the continuous u a smooth gate reads)
+static inline bool surrogate_ok(int id, float k, int save_bf16) {
+    if (id == SPARCH_SURROGATE_BOXCAR) return true;
+    if (id != SPARCH_SURROGATE_TRIANGLE && id != SPARCH_SURROGATE_FAST_SIGMOID && id != SPARCH_SURROGATE_ATAN) return false;
+    return k > 0.0f && k <= 3.402823466e38f && !save_bf16;
+}
+
 // ---- optional bf16 storage of the states saved for the backward pass (u, w): half the bytes of the two
 // largest tensors a spiking layer keeps.  The backward takes three DISCRETE decisions from a saved membrane
 // potential — the spike u - theta > 0 and the box-car edges u - theta <= -0.5, u - theta > 0.5 — and those

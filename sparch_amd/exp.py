@@ -36,7 +36,7 @@ from . import functional as Fn
 from .functional import check_status, fbank
 from .parsers import print_model_options, print_training_options
 from .anns import ANN
-from .snns import SNN
+from .snns import SNN, parse_surrogate
 
 logger = logging.getLogger(__name__)
 
@@ -103,6 +103,11 @@ class Experiment:
         self.seq_len = getattr(args, "seq_len", 100)
         self.sync_bn = getattr(args, "sync_bn", False)
         self.compute_dtype = getattr(args, "compute_dtype", "fp32")
+
+        # SPARCH_SURROGATE=name[:scale]: the spiking layers' surrogate gradient (snns.resolve_surrogate).  Parsed once,
+        # here, so that a malformed value is refused before folders, data or device are touched.
+        spec = os.environ.get("SPARCH_SURROGATE", "")
+        self.surrogate = parse_surrogate(spec) if spec.strip() else None
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -275,11 +280,21 @@ class Experiment:
         if self.use_pretrained_model:
             self.net = torch.load(self.load_path, map_location=self.device, weights_only=False)  # our own file
             logging.info(f"\nLoaded model at: {self.load_path}\n {self.net}\n")
+            if self.surrogate is not None:
+                own = (f"{getattr(self.net, 'surrogate', 'boxcar')} (scale {getattr(self.net, 'surrogate_scale', None)})"
+                       if getattr(self.net, "is_snn", False) else "none (not a spiking model)")
+                logging.warning(f"SPARCH_SURROGATE={self.surrogate[0]} is ignored: the loaded model keeps its own "
+                                f"surrogate gradient, {own}")
         elif self.model_type in ["LIF", "adLIF", "RLIF", "RadLIF"]:
+            name, scale = self.surrogate if self.surrogate is not None else ("boxcar", None)
             self.net = SNN(input_shape=input_shape, layer_sizes=layer_sizes, neuron_type=self.model_type,
                            dropout=self.pdrop, normalization=self.normalization, use_bias=self.use_bias,
-                           bidirectional=self.bidirectional, use_readout_layer=True).to(self.device)
+                           bidirectional=self.bidirectional, use_readout_layer=True, surrogate=name,
+                           surrogate_scale=scale).to(self.device)
             logging.info(f"\nCreated new spiking model:\n {self.net}\n")
+            if self.surrogate is not None:
+                logging.info(f"Surrogate gradient: {name}" + ("" if scale is None else f", scale {scale:g}")
+                             + " (SPARCH_SURROGATE)")
         elif self.model_type in ["MLP", "RNN", "LiGRU", "GRU"]:
             # exp.py:311-322: MLP and RNN on the fused / persistent kernels, LiGRU and GRU
             # launch-per-step
@@ -287,6 +302,8 @@ class Experiment:
                            dropout=self.pdrop, normalization=self.normalization, use_bias=self.use_bias,
                            bidirectional=self.bidirectional, use_readout_layer=True).to(self.device)
             logging.info(f"\nCreated new non-spiking model:\n {self.net}\n")
+            if self.surrogate is not None:
+                logging.warning(f"SPARCH_SURROGATE is ignored: {self.model_type} has no spike function")
         else:
             raise ValueError(f"Invalid model type {self.model_type}")
         if self.world > 1:  # identical initial replicas

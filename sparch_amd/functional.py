@@ -709,14 +709,14 @@ def spike_placeholder(B, T, F, device):
     return z.expand(B, T, F)
 
 
-def _persistent(label, entry, lead, nbytes, dev, L, *tail):
+def _persistent(label, entry, lead, nbytes, dev, L, *tail, sg=None):
     """One persistent recurrent launch (a kernel whose workgroups wait for each other): `entry`(*lead, channel buffer
-    of `nbytes`, its size, status word, L time steps per launch, stream, *tail) inside `_persistent_launch()`, timed
-    under `label` (None: not timed)."""
+    of `nbytes`, its size, status word, L time steps per launch, [*sg: surrogate id and scale of an `_sg` entry,]
+    stream, *tail) inside `_persistent_launch()`, timed under `label` (None: not timed)."""
     chan = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)  # (ceil: the byte count need not be a multiple of 8)
     tok = timer.start(label) if label is not None else None
     with _persistent_launch():
-        check(getattr(lib, entry)(*lead, ptr(chan), nbytes, ptr(status_word(dev)), L, _stream(), *tail), entry)
+        check(getattr(lib, entry)(*lead, ptr(chan), nbytes, ptr(status_word(dev)), L, *(sg or ()), _stream(), *tail), entry)
     timer.stop(tok)
 
 
@@ -728,8 +728,22 @@ def _vpack(H, V, flags, vmask=None):
     return vpack
 
 
+SURROGATES = {"boxcar": 0, "triangle": 1, "fast_sigmoid": 2, "atan": 3}  # SPARCH_SURROGATE_*
+
+
+def surrogate_args(surrogate):
+    """None or ("name", scale) -> None for the reference's box-car, else (SPARCH_SURROGATE_* id, scale) of a smooth
+    form (the forward pass is the same under every surrogate; the smooth ones run the `_sg` backward entry points)."""
+    if surrogate is None or surrogate[0] == "boxcar":
+        return None
+    name, scale = surrogate
+    if name not in SURROGATES:
+        raise ValueError(f"unknown surrogate {name!r}: one of {sorted(SURROGATES)}")
+    return SURROGATES[name], float(scale)
+
+
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
-                 want_s_out=True, want_saves=True):
+                 want_s_out=True, want_saves=True, surrogate=None):
     """Run one spiking cell over the whole sequence on the device.
 
     Wx (B,T,H) raw projection (+ optional per-column scale/shift); u0/w0/s0 (B*dirs,H).
@@ -739,7 +753,8 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     (the reference materialises it because its next op is a dense nn.Linear, snns.py:261; here it was 4 of the
     14 bytes a recurrent forward step stores per element).  want_saves=False (LIF / adLIF, nothing will be
     differentiated — validation and test forwards, exp.py:405-518): u / w are not saved either (8 of an adLIF step's
-    14 bytes); `saved` is then (None, None)."""
+    14 bytes); `saved` is then (None, None).  surrogate: with a smooth form the saves stay fp32 whatever
+    SPARCH_SAVE_DTYPE says — a bf16 save keeps the box-car's three decisions, not the u a smooth gate reads."""
     _, T, H = Wx.shape
     Bp = B * dirs
     dev = Wx.device
@@ -752,6 +767,8 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     # bf16 saves: the recurrent kernels take them for whole-sequence launches only (a chunked forward resumes
     # from the saved state, which must then be exact)
     save16 = SAVE_BF16 and H % 4 == 0 and (not recurrent or (L >= T and not rec_step_path(H)))
+    if surrogate_args(surrogate) is not None:
+        save16 = False
     sdt = torch.bfloat16 if save16 else torch.float32
     want_saves = want_saves or recurrent  # (the recurrent kernels always save)
     u_save = torch.empty(Bp, T, H, dtype=sdt, device=dev) if want_saves else None
@@ -774,7 +791,8 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
             pp = {k_: (torch.nn.functional.pad(v, (0, H4 - H, 0, H4 - H)) if k_ == "V" else padh(v)) for k_, v in p.items()}
             s_p, count_p, saved_p, s16_p = cell_forward(kind, padh(Wx), padh(scale), padh(shift), pp, padh(u0), padh(w0),
                                                         padh(s0), B=B, dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
-                                                        steps_per_launch=steps_per_launch, want_s_out=want_s_out)
+                                                        steps_per_launch=steps_per_launch, want_s_out=want_s_out,
+                                                        surrogate=surrogate)
             cut = lambda t_: None if t_ is None else t_.view(B, T, dirs, H4)[..., :H].reshape(B, T, dirs * H).contiguous()  # noqa: E731
             return (cut(s_p), count_p.view(dirs, H4)[:, :H].reshape(-1).contiguous(), saved_p, cut(s16_p))
         V = p["V"]
@@ -815,10 +833,13 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
 
 
 def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, theta, p_drop, seed,
-                  steps_per_launch=None, bn=None):
+                  steps_per_launch=None, bn=None, surrogate=None):
     """Reverse-time pass.  Returns dWx (B*dirs,T,H) [virtual rows, original time index],
     param grads dict (alpha[,beta,a,b][,V]) — plus, with bn = (Wx_raw (B,T,H), mean, invstd), the entry
-    "bn_sums" = (dbeta, dgamma): BatchNorm backward's column sums, accumulated by the same kernel."""
+    "bn_sums" = (dbeta, dgamma): BatchNorm backward's column sums, accumulated by the same kernel.
+    surrogate: None or ("name", scale).  None / "boxcar" issue the calls they always did; a smooth form issues the
+    `_sg` entry points with (id, scale) in front of the stream (timer labels unchanged)."""
+    sg = surrogate_args(surrogate)
     Bp = B * dirs
     dev = g_out.device
     k = KIND[kind]
@@ -831,7 +852,8 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         g_p = padh(g_out.reshape(B, T, dirs, H)).reshape(B, T, dirs * H4)
         gr_p = None if g_rate is None else padh(g_rate.reshape(dirs, H)).reshape(dirs * H4)
         dWx_p, gp = cell_backward(kind, g_p, gr_p, pp, padh(u0), padh(w0), padh(s0), saved, B=B, dirs=dirs, T=T, H=H4,
-                                  theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None)
+                                  theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
+                                  surrogate=surrogate)
         grads = {k_: (v[:H, :H].contiguous() if k_ == "V" else v[:H].contiguous()) for k_, v in gp.items()}
         return dWx_p[..., :H].contiguous(), grads
     vpack_fwd_made = saved[2] if len(saved) > 2 else None  # backward fragments of V packed by cell_forward
@@ -843,10 +865,14 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
     grads = {}
     if not recurrent:
         tok = timer.start(f"cell_bwd[{kind}]")
-        check(lib.sparch_cell_bwd(k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
-                                  ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
-                                  ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
-                                  ptr(bn_invstd), _stream()), "sparch_cell_bwd")
+        lead = (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
+                ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
+                ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
+                ptr(bn_invstd))
+        if sg is None:
+            check(lib.sparch_cell_bwd(*lead, _stream()), "sparch_cell_bwd")
+        else:
+            check(lib.sparch_cell_bwd_sg(*lead, *sg, _stream()), "sparch_cell_bwd_sg")
         timer.stop(tok)
     else:
         V = p["V"]
@@ -861,22 +887,26 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
             for t in range(T - 1, -1, -1):
                 if t + 1 < T:
                     rec, _ = gemm_nt(dwx_step, vmask)     # rec[b,i] = sum_j dWx[b,j] Vm[i,j]
-                check(lib.sparch_rec_cell_step_bwd(k, B, dirs, T, H, t, ptr(g_out), ptr(g_rate), ptr(u_save),
-                                                   ptr(w_save), ptr(p["alpha"]), ptr(p.get("beta")),
-                                                   ptr(p.get("a")), ptr(p.get("b")), ptr(rec), ptr(u0), ptr(w0),
-                                                   ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws),
-                                                   ptr(bn_x), ptr(bn_mean), ptr(bn_invstd), ptr(dwx_step),
-                                                   _stream()), "sparch_rec_cell_step_bwd")
+                lead = (k, B, dirs, T, H, t, ptr(g_out), ptr(g_rate), ptr(u_save),
+                        ptr(w_save), ptr(p["alpha"]), ptr(p.get("beta")),
+                        ptr(p.get("a")), ptr(p.get("b")), ptr(rec), ptr(u0), ptr(w0),
+                        ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws),
+                        ptr(bn_x), ptr(bn_mean), ptr(bn_invstd), ptr(dwx_step))
+                if sg is None:
+                    check(lib.sparch_rec_cell_step_bwd(*lead, _stream()), "sparch_rec_cell_step_bwd")
+                else:
+                    check(lib.sparch_rec_cell_step_bwd_sg(*lead, *sg, _stream()), "sparch_rec_cell_step_bwd_sg")
             timer.stop(tok)
         else:
             vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
-            _persistent(f"rec_cell_bwd[{kind}]", "sparch_rec_cell_bwd",
+            _persistent(f"rec_cell_bwd[{kind}]", "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg",
                         (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
                          ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack_t), ptr(u0),
                          ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws), ptr(bn_x), ptr(bn_mean),
                          ptr(bn_invstd)),
                         lib.sparch_rec_chan_bytes(Bp, T, H), dev,
-                        steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec())
+                        steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec(),
+                        sg=sg)
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
@@ -924,7 +954,8 @@ class SpikingLayerFn(torch.autograd.Function):
         s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
                                                 dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                 want_s_out=cfg.get("fp32_out", True),
-                                                want_saves=any(ctx.needs_input_grad))
+                                                want_saves=any(ctx.needs_input_grad),
+                                                surrogate=cfg.get("surrogate"))
         if s_out is None:
             s_out = spike_placeholder(B, T, H * dirs, x.device)
         inv_keep = 1.0 / (1.0 - p_drop)
@@ -955,7 +986,8 @@ class SpikingLayerFn(torch.autograd.Function):
         # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
-                                theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn)
+                                theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn,
+                                surrogate=cfg.get("surrogate"))
         ctx.cell_saved = None
         dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
@@ -1024,14 +1056,16 @@ class SpikingCellFn(torch.autograd.Function):
     Mirrors the reference's `_lif_cell`/`_adlif_cell`/`_rlif_cell`/`_radlif_cell` methods."""
 
     @staticmethod
-    def forward(ctx, kind, theta, Wx, alpha, beta, a, b, V, u0, w0, s0, steps_per_launch=None):
+    def forward(ctx, kind, theta, Wx, alpha, beta, a, b, V, u0, w0, s0, steps_per_launch=None, surrogate=None):
         _require_device(Wx, "Wx")
         Wx = _f32c(Wx)
         Bp, T, H = Wx.shape
         p = {k_: v for k_, v in dict(alpha=alpha, beta=beta, a=a, b=b, V=V).items() if v is not None}
         s, _, saved, _ = cell_forward(kind, Wx, None, None, p, u0, w0, s0, B=Bp, dirs=1, theta=theta, p_drop=0.0,
-                                      seed=0, steps_per_launch=steps_per_launch, want_saves=any(ctx.needs_input_grad))
+                                      seed=0, steps_per_launch=steps_per_launch, want_saves=any(ctx.needs_input_grad),
+                                      surrogate=surrogate)
         ctx.kind, ctx.theta, ctx.dims, ctx.cell_saved, ctx.spl = kind, theta, (Bp, T, H), saved, steps_per_launch
+        ctx.surrogate = surrogate
         ctx.save_for_backward(alpha, beta, a, b, V, u0, w0, s0)
         return s
 
@@ -1041,9 +1075,10 @@ class SpikingCellFn(torch.autograd.Function):
         Bp, T, H = ctx.dims
         p = {k_: v for k_, v in dict(alpha=alpha, beta=beta, a=a, b=b, V=V).items() if v is not None}
         dWx, pg = cell_backward(ctx.kind, _f32c(g_s), None, p, u0, w0, s0, ctx.cell_saved, B=Bp, dirs=1, T=T,
-                                H=H, theta=ctx.theta, p_drop=0.0, seed=0, steps_per_launch=ctx.spl)
+                                H=H, theta=ctx.theta, p_drop=0.0, seed=0, steps_per_launch=ctx.spl,
+                                surrogate=ctx.surrogate)
         return (None, None, dWx, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"), pg.get("V"),
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 class ReadoutCellFn(torch.autograd.Function):

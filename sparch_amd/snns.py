@@ -48,6 +48,86 @@ class SpikeFunctionBoxcar(torch.autograd.Function):
         return grad_x
 
 
+# The selectable surrogates: name -> the scale k a bare name stands for, chosen so that the
+# area under the gate is the box-car's 1 (triangle 1/k, fast sigmoid 2/k, arctangent pi/k).  Derived, not tuned.
+SURROGATE_DEFAULT_SCALE = {"boxcar": None, "triangle": 1.0, "fast_sigmoid": 2.0, "atan": math.pi}
+
+
+def resolve_surrogate(surrogate="boxcar", surrogate_scale=None):
+    """(name, scale) checked and completed: the default scale for a bare name; ValueError for an unknown name, a
+    scale that is not a finite number > 0, or any scale with the box-car (which has none)."""
+    names = ", ".join(SURROGATE_DEFAULT_SCALE)
+    if surrogate not in SURROGATE_DEFAULT_SCALE:
+        raise ValueError(f"unknown surrogate {surrogate!r}: one of {names}")
+    if surrogate == "boxcar":
+        if surrogate_scale is not None:
+            raise ValueError(f"the boxcar surrogate takes no scale (got {surrogate_scale!r}); surrogates: {names}")
+        return "boxcar", None
+    if surrogate_scale is None:
+        return surrogate, SURROGATE_DEFAULT_SCALE[surrogate]
+    try:
+        k = float(surrogate_scale)
+    except (TypeError, ValueError):
+        k = float("nan")
+    if not (k > 0.0 and math.isfinite(k)):
+        raise ValueError(f"surrogate_scale must be a finite number > 0 (got {surrogate_scale!r}); surrogates: {names}")
+    return surrogate, k
+
+
+def parse_surrogate(text):
+    """`name[:scale]` (the SPARCH_SURROGATE environment variable) -> (name, scale) as resolve_surrogate returns it."""
+    name, sep, scale = text.strip().partition(":")
+    if sep and not scale.strip():
+        raise ValueError(f"malformed surrogate {text!r}: expected name[:scale]")
+    if sep:
+        try:
+            scale = float(scale)
+        except ValueError:
+            raise ValueError(f"malformed surrogate {text!r}: the scale is not a number") from None
+    return resolve_surrogate(name.strip(), scale if sep else None)
+
+
+class SpikeFunctionSurrogate(torch.autograd.Function):
+    """Heaviside step `x > 0` with a selectable surrogate gradient, in plain torch and in x's own dtype:
+    SpikeFunctionSurrogate.apply(x, name, scale).  "boxcar" is SpikeFunctionBoxcar's rule (assignment); the smooth
+    forms multiply: triangle max(0, 1 - k|x|), fast_sigmoid 1 / (1 + k|x|)^2, atan 1 / (1 + (k x)^2).
+    Inside the layers the pair is fused into the cell kernels (csrc/common.h smooth_gate)."""
+
+    @staticmethod
+    def forward(ctx, x, name="boxcar", scale=None):
+        ctx.save_for_backward(x)
+        ctx.surrogate = resolve_surrogate(name, scale)
+        return (x > 0).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_spikes):
+        (x,) = ctx.saved_tensors
+        name, k = ctx.surrogate
+        if name == "boxcar":
+            grad_x = grad_spikes.clone()
+            grad_x[x <= -0.5] = 0
+            grad_x[x > 0.5] = 0
+        elif name == "triangle":
+            grad_x = grad_spikes * torch.clamp(1 - k * x.abs(), min=0)
+        elif name == "fast_sigmoid":
+            d = 1 + k * x.abs()
+            grad_x = grad_spikes / (d * d)
+        else:
+            kx = k * x
+            grad_x = grad_spikes / (1 + kx * kx)
+        return grad_x, None, None
+
+
+class _SurrogateSpike:
+    """`spike_fct` of a layer with a smooth surrogate: x -> SpikeFunctionSurrogate.apply(x, name, scale) (picklable)."""
+
+    def __init__(self, name, scale):
+        self.name, self.scale = name, scale
+
+    def __call__(self, x):
+        return SpikeFunctionSurrogate.apply(x, self.name, self.scale)
+
+
 def _tag_spikes(s, scale, s16, placeholder=False):
     """Mark `s` as a spike train of ours (entries 0 or `scale`, `s16` the same spikes as a bf16 0/1 plane) so
     that the next layer can take the exact spike GEMMs.  The tag carries the tensor's version counter: an
@@ -298,8 +378,10 @@ class _SpikingLayer(nn.Module):
     kind = None  # set by subclasses
 
     def __init__(self, input_size, hidden_size, batch_size, threshold=1.0, dropout=0.0,
-                 normalization="batchnorm", use_bias=False, bidirectional=False):
+                 normalization="batchnorm", use_bias=False, bidirectional=False, surrogate="boxcar",
+                 surrogate_scale=None):
         super().__init__()
+        self.surrogate, self.surrogate_scale = resolve_surrogate(surrogate, surrogate_scale)
         adaptive = self.kind in ("adLIF", "RadLIF")
         recurrent = self.kind in ("RLIF", "RadLIF")
 
@@ -316,7 +398,8 @@ class _SpikingLayer(nn.Module):
             self.beta_lim = [math.exp(-1 / 30), math.exp(-1 / 120)]
             self.a_lim = [-1.0, 1.0]
             self.b_lim = [0.0, 2.0]
-        self.spike_fct = SpikeFunctionBoxcar.apply
+        self.spike_fct = (SpikeFunctionBoxcar.apply if self.surrogate == "boxcar"
+                          else _SurrogateSpike(self.surrogate, self.surrogate_scale))
 
         # Parameters, created and initialised in the reference's order so that identical
         # seeds give identical initial weights (snns.py:233-235, 363-372, 502-507, 638-649).
@@ -381,6 +464,16 @@ class _SpikingLayer(nn.Module):
         base = torch.cuda.initial_seed() if device.type == "cuda" else torch.initial_seed()
         return (base * 0x9E3779B97F4A7C15 + (index + 1) * 0x100000001B3 + self._calls) & 0x7FFFFFFFFFFFFFFF
 
+    def _surrogate(self):
+        """None for the box-car (also: a module un-pickled from a checkpoint that predates the setting, or from the
+        reference's), else ("name", scale) as the functional layer takes it."""
+        name = getattr(self, "surrogate", "boxcar")
+        return None if name == "boxcar" else (name, float(getattr(self, "surrogate_scale", None)))
+
+    def extra_repr(self):
+        sg = self._surrogate()
+        return "" if sg is None else f"surrogate={sg[0]}, surrogate_scale={sg[1]:g}"
+
     def _cell_params(self):
         p = {"alpha": self.alpha}
         if self.kind in ("adLIF", "RadLIF"):
@@ -427,6 +520,8 @@ class _SpikingLayer(nn.Module):
             "in_plane": Fn.input_plane_of(x) if in_scale is None else None,
             # BatchNorm1d's counter: advanced by the statistics kernel (no separate launch; not on skipped steps)
             "num_batches_tracked": self.norm.num_batches_tracked if (is_bn and self.training) else None,
+            # the backward's surrogate: None = the reference's box-car, else ("name", scale) — fp32 saves then
+            "surrogate": self._surrogate(),
         }
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
@@ -448,7 +543,7 @@ class _SpikingLayer(nn.Module):
         u0, w0, s0 = self._draw_states(Wx.shape[0], Wx.device)
         p = self._cell_params()
         return Fn.SpikingCellFn.apply(self.kind, float(self.threshold), Wx, p["alpha"], p.get("beta"),
-                                      p.get("a"), p.get("b"), p.get("V"), u0, w0, s0, None)
+                                      p.get("a"), p.get("b"), p.get("V"), u0, w0, s0, None, self._surrogate())
 
 
 class LIFLayer(_SpikingLayer):
@@ -550,8 +645,10 @@ class SNN(nn.Module):
         (batch, time, feats); firing_rates has one entry per hidden neuron (all layers)."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
-                 normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True):
+                 normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
+                 surrogate="boxcar", surrogate_scale=None):
         super().__init__()
+        self.surrogate, self.surrogate_scale = resolve_surrogate(surrogate, surrogate_scale)
         self.reshape = len(input_shape) > 3
         self.input_size = float(torch.prod(torch.tensor(input_shape[2:])))
         self.batch_size = input_shape[0]
@@ -581,7 +678,8 @@ class SNN(nn.Module):
             layers.append(layer_cls(
                 input_size=fan_in, hidden_size=self.layer_sizes[i], batch_size=self.batch_size,
                 threshold=self.threshold, dropout=self.dropout, normalization=self.normalization,
-                use_bias=self.use_bias, bidirectional=self.bidirectional))
+                use_bias=self.use_bias, bidirectional=self.bidirectional, surrogate=self.surrogate,
+                surrogate_scale=self.surrogate_scale))
             layers[-1]._layer_index = i
             fan_in = self.layer_sizes[i] * (1 + self.bidirectional)
         if self.use_readout_layer:
@@ -589,6 +687,10 @@ class SNN(nn.Module):
                 input_size=fan_in, hidden_size=self.layer_sizes[-1], batch_size=self.batch_size,
                 dropout=self.dropout, normalization=self.normalization, use_bias=self.use_bias))
         return layers
+
+    def extra_repr(self):
+        name = getattr(self, "surrogate", "boxcar")
+        return "" if name == "boxcar" else f"surrogate={name}, surrogate_scale={getattr(self, 'surrogate_scale', None):g}"
 
     def draw_states(self, batch, device, out=None):
         """Every layer's initial states for one forward, drawn from torch's global CPU generator in the
