@@ -6,7 +6,7 @@ tests/test_gemm_numpy_host.py shows that the bound sees a lost bf16 plane term. 
 Model of a product (what a kernel may legitimately do), C = scale * sum over terms (i, j) of a_i @ b_j, per operand:
   spike    (fp32 0 / c, or a bf16 0/1 plane)          one plane (x != 0); c goes into `scale`
   exact    (the flagged operand of *_auto*_f1)         one plane, the values themselves
-  dense    fp32 mode: the three planes of the truncation split (tests/test_gemm_layouts_gpu.split3_host)
+  dense    fp32 mode: the three planes of the truncation split (tests/kit.split3_host)
            bf16 mode: one plane, rounded once to nearest-even
   fp32 MFMA (gemm.hip)                                 one "plane", the fp32 values
 dense x dense on three planes keeps six terms, smallest first: a1 b1, a2 b0, a0 b2, a1 b0, a0 b1, a0 b0; one plane
@@ -29,7 +29,8 @@ import zlib
 
 import numpy as np
 
-F32, F64 = np.float32, np.float64
+from tests.kit import F32, F64
+
 KB = 32
 C_SPK = 1.25
 STAT_ROWS = 128
@@ -38,7 +39,7 @@ TENSORS = ("C", "sum", "sq")
 SHAPES = {"sweep": (37, 35, 41), "mid": (130, 131, 70), "fast": (384, 384, 288), "ktail": (384, 384, 300),
           "stats": (256, 256, 256), "split": (96, 96, 520), "fastsplit": (384, 384, 520)}
 
-# The 26 entry rows of tests/test_gemm_layouts_gpu.ENTRY_NAMES: form, what A and B are (that file's vocabulary), the
+# The 26 entry rows of tests/gemm_cases.ENTRY_NAMES: form, what A and B are (that file's vocabulary), the
 # flag of the gated entries, which rule cuts the product into K ranges (None: never cut), the tile the rule counts.
 _E = types.SimpleNamespace
 ENTRIES = {
@@ -140,9 +141,9 @@ def bf16_trunc(x):
 
 
 def split3(x):
-    """The three planes of tests/test_gemm_layouts_gpu.split3_host as fp32 arrays (not a second split)."""
+    """The three planes of tests/kit.split3_host as fp32 arrays (not a second split)."""
     t = _torch()
-    from tests.test_gemm_layouts_gpu import split3_host
+    from tests.kit import split3_host
     x = np.array(x, dtype=F32)       # (a writable copy: torch refuses read-only arrays)
     return tuple(split3_host(t.from_numpy(x)).to(t.float32).numpy().reshape((3,) + x.shape))
 

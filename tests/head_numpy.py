@@ -25,10 +25,10 @@ import math
 import numpy as np
 
 from tests.dropout_numpy import keep_mask
+from tests.kit import F32
 
 U = 2.0 ** -24
 TINY = 2.0 ** -126
-F32 = np.float32
 
 
 def _f64(a):

@@ -108,6 +108,14 @@ def layernorm_bwd_terms(dy, x, mu, rstd):
 
 
 # ---------------------------------------------------------------------------------------------- column sums
+def edge_values(lo, hi):
+    """fp32 values around a clamp range: inside, the two ends, one ulp outside each, NaN."""
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    return np.array([0.5 * (lo32 + hi32), lo32, hi32, np.nextafter(lo32, np.float32(-np.inf)),
+                     np.nextafter(hi32, np.float32(np.inf)), np.nan, np.nextafter(lo32, np.float32(np.inf)),
+                     np.nextafter(hi32, np.float32(-np.inf))], dtype=np.float32)
+
+
 def clamp_gate(raw, lo, hi):
     """1 where torch.clamp(raw, lo, hi) passes its gradient: lo <= raw <= hi, both ends included; 0 for NaN."""
     raw = _f64(raw)
@@ -130,10 +138,10 @@ def colsum_clamped(ws, raws=None, lims=None):
 # ---------------------------------------------------------------------------------------------- bf16 planes
 def split3_planes(x):
     """The exact truncation split x = p0 + p1 + p2 of an fp32 array (M, H) as (3, M, H) uint16 bf16 bit patterns —
-    the helper of tests/test_gemm_layouts_gpu.py (sparch_split3's restatement), not a second one."""
+    tests/kit.split3_host (sparch_split3's restatement), not a second one."""
     import torch
 
-    from tests.test_gemm_layouts_gpu import split3_host
+    from tests.kit import split3_host
     x = np.ascontiguousarray(x, dtype=np.float32)
     p = split3_host(torch.from_numpy(x))                     # (3 * M, H) bf16
     return p.view(torch.int16).numpy().view(np.uint16).reshape((3,) + x.shape)

@@ -50,7 +50,8 @@ import math
 
 import numpy as np
 
-F32, F64 = np.float32, np.float64
+from tests.kit import F32, F64
+
 KINDS = ("LIF", "adLIF", "RLIF", "RadLIF")
 ADAPTIVE = {"LIF": False, "adLIF": True, "RLIF": False, "RadLIF": True}
 RECURRENT = {"LIF": False, "adLIF": False, "RLIF": True, "RadLIF": True}
@@ -127,10 +128,10 @@ def save_u16(u, theta):
 
 def split3(x):
     """The exact TRUNCATION split x = t1 + t2 + t3 of an fp32 array as three fp32 arrays (what the backward kernels do
-    to dWx; tests/test_gemm_layouts_gpu.split3_host, not a second restatement)."""
+    to dWx; tests/kit.split3_host, not a second restatement)."""
     import torch
 
-    from tests.test_gemm_layouts_gpu import split3_host
+    from tests.kit import split3_host
     x = np.ascontiguousarray(x, dtype=F32)
     p = split3_host(torch.from_numpy(x.reshape(-1, x.shape[-1]))).to(torch.float32).numpy()
     return tuple(p.reshape((3,) + x.shape))
@@ -294,7 +295,7 @@ def teacher_forced_forward(kind, dtype, Wx, scale, shift, p, u0, w0, s0, u_save,
 
 # ------------------------------------------------------------------------------------------------ backward
 def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, dirs, theta=1.0, k_order=None,
-             operand=None, rec_operand=None, rec_product=None, bn=None, keep=None, row_order=None, mutant=None):
+             operand=None, rec_operand=None, rec_product=None, bn=None, keep=None, row_order=None, mutant=None, gate=None):
     """The reverse recurrences on supplied saves (module docstring).  g_out (B,T,H*dirs); g_rate (H*dirs) or None;
     u_save / w_save (Bp,T,H) in cell time order.  rec_operand: (Bp,T,H) at the original time index, the dWx values
     the dense products read; rec_product(dwx, VmT, k_order) replaces dWx @ Vm^T (the host test's mutant).
@@ -303,6 +304,8 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
     row_order None: the sums over the virtual rows (parameter gradients, bn_sums) are numpy's; "asc" / "desc": added
     up row by row in that order, in `dtype` (bn_sums: first over the steps of a row in reverse cell time, as the
     kernels accumulate them).  mutant (tests/test_spiking_numpy_host.py only): one of SCAN_MUTANTS.
+    gate None: the box-car; else gate(ds, x) is the surrogate gradient's gate (tests/surrogate_numpy.py), x = u_t - theta
+    taken in the save's own type and widened to `dtype`.
     Returns dWx (Bp,T,H) at the original time index, the per-row partials ws_alpha [ws_beta, ws_a, ws_b] (Bp,H), the
     gradients alpha [beta, a, b] [V] and, with bn, bn_sums = (sum dWx, sum dWx xhat)."""
     assert mutant is None or mutant in SCAN_MUTANTS, mutant
@@ -323,6 +326,7 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
     XS = us - us.dtype.type(theta)
     S = (XS > 0).astype(dtype)
     SHUT = (XS <= us.dtype.type(-0.5)) | (XS > us.dtype.type(0.5))
+    X = None if gate is None else XS.astype(dtype)
     W = np.asarray(w_save, dtype=dtype) if P.adaptive else None
     u0, s0 = np.asarray(u0, dtype=dtype), np.asarray(s0, dtype=dtype)
     w0 = np.asarray(w0, dtype=dtype) if P.adaptive else None
@@ -342,7 +346,7 @@ def backward(kind, dtype, g_out, g_rate, u_save, w_save, p, u0, w0, s0, *, B, di
         if P.recurrent and t + 1 < T:
             x_op = P.op(dwx_next if rec_op is None else rec_op[:, t + 1])
             ds = ds + (rec_product or matmul_blocks)(x_op, P.VmT, k_order)
-        du = np.where(SHUT[:, t], dtype(0), ds) + aldu
+        du = (np.where(SHUT[:, t], dtype(0), ds) if gate is None else gate(ds, X[:, t])) + aldu
         if P.adaptive:
             du = du + P.a * dw_n
         dwx = P.oma * du
@@ -516,13 +520,13 @@ SCAN_KINDS = ("LIF", "adLIF")
 SCAN_SHAPES = [(k,) + g[:2] + (T, g[2]) for k in SCAN_KINDS for g, T in ((V4, T_V4), (V1, T_V1), (V1BIG, T_V4), (V1ODD, T_V1))]
 SCAN_SALT = {}              # (kind, B, dirs, T, H) -> added to the seed where the first one broke a condition of the GPU file
 P_DROP = 0.25
+OUTSIDE = {"alpha": (0.5, 1.2), "beta": (0.9, 1.1), "a": (-1.5, 1.5), "b": (-0.5, 2.5)}   # neuron 0 / neuron 1
 
 
 def scan_case(kind, B, dirs, T, H):
     """make_inputs(..., "drive", affine_in=True) with g_rate scaled by B T (as drawn the rate term is 0.3 % of g_out),
     parameter 0 of every neuron parameter below its clamp range and parameter 1 above it, and BatchNorm operands
     bn = (raw projection 0.8 Wx + 0.3, mean ~ U(0.2, 0.6), invstd ~ U(0.5, 1.5))."""
-    from tests.test_spiking_bits_gpu import OUTSIDE
     seed = case_seed(kind, B, dirs, T, H) + SCAN_SALT.get((kind, B, dirs, T, H), 0)
     c = make_inputs(kind, B, dirs, T, H, seed, "drive", affine_in=True)
     c["g_rate"] = c["g_rate"] * F32(B * T)

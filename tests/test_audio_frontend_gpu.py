@@ -11,10 +11,10 @@ import torch
 
 from oracle import fbank_numpy as fo
 from tests.audio_trees import make_hd_tree, make_sc_tree
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 LENGTHS = [0, 399, 400, 559, 560, 12345, 16000, 23999]
 LD = 24000
 

@@ -14,10 +14,10 @@ import torch
 
 from tests import flac_writer as fw
 from tests.audio_trees import make_hd_tree, make_sc_tree
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FBANK_LENGTHS = [0, 399, 400, 401, 559, 560, 16000, 16001]
 AUGM_LENGTHS = [0, 1, 2, 399, 400, 5000, 16000, 16001]

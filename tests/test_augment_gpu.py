@@ -11,10 +11,10 @@ import torch
 from tests import augment_numpy as an
 from tests import flac_writer as fw
 from tests.audio_trees import clip_pcm, make_hd_tree, make_sc_tree
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 LENGTHS = [0, 1, 2, 39, 40, 41, 399, 400, 12345, 16000]
 RDS = [(0, 0, 0), (99, 99, 99), (0, 99, 0), (99, 0, 99)]
 

@@ -23,17 +23,17 @@ import torch
 
 from oracle import snn_oracle as orc
 from tests import dropout_numpy as dn
-from tests.test_hip_parity import DEV, _Fn, bf16_mode, relmax  # noqa: F401  (bf16_mode: fixture)
+from tests.kit import DEV, SEED, bf16_mode, relmax  # noqa: F401  (bf16_mode: a fixture)
+from tests.kit import Fn as _Fn
 
 pytestmark = pytest.mark.gpu
 
 ADAPTIVE, RECURRENT = orc.ADAPTIVE, orc.RECURRENT
-SEED = 0x1234567_89ABCDEF  # both 32-bit halves of the seed take part
 
 
 # ---------------------------------------------------------------------------------------------- helpers
 def _case(kind, B, T, H, dirs, seed):
-    """The `_dyadic_cell_case` recipe of tests/test_hip_parity.py (V on a 2^-6 grid, binary s0: every partial sum of
+    """The `dyadic_cell_case` recipe of tests/spiking_cases.py (V on a 2^-6 grid, binary s0: every partial sum of
     s @ V is exact in fp32, so raw spikes cannot depend on summation order) for a layer with `dirs` directions:
     Wx (B,T,H), states (B*dirs,H), upstream gradients g_s (B,T,dirs*H) and g_r (dirs*H).  g_r has every unit
     non-zero and is O(B*T), so that the rate term g_r / (B*T) is as large as g_s and a wrong scale, offset or a
@@ -510,7 +510,7 @@ def test_dyadic_networks_with_dropout_and_regulariser_vs_oracle(name, thresholds
     guaranteed (the last bit of the batch variance depends on summation order), as that test's docstring says."""
     import sparch_amd
     from tests.golden_io import snn_case
-    from tests.test_hip_parity import _run_dyadic
+    from tests.spiking_cases import run_dyadic as _run_dyadic
 
     cfg, x, y, params, init, z = snn_case(name)
     seeds = _layer_seeds(len(cfg["layer_sizes"]) - 1)

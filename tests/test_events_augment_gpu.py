@@ -13,11 +13,14 @@ import torch
 
 from oracle import events_numpy as ev
 from tests import events_augment_numpy as evaug
-from tests.test_events_resident_gpu import _dense, _fake_h5, _samples, _store
+from tests.event_cases import dense as _dense
+from tests.event_cases import fake_h5 as _fake_h5
+from tests.event_cases import samples as _samples
+from tests.event_cases import store as _store
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_TIME = 1.4
 BELOW_ONE = float(np.nextafter(np.float32(1), np.float32(0)))

@@ -8,7 +8,7 @@ import pytest
 
 from oracle import events_numpy as ev
 from tests import events_augment_numpy as evaug
-from tests.test_events_resident_host import fake_h5
+from tests.event_cases import fake_h5
 
 FULL = "shift=40,scale=0.2,offset=0.1,drop=0.1,tmask=0.15,umask=70"
 

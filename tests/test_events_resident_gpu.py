@@ -12,42 +12,15 @@ import pytest
 import torch
 
 from oracle import events_numpy as ev
+from tests.event_cases import dense as _dense
+from tests.event_cases import fake_h5 as _fake_h5
+from tests.event_cases import samples as _samples
+from tests.event_cases import store as _store
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _samples(rng, nb_steps, nb_units, max_time, tdtype, n_random, sort):
-    """(times, units) per sample: an empty one, random ones of up to a few thousand events, and one of hand-made
-    cases — events exactly on edges, duplicates, t < 0, t >= max_time, units out of range."""
-    edges = np.linspace(0, max_time, nb_steps)
-    out = [(np.zeros(0, tdtype), np.zeros(0, np.int64))]
-    for i in range(n_random):
-        m = int(rng.integers(1, 6000 if i % 3 == 0 else 300))
-        out.append((rng.uniform(0, max_time, m).astype(tdtype), rng.integers(0, nb_units, m)))
-    on_edge = edges[[0, 1, nb_steps // 2, nb_steps - 1]].astype(tdtype)           # rounded to the store's format
-    below = np.nextafter(on_edge[1:2], tdtype(0))
-    t = np.concatenate([on_edge, below, np.array([0.7, 0.7, 0.7, 0.7, -0.1, -1e-3, max_time, 1.5 * max_time, 9.0,
-                                                  0.3, 0.31, 0.32], np.float64).astype(tdtype)])
-    u = np.concatenate([np.arange(len(on_edge) + 1) % nb_units,
-                        np.array([0, 0, 0, nb_units - 1, 0, nb_units - 1, 0, 0, 0, nb_units, -1, 70000])])
-    out.append((t, u))
-    out.append((np.zeros(0, tdtype), np.zeros(0, np.int64)))                        # the last sample is empty too
-    if sort:
-        out = [(t[o], u[o]) for t, u in out for o in [np.argsort(t, kind="stable")]]
-    else:
-        out = [(t[o], u[o]) for t, u in out for o in [rng.permutation(len(t))]]
-    return out
-
-
-def _store(samples, nb_units, max_time, labels=None):
-    from sparch_amd import functional as Fn
-
-    labels = np.arange(len(samples)) * 3 if labels is None else labels
-    h5 = {"spikes": {"times": [s[0] for s in samples], "units": [s[1] for s in samples]}, "labels": labels}
-    return Fn.EventStore.from_mapping(h5, device=DEV, nb_units=nb_units, max_time=max_time)
 
 
 def _check(store, samples, idx, nb_steps, nb_units, max_time):
@@ -130,21 +103,6 @@ def test_argument_checks():
     # an index outside the store: an empty sample with label -1, nothing read out of bounds
     got = store.gather(torch.tensor([1, 99, -1], dtype=torch.int64, device=DEV), 100, dense=True)
     assert got["y"].cpu().tolist()[1:] == [-1, -1] and float(got["dense"][1:].abs().sum()) == 0.0
-
-
-def _fake_h5(n=11, seed=3, tdtype=np.float32):
-    from tests.test_events_resident_host import fake_h5
-    return fake_h5(n, seed, tdtype)
-
-
-def _dense(x):
-    from sparch_amd import functional as Fn
-
-    tag = Fn.input_plane_of(x)
-    if tag is None:
-        return x
-    B, T, K = x.shape
-    return tag[0].view(B, T, -1)[:, :, :K].float()
 
 
 @pytest.mark.parametrize("tdtype", [np.float16, np.float32])

@@ -10,23 +10,10 @@ import torch
 
 from sparch_amd import functional as Fn
 from sparch_amd.dataloaders import spiking_datasets as sd
+from tests.event_cases import fake_h5
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-def fake_h5(n=11, seed=3, tdtype=np.float32):
-    """Laid out like tests/test_host.py::_fake_h5: sorted times, one empty sample, events on the first edge."""
-    rng = np.random.default_rng(seed)
-    times, units = [], []
-    for i in range(n):
-        m = int(rng.integers(0, 400)) if i != 4 else 0
-        t = np.sort(rng.uniform(0.0, 1.39, m)).astype(tdtype)
-        if m > 3:
-            t[:2] = 0.0
-        times.append(t)
-        units.append(rng.integers(0, 700, m).astype(np.int32))
-    return {"spikes": {"times": times, "units": units}, "labels": rng.integers(0, 20, n)}
 
 
 @pytest.mark.parametrize("tdtype", [np.float16, np.float32])

@@ -9,10 +9,9 @@ import torch
 
 from tests import flac_writer as fw
 from tests.audio_trees import clip_pcm, make_hd_tree
+from tests.kit import DEV
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
 
 
 def _signal(n, bps, channels=1, seed=0, noise=0.02):

@@ -21,15 +21,10 @@ import pytest
 import torch
 
 from tests.guarded import guard_arena
+from tests.kit import DEV
+from tests.kit import Fn as _Fn
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
 
 
 def _flat(out):

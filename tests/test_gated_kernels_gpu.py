@@ -38,7 +38,6 @@ Every shape and pointer a kernel receives is valid.
 """
 import ctypes
 import functools
-import hashlib
 import json
 import os
 
@@ -48,13 +47,13 @@ import torch
 
 from tests import gated_numpy as gn
 from tests.guarded import embed
+from tests.kit import DEV, EINVAL, EWORKSPACE, F32, F64, D, N, nan_, ptr, same_bits, sha, within
+from tests.kit import Fn as _Fn
+from tests.kit import capi as _capi
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-EINVAL, EWORKSPACE = -1, -3
-SEED = 0x1234567089ABCDEF                    # < 2^63: the seed itself, not an address
-F32, F64 = np.float32, np.float64
+SEED = 0x1234567089ABCDEF                    # < 2^63: the seed, not an address; not kit.SEED: the recorded bits hold it
 
 CELLS = [("RNN", "sigmoid"), ("RNN", "relu"), ("RNN", "tanh"), ("LiGRU", None), ("GRU", None)]
 CELL_IDS = ["rnn_sigmoid", "rnn_relu", "rnn_tanh", "ligru", "gru"]
@@ -64,51 +63,6 @@ BWD_NUM = {"RNN": ("dpre",), "LiGRU": ("dz_all", "dc_all"), "GRU": ("dz_all", "d
 BWD_OUT = {"RNN": ("dpre", "y_prev"), "LiGRU": ("dz_all", "dc_all", "yprev_all"),
            "GRU": ("dz_all", "dr_all", "dc_all", "yprev_all", "ry_all")}
 SAVES = {"RNN": ("y_state",), "LiGRU": ("y_state", "z_save", "c_save"), "GRU": ("y_state", "z_save", "r_save", "c_save")}
-
-
-def _capi():
-    from sparch_amd import _capi
-    return _capi
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(DEV)
-
-
-def N(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def nan_(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())
-
-
-def within(got, ref, bound, what):
-    """Asserts |got - ref| <= bound everywhere (no NaN in got) and returns the worst fraction of the bound."""
-    err = np.abs(np.asarray(got, F64) - np.asarray(ref, F64))
-    assert not np.isnan(err).any(), f"{what}: NaN"
-    worst = float(err.max())
-    if worst == 0.0:
-        return 0.0
-    f = worst / bound if bound > 0 else float("inf")
-    assert f <= 1.0, (f"{what}: {f:.3f} of the bound {bound:.3e} (at {np.unravel_index(int(np.argmax(err)), err.shape)}; "
-                      f"{int((err > bound).sum())} of {err.size} elements above it)")
-    return f
 
 
 def guarded(rows, cols):
@@ -166,14 +120,14 @@ def case(cell, kind, B, T, H, dirs, p_drop):
 
 def dev(c):
     if c.dev is None:
-        c.dev = {"X": {m: tuple(D(a) for a in c.X[m]) for m in c.X}, "V": {m: D(c.V[m]) for m in c.V},
-                 "g_out": D(c.g_out), "saves": {k: D(v) for k, v in c.saves.items()}}
+        c.dev = {"X": {m: tuple(D(a, F32) for a in c.X[m]) for m in c.X}, "V": {m: D(c.V[m], F32) for m in c.V},
+                 "g_out": D(c.g_out, F32), "saves": {k: D(v, F32) for k, v in c.saves.items()}}
     return c.dev
 
 
 def steps_first(a):
     """(Bp,T,W) in cell time order -> device (T,Bp,W): one contiguous (Bp,W) operand per step."""
-    return D(np.asarray(a).transpose(1, 0, 2))
+    return D(np.asarray(a).transpose(1, 0, 2), F32)
 
 
 # ====================================================================================================== launches
@@ -532,13 +486,6 @@ BITS_B, BITS_T = 33, 6
 BITS_H = {96: (2, 0.25), 256: (1, 0.0), 512: (1, 0.0), 1024: (2, 0.25)}        # H -> (dirs, p_drop)
 
 
-def sha(*arrays):
-    h = hashlib.sha256()
-    for a in arrays:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
-
-
 def baseline_bits(cell, kind, H):
     """{"inputs": hash of everything the kernels are given, "fwd.<output>" / "bwd.<output>": hash of that tensor}."""
     dirs, p = BITS_H[H]
@@ -568,7 +515,7 @@ def test_whole_launch_outputs_have_the_recorded_bits(cell, kind, H):
     the bit; the fp64 tests above have tolerances and would pass a reordered sum.
 
     The file was recorded with the build of the commit BEFORE the kernels were rewritten on shared ring helpers, never
-    from the code under test.  Re-record it (python -m tests.test_gated_kernels_gpu > the file, on the last commit
+    from the code under test.  Re-record it (this module run with python -m, > the file, on the last commit
     whose bits are trusted) only for a new toolchain or a deliberate change of arithmetic, such as fp16 planes, and
     say which in the commit message.  A differing "inputs" hash means that the host-side numpy inputs moved, not a
     kernel."""

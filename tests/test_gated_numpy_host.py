@@ -17,6 +17,7 @@ import torch
 
 from oracle import ann_oracle as ao
 from tests import gated_numpy as gn
+from tests.kit import same_bits
 
 B, T, H = 5, 7, 8
 CELLS = [("RNN", "sigmoid"), ("RNN", "relu"), ("RNN", "tanh"), ("LiGRU", None), ("GRU", None)]
@@ -31,12 +32,6 @@ def close(got, want, what):
     scale = np.abs(want).max()
     assert scale > 0, f"{what}: the reference is all zero"
     assert np.abs(got - want).max() <= 1e-12 * scale, f"{what}: {np.abs(got - want).max() / scale:.3e} relative"
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
-    return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(u) == b.view(u)).all())
 
 
 def forward(cell, kind, X, V, dirs, p, dtype=np.float64, matmul=np.matmul):

@@ -12,7 +12,8 @@ import re
 
 import pytest
 
-OK, EINVAL, EALIGN, EWORKSPACE = 0, -1, -2, -3
+from tests.kit import EALIGN, EINVAL, EWORKSPACE
+
 P, MIS = 16, 20
 M, N, K = 16, 24, 40          # direct products
 KC = 4096                      # the cut ones: one tile, 128 K tiles -> 16 K ranges by either split rule

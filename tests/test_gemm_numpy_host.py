@@ -11,13 +11,13 @@ import numpy as np
 import pytest
 
 from tests import gemm_numpy as gn
+from tests.kit import F32, F64
 
-F32, F64 = np.float32, np.float64
 IDS = [gn.case_id(k) for k in gn.CASE_KEYS]
 
 
 def test_entry_table_covers_every_entry_row_of_the_layout_file():
-    from tests.test_gemm_layouts_gpu import CASES, ENTRY_NAMES
+    from tests.gemm_cases import CASES, ENTRY_NAMES
     assert list(gn.ENTRIES) == ENTRY_NAMES and len(ENTRY_NAMES) == 26
     assert sorted({(k[0], k[1]) for k in gn.CASE_KEYS}) == sorted(CASES)
     assert {s for _, _, s, _ in gn.CASE_KEYS} == set(gn.SHAPES)

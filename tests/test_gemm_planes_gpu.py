@@ -1,5 +1,5 @@
 """
-Every matrix product of the C ABI (the 26 entry rows of tests/test_gemm_layouts_gpu.ENTRY_NAMES, both operand
+Every matrix product of the C ABI (the 26 entry rows of tests/gemm_cases.ENTRY_NAMES, both operand
 precisions where the entry takes one) on REAL-VALUED operands, held to a bound that sees a lost bf16 plane term.
 
 The suite's fixed bound, 2e-6 * sum|a||b| + 1e-6, is about twenty times looser than these kernels' arithmetic: a
@@ -33,14 +33,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gemm_cases as lay
 from tests import gemm_numpy as gn
-from tests import test_gemm_layouts_gpu as lay
 from tests.guarded import embed
+from tests.kit import DEV, F64, split3_host
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-F64 = np.float64
 IDS = [gn.case_id(k) for k in gn.CASE_KEYS]
 
 
@@ -78,7 +77,7 @@ def call(e, c, plane_of_values=False):
             t = lay.place(host, lay.BASE)
             setattr(x, side, t)
             if kind_ == "f32p":
-                tp = embed(lay.split3_host(host).to(DEV), t.ld, 0)
+                tp = embed(split3_host(host).to(DEV), t.ld, 0)
                 setattr(x, side + "p", tp)
                 guards.append((tp, side + " planes"))
             if kind_ == "ex16":       # upper halves, rows padded with zeros to a multiple of 8

@@ -33,56 +33,13 @@ import torch
 from tests import head_numpy as hn
 from tests.dropout_numpy import keep_mask
 from tests.guarded import embed
+from tests.kit import DEV, EALIGN, EINVAL, F32, D, N, nan_, same_bits, within
+from tests.kit import Fn as _Fn
+from tests.kit import capi as _capi
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-EINVAL, EALIGN = -1, -2
 U = 2.0 ** -24
-
-
-def _capi():
-    from sparch_amd import _capi
-    return _capi
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def D(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def N(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def nan_(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
-
-
-def within(got, ref, bound, what):
-    """Asserts |got - ref| <= bound everywhere (no NaN in got) and returns the worst fraction of the bound."""
-    err = np.atleast_1d(np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64)))
-    bound = np.broadcast_to(np.asarray(bound, np.float64), err.shape)
-    assert not np.isnan(err).any(), f"{what}: NaN"
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(err == 0, 0.0, err / bound)
-    f = float(r.max()) if r.size else 0.0
-    assert f <= 1.0, f"{what}: {f} of the bound (at {np.unravel_index(int(np.argmax(r)), r.shape)})"
-    return f
 
 
 def adjacent32(got, want):
@@ -123,10 +80,10 @@ class AdamTable:
                     lst.append(None)
                 continue
             n = h[0].size
-            self.p.append(embed(D(h[0]).view(1, n), n, 0))
-            self.g.append(D(h[1]))
-            self.m.append(embed(D(h[2]).view(1, n), n, 0))
-            self.v.append(embed(D(h[3]).view(1, n), n, 0))
+            self.p.append(embed(D(h[0], F32).view(1, n), n, 0))
+            self.g.append(D(h[1], F32))
+            self.m.append(embed(D(h[2], F32).view(1, n), n, 0))
+            self.v.append(embed(D(h[3], F32).view(1, n), n, 0))
 
     def call(self, s, **kw):
         return adam_call(self.p, self.g, self.m, self.v, self.sizes, s, **kw)
@@ -217,7 +174,7 @@ def test_adam_step_reads_the_device_scalars_when_given():
     s = hn.adam_scalars32(1000, eps=1e-8)
     wrong = dict(s, step_size=np.float32(0.5), bc2_sqrt=np.float32(0.25))
     a, b = AdamTable(_layout("25"), 1000, 0.0, 5), AdamTable(_layout("25"), 1000, 0.0, 5)
-    sd = D(np.array([s["step_size"], s["bc2_sqrt"]], dtype=np.float32))
+    sd = D(np.array([s["step_size"], s["bc2_sqrt"]], dtype=np.float32), F32)
     assert a.call(wrong, scalars_dev=sd) == 0          # the arguments are deliberately different: the pair is used
     a.check_against_reference(s, "scalars_dev")
     assert b.call(wrong) == 0                          # ... and without the pair the arguments are
@@ -280,15 +237,15 @@ def _make_opt(lr=1e-2, step0=None, seed=0, groups=None, **kw):
     step count and populated moments (as a checkpoint would)."""
     from sparch_amd.optim import Adam
     rng = np.random.default_rng(seed)
-    params = [torch.nn.Parameter(D(rng.standard_normal(sh))) for sh in OPT_SHAPES]
+    params = [torch.nn.Parameter(D(rng.standard_normal(sh), F32)) for sh in OPT_SHAPES]
     for p in params:
         p.grad = torch.zeros_like(p)
     opt = Adam(params if groups is None else groups(params), lr=lr, **kw)
     if step0 is not None:
         steps = step0 if isinstance(step0, (list, tuple)) else [step0] * len(params)
         state = {i: {"step": torch.tensor(float(steps[i])),
-                     "exp_avg": D(0.1 * rng.standard_normal(p.shape)),
-                     "exp_avg_sq": D(0.01 * (rng.random(p.shape) + 0.01))} for i, p in enumerate(params)}
+                     "exp_avg": D(0.1 * rng.standard_normal(p.shape), F32),
+                     "exp_avg_sq": D(0.01 * (rng.random(p.shape) + 0.01), F32)} for i, p in enumerate(params)}
         opt.load_state_dict({"state": state, "param_groups": opt.state_dict()["param_groups"]})
     return opt, params
 
@@ -296,7 +253,7 @@ def _make_opt(lr=1e-2, step0=None, seed=0, groups=None, **kw):
 def _fill_grads(params, seed):
     rng = np.random.default_rng(seed)
     for i, p in enumerate(params):
-        p.grad.copy_(D(rng.standard_normal(tuple(p.shape)) * 10.0 ** (i - 1)))
+        p.grad.copy_(D(rng.standard_normal(tuple(p.shape)) * 10.0 ** (i - 1), F32))
 
 
 def _snapshot(opt, params):
@@ -445,7 +402,7 @@ def test_adam_eager_mixed_steps_and_two_groups(record_property):
 def ce_call(x, y):
     c = _capi()
     B, C = x.shape
-    xd, yd = D(x), D(y, np.int64)
+    xd, yd = D(x, F32), D(y, np.int64)
     loss, dl = nan_(1), embed(nan_(B, C), C, 0)
     rc = c.lib.sparch_ce_loss(B, C, c.ptr(xd), c.ptr(yd), c.ptr(loss), c.ptr(dl), None)
     torch.cuda.synchronize()
@@ -469,10 +426,10 @@ def test_ce_loss_against_fp64(B, C, record_property):
         what = f"({B},{C}) {fam}"
         worst["loss"] = max(worst["loss"], within(loss, r["loss"], b["loss"], what + " loss"))
         worst["dlogits"] = max(worst["dlogits"], within(dl, r["dlogits"], b["dlogits"], what + " dlogits"))
-        worst["rowsum"] = max(worst["rowsum"], within(dl.astype(np.float64).sum(1), 0.0, b["dlogits"].sum(1),
+        worst["rowsum"] = max(worst["rowsum"], within(dl.astype(np.float64).sum(1), np.zeros(B), b["dlogits"].sum(1),
                                                       what + " sum_c dlogits"))
         # an upstream factor (the regulariser adds to the loss): one more rounding per element
-        xd = D(x).requires_grad_(True)
+        xd = D(x, F32).requires_grad_(True)
         got = Fn.CrossEntropyLoss()(xd, D(y, np.int64))
         (got * 1.5).backward()
         assert same_bits(N(got).reshape(1), np.float32([loss]))
@@ -516,14 +473,14 @@ def test_ce_python_layer_contiguity_fallback_and_device_guard():
     B, C = 257, 35
     y = hn.ce_labels(B, C, 7)[0]
     x = hn.ce_logits(B, C, "randn3", y, 8)
-    wide = D(np.concatenate([x, -x, x], axis=1))
+    wide = D(np.concatenate([x, -x, x], axis=1), F32)
     y2 = D(np.stack([y, (y + 1) % C], axis=1).reshape(-1), np.int64)
 
     def run(xt, yt):
         xt = xt.detach().requires_grad_(True)
         loss = Fn.cross_entropy(xt, yt)
         return loss, xt
-    l0, x0 = run(D(x), D(y, np.int64))
+    l0, x0 = run(D(x, F32), D(y, np.int64))
     l0.backward()
     xs = wide[:, 2 * C:].detach()                    # a column slice and an every-other-element label view
     ys = y2[::2]
@@ -535,7 +492,7 @@ def test_ce_python_layer_contiguity_fallback_and_device_guard():
     assert type(l0.grad_fn).__name__.startswith("CrossEntropyFn")
     # int32 labels are not the kernel's: torch's own cross_entropy takes over
     try:
-        l2, x2 = run(D(x), D(y, np.int32))
+        l2, x2 = run(D(x, F32), D(y, np.int32))
     except RuntimeError as e:                         # (torch itself refuses int32 class indices on some builds)
         assert "sparch" not in str(e)
         l2 = None
@@ -543,7 +500,7 @@ def test_ce_python_layer_contiguity_fallback_and_device_guard():
         assert not type(l2.grad_fn).__name__.startswith("CrossEntropyFn")
         assert abs(float(l2) - float(l0)) <= 1e-5 * max(1.0, abs(float(l0)))
     with pytest.raises(RuntimeError, match="labels is on 'cpu'"):
-        Fn.cross_entropy(D(x).requires_grad_(True), torch.from_numpy(y))
+        Fn.cross_entropy(D(x, F32).requires_grad_(True), torch.from_numpy(y))
     with pytest.raises(RuntimeError, match="logits is on 'cpu'"):
         Fn.cross_entropy(torch.from_numpy(x).requires_grad_(True), D(y, np.int64))
     c = _capi()
@@ -575,8 +532,8 @@ def act_call(kind, z, sc, sh, dy, p_drop=0.0, seed=0, bwd=False, n=None, H=None,
 
 
 def _act_case(kind, M, H, fam, affine, z, sc, sh, dy, drops, worst):
-    zd, dyd = D(z), D(dy)
-    scd, shd = (D(sc), D(sh)) if affine else (None, None)
+    zd, dyd = D(z, F32), D(dy, F32)
+    scd, shd = (D(sc, F32), D(sh, F32)) if affine else (None, None)
     what = f"{kind} ({M},{H}) {fam} affine={affine}"
     raw = None
     for p_drop, seed in drops:
@@ -645,9 +602,9 @@ def test_act_kernels_nonfinite_inputs_as_torch(kind, affine):
     v.requires_grad_(True)
     out = f(v)
     out.backward(torch.from_numpy(dy))
-    scd, shd = (D(sc), D(sh)) if affine else (None, None)
-    rc, y = act_call(kind, D(z), scd, shd, None)
-    rc2, dz = act_call(kind, D(z), scd, shd, D(dy), bwd=True)
+    scd, shd = (D(sc, F32), D(sh, F32)) if affine else (None, None)
+    rc, y = act_call(kind, D(z, F32), scd, shd, None)
+    rc2, dz = act_call(kind, D(z, F32), scd, shd, D(dy, F32), bwd=True)
     assert rc == 0 and rc2 == 0
     want_y, want_dz = np.isnan(out.detach().numpy()), np.isnan(v.grad.numpy())
     assert want_y.sum() >= 3
@@ -744,15 +701,15 @@ def test_softmax_sum_against_fp64(B, T, K, record_property):
     for b_, t_, k_, fam, x, g in hn.ss_cases():
         if (b_, t_, k_) != (B, T, K):
             continue
-        rc1, rc2, out, dx = ss_call(D(x), D(g))
+        rc1, rc2, out, dx = ss_call(D(x, F32), D(g, F32))
         assert rc1 == 0 and rc2 == 0
         (ro, rdx), (bo, bdx) = hn.ss_ref(x, g), hn.ss_bound(x, g)
         what = f"({B},{T},{K}) {fam}"
         worst["out"] = max(worst["out"], within(out, ro, bo, what + " out"))
         worst["dx"] = max(worst["dx"], within(dx, rdx, bdx, what + " dx"))
-        worst["out_sum"] = max(worst["out_sum"], within(out.astype(np.float64).sum(1), float(T), bo.sum(1),
+        worst["out_sum"] = max(worst["out_sum"], within(out.astype(np.float64).sum(1), np.full(B, float(T)), bo.sum(1),
                                                         what + " sum_k out = T"))
-        worst["dx_sum"] = max(worst["dx_sum"], within(dx.astype(np.float64).sum(2), 0.0, bdx.sum(2),
+        worst["dx_sum"] = max(worst["dx_sum"], within(dx.astype(np.float64).sum(2), np.zeros((B, T)), bdx.sum(2),
                                                       what + " sum_k dx = 0"))
     for k, f in worst.items():
         record_property(f"softmax_sum_{k}_err_over_bound", f)

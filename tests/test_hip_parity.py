@@ -20,30 +20,17 @@ import torch
 
 from oracle import snn_oracle as orc
 from tests.golden_io import CELL_KINDS, DYADIC_CASES, DYADIC_LONG, SNN_CASES, layer_spikes, load, snn_case
+from tests.kit import DEV, bf16_mode, relmax, sp  # noqa: F401  (bf16_mode, sp: fixtures)
+from tests.kit import Fn as _Fn
+from tests.spiking_cases import build_snn as _build
+from tests.spiking_cases import dyadic_cell_case as _dyadic_cell_case
+from tests.spiking_cases import run_dyadic as _run_dyadic
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def sp():
-    import sparch_amd
-    return sparch_amd
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
 
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def relmax(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-6))
 
 
 # ------------------------------------------------------------------------------------ GEMM
@@ -167,15 +154,6 @@ def test_gemm_spike_tn_exact_split(M, N, K, side, zd):
     Fn.gemm_tn(A[:64].to(DEV), B[:64].to(DEV), zero_diag=zd, out=acc)
     ref2 = ref + (lambda r: (r.fill_diagonal_(0) if zd else r))(A[:64].double().T @ B[:64].double())
     assert bool(((acc.cpu().double() - ref2).abs() <= 2 * bound).all())
-
-
-@pytest.fixture
-def bf16_mode():
-    """The bf16 operand mode (sparch_set_operand_precision) for one test; fp32 restored afterwards."""
-    Fn = _Fn()
-    prev = Fn.set_compute_dtype("bf16")
-    yield Fn
-    Fn.set_compute_dtype(prev)
 
 
 def _rb(x):
@@ -409,21 +387,6 @@ def test_recurrent_cell_bit_exact_with_dyadic_V(kind, spl, Bp, T, H):
     Fn.check_status()
     assert ref.sum() > 0
     assert torch.equal(s.cpu(), ref), float((s.cpu() != ref).float().mean())
-
-
-def _dyadic_cell_case(kind, Bp, T, H, seed):
-    g = torch.Generator().manual_seed(seed)
-    V = torch.randint(-24, 25, (H, H), generator=g).float() / 64.0
-    Wx = torch.randn(Bp, T, H, generator=g) * 1.5 + 0.4
-    p = {"alpha": torch.rand(H, generator=g) * 0.2 + 0.78, "V": V}
-    if kind == "RadLIF":
-        p.update(beta=torch.rand(H, generator=g) * 0.05 + 0.95, a=torch.rand(H, generator=g) * 2.4 - 1.2,
-                 b=torch.rand(H, generator=g) * 2.4 - 0.2)
-    u0 = torch.rand(Bp, H, generator=g)
-    w0 = torch.rand(Bp, H, generator=g) if kind == "RadLIF" else None
-    s0 = (torch.rand(Bp, H, generator=g) < 0.3).float()
-    g_s = torch.randn(Bp, T, H, generator=g)
-    return Wx, p, u0, w0, s0, g_s
 
 
 def _run_cell(kind, Wx, p, u0, w0, s0, g_s):
@@ -1038,15 +1001,6 @@ def test_readout_cell_vs_reference_golden():
 
 
 # ------------------------------------------------------------------------------------ whole SNN
-def _build(sp, cfg, params, dropout=0.0):
-    net = sp.SNN((cfg["B"], None, cfg["C"]), cfg["layer_sizes"], neuron_type=cfg["neuron_type"], dropout=dropout,
-                 normalization=cfg["normalization"], use_bias=cfg["use_bias"], bidirectional=cfg["bidirectional"],
-                 use_readout_layer=cfg["use_readout_layer"])
-    missing = net.load_state_dict(params, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return net.to(DEV)
-
-
 @pytest.mark.parametrize("name", SNN_CASES)
 def test_snn_train_step_vs_reference_golden(sp, name):
     """Same parameters, same input, same torch.manual_seed as the reference run:
@@ -1104,43 +1058,6 @@ def test_snn_train_step_vs_reference_golden(sp, name):
         assert np.abs(rates_e.cpu().numpy() - z["rates_eval"]).max() <= 2.5 / (cfg["B"] * T) + 1e-6
     else:
         assert np.abs(rates_e.cpu().numpy() - z["rates_eval"]).mean() <= 0.02
-
-
-def _run_dyadic(sp, name, monkeypatch, dropout=0.0, seeds=None, loss_kw=None):
-    """One training step of a dyadic fixture's network on the HIP path, fed the fixture's initial states in
-    the reference's draw order.  Returns (cfg, z, per-layer spikes, out, loss, net).  With dropout, `seeds[k]` is
-    the dropout seed hidden layer k hands its kernels; `loss_kw` goes to oracle.train_step_loss (the regulariser)."""
-    Fn = _Fn()
-    cfg, x, y, params, init, z = snn_case(name)
-    net = _build(sp, cfg, params, dropout).train()
-    if seeds is not None:
-        for lay, seed in zip(list(net.snn)[:-1], seeds):
-            lay._dropout_seed = lambda device, seed=seed: seed
-    order = []
-    for st in init:
-        order += [st[k] for k in ("u0", "w0", "s0") if k in st]
-    states = iter(order)
-
-    def next_state(rows, cols, device):
-        t = next(states)
-        assert tuple(t.shape) == (rows, cols)
-        return t.to(device)
-
-    from sparch_amd import snns as snn_mod
-    monkeypatch.setattr(snn_mod, "_rand_to", next_state)
-    rec = {}
-    for k, lay in enumerate(list(net.snn)[:-1]):
-        def wrapped(inp, states=None, orig=lay.forward_with_rate, k=k, **kw):
-            s, r = orig(inp, states=states, **kw)
-            rec[k] = snn_mod.materialize_spikes(s).detach()  # between the network's layers: the bf16 plane
-            return s, r
-        lay.forward_with_rate = wrapped
-    out, rates = net(x.to(DEV))
-    Fn.check_status()
-    loss = orc.train_step_loss(out, rates, y.to(DEV), **(loss_kw or {}))
-    loss.backward()
-    Fn.check_status()
-    return cfg, z, rec, out, loss, net
 
 
 @pytest.mark.parametrize("name", DYADIC_CASES)
@@ -2018,7 +1935,7 @@ def test_shd_ssc_loader_batches_binned_on_device():
     (x, xlens, y) collate contract (spiking_datasets.py:80-87)."""
     from oracle import events_numpy as ev
     from sparch_amd.dataloaders.spiking_datasets import load_shd_or_ssc
-    from tests.test_host import _fake_h5
+    from tests.event_cases import fake_h5 as _fake_h5
 
     h5 = _fake_h5(n=11)
     loader = load_shd_or_ssc("shd", "/unused", "valid", batch_size=4, shuffle=False, h5_file=h5, device=DEV)

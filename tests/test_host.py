@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import sparch_amd
+from tests.event_cases import fake_h5 as _fake_h5
 from tests.golden_io import snn_case
 
 
@@ -109,19 +110,6 @@ def test_ann_construction_matches_reference_rng_and_keys(name):
 
 
 # ------------------------------------------------------------------ f-3: SHD / SSC loader API
-def _fake_h5(n=11, seed=3):
-    rng = np.random.default_rng(seed)
-    times, units = [], []
-    for i in range(n):
-        m = int(rng.integers(0, 400)) if i != 4 else 0          # one empty sample
-        t = np.sort(rng.uniform(0.0, 1.39, m)).astype(np.float32)
-        if m > 3:
-            t[:2] = 0.0                                           # exactly on the first edge
-        times.append(t)
-        units.append(rng.integers(0, 700, m).astype(np.int32))
-    return {"spikes": {"times": times, "units": units}, "labels": rng.integers(0, 20, n)}
-
-
 def test_spiking_dataset_api_and_errors():
     from sparch_amd.dataloaders.spiking_datasets import SpikingDataset, load_shd_or_ssc
     from oracle import events_numpy as ev
@@ -217,7 +205,6 @@ def test_bench_roofline_traffic_comes_from_the_profile_of_the_workload_run():
     assert val is not None and src["file"].endswith("cfg2.json")
     assert bench.pmc_traffic("rec_cell_bwd[RadLIF]", "cfg5", False) == (None, None)  # no fp32 pass of cfg5 is tracked
     assert bench.pmc_traffic("gemm_nn[64000x1024x1024]", "mlp", False) == (None, None)
-
 
 
 def test_bench_dump_outputs_writes_float32_npy(tmp_path):

@@ -29,56 +29,18 @@ import torch
 
 from tests import norm_numpy as nn_
 from tests.guarded import embed, guard_arena
-from tests.test_norm_numpy_host import edge_values
+from tests.kit import DEV, EALIGN, EINVAL, EWORKSPACE, F32, D, N, bits, nan_, relmax, same_bits, within
+from tests.kit import capi as _capi
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-EINVAL, EALIGN, EWORKSPACE = -1, -2, -3
 U = 2.0 ** -24
 EPS = 1e-5
 MOM32 = float(np.float32(nn_.BN_MOMENTUM))
 
 
-def _capi():
-    from sparch_amd import _capi
-    return _capi
-
-
-def D(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def N(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def nan_(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
-
-
 def f32(a):
     return np.asarray(a, dtype=np.float64).astype(np.float32)
-
-
-def relmax(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-6))
-
-
-def within(got, ref, bound, what):
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    assert (err <= bound).all(), f"{what}: {float((err / bound).max())} of the bound (at {int(np.argmax(err / bound))})"
 
 
 # ================================================================================================ a. bn_finalize
@@ -88,8 +50,8 @@ class Finalize:
     def __init__(self, s, ss, gamma, beta, rm, rv, skip=None, nbt=None):
         self.H = int(np.asarray(gamma).size)
         self.n_tiles = int(np.asarray(s).shape[0])
-        self.ws = D(np.concatenate([np.asarray(s).reshape(-1), np.asarray(ss).reshape(-1)]))
-        self.gamma, self.beta, self.rm, self.rv = D(gamma), D(beta), D(rm), D(rv)
+        self.ws = D(np.concatenate([np.asarray(s).reshape(-1), np.asarray(ss).reshape(-1)]), F32)
+        self.gamma, self.beta, self.rm, self.rv = D(gamma, F32), D(beta, F32), D(rm, F32), D(rv, F32)
         self.skip = None if skip is None else torch.tensor([skip, 0, 0, 0], dtype=torch.int32, device=DEV)
         self.nbt = None if nbt is None else torch.tensor([nbt], dtype=torch.int64, device=DEV)
         self.o = {k: nan_(self.H) for k in ("scale", "shift", "save_mean", "save_invstd")}
@@ -332,7 +294,7 @@ def test_gemm_colstats_and_finalize_of_off_centre_columns(M, K, H, dense, monkey
     c = _capi()
     o = {k: nan_(H) for k in ("scale", "shift", "mean", "invstd")}
     rm, rv = torch.zeros(H, device=DEV), torch.zeros(H, device=DEV)
-    gd, bd = D(gamma), D(beta)
+    gd, bd = D(gamma, F32), D(beta, F32)
     c.check(c.lib.sparch_bn_finalize(H, M, n_tiles, 1, c.ptr(ws), c.ptr(gd), c.ptr(bd), c.ptr(rm), c.ptr(rv),
                                      1.0, EPS, 1, c.ptr(o["scale"]), c.ptr(o["shift"]), c.ptr(o["mean"]),
                                      c.ptr(o["invstd"]), None, None, None), "sparch_bn_finalize")
@@ -388,7 +350,7 @@ def test_bn_bwd_reduce_dyadic_is_exact(M, H):
     invstd = 2.0 ** rng.integers(-1, 2, H)
     with guard_arena(None, nbytes=1 << 20) as arena:
         ws = arena.empty(2 * ((M + 255) // 256) * H * 4, dtype=torch.uint8)       # exactly the queried size
-        rc, dg, db = reduce_call(M, H, D(dy), D(x), D(mean), D(invstd), ws=ws)
+        rc, dg, db = reduce_call(M, H, D(dy, F32), D(x, F32), D(mean, F32), D(invstd, F32), ws=ws)
         assert rc == 0
     dgamma, dbeta = nn_.bn_bwd_reduce(dy, x, mean, invstd)
     assert same_bits(N(dg), f32(dgamma)) and same_bits(N(db), f32(dbeta))
@@ -403,7 +365,7 @@ def test_bn_bwd_reduce_randn_columns_with_offset_and_scale(M, H):
     dy = f32(rng.standard_normal((M, H)))
     mean = f32(x.astype(np.float64).mean(0))
     invstd = f32(1.0 / np.sqrt(x.astype(np.float64).var(0) + EPS))
-    rc, dg, db = reduce_call(M, H, D(dy), D(x), D(mean), D(invstd))
+    rc, dg, db = reduce_call(M, H, D(dy, F32), D(x, F32), D(mean, F32), D(invstd, F32))
     assert rc == 0
     dgamma, dbeta = nn_.bn_bwd_reduce(dy, x, mean, invstd)
     t1, t0 = nn_.bn_bwd_terms(dy, x, mean, invstd)
@@ -441,13 +403,13 @@ def colsum_call(M, H, x, ws=None, ws_bytes=None):
 def test_colsum_dyadic_exact_and_randn_bounded(M, H):
     rng = np.random.default_rng(M * 13 + H)
     x = rng.integers(-64, 65, (M, H)) / 8.0
-    rc, out = colsum_call(M, H, D(x))
+    rc, out = colsum_call(M, H, D(x, F32))
     assert rc == 0 and same_bits(N(out), f32(x.sum(0)))
     x = f32(rng.standard_normal((M, H)) * np.exp(rng.standard_normal(H)) + rng.standard_normal(H))
-    rc, out = colsum_call(M, H, D(x))
+    rc, out = colsum_call(M, H, D(x, F32))
     assert rc == 0
     within(N(out), x.astype(np.float64).sum(0), 2e-6 * np.abs(x.astype(np.float64)).sum(0) + 1e-6, "colsum")
-    rc, out = colsum_call(M, H, D(x), ws_bytes=2 * ((M + 255) // 256) * H * 4 - 1)
+    rc, out = colsum_call(M, H, D(x, F32), ws_bytes=2 * ((M + 255) // 256) * H * 4 - 1)
     assert rc == EWORKSPACE and np.isnan(N(out)).all()
 
 
@@ -569,7 +531,7 @@ def test_layernorm_forward(M, H, Hn):
     p = c.ptr
     x, gamma, beta, _ = ln_case(M, H, Hn, 1000 * M + H)
     y, mu, rstd = nan_(M, H), nan_(M), nan_(M)
-    xd, gd, bd = D(x), D(gamma), D(beta)
+    xd, gd, bd = D(x, F32), D(gamma, F32), D(beta, F32)
     c.check(c.lib.sparch_layernorm_fwd(M, H, Hn, p(xd), p(gd), p(bd), EPS, p(y), p(mu), p(rstd), None),
             "sparch_layernorm_fwd")
     y, mu, rstd = N(y), N(mu), N(rstd)
@@ -602,10 +564,10 @@ def test_layernorm_backward(M, H, Hn):
     t1, t0 = nn_.layernorm_bwd_terms(dy, x, mu, rstd)
     need = c.lib.sparch_bn_bwd_workspace_bytes(M, H)
     outs = []
-    xd, mud, rstdd, gd = D(x), D(mu), D(rstd), D(gamma)
+    xd, mud, rstdd, gd = D(x, F32), D(mu, F32), D(rstd, F32), D(gamma, F32)
     with guard_arena(None, nbytes=4 << 20) as arena:
         for alias in (False, True):
-            dyd = D(dy)
+            dyd = D(dy, F32)
             dx = dyd if alias else nan_(M, H)
             dg, db = nan_(H), nan_(H)
             ws = arena.empty(need, dtype=torch.uint8)
@@ -678,14 +640,14 @@ def test_colsum_clamped_gate_is_torch_clamps(n_params, H):
     lims = [lims[j % 3] for j in range(n_params)]
     raws = []
     for j, (lo, hi) in enumerate(lims):
-        raws.append(None if j % 3 == 1 else np.resize(edge_values(lo, hi), H + j)[j:])
+        raws.append(None if j % 3 == 1 else np.resize(nn_.edge_values(lo, hi), H + j)[j:])
     if n_params == 1:
-        raws[0] = np.resize(edge_values(*lims[0])[1:], H)           # H = 1: the value exactly at lo
+        raws[0] = np.resize(nn_.edge_values(*lims[0])[1:], H)           # H = 1: the value exactly at lo
     flat = [v for lo_hi in lims for v in lo_hi]
     for rows in CL_ROWS:
         ws = rng.integers(-64, 65, (n_params, rows, H)) / 8.0
-        wsd = D(ws)
-        raws_d = [None if r is None else D(r) for r in raws]
+        wsd = D(ws, F32)
+        raws_d = [None if r is None else D(r, F32) for r in raws]
         rc, outs = clamped_call(wsd, raws_d, flat, H)
         assert rc == 0
         ref = nn_.colsum_clamped(ws, raws, lims)

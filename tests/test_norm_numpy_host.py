@@ -139,17 +139,9 @@ def test_layernorm_of_a_constant_row_is_beta():
     assert (y == np.arange(6.0) / 4).all() and (mu == 3.0).all() and (rstd == 1.0 / np.sqrt(nn_.NORM_EPS)).all()
 
 
-def edge_values(lo, hi):
-    """fp32 values around a clamp range: inside, the two ends, one ulp outside each, NaN."""
-    lo32, hi32 = np.float32(lo), np.float32(hi)
-    return np.array([0.5 * (lo32 + hi32), lo32, hi32, np.nextafter(lo32, np.float32(-np.inf)),
-                     np.nextafter(hi32, np.float32(np.inf)), np.nan, np.nextafter(lo32, np.float32(np.inf)),
-                     np.nextafter(hi32, np.float32(-np.inf))], dtype=np.float32)
-
-
 @pytest.mark.parametrize("lo,hi", [(0.0, 1.0), (-1.0, 1.0), (0.36787944, 0.96)])
 def test_clamp_gate_is_torch_clamps_backward(lo, hi):
-    raw = edge_values(lo, hi)
+    raw = nn_.edge_values(lo, hi)
     lo, hi = float(np.float32(lo)), float(np.float32(hi))
     p = torch.from_numpy(raw.astype(np.float64)).requires_grad_(True)
     w = torch.arange(1.0, raw.size + 1.0, dtype=torch.float64)

@@ -34,17 +34,10 @@ import pytest
 import torch
 
 from tests import spiking_numpy as sn
-from tests.test_rec_cell_real_V_gpu import D, N, record, within
+from tests.kit import DEV, F32, F64, D, N, record, within
+from tests.kit import Fn as _Fn
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-F32, F64 = np.float32, np.float64
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
 
 
 @functools.lru_cache(maxsize=2)

@@ -18,7 +18,7 @@ or a small cross term of the backward product.  Here nothing is exempted, becaus
 
 Bound (never taken from the code under test): per output tensor, 4 x the worst max-abs error of two fp32 runs of the
 restatement (k blocks of 32 ascending, descending) against its fp64 run on the same inputs — the rule of
-tests/test_gated_kernels_gpu.py.  tests/test_spiking_numpy_host.py shows on the CPU that, for every drive-regime case
+tests/test_gated_kernels_gpu.py, applied by tests/kit.within.  tests/test_spiking_numpy_host.py shows on the CPU that, for every drive-regime case
 here, losing plane 2 of V, a quarter of it, or the t3 * hi term of the backward leaves that bound behind.  Each test
 records its worst fraction of the bound (record_property "worst_fraction_of_bound"; DESIGN.md has the figures measured
 on an MI355X).
@@ -32,74 +32,18 @@ directions (B = 17, with scale / shift and g_rate) and the launch-per-step path 
 selects the 64-column workgroups by SPARCH_REC_CW, so none does here.)  The non-recurrent kinds run their backward
 through the same restatement and rule at (33, 17, 100), with and without the folded BatchNorm sums.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 from tests import spiking_numpy as sn
+from tests.kit import F32, F64, D, N, bf16_mode, record, within  # noqa: F401  (bf16_mode: a fixture)
+from tests.kit import Fn as _Fn
+from tests.spiking_cases import collect
+from tests.spiking_cases import rec_case as case
+from tests.spiking_cases import rec_forward as kernel_forward
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-F32, F64 = np.float32, np.float64
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def D(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def N(t):
-    return None if t is None else t.detach().float().cpu().numpy()
-
-
-@pytest.fixture
-def bf16_mode():
-    """The bf16 operand mode (sparch_set_operand_precision) for one test; fp32 restored afterwards."""
-    Fn = _Fn()
-    prev = Fn.set_compute_dtype("bf16")
-    yield Fn
-    Fn.set_compute_dtype(prev)
-
-
-def within(got, ref, bound, what):
-    """Asserts |got - ref| <= bound everywhere (no NaN in got) and returns the worst fraction of the bound."""
-    err = np.abs(np.asarray(got, F64) - np.asarray(ref, F64))
-    assert got.shape == ref.shape and not np.isnan(err).any(), f"{what}: shape or NaN"
-    worst = float(err.max())
-    if worst == 0.0:
-        return 0.0
-    f = worst / bound if bound > 0 else float("inf")
-    print(f"  {what}: {f:.3f} of the bound {bound:.3e}")
-    assert f <= 1.0, (f"{what}: {f:.3f} of the bound {bound:.3e} (at {np.unravel_index(int(np.argmax(err)), err.shape)}; "
-                      f"{int((err > bound).sum())} of {err.size} elements above it)")
-    return f
-
-
-@functools.lru_cache(maxsize=4)
-def case(kind, B, dirs, T, H, regime):
-    """Inputs of one case on the host and on the device, made once and never written to."""
-    c = sn.make_inputs(kind, B, dirs, T, H, sn.case_seed(kind, B, dirs, T, H), regime, affine_in=(dirs == 2))
-    c["dev"] = {k: D(c[k]) for k in ("Wx", "scale", "shift", "u0", "w0", "s0", "g_out", "g_rate")}
-    c["dev"]["p"] = {k: D(v) for k, v in c["p"].items()}
-    return c
-
-
-def kernel_forward(c, spl):
-    Fn, d = _Fn(), c["dev"]
-    assert not Fn.SAVE_BF16
-    s_out, count, saved, s16 = Fn.cell_forward(c["kind"], d["Wx"], d["scale"], d["shift"], d["p"], d["u0"], d["w0"], d["s0"],
-                                               B=c["B"], dirs=c["dirs"], theta=c["theta"], p_drop=0.0, seed=0,
-                                               steps_per_launch=spl)
-    Fn.check_status()
-    torch.cuda.synchronize()
-    return s_out, count, saved, s16
 
 
 def check_forward(c, spl, operand, record_property):
@@ -113,7 +57,7 @@ def check_forward(c, spl, operand, record_property):
     want = sn.out_layout(S, B, dirs)
     assert np.array_equal(N(s_out), want), float((N(s_out) != want).mean())
     if s16 is not None:
-        assert s16.dtype == torch.bfloat16 and np.array_equal(N(s16), want)
+        assert s16.dtype == torch.bfloat16 and np.array_equal(N(s16, torch.float32), want)
     assert np.array_equal(N(count).astype(np.int64), want.sum((0, 1)).astype(np.int64))
     # non-vacuity
     frac = float(S.mean())
@@ -152,10 +96,7 @@ def check_backward(c, spl, operand, with_rate=False, bn=None):
                                   H=H, theta=theta, p_drop=0.0, seed=0, steps_per_launch=spl, bn=bn_dev)
     Fn.check_status()
     torch.cuda.synchronize()
-    got = {"dWx": N(dWx)}
-    got.update({k: N(v) for k, v in grads.items() if k != "bn_sums"})
-    if bn is not None:
-        got["bn_dy"], got["bn_dyx"] = N(grads["bn_sums"][0]), N(grads["bn_sums"][1])
+    got = collect(dWx, grads, bn is not None)
     # (bf16 operand mode: the dense products of the reference read the kernel's own dWx, rounded as the kernel rounds it)
     rec_operand = got["dWx"] if operand is not None else None
 
@@ -172,11 +113,6 @@ def check_backward(c, spl, operand, with_rate=False, bn=None):
     if "V" in got:
         assert np.all(np.diag(got["V"]) == 0) and np.abs(got["V"]).max() > 0
     return worst
-
-
-def record(record_property, *worst):
-    record_property("worst_fraction_of_bound", round(max(worst), 3))
-    print(f"  worst fraction of bound {max(worst):.3f}")
 
 
 # ------------------------------------------------------------------------------------------------ recurrent kinds

@@ -7,40 +7,8 @@ import re
 
 import pytest
 
-OK, EINVAL, EALIGN, EWORKSPACE = 0, -1, -2, -3
-P, MIS = 16, 20
-NAN = float("nan")
-RLIF, RADLIF = 2, 3
-B, T, H = 2, 3, 8          # spiking / ANN base shape
-HG = 32                    # gated base hidden size
-
-
-class Entry:
-    def __init__(self, name, args):
-        self.name, self.args = name, args
-
-    def __call__(self, **over):
-        from sparch_amd._capi import lib
-        unknown = set(over) - {k for k, _ in self.args}
-        assert not unknown, (self.name, unknown)
-        return getattr(lib, self.name)(*[over.get(k, v) for k, v in self.args])
-
-
-def head(first, step=None, Hv=H):
-    a = [first, ("B", B), ("dirs", 1), ("T", T), ("H", Hv)]
-    if first is None:
-        a = a[1:]
-    return a + ([(step, 0)] if step else [])
-
-
-def ptrs(names, none=()):
-    none = none.split() if isinstance(none, str) else none
-    return [(n, None if n in none else P) for n in names.split()]
-
-
-WS = [("chan", None), ("chan_bytes", 1 << 20), ("status", P), ("steps_per_launch", T), ("stream", None)]
-KIND = ("kind", RADLIF)
-ACT = ("act", 0)
+from tests.entry_probes import ACT, HG, KIND, MIS, NAN, RADLIF, WS, Entry, H, P, T, head, ptrs
+from tests.kit import EALIGN, EINVAL, EWORKSPACE
 
 REC_FWD = Entry("sparch_rec_cell_fwd", head(KIND) + ptrs("Wx scale shift alpha beta a b vpack rec0 u0 w0 s0", "scale shift")
                 + [("theta", 1.0), ("p_drop", 0.0), ("seed", 1)] + ptrs("s_out s16_out u_save w_save", "s16_out")

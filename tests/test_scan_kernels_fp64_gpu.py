@@ -33,62 +33,20 @@ depth 8: one main trip and a one-step tail that is cell step 0), T = 17 at V1 (d
 T on both sides of every depth on the fullest variant.  The stream entry sparch_cell_stream_fwd runs at (33, 15888),
 four neurons per thread, through StreamingSNN's own call.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 from tests import spiking_numpy as sn
-from tests.test_dropout_rate_backward_gpu import SEED
-from tests.test_rec_cell_real_V_gpu import D, N, record, within
+from tests.kit import DEV, F32, F64, SEED, D, N, record, within, words
+from tests.kit import Fn as _Fn
+from tests.spiking_cases import collect
+from tests.spiking_cases import scan_case_of as case_of
+from tests.spiking_cases import scan_forward as kernel_forward
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-F32, F64 = np.float32, np.float64
 P_DROP = sn.P_DROP
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def words(t):
-    """The 16-bit words of a bf16 device tensor."""
-    return t.detach().contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-@functools.lru_cache(maxsize=2)
-def case(kind, B, dirs, T, H):
-    """Inputs of one case on the host and on the device, made once and never written to; the conditions, asserted on
-    the fp32 restatement's own free run."""
-    c = sn.scan_case(kind, B, dirs, T, H)
-    c["dev"] = {k: D(c[k]) for k in ("Wx", "scale", "shift", "u0", "w0", "s0", "g_out", "g_rate")}
-    c["dev"]["p"] = {k: D(v) for k, v in c["p"].items()}
-    c["dev"]["bn"] = tuple(D(v) for v in c["bn"])
-    c["keep"] = sn.scan_keep(c, SEED)
-    free = sn.forward(kind, F32, c["Wx"], c["scale"], c["shift"], c["p"], c["u0"], c["w0"], c["s0"], B=B, dirs=dirs,
-                      theta=c["theta"])
-    c["spikes"], c["box"] = sn.scan_conditions(c, free["u_save"], c["keep"])
-    # V4 takes four neurons per thread, everything else one (launch_cell of cell.hip)
-    assert (B * dirs * H >= 524288 and H % 4 == 0) == ((B, dirs, H) == sn.V4)
-    return c
-
-
-def kernel_forward(c, p_drop, save16=False, **kw):
-    Fn, d = _Fn(), c["dev"]
-    prev = Fn.SAVE_BF16
-    Fn.SAVE_BF16 = save16
-    try:
-        res = Fn.cell_forward(c["kind"], d["Wx"], d["scale"], d["shift"], d["p"], d["u0"], d["w0"], d["s0"], B=c["B"],
-                              dirs=c["dirs"], theta=c["theta"], p_drop=p_drop, seed=SEED, **kw)
-    finally:
-        Fn.SAVE_BF16 = prev
-    Fn.check_status()
-    torch.cuda.synchronize()
-    return res
 
 
 def check_forward(c, p_drop):
@@ -105,7 +63,7 @@ def check_forward(c, p_drop):
     cnt = plane.sum((0, 1)).astype(np.int64)
     assert 0.02 <= S.mean() <= 0.5 and (p_drop == 0 or 0 < cnt.sum() < S.sum())
     assert np.array_equal(N(s_out), want), float((N(s_out) != want).mean())
-    assert s16.dtype == torch.bfloat16 and np.array_equal(N(s16), plane)
+    assert s16.dtype == torch.bfloat16 and np.array_equal(N(s16, torch.float32), plane)
     assert np.array_equal(N(count).astype(np.int64), cnt)
     # the saved states against the teacher-forced restatement
     args = (c["Wx"], c["scale"], c["shift"], c["p"], c["u0"], c["w0"], c["s0"], us, ws)
@@ -138,17 +96,14 @@ def check_backward(c, save16, with_bn, p_drop):
     kind, B, dirs, T, H, theta = c["kind"], c["B"], c["dirs"], c["T"], c["H"], c["theta"]
     _, _, saved, _ = kernel_forward(c, p_drop, save16)
     assert saved[0].dtype == (torch.bfloat16 if save16 else torch.float32)
-    us, ws = N(saved[0]), N(saved[1])                                      # (bf16 -> fp32 is exact)
+    us, ws = N(saved[0], torch.float32), N(saved[1], torch.float32)        # (bf16 -> fp32 is exact)
     x = us - F32(theta)
     assert 0.02 <= (x > 0).mean() <= 0.5 and 0.05 <= ((x > F32(-0.5)) & (x <= F32(0.5))).mean() <= 0.95
     dWx, grads = Fn.cell_backward(kind, d["g_out"], d["g_rate"], d["p"], d["u0"], d["w0"], d["s0"], saved, B=B, dirs=dirs,
                                   T=T, H=H, theta=theta, p_drop=p_drop, seed=SEED, bn=d["bn"] if with_bn else None)
     Fn.check_status()
     torch.cuda.synchronize()
-    got = {"dWx": N(dWx)}
-    got.update({k: N(v) for k, v in grads.items() if k != "bn_sums"})
-    if with_bn:
-        got["bn_dy"], got["bn_dyx"] = N(grads["bn_sums"][0]), N(grads["bn_sums"][1])
+    got = collect(dWx, grads, with_bn)
 
     def bw(dt, ro):
         return sn.flat(sn.backward(kind, dt, c["g_out"], c["g_rate"], us, ws, c["p"], c["u0"], c["w0"], c["s0"], B=B,
@@ -163,14 +118,6 @@ def check_backward(c, save16, with_bn, p_drop):
     for k in c["p"]:                                                       # neuron 0 below, neuron 1 above the clamp range
         assert got[k][0] == 0 and got[k][1] == 0 and np.abs(got[k][2:]).max() > 0, k
     return worst
-
-
-GEOM = {"V4": sn.V4 + (sn.T_V4,), "V1": sn.V1 + (sn.T_V1,), "V1big": sn.V1BIG + (sn.T_V4,), "V1odd": sn.V1ODD + (sn.T_V1,)}
-
-
-def case_of(kind, geom, T=None):
-    B, dirs, H, T0 = GEOM[geom]
-    return case(kind, B, dirs, T0 if T is None else T, H)
 
 
 FORWARD = [(g, p) for g in ("V4", "V1") for p in (0.0, P_DROP)] + [("V1big", P_DROP), ("V1odd", P_DROP)]

@@ -13,7 +13,7 @@ states end in a burst at the first step and a silent population behind it: under
 
 The file was recorded with the build of the commit BEFORE the kernels were rewritten on the shared helpers of neuron.h /
 stream_common.h, twice in one visit with byte-identical results, never from the code under test.  Re-record it
-(python -m tests.test_spiking_bits_gpu > the file, on the last commit whose bits are trusted) only for a new toolchain
+(this module run with python -m, > the file, on the last commit whose bits are trusted) only for a new toolchain
 or a deliberate change of arithmetic, and say which in the commit message.  A differing "inputs" hash means that the
 host-side numpy inputs moved, not a kernel.  So that a hash cannot hide a dead case, every hashed spike tensor must hold
 between 1 % and 50 % non-zeros: asserted here, and checked beforehand on the CPU with tests/spiking_numpy.py and
@@ -38,7 +38,6 @@ Cases (B = 33: two row tiles, the second ragged; T = 6):
 """
 import contextlib
 import functools
-import hashlib
 import json
 import os
 import zlib
@@ -48,38 +47,15 @@ import pytest
 import torch
 
 from tests import spiking_numpy as sn
+from tests.kit import DEV, F32, D, raw, sha
+from tests.kit import Fn as _Fn
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-F32 = np.float32
 BITS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spiking_bits.json")
 B, T, THETA = 33, 6, 0.25
 KIND = {"LIF": 0, "adLIF": 1, "RLIF": 2, "RadLIF": 3}
-OUTSIDE = {"alpha": (0.5, 1.2), "beta": (0.9, 1.1), "a": (-1.5, 1.5), "b": (-0.5, 2.5)}   # neuron 0 / neuron 1
 SALT = {}       # case id -> another seed, where the first one left a spike tensor outside 1 .. 50 %
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def D(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def raw(t):
-    """The bytes of a device tensor as a numpy array (bf16 as its 16-bit words)."""
-    t = t.detach().contiguous().cpu()
-    return (t.view(torch.int16) if t.dtype == torch.bfloat16 else t).numpy()
-
-
-def sha(*arrays):
-    h = hashlib.sha256()
-    for a in arrays:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
 
 
 def sha_inputs(c):
@@ -103,7 +79,7 @@ def neuron_params(kind, H, rng, alpha_only=False):
         p.update(beta=rng.uniform(0.968, 0.991, H).astype(F32), a=rng.uniform(-0.9, 0.9, H).astype(F32),
                  b=rng.uniform(0.1, 1.9, H).astype(F32))
     for k in p:
-        p[k][0], p[k][1] = OUTSIDE[k]
+        p[k][0], p[k][1] = sn.OUTSIDE[k]
     if sn.RECURRENT.get(kind) and not alpha_only:
         p["V"] = (0.5 * rng.standard_normal((H, H))).astype(F32)
     return p
@@ -411,7 +387,7 @@ def recorded_bits():
 @pytest.mark.parametrize("case_id", list(CASES))
 def test_spiking_forward_outputs_have_the_recorded_bits(case_id):
     """See the module docstring: recorded on the commit before the kernels moved onto neuron.h / stream_common.h, never
-    from the code under test.  Re-record (python -m tests.test_spiking_bits_gpu > tests/golden/spiking_bits.json, on the
+    from the code under test.  Re-record (this module run with python -m, > tests/golden/spiking_bits.json, on the
     last commit whose bits are trusted) only for a new toolchain or a deliberate change of arithmetic, and say which in
     the commit message.  A differing "inputs" hash means that the numpy inputs moved, not a kernel."""
     want = recorded_bits()[case_id]

@@ -47,8 +47,7 @@ import torch
 from oracle import bptt_numpy as bn
 from oracle import snn_oracle as orc
 from tests import spiking_numpy as sn
-
-F32, F64 = np.float32, np.float64
+from tests.kit import F32, F64, SEED
 
 
 def _args(c):
@@ -192,7 +191,6 @@ def test_bound_of_the_gpu_file_resolves_the_mutants(kind, B, dirs, T, H, record_
 # tests/test_scan_kernels_fp64_gpu.py and tests/test_readout_kernels_fp64_gpu.py rest on the pieces pinned here: the
 # dropout multiplier of backward(), the readout restatement, save_u16 in numpy, the decisions taken in the save's own
 # type (the tie regression) and the sharpness of the two files' bounds.
-SEED = 0x1234567_89ABCDEF
 
 
 @pytest.mark.parametrize("dirs", [1, 2])

@@ -35,35 +35,12 @@ import torch
 from tests import stream_ann_numpy as sn
 from tests.golden_io import load
 from tests.guarded import embed
+from tests.kit import DEV, F32, F64, D, N, nan_, ptr, relmax, same_bits, within
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-F32, F64 = np.float32, np.float64
 FIXTURES = ["ann_MLP_bn", "ann_RNN_bn", "ann_LiGRU_bn", "ann_GRU_bn", "ann_MLP_ln_bias_noreadout"]
 STEPS = 6
-
-
-def relmax(a, b):
-    a, b = np.asarray(a, F64), np.asarray(b, F64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-6))
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
-
-
-def N(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(DEV)
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 # ====================================================================================================== networks
@@ -227,14 +204,6 @@ def bound_of(ref, runs):
     return max(4.0 * worst, 4.0 * 2.0 ** -24 * float(np.abs(ref).max()))
 
 
-def within(got, ref, bound, what):
-    err = np.abs(np.asarray(got, F64) - ref)
-    assert not np.isnan(err).any(), f"{what}: NaN"
-    f = float(err.max()) / bound
-    assert f <= 1.0, f"{what}: {f:.3f} of the bound {bound:.3e}; {int((err > bound).sum())} of {err.size} elements above it"
-    return f
-
-
 @functools.lru_cache(maxsize=4)
 def step_case(cell, act, B, K, H):
     """Inputs and the three free-running reference runs of one case (never written to)."""
@@ -256,10 +225,6 @@ def step_case(cell, act, B, K, H):
     return gates, xs, runs[0], bound_of(runs[0], runs[1:])
 
 
-def nan_(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
-
-
 @pytest.mark.parametrize("B,K,H", SHAPES, ids=SHAPE_IDS)
 @pytest.mark.parametrize("cell,act", CELLS, ids=CELL_IDS)
 def test_step_kernel_geometries_against_fp64(cell, act, B, K, H, record_property):
@@ -271,10 +236,10 @@ def test_step_kernel_geometries_against_fp64(cell, act, B, K, H, record_property
     ld, ldx = strides(B, K, H)
     rec, gru = cell != "MLP", cell == "GRU"
     arr = ctypes.c_void_p * 3
-    dev = {g: {k: (None if v is None else embed(D(v).view(1, -1) if v.ndim == 1 else D(v))) for k, v in gates[g].items()}
-           for g in gates}
+    dev = {g: {k: (None if v is None else embed(D(v, F32).view(1, -1) if v.ndim == 1 else D(v, F32)))
+               for k, v in gates[g].items()} for g in gates}
     slots = lambda k: arr(*[ptr(dev[g][k]) if g in dev else None for g in ("c", "z", "r")])  # noqa: E731
-    x_dev = [embed(D(xs[t]), ldx, 0) for t in range(STEPS)]
+    x_dev = [embed(D(xs[t], F32), ldx, 0) for t in range(STEPS)]
     y = [embed(torch.zeros(B, H, device=DEV), ld, 0), embed(nan_(B, H), ld, 0)]      # the zero state, the other copy
     z, ry = (embed(nan_(B, H), ld, 0), embed(nan_(B, H), ld, 0)) if gru else (None, None)
     got = []
@@ -314,9 +279,9 @@ def test_step_with_ready_made_projections_equals_the_one_launch_form():
     runs = []                                                    # x = 0 and bias = pre: the cell on a given projection
     for dt, mm in ((F64, np.matmul), (F32, np.matmul), (F32, sn.matmul_chunked)):
         runs.append(sn.hidden_step("GRU", np.zeros((B, 1), F32), y0, ready, "sigmoid", dt, mm)["y"])
-    pre = {g: embed(D(pre64[g])) for g in order}
-    V = {g: embed(D(gates[g]["V"])) for g in order}
-    y_in, y_out, z, ry = embed(D(y0)), embed(nan_(B, H)), embed(nan_(B, H)), embed(nan_(B, H))
+    pre = {g: embed(D(pre64[g], F32)) for g in order}
+    V = {g: embed(D(gates[g]["V"], F32)) for g in order}
+    y_in, y_out, z, ry = embed(D(y0, F32)), embed(nan_(B, H)), embed(nan_(B, H)), embed(nan_(B, H))
     for phase in (1, 2):
         rc = lib.sparch_ann_stream_step(3, phase, 0, B, K, H, H, None, 0, None, None, None, None,
                                         arr(*[ptr(pre[g]) for g in order]), arr(*[ptr(V[g]) for g in order]), ptr(y_in),
@@ -359,9 +324,9 @@ def test_readout_kernel_against_fp64(B, K, H, norm, record_property):
     worst = 0.0
     for C in CLASSES:
         W, bias, p0, p1, ys, ref_out, ref_acc, b_out, b_acc = readout_case(B, K, C, norm)
-        row = lambda v: None if v is None else embed(D(v).view(1, -1))  # noqa: E731
-        Wd, bd, p0d, p1d = embed(D(W)), row(bias), row(p0), row(p1)
-        y_dev = [embed(D(ys[t]), ldy, 0) for t in range(STEPS)]
+        row = lambda v: None if v is None else embed(D(v, F32).view(1, -1))  # noqa: E731
+        Wd, bd, p0d, p1d = embed(D(W, F32)), row(bias), row(p0), row(p1)
+        y_dev = [embed(D(ys[t], F32), ldy, 0) for t in range(STEPS)]
         acc, out = embed(torch.zeros(B, K, device=DEV)), embed(nan_(B, C))
         outs = []
         for t in range(STEPS):

@@ -16,9 +16,9 @@ import torch
 
 from tests import stream_ann_numpy as sn
 from tests.golden_io import load
+from tests.kit import EALIGN, EINVAL
 
 FIXTURES = ["ann_MLP_bn", "ann_RNN_bn", "ann_LiGRU_bn", "ann_GRU_bn", "ann_MLP_ln_bias_noreadout"]
-EINVAL, EALIGN = -1, -2
 
 
 def _chunks(T):

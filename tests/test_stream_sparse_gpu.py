@@ -1,9 +1,9 @@
 """GPU: the event-driven fused streaming step — StreamingSNN(fused=True, sparse=True), sparch_stream_step_sparse_fwd /
 sparch_stream_step_sparse_readout (csrc/streamsparse.hip).
 
-The scenarios and assertions are those of tests/test_stream_fused_gpu.py, run on a module stand-in whose
-StreamingSNN(fused=True) is StreamingSNN(fused=True, sparse=True): the reference's dyadic fixtures in chunks of 1 (eager
-and as two alternately replayed graphs), eval-mode BatchNorm, fused and chunked steps mixed on one state, set_state /
+The scenarios and assertions are those of tests/test_stream_fused_gpu.py (the check_* bodies of tests/stream_cases.py,
+which both files call), run on a module stand-in whose StreamingSNN(fused=True) is StreamingSNN(fused=True,
+sparse=True): the reference's dyadic fixtures in chunks of 1 (eager and as two alternately replayed graphs), eval-mode BatchNorm, fused and chunked steps mixed on one state, set_state /
 refresh behind an odd number of steps, reset(rows=...) mid-stream (real-valued fresh rows beside binary rows in one
 row tile), uint8 counts, a padded layer feeding the next, and the teacher-forced real-valued cases with their bars
 unchanged.  Every such test also asserts that the sparse entry points, and not the dense fused ones, were called.
@@ -11,19 +11,17 @@ Of its own: the kernel geometries against the oracle on dyadic W and V with list
 waves, a full list beyond one piece, empty / full / 5 % rows in one row tile, a step without any input), the readout
 kernel against its dense twin at the C ABI, and the library calls of one step.
 """
-import contextlib
-
 import pytest
 import torch
 
-from oracle import snn_oracle as orc
-from tests import test_stream_fused_gpu as F
-from tests.test_stream_fused_gpu import dyadic_layer, exact_projection, one_layer_net, state_of
-from tests.test_streaming_gpu import dyadic_net, run_stream
+from tests import stream_cases as cases
+from tests.golden_io import DYADIC_LONG
+from tests.kit import DEV, sp  # noqa: F401  (sp: a fixture)
+from tests.kit import Fn as _Fn
+from tests.stream_cases import calls_of, dyadic_net, recorded_calls
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 SPARSE = ("sparch_stream_step_sparse_fwd", "sparch_stream_step_sparse_readout")
 DENSE = ("sparch_stream_step_fwd", "sparch_stream_step_readout")
 
@@ -44,37 +42,11 @@ class SparseModule:
         return st
 
 
-@contextlib.contextmanager
-def recorded_calls():
-    """The names of the fused-step entry points (dense and sparse) called meanwhile, in order."""
-    from sparch_amd import _capi
-    saved, seen = {}, []
-    for name in SPARSE + DENSE:
-        f = getattr(_capi.lib, name)
-        saved[name] = f
-
-        def wrapped(*a, _f=f, _n=name):
-            seen.append(_n)
-            return _f(*a)
-        setattr(_capi.lib, name, wrapped)
-    try:
-        yield seen
-    finally:
-        for name, f in saved.items():
-            setattr(_capi.lib, name, f)
-
-
-@pytest.fixture(scope="module")
-def sp():
-    import sparch_amd
-    return sparch_amd
-
-
 @pytest.fixture
 def spx(sp):
     """The stand-in module; behind the test: every fused stream was sparse, and only the sparse entry points ran."""
     mod = SparseModule(sp)
-    with recorded_calls() as seen:
+    with recorded_calls(SPARSE + DENSE) as seen:
         yield mod
     assert mod.made and all(st.sparse and st.sparse_active for st in mod.made)
     assert seen and all(n in SPARSE for n in seen), sorted(set(seen))
@@ -82,31 +54,31 @@ def spx(sp):
 
 # ------------------------------------------------------------------------------------------ 1. reference-pinned
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
-@pytest.mark.parametrize("name", ["dyadic_RadLIF_none", "dyadic_RLIF_none_bias", F.DYADIC_LONG])
+@pytest.mark.parametrize("name", ["dyadic_RadLIF_none", "dyadic_RLIF_none_bias", DYADIC_LONG])
 def test_sparse_stream_equals_reference_fixture(spx, name, graph):
-    F.test_fused_stream_equals_reference_fixture(spx, name, graph)   # (asserts both parities captured and replayed)
+    cases.check_fused_stream_equals_reference_fixture(spx, name, graph)   # (asserts both parities captured and replayed)
 
 
 # ------------------------------------------------------------------------------------------ 2. eval BatchNorm
 @pytest.mark.parametrize("kind", ["RadLIF", "adLIF", "LIF"])
 def test_sparse_stream_equals_eval_forward_with_batchnorm(spx, kind):
-    F.test_fused_stream_equals_eval_forward_with_batchnorm(spx, kind)
+    cases.check_fused_stream_equals_eval_forward_with_batchnorm(spx, kind)
 
 
 # ------------------------------------------------------------------------------------------ 3. parity, path mixing
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 def test_sparse_and_chunked_steps_alternate_on_one_state(spx, graph):
-    F.test_fused_and_chunked_steps_alternate_on_one_state(spx, graph)
+    cases.check_fused_and_chunked_steps_alternate_on_one_state(spx, graph)
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 @pytest.mark.parametrize("how", ["set_state", "refresh"])
 def test_stream_continues_behind_an_odd_number_of_sparse_steps(spx, how, graph):
-    F.test_stream_continues_behind_an_odd_number_of_fused_steps(spx, how, graph)
+    cases.check_stream_continues_behind_an_odd_number_of_fused_steps(spx, how, graph)
 
 
 def test_sparse_reset_rows_mid_stream(spx):
-    F.test_fused_reset_rows_mid_stream(spx)
+    cases.check_fused_reset_rows_mid_stream(spx)
 
 
 # ------------------------------------------------------------------------------------------ 4. geometry
@@ -142,35 +114,18 @@ GEOMETRIES = [("LIF", 1, 5, 3, 12, 126, 0.3), ("adLIF", 33, 70, 100, 12, 270, 0.
                          ids=[f"{g[0]}-{g[1]}-{g[2]}-{g[3]}-{g[6] if isinstance(g[6], float) else g[6].__name__[3:]}"
                               for g in GEOMETRIES])
 def test_sparse_step_geometries_vs_oracle(spx, kind, B, K, H, T, seed, inp):
-    W, p, u0, w0, s0 = dyadic_layer(kind, B, T, K, H, seed)
     x = _x(B, T, K, inp) if isinstance(inp, float) else inp(B, T, K)
-    with torch.no_grad():
-        ref = orc.spiking_cell(kind, exact_projection(x, W), p, u0, w0, s0)
-    assert ref.sum() > 0
-    st = spx.StreamingSNN(one_layer_net(spx, kind, K, [H], [W], [p]), B, fused=True)
-    st.set_state([state_of(u0, w0, s0)])
-    outs, rec = run_stream(st, x.to(DEV), [1] * T)
-    F._Fn().check_status()
-    s = torch.cat(outs, dim=1).cpu()
-    assert s.shape == ref.shape and torch.equal(s, ref), float((s != ref).float().mean())
-    assert torch.equal(rec[0], ref)
-    got = st.get_state()[0]
-    assert got["u"].shape == (B, H) and torch.equal(got["s"].cpu(), ref[:, -1])
-    assert torch.equal(st.firing_rates().cpu(), ref.sum(dim=(0, 1)).to(torch.int32) * (1.0 / float(B * T)))
-    L = st._layers[0]
-    if L.Hs != H:                                                   # the padded columns were never written
-        assert float(L.s[:, H:].abs().sum()) == 0 and float(L.s_alt[:, H:].abs().sum()) == 0
-        assert float(L.u[:, H:].abs().sum()) == 0 and int(L.count[H:].sum()) == 0
+    cases.check_step_geometry_vs_oracle(spx, kind, B, K, H, T, seed, x)
 
 
 # ------------------------------------------------------------------------------------------ 5. uint8, 6. padded layers
 def test_sparse_step_reads_uint8_counts_like_their_fp32_twin(spx):
-    F.test_fused_step_reads_uint8_counts_like_their_fp32_twin(spx)       # (counts up to 3; equal to the oracle too)
+    cases.check_fused_step_reads_uint8_counts_like_their_fp32_twin(spx)       # (counts up to 3; equal to the oracle too)
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 def test_sparse_padded_layer_feeds_the_next(spx, graph):
-    F.test_padded_layer_feeds_the_next(spx, graph)
+    cases.check_padded_layer_feeds_the_next(spx, graph)
 
 
 # ------------------------------------------------------------------------------------------ 7. real-valued
@@ -181,14 +136,14 @@ def test_sparse_padded_layer_feeds_the_next(spx, graph):
 def test_sparse_step_one_step_ahead_vs_oracle_trajectory(spx, kind, B, T, K, H, inp):
     """The dense fused test's cases and bars, unchanged: a spike may differ only where the oracle's |u - 1| <= 1e-4;
     flips <= 1e-4 N + 2; oracle rate > 0.003."""
-    F.test_fused_step_one_step_ahead_vs_oracle_trajectory(spx, kind, B, T, K, H, inp)
+    cases.check_fused_step_one_step_ahead_vs_oracle_trajectory(spx, kind, B, T, K, H, inp)
 
 
 # ------------------------------------------------------------------------------------------ 8. readout at the C ABI
 @pytest.mark.parametrize("B,K,C", [(1, 5, 5), (33, 130, 35), (4, 1024, 256)])
 def test_sparse_readout_kernel_equals_the_dense_readout_step(B, K, C):
     from sparch_amd._capi import check, lib, ptr
-    Fn = F._Fn()
+    Fn = _Fn()
     g = torch.Generator().manual_seed(B + K + C)
     W = (torch.randint(-24, 25, (C, K), generator=g).float() / 64.0).to(DEV)
     ldc = (C + 3) // 4 * 4
@@ -217,28 +172,8 @@ def test_sparse_readout_kernel_equals_the_dense_readout_step(B, K, C):
 
 # ------------------------------------------------------------------------------------------ 9. library calls
 def test_sparse_step_is_one_library_call_per_layer(sp):
-    from sparch_amd import _capi
     net, init = dyadic_net(sp, "RadLIF", 4, 64, [64, 64, 20], "none", 13)
     x = (torch.rand(4, 3, 64, generator=torch.Generator().manual_seed(2)) < 0.3).float().to(DEV)
-
-    def calls_of(fn):
-        names = [n for n in _capi.PROTOTYPES if not n.endswith("_bytes") and n not in ("sparch_device_cus",)]
-        saved, seen = {}, []
-        for name in names:
-            f = getattr(_capi.lib, name)
-            saved[name] = f
-
-            def wrapped(*a, _f=f, _n=name):
-                seen.append(_n)
-                return _f(*a)
-            setattr(_capi.lib, name, wrapped)
-        try:
-            fn()
-        finally:
-            for name, f in saved.items():
-                setattr(_capi.lib, name, f)
-        return seen
-
     sparse, dense = sp.StreamingSNN(net, 4, fused=True, sparse=True), sp.StreamingSNN(net, 4, fused=True)
     assert sparse.sparse_active and not dense.sparse_active
     for st in (sparse, dense):

@@ -16,60 +16,13 @@ from oracle import bptt_numpy as bp
 from oracle import snn_oracle as orc
 from tests.golden_io import DYADIC_LONG, layer_spikes, snn_case
 from tests.guarded import guard_arena
+from tests.kit import DEV, bf16_mode, sp  # noqa: F401  (bf16_mode, sp: fixtures)
+from tests.kit import Fn as _Fn
+from tests.spiking_cases import build_snn as _build
+from tests.spiking_cases import dyadic_cell_case_fwd as _dyadic_cell_case
+from tests.stream_cases import chunkings, dyadic_net, run_stream, whole_forward
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def sp():
-    import sparch_amd
-    return sparch_amd
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-@pytest.fixture
-def bf16_mode():
-    Fn = _Fn()
-    prev = Fn.set_compute_dtype("bf16")
-    yield Fn
-    Fn.set_compute_dtype(prev)
-
-
-def _build(sp, cfg, params):
-    net = sp.SNN((cfg["B"], None, cfg["C"]), cfg["layer_sizes"], neuron_type=cfg["neuron_type"], dropout=0.0,
-                 normalization=cfg["normalization"], use_bias=cfg["use_bias"], bidirectional=cfg["bidirectional"],
-                 use_readout_layer=cfg["use_readout_layer"])
-    missing = net.load_state_dict(params, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return net.to(DEV)
-
-
-def chunkings(T):
-    uneven, pat, i = [], [5, 1, 13, 2, 8, 1, 1, 30], 0
-    while sum(uneven) < T:
-        uneven.append(min(pat[i % len(pat)], T - sum(uneven)))
-        i += 1
-    return {"ones": [1] * T, "sevens": [7] * (T // 7) + ([T % 7] if T % 7 else []), "whole": [T], "uneven": uneven}
-
-
-def run_stream(st, x, chunks):
-    """Feed x (B,T,C) on the device in `chunks`; returns (final out or concatenated spikes, per-layer spikes)."""
-    rec = {}
-    st._spike_tap = lambda k, s: rec.setdefault(k, []).append(s.float().cpu())
-    outs, t0 = [], 0
-    for n in chunks:
-        out = st.step(x[:, t0:t0 + n])
-        outs.append(out.clone())
-        t0 += n
-    assert t0 == x.shape[1] and st.steps_seen >= t0
-    st._spike_tap = None
-    return outs, {k: torch.cat(v, dim=1) for k, v in rec.items()}
 
 
 # ------------------------------------------------------------------------------------------ 1. reference-pinned
@@ -103,59 +56,6 @@ def test_stream_equals_reference_fixture(sp, name, chunking, graph):
 
 
 # ------------------------------------------------------------------------------------------ 2. chunked == whole
-def whole_forward(net, x, order):
-    """net(x) in eval with the initial states `order` (flat list, the draw order) injected; per-layer spikes taken
-    from the layers' outputs as they travel (the bf16 plane)."""
-    from sparch_amd import snns as snn_mod
-    states = iter(order)
-
-    def next_state(rows, cols, device):
-        t = next(states)
-        assert tuple(t.shape) == (rows, cols)
-        return t.to(device)
-
-    rec, originals = {}, []
-    hidden = list(net.snn)[:-1] if net.use_readout_layer else list(net.snn)
-    for k, lay in enumerate(hidden):
-        def wrapped(inp, states=None, orig=lay.forward_with_rate, k=k, **kw):
-            s, r = orig(inp, states=states, **kw)
-            rec[k] = snn_mod.materialize_spikes(s).detach().float().cpu()
-            return s, r
-        originals.append(lay)
-        lay.forward_with_rate = wrapped
-    old = snn_mod._rand_to
-    snn_mod._rand_to = next_state
-    try:
-        with torch.no_grad():
-            out, rates = net(x)
-    finally:
-        snn_mod._rand_to = old
-        for lay in originals:
-            del lay.forward_with_rate
-    return out, rates, rec
-
-
-def dyadic_net(sp, kind, B, C, sizes, norm, seed):
-    """A network with W on a 2^-6 grid (V too), BatchNorm statistics moved off their initial values, 0/1 input and
-    initial states on a 2^-4 grid: every projection sum is exact in any order."""
-    torch.manual_seed(seed)
-    net = sp.SNN((B, None, C), sizes, neuron_type=kind, dropout=0.0, normalization=norm)
-    g = torch.Generator().manual_seed(seed + 1)
-    with torch.no_grad():
-        for lay in net.snn:
-            lay.W.weight.copy_(torch.round(lay.W.weight * 4 * 64) / 64)
-            if hasattr(lay, "V"):
-                lay.V.weight.copy_(torch.round(lay.V.weight * 64) / 64)
-            if norm == "batchnorm":
-                lay.norm.running_mean.copy_(torch.rand(lay.hidden_size, generator=g) * 0.2 - 0.1)
-                lay.norm.running_var.copy_(torch.rand(lay.hidden_size, generator=g) * 0.1 + 0.02)
-                lay.norm.weight.copy_(torch.rand(lay.hidden_size, generator=g) + 0.5)
-                lay.norm.bias.copy_(torch.rand(lay.hidden_size, generator=g) * 0.4)
-    init = orc.draw_init_states(B, sizes, kind)
-    init = [{k: torch.floor(v * 16) / 16 for k, v in st.items()} for st in init]
-    return net.to(DEV).eval(), init
-
-
 def check_stream_equals_whole(sp, net, x, init, chunks, graph=False, spiking=None):
     Fn = _Fn()
     order = [st[k] for st in init for k in ("u0", "w0", "s0") if k in st]
@@ -375,20 +275,6 @@ def test_recurrent_stream_one_step_ahead_vs_oracle_trajectory(sp, kind, Bp, T, H
 
 
 # ------------------------------------------------------------------------------------------ 4. geometry
-def _dyadic_cell_case(kind, Bp, T, H, seed):
-    g = torch.Generator().manual_seed(seed)
-    V = torch.randint(-24, 25, (H, H), generator=g).float() / 64.0
-    Wx = torch.randn(Bp, T, H, generator=g) * 1.5 + 0.4
-    p = {"alpha": torch.rand(H, generator=g) * 0.2 + 0.78, "V": V}
-    if kind == "RadLIF":
-        p.update(beta=torch.rand(H, generator=g) * 0.05 + 0.95, a=torch.rand(H, generator=g) * 2.4 - 1.2,
-                 b=torch.rand(H, generator=g) * 2.4 - 0.2)
-    u0 = torch.rand(Bp, H, generator=g)
-    w0 = torch.rand(Bp, H, generator=g) if kind == "RadLIF" else None
-    s0 = (torch.rand(Bp, H, generator=g) < 0.3).float()
-    return Wx, p, u0, w0, s0
-
-
 @pytest.mark.parametrize("kind,Bp,T,H,chunk", [("RadLIF", 256, 250, 1024, 10), ("RadLIF", 1, 30, 64, 7),
                                                ("RLIF", 33, 30, 96, 4), ("RadLIF", 5, 12, 1536, 5),
                                                ("RLIF", 9, 20, 130, 3), ("RadLIF", 40, 20, 130, 20)])

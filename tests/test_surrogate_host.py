@@ -25,10 +25,8 @@ import torch
 
 from tests import spiking_numpy as sn
 from tests import surrogate_numpy as sg
-from tests.test_rec_entry_validation_host import (EALIGN, EINVAL, EWORKSPACE, KIND, MIS, NAN, P, RLIF, WS, Entry, T,
-                                                  head, ptrs)
-
-F32, F64 = np.float32, np.float64
+from tests.entry_probes import KIND, MIS, NAN, RLIF, WS, Entry, P, T, head, ptrs
+from tests.kit import EALIGN, EINVAL, EWORKSPACE, F32, F64
 
 
 # ------------------------------------------------------------------------------------------------ the restatement

@@ -33,32 +33,16 @@ import torch
 
 from tests import spiking_numpy as sn
 from tests import surrogate_numpy as sg
-from tests.test_dropout_rate_backward_gpu import SEED
-from tests.test_rec_cell_real_V_gpu import N, bf16_mode, record, within  # noqa: F401  (bf16_mode: a fixture)
-from tests.test_rec_cell_real_V_gpu import case as rec_case
-from tests.test_scan_kernels_fp64_gpu import GEOM, case_of
-from tests.test_scan_kernels_fp64_gpu import kernel_forward as scan_forward
+from tests.kit import DEV, F32, F64, SEED, N, bf16_mode, record, within  # noqa: F401  (bf16_mode: a fixture)
+from tests.kit import Fn as _Fn
+from tests.spiking_cases import GEOM, collect, rec_case, scan_forward
+from tests.spiking_cases import scan_case_of as case_of
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-F32, F64 = np.float32, np.float64
 P_DROP = sn.P_DROP
 FORMS = [(name, sg.TEST_SCALE[name]) for name in sg.SMOOTH]
 form_id = lambda f: f[0] if isinstance(f, tuple) else None  # noqa: E731
-
-
-def _Fn():
-    from sparch_amd import functional
-    return functional
-
-
-def collect(dWx, grads, with_bn):
-    got = {"dWx": N(dWx)}
-    got.update({k: N(v) for k, v in grads.items() if k != "bn_sums"})
-    if with_bn:
-        got["bn_dy"], got["bn_dyx"] = N(grads["bn_sums"][0]), N(grads["bn_sums"][1])
-    return got
 
 
 def held(got, kind, with_bn, bw):
