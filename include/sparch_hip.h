@@ -345,6 +345,30 @@ int sparch_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_o
                        float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
                        const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
                        void* stream);
+/* Ragged batches ("Ragged batches"): the `_len` forms of the cell and readout entry points take
+ * lengths (B,) int32 on the device, 1 <= lengths[b] <= T, and n_valid = sum(lengths).  Row b then comes out as the
+ * row run alone over its first lengths[b] steps would:
+ *   forward : s_out / s16_out are exactly 0 for t >= lengths[b], and those steps are not counted in spike_count
+ *             (the state runs on over the padding: u_save / w_save hold values there that nothing valid depends on);
+ *   backward: the incoming gradient (g_out plus the rate term) counts as 0 for t >= lengths[b] — whatever g_out
+ *             holds there, a NaN included — so dWx is exactly 0 there and the partial sums see valid steps only;
+ *             the rate gradient is scaled by 1 / n_valid instead of 1 / (B T); `surrogate` as in the _sg forms.
+ * SPARCH_EINVAL, before any device work, for dirs != 1, lengths == NULL and n_valid < 1; everything else as the
+ * entry point without lengths.                                                                                  */
+int sparch_cell_fwd_len(int kind, int B, int dirs, int T, int H, const float* Wx,
+                        const float* scale, const float* shift, const float* alpha,
+                        const float* beta, const float* a, const float* b, const float* u0,
+                        const float* w0, const float* s0, float theta, float p_drop,
+                        uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                        int save_bf16, uint32_t* spike_count, const int* lengths, long long n_valid,
+                        void* stream);
+int sparch_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_out,
+                        const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                        const float* alpha, const float* beta, const float* a, const float* b,
+                        const float* u0, const float* w0, const float* s0, float theta,
+                        float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                        const float* bn_mean, const float* bn_invstd, const int* lengths, long long n_valid,
+                        int surrogate, float surrogate_scale, void* stream);
 
 /* Recurrent kinds (RLIF, RadLIF).  V (H,H) = V.weight; the diagonal is masked inside
  * (snns.py:566/712).  The recurrent product s_{t-1}*V runs on MFMA with the V slice of
@@ -420,6 +444,28 @@ int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float*
                            const float* bn_x, const float* bn_mean, const float* bn_invstd,
                            void* chan, size_t chan_bytes, uint32_t* status,
                            int steps_per_launch, int surrogate, float surrogate_scale, void* stream, int precision);
+/* The ragged forms (see sparch_cell_fwd_len): persistent and chunked steps_per_launch, both operand precisions, fp32
+ * and bf16 saves (bf16 with the box-car only, as above).  The spikes the workgroups hand each other stay unmasked —
+ * a row's padded steps never reach one of its valid steps.  H <= 1024 (there is no ragged per-step form).      */
+int sparch_rec_cell_fwd_len(int kind, int B, int dirs, int T, int H, const float* Wx,
+                            const float* scale, const float* shift, const float* alpha,
+                            const float* beta, const float* a, const float* b,
+                            const float* vpack, const float* rec0, const float* u0,
+                            const float* w0, const float* s0, float theta, float p_drop,
+                            uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save,
+                            void* w_save, int save_bf16, uint32_t* spike_count, const int* lengths,
+                            long long n_valid, void* chan, size_t chan_bytes, uint32_t* status,
+                            int steps_per_launch, void* stream, int precision);
+int sparch_rec_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_out,
+                            const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                            const float* alpha, const float* beta, const float* a,
+                            const float* b, const float* vpack_t, const float* u0,
+                            const float* w0, const float* s0, float theta, float p_drop,
+                            uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                            const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                            const int* lengths, long long n_valid, void* chan, size_t chan_bytes,
+                            uint32_t* status, int steps_per_launch, int surrogate, float surrogate_scale,
+                            void* stream, int precision);
 /* ONE time step t of the same cells with the recurrent product supplied by the caller — the path for hidden
  * sizes whose V slice does not fit the persistent kernels' register-resident layout (H > 1024; the reference
  * accepts any nb_hiddens, snns.py:608-661): any grid size, nothing waits inside a launch.
@@ -544,6 +590,16 @@ int sparch_readout_bwd(int B, int T, int C, const float* g_out, const float* bn_
                        const float* bn_mean, const float* bn_invstd, const float* u_save,
                        const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
                        void* stream);
+/* The ragged forms (see sparch_cell_fwd_len): out[b] = sum_{t < lengths[b]} softmax(u_t) — a truncated sum, not a
+ * mean — with the recurrence, the softmax and the sum bounded by the row's length (u_save is not written past it);
+ * the backward starts its reverse recurrence at the row's last step and writes dWx = 0 behind it.              */
+int sparch_readout_fwd_len(int B, int T, int C, const float* Wx, const float* scale,
+                           const float* shift, const float* alpha, const float* u0, float* out,
+                           float* u_save, const int* lengths, long long n_valid, void* stream);
+int sparch_readout_bwd_len(int B, int T, int C, const float* g_out, const float* bn_x,
+                           const float* bn_mean, const float* bn_invstd, const float* u_save,
+                           const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                           const int* lengths, long long n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * G9  mel filterbank front-end  (replaces torchaudio.compliance.kaldi.fbank(x,

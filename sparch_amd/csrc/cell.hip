@@ -36,6 +36,10 @@ struct CellArgs {
     int save16;  // u_save / w_save hold bf16 (common.h save_u16) instead of fp32
 };
 
+// The ragged entry points (`_len`): per-row sequence lengths (B,) behind CellArgs, which does not grow — only the
+// `_len` instantiations take them.
+struct CellLenArgs : CellArgs { const int* lengths; };
+
 template <int VEC>
 __device__ __forceinline__ void ldv(float (&d)[VEC], const float* p) {
     if constexpr (VEC == 4) {
@@ -137,8 +141,10 @@ template <> struct SavedVec<1, true> {
 // wait-count pass fall back to `s_waitcnt vmcnt(0)` at the join, once per trip — the ring would drain every D steps)
 // STATE (streaming, sparch_cell_stream_fwd): u0 / w0 / s0 are the stream's (Bp,H) state buffers — read here as ever,
 // and written back from the registers behind the last step, so that the next chunk's launch continues the sequence.
-template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP, bool STATE = false>
-__global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
+// LEN (sparch_cell_fwd_len, one direction): the row's length is held by the thread, and the output spikes of steps at
+// or past it are 0 — a select on the value, not a branch (see DROP).  The state still runs on over the padding.
+template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP, bool STATE = false, bool LEN = false>
+__global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<LEN, CellLenArgs, CellArgs> c) {
     constexpr int D = pipe_depth(VEC, 1 + (SOUT ? 1 : 0) + (S16OUT ? 1 : 0) + (SAVE ? 1 + (ADAPT ? 1 : 0) : 0));
     const int HQ = c.H / VEC;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -165,6 +171,8 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
     const bool has_norm = c.scale != nullptr;
     constexpr bool drop = DROP;
     const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
+    int len = T;
+    if constexpr (LEN) len = c.lengths[b];
 
     const float* xrow = c.Wx + (size_t)b * T * H + h;
     auto fetch = [&](float (&x)[VEC], int t) __attribute__((always_inline)) {
@@ -181,6 +189,7 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
             neuron_step<ADAPT, false>(u[e], w[e], s[e], xn, 0.f, p[e], c.theta);
             const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
             so[e] = s[e] * k;
+            if constexpr (LEN) so[e] = t < len ? so[e] : 0.0f;
             cnt[e] += (so[e] != 0.0f) ? 1u : 0u;
         }
         if (SOUT) stv<VEC>(c.s_out + o, so);
@@ -236,6 +245,12 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(CellArgs c) {
 // The reverse pass exists as two kernel families with ONE body (cell_bwd_body.inc): cell_bwd_pipe_kernel gates with
 // the reference's box-car, cell_bwd_pipe_sg_kernel with one of the smooth surrogates, chosen by a wave-uniform switch
 // on its second argument (fp32 saves only: S16 is never set there).
+// cell_bwd_pipe_len_kernel (sparch_cell_bwd_len) is the ragged one: ROW_LEN(b) is the row's length and TAIL_ZERO(t, v)
+// takes the incoming gradient of step t as 0 at or past it; cell_bwd_pipe_len_sg_kernel is the same with a smooth gate
+// (two kernels as above: with both gates behind one run-time switch the box-car's VEC = 4 kernels came out of hipcc
+// with the smooth kernels' 256 VGPRs + AGPR copies at one wave per SIMD).
+#define ROW_LEN(b) T
+#define TAIL_ZERO(t, v) (v)
 template <bool ADAPT, int VEC, bool S16, bool BN, bool DROP>
 __global__ __launch_bounds__(256) void cell_bwd_pipe_kernel(CellArgs c)
 #define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
@@ -246,6 +261,24 @@ __global__ __launch_bounds__(256) void cell_bwd_pipe_sg_kernel(CellArgs c, Surro
 #define SURROGATE_GATE(ds, x) smooth_gate(sg.id, sg.k, ds, x)
 #include "cell_bwd_body.inc"
 #undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
+// (the select as a bit mask on the value: as `t < row_len ? v : 0.0f` hipcc gave the box-car kernels 167 VGPRs for 95 at one
+// neuron per thread and 256 + 182 AGPR copies for 246 at four — one wave per SIMD less; as a mask 110 and 246)
+#define ROW_LEN(b) c.lengths[b]
+#define TAIL_ZERO(t, v) __uint_as_float(__float_as_uint(v) & ((t) < row_len ? 0xFFFFFFFFu : 0u))
+template <bool ADAPT, int VEC, bool S16, bool BN, bool DROP>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_len_kernel(CellLenArgs c)
+#define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+template <bool ADAPT, int VEC, bool BN, bool DROP, bool S16 = false>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_len_sg_kernel(CellLenArgs c, SurrogateArgs sg)
+#define SURROGATE_GATE(ds, x) smooth_gate(sg.id, sg.k, ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
 
 // ------------------------------------------------------------------ readout cell
 // Readout layer (snns.py:815-825): u_t = alpha u_{t-1} + (1-alpha) x_t, out = sum_t softmax_c(u_t).
@@ -304,16 +337,20 @@ struct RoCursor {
 // STREAM (sparch_readout_stream_fwd): `u_io` (B,C) is the membrane state, read in place of u0 and written back behind
 // the last step, and `out` comes in holding the running sum: the accumulator CONTINUES the one sequential sum over t
 // (per-chunk sums added afterwards would round differently).
-template <bool STREAM>
+// LEN (sparch_readout_fwd_len): the row's own length bounds the recurrence, the softmax and the sum — out is the
+// truncated sum over t < lengths[b], what the clip run alone gives; u_save is not written past it.
+template <bool STREAM, bool LEN = false>
 __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C, int rows, const float* __restrict__ Wx,
                                                             const float* __restrict__ scale,
                                                             const float* __restrict__ shift,
                                                             const float* __restrict__ alpha,
                                                             const float* __restrict__ u0, float* __restrict__ out,
-                                                            float* __restrict__ u_save, float* u_io) {
+                                                            float* __restrict__ u_save, float* u_io,
+                                                            const int* __restrict__ lengths) {
     __shared__ float us[RO_FWD_FLOATS];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
+    const int Tb = LEN ? min(max(lengths[b], 0), T) : T;  // the steps this row has
     const int CS = ro_row_stride(C);
     const bool act = tid < C;
     const bool wave_has_class = (tid & ~63) < C;  // wave-uniform: waves past the classes skip the class phases
@@ -325,8 +362,8 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     float u = STREAM ? u_io[(size_t)b * C + cp] : u0[(size_t)b * C + cp];
     float acc = STREAM ? out[(size_t)b * C + cp] : 0.f;
     const __amdgpu_buffer_rsrc_t rx = ro_row(Wx, (size_t)T * C, b), ru = ro_row(u_save, (size_t)T * C, b);
-    for (int c0 = 0; c0 < T; c0 += rows) {
-        const int len = min(rows, T - c0), n = len * C;
+    for (int c0 = 0; c0 < Tb; c0 += rows) {
+        const int len = min(rows, Tb - c0), n = len * C;
         // thread = element: the chunk's projection -> LDS
         {
             RoCursor cur(tid, C);
@@ -408,7 +445,9 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
 //   du_t = alpha du_{t+1} + e_t,  dWx_t = (1-alpha) du_t,  dalpha += du_t (u_{t-1} - u_t) / (1-alpha)
 //                                          (thread = class; reverse time)
 // Three chunk images in LDS: u (overwritten by e), u_{t-1} - u_t, and BatchNorm's xhat of the raw projection.
+// LEN (sparch_readout_bwd_len): the reverse recurrence starts at the row's last valid step; dWx past it is written as 0.
 extern __shared__ __attribute__((aligned(16))) float ro_dyn_lds[];
+template <bool LEN>
 __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C, int rows, const float* __restrict__ g_out,
                                                             const float* __restrict__ u_save,
                                                             const float* __restrict__ alpha,
@@ -416,10 +455,12 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                                                             float* __restrict__ dalpha_ws,
                                                             const float* __restrict__ bn_x,
                                                             const float* __restrict__ bn_mean,
-                                                            const float* __restrict__ bn_invstd) {
+                                                            const float* __restrict__ bn_invstd,
+                                                            const int* __restrict__ lengths) {
     __shared__ float gs[RO_NT];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
+    const int Tb = LEN ? min(max(lengths[b], 0), T) : T;  // the steps this row has
     const int CS = ro_row_stride(C);
     float* const ue = ro_dyn_lds;            // [rows][CS] u_t, then e_t
     float* const dl = ue + rows * CS;        // [rows][CS] u_{t-1} - u_t
@@ -436,9 +477,12 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     float acc_dy = 0.f, acc_dyx = 0.f;
     const __amdgpu_buffer_rsrc_t ru = ro_row(u_save, (size_t)T * C, b), rb = ro_row(bn_x, (size_t)T * C, b),
                                  rd = ro_row(dWx, (size_t)T * C, b), r0 = ro_row(u0, (size_t)C, b);
-    const int nchunk = (T + rows - 1) / rows;
+    if constexpr (LEN) {  // thread = element: the padded tail of dWx
+        for (int idx = Tb * C + tid; idx < T * C; idx += RO_NT) ro_store(0.f, rd, (unsigned)((size_t)idx * sizeof(float)));
+    }
+    const int nchunk = (Tb + rows - 1) / rows;
     for (int ch = nchunk - 1; ch >= 0; --ch) {
-        const int c0 = ch * rows, len = min(rows, T - c0), n = len * C;
+        const int c0 = ch * rows, len = min(rows, Tb - c0), n = len * C;
         // thread = element: u_t, u_{t-1} - u_t (u_{-1} = u0) and xhat_t of the chunk -> LDS
         {
             RoCursor cur(tid, C);
@@ -527,8 +571,24 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     }
 }
 
-template <bool ADAPT, int VEC, bool DROP>
-void launch_cell_pipe(bool bwd, const CellArgs& c, const SurrogateArgs& sg, unsigned blocks, hipStream_t st) {
+// Args = CellLenArgs: the ragged instantiations (the forward's LEN, and the one backward family of every surrogate)
+template <bool ADAPT, int VEC, bool DROP, class Args>
+void launch_cell_pipe(bool bwd, const Args& c, const SurrogateArgs& sg, unsigned blocks, hipStream_t st) {
+    constexpr bool LEN = std::is_same_v<Args, CellLenArgs>;
+    if constexpr (LEN) {
+        if (bwd) {
+            auto go = [&](auto s16, auto bn) {  // (bf16 saves: the box-car only — the entry point has refused the rest)
+                constexpr bool S16 = decltype(s16)::value, BN = decltype(bn)::value;
+                if (S16 || sg.id == SPARCH_SURROGATE_BOXCAR)
+                    hipLaunchKernelGGL((cell_bwd_pipe_len_kernel<ADAPT, VEC, S16, BN, DROP>), dim3(blocks), dim3(256), 0, st, c);
+                else
+                    hipLaunchKernelGGL((cell_bwd_pipe_len_sg_kernel<ADAPT, VEC, BN, DROP>), dim3(blocks), dim3(256), 0, st, c, sg);
+            };
+            if (c.save16) { if (c.bn_x) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+            else          { if (c.bn_x) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
+            return;
+        }
+    } else {
     if (bwd && sg.id != SPARCH_SURROGATE_BOXCAR) {  // (fp32 saves: the entry point has refused bf16 ones)
         auto go = [&](auto bn) {
             hipLaunchKernelGGL((cell_bwd_pipe_sg_kernel<ADAPT, VEC, decltype(bn)::value, DROP>), dim3(blocks), dim3(256), 0,
@@ -546,9 +606,10 @@ void launch_cell_pipe(bool bwd, const CellArgs& c, const SurrogateArgs& sg, unsi
         else          { if (c.bn_x) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
         return;
     }
+    }
     auto go = [&](auto save, auto sout, auto s16out) {
         hipLaunchKernelGGL((cell_fwd_pipe_kernel<ADAPT, VEC, decltype(save)::value, decltype(sout)::value,
-                                                 decltype(s16out)::value, DROP>),
+                                                 decltype(s16out)::value, DROP, false, LEN>),
                            dim3(blocks), dim3(256), 0, st, c);
     };
     auto outs = [&](auto save) {
@@ -561,8 +622,8 @@ void launch_cell_pipe(bool bwd, const CellArgs& c, const SurrogateArgs& sg, unsi
     else outs(std::integral_constant<int, 1>{});
 }
 
-template <bool ADAPT>
-int launch_cell(bool bwd, CellArgs& c, hipStream_t st, const SurrogateArgs sg = {}) {
+template <bool ADAPT, class Args>
+int launch_cell(bool bwd, Args& c, hipStream_t st, const SurrogateArgs sg = {}) {
     const long long work = (long long)c.B * c.dirs * c.H;
     const bool vec_ok = (c.H % 4 == 0);
     // VEC=4 only when it still leaves >= 8 waves per CU; small problems favour more threads
@@ -570,8 +631,8 @@ int launch_cell(bool bwd, CellArgs& c, hipStream_t st, const SurrogateArgs sg = 
     const long long threads = vec4 ? work / 4 : work;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
     const bool drop = c.p_drop > 0.0f;
-    if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 4, false>(bwd, c, sg, blocks, st); }
-    else      { if (drop) launch_cell_pipe<ADAPT, 1, true>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 1, false>(bwd, c, sg, blocks, st); }
+    if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true, Args>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 4, false, Args>(bwd, c, sg, blocks, st); }
+    else      { if (drop) launch_cell_pipe<ADAPT, 1, true, Args>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 1, false, Args>(bwd, c, sg, blocks, st); }
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -605,15 +666,13 @@ bool ptrs_aligned(std::initializer_list<const void*> ps) {
     return true;
 }
 
-}  // namespace
-
-extern "C" int sparch_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+// sparch_cell_fwd and sparch_cell_fwd_len (ragged: the row lengths, checked by the caller)
+int cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
                                const float* scale, const float* shift, const float* alpha,
                                const float* beta, const float* a, const float* b, const float* u0,
                                const float* w0, const float* s0, float theta, float p_drop,
                                uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
-                               int save_bf16, uint32_t* spike_count, void* stream) {
-    SPARCH_ENTER();
+                               int save_bf16, uint32_t* spike_count, void* stream, const int* lengths) {
     if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
     const bool adapt = kind == SPARCH_KIND_ADLIF;
     if (B <= 0 || T <= 0 || H <= 0 || (dirs != 1 && dirs != 2) || !Wx || !alpha || !u0 || !s0 || (!s_out && !s16_out))
@@ -631,8 +690,76 @@ extern "C" int sparch_cell_fwd(int kind, int B, int dirs, int T, int H, const fl
     c.theta = theta; c.p_drop = p_drop; c.inv_keep = 1.0f / (1.0f - p_drop); c.seed = seed;
     c.s_out = s_out; c.s16_out = s16_out; c.u_save = (float*)u_save; c.w_save = (float*)w_save;
     c.save16 = save_bf16 != 0; c.spike_count = spike_count;
+    if (lengths) {
+        CellLenArgs cl{c, lengths};
+        return adapt ? launch_cell<true>(false, cl, (hipStream_t)stream) : launch_cell<false>(false, cl, (hipStream_t)stream);
+    }
     return adapt ? launch_cell<true>(false, c, (hipStream_t)stream)
                  : launch_cell<false>(false, c, (hipStream_t)stream);
+}
+
+// sparch_cell_bwd_sg and sparch_cell_bwd_len (ragged: n_valid is the rate gradient's sample count)
+int cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                  const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                  const float* alpha, const float* beta, const float* a, const float* b,
+                                  const float* u0, const float* w0, const float* s0, float theta,
+                                  float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                                  const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
+                                  void* stream, const int* lengths, long long n_valid) {
+    if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
+    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
+    if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x))) return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_ADLIF;
+    if (B <= 0 || T <= 0 || H <= 0 || (dirs != 1 && dirs != 2) || !g_out || !u_save || !alpha || !u0 ||
+        !s0 || !dWx || !dparam_ws)
+        return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
+    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!ptrs_aligned({g_out, u_save, w_save, u0, w0, s0, dWx, dparam_ws})) return SPARCH_EALIGN;
+    CellArgs c{};
+    c.B = B; c.dirs = dirs; c.T = T; c.H = H;
+    c.alpha = alpha; c.beta = beta; c.a = a; c.b = b;
+    c.u0 = u0; c.w0 = w0; c.s0 = s0;
+    c.theta = theta; c.p_drop = p_drop; c.inv_keep = 1.0f / (1.0f - p_drop); c.seed = seed;
+    c.u_save = (float*)const_cast<void*>(u_save); c.w_save = (float*)const_cast<void*>(w_save);
+    c.save16 = save_bf16 != 0;
+    c.g_out = g_out; c.g_rate = g_rate;
+    c.g_rate_scale = lengths ? 1.0f / (float)n_valid : 1.0f / ((float)B * (float)T);
+    c.dWx = dWx; c.dparam_ws = dparam_ws;
+    c.bn_x = bn_x; c.bn_mean = bn_mean; c.bn_invstd = bn_invstd;
+    const SurrogateArgs sg{surrogate, surrogate_scale};
+    if (lengths) {
+        CellLenArgs cl{c, lengths};
+        return adapt ? launch_cell<true>(true, cl, (hipStream_t)stream, sg) : launch_cell<false>(true, cl, (hipStream_t)stream, sg);
+    }
+    return adapt ? launch_cell<true>(true, c, (hipStream_t)stream, sg)
+                 : launch_cell<false>(true, c, (hipStream_t)stream, sg);
+}
+
+}  // namespace
+
+extern "C" int sparch_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                               const float* scale, const float* shift, const float* alpha,
+                               const float* beta, const float* a, const float* b, const float* u0,
+                               const float* w0, const float* s0, float theta, float p_drop,
+                               uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                               int save_bf16, uint32_t* spike_count, void* stream) {
+    SPARCH_ENTER();
+    return cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed, s_out,
+                    s16_out, u_save, w_save, save_bf16, spike_count, stream, nullptr);
+}
+
+extern "C" int sparch_cell_fwd_len(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                   const float* scale, const float* shift, const float* alpha,
+                                   const float* beta, const float* a, const float* b, const float* u0,
+                                   const float* w0, const float* s0, float theta, float p_drop,
+                                   uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                                   int save_bf16, uint32_t* spike_count, const int* lengths, long long n_valid,
+                                   void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(dirs, lengths, n_valid)) return SPARCH_EINVAL;
+    return cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed, s_out,
+                    s16_out, u_save, w_save, save_bf16, spike_count, stream, lengths);
 }
 
 extern "C" int sparch_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
@@ -667,29 +794,22 @@ extern "C" int sparch_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const
                                   const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
                                   void* stream) {
     SPARCH_ENTER();
-    if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
-    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
-    if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x))) return SPARCH_EINVAL;
-    const bool adapt = kind == SPARCH_KIND_ADLIF;
-    if (B <= 0 || T <= 0 || H <= 0 || (dirs != 1 && dirs != 2) || !g_out || !u_save || !alpha || !u0 ||
-        !s0 || !dWx || !dparam_ws)
-        return SPARCH_EINVAL;
-    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
-    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
-    if (!ptrs_aligned({g_out, u_save, w_save, u0, w0, s0, dWx, dparam_ws})) return SPARCH_EALIGN;
-    CellArgs c{};
-    c.B = B; c.dirs = dirs; c.T = T; c.H = H;
-    c.alpha = alpha; c.beta = beta; c.a = a; c.b = b;
-    c.u0 = u0; c.w0 = w0; c.s0 = s0;
-    c.theta = theta; c.p_drop = p_drop; c.inv_keep = 1.0f / (1.0f - p_drop); c.seed = seed;
-    c.u_save = (float*)const_cast<void*>(u_save); c.w_save = (float*)const_cast<void*>(w_save);
-    c.save16 = save_bf16 != 0;
-    c.g_out = g_out; c.g_rate = g_rate; c.g_rate_scale = 1.0f / ((float)B * (float)T);
-    c.dWx = dWx; c.dparam_ws = dparam_ws;
-    c.bn_x = bn_x; c.bn_mean = bn_mean; c.bn_invstd = bn_invstd;
-    const SurrogateArgs sg{surrogate, surrogate_scale};
-    return adapt ? launch_cell<true>(true, c, (hipStream_t)stream, sg)
-                 : launch_cell<false>(true, c, (hipStream_t)stream, sg);
+    return cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, u0, w0, s0, theta,
+                    p_drop, seed, dWx, dparam_ws, bn_x, bn_mean, bn_invstd, surrogate, surrogate_scale, stream, nullptr, 0);
+}
+
+extern "C" int sparch_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                   const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                   const float* alpha, const float* beta, const float* a, const float* b,
+                                   const float* u0, const float* w0, const float* s0, float theta,
+                                   float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                                   const float* bn_mean, const float* bn_invstd, const int* lengths, long long n_valid,
+                                   int surrogate, float surrogate_scale, void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(dirs, lengths, n_valid)) return SPARCH_EINVAL;
+    return cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, u0, w0, s0, theta,
+                    p_drop, seed, dWx, dparam_ws, bn_x, bn_mean, bn_invstd, surrogate, surrogate_scale, stream, lengths,
+                    n_valid);
 }
 
 extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
@@ -703,16 +823,56 @@ extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const fl
                               SPARCH_SURROGATE_BOXCAR, 0.0f, stream);
 }
 
+namespace {
+int readout_fwd(int B, int T, int C, const float* Wx, const float* scale, const float* shift, const float* alpha,
+                const float* u0, float* out, float* u_save, const int* lengths, void* stream) {
+    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    const int rows = ro_chunk_steps(T, C, RO_FWD_FLOATS);
+    if (lengths)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, true>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C, rows, Wx,
+                           scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths);
+    else
+        hipLaunchKernelGGL((readout_fwd_kernel<false>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C, rows, Wx,
+                           scale, shift, alpha, u0, out, u_save, (float*)nullptr, (const int*)nullptr);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+template <bool LEN>
+int readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                const float* u_save, const float* alpha, const float* u0, float* dWx, float* dalpha_ws, const int* lengths,
+                void* stream) {
+    // (dalpha uses u_{t-1}-x_t = (u_{t-1}-u_t)/(1-alpha): the projection is re-read only for BatchNorm's sums)
+    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !g_out || !u_save || !alpha || !u0 || !dWx || !dalpha_ws)
+        return SPARCH_EINVAL;
+    if (bn_x && (!bn_mean || !bn_invstd)) return SPARCH_EINVAL;
+    const int rows = ro_chunk_steps(T, C, RO_BWD_FLOATS / 3);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_bwd_kernel<LEN>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       (int)(RO_BWD_FLOATS * sizeof(float)));
+    if (attr != hipSuccess) { sparch_note_hip_error((int)attr); return SPARCH_ELAUNCH; }
+    hipLaunchKernelGGL(readout_bwd_kernel<LEN>, dim3(B), dim3(RO_NT), (size_t)3 * rows * ro_row_stride(C) * sizeof(float),
+                       (hipStream_t)stream, B, T, C, rows, g_out, u_save, alpha, u0, dWx, dalpha_ws, bn_x, bn_mean,
+                       bn_invstd, lengths);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+}  // namespace
+
 extern "C" int sparch_readout_fwd(int B, int T, int C, const float* Wx, const float* scale,
                                   const float* shift, const float* alpha, const float* u0, float* out,
                                   float* u_save, void* stream) {
     SPARCH_ENTER();
-    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
-    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
-    hipLaunchKernelGGL(readout_fwd_kernel<false>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
-                       ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, nullptr, stream);
+}
+
+extern "C" int sparch_readout_fwd_len(int B, int T, int C, const float* Wx, const float* scale,
+                                      const float* shift, const float* alpha, const float* u0, float* out,
+                                      float* u_save, const int* lengths, long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, stream);
 }
 
 extern "C" int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, const float* scale,
@@ -723,7 +883,7 @@ extern "C" int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, c
     if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
     hipLaunchKernelGGL(readout_fwd_kernel<true>, dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
                        ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, (const float*)nullptr, out,
-                       (float*)nullptr, u);
+                       (float*)nullptr, u, (const int*)nullptr);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -733,18 +893,14 @@ extern "C" int sparch_readout_bwd(int B, int T, int C, const float* g_out, const
                                   const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
                                   void* stream) {
     SPARCH_ENTER();
-    // (dalpha uses u_{t-1}-x_t = (u_{t-1}-u_t)/(1-alpha): the projection is re-read only for BatchNorm's sums)
-    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !g_out || !u_save || !alpha || !u0 || !dWx || !dalpha_ws)
-        return SPARCH_EINVAL;
-    if (bn_x && (!bn_mean || !bn_invstd)) return SPARCH_EINVAL;
-    const int rows = ro_chunk_steps(T, C, RO_BWD_FLOATS / 3);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_bwd_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)(RO_BWD_FLOATS * sizeof(float)));
-    if (attr != hipSuccess) { sparch_note_hip_error((int)attr); return SPARCH_ELAUNCH; }
-    hipLaunchKernelGGL(readout_bwd_kernel, dim3(B), dim3(RO_NT), (size_t)3 * rows * ro_row_stride(C) * sizeof(float),
-                       (hipStream_t)stream, B, T, C, rows, g_out, u_save, alpha, u0, dWx, dalpha_ws, bn_x, bn_mean,
-                       bn_invstd);
-    SPARCH_CHECK_LAUNCH();
-    return SPARCH_OK;
+    return readout_bwd<false>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, nullptr, stream);
+}
+
+extern "C" int sparch_readout_bwd_len(int B, int T, int C, const float* g_out, const float* bn_x,
+                                      const float* bn_mean, const float* bn_invstd, const float* u_save,
+                                      const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                                      const int* lengths, long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
+    return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream);
 }

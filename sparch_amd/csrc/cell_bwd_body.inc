@@ -1,7 +1,10 @@
 // The body of the LIF / adLIF reverse pass (cell.hip includes it once per kernel family, behind the kernel's
 // signature): template parameters ADAPT, VEC, S16, BN, DROP, the argument `CellArgs c`, and SURROGATE_GATE(ds, x), the
 // surrogate gradient's gate — boxcar_gate for cell_bwd_pipe_kernel, smooth_gate on the second kernel argument for
-// cell_bwd_pipe_sg_kernel.  Text, not a function: inlined from a shared __device__ function the box-car kernels came
+// cell_bwd_pipe_sg_kernel, the same two for the ragged cell_bwd_pipe_len_kernel / cell_bwd_pipe_len_sg_kernel — and ROW_LEN(b) / TAIL_ZERO(t, v): the row's
+// length and the select that zeroes the incoming gradient of padded steps (T and the value itself in the kernels without
+// lengths; from a zero gradient the carries du, dw stay zero over the tail, and with them dWx and every partial sum).
+// Text, not a function: inlined from a shared __device__ function the box-car kernels came
 // out of the compiler with another schedule, and they are held to the instructions they had (DESIGN.md section 6).
 {
     constexpr int D = pipe_depth(VEC, 3 + (ADAPT ? 1 : 0) + (BN ? 1 : 0));
@@ -12,6 +15,7 @@
     const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
     const int d = bp / c.B, b = bp - d * c.B;
     const int T = c.T, H = c.H, HO = c.H * c.dirs;
+    [[maybe_unused]] const int row_len = ROW_LEN(b);
 
     float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], gr[VEC];
     float du_n[VEC], dw_n[VEC], u_t[VEC];
@@ -67,7 +71,7 @@
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
-            const float gs = (q.g[e] + gr[e]) * k;
+            const float gs = TAIL_ZERO(t, (q.g[e] + gr[e]) * k);
             float ds = gs - al[e] * du_n[e];
             if (ADAPT) ds = ds + pb[e] * dw_n[e];
             const float xs = u_t[e] - c.theta;

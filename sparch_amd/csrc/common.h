@@ -73,6 +73,10 @@ __device__ __forceinline__ float smooth_gate(int id, float k, float g, float x) 
     const float kx = k * x;
     return g / (1.0f + kx * kx);
 }
+// every surrogate behind one switch (the ragged `_len` backward kernels: one kernel family for all four)
+__device__ __forceinline__ float any_gate(int id, float k, float g, float x) {
+    return id == SPARCH_SURROGATE_BOXCAR ? boxcar_gate(g, x) : smooth_gate(id, k, g, x);
+}
 // what the _sg entry points check before any device work: a known id, a finite scale > 0 for the smooth forms, and
 // fp32 saves with them (bf16 saves keep the box-car's three decisions, not the continuous u a smooth gate reads)
 static inline bool surrogate_ok(int id, float k, int save_bf16) {
@@ -80,6 +84,10 @@ static inline bool surrogate_ok(int id, float k, int save_bf16) {
     if (id != SPARCH_SURROGATE_TRIANGLE && id != SPARCH_SURROGATE_FAST_SIGMOID && id != SPARCH_SURROGATE_ATAN) return false;
     return k > 0.0f && k <= 3.402823466e38f && !save_bf16;
 }
+
+// what a ragged (`_len`) entry point checks before any device work: one direction (a flipped direction would have to turn
+// inside each row's own length), the lengths, and at least one valid step in the batch
+static inline bool ragged_ok(int dirs, const int* lengths, long long n_valid) { return dirs == 1 && lengths && n_valid >= 1; }
 
 // ---- optional bf16 storage of the states saved for the backward pass (u, w): half the bytes of the two
 // largest tensors a spiking layer keeps.  The backward takes three DISCRETE decisions from a saved membrane

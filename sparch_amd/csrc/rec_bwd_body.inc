@@ -1,7 +1,8 @@
 // The body of the RLIF / RadLIF reverse pass (reccell.hip includes it once per kernel family, behind the kernel's
 // signature): template parameters ADAPT, KGW, NW, EXT, NP, S16, CW, the argument `a` (RecArgs, or RecSgArgs), and
 // SURROGATE_GATE(ds, x), the surrogate gradient's gate — boxcar_gate for rec_bwd_kernel, smooth_gate on `a.sg`
-// for rec_bwd_sg_kernel.  Text, not a function: see cell_bwd_body.inc.
+// for rec_bwd_sg_kernel, any_gate for the ragged rec_bwd_len_kernel (RecLenArgs) — and ROW_LEN(b) / TAIL_ZERO(t, v), the
+// row's length and the select on the incoming gradient of padded steps.  Text, not a function: see cell_bwd_body.inc.
 {
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT && NP == 1), "64-column workgroups: bf16 operand mode, 8 waves");
     // cross-wave reduction tiles: written before the step's first barrier, read after it by the pointwise
@@ -53,6 +54,7 @@
     const bool valid_hi = !pw && bp < a.Bp && col < H;  // upper-wave thread: same (row, columns) as tid - 256
     const int bpc = min(bp, a.Bp - 1), colc = min(col, H - 4);
     const int d = bpc / a.B, b = bpc - d * a.B;
+    [[maybe_unused]] const int row_len = ROW_LEN(b);
 
     u32x4 vb[CW][KGW][2][NP == 3 ? 2 : 1];
 #pragma unroll
@@ -186,7 +188,7 @@
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
-                const float gs = (gv[e] + gr[e]) * k;
+                const float gs = TAIL_ZERO(t, (gv[e] + gr[e]) * k);
                 pre_aldu[e] = al[e] * du_n[e];
                 float ds = gs - pre_aldu[e];
                 pre_padw[e] = ADAPT ? pa[e] * dw_n[e] : 0.f;

@@ -94,6 +94,12 @@ struct RecArgs {
     unsigned* xcd_tab;  // [n_rt_total][n_ct] agreement table of the XCD-local stores (whole-sequence launches), or null
 };
 
+// RecArgs itself does not grow (every kernel's argument segment would): the smooth-surrogate backward kernels take it
+// with the surrogate behind it, the ragged (`_len`) kernels with the surrogate and the per-row lengths (B,), as one
+// by-value argument (the kernel table's rows are KernelRef<Args>)
+struct RecSgArgs : RecArgs { SurrogateArgs sg; };
+struct RecLenArgs : RecSgArgs { const int* lengths; };
+
 // Diagnostic build only (-DSPARCH_REC_PROF, never shipped): per-workgroup sums of s_memtime
 // deltas for the segments of a time step, written to a private buffer no kernel reads.
 #ifdef SPARCH_REC_PROF
@@ -139,8 +145,11 @@ __device__ u64 g_rec_prof[2][512][12];
 // w0 / s0 are the stream's (Bp,H) state buffers: EVERY launch starts from them (a launch per step included) and
 // writes the state it ended in back behind its last step, each thread its own elements; the last step's raw spikes
 // also go to s_step16 as a bf16 0/1 plane, the operand of the caller's next s @ V product.
-template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool STREAM = false>
-__global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
+// LEN (sparch_rec_cell_fwd_len, one direction): the output spikes of steps at or past the row's length are 0 and not
+// counted — a select in the dropout block.  The spikes PUBLISHED to the peers and the saved states stay unmasked: a
+// row's padded steps are garbage in, masked out, and nothing of them reaches a valid step (time runs forward only).
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool STREAM = false, bool LEN = false>
+__global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<LEN, RecLenArgs, RecArgs> a) {
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT), "64-column workgroups: the 8-wave persistent kernels");
     static_assert(!STREAM || CW == 1, "the streaming kernels own 32 columns per workgroup");
     __shared__ __attribute__((aligned(16))) float red[2][NW][CW][RT * RED_LD4];
@@ -214,6 +223,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
     const bool has_norm = a.scale != nullptr;
     const bool drop = a.p_drop > 0.0f;
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
+    int len = T;
+    if constexpr (LEN) len = a.lengths[b];
     auto wx_ptr = [&](int t) {
         const int tt = d ? (T - 1 - t) : t;
         return a.Wx + ((size_t)b * T + tt) * H + colc;
@@ -412,6 +423,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
             for (int e = 0; e < 4; ++e) {
                 const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
                 so[e] = s[e] * k;
+                if constexpr (LEN) so[e] = t < len ? so[e] : 0.0f;
                 cnt[e] += (so[e] != 0.0f) ? 1u : 0u;
             }
             pend_s = so; pend_u = uo; pend_w = wo;
@@ -475,19 +487,32 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(RecArgs a) {
 // The kernel exists as two families with ONE body (rec_bwd_body.inc): rec_bwd_kernel gates with the reference's
 // box-car, rec_bwd_sg_kernel with one of the smooth surrogates, chosen by a wave-uniform switch on `sg` (fp32 saves
 // only: S16 is never set there).
+// ROW_LEN(b) / TAIL_ZERO(t, v): see cell_bwd_body.inc — the ragged family's row length and its select on the incoming
+// gradient (a row's recurrent term is its own dWx_{t+1} row times V^T: zero over its tail like the carries).
+#define ROW_LEN(b) T
+#define TAIL_ZERO(t, v) (v)
 template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, bool S16 = false, int CW = 1>
 __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_kernel(RecArgs a)
 #define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
 #include "rec_bwd_body.inc"
 #undef SURROGATE_GATE
-// RecArgs itself does not grow (every kernel's argument segment would): the smooth kernels take it with the surrogate
-// behind it, as one by-value argument (the kernel table's rows are KernelRef<Args>)
-struct RecSgArgs : RecArgs { SurrogateArgs sg; };
 template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool S16 = false>
 __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_sg_kernel(RecSgArgs a)
 #define SURROGATE_GATE(ds, x) smooth_gate(a.sg.id, a.sg.k, ds, x)
 #include "rec_bwd_body.inc"
 #undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
+// the ragged family (sparch_rec_cell_bwd_len): any surrogate, the box-car included, fp32 or bf16 saves
+#define ROW_LEN(b) a.lengths[b]
+#define TAIL_ZERO(t, v) ((t) < row_len ? (v) : 0.0f)
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, bool S16 = false, int CW = 1>
+__global__ __launch_bounds__(64 * NW, 1) void rec_bwd_len_kernel(RecLenArgs a)
+#define SURROGATE_GATE(ds, x) any_gate(a.sg.id, a.sg.k, ds, x)
+#include "rec_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
 
 
 // ------------------------------------------------------------------ dense recurrent cell (ANN baselines, f-4)
@@ -782,6 +807,36 @@ RecKernelOf<SG> rec_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
         });
     });
 }
+// the ragged kernels (RecLenArgs): the persistent forward with LEN, and the one backward family of every surrogate
+using RecLenKernel = KernelRef<RecLenArgs>;
+template <bool BWD>
+RecLenKernel rec_len_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
+    return rec_plan::with_kgw(kgw, [&](auto k) {
+        return rec_plan::with_bool(adapt, [&](auto ad) {
+            return rec_plan::with_bool(BWD && save16, [&](auto s16) -> RecLenKernel {
+                constexpr int K = decltype(k)::value, KB = rec_kb(K), NW = rec_nw(K);
+                constexpr bool A = decltype(ad)::value, S16 = decltype(s16)::value;
+                auto of = [](auto np, auto cwc) -> RecLenKernel {
+                    constexpr int NP = decltype(np)::value, CW = decltype(cwc)::value;
+                    if constexpr (BWD) return kernel_with_occupancy<RecLenArgs, rec_bwd_len_kernel<A, KB, NW, false, NP, S16, CW>, 64 * NW>();
+                    else return kernel_with_occupancy<RecLenArgs, rec_fwd_kernel<A, KB, NW, false, NP, CW, false, true>, 64 * NW>();
+                };
+                using rec_plan::kgw_c;
+                if (!low) return of(kgw_c<3>{}, kgw_c<1>{});
+                if constexpr (K >= 2)
+                    if (cw == 2) return of(kgw_c<1>{}, kgw_c<2>{});
+                return of(kgw_c<1>{}, kgw_c<1>{});
+            });
+        });
+    });
+}
+RecLenArgs with_lengths(const RecArgs& a, const SurrogateArgs sg, const int* lengths) {
+    RecLenArgs g;
+    static_cast<RecArgs&>(g) = a;
+    g.sg = sg;
+    g.lengths = lengths;
+    return g;
+}
 // the step variants (EXT): the recurrent product comes from the caller, one k-group class, no hand-off
 template <bool BWD, bool STREAM = false>
 RecKernel rec_step_kernel(bool adapt) {
@@ -821,8 +876,11 @@ AnnKernel ann_kernel(int act, int kgw) {
 
 // ---- one pass of the persistent kernels: size and check the workspace, clear it, plan and walk (rec_plan.h)
 // SG (backward): `sg` names a smooth surrogate and the pass runs on the rec_bwd_sg_kernel rows of the table
-template <bool BWD, bool STREAM = false, bool SG = false>
-int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st, const SurrogateArgs sg = {}) {
+// lengths (not null): the ragged pass, on the rec_len_kernel table (`sg` is then any surrogate)
+template <bool BWD, bool STREAM = false, bool SG = false, bool LEN = false>
+int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st, const SurrogateArgs sg = {},
+            const int* lengths = nullptr) {
+    static_assert(!LEN || (!STREAM && !SG), "the ragged pass has its own table");
     const bool adapt = kind == SPARCH_KIND_RADLIF;
     const bool low = sparch_operand_bf16() != 0;  // the V pack must have been made in the same mode
     const int kgw = pick_kgw(a.H);
@@ -845,11 +903,19 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     pol.cw_override = cw_env;
     const int cus = sparch_device_cus();
     const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, cus, pol, [&](unsigned grid, int cw) {
-        return co_resident(rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
+        if constexpr (LEN) return co_resident(rec_len_kernel<BWD>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
+        else return co_resident(rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
     });
     if (!q.ok) return SPARCH_EINVAL;
     // whole-sequence launches only (one agreement per launch)
     a.xcd_tab = q.whole && xcd_local_enabled() ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.chan) + hb) : nullptr;
+    if constexpr (LEN) {
+        const RecLenKernel k = rec_len_kernel<BWD>(adapt, low, kgw, q.cw, a.save16 != 0);
+        return rec_plan::walk(q, BWD, [&](int rt0, int n_rt, int t0, int t1) {
+            a.rt_base = rt0; a.n_rt_launch = n_rt; a.t_begin = t0; a.t_end = t1;
+            return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), with_lengths(a, sg, lengths), st);
+        });
+    }
     const RecKernelOf<SG> k = rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, q.cw, a.save16 != 0);
     return rec_plan::walk(q, BWD, [&](int rt0, int n_rt, int t0, int t1) {
         a.rt_base = rt0; a.n_rt_launch = n_rt; a.t_begin = t0; a.t_end = t1;
@@ -1008,15 +1074,17 @@ extern "C" size_t sparch_rec_chan_bytes(int Bp, int T, int H) {
     return ((f > b ? f : b) + xcd_tab_bytes(Bp, H) + 15) & ~(size_t)15;
 }
 
-extern "C" int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+namespace {
+// sparch_rec_cell_fwd and sparch_rec_cell_fwd_len (lengths not null, checked by the caller)
+int rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
                                    const float* scale, const float* shift, const float* alpha,
                                    const float* beta, const float* a, const float* b,
                                    const float* vpack, const float* rec0, const float* u0,
                                    const float* w0, const float* s0, float theta, float p_drop,
                                    uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
                                    int save_bf16, uint32_t* spike_count, void* chan, size_t chan_bytes,
-                                   uint32_t* status, int steps_per_launch, void* stream, int precision) {
-    SPARCH_ENTER();
+                                   uint32_t* status, int steps_per_launch, void* stream, int precision,
+                                   const int* lengths) {
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
     // bf16 saved states cannot carry the exact state from one launch of a chunked forward to the next
@@ -1030,7 +1098,39 @@ extern "C" int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, cons
     r.vpack = reinterpret_cast<const u32x4*>(vpack);
     r.u_save = (float*)u_save; r.w_save = (float*)w_save; r.save16 = save_bf16 != 0;
     r.chan = (u64*)chan; r.status = status;
+    if (lengths) return run_rec<false, false, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream, {}, lengths);
     return run_rec<false>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int sparch_rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                   const float* scale, const float* shift, const float* alpha,
+                                   const float* beta, const float* a, const float* b,
+                                   const float* vpack, const float* rec0, const float* u0,
+                                   const float* w0, const float* s0, float theta, float p_drop,
+                                   uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                                   int save_bf16, uint32_t* spike_count, void* chan, size_t chan_bytes,
+                                   uint32_t* status, int steps_per_launch, void* stream, int precision) {
+    SPARCH_ENTER();
+    return rec_cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, vpack, rec0, u0, w0, s0, theta, p_drop,
+                        seed, s_out, s16_out, u_save, w_save, save_bf16, spike_count, chan, chan_bytes, status,
+                        steps_per_launch, stream, precision, nullptr);
+}
+
+extern "C" int sparch_rec_cell_fwd_len(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                       const float* scale, const float* shift, const float* alpha,
+                                       const float* beta, const float* a, const float* b,
+                                       const float* vpack, const float* rec0, const float* u0,
+                                       const float* w0, const float* s0, float theta, float p_drop,
+                                       uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                                       int save_bf16, uint32_t* spike_count, const int* lengths, long long n_valid,
+                                       void* chan, size_t chan_bytes, uint32_t* status, int steps_per_launch,
+                                       void* stream, int precision) {
+    SPARCH_ENTER();
+    if (!ragged_ok(dirs, lengths, n_valid)) return SPARCH_EINVAL;
+    return rec_cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, vpack, rec0, u0, w0, s0, theta, p_drop,
+                        seed, s_out, s16_out, u_save, w_save, save_bf16, spike_count, chan, chan_bytes, status,
+                        steps_per_launch, stream, precision, lengths);
 }
 
 extern "C" int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
@@ -1056,7 +1156,9 @@ extern "C" int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int 
     return run_rec<false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
 
-extern "C" int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_out,
+namespace {
+// sparch_rec_cell_bwd_sg and sparch_rec_cell_bwd_len (lengths not null: n_valid is the rate gradient's sample count)
+int rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                       const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
                                       const float* alpha, const float* beta, const float* a,
                                       const float* b, const float* vpack_t, const float* u0,
@@ -1065,8 +1167,7 @@ extern "C" int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, c
                                       const float* bn_x, const float* bn_mean, const float* bn_invstd,
                                       void* chan, size_t chan_bytes, uint32_t* status,
                                       int steps_per_launch, int surrogate, float surrogate_scale, void* stream,
-                                      int precision) {
-    SPARCH_ENTER();
+                                      int precision, const int* lengths, long long n_valid) {
     if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
@@ -1081,9 +1182,48 @@ extern "C" int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, c
     r.vpack = reinterpret_cast<const u32x4*>(vpack_t);
     r.save16 = save_bf16 != 0;
     r.chan = (u64*)chan; r.status = status;
+    if (lengths) {
+        r.g_rate_scale = 1.0f / (float)n_valid;
+        return run_rec<true, false, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream,
+                                                 SurrogateArgs{surrogate, surrogate_scale}, lengths);
+    }
     if (surrogate == SPARCH_SURROGATE_BOXCAR) return run_rec<true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
     return run_rec<true, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream,
                                       SurrogateArgs{surrogate, surrogate_scale});
+}
+}  // namespace
+
+extern "C" int sparch_rec_cell_bwd_sg(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                      const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                      const float* alpha, const float* beta, const float* a,
+                                      const float* b, const float* vpack_t, const float* u0,
+                                      const float* w0, const float* s0, float theta, float p_drop,
+                                      uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                                      const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                      void* chan, size_t chan_bytes, uint32_t* status,
+                                      int steps_per_launch, int surrogate, float surrogate_scale, void* stream,
+                                      int precision) {
+    SPARCH_ENTER();
+    return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
+                        s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
+                        steps_per_launch, surrogate, surrogate_scale, stream, precision, nullptr, 0);
+}
+
+extern "C" int sparch_rec_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                       const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                       const float* alpha, const float* beta, const float* a,
+                                       const float* b, const float* vpack_t, const float* u0,
+                                       const float* w0, const float* s0, float theta, float p_drop,
+                                       uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                                       const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                       const int* lengths, long long n_valid, void* chan, size_t chan_bytes,
+                                       uint32_t* status, int steps_per_launch, int surrogate, float surrogate_scale,
+                                       void* stream, int precision) {
+    SPARCH_ENTER();
+    if (!ragged_ok(dirs, lengths, n_valid)) return SPARCH_EINVAL;
+    return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
+                        s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
+                        steps_per_launch, surrogate, surrogate_scale, stream, precision, lengths, n_valid);
 }
 extern "C" int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                    const float* g_rate, const void* u_save, const void* w_save, int save_bf16,

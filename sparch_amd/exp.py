@@ -92,6 +92,16 @@ class _SyntheticLoader:
             yield x, xlens, y
 
 
+def parse_lengths_mode(value):
+    """SPARCH_LENGTHS: unset or empty -> False (the lengths are dropped, the reference's behaviour), "mask" -> True;
+    anything else is refused."""
+    if value is None or value == "":
+        return False
+    if value == "mask":
+        return True
+    raise ValueError(f"SPARCH_LENGTHS={value!r}: the only value is 'mask' (unset: clips run to the batch's longest one)")
+
+
 class Experiment:
     """Training / testing of spiking networks on the four speech-command datasets."""
 
@@ -108,6 +118,14 @@ class Experiment:
         # here, so that a malformed value is refused before folders, data or device are touched.
         spec = os.environ.get("SPARCH_SURROGATE", "")
         self.surrogate = parse_surrogate(spec) if spec.strip() else None
+
+        # SPARCH_LENGTHS=mask: train, validation and test pass each batch's clip lengths to the network (ragged
+        # batches, SNN.forward); unset: every clip runs to the batch's longest one, as in the reference
+        self.mask_lengths = parse_lengths_mode(os.environ.get("SPARCH_LENGTHS"))
+        if self.mask_lengths and self.sync_bn:
+            raise ValueError("sparch_amd: SPARCH_LENGTHS=mask with --sync_bn is not supported")
+        if self.mask_lengths and self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
+            raise ValueError(f"sparch_amd: SPARCH_LENGTHS=mask needs a spiking model (got {self.model_type})")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -369,6 +387,14 @@ class Experiment:
                         t.record_stream(main)
             yield xd, xlens, yd
 
+    def _net(self, x, xlens):
+        """The network on one batch: with SPARCH_LENGTHS=mask the clips' lengths go with it."""
+        if not self.mask_lengths:
+            return self.net(x)
+        if not getattr(self.net, "is_snn", False):
+            raise ValueError("sparch_amd: SPARCH_LENGTHS=mask needs a spiking model")
+        return self.net(x, lengths=xlens)
+
     def _mean_over_ranks(self, value):
         if self.world == 1:
             return value
@@ -387,9 +413,9 @@ class Experiment:
         # No host round trip inside the loop: the reference's per-step `.item()` / `.cpu()`
         # (exp.py:363, 381) become device-side lists read back ONCE per epoch — the same fp32 per-batch
         # values, the same float64 means — and the kernels' status word is checked at the same point.
-        for step, (x, _, y) in enumerate(self._prefetched(self.train_loader)):
+        for step, (x, xlens, y) in enumerate(self._prefetched(self.train_loader)):
             x, y = self._to_device(x, y)
-            output, firing_rates = self.net(x)
+            output, firing_rates = self._net(x, xlens)
             loss_val = self.loss_fn(output, y)
             losses.append(loss_val.detach())
             if self.net.is_snn:
@@ -450,9 +476,9 @@ class Experiment:
         losses, accs, sizes = [], [], []
         epoch_spike_rate = 0
         step = 0
-        for step, (x, _, y) in enumerate(self._prefetched(loader)):
+        for step, (x, xlens, y) in enumerate(self._prefetched(loader)):
             x, y = self._to_device(x, y)
-            output, firing_rates = self.net(x)
+            output, firing_rates = self._net(x, xlens)
             losses.append(self.loss_fn(output, y).detach())
             pred = torch.argmax(output, dim=1)
             accs.append((y == pred).sum())

@@ -488,10 +488,13 @@ class _Norm:
     (scale, shift) consumed by the cell kernel; LayerNorm materialises the normalised tensor."""
 
     @staticmethod
-    def forward(mode, Wx_raw, colstat, weight, bias, running_mean, running_var, training, dup, nbt=None, ln_width=None):
+    def forward(mode, Wx_raw, colstat, weight, bias, running_mean, running_var, training, dup, nbt=None, ln_width=None,
+                n_valid=None):
         """nbt: BatchNorm's num_batches_tracked (int64 device tensor) — incremented by the finalize kernel itself,
         under the status-word guard, instead of by a separate host-side `+= 1` (None: the caller keeps doing that).
-        ln_width: LayerNorm's width when the layer runs zero-padded to more columns (None: all H columns)."""
+        ln_width: LayerNorm's width when the layer runs zero-padded to more columns (None: all H columns).
+        n_valid: ragged batch — BatchNorm's sample count is the number of valid rows (the padded rows of Wx_raw are
+        exactly zero and have added nothing to the column sums); None: all M rows."""
         M, H = Wx_raw.shape
         dev = Wx_raw.device
         if mode == "batchnorm":
@@ -499,7 +502,7 @@ class _Norm:
             shift = torch.empty(H, dtype=torch.float32, device=dev)
             mean = torch.empty(H, dtype=torch.float32, device=dev)
             invstd = torch.empty(H, dtype=torch.float32, device=dev)
-            n_tiles, rows = (M + 127) // 128, M
+            n_tiles, rows = (M + 127) // 128, (M if n_valid is None else n_valid)
             if training and SYNC_BN is not None and SYNC_BN["world"] > 1:
                 import torch.distributed as dist
 
@@ -526,12 +529,14 @@ class _Norm:
 
     @staticmethod
     def backward(mode, dy, Wx_raw, weight, saved, training, sums=None, planes=False, dy2=None, keep_fp32=True,
-                 ln_width=None):
+                 ln_width=None, n_valid=None):
         """dy (M,H) grad wrt the normalised projection -> (dx_raw, dweight, dbias). May overwrite dy.
         sums = (dbeta, dgamma) when the cell's backward kernel already produced BatchNorm's column sums.
         planes=True (batchnorm, H % 8 == 0): returns (dx_raw or None, dweight, dbias, dx_planes) with dx_planes the
         (3, M, H) bf16 planes of dx_raw; keep_fp32=False skips the fp32 tensor (dx_raw is None).  dy2: the second
-        direction's gradient of a bidirectional layer, added in the same pass (dy + dy2)."""
+        direction's gradient of a bidirectional layer, added in the same pass (dy + dy2).  n_valid: ragged batch —
+        BatchNorm's two means are over the valid rows (dy is zero on the padded ones, so the column sums are right as
+        they come; the apply kernels divide by M, so the sums go in scaled by M / n_valid)."""
         M, H = dy.shape
         dev = dy.device
         if mode == "batchnorm":
@@ -554,6 +559,8 @@ class _Norm:
                 cg, cb = red[0], red[1]
             elif training:
                 cg, cb = dgamma, dbeta
+                if n_valid is not None and n_valid != M:
+                    cg, cb = dgamma * (M / n_valid), dbeta * (M / n_valid)
             else:  # fixed statistics: dx = dy * gamma * invstd, i.e. the batch-coupling terms vanish
                 cg = torch.zeros(H, dtype=torch.float32, device=dev)
                 cb = cg
@@ -628,6 +635,12 @@ def _layer_input(cfg, x, gated=True):
     return _LayerInput(x2, None, None, flag_bf16_exact(x2))
 
 
+def _n_valid(cfg):
+    """The ragged batch's number of valid rows (cfg["lengths"] = (device int32 (B,), their sum)), or None."""
+    lengths = cfg.get("lengths")
+    return None if lengths is None else lengths[1]
+
+
 def _project(inp, W, Wb, nw, nb, cfg, dup, ln_width=None):
     """norm(x W^T + Wb) of a layer -> (Wx_in, scale, shift, nsaved, Wx_raw): what the cell reads (BatchNorm stays
     folded into scale / shift), what _Norm.backward needs, and the raw projection where backward needs it (else
@@ -636,7 +649,8 @@ def _project(inp, W, Wb, nw, nb, cfg, dup, ln_width=None):
     Wx_raw, colstat = inp.project(W, Wb, colstat=(norm == "batchnorm" and training))
     Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
                                                 cfg.get("running_var"), training, dup,
-                                                nbt=cfg.get("num_batches_tracked"), ln_width=ln_width)
+                                                nbt=cfg.get("num_batches_tracked"), ln_width=ln_width,
+                                                n_valid=_n_valid(cfg))
     return Wx_in, scale, shift, nsaved, Wx_raw if norm in ("batchnorm", "layernorm") else None
 
 
@@ -664,7 +678,7 @@ def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, n
         B = dy.shape[0] // dirs
         dy2 = dy[B:].view(M, H) if dirs == 2 else None  # second direction: added by the same pass
         dx_raw, dnw, dnb, dxp = _Norm.backward(norm, dy[:B].view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
-                                               planes=True, dy2=dy2, keep_fp32=need_bias)
+                                               planes=True, dy2=dy2, keep_fp32=need_bias, n_valid=_n_valid(cfg))
         nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(H, K, M, _prec())
         ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=W.device)
         dW = torch.empty(H, K, dtype=torch.float32, device=W.device)
@@ -678,7 +692,7 @@ def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, n
             halves, dy = dy, torch.empty(dy.shape[0] // 2, dy.shape[1], H, dtype=torch.float32, device=W.device)
             check(lib.sparch_add_halves(M * H, ptr(halves), ptr(dy), _stream()), "sparch_add_halves")
         dx_raw, dnw, dnb = _Norm.backward(norm, dy.view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
-                                          ln_width=ln_width)
+                                          ln_width=ln_width, n_valid=_n_valid(cfg))
         dW = inp.weight_grad(dx_raw)
     dWb = _colsum(dx_raw) if need_bias else None
     if raw_dx:
@@ -742,8 +756,20 @@ def surrogate_args(surrogate):
     return SURROGATES[name], float(scale)
 
 
+def _check_ragged(lengths, dirs, recurrent, H):
+    """What the `_len` kernels do not take."""
+    if lengths is None:
+        return
+    if dirs != 1:
+        raise ValueError("sparch_amd: lengths with bidirectional=True is not supported (the reverse direction would "
+                         "have to flip inside each clip's own length)")
+    if recurrent and rec_step_path(H):
+        raise ValueError(f"sparch_amd: lengths with a recurrent hidden size above 1024 (got {H}) is not supported "
+                         "(the per-step recurrent path takes no lengths)")
+
+
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
-                 want_s_out=True, want_saves=True, surrogate=None):
+                 want_s_out=True, want_saves=True, surrogate=None, lengths=None):
     """Run one spiking cell over the whole sequence on the device.
 
     Wx (B,T,H) raw projection (+ optional per-column scale/shift); u0/w0/s0 (B*dirs,H).
@@ -754,12 +780,16 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     14 bytes a recurrent forward step stores per element).  want_saves=False (LIF / adLIF, nothing will be
     differentiated — validation and test forwards, exp.py:405-518): u / w are not saved either (8 of an adLIF step's
     14 bytes); `saved` is then (None, None).  surrogate: with a smooth form the saves stay fp32 whatever
-    SPARCH_SAVE_DTYPE says — a bf16 save keeps the box-car's three decisions, not the u a smooth gate reads."""
+    SPARCH_SAVE_DTYPE says — a bf16 save keeps the box-car's three decisions, not the u a smooth gate reads.
+    lengths: None, or (device int32 (B,), their sum) of a ragged batch — the `_len` entry points then zero the output
+    spikes of every row's padded steps and leave them out of `count`."""
     _, T, H = Wx.shape
     Bp = B * dirs
     dev = Wx.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    _check_ragged(lengths, dirs, recurrent, H)
+    len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
     # the same spikes as a bf16 0/1 plane for the GEMMs of the next layer (rows must stay 16-byte aligned)
     s16 = torch.empty(B, T, H * dirs, dtype=torch.bfloat16, device=dev)
     s_out = torch.empty(B, T, H * dirs, dtype=torch.float32, device=dev) if want_s_out else None
@@ -776,10 +806,11 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     count = torch.zeros(H * dirs, dtype=torch.int32, device=dev)
     if not recurrent:
         tok = timer.start(f"cell_fwd[{kind}]")
-        check(lib.sparch_cell_fwd(k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]),
+        entry = "sparch_cell_fwd" if lengths is None else "sparch_cell_fwd_len"
+        check(getattr(lib, entry)(k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]),
                                   ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0), ptr(w0),
                                   ptr(s0), theta, p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save),
-                                  int(save16), ptr(count), _stream()), "sparch_cell_fwd")
+                                  int(save16), ptr(count), *len_args, _stream()), entry)
         timer.stop(tok)
     else:
         if H % 4 != 0:
@@ -792,7 +823,7 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
             s_p, count_p, saved_p, s16_p = cell_forward(kind, padh(Wx), padh(scale), padh(shift), pp, padh(u0), padh(w0),
                                                         padh(s0), B=B, dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                         steps_per_launch=steps_per_launch, want_s_out=want_s_out,
-                                                        surrogate=surrogate)
+                                                        surrogate=surrogate, lengths=lengths)
             cut = lambda t_: None if t_ is None else t_.view(B, T, dirs, H4)[..., :H].reshape(B, T, dirs * H).contiguous()  # noqa: E731
             return (cut(s_p), count_p.view(dirs, H4)[:, :H].reshape(-1).contiguous(), saved_p, cut(s16_p))
         V = p["V"]
@@ -823,27 +854,32 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
         # t = 0 drive: s0 is uniform noise, not binary (snns.py:559/702): a (B', H, H) dense product, split-K so
         # that its 16 output tiles become a full grid (38 -> ~15 us at B' = 256, H = 1024)
         rec0 = _gemm_small(s0, vmask, nn=True)
-        _persistent(f"rec_cell_fwd[{kind}]", "sparch_rec_cell_fwd",
+        _persistent(f"rec_cell_fwd[{kind}]", "sparch_rec_cell_fwd" if lengths is None else "sparch_rec_cell_fwd_len",
                     (k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]), ptr(p.get("beta")),
                      ptr(p.get("a")), ptr(p.get("b")), ptr(vpack), ptr(rec0), ptr(u0), ptr(w0), ptr(s0), theta, p_drop,
-                     seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count)),
+                     seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count), *len_args),
                     lib.sparch_rec_chan_bytes(Bp, T, H), dev, L, _prec())
         return s_out, count, (u_save, w_save, vpack_t), s16
     return s_out, count, (u_save, w_save), s16
 
 
 def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, theta, p_drop, seed,
-                  steps_per_launch=None, bn=None, surrogate=None):
+                  steps_per_launch=None, bn=None, surrogate=None, lengths=None):
     """Reverse-time pass.  Returns dWx (B*dirs,T,H) [virtual rows, original time index],
     param grads dict (alpha[,beta,a,b][,V]) — plus, with bn = (Wx_raw (B,T,H), mean, invstd), the entry
     "bn_sums" = (dbeta, dgamma): BatchNorm backward's column sums, accumulated by the same kernel.
     surrogate: None or ("name", scale).  None / "boxcar" issue the calls they always did; a smooth form issues the
-    `_sg` entry points with (id, scale) in front of the stream (timer labels unchanged)."""
+    `_sg` entry points with (id, scale) in front of the stream (timer labels unchanged).
+    lengths: as in cell_forward — the `_len` entry points (one per family, any surrogate) take the incoming gradient of
+    a row's padded steps as zero, whatever g_out holds there; dWx is exactly 0 on them."""
     sg = surrogate_args(surrogate)
     Bp = B * dirs
     dev = g_out.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    _check_ragged(lengths, dirs, recurrent, H)
+    len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
+    sg_len = sg if sg is not None else (SURROGATES["boxcar"], 0.0)
     u_save, w_save = saved[0], saved[1]
     if recurrent and u_save.shape[-1] != H:  # forward ran zero-padded to a multiple of 4 columns (see cell_forward)
         H4 = u_save.shape[-1]
@@ -853,7 +889,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         gr_p = None if g_rate is None else padh(g_rate.reshape(dirs, H)).reshape(dirs * H4)
         dWx_p, gp = cell_backward(kind, g_p, gr_p, pp, padh(u0), padh(w0), padh(s0), saved, B=B, dirs=dirs, T=T, H=H4,
                                   theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
-                                  surrogate=surrogate)
+                                  surrogate=surrogate, lengths=lengths)
         grads = {k_: (v[:H, :H].contiguous() if k_ == "V" else v[:H].contiguous()) for k_, v in gp.items()}
         return dWx_p[..., :H].contiguous(), grads
     vpack_fwd_made = saved[2] if len(saved) > 2 else None  # backward fragments of V packed by cell_forward
@@ -869,7 +905,9 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                 ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
                 ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
                 ptr(bn_invstd))
-        if sg is None:
+        if lengths is not None:
+            check(lib.sparch_cell_bwd_len(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_len")
+        elif sg is None:
             check(lib.sparch_cell_bwd(*lead, _stream()), "sparch_cell_bwd")
         else:
             check(lib.sparch_cell_bwd_sg(*lead, *sg, _stream()), "sparch_cell_bwd_sg")
@@ -899,14 +937,16 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
             timer.stop(tok)
         else:
             vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
-            _persistent(f"rec_cell_bwd[{kind}]", "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg",
+            entry = ("sparch_rec_cell_bwd_len" if lengths is not None
+                     else "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg")
+            _persistent(f"rec_cell_bwd[{kind}]", entry,
                         (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
                          ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack_t), ptr(u0),
                          ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws), ptr(bn_x), ptr(bn_mean),
-                         ptr(bn_invstd)),
+                         ptr(bn_invstd), *len_args),
                         lib.sparch_rec_chan_bytes(Bp, T, H), dev,
                         steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec(),
-                        sg=sg)
+                        sg=sg_len if lengths is not None else sg)
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
@@ -955,11 +995,12 @@ class SpikingLayerFn(torch.autograd.Function):
                                                 dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                 want_s_out=cfg.get("fp32_out", True),
                                                 want_saves=any(ctx.needs_input_grad),
-                                                surrogate=cfg.get("surrogate"))
+                                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"))
         if s_out is None:
             s_out = spike_placeholder(B, T, H * dirs, x.device)
         inv_keep = 1.0 / (1.0 - p_drop)
-        rate = count * (inv_keep / float(B * T))  # snns.py:174 on post-dropout spikes (int32 * float -> fp32, one kernel)
+        n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]  # ragged: the mean is over valid steps
+        rate = count * (inv_keep / float(n_steps))  # snns.py:174 on post-dropout spikes (int32 * float -> fp32, one kernel)
         ctx.cfg, ctx.inp = cfg, inp
         ctx.shape = (B, T, K, H)
         ctx.nsaved = nsaved
@@ -987,7 +1028,7 @@ class SpikingLayerFn(torch.autograd.Function):
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
                                 theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn,
-                                surrogate=cfg.get("surrogate"))
+                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"))
         ctx.cell_saved = None
         dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
@@ -1013,8 +1054,14 @@ class ReadoutLayerFn(torch.autograd.Function):
         Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1)  # snns.py:796, 799-801
         out = torch.empty(B, C, dtype=torch.float32, device=x.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
-        check(lib.sparch_readout_fwd(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
-                                     ptr(u_save), _stream()), "sparch_readout_fwd")
+        lengths = cfg.get("lengths")
+        if lengths is None:
+            check(lib.sparch_readout_fwd(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
+                                         ptr(u_save), _stream()), "sparch_readout_fwd")
+        else:  # ragged: each row's truncated sum over its own steps
+            check(lib.sparch_readout_fwd_len(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
+                                             ptr(u_save), ptr(lengths[0]), int(lengths[1]), _stream()),
+                  "sparch_readout_fwd_len")
         ctx.cfg, ctx.inp = cfg, inp
         ctx.shape = (B, T, K, C)
         ctx.nsaved = nsaved
@@ -1033,10 +1080,13 @@ class ReadoutLayerFn(torch.autograd.Function):
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         fuse = norm == "batchnorm"
         ws = torch.empty(3 if fuse else 1, B, C, dtype=torch.float32, device=dev)
-        check(lib.sparch_readout_bwd(B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None,
-                                     ptr(ctx.nsaved[0]) if fuse else None, ptr(ctx.nsaved[1]) if fuse else None,
-                                     ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws), _stream()),
-              "sparch_readout_bwd")
+        lead = (B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None, ptr(ctx.nsaved[0]) if fuse else None,
+                ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
+        lengths = cfg.get("lengths")
+        if lengths is None:
+            check(lib.sparch_readout_bwd(*lead, _stream()), "sparch_readout_bwd")
+        else:
+            check(lib.sparch_readout_bwd_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()), "sparch_readout_bwd_len")
         if fuse:  # dalpha and BatchNorm's two column sums: one launch
             dalpha, s1, s2 = _finish_param_grads(ws, B, C, [alpha, None, None], [ALPHA_LIM, (0.0, 0.0), (0.0, 0.0)])
             sums = (s1, s2)

@@ -483,7 +483,7 @@ class _SpikingLayer(nn.Module):
         return p
 
     # ------------------------------------------------------------------ forward
-    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True):
+    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None):
         """Returns (spikes (B,T,H*(1+bidir)), firing_rate (H*(1+bidir),)).  Equivalent to the
         reference forward (e.g. snns.py:663-694) followed by `.mean(dim=(0,1))` (174).
         states: (u0, w0, s0) drawn ahead of time by SNN.forward (same generator, same order);
@@ -491,7 +491,11 @@ class _SpikingLayer(nn.Module):
         projection GEMM has been enqueued (the upload runs under it);
         fp32_out=False: the caller feeds the result to another layer of this module only — the returned
         tensor is then a placeholder of the right shape whose VALUES ARE NOT WRITTEN (the spikes travel as the
-        bf16 plane in its tag); SNN.forward uses it between its own layers."""
+        bf16 plane in its tag); SNN.forward uses it between its own layers.
+        lengths: None, or what prepare_lengths() returned for this batch — the layer's output is then exactly 0 on
+        every row's padded steps and the firing rate is the mean over valid steps (SNN.forward has the contract)."""
+        if lengths is not None:
+            _check_ragged_layer(self, lengths)
         Fn._require_device(x, "input")
         dirs = 2 if self.bidirectional else 1
         rows = x.shape[0] * dirs
@@ -523,6 +527,8 @@ class _SpikingLayer(nn.Module):
             # the backward's surrogate: None = the reference's box-car, else ("name", scale) — fp32 saves then
             "surrogate": self._surrogate(),
         }
+        if lengths is not None:  # (absent without lengths: the calls and their arguments are then what they always were)
+            cfg["lengths"] = lengths
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         s, rate, s16 = Fn.SpikingLayerFn.apply(
@@ -602,7 +608,10 @@ class ReadoutLayer(nn.Module):
             self.norm = norm
         self.drop = nn.Dropout(p=dropout)
 
-    def forward(self, x, u0=None):
+    def forward(self, x, u0=None, lengths=None):
+        """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b]."""
+        if lengths is not None:
+            _check_ragged_layer(self, lengths)
         Fn._require_device(x, "input")
         if u0 is None:
             u0 = _rand_to(x.shape[0], self.hidden_size, x.device)  # snns.py:812
@@ -617,6 +626,8 @@ class ReadoutLayer(nn.Module):
             "in_spike16": in_s16,  # the same spikes as a bf16 plane
             "num_batches_tracked": self.norm.num_batches_tracked if (is_bn and self.training) else None,
         }
+        if lengths is not None:
+            cfg["lengths"] = lengths
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         return Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
@@ -625,6 +636,40 @@ class ReadoutLayer(nn.Module):
         Fn._require_device(Wx, "Wx")
         u0 = _rand_to(Wx.shape[0], Wx.shape[2], Wx.device)
         return Fn.ReadoutCellFn.apply(Wx, self.alpha, u0)
+
+
+def prepare_lengths(lengths, batch, T, device):
+    """lengths (B,) integers on the host or the device, 1 <= lengths[b] <= T  ->  (int32 tensor on `device`, their sum):
+    what the layers take as `lengths`.  Made once per forward: one upload (or one read-back of min, max and sum for
+    lengths that are already on the device)."""
+    lengths = torch.as_tensor(lengths)
+    if lengths.ndim != 1 or lengths.shape[0] != batch or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+        raise ValueError(f"lengths: expected {batch} integers, one per batch row (got {tuple(lengths.shape)}, {lengths.dtype})")
+    if lengths.device.type == "cpu":
+        lo, hi, n_valid = int(lengths.min()), int(lengths.max()), int(lengths.sum())
+    else:
+        lo, hi, n_valid = torch.stack([lengths.min(), lengths.max(), lengths.sum()]).tolist()
+    if lo < 1 or hi > T:
+        raise ValueError(f"lengths: every entry must be in [1, {T}] (got min {lo}, max {hi})")
+    lengths = lengths.to(torch.int32).contiguous()
+    if lengths.device.type == "cpu" and torch.device(device).type != "cpu":
+        # pinned and non-blocking: a pageable upload makes the host wait for everything queued on the device, once per
+        # forward (measured: 0.8 ms of a 6.4 ms step at BASELINE configs[2])
+        lengths = lengths.pin_memory().to(device, non_blocking=True)
+    return lengths.to(device), int(n_valid)
+
+
+def _check_ragged_layer(layer, lengths=None):
+    """What a layer refuses with lengths; lengths: also checked to be prepare_lengths()'s."""
+    if lengths is not None and not (isinstance(lengths, tuple) and len(lengths) == 2 and torch.is_tensor(lengths[0])
+                                    and lengths[0].dtype == torch.int32):
+        raise ValueError("lengths: pass what snns.prepare_lengths() returns (SNN.forward does so itself)")
+    Fn._check_ragged(True, 2 if getattr(layer, "bidirectional", False) else 1, hasattr(layer, "V"), layer.hidden_size)
+    if layer.normalization == "batchnorm" and layer.normalize and layer.use_bias:
+        raise ValueError("sparch_amd: lengths with BatchNorm and use_bias=True is not supported (the bias makes the "
+                         "padded rows non-zero, and BatchNorm removes the bias anyway)")
+    if Fn.SYNC_BN is not None and Fn.SYNC_BN["world"] > 1:
+        raise ValueError("sparch_amd: lengths with --sync_bn is not supported")
 
 
 _LAYER_CLASSES = {"LIF": LIFLayer, "adLIF": adLIFLayer, "RLIF": RLIFLayer, "RadLIF": RadLIFLayer}
@@ -640,9 +685,16 @@ def _global_forward_hooks():
 class SNN(nn.Module):
     """Multi-layer spiking network (reference SNN, snns.py:39-176).
 
-    forward(x: (batch, time, feat) or 4-D (batch, time, feat, channel)) ->
+    forward(x: (batch, time, feat) or 4-D (batch, time, feat, channel), lengths=None) ->
         (out, firing_rates): out is (batch, classes) with a readout layer, else
-        (batch, time, feats); firing_rates has one entry per hidden neuron (all layers)."""
+        (batch, time, feats); firing_rates has one entry per hidden neuron (all layers).
+
+    lengths (ragged batches): integers (batch,), on the host or the device, 1 <= lengths[b] <=
+    time, for an x that is ZERO at every row's steps t >= lengths[b] (what pad_sequence gives).  Row b of every output
+    is then what the network gives for x[b:b+1, :lengths[b]] run on its own with the same initial-state rows (in train
+    mode: with the same normalisation statistics, taken over the valid steps): hidden spikes are 0 on the padding, the
+    readout sums over the row's own steps, firing rates are means over valid steps.  None: every row runs to `time`,
+    as the reference does."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
@@ -753,12 +805,22 @@ class SNN(nn.Module):
                     fill(w0)
                 fill(s0)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
         if self.reshape:
             if x.ndim == 4:
                 x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
             else:
                 raise NotImplementedError
+        if lengths is not None:  # (the refusals come before anything else, the device check included)
+            if getattr(self, "_static_states", None) is not None:
+                raise ValueError("sparch_amd: lengths inside a captured step (GraphedTrainStep) is not supported: the "
+                                 "lengths and their sum change with every batch")
+            for layer in self.snn:  # every refusal before the first kernel
+                _check_ragged_layer(layer)
+            lengths = prepare_lengths(lengths, x.shape[0], x.shape[1], x.device)  # on the device once per forward
+            if x.requires_grad:  # the input's gradient is 0 on the padding (x is 0 there: the values do not change)
+                steps = torch.arange(x.shape[1], device=x.device)
+                x = x * (steps[None, :] < lengths[0][:, None]).unsqueeze(-1).to(x.dtype)
         Fn._require_device(x, "input")
         # All initial states of this forward are drawn NOW, in the reference's order (layer by layer u, [w], s,
         # then the readout's u: snns.py:286-287 ... 812) from the same CPU generator, so the stream is the one
@@ -775,13 +837,13 @@ class SNN(nn.Module):
             if self.use_readout_layer and i == last:
                 if wait is not None:
                     wait()
-                x = layer(x, u0=states[i])
+                x = layer(x, u0=states[i]) if lengths is None else layer(x, u0=states[i], lengths=lengths)
             else:
                 # between two layers of ours the spikes travel as a bf16 plane: no fp32 copy (unless somebody
                 # else may look at the layer's output: forward hooks, the network's own output)
                 inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
                 x, r = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
-                                               fp32_out=not inner)
+                                               fp32_out=not inner, **({} if lengths is None else {"lengths": lengths}))
                 if wait is not None:
                     wait()  # (no-op once the first layer's call has waited)
                 rates.append(r)

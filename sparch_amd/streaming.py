@@ -454,8 +454,10 @@ class StreamingSNN(_Stream):
             for i, t in enumerate(taps):
                 self._spike_tap(i, t)
 
-    def step(self, x_chunk):
+    def step(self, x_chunk, lengths=None):
         """x_chunk (B,Tc,C) float32, or uint8 spike counts, on the device; any Tc >= 1."""
+        if lengths is not None:  # (a stream ends when its caller stops feeding it: DESIGN.md section 7)
+            raise ValueError("sparch_amd: lengths are not supported by the streaming classes (StreamingSNN)")
         self._ensure()
         x = self._chunk(x_chunk)
         Tc = x.shape[1]
