@@ -951,6 +951,46 @@ int sparch_adam_step(int n_tensors, float* const* params, const float* const* gr
 int sparch_adam_scalars(double* t_dev, const double* lr_dev, double beta1, double beta2, float* scalars_dev,
                         void* stream);
 
+/* ---- gradient clipping by global norm, on the device (gradclip.hip; DESIGN.md section 6, "Gradient clipping") ----
+ * sparch_grad_norm: the 2-norm over a whole gradient list (`grads`: a HOST array of n_tensors DEVICE pointers, `numel`
+ * a host array, as sparch_adam_step; empty tensors are passed over and may be NULL), accumulated in double in a FIXED
+ * order — no atomics: the same table gives the same bits on every call and on every replica, whatever the alignment of
+ * the tensors (4-byte aligned views are fine) — and the clip state made from it, 8 words of 32 bits the caller owns and
+ * has zeroed once:
+ *   clip[0] float  this step's global norm, (float)sqrt(sum of squares in double)
+ *   clip[1] float  this step's coefficient fminf(max_norm / (norm + 1e-6f), 1.0f): torch.nn.utils.clip_grad_norm_'s
+ *                  formula and epsilon in fp32; max_norm = +inf gives 1 (measure and guard only)
+ *   clip[2] u32    1 if this step's norm is not finite (a NaN or inf gradient, or a norm above fp32's range), else 0
+ *   clip[3] u32    steps skipped for a non-finite norm since the state was zeroed (+1 per call, not per launch)
+ *   clip[4] u32    finite steps counted          clip[5] u32  of those, steps with coefficient < 1
+ *   clip[6] float  largest finite norm seen      clip[7] u32  0, reserved
+ * tensor_norms (nullable): n_tensors floats, each tensor's own norm (0 for an empty one) — which matrix blew up.
+ * skip_if_nonzero (nullable): the recurrent kernels' status word; while it is raised (the step's gradients are garbage)
+ * words 3-6 stay as they are and the call writes coefficient 1, flag 0: the optimizer skips on the word itself.
+ * ws: sparch_grad_norm_ws_bytes(n_tensors, numel) bytes, 8-byte aligned (one double per 4096 elements of every tensor,
+ * plus 24 bytes per tensor); fewer: SPARCH_EWORKSPACE.  SPARCH_EINVAL, before any device work and in front of the
+ * workspace check: n_tensors < 0, a NULL table with n_tensors > 0, a negative numel, a NULL pointer behind a non-empty
+ * tensor, max_norm NaN or <= 0, clip NULL.  n_tensors == 0 is a valid call: norm 0, coefficient 1. */
+size_t sparch_grad_norm_ws_bytes(int n_tensors, const int64_t* numel);
+int sparch_grad_norm(int n_tensors, const float* const* grads, const int64_t* numel, float max_norm, void* ws,
+                     size_t ws_bytes, uint32_t* clip, float* tensor_norms, const uint32_t* skip_if_nonzero,
+                     void* stream);
+
+/* sparch_adam_step on gradients scaled by clip[1] — g * coefficient, one fp32 multiply, then sparch_adam_step's
+ * arithmetic bit for bit; the gradients are read, never rewritten.  Checked in this order: skip_if_nonzero (the no-op
+ * and the once-per-call count of sparch_adam_step), then clip[2]: when set, parameters and moments stay untouched (the
+ * skipped step was counted in clip[3] by sparch_grad_norm).  clip NULL, or any fault of the table: SPARCH_EINVAL before
+ * the first launch. */
+int sparch_adam_step_clip(int n_tensors, float* const* params, const float* const* grads,
+                          float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                          float step_size, float beta1, float beta2, float bc2_sqrt, float eps,
+                          float weight_decay, const float* scalars_dev, uint32_t* skip_if_nonzero,
+                          const uint32_t* clip, void* stream);
+
+/* g *= clip[1] in place, for callers that keep another optimizer.  When clip[2] is set the gradients are left as they
+ * are (torch.nn.utils.clip_grad_norm_ would write NaNs into all of them): check clip[2], or use the fused step. */
+int sparch_scale_grads(int n_tensors, float* const* grads, const int64_t* numel, const uint32_t* clip, void* stream);
+
 /* ---- G1/G2, round 3: the gradient of a BatchNorm'd projection as bf16 planes, made ONCE.
  * sparch_bn_bwd_apply_planes = sparch_bn_bwd_apply (dx = gamma*invstd*(dy - dbeta/M - xhat*dgamma/M)) writing dx as
  * its three exact bf16 planes (3 x M x H uint16, truncation split: dx = t1 + t2 + t3 — the split the dense GEMMs

@@ -177,6 +177,11 @@ PROTOTYPES = {
     "sparch_ce_loss": (c_int, [c_int, c_int, P, P, P, P, P]),
     "sparch_adam_scalars": (c_int, [P, P, c_double, c_double, P, P]),
     "sparch_adam_step": (c_int, [c_int, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, P, P, P]),
+    "sparch_grad_norm_ws_bytes": (c_size_t, [c_int, P]),
+    "sparch_grad_norm": (c_int, [c_int, P, P, c_float, P, c_size_t, P, P, P, P]),
+    "sparch_adam_step_clip": (c_int, [c_int, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, P, P,
+                                      P, P]),
+    "sparch_scale_grads": (c_int, [c_int, P, P, P, P]),
 }
 
 

@@ -102,6 +102,20 @@ def parse_lengths_mode(value):
     raise ValueError(f"SPARCH_LENGTHS={value!r}: the only value is 'mask' (unset: clips run to the batch's longest one)")
 
 
+def parse_clip_grad(value):
+    """SPARCH_CLIP_GRAD: unset or empty -> None (no clipping, no new call); a positive number or "inf" (measure the
+    gradient norm and skip non-finite steps without scaling) -> that float; anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    try:
+        c = float(value)
+    except ValueError:
+        c = float("nan")
+    if not c > 0:
+        raise ValueError(f"SPARCH_CLIP_GRAD={value!r}: a positive number or 'inf' (the cap on the global gradient norm)")
+    return c
+
+
 class Experiment:
     """Training / testing of spiking networks on the four speech-command datasets."""
 
@@ -118,6 +132,9 @@ class Experiment:
         # here, so that a malformed value is refused before folders, data or device are touched.
         spec = os.environ.get("SPARCH_SURROGATE", "")
         self.surrogate = parse_surrogate(spec) if spec.strip() else None
+        # SPARCH_CLIP_GRAD=<positive float>|inf: clip the gradients by their global norm inside the optimizer step
+        # (optim.Adam(max_grad_norm=...)); refused here for the same reason
+        self.clip_grad = parse_clip_grad(os.environ.get("SPARCH_CLIP_GRAD"))
 
         # SPARCH_LENGTHS=mask: train, validation and test pass each batch's clip lengths to the network (ragged
         # batches, SNN.forward); unset: every clip runs to the batch's longest one, as in the reference
@@ -156,7 +173,12 @@ class Experiment:
         self.init_dataset()
         self.init_model()
 
-        self.opt = optim.Adam(self.net.parameters(), self.lr)  # exp.py:89, one launch per step (f-2)
+        if self.clip_grad is None:
+            self.opt = optim.Adam(self.net.parameters(), self.lr)  # exp.py:89, one launch per step (f-2)
+        else:
+            self.opt = optim.Adam(self.net.parameters(), self.lr, max_grad_norm=self.clip_grad)
+            logging.info(f"Gradients are clipped to a global norm of {self.clip_grad} inside the optimizer step "
+                         "(SPARCH_CLIP_GRAD); a step whose norm is not finite is skipped")
         self.scheduler = ReduceLROnPlateau(optimizer=self.opt, mode="max", factor=self.scheduler_factor,
                                            patience=self.scheduler_patience, min_lr=1e-6)
         self.loss_fn = Fn.CrossEntropyLoss()  # exp.py:100 (one launch for the loss and its gradient)
@@ -441,6 +463,11 @@ class Experiment:
         logging.info(f"Epoch {e}: lr={self.opt.param_groups[-1]['lr']}")
         logging.info(f"Epoch {e}: train loss={self._mean_over_ranks(np.mean(losses))}")
         logging.info(f"Epoch {e}: train acc={self._mean_over_ranks(np.mean(accs))}")
+        if self.clip_grad is not None:
+            s = self.opt.clip_stats()
+            self.opt.reset_clip_stats()  # (per-epoch figures)
+            logging.info(f"Epoch {e}: grad norm max={s['max_norm']}, clipped {s['clipped']} of {s['steps']} steps, "
+                         f"skipped {s['skipped']} non-finite")
         if self.net.is_snn:
             epoch_spike_rate /= step  # sic: the reference divides by the last batch index (exp.py:398)
             logging.info(f"Epoch {e}: train mean act rate={epoch_spike_rate}")
@@ -452,7 +479,12 @@ class Experiment:
         """Read the recurrent kernels' status word.  After an in-kernel timeout (the persistent grid could
         not become co-resident: GPU shared or partitioned) the steps since the last check were no-ops on the
         device (the optimizer and the BatchNorm statistics skip themselves while the word is raised); this
-        process now continues with one launch per time step — new launches, same process."""
+        process now continues with one launch per time step — new launches, same process.  With SPARCH_CLIP_GRAD the
+        same read takes back the steps skipped for a non-finite gradient norm (every rank skipped the same ones)."""
+        if self.clip_grad is not None:
+            n = self.opt.sync_skipped()
+            if n:
+                logging.warning(f"Epoch {e}, step {step}: {n} step(s) had a NaN or inf gradient norm and were skipped")
         if self._timeout_on_any_rank():
             logging.warning(f"Epoch {e}, step {step}: {Fn._TIMEOUT_TEXT}  [{Fn.describe_timeout()}]  Steps since the "
                             "timeout were skipped on every rank; continuing with one kernel launch per time step "
