@@ -369,6 +369,38 @@ int sparch_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_
                         float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
                         const float* bn_mean, const float* bn_invstd, const int* lengths, long long n_valid,
                         int surrogate, float surrogate_scale, void* stream);
+/* Packed ragged batches ("Packed ragged batches"): the `_pk` forms skip the padded steps instead
+ * of masking them.  The batch's B sequences are sorted by length, descending; sequence j has lengths[j] steps and owns
+ * rows [offsets[j], offsets[j] + lengths[j]) of every per-step tensor, which is (N, .) with N = n_valid = offsets[B]
+ * instead of (B, T, .): Wx, s_out, s16_out, u_save, w_save, g_out, dWx, bn_x.  lengths (B,) and offsets (B + 1,) are
+ * int32 on the device; T is the longest length; the per-sequence tensors (u0, w0, s0, dparam_ws, out) keep B rows, in
+ * the sorted order.  A sequence runs exactly its own steps: there is no padded step, no saved state behind a
+ * sequence's end, and the dropout mask's element index is the position in the packed tensor.  The rate gradient is
+ * scaled by 1 / n_valid.  SPARCH_EINVAL, before any device work, for dirs != 1, lengths == NULL, offsets == NULL and
+ * n_valid < 1; everything else as the entry point without lengths.                                              */
+int sparch_cell_fwd_pk(int kind, int B, int dirs, int T, int H, const float* Wx,
+                       const float* scale, const float* shift, const float* alpha,
+                       const float* beta, const float* a, const float* b, const float* u0,
+                       const float* w0, const float* s0, float theta, float p_drop,
+                       uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                       int save_bf16, uint32_t* spike_count, const int* lengths, const int* offsets,
+                       long long n_valid, void* stream);
+int sparch_cell_bwd_pk(int kind, int B, int dirs, int T, int H, const float* g_out,
+                       const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                       const float* alpha, const float* beta, const float* a, const float* b,
+                       const float* u0, const float* w0, const float* s0, float theta,
+                       float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                       const float* bn_mean, const float* bn_invstd, const int* lengths, const int* offsets,
+                       long long n_valid, int surrogate, float surrogate_scale, void* stream);
+/* The row gather / scatter between a padded (B,T,C) tensor and the packed (N,C) one, for elements of elem_size = 1, 2
+ * or 4 bytes (moved as raw bytes).  order (B,) int32: sequence j is batch row order[j].  sparch_pack_rows copies step
+ * t < lengths[j] of batch row order[j] to packed row offsets[j] + t; sparch_unpack_rows copies it back and writes
+ * zeros to every step t >= lengths[j], so every element of dst (B,T,C) is written.  SPARCH_EINVAL for a NULL pointer,
+ * another element size, n_valid < 1 or n_valid > B T.                                                            */
+int sparch_pack_rows(int B, int T, int C, int elem_size, const void* src, void* dst, const int* order,
+                     const int* lengths, const int* offsets, long long n_valid, void* stream);
+int sparch_unpack_rows(int B, int T, int C, int elem_size, const void* src, void* dst, const int* order,
+                       const int* lengths, const int* offsets, long long n_valid, void* stream);
 
 /* Recurrent kinds (RLIF, RadLIF).  V (H,H) = V.weight; the diagonal is masked inside
  * (snns.py:566/712).  The recurrent product s_{t-1}*V runs on MFMA with the V slice of
@@ -456,6 +488,30 @@ int sparch_rec_cell_fwd_len(int kind, int B, int dirs, int T, int H, const float
                             void* w_save, int save_bf16, uint32_t* spike_count, const int* lengths,
                             long long n_valid, void* chan, size_t chan_bytes, uint32_t* status,
                             int steps_per_launch, void* stream, int precision);
+/* The packed forms (see sparch_cell_fwd_pk): tensors per step are (N, .), sequence j at rows offsets[j] ...; T is the
+ * longest length and sizes chan (sparch_rec_chan_bytes(B, T, H)).  A 32-row tile runs to the length of its first row, its
+ * longest; a shorter row's loads are clamped into its own rows and its stores end at its own length.  Whole-sequence
+ * launches only: SPARCH_EINVAL for steps_per_launch < T (and where the grid cannot be co-resident), besides what the
+ * `_len` forms refuse.  s_prev16 (backward) is (N, H) like dWx.                                                  */
+int sparch_rec_cell_fwd_pk(int kind, int B, int dirs, int T, int H, const float* Wx,
+                           const float* scale, const float* shift, const float* alpha,
+                           const float* beta, const float* a, const float* b,
+                           const float* vpack, const float* rec0, const float* u0,
+                           const float* w0, const float* s0, float theta, float p_drop,
+                           uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                           int save_bf16, uint32_t* spike_count, const int* lengths, const int* offsets,
+                           long long n_valid, void* chan, size_t chan_bytes, uint32_t* status,
+                           int steps_per_launch, void* stream, int precision);
+int sparch_rec_cell_bwd_pk(int kind, int B, int dirs, int T, int H, const float* g_out,
+                           const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                           const float* alpha, const float* beta, const float* a,
+                           const float* b, const float* vpack_t, const float* u0,
+                           const float* w0, const float* s0, float theta, float p_drop,
+                           uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                           const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                           const int* lengths, const int* offsets, long long n_valid, void* chan,
+                           size_t chan_bytes, uint32_t* status, int steps_per_launch, int surrogate,
+                           float surrogate_scale, void* stream, int precision);
 int sparch_rec_cell_bwd_len(int kind, int B, int dirs, int T, int H, const float* g_out,
                             const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
                             const float* alpha, const float* beta, const float* a,
@@ -600,6 +656,15 @@ int sparch_readout_bwd_len(int B, int T, int C, const float* g_out, const float*
                            const float* bn_mean, const float* bn_invstd, const float* u_save,
                            const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
                            const int* lengths, long long n_valid, void* stream);
+/* The packed forms (see sparch_cell_fwd_pk): Wx, u_save, dWx and bn_x are (N,C), row b's steps at rows offsets[b] ...;
+ * out, u0 and dalpha_ws keep B rows.  Nothing is written outside a row's own packed range.                       */
+int sparch_readout_fwd_pk(int B, int T, int C, const float* Wx, const float* scale,
+                          const float* shift, const float* alpha, const float* u0, float* out,
+                          float* u_save, const int* lengths, const int* offsets, long long n_valid, void* stream);
+int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* bn_x,
+                          const float* bn_mean, const float* bn_invstd, const float* u_save,
+                          const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                          const int* lengths, const int* offsets, long long n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * G9  mel filterbank front-end  (replaces torchaudio.compliance.kaldi.fbank(x,

@@ -78,6 +78,12 @@ PROTOTYPES = {
                                     c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, c_longlong, P]),
     "sparch_cell_bwd_len": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
                                     c_float, c_float, c_uint64, P, P, P, P, P, P, c_longlong, c_int, c_float, P]),
+    "sparch_cell_fwd_pk": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P,
+                                   c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, P, c_longlong, P]),
+    "sparch_cell_bwd_pk": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
+                                   c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_longlong, c_int, c_float, P]),
+    "sparch_pack_rows": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, c_longlong, P]),
+    "sparch_unpack_rows": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, c_longlong, P]),
     "sparch_vpack_bytes": (c_size_t, [c_int]),
     "sparch_set_xcd_local": (c_int, [c_int]),
     "sparch_vpack": (c_int, [c_int, P, c_int, P, P, P, c_int]),
@@ -99,6 +105,12 @@ PROTOTYPES = {
     "sparch_rec_cell_bwd_len": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
                                         c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_longlong, P, c_size_t, P,
                                         c_int, c_int, c_float, P, c_int]),
+    "sparch_rec_cell_fwd_pk": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P,
+                                       c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, P, c_longlong, P, c_size_t, P,
+                                       c_int, P, c_int]),
+    "sparch_rec_cell_bwd_pk": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
+                                       c_float, c_float, c_uint64, P, P, P, P, P, P, P, P, c_longlong, P, c_size_t, P,
+                                       c_int, c_int, c_float, P, c_int]),
     "sparch_rec_cell_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                          c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
     "sparch_rec_cell_step_stream_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P,
@@ -115,6 +127,8 @@ PROTOTYPES = {
     "sparch_readout_bwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
     "sparch_readout_fwd_len": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_longlong, P]),
     "sparch_readout_bwd_len": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_longlong, P]),
+    "sparch_readout_fwd_pk": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_longlong, P]),
+    "sparch_readout_bwd_pk": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, c_longlong, P]),
     "sparch_stream_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P,
                                        P, P, P, P, P, c_float, P, P]),
     "sparch_stream_step_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),

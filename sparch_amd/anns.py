@@ -79,7 +79,9 @@ class ANN(nn.Module):
                                           normalization=self.normalization, use_bias=self.use_bias))
         return nn.ModuleList(layers)
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, pack=False):
+        if pack:
+            raise ValueError("sparch_amd: pack=True is not supported by the non-spiking baselines (ANN)")
         if lengths is not None:  # (SNN.forward takes them: DESIGN.md section 7)
             raise ValueError("sparch_amd: lengths are not supported by the non-spiking baselines (ANN)")
         if self.reshape:

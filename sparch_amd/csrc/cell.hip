@@ -39,6 +39,13 @@ struct CellArgs {
 // The ragged entry points (`_len`): per-row sequence lengths (B,) behind CellArgs, which does not grow — only the
 // `_len` instantiations take them.
 struct CellLenArgs : CellArgs { const int* lengths; };
+// The packed entry points (`_pk`): the batch's sequences sorted by length, sequence j in rows [offsets[j], offsets[j] +
+// lengths[j]) of every (N,H) tensor (N = offsets[B]); B counts sequences and T is the longest length.
+struct CellPkArgs : CellArgs { const int* lengths; const int* offsets; };
+// The packed kernels give every sequence whole waves: a row of HQ threads is padded to the next multiple of 64 (the lanes
+// behind HQ leave at once), so that no wave straddles two sequences and a wave's length and row offset are scalars.
+__host__ __device__ constexpr int pk_row_threads(int HQ) { return (HQ + 63) / 64 * 64; }
+template <class Args> constexpr int cell_mode = std::is_same_v<Args, CellPkArgs> ? 2 : std::is_same_v<Args, CellLenArgs> ? 1 : 0;
 
 template <int VEC>
 __device__ __forceinline__ void ldv(float (&d)[VEC], const float* p) {
@@ -143,16 +150,30 @@ template <> struct SavedVec<1, true> {
 // and written back from the registers behind the last step, so that the next chunk's launch continues the sequence.
 // LEN (sparch_cell_fwd_len, one direction): the row's length is held by the thread, and the output spikes of steps at
 // or past it are 0 — a select on the value, not a branch (see DROP).  The state still runs on over the padding.
-template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP, bool STATE = false, bool LEN = false>
-__global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<LEN, CellLenArgs, CellArgs> c) {
+// PK (sparch_cell_fwd_pk, one direction): the packed layout.  The thread's T is its sequence's own length and its rows
+// start at offsets[b]: the loop, the ring's clamp and every index below are the plain kernel's on those two values, so
+// there is no padded step to select away.
+template <bool ADAPT, int VEC, int SAVE, bool SOUT, bool S16OUT, bool DROP, bool STATE = false, bool LEN = false, bool PK = false>
+__global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(
+    std::conditional_t<PK, CellPkArgs, std::conditional_t<LEN, CellLenArgs, CellArgs>> c) {
+    static_assert(!(PK && (LEN || STATE)), "packed: no lengths mask, no stream state");
     constexpr int D = pipe_depth(VEC, 1 + (SOUT ? 1 : 0) + (S16OUT ? 1 : 0) + (SAVE ? 1 + (ADAPT ? 1 : 0) : 0));
-    const int HQ = c.H / VEC;
+    // (PK is a constant: of `PK ? :` only the live arm is compiled, and without PK that is the expression it always was)
+    const int HQ = PK ? pk_row_threads(c.H / VEC) : c.H / VEC;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int Bp = c.B * c.dirs;
     if (idx >= (long long)Bp * HQ) return;
     const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
+    if (PK && h >= c.H) return;
     const int d = bp / c.B, b = bp - d * c.B;
-    const int T = c.T, H = c.H, HO = c.H * c.dirs;
+    // PK: a wave lies inside one sequence (pk_row_threads), so its length and first row are wave-uniform: scalars,
+    // like c.T — the time loop keeps its scalar branches and the ring its counted waits
+    [[maybe_unused]] int pk_len = 0, pk_row0 = 0;
+    if constexpr (PK) {
+        pk_len = __builtin_amdgcn_readfirstlane(c.lengths[b]);
+        pk_row0 = __builtin_amdgcn_readfirstlane(c.offsets[b]);
+    }
+    const int T = PK ? pk_len : c.T, H = c.H, HO = c.H * c.dirs;
 
     Neuron<ADAPT> p[VEC];
     float sc[VEC], sh[VEC];
@@ -174,7 +195,7 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<L
     int len = T;
     if constexpr (LEN) len = c.lengths[b];
 
-    const float* xrow = c.Wx + (size_t)b * T * H + h;
+    const float* xrow = c.Wx + (PK ? (size_t)pk_row0 : (size_t)b * T) * H + h;
     auto fetch = [&](float (&x)[VEC], int t) __attribute__((always_inline)) {
         const int tc = min(t, T - 1);  // past the end: a step that is in range and never used
         ldv<VEC>(x, xrow + (size_t)(d ? (T - 1 - tc) : tc) * H);
@@ -182,7 +203,7 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<L
     auto step = [&](int t, const float (&x)[VEC]) __attribute__((always_inline)) {
         const int tt = d ? (T - 1 - t) : t;
         float so[VEC];
-        const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
+        const size_t o = ((PK ? (size_t)pk_row0 : (size_t)b * T) + tt) * HO + (size_t)d * H + h;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float xn = neuron_input(x[e], false, 0.f, has_norm, sc[e], sh[e]);
@@ -198,8 +219,8 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<L
             else c.s16_out[o] = spike_bf16(so[0] != 0.0f);
         }
         if (SAVE) {
-            st_saved<VEC, true>(c.u_save, ((size_t)bp * T + t) * H + h, u, SAVE == 2, c.theta);
-            if (ADAPT) st_saved<VEC, false>(c.w_save, ((size_t)bp * T + t) * H + h, w, SAVE == 2, c.theta);
+            st_saved<VEC, true>(c.u_save, ((PK ? (size_t)pk_row0 : (size_t)bp * T) + t) * H + h, u, SAVE == 2, c.theta);
+            if (ADAPT) st_saved<VEC, false>(c.w_save, ((PK ? (size_t)pk_row0 : (size_t)bp * T) + t) * H + h, w, SAVE == 2, c.theta);
         }
     };
 
@@ -249,6 +270,13 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(std::conditional_t<L
 // takes the incoming gradient of step t as 0 at or past it; cell_bwd_pipe_len_sg_kernel is the same with a smooth gate
 // (two kernels as above: with both gates behind one run-time switch the box-car's VEC = 4 kernels came out of hipcc
 // with the smooth kernels' 256 VGPRs + AGPR copies at one wave per SIMD).
+// cell_bwd_pipe_pk_kernel / cell_bwd_pipe_pk_sg_kernel (sparch_cell_bwd_pk) are the packed ones: ROW_T(b) is the
+// sequence's own length and ROW0(r) its first packed row, and there is no tail to zero.
+#define ROW_THREADS(HQ) (HQ)
+#define ROW_GUARD(h)
+#define ROW0_INIT(b) 0
+#define ROW_T(b) c.T
+#define ROW0(r) ((size_t)(r) * T)
 #define ROW_LEN(b) T
 #define TAIL_ZERO(t, v) (v)
 template <bool ADAPT, int VEC, bool S16, bool BN, bool DROP>
@@ -279,6 +307,36 @@ __global__ __launch_bounds__(256) void cell_bwd_pipe_len_sg_kernel(CellLenArgs c
 #undef SURROGATE_GATE
 #undef ROW_LEN
 #undef TAIL_ZERO
+#undef ROW_T
+#undef ROW0
+#undef ROW_THREADS
+#undef ROW_GUARD
+#undef ROW0_INIT
+// (whole waves per sequence, see pk_row_threads: the length and the row offset are wave-uniform, i.e. scalars like c.T)
+#define ROW_THREADS(HQ) pk_row_threads(HQ)
+#define ROW_GUARD(h) if ((h) >= c.H) return;
+#define ROW0_INIT(b) __builtin_amdgcn_readfirstlane(c.offsets[b])
+#define ROW_T(b) __builtin_amdgcn_readfirstlane(c.lengths[b])
+#define ROW0(r) ((size_t)row0_pk)
+#define ROW_LEN(b) T
+#define TAIL_ZERO(t, v) (v)
+template <bool ADAPT, int VEC, bool S16, bool BN, bool DROP>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_pk_kernel(CellPkArgs c)
+#define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+template <bool ADAPT, int VEC, bool BN, bool DROP, bool S16 = false>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_pk_sg_kernel(CellPkArgs c, SurrogateArgs sg)
+#define SURROGATE_GATE(ds, x) smooth_gate(sg.id, sg.k, ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
+#undef ROW_T
+#undef ROW0
+#undef ROW_THREADS
+#undef ROW_GUARD
+#undef ROW0_INIT
 
 // ------------------------------------------------------------------ readout cell
 // Readout layer (snns.py:815-825): u_t = alpha u_{t-1} + (1-alpha) x_t, out = sum_t softmax_c(u_t).
@@ -311,10 +369,11 @@ __device__ __forceinline__ void ro_barrier() {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ro_row(const float* base, size_t row_elems, size_t row) {
+// `n_rows` rows of `row_elems` floats from row `row` on (one row: a batch row's whole (T,C) image)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ro_row(const float* base, size_t row_elems, size_t row, int n_rows = 1) {
     // a null base gives an empty resource: loads return 0, stores are dropped
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base ? base + row * row_elems : nullptr), 0,
-                                             base ? (int)(row_elems * sizeof(float)) : 0, 0x00020000);
+                                             base ? (int)(n_rows * row_elems * sizeof(float)) : 0, 0x00020000);
 }
 // bounds-checked fp32 accesses (the builtins move raw 32-bit words: bit casts, not conversions)
 __device__ __forceinline__ float ro_load(__amdgpu_buffer_rsrc_t r, unsigned off) {
@@ -332,6 +391,8 @@ struct RoCursor {
         if (c >= C) { c -= C; ++t; }
     }
 };
+__device__ __forceinline__ const int* ro_offsets() { return nullptr; }
+__device__ __forceinline__ const int* ro_offsets(const int* offsets) { return offsets; }
 // (ro_softmax_row: common.h — the streaming step's readout kernel, streamstep.hip, shares it)
 
 // STREAM (sparch_readout_stream_fwd): `u_io` (B,C) is the membrane state, read in place of u0 and written back behind
@@ -339,14 +400,20 @@ struct RoCursor {
 // (per-chunk sums added afterwards would round differently).
 // LEN (sparch_readout_fwd_len): the row's own length bounds the recurrence, the softmax and the sum — out is the
 // truncated sum over t < lengths[b], what the clip run alone gives; u_save is not written past it.
-template <bool STREAM, bool LEN = false>
+// Offsets (sparch_readout_fwd_pk, with LEN: one more argument, `const int* offsets`): the packed layout — the row's steps
+// are rows [offsets[b], offsets[b] + lengths[b]) of Wx / u_save (N,C), and its buffer resources end at its own last step.
+// (A trailing parameter pack: the kernels without it keep the argument list they had.)
+template <bool STREAM, bool LEN = false, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C, int rows, const float* __restrict__ Wx,
                                                             const float* __restrict__ scale,
                                                             const float* __restrict__ shift,
                                                             const float* __restrict__ alpha,
                                                             const float* __restrict__ u0, float* __restrict__ out,
                                                             float* __restrict__ u_save, float* u_io,
-                                                            const int* __restrict__ lengths) {
+                                                            const int* __restrict__ lengths, Offsets... pk) {
+    constexpr bool PK = sizeof...(Offsets) == 1;
+    static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
+    [[maybe_unused]] const int* offsets = ro_offsets(pk...);
     __shared__ float us[RO_FWD_FLOATS];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -361,7 +428,8 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     const float sc = has_bn ? scale[cp] : 1.0f, sh = has_bn ? shift[cp] : 0.0f;
     float u = STREAM ? u_io[(size_t)b * C + cp] : u0[(size_t)b * C + cp];
     float acc = STREAM ? out[(size_t)b * C + cp] : 0.f;
-    const __amdgpu_buffer_rsrc_t rx = ro_row(Wx, (size_t)T * C, b), ru = ro_row(u_save, (size_t)T * C, b);
+    const __amdgpu_buffer_rsrc_t rx = PK ? ro_row(Wx, (size_t)C, offsets[b], Tb) : ro_row(Wx, (size_t)T * C, b),
+                                 ru = PK ? ro_row(u_save, (size_t)C, offsets[b], Tb) : ro_row(u_save, (size_t)T * C, b);
     for (int c0 = 0; c0 < Tb; c0 += rows) {
         const int len = min(rows, Tb - c0), n = len * C;
         // thread = element: the chunk's projection -> LDS
@@ -446,8 +514,9 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
 //                                          (thread = class; reverse time)
 // Three chunk images in LDS: u (overwritten by e), u_{t-1} - u_t, and BatchNorm's xhat of the raw projection.
 // LEN (sparch_readout_bwd_len): the reverse recurrence starts at the row's last valid step; dWx past it is written as 0.
+// Offsets (sparch_readout_bwd_pk, with LEN): packed rows as in the forward; there is no tail of dWx to write.
 extern __shared__ __attribute__((aligned(16))) float ro_dyn_lds[];
-template <bool LEN>
+template <bool LEN, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C, int rows, const float* __restrict__ g_out,
                                                             const float* __restrict__ u_save,
                                                             const float* __restrict__ alpha,
@@ -456,7 +525,10 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                                                             const float* __restrict__ bn_x,
                                                             const float* __restrict__ bn_mean,
                                                             const float* __restrict__ bn_invstd,
-                                                            const int* __restrict__ lengths) {
+                                                            const int* __restrict__ lengths, Offsets... pk) {
+    constexpr bool PK = sizeof...(Offsets) == 1;
+    static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
+    [[maybe_unused]] const int* offsets = ro_offsets(pk...);
     __shared__ float gs[RO_NT];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -475,9 +547,11 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     // BatchNorm backward's column sums folded in (nullable): sum_t dWx and sum_t dWx*xhat per (row, class)
     const bool bn = bn_x != nullptr;
     float acc_dy = 0.f, acc_dyx = 0.f;
-    const __amdgpu_buffer_rsrc_t ru = ro_row(u_save, (size_t)T * C, b), rb = ro_row(bn_x, (size_t)T * C, b),
-                                 rd = ro_row(dWx, (size_t)T * C, b), r0 = ro_row(u0, (size_t)C, b);
-    if constexpr (LEN) {  // thread = element: the padded tail of dWx
+    const __amdgpu_buffer_rsrc_t ru = PK ? ro_row(u_save, (size_t)C, offsets[b], Tb) : ro_row(u_save, (size_t)T * C, b),
+                                 rb = PK ? ro_row(bn_x, (size_t)C, offsets[b], Tb) : ro_row(bn_x, (size_t)T * C, b),
+                                 rd = PK ? ro_row(dWx, (size_t)C, offsets[b], Tb) : ro_row(dWx, (size_t)T * C, b),
+                                 r0 = ro_row(u0, (size_t)C, b);
+    if constexpr (LEN && !PK) {  // thread = element: the padded tail of dWx
         for (int idx = Tb * C + tid; idx < T * C; idx += RO_NT) ro_store(0.f, rd, (unsigned)((size_t)idx * sizeof(float)));
     }
     const int nchunk = (Tb + rows - 1) / rows;
@@ -571,14 +645,20 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     }
 }
 
-// Args = CellLenArgs: the ragged instantiations (the forward's LEN, and the one backward family of every surrogate)
+// Args = CellLenArgs / CellPkArgs: the ragged / packed instantiations (the forward's LEN / PK, and their backward families)
 template <bool ADAPT, int VEC, bool DROP, class Args>
 void launch_cell_pipe(bool bwd, const Args& c, const SurrogateArgs& sg, unsigned blocks, hipStream_t st) {
-    constexpr bool LEN = std::is_same_v<Args, CellLenArgs>;
-    if constexpr (LEN) {
+    constexpr bool LEN = cell_mode<Args> == 1, PK = cell_mode<Args> == 2;
+    if constexpr (LEN || PK) {
         if (bwd) {
             auto go = [&](auto s16, auto bn) {  // (bf16 saves: the box-car only — the entry point has refused the rest)
                 constexpr bool S16 = decltype(s16)::value, BN = decltype(bn)::value;
+                if constexpr (PK) {
+                    if (S16 || sg.id == SPARCH_SURROGATE_BOXCAR)
+                        hipLaunchKernelGGL((cell_bwd_pipe_pk_kernel<ADAPT, VEC, S16, BN, DROP>), dim3(blocks), dim3(256), 0, st, c);
+                    else
+                        hipLaunchKernelGGL((cell_bwd_pipe_pk_sg_kernel<ADAPT, VEC, BN, DROP>), dim3(blocks), dim3(256), 0, st, c, sg);
+                } else
                 if (S16 || sg.id == SPARCH_SURROGATE_BOXCAR)
                     hipLaunchKernelGGL((cell_bwd_pipe_len_kernel<ADAPT, VEC, S16, BN, DROP>), dim3(blocks), dim3(256), 0, st, c);
                 else
@@ -609,7 +689,7 @@ void launch_cell_pipe(bool bwd, const Args& c, const SurrogateArgs& sg, unsigned
     }
     auto go = [&](auto save, auto sout, auto s16out) {
         hipLaunchKernelGGL((cell_fwd_pipe_kernel<ADAPT, VEC, decltype(save)::value, decltype(sout)::value,
-                                                 decltype(s16out)::value, DROP, false, LEN>),
+                                                 decltype(s16out)::value, DROP, false, LEN, PK>),
                            dim3(blocks), dim3(256), 0, st, c);
     };
     auto outs = [&](auto save) {
@@ -628,7 +708,8 @@ int launch_cell(bool bwd, Args& c, hipStream_t st, const SurrogateArgs sg = {}) 
     const bool vec_ok = (c.H % 4 == 0);
     // VEC=4 only when it still leaves >= 8 waves per CU; small problems favour more threads
     const bool vec4 = vec_ok && work >= (long long)256 * 8 * 64 * 4;
-    const long long threads = vec4 ? work / 4 : work;
+    long long threads = vec4 ? work / 4 : work;
+    if constexpr (cell_mode<Args> == 2) threads = (long long)c.B * pk_row_threads(vec4 ? c.H / 4 : c.H);  // whole waves per sequence
     const unsigned blocks = (unsigned)((threads + 255) / 256);
     const bool drop = c.p_drop > 0.0f;
     if (vec4) { if (drop) launch_cell_pipe<ADAPT, 4, true, Args>(bwd, c, sg, blocks, st); else launch_cell_pipe<ADAPT, 4, false, Args>(bwd, c, sg, blocks, st); }
@@ -672,7 +753,8 @@ int cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
                                const float* beta, const float* a, const float* b, const float* u0,
                                const float* w0, const float* s0, float theta, float p_drop,
                                uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
-                               int save_bf16, uint32_t* spike_count, void* stream, const int* lengths) {
+                               int save_bf16, uint32_t* spike_count, void* stream, const int* lengths,
+                               const int* offsets = nullptr) {
     if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
     const bool adapt = kind == SPARCH_KIND_ADLIF;
     if (B <= 0 || T <= 0 || H <= 0 || (dirs != 1 && dirs != 2) || !Wx || !alpha || !u0 || !s0 || (!s_out && !s16_out))
@@ -690,6 +772,10 @@ int cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
     c.theta = theta; c.p_drop = p_drop; c.inv_keep = 1.0f / (1.0f - p_drop); c.seed = seed;
     c.s_out = s_out; c.s16_out = s16_out; c.u_save = (float*)u_save; c.w_save = (float*)w_save;
     c.save16 = save_bf16 != 0; c.spike_count = spike_count;
+    if (offsets) {
+        CellPkArgs cp{c, lengths, offsets};
+        return adapt ? launch_cell<true>(false, cp, (hipStream_t)stream) : launch_cell<false>(false, cp, (hipStream_t)stream);
+    }
     if (lengths) {
         CellLenArgs cl{c, lengths};
         return adapt ? launch_cell<true>(false, cl, (hipStream_t)stream) : launch_cell<false>(false, cl, (hipStream_t)stream);
@@ -705,7 +791,7 @@ int cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                   const float* u0, const float* w0, const float* s0, float theta,
                                   float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
                                   const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
-                                  void* stream, const int* lengths, long long n_valid) {
+                                  void* stream, const int* lengths, long long n_valid, const int* offsets = nullptr) {
     if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
     if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
     if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x))) return SPARCH_EINVAL;
@@ -728,6 +814,10 @@ int cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
     c.dWx = dWx; c.dparam_ws = dparam_ws;
     c.bn_x = bn_x; c.bn_mean = bn_mean; c.bn_invstd = bn_invstd;
     const SurrogateArgs sg{surrogate, surrogate_scale};
+    if (offsets) {
+        CellPkArgs cp{c, lengths, offsets};
+        return adapt ? launch_cell<true>(true, cp, (hipStream_t)stream, sg) : launch_cell<false>(true, cp, (hipStream_t)stream, sg);
+    }
     if (lengths) {
         CellLenArgs cl{c, lengths};
         return adapt ? launch_cell<true>(true, cl, (hipStream_t)stream, sg) : launch_cell<false>(true, cl, (hipStream_t)stream, sg);
@@ -760,6 +850,19 @@ extern "C" int sparch_cell_fwd_len(int kind, int B, int dirs, int T, int H, cons
     if (!ragged_ok(dirs, lengths, n_valid)) return SPARCH_EINVAL;
     return cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed, s_out,
                     s16_out, u_save, w_save, save_bf16, spike_count, stream, lengths);
+}
+
+extern "C" int sparch_cell_fwd_pk(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                  const float* scale, const float* shift, const float* alpha,
+                                  const float* beta, const float* a, const float* b, const float* u0,
+                                  const float* w0, const float* s0, float theta, float p_drop,
+                                  uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                                  int save_bf16, uint32_t* spike_count, const int* lengths, const int* offsets,
+                                  long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!packed_ok(dirs, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    return cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, u0, w0, s0, theta, p_drop, seed, s_out,
+                    s16_out, u_save, w_save, save_bf16, spike_count, stream, lengths, offsets);
 }
 
 extern "C" int sparch_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
@@ -812,6 +915,20 @@ extern "C" int sparch_cell_bwd_len(int kind, int B, int dirs, int T, int H, cons
                     n_valid);
 }
 
+extern "C" int sparch_cell_bwd_pk(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                  const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                  const float* alpha, const float* beta, const float* a, const float* b,
+                                  const float* u0, const float* w0, const float* s0, float theta,
+                                  float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                                  const float* bn_mean, const float* bn_invstd, const int* lengths, const int* offsets,
+                                  long long n_valid, int surrogate, float surrogate_scale, void* stream) {
+    SPARCH_ENTER();
+    if (!packed_ok(dirs, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    return cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, u0, w0, s0, theta,
+                    p_drop, seed, dWx, dparam_ws, bn_x, bn_mean, bn_invstd, surrogate, surrogate_scale, stream, lengths,
+                    n_valid, offsets);
+}
+
 extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
                                const float* alpha, const float* beta, const float* a, const float* b,
@@ -825,11 +942,14 @@ extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const fl
 
 namespace {
 int readout_fwd(int B, int T, int C, const float* Wx, const float* scale, const float* shift, const float* alpha,
-                const float* u0, float* out, float* u_save, const int* lengths, void* stream) {
+                const float* u0, float* out, float* u_save, const int* lengths, const int* offsets, void* stream) {
     if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
     if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
     const int rows = ro_chunk_steps(T, C, RO_FWD_FLOATS);
-    if (lengths)
+    if (offsets)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, true, const int*>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                           rows, Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths, offsets);
+    else if (lengths)
         hipLaunchKernelGGL((readout_fwd_kernel<false, true>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C, rows, Wx,
                            scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths);
     else
@@ -839,22 +959,23 @@ int readout_fwd(int B, int T, int C, const float* Wx, const float* scale, const 
     return SPARCH_OK;
 }
 
-template <bool LEN>
+// offsets: none, or the packed form's `const int* offsets`
+template <bool LEN, class... Offsets>
 int readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x, const float* bn_mean, const float* bn_invstd,
                 const float* u_save, const float* alpha, const float* u0, float* dWx, float* dalpha_ws, const int* lengths,
-                void* stream) {
+                void* stream, Offsets... offsets) {
     // (dalpha uses u_{t-1}-x_t = (u_{t-1}-u_t)/(1-alpha): the projection is re-read only for BatchNorm's sums)
     if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !g_out || !u_save || !alpha || !u0 || !dWx || !dalpha_ws)
         return SPARCH_EINVAL;
     if (bn_x && (!bn_mean || !bn_invstd)) return SPARCH_EINVAL;
     const int rows = ro_chunk_steps(T, C, RO_BWD_FLOATS / 3);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_bwd_kernel<LEN>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_bwd_kernel<LEN, Offsets...>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        (int)(RO_BWD_FLOATS * sizeof(float)));
     if (attr != hipSuccess) { sparch_note_hip_error((int)attr); return SPARCH_ELAUNCH; }
-    hipLaunchKernelGGL(readout_bwd_kernel<LEN>, dim3(B), dim3(RO_NT), (size_t)3 * rows * ro_row_stride(C) * sizeof(float),
-                       (hipStream_t)stream, B, T, C, rows, g_out, u_save, alpha, u0, dWx, dalpha_ws, bn_x, bn_mean,
-                       bn_invstd, lengths);
+    hipLaunchKernelGGL((readout_bwd_kernel<LEN, Offsets...>), dim3(B), dim3(RO_NT),
+                       (size_t)3 * rows * ro_row_stride(C) * sizeof(float), (hipStream_t)stream, B, T, C, rows, g_out, u_save,
+                       alpha, u0, dWx, dalpha_ws, bn_x, bn_mean, bn_invstd, lengths, offsets...);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }
@@ -864,7 +985,7 @@ extern "C" int sparch_readout_fwd(int B, int T, int C, const float* Wx, const fl
                                   const float* shift, const float* alpha, const float* u0, float* out,
                                   float* u_save, void* stream) {
     SPARCH_ENTER();
-    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, nullptr, stream);
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, nullptr, nullptr, stream);
 }
 
 extern "C" int sparch_readout_fwd_len(int B, int T, int C, const float* Wx, const float* scale,
@@ -872,7 +993,16 @@ extern "C" int sparch_readout_fwd_len(int B, int T, int C, const float* Wx, cons
                                       float* u_save, const int* lengths, long long n_valid, void* stream) {
     SPARCH_ENTER();
     if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
-    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, stream);
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, nullptr, stream);
+}
+
+extern "C" int sparch_readout_fwd_pk(int B, int T, int C, const float* Wx, const float* scale,
+                                     const float* shift, const float* alpha, const float* u0, float* out,
+                                     float* u_save, const int* lengths, const int* offsets, long long n_valid,
+                                     void* stream) {
+    SPARCH_ENTER();
+    if (!packed_ok(1, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, offsets, stream);
 }
 
 extern "C" int sparch_readout_stream_fwd(int B, int T, int C, const float* Wx, const float* scale,
@@ -903,4 +1033,14 @@ extern "C" int sparch_readout_bwd_len(int B, int T, int C, const float* g_out, c
     SPARCH_ENTER();
     if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
     return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream);
+}
+
+extern "C" int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* bn_x,
+                                     const float* bn_mean, const float* bn_invstd, const float* u_save,
+                                     const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                                     const int* lengths, const int* offsets, long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!packed_ok(1, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream,
+                                   offsets);
 }

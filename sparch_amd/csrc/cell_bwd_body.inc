@@ -1,20 +1,30 @@
 // The body of the LIF / adLIF reverse pass (cell.hip includes it once per kernel family, behind the kernel's
-// signature): template parameters ADAPT, VEC, S16, BN, DROP, the argument `CellArgs c`, and SURROGATE_GATE(ds, x), the
-// surrogate gradient's gate — boxcar_gate for cell_bwd_pipe_kernel, smooth_gate on the second kernel argument for
-// cell_bwd_pipe_sg_kernel, the same two for the ragged cell_bwd_pipe_len_kernel / cell_bwd_pipe_len_sg_kernel — and ROW_LEN(b) / TAIL_ZERO(t, v): the row's
-// length and the select that zeroes the incoming gradient of padded steps (T and the value itself in the kernels without
-// lengths; from a zero gradient the carries du, dw stay zero over the tail, and with them dWx and every partial sum).
+// signature): template parameters ADAPT, VEC, S16, BN, DROP, the argument `c` (CellArgs, CellLenArgs or CellPkArgs) and
+// the macros below.  The families: cell_bwd_pipe_kernel / cell_bwd_pipe_sg_kernel (no lengths),
+// cell_bwd_pipe_len_kernel / cell_bwd_pipe_len_sg_kernel (ragged, masked), cell_bwd_pipe_pk_kernel /
+// cell_bwd_pipe_pk_sg_kernel (ragged, packed).
+//   SURROGATE_GATE(ds, x)  the surrogate gradient's gate: boxcar_gate, or smooth_gate on the `_sg` kernels' second argument
+//   ROW_LEN(b)             the row's length; TAIL_ZERO(t, v): the incoming gradient v of step t, 0 at or past that length.
+//                          T and v itself except in the `_len` family.  (From a zero gradient the carries du, dw stay zero
+//                          over the tail, and with them dWx and every partial sum.)
+//   ROW_T(b)               the steps row b runs: c.T; packed: the sequence's own length
+//   ROW0(r)                the first row of row r's (rows, H) tensors: r * T; packed: the sequence's offset (row0_pk,
+//                          which ROW0_INIT(b) loads once; 0 elsewhere)
+//   ROW_THREADS(HQ)        threads per row: HQ; packed: HQ padded to whole waves, so that ROW_T and ROW0 are wave-uniform
+//                          (scalars, like c.T), and ROW_GUARD(h) retires the lanes behind the row (empty elsewhere)
 // Text, not a function: inlined from a shared __device__ function the box-car kernels came
 // out of the compiler with another schedule, and they are held to the instructions they had (DESIGN.md section 6).
 {
     constexpr int D = pipe_depth(VEC, 3 + (ADAPT ? 1 : 0) + (BN ? 1 : 0));
-    const int HQ = c.H / VEC;
+    const int HQ = ROW_THREADS(c.H / VEC);
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int Bp = c.B * c.dirs;
     if (idx >= (long long)Bp * HQ) return;
     const int bp = (int)(idx / HQ), h = (int)(idx % HQ) * VEC;
+    ROW_GUARD(h)
     const int d = bp / c.B, b = bp - d * c.B;
-    const int T = c.T, H = c.H, HO = c.H * c.dirs;
+    [[maybe_unused]] const int row0_pk = ROW0_INIT(b);
+    const int T = ROW_T(b), H = c.H, HO = c.H * c.dirs;
     [[maybe_unused]] const int row_len = ROW_LEN(b);
 
     float al[VEC], oma[VEC], be[VEC], pa[VEC], pb[VEC], gr[VEC];
@@ -32,7 +42,7 @@
         du_n[e] = dw_n[e] = 0.f;
         acc_al[e] = acc_be[e] = acc_a[e] = acc_b[e] = 0.f;
     }
-    ld_saved<VEC>(u_t, c.u_save, ((size_t)bp * T + (T - 1)) * H + h, S16);
+    ld_saved<VEC>(u_t, c.u_save, (ROW0(bp) + (T - 1)) * H + h, S16);
     // the initial states: read by cell step 0 (the last of the reverse pass) only; fetched here, off the loop
     float u0v[VEC], w0v[VEC], s0v[VEC];
     ldv<VEC>(u0v, c.u0 + (size_t)bp * H + h);
@@ -42,9 +52,9 @@
     const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
 
     struct Slot { float g[VEC]; float xr[BN ? VEC : 1]; SavedVec<VEC, S16> up; SavedVec<VEC, S16> wp; };
-    const float* grow = c.g_out + (size_t)b * T * HO + (size_t)d * H + h;
-    const float* xrow = BN ? c.bn_x + (size_t)b * T * H + h : nullptr;
-    const size_t srow = (size_t)bp * T * H + h;
+    const float* grow = c.g_out + ROW0(b) * HO + (size_t)d * H + h;
+    const float* xrow = BN ? c.bn_x + ROW0(b) * H + h : nullptr;
+    const size_t srow = ROW0(bp) * H + h;
     auto fetch = [&](Slot& q, int t) __attribute__((always_inline)) {
         const int tc = max(t, 0);  // before the start: a step that is in range and never used
         const int tt = d ? (T - 1 - tc) : tc;
@@ -58,7 +68,7 @@
     auto step = [&](int t, const Slot& q, auto first_tag) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_tag)::value;
         const int tt = d ? (T - 1 - t) : t;
-        const size_t o = ((size_t)b * T + tt) * HO + (size_t)d * H + h;
+        const size_t o = (ROW0(b) + tt) * HO + (size_t)d * H + h;
         float up[VEC], wp[VEC], sp[VEC], dwx[VEC];
         q.up.expand(up);
         if (ADAPT) q.wp.expand(wp);
@@ -97,7 +107,7 @@
             // mid-loop — each of which waits for a load issued a few operations earlier
             asm volatile("v_mov_b32 %0, %1" : "=&v"(u_t[e]) : "v"(up[e]));
         }
-        stv<VEC>(c.dWx + ((size_t)bp * T + tt) * H + h, dwx);
+        stv<VEC>(c.dWx + (ROW0(bp) + tt) * H + h, dwx);
     };
 
     Slot ring[D];

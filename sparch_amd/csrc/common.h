@@ -88,6 +88,11 @@ static inline bool surrogate_ok(int id, float k, int save_bf16) {
 // what a ragged (`_len`) entry point checks before any device work: one direction (a flipped direction would have to turn
 // inside each row's own length), the lengths, and at least one valid step in the batch
 static inline bool ragged_ok(int dirs, const int* lengths, long long n_valid) { return dirs == 1 && lengths && n_valid >= 1; }
+// the same for a packed (`_pk`) entry point: the sorted lengths (B,) and their exclusive prefix sum (B + 1,), the packed
+// row count n_valid = offsets[B]
+static inline bool packed_ok(int dirs, const int* lengths, const int* offsets, long long n_valid) {
+    return ragged_ok(dirs, lengths, n_valid) && offsets;
+}
 
 // ---- optional bf16 storage of the states saved for the backward pass (u, w): half the bytes of the two
 // largest tensors a spiking layer keeps.  The backward takes three DISCRETE decisions from a saved membrane

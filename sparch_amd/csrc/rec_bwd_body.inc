@@ -3,6 +3,17 @@
 // SURROGATE_GATE(ds, x), the surrogate gradient's gate — boxcar_gate for rec_bwd_kernel, smooth_gate on `a.sg`
 // for rec_bwd_sg_kernel, any_gate for the ragged rec_bwd_len_kernel (RecLenArgs) — and ROW_LEN(b) / TAIL_ZERO(t, v), the
 // row's length and the select on the incoming gradient of padded steps.  Text, not a function: see cell_bwd_body.inc.
+// The packed rec_bwd_pk_kernel (RecPkArgs, whole-sequence launches) differs in five more macros; elsewhere they are the
+// expressions this body always had:
+//   ROW_PK_INIT         declares row0 (the row's first packed row) and t_tile (the length of the tile's first, longest
+//                       row: the same in all of the tile's workgroups, so the hand-off protocol is untouched); else empty
+//   T_HI                the step count the launch walks down from: a.t_end; packed: min(a.t_end, t_tile)
+//   T_RING              the bound of the ring's conditions (is there a step t + 1 / t + 2): T; packed: t_tile
+//   RROW(r, t)          row of step t of row r in the (rows, .) tensors: r * T + t; packed: row0 + min(t, row_len - 1) —
+//                       a shorter row's loads stay inside its own packed rows
+//   ROW_STORE(t)        whether step t's dWx / s_prev16 are stored: true; packed: t < row_len (a store behind a row's
+//                       end would land in the next sequence).  Such a step's incoming gradient is zero (TAIL_ZERO), its
+//                       recurrent term is its own zero dWx row times V^T: it computes and publishes zeros.
 {
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT && NP == 1), "64-column workgroups: bf16 operand mode, 8 waves");
     // cross-wave reduction tiles: written before the step's first barrier, read after it by the pointwise
@@ -55,6 +66,7 @@
     const int bpc = min(bp, a.Bp - 1), colc = min(col, H - 4);
     const int d = bpc / a.B, b = bpc - d * a.B;
     [[maybe_unused]] const int row_len = ROW_LEN(b);
+    ROW_PK_INIT
 
     u32x4 vb[CW][KGW][2][NP == 3 ? 2 : 1];
 #pragma unroll
@@ -121,7 +133,7 @@
         }
     }
     {
-        const f32x4 v = expand_saved(ld_saved_raw<S16>(a.u_save, ((size_t)bpc * T + (a.t_end - 1)) * H + colc));
+        const f32x4 v = expand_saved(ld_saved_raw<S16>(a.u_save, RROW(bpc, T_HI - 1) * H + colc));
         u_t[0] = v.x; u_t[1] = v.y; u_t[2] = v.z; u_t[3] = v.w;
     }
     if (tid < 2) abort_flag[tid] = 0;
@@ -148,23 +160,23 @@
     typedef typename SavedRaw<S16>::type saved_raw;
     auto load_step = [&](int t, f32x4& g, saved_raw& up, saved_raw& wp, f32x4& xr) {
         const int tt = d ? (T - 1 - t) : t;
-        const float* gp = a.g_out + ((size_t)b * T + tt) * HO + (size_t)d * H + colc;
+        const float* gp = a.g_out + RROW(b, tt) * HO + (size_t)d * H + colc;
         g = ld4s(gp);
-        xr = ld4s(a.bn_src + ((size_t)b * T + tt) * H + colc);
-        const size_t o = ((size_t)bpc * T + (size_t)max(t - 1, 0)) * H + colc;
+        xr = ld4s(a.bn_src + RROW(b, tt) * H + colc);
+        const size_t o = RROW(bpc, (size_t)max(t - 1, 0)) * H + colc;
         up = ld_saved_raw<S16>(a.u_save, o);
         if (ADAPT) wp = ld_saved_raw<S16>(a.w_save, o);
     };
     f32x4 g_nx = {0.f, 0.f, 0.f, 0.f}, xr_nx = g_nx;
     saved_raw up_nx = {}, wp_nx = {};
-    if (pw) load_step(a.t_end - 1, g_nx, up_nx, wp_nx, xr_nx);
+    if (pw) load_step(T_HI - 1, g_nx, up_nx, wp_nx, xr_nx);
     vm_settled();  // every prologue load is in: the loop is entered with nothing outstanding
     // (Unlike the forward, holding this kernel's fp32 stores / prefetch back until after the tag poll does
     // not pay: measured 16.8k -> 18.2k cycles per step, the deferred traffic then competes with the tile loads.)
     PROF_DECL
 
     int t_stop = -1;  // the step an abort was seen at (diagnostics of the status word)
-    for (int t = a.t_end - 1; t >= a.t_begin; --t) {
+    for (int t = T_HI - 1; t >= a.t_begin; --t) {
         PROF_STAMP(-1);
         const int pt = CW == 2 ? tid : (tid & 255);
         const f32x4 gv = g_nx, xrv = xr_nx;
@@ -181,7 +193,7 @@
         // behind the barrier is then `+ rec`, the box-car gate, two adds and a multiply.  Same operations in the
         // same order as the reference's autograd replay: bit-identical results.
         const int tt = d ? (T - 1 - t) : t;
-        const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + colc;
+        const size_t o_out = RROW(b, tt) * HO + (size_t)d * H + colc;
         float pre_ds[4], pre_aldu[4], pre_padw[4];
         auto pre_pointwise = [&]() __attribute__((always_inline)) {
             const f32x4 al = pcol[0][d][cqx], pa = pcol[2][d][cqx], pb = pcol[3][d][cqx], gr = pcol[4][d][cqx];
@@ -197,9 +209,9 @@
                 asm volatile("" : "+v"(pre_ds[e]), "+v"(pre_aldu[e]), "+v"(pre_padw[e]));  // not sunk behind the barrier
             }
         };
-        if (!(t + 1 < T && !EXT) && pw) pre_pointwise();
+        if (!(t + 1 < T_RING && !EXT) && pw) pre_pointwise();
 
-        if (t + 1 < T && !EXT) {
+        if (t + 1 < T_RING && !EXT) {
             // ---- the dWx_{t+1} tiles of this wave's producers: load, re-load what has not landed yet
             const unsigned slot = (unsigned)((t + 1) % RING);
             const unsigned base = slot * slot_bytes + rt_off + (unsigned)lane * 16u;
@@ -303,15 +315,17 @@
                 const int piece = (tid - 256) + 256 * q;
                 // (nothing to reset: an offset beyond the buffer resource — chosen per piece, a base of 0xFFFFF000
                 // plus 16 * piece would wrap around into the ring's first tile)
-                const unsigned o = (t + 2 < T && piece < PIECES) ? so + (unsigned)piece * 16u : 0xFFFFF000u;
+                const unsigned o = (t + 2 < T_RING && piece < PIECES) ? so + (unsigned)piece * 16u : 0xFFFFF000u;
                 if (xcd_local) __builtin_amdgcn_raw_buffer_store_b128(sent4, rsrc, o, 0, 0);
                 else __builtin_amdgcn_raw_buffer_store_b128(sent4, rsrc, o, 0, AUX_SC1);
             }
         }
-        if (BXS && valid_hi && t + 1 < a.t_end) {  // the previous step's staged outputs -> HBM (upper waves)
+        if (BXS && valid_hi && t + 1 < T_HI) {  // the previous step's staged outputs -> HBM (upper waves)
             const int t1 = t + 1, tt1 = d ? (T - 1 - t1) : t1;
-            st4(a.dWx + ((size_t)bp * T + tt1) * H + col, stage_dwx[tid & 255]);
-            st2(a.s_prev16 + ((size_t)bp * T + tt1) * H + col, stage_sp[tid & 255]);
+            if (ROW_STORE(t1)) {
+                st4(a.dWx + RROW(bp, tt1) * H + col, stage_dwx[tid & 255]);
+                st2(a.s_prev16 + RROW(bp, tt1) * H + col, stage_sp[tid & 255]);
+            }
         }
         // From here to the publish barrier: the waves that own pointwise state only (a WAVE-UNIFORM branch, round 3
         // — until then the upper four waves ran the reduction reads and the whole reverse step on dead values and
@@ -323,10 +337,10 @@
         // NP = 1 kernels follows these declarations, and the shipped instruction order is the measured one)
         f32x4 up_use = upv, ut_use = {u_t[0], u_t[1], u_t[2], u_t[3]};
         if (pw_wave) {
-        if (t + 1 < T && EXT) {
+        if (t + 1 < T_RING && EXT) {
             const f32x4 v = ld4(a.rec0 + (size_t)bpc * H + colc);
             rec[0] = v.x; rec[1] = v.y; rec[2] = v.z; rec[3] = v.w;
-        } else if (t + 1 < T) {
+        } else if (t + 1 < T_RING) {
             f32x4 sum = *reinterpret_cast<const f32x4*>(&red[0][cj][r * RED_LD4 + cq * 4]);  // (see the forward)
 #pragma unroll
             for (int w = 1; w < NW; ++w) {
@@ -402,7 +416,7 @@
             }
             if (!BXS) {  // (8-wave kernels: the upper waves put the sentinels back, see above)
                 const u32x2 sent = {SENTINEL, SENTINEL};
-                const unsigned so = t + 2 < T ? (unsigned)((t + 2) % RING) * slot_bytes + tile_off : 0xFFFFF000u;
+                const unsigned so = t + 2 < T_RING ? (unsigned)((t + 2) % RING) * slot_bytes + tile_off : 0xFFFFF000u;
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     if (xcd_local) __builtin_amdgcn_raw_buffer_store_b64(sent, rsrc, so + (unsigned)(p * 1024), 0, 0);
@@ -421,9 +435,9 @@
             h.y = (spv[2] != 0.f ? 0x3F80u : 0u) | (spv[3] != 0.f ? 0x3F800000u : 0u);
             if (BXS) {
                 stage_dwx[tid] = dwx; stage_sp[tid] = h;
-            } else {
-                st4(a.dWx + ((size_t)bp * T + tt) * H + col, dwx);
-                st2(a.s_prev16 + ((size_t)bp * T + tt) * H + col, h);
+            } else if (ROW_STORE(t)) {
+                st4(a.dWx + RROW(bp, tt) * H + col, dwx);
+                st2(a.s_prev16 + RROW(bp, tt) * H + col, h);
             }
         }
         if (pw) {
@@ -467,8 +481,8 @@
         __syncthreads();
         if (!aborted && valid_hi && a.t_end > a.t_begin) {
             const int t1 = a.t_begin, tt1 = d ? (T - 1 - t1) : t1;
-            st4(a.dWx + ((size_t)bp * T + tt1) * H + col, stage_dwx[tid & 255]);
-            st2(a.s_prev16 + ((size_t)bp * T + tt1) * H + col, stage_sp[tid & 255]);
+            st4(a.dWx + RROW(bp, tt1) * H + col, stage_dwx[tid & 255]);      // (step 0: every row has it)
+            st2(a.s_prev16 + RROW(bp, tt1) * H + col, stage_sp[tid & 255]);
         }
     }
     if (tid == 0 && (lds_flag_read(&abort_flag[0]) | lds_flag_read(&abort_flag[1])))

@@ -99,6 +99,9 @@ struct RecArgs {
 // by-value argument (the kernel table's rows are KernelRef<Args>)
 struct RecSgArgs : RecArgs { SurrogateArgs sg; };
 struct RecLenArgs : RecSgArgs { const int* lengths; };
+// the packed (`_pk`) kernels: the sorted lengths and the exclusive prefix sum (B + 1,) behind them — sequence j owns rows
+// [offsets[j], offsets[j] + lengths[j]) of every (N, .) tensor; B counts sequences and T is the longest length
+struct RecPkArgs : RecLenArgs { const int* offsets; };
 
 // Diagnostic build only (-DSPARCH_REC_PROF, never shipped): per-workgroup sums of s_memtime
 // deltas for the segments of a time step, written to a private buffer no kernel reads.
@@ -148,8 +151,16 @@ __device__ u64 g_rec_prof[2][512][12];
 // LEN (sparch_rec_cell_fwd_len, one direction): the output spikes of steps at or past the row's length are 0 and not
 // counted — a select in the dropout block.  The spikes PUBLISHED to the peers and the saved states stay unmasked: a
 // row's padded steps are garbage in, masked out, and nothing of them reaches a valid step (time runs forward only).
-template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool STREAM = false, bool LEN = false>
-__global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<LEN, RecLenArgs, RecArgs> a) {
+// PK (sparch_rec_cell_fwd_pk, with LEN; whole-sequence launches only): the packed layout.  A row tile runs t < the length
+// of its first row, its longest (the rows are sorted): the bound is the same in all of the tile's workgroups, so the
+// poll / publish protocol is untouched.  A shorter row keeps computing and publishing (unmasked, as with LEN) up to the
+// tile's bound; its projection loads are clamped into its own packed rows and its stores happen only for t < its length
+// — a store behind a row's end would land in the next sequence.
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, int CW = 1, bool STREAM = false, bool LEN = false,
+          bool PK = false>
+__global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(
+    std::conditional_t<PK, RecPkArgs, std::conditional_t<LEN, RecLenArgs, RecArgs>> a) {
+    static_assert(!PK || (LEN && !EXT && !STREAM), "packed: the ragged whole-sequence forward");
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT), "64-column workgroups: the 8-wave persistent kernels");
     static_assert(!STREAM || CW == 1, "the streaming kernels own 32 columns per workgroup");
     __shared__ __attribute__((aligned(16))) float red[2][NW][CW][RT * RED_LD4];
@@ -225,9 +236,16 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<
     const uint64_t seed = drop ? resolve_seed(a.seed) : 0;
     int len = T;
     if constexpr (LEN) len = a.lengths[b];
+    // (PK is a constant: of `PK ? :` only the live arm is compiled, and without PK that is the expression it always was)
+    [[maybe_unused]] size_t row0 = 0;   // the row's first packed row
+    [[maybe_unused]] int t_tile = 0;    // the tile's bound: the length of its first row
+    if constexpr (PK) {
+        row0 = (size_t)a.offsets[b];
+        t_tile = __builtin_amdgcn_readfirstlane(a.lengths[min(rt * RT, a.Bp - 1)]);
+    }
     auto wx_ptr = [&](int t) {
         const int tt = d ? (T - 1 - t) : t;
-        return a.Wx + ((size_t)b * T + tt) * H + colc;
+        return a.Wx + (PK ? row0 + min(t, len - 1) : (size_t)b * T + tt) * H + colc;
     };
     f32x4 x_next = {0.f, 0.f, 0.f, 0.f};
     if (pw) x_next = ld4s(wx_ptr(a.t_begin));
@@ -252,23 +270,23 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<
     // for its slowest wave.  DESIGN.md, "Retired experiment switches".)
     auto store_step = [&](int st_t, const f32x4& vs, const f32x4& vu, const f32x4& vw) {
         const int ptt = d ? (T - 1 - st_t) : st_t;
-        const size_t o_s = ((size_t)b * T + ptt) * HO + (size_t)d * H + colc;
+        const size_t o_s = (PK ? row0 + st_t : (size_t)b * T + ptt) * HO + (size_t)d * H + colc;
         if (a.s_out) st4(a.s_out + o_s, vs);  // the fp32 copy: only for callers that read the layer's output tensor
         if (a.s16_out) {  // the same spikes as a bf16 plane (0 / 1.0) for the GEMMs that consume them
             st2(a.s16_out + o_s, spike_quad16(vs));
         }
         if constexpr (!STREAM) {
-            st4_saved<true>(a.u_save, ((size_t)bp * T + st_t) * H + col, vu, a.save16, a.theta);
-            if (ADAPT) st4_saved<false>(a.w_save, ((size_t)bp * T + st_t) * H + col, vw, a.save16, a.theta);
+            st4_saved<true>(a.u_save, (PK ? row0 + st_t : (size_t)bp * T + st_t) * H + col, vu, a.save16, a.theta);
+            if (ADAPT) st4_saved<false>(a.w_save, (PK ? row0 + st_t : (size_t)bp * T + st_t) * H + col, vw, a.save16, a.theta);
         }
     };
     auto flush_pending = [&]() {
-        if (pend_t >= 0 && valid) store_step(pend_t, pend_s, pend_u, pend_w);
+        if (pend_t >= 0 && valid && (!PK || pend_t < len)) store_step(pend_t, pend_s, pend_u, pend_w);
         pend_t = -1;
     };
     PROF_DECL
 
-    for (int t = a.t_begin; t < a.t_end; ++t) {
+    for (int t = a.t_begin; t < (PK ? min(a.t_end, t_tile) : a.t_end); ++t) {
         PROF_STAMP(-1);
         // this step's projection row.  (The take-over copy of the prefetch register ends up at the loop latch with
         // an `s_waitcnt vmcnt(0)` in front of the next poll's issue.  Measured against it in one call, 40 launches
@@ -407,7 +425,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<
             if (valid) {  // the step's raw (pre-dropout) spikes: operand of the caller's s_t @ V product
                 *reinterpret_cast<u32x2*>(a.s_step16 + (size_t)bp * H + col) = spike_quad16(s);
             }
-        } else if (pw && cq == 0 && t + 1 < T) {
+        } else if (pw && cq == 0 && t + 1 < (PK ? t_tile : T)) {
             gu64* slot = (gu64*)a.chan + (((size_t)t * a.n_rt_total + rt) * a.n_ct + ct) * 32 + r;
             const u64 granule = ((u64)(unsigned)(t + 1) << 32) | (u64)word;
             if (xcd_local) __hip_atomic_store(slot, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -417,7 +435,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<
         PROF_STAMP(3);  // pointwise + publish
         if (valid) {
             const int tt = d ? (T - 1 - t) : t;
-            const size_t o_out = ((size_t)b * T + tt) * HO + (size_t)d * H + colc;
+            const size_t o_out = (PK ? row0 + t : (size_t)b * T + tt) * HO + (size_t)d * H + colc;
             f32x4 so;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -489,6 +507,11 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(std::conditional_t<
 // only: S16 is never set there).
 // ROW_LEN(b) / TAIL_ZERO(t, v): see cell_bwd_body.inc — the ragged family's row length and its select on the incoming
 // gradient (a row's recurrent term is its own dWx_{t+1} row times V^T: zero over its tail like the carries).
+#define ROW_PK_INIT
+#define T_HI a.t_end
+#define T_RING T
+#define RROW(r, t) ((size_t)(r) * T + (t))
+#define ROW_STORE(t) true
 #define ROW_LEN(b) T
 #define TAIL_ZERO(t, v) (v)
 template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, bool S16 = false, int CW = 1>
@@ -511,6 +534,29 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_len_kernel(RecLenArgs a)
 #define SURROGATE_GATE(ds, x) any_gate(a.sg.id, a.sg.k, ds, x)
 #include "rec_bwd_body.inc"
 #undef SURROGATE_GATE
+#undef ROW_PK_INIT
+#undef T_HI
+#undef T_RING
+#undef RROW
+#undef ROW_STORE
+// the packed family (sparch_rec_cell_bwd_pk): the ragged one's length and gradient select, on packed rows
+#define ROW_PK_INIT                                   \
+    const size_t row0 = (size_t)a.offsets[b];         \
+    const int t_tile = __builtin_amdgcn_readfirstlane(a.lengths[min(rt * RT, a.Bp - 1)]);
+#define T_HI min(a.t_end, t_tile)
+#define T_RING t_tile
+#define RROW(r, t) (row0 + (size_t)min((int)(t), row_len - 1))
+#define ROW_STORE(t) ((t) < row_len)
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, bool S16 = false, int CW = 1>
+__global__ __launch_bounds__(64 * NW, 1) void rec_bwd_pk_kernel(RecPkArgs a)
+#define SURROGATE_GATE(ds, x) any_gate(a.sg.id, a.sg.k, ds, x)
+#include "rec_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_PK_INIT
+#undef T_HI
+#undef T_RING
+#undef RROW
+#undef ROW_STORE
 #undef ROW_LEN
 #undef TAIL_ZERO
 
@@ -807,18 +853,23 @@ RecKernelOf<SG> rec_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
         });
     });
 }
-// the ragged kernels (RecLenArgs): the persistent forward with LEN, and the one backward family of every surrogate
-using RecLenKernel = KernelRef<RecLenArgs>;
-template <bool BWD>
-RecLenKernel rec_len_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
+// the ragged kernels (RecLenArgs): the persistent forward with LEN, and the one backward family of every surrogate;
+// PK: their packed forms (RecPkArgs)
+template <bool PK> using RecLenArgsOf = std::conditional_t<PK, RecPkArgs, RecLenArgs>;
+template <bool PK> using RecLenKernelOf = KernelRef<RecLenArgsOf<PK>>;
+using RecLenKernel = RecLenKernelOf<false>;
+template <bool BWD, bool PK = false>
+RecLenKernelOf<PK> rec_len_kernel(bool adapt, bool low, int kgw, int cw, bool save16) {
     return rec_plan::with_kgw(kgw, [&](auto k) {
         return rec_plan::with_bool(adapt, [&](auto ad) {
-            return rec_plan::with_bool(BWD && save16, [&](auto s16) -> RecLenKernel {
+            return rec_plan::with_bool(BWD && save16, [&](auto s16) -> RecLenKernelOf<PK> {
                 constexpr int K = decltype(k)::value, KB = rec_kb(K), NW = rec_nw(K);
                 constexpr bool A = decltype(ad)::value, S16 = decltype(s16)::value;
-                auto of = [](auto np, auto cwc) -> RecLenKernel {
+                auto of = [](auto np, auto cwc) -> RecLenKernelOf<PK> {
                     constexpr int NP = decltype(np)::value, CW = decltype(cwc)::value;
-                    if constexpr (BWD) return kernel_with_occupancy<RecLenArgs, rec_bwd_len_kernel<A, KB, NW, false, NP, S16, CW>, 64 * NW>();
+                    if constexpr (BWD && PK) return kernel_with_occupancy<RecPkArgs, rec_bwd_pk_kernel<A, KB, NW, false, NP, S16, CW>, 64 * NW>();
+                    else if constexpr (PK) return kernel_with_occupancy<RecPkArgs, rec_fwd_kernel<A, KB, NW, false, NP, CW, false, true, true>, 64 * NW>();
+                    else if constexpr (BWD) return kernel_with_occupancy<RecLenArgs, rec_bwd_len_kernel<A, KB, NW, false, NP, S16, CW>, 64 * NW>();
                     else return kernel_with_occupancy<RecLenArgs, rec_fwd_kernel<A, KB, NW, false, NP, CW, false, true>, 64 * NW>();
                 };
                 using rec_plan::kgw_c;
@@ -830,11 +881,13 @@ RecLenKernel rec_len_kernel(bool adapt, bool low, int kgw, int cw, bool save16) 
         });
     });
 }
-RecLenArgs with_lengths(const RecArgs& a, const SurrogateArgs sg, const int* lengths) {
-    RecLenArgs g;
+template <bool PK = false>
+RecLenArgsOf<PK> with_lengths(const RecArgs& a, const SurrogateArgs sg, const int* lengths, const int* offsets = nullptr) {
+    RecLenArgsOf<PK> g;
     static_cast<RecArgs&>(g) = a;
     g.sg = sg;
     g.lengths = lengths;
+    if constexpr (PK) g.offsets = offsets;
     return g;
 }
 // the step variants (EXT): the recurrent product comes from the caller, one k-group class, no hand-off
@@ -876,11 +929,14 @@ AnnKernel ann_kernel(int act, int kgw) {
 
 // ---- one pass of the persistent kernels: size and check the workspace, clear it, plan and walk (rec_plan.h)
 // SG (backward): `sg` names a smooth surrogate and the pass runs on the rec_bwd_sg_kernel rows of the table
-// lengths (not null): the ragged pass, on the rec_len_kernel table (`sg` is then any surrogate)
-template <bool BWD, bool STREAM = false, bool SG = false, bool LEN = false>
+// lengths (not null): the ragged pass, on the rec_len_kernel table (`sg` is then any surrogate); PK: its packed form
+// (offsets not null), whole-sequence launches only
+template <bool BWD, bool STREAM = false, bool SG = false, bool LEN = false, bool PK = false>
 int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st, const SurrogateArgs sg = {},
-            const int* lengths = nullptr) {
+            const int* lengths = nullptr, const int* offsets = nullptr) {
     static_assert(!LEN || (!STREAM && !SG), "the ragged pass has its own table");
+    static_assert(!PK || LEN, "the packed pass is a ragged one");
+    if (PK && steps_per_launch < a.T) return SPARCH_EINVAL;
     const bool adapt = kind == SPARCH_KIND_RADLIF;
     const bool low = sparch_operand_bf16() != 0;  // the V pack must have been made in the same mode
     const int kgw = pick_kgw(a.H);
@@ -898,22 +954,23 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     static const int cw_env = [] { const char* e = getenv("SPARCH_REC_CW"); return e ? atoi(e) : 0; }();
     rec_plan::Policy pol;
     pol.ask_occupancy = true;
-    pol.refuse_degrade = a.save16 && !BWD;  // bf16 saves need the whole-sequence forward launch
+    pol.refuse_degrade = (a.save16 && !BWD) || PK;  // bf16 saves need the whole-sequence forward launch; so do packed rows
     pol.has_cw2 = !STREAM && low && kgw >= 2;
     pol.cw_override = cw_env;
     const int cus = sparch_device_cus();
     const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, cus, pol, [&](unsigned grid, int cw) {
-        if constexpr (LEN) return co_resident(rec_len_kernel<BWD>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
+        if constexpr (LEN) return co_resident(rec_len_kernel<BWD, PK>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
         else return co_resident(rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
     });
     if (!q.ok) return SPARCH_EINVAL;
     // whole-sequence launches only (one agreement per launch)
     a.xcd_tab = q.whole && xcd_local_enabled() ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.chan) + hb) : nullptr;
     if constexpr (LEN) {
-        const RecLenKernel k = rec_len_kernel<BWD>(adapt, low, kgw, q.cw, a.save16 != 0);
+        if (PK && !q.whole) return SPARCH_EINVAL;
+        const RecLenKernelOf<PK> k = rec_len_kernel<BWD, PK>(adapt, low, kgw, q.cw, a.save16 != 0);
         return rec_plan::walk(q, BWD, [&](int rt0, int n_rt, int t0, int t1) {
             a.rt_base = rt0; a.n_rt_launch = n_rt; a.t_begin = t0; a.t_end = t1;
-            return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), with_lengths(a, sg, lengths), st);
+            return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), with_lengths<PK>(a, sg, lengths, offsets), st);
         });
     }
     const RecKernelOf<SG> k = rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, q.cw, a.save16 != 0);
@@ -1084,7 +1141,7 @@ int rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
                                    uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
                                    int save_bf16, uint32_t* spike_count, void* chan, size_t chan_bytes,
                                    uint32_t* status, int steps_per_launch, void* stream, int precision,
-                                   const int* lengths) {
+                                   const int* lengths, const int* offsets = nullptr) {
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
     // bf16 saved states cannot carry the exact state from one launch of a chunked forward to the next
@@ -1098,6 +1155,8 @@ int rec_cell_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
     r.vpack = reinterpret_cast<const u32x4*>(vpack);
     r.u_save = (float*)u_save; r.w_save = (float*)w_save; r.save16 = save_bf16 != 0;
     r.chan = (u64*)chan; r.status = status;
+    if (offsets)
+        return run_rec<false, false, false, true, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream, {}, lengths, offsets);
     if (lengths) return run_rec<false, false, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream, {}, lengths);
     return run_rec<false>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream);
 }
@@ -1131,6 +1190,22 @@ extern "C" int sparch_rec_cell_fwd_len(int kind, int B, int dirs, int T, int H, 
     return rec_cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, vpack, rec0, u0, w0, s0, theta, p_drop,
                         seed, s_out, s16_out, u_save, w_save, save_bf16, spike_count, chan, chan_bytes, status,
                         steps_per_launch, stream, precision, lengths);
+}
+
+extern "C" int sparch_rec_cell_fwd_pk(int kind, int B, int dirs, int T, int H, const float* Wx,
+                                      const float* scale, const float* shift, const float* alpha,
+                                      const float* beta, const float* a, const float* b,
+                                      const float* vpack, const float* rec0, const float* u0,
+                                      const float* w0, const float* s0, float theta, float p_drop,
+                                      uint64_t seed, float* s_out, uint16_t* s16_out, void* u_save, void* w_save,
+                                      int save_bf16, uint32_t* spike_count, const int* lengths, const int* offsets,
+                                      long long n_valid, void* chan, size_t chan_bytes, uint32_t* status,
+                                      int steps_per_launch, void* stream, int precision) {
+    SPARCH_ENTER();
+    if (!packed_ok(dirs, lengths, offsets, n_valid) || steps_per_launch < T) return SPARCH_EINVAL;
+    return rec_cell_fwd(kind, B, dirs, T, H, Wx, scale, shift, alpha, beta, a, b, vpack, rec0, u0, w0, s0, theta, p_drop,
+                        seed, s_out, s16_out, u_save, w_save, save_bf16, spike_count, chan, chan_bytes, status,
+                        steps_per_launch, stream, precision, lengths, offsets);
 }
 
 extern "C" int sparch_rec_cell_stream_fwd(int kind, int B, int dirs, int T, int H, const float* Wx,
@@ -1167,7 +1242,8 @@ int rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                       const float* bn_x, const float* bn_mean, const float* bn_invstd,
                                       void* chan, size_t chan_bytes, uint32_t* status,
                                       int steps_per_launch, int surrogate, float surrogate_scale, void* stream,
-                                      int precision, const int* lengths, long long n_valid) {
+                                      int precision, const int* lengths, long long n_valid,
+                                      const int* offsets = nullptr) {
     if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
@@ -1184,6 +1260,9 @@ int rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
     r.chan = (u64*)chan; r.status = status;
     if (lengths) {
         r.g_rate_scale = 1.0f / (float)n_valid;
+        if (offsets)
+            return run_rec<true, false, false, true, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream,
+                                                           SurrogateArgs{surrogate, surrogate_scale}, lengths, offsets);
         return run_rec<true, false, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream,
                                                  SurrogateArgs{surrogate, surrogate_scale}, lengths);
     }
@@ -1224,6 +1303,22 @@ extern "C" int sparch_rec_cell_bwd_len(int kind, int B, int dirs, int T, int H, 
     return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
                         s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
                         steps_per_launch, surrogate, surrogate_scale, stream, precision, lengths, n_valid);
+}
+extern "C" int sparch_rec_cell_bwd_pk(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                      const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                      const float* alpha, const float* beta, const float* a,
+                                      const float* b, const float* vpack_t, const float* u0,
+                                      const float* w0, const float* s0, float theta, float p_drop,
+                                      uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                                      const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                      const int* lengths, const int* offsets, long long n_valid, void* chan,
+                                      size_t chan_bytes, uint32_t* status, int steps_per_launch, int surrogate,
+                                      float surrogate_scale, void* stream, int precision) {
+    SPARCH_ENTER();
+    if (!packed_ok(dirs, lengths, offsets, n_valid) || steps_per_launch < T) return SPARCH_EINVAL;
+    return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
+                        s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
+                        steps_per_launch, surrogate, surrogate_scale, stream, precision, lengths, n_valid, offsets);
 }
 extern "C" int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                    const float* g_rate, const void* u_save, const void* w_save, int save_bf16,

@@ -93,13 +93,17 @@ class _SyntheticLoader:
 
 
 def parse_lengths_mode(value):
-    """SPARCH_LENGTHS: unset or empty -> False (the lengths are dropped, the reference's behaviour), "mask" -> True;
+    """SPARCH_LENGTHS: unset or empty -> False (the lengths are dropped, the reference's behaviour), "mask" -> True,
+    "pack" -> "pack" (the lengths go with the batch and the padded steps are skipped: SNN.forward(..., pack=True));
     anything else is refused."""
     if value is None or value == "":
         return False
     if value == "mask":
         return True
-    raise ValueError(f"SPARCH_LENGTHS={value!r}: the only value is 'mask' (unset: clips run to the batch's longest one)")
+    if value == "pack":
+        return "pack"
+    raise ValueError(f"SPARCH_LENGTHS={value!r}: the values are 'mask' and 'pack' (unset: clips run to the batch's "
+                     "longest one)")
 
 
 def parse_clip_grad(value):
@@ -138,11 +142,22 @@ class Experiment:
 
         # SPARCH_LENGTHS=mask: train, validation and test pass each batch's clip lengths to the network (ragged
         # batches, SNN.forward); unset: every clip runs to the batch's longest one, as in the reference
-        self.mask_lengths = parse_lengths_mode(os.environ.get("SPARCH_LENGTHS"))
-        if self.mask_lengths and self.sync_bn:
-            raise ValueError("sparch_amd: SPARCH_LENGTHS=mask with --sync_bn is not supported")
-        if self.mask_lengths and self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
-            raise ValueError(f"sparch_amd: SPARCH_LENGTHS=mask needs a spiking model (got {self.model_type})")
+        # SPARCH_LENGTHS=pack: the same, in the packed layout (the padded steps are skipped instead of masked)
+        self.lengths_mode = {False: None, True: "mask", "pack": "pack"}[parse_lengths_mode(os.environ.get("SPARCH_LENGTHS"))]
+        mode = self.lengths_mode
+        if mode and self.sync_bn:
+            raise ValueError(f"sparch_amd: SPARCH_LENGTHS={mode} with --sync_bn is not supported")
+        if mode and self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
+            raise ValueError(f"sparch_amd: SPARCH_LENGTHS={mode} needs a spiking model (got {self.model_type})")
+        if mode == "pack" and not self.use_pretrained_model:
+            if getattr(args, "bidirectional", False):
+                raise ValueError("sparch_amd: SPARCH_LENGTHS=pack with --bidirectional is not supported")
+            if self.model_type in ["RLIF", "RadLIF"] and Fn.rec_steps_per_launch(2) < 2:
+                raise ValueError("sparch_amd: SPARCH_LENGTHS=pack in the degraded step mode (one recurrent launch per time "
+                                 "step, SPARCH_REC_STEPS_PER_LAUNCH=1) is not supported (use SPARCH_LENGTHS=mask)")
+            if self.model_type in ["RLIF", "RadLIF"] and Fn.rec_step_path(getattr(args, "nb_hiddens", 0)):
+                raise ValueError(f"sparch_amd: SPARCH_LENGTHS=pack with recurrent layers above 1024 hidden units (got "
+                                 f"{args.nb_hiddens}) is not supported (use SPARCH_LENGTHS=mask)")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -410,11 +425,13 @@ class Experiment:
             yield xd, xlens, yd
 
     def _net(self, x, xlens):
-        """The network on one batch: with SPARCH_LENGTHS=mask the clips' lengths go with it."""
-        if not self.mask_lengths:
+        """The network on one batch: with SPARCH_LENGTHS=mask or pack the clips' lengths go with it."""
+        if self.lengths_mode is None:
             return self.net(x)
         if not getattr(self.net, "is_snn", False):
-            raise ValueError("sparch_amd: SPARCH_LENGTHS=mask needs a spiking model")
+            raise ValueError("sparch_amd: SPARCH_LENGTHS needs a spiking model")
+        if self.lengths_mode == "pack":
+            return self.net(x, lengths=xlens, pack=True)
         return self.net(x, lengths=xlens)
 
     def _mean_over_ranks(self, value):

@@ -756,6 +756,105 @@ def surrogate_args(surrogate):
     return SURROGATES[name], float(scale)
 
 
+class PackPlan(typing.NamedTuple):
+    """A packed ragged batch (snns.prepare_packing; DESIGN.md section 6, "Packed ragged batches"): the sequences sorted
+    by length, descending and stable.  order / lengths / offsets / inverse are int32 views of ONE device buffer: sequence j
+    is batch row order[j], has lengths[j] steps and owns packed rows [offsets[j], offsets[j] + lengths[j]); offsets has
+    batch + 1 entries and offsets[batch] = n; inverse[order[j]] = j.  t_max is the longest length, T the padded tensors'
+    time axis.  host: (order, lengths, offsets) as numpy arrays."""
+    order: torch.Tensor
+    lengths: torch.Tensor
+    offsets: torch.Tensor
+    inverse: torch.Tensor
+    n: int
+    t_max: int
+    batch: int
+    T: int
+    host: tuple
+
+    def args(self):
+        """(lengths, offsets, n_valid) as the `_pk` entry points take them."""
+        return ptr(self.lengths), ptr(self.offsets), int(self.n)
+
+
+def _pack_call(entry, src, dst, plan, C):
+    check(getattr(lib, entry)(plan.batch, plan.T, C, src.element_size(), ptr(src), ptr(dst), ptr(plan.order),
+                              ptr(plan.lengths), ptr(plan.offsets), int(plan.n), _stream()), entry)
+
+
+def pack_rows(x, plan):
+    """x (batch, T, C), elements of 1, 2 or 4 bytes -> (n, C): every sequence's own steps, in the plan's order."""
+    _require_device(x, "input")
+    x = x.contiguous()
+    B, T, C = x.shape
+    if (B, T) != (plan.batch, plan.T) or x.element_size() not in (1, 2, 4):
+        raise ValueError(f"pack_rows: a ({plan.batch}, {plan.T}, C) tensor of 1-, 2- or 4-byte elements (got "
+                         f"{tuple(x.shape)}, {x.dtype})")
+    out = torch.empty(plan.n, C, dtype=x.dtype, device=x.device)
+    tok = timer.start("pack_rows")
+    _pack_call("sparch_pack_rows", x, out, plan, C)
+    timer.stop(tok)
+    return out
+
+
+def unpack_rows(xp, plan):
+    """xp (n, C) -> (batch, T, C) in the caller's row order, exactly 0 on every row's steps t >= its length."""
+    _require_device(xp, "input")
+    xp = xp.contiguous()
+    if xp.ndim != 2 or xp.shape[0] != plan.n or xp.element_size() not in (1, 2, 4):
+        raise ValueError(f"unpack_rows: a ({plan.n}, C) tensor of 1-, 2- or 4-byte elements (got {tuple(xp.shape)}, {xp.dtype})")
+    out = torch.empty(plan.batch, plan.T, xp.shape[1], dtype=xp.dtype, device=xp.device)
+    tok = timer.start("unpack_rows")
+    _pack_call("sparch_unpack_rows", xp, out, plan, xp.shape[1])
+    timer.stop(tok)
+    return out
+
+
+class PackRowsFn(torch.autograd.Function):
+    """pack_rows with its gradient: unpack_rows (zero on the padding)."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return pack_rows(x, plan)
+
+    @staticmethod
+    def backward(ctx, g):
+        return unpack_rows(_f32c(g), ctx.plan), None
+
+
+class UnpackRowsFn(torch.autograd.Function):
+    """unpack_rows with its gradient: pack_rows (what arrives on the padding is dropped)."""
+
+    @staticmethod
+    def forward(ctx, xp, plan):
+        ctx.plan = plan
+        return unpack_rows(xp, plan)
+
+    @staticmethod
+    def backward(ctx, g):
+        return pack_rows(_f32c(g), ctx.plan), None
+
+
+def _check_packed(pack, dirs, recurrent, H):
+    """What the `_pk` kernels do not take."""
+    if pack is None:
+        return
+    if dirs != 1:
+        raise ValueError("sparch_amd: pack=True with bidirectional=True is not supported (the reverse direction would "
+                         "read each sequence's packed rows backwards: a change of its own)")
+    if recurrent and rec_step_path(H):
+        raise ValueError(f"sparch_amd: pack=True with a recurrent hidden size above 1024 (got {H}) is not supported "
+                         "(the per-step recurrent path takes no packed batches)")
+    if recurrent and rec_steps_per_launch(2) < 2:
+        raise ValueError("sparch_amd: pack=True in the degraded step mode (one recurrent launch per time step) is not "
+                         "supported: the packed recurrent kernels run whole sequences only")
+    if recurrent and isinstance(pack, PackPlan) and rec_steps_per_launch(pack.t_max) < pack.t_max:
+        raise ValueError(f"sparch_amd: pack=True with chunked recurrent launches (SPARCH_REC_STEPS_PER_LAUNCH="
+                         f"{rec_steps_per_launch(pack.t_max)} for sequences of up to {pack.t_max} steps) is not supported: "
+                         "the packed recurrent kernels run whole sequences only")
+
+
 def _check_ragged(lengths, dirs, recurrent, H):
     """What the `_len` kernels do not take."""
     if lengths is None:
@@ -769,7 +868,7 @@ def _check_ragged(lengths, dirs, recurrent, H):
 
 
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
-                 want_s_out=True, want_saves=True, surrogate=None, lengths=None):
+                 want_s_out=True, want_saves=True, surrogate=None, lengths=None, pack=None):
     """Run one spiking cell over the whole sequence on the device.
 
     Wx (B,T,H) raw projection (+ optional per-column scale/shift); u0/w0/s0 (B*dirs,H).
@@ -782,13 +881,16 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     14 bytes); `saved` is then (None, None).  surrogate: with a smooth form the saves stay fp32 whatever
     SPARCH_SAVE_DTYPE says — a bf16 save keeps the box-car's three decisions, not the u a smooth gate reads.
     lengths: None, or (device int32 (B,), their sum) of a ragged batch — the `_len` entry points then zero the output
-    spikes of every row's padded steps and leave them out of `count`."""
+    spikes of every row's padded steps and leave them out of `count`.
+    pack: None, or a PackPlan — Wx is then the packed (1, n, H) projection, B = 1, u0 / w0 / s0 hold the plan's `batch`
+    rows in its sorted order, and every (B,T,.) result above is (1, n, .): the `_pk` entry points."""
     _, T, H = Wx.shape
     Bp = B * dirs
     dev = Wx.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
     _check_ragged(lengths, dirs, recurrent, H)
+    _check_packed(pack, dirs, recurrent, H)
     len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
     # the same spikes as a bf16 0/1 plane for the GEMMs of the next layer (rows must stay 16-byte aligned)
     s16 = torch.empty(B, T, H * dirs, dtype=torch.bfloat16, device=dev)
@@ -806,7 +908,9 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     count = torch.zeros(H * dirs, dtype=torch.int32, device=dev)
     if not recurrent:
         tok = timer.start(f"cell_fwd[{kind}]")
-        entry = "sparch_cell_fwd" if lengths is None else "sparch_cell_fwd_len"
+        entry = "sparch_cell_fwd_pk" if pack is not None else "sparch_cell_fwd" if lengths is None else "sparch_cell_fwd_len"
+        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them)
+            B, T, len_args = pack.batch, pack.t_max, pack.args()
         check(getattr(lib, entry)(k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]),
                                   ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0), ptr(w0),
                                   ptr(s0), theta, p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save),
@@ -823,7 +927,7 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
             s_p, count_p, saved_p, s16_p = cell_forward(kind, padh(Wx), padh(scale), padh(shift), pp, padh(u0), padh(w0),
                                                         padh(s0), B=B, dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                         steps_per_launch=steps_per_launch, want_s_out=want_s_out,
-                                                        surrogate=surrogate, lengths=lengths)
+                                                        surrogate=surrogate, lengths=lengths, pack=pack)
             cut = lambda t_: None if t_ is None else t_.view(B, T, dirs, H4)[..., :H].reshape(B, T, dirs * H).contiguous()  # noqa: E731
             return (cut(s_p), count_p.view(dirs, H4)[:, :H].reshape(-1).contiguous(), saved_p, cut(s16_p))
         V = p["V"]
@@ -854,7 +958,11 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
         # t = 0 drive: s0 is uniform noise, not binary (snns.py:559/702): a (B', H, H) dense product, split-K so
         # that its 16 output tiles become a full grid (38 -> ~15 us at B' = 256, H = 1024)
         rec0 = _gemm_small(s0, vmask, nn=True)
-        _persistent(f"rec_cell_fwd[{kind}]", "sparch_rec_cell_fwd" if lengths is None else "sparch_rec_cell_fwd_len",
+        entry = "sparch_rec_cell_fwd_pk" if pack is not None else "sparch_rec_cell_fwd" if lengths is None else "sparch_rec_cell_fwd_len"
+        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them; whole sequences only)
+            B, T, Bp, len_args = pack.batch, pack.t_max, pack.batch, pack.args()
+            L = steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T)
+        _persistent(f"rec_cell_fwd[{kind}]", entry,
                     (k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]), ptr(p.get("beta")),
                      ptr(p.get("a")), ptr(p.get("b")), ptr(vpack), ptr(rec0), ptr(u0), ptr(w0), ptr(s0), theta, p_drop,
                      seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count), *len_args),
@@ -864,20 +972,22 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
 
 
 def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, theta, p_drop, seed,
-                  steps_per_launch=None, bn=None, surrogate=None, lengths=None):
+                  steps_per_launch=None, bn=None, surrogate=None, lengths=None, pack=None):
     """Reverse-time pass.  Returns dWx (B*dirs,T,H) [virtual rows, original time index],
     param grads dict (alpha[,beta,a,b][,V]) — plus, with bn = (Wx_raw (B,T,H), mean, invstd), the entry
     "bn_sums" = (dbeta, dgamma): BatchNorm backward's column sums, accumulated by the same kernel.
     surrogate: None or ("name", scale).  None / "boxcar" issue the calls they always did; a smooth form issues the
     `_sg` entry points with (id, scale) in front of the stream (timer labels unchanged).
     lengths: as in cell_forward — the `_len` entry points (one per family, any surrogate) take the incoming gradient of
-    a row's padded steps as zero, whatever g_out holds there; dWx is exactly 0 on them."""
+    a row's padded steps as zero, whatever g_out holds there; dWx is exactly 0 on them.
+    pack: as in cell_forward (B = 1, T = n: g_out, dWx and bn's projection are the packed (1, n, .) tensors)."""
     sg = surrogate_args(surrogate)
     Bp = B * dirs
     dev = g_out.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
     _check_ragged(lengths, dirs, recurrent, H)
+    _check_packed(pack, dirs, recurrent, H)
     len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
     sg_len = sg if sg is not None else (SURROGATES["boxcar"], 0.0)
     u_save, w_save = saved[0], saved[1]
@@ -889,13 +999,15 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         gr_p = None if g_rate is None else padh(g_rate.reshape(dirs, H)).reshape(dirs * H4)
         dWx_p, gp = cell_backward(kind, g_p, gr_p, pp, padh(u0), padh(w0), padh(s0), saved, B=B, dirs=dirs, T=T, H=H4,
                                   theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
-                                  surrogate=surrogate, lengths=lengths)
+                                  surrogate=surrogate, lengths=lengths, pack=pack)
         grads = {k_: (v[:H, :H].contiguous() if k_ == "V" else v[:H].contiguous()) for k_, v in gp.items()}
         return dWx_p[..., :H].contiguous(), grads
     vpack_fwd_made = saved[2] if len(saved) > 2 else None  # backward fragments of V packed by cell_forward
     save16 = u_save.dtype == torch.bfloat16
     dWx = torch.empty(Bp, T, H, dtype=torch.float32, device=dev)
     n_base = 6 if recurrent else 4
+    if pack is not None:  # (the kernels' B and T; the partial sums are per sequence)
+        B, T, Bp, len_args = pack.batch, pack.t_max, pack.batch, pack.args()
     ws = torch.empty(n_base + (2 if bn is not None else 0), Bp, H, dtype=torch.float32, device=dev)
     bn_x, bn_mean, bn_invstd = bn if bn is not None else (None, None, None)
     grads = {}
@@ -905,7 +1017,9 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                 ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
                 ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
                 ptr(bn_invstd))
-        if lengths is not None:
+        if pack is not None:
+            check(lib.sparch_cell_bwd_pk(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_pk")
+        elif lengths is not None:
             check(lib.sparch_cell_bwd_len(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_len")
         elif sg is None:
             check(lib.sparch_cell_bwd(*lead, _stream()), "sparch_cell_bwd")
@@ -914,7 +1028,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         timer.stop(tok)
     else:
         V = p["V"]
-        s_prev = torch.empty(Bp, T, H, dtype=torch.bfloat16, device=dev)  # bf16 0/1 plane
+        s_prev = torch.empty(dWx.shape, dtype=torch.bfloat16, device=dev)  # bf16 0/1 plane
         if rec_step_path(H):
             # reverse-time steps with dWx_{t+1} @ V^T between them (exact six-term split GEMM)
             vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
@@ -937,7 +1051,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
             timer.stop(tok)
         else:
             vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
-            entry = ("sparch_rec_cell_bwd_len" if lengths is not None
+            entry = ("sparch_rec_cell_bwd_pk" if pack is not None else "sparch_rec_cell_bwd_len" if lengths is not None
                      else "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg")
             _persistent(f"rec_cell_bwd[{kind}]", entry,
                         (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
@@ -946,14 +1060,16 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                          ptr(bn_invstd), *len_args),
                         lib.sparch_rec_chan_bytes(Bp, T, H), dev,
                         steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec(),
-                        sg=sg_len if lengths is not None else sg)
+                        sg=sg_len if (lengths is not None or pack is not None) else sg)
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
-        dV = gemm_tn(s_prev.view(Bp * T, H), dWx.view(Bp * T, H), zero_diag=True, spike_side=0, spike16=True)
+        dV = gemm_tn(s_prev.view(-1, H), dWx.view(-1, H), zero_diag=True, spike_side=0, spike16=True)
         for dd in range(dirs):  # s_prev rows of cell step 0 are zero: add the s0 term
             rows = slice(dd * B, (dd + 1) * B)
-            gemm_tn(s0[rows], dWx[rows, (T - 1) if dd else 0, :], zero_diag=True, out=dV)
+            first = (dWx[rows, (T - 1) if dd else 0, :] if pack is None  # (packed: every sequence's first row)
+                     else dWx.view(-1, H).index_select(0, pack.offsets[:pack.batch]))
+            gemm_tn(s0[rows], first, zero_diag=True, out=dV)
         grads["V"] = dV
     names = ["alpha"] + (["beta", "a", "b"] if adaptive else [])
     lims = [ALPHA_LIM] + ([BETA_LIM, A_LIM, B_LIM] if adaptive else [])
@@ -995,7 +1111,8 @@ class SpikingLayerFn(torch.autograd.Function):
                                                 dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                 want_s_out=cfg.get("fp32_out", True),
                                                 want_saves=any(ctx.needs_input_grad),
-                                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"))
+                                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
+                                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
         if s_out is None:
             s_out = spike_placeholder(B, T, H * dirs, x.device)
         inv_keep = 1.0 / (1.0 - p_drop)
@@ -1028,7 +1145,8 @@ class SpikingLayerFn(torch.autograd.Function):
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
                                 theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn,
-                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"))
+                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
+                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
         ctx.cell_saved = None
         dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
@@ -1052,10 +1170,14 @@ class ReadoutLayerFn(torch.autograd.Function):
             raise ValueError(f"sparch_amd: the readout kernels handle at most 256 classes (got {C})")
         inp = _layer_input(cfg, x, gated=False)
         Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1)  # snns.py:796, 799-801
-        out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        pack = cfg.get("pack")  # a PackPlan: x is the packed (1, n, K) batch, out and u0 hold the plan's sorted rows
+        out = torch.empty(B if pack is None else pack.batch, C, dtype=torch.float32, device=x.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
         lengths = cfg.get("lengths")
-        if lengths is None:
+        if pack is not None:
+            check(lib.sparch_readout_fwd_pk(pack.batch, pack.t_max, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0),
+                                            ptr(out), ptr(u_save), *pack.args(), _stream()), "sparch_readout_fwd_pk")
+        elif lengths is None:
             check(lib.sparch_readout_fwd(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
                                          ptr(u_save), _stream()), "sparch_readout_fwd")
         else:  # ragged: each row's truncated sum over its own steps
@@ -1079,11 +1201,16 @@ class ReadoutLayerFn(torch.autograd.Function):
         g_out = _f32c(g_out)
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         fuse = norm == "batchnorm"
+        pack = cfg.get("pack")
+        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them)
+            B, T = pack.batch, pack.t_max
         ws = torch.empty(3 if fuse else 1, B, C, dtype=torch.float32, device=dev)
         lead = (B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None, ptr(ctx.nsaved[0]) if fuse else None,
                 ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
         lengths = cfg.get("lengths")
-        if lengths is None:
+        if pack is not None:
+            check(lib.sparch_readout_bwd_pk(*lead, *pack.args(), _stream()), "sparch_readout_bwd_pk")
+        elif lengths is None:
             check(lib.sparch_readout_bwd(*lead, _stream()), "sparch_readout_bwd")
         else:
             check(lib.sparch_readout_bwd_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()), "sparch_readout_bwd_len")
@@ -1096,7 +1223,7 @@ class ReadoutLayerFn(torch.autograd.Function):
         dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx.view(M, C),
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
                                                   sums=sums)
-        dx = None if dx is None else dx.view(B, T, K)
+        dx = None if dx is None else dx.view(*ctx.shape[:3])
         ctx.inp = None
         return None, dx, dW, dWb, dnw, dnb, dalpha, None
 

@@ -483,7 +483,7 @@ class _SpikingLayer(nn.Module):
         return p
 
     # ------------------------------------------------------------------ forward
-    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None):
+    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None, pack=None):
         """Returns (spikes (B,T,H*(1+bidir)), firing_rate (H*(1+bidir),)).  Equivalent to the
         reference forward (e.g. snns.py:663-694) followed by `.mean(dim=(0,1))` (174).
         states: (u0, w0, s0) drawn ahead of time by SNN.forward (same generator, same order);
@@ -493,12 +493,16 @@ class _SpikingLayer(nn.Module):
         tensor is then a placeholder of the right shape whose VALUES ARE NOT WRITTEN (the spikes travel as the
         bf16 plane in its tag); SNN.forward uses it between its own layers.
         lengths: None, or what prepare_lengths() returned for this batch — the layer's output is then exactly 0 on
-        every row's padded steps and the firing rate is the mean over valid steps (SNN.forward has the contract)."""
+        every row's padded steps and the firing rate is the mean over valid steps (SNN.forward has the contract).
+        pack: None, or what prepare_packing() returned — x is then the PACKED batch (1, n, feat) (functional.pack_rows)
+        and so is the result; `states` hold the plan's `batch` rows in its sorted order (drawn so when not given)."""
         if lengths is not None:
             _check_ragged_layer(self, lengths)
+        if pack is not None:
+            _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
         dirs = 2 if self.bidirectional else 1
-        rows = x.shape[0] * dirs
+        rows = (x.shape[0] if pack is None else pack.batch) * dirs
         if self.batch_size != rows:
             self.batch_size = rows
         u0, w0, s0 = states if states is not None else self._draw_states(rows, x.device)
@@ -529,6 +533,8 @@ class _SpikingLayer(nn.Module):
         }
         if lengths is not None:  # (absent without lengths: the calls and their arguments are then what they always were)
             cfg["lengths"] = lengths
+        if pack is not None:
+            cfg["pack"] = pack
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         s, rate, s16 = Fn.SpikingLayerFn.apply(
@@ -608,13 +614,17 @@ class ReadoutLayer(nn.Module):
             self.norm = norm
         self.drop = nn.Dropout(p=dropout)
 
-    def forward(self, x, u0=None, lengths=None):
-        """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b]."""
+    def forward(self, x, u0=None, lengths=None, pack=None):
+        """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b].
+        pack: None, or prepare_packing()'s result — x is the packed batch (1, n, feat); out and u0 hold the plan's
+        `batch` rows in its sorted order."""
         if lengths is not None:
             _check_ragged_layer(self, lengths)
+        if pack is not None:
+            _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
         if u0 is None:
-            u0 = _rand_to(x.shape[0], self.hidden_size, x.device)  # snns.py:812
+            u0 = _rand_to(x.shape[0] if pack is None else pack.batch, self.hidden_size, x.device)  # snns.py:812
         is_bn = self.normalization == "batchnorm"
         in_scale, in_s16 = _spike_tag(x)
         cfg = {
@@ -628,6 +638,8 @@ class ReadoutLayer(nn.Module):
         }
         if lengths is not None:
             cfg["lengths"] = lengths
+        if pack is not None:
+            cfg["pack"] = pack
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         return Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
@@ -657,6 +669,52 @@ def prepare_lengths(lengths, batch, T, device):
         # forward (measured: 0.8 ms of a 6.4 ms step at BASELINE configs[2])
         lengths = lengths.pin_memory().to(device, non_blocking=True)
     return lengths.to(device), int(n_valid)
+
+
+def prepare_packing(lengths, batch, T, device):
+    """lengths as prepare_lengths takes them (and refuses them)  ->  the functional.PackPlan of the batch: the stable
+    descending order of the lengths, the sorted lengths, their exclusive prefix sum, n = sum(lengths) and the longest
+    length.  Made on the host (lengths on the device cost one read-back) and uploaded as one pinned buffer."""
+    import numpy as np
+
+    lengths = torch.as_tensor(lengths)
+    if lengths.ndim != 1 or lengths.shape[0] != batch or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+        raise ValueError(f"lengths: expected {batch} integers, one per batch row (got {tuple(lengths.shape)}, {lengths.dtype})")
+    host = lengths.detach().to("cpu", torch.int64).numpy()
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 1 or hi > T:
+        raise ValueError(f"lengths: every entry must be in [1, {T}] (got min {lo}, max {hi})")
+    order = np.argsort(-host, kind="stable")
+    lens = host[order]
+    n = int(lens.sum())
+    if n >= 2 ** 31:
+        raise ValueError(f"lengths: the packed batch has {n} rows, more than the int32 offsets hold")
+    buf = np.empty(4 * batch + 1, np.int32)
+    buf[:batch] = order
+    buf[batch:2 * batch] = lens
+    buf[2 * batch] = 0
+    np.cumsum(lens, out=buf[2 * batch + 1:3 * batch + 1])
+    buf[3 * batch + 1 + order] = np.arange(batch, dtype=np.int32)
+    flat = torch.from_numpy(buf)
+    if torch.device(device).type != "cpu":  # (pinned and non-blocking: see prepare_lengths)
+        flat = flat.pin_memory().to(device, non_blocking=True)
+    cut = lambda a, b: flat[a:b]  # noqa: E731
+    host_views = (buf[:batch], buf[batch:2 * batch], buf[2 * batch:3 * batch + 1])
+    return Fn.PackPlan(cut(0, batch), cut(batch, 2 * batch), cut(2 * batch, 3 * batch + 1), cut(3 * batch + 1, 4 * batch + 1),
+                       n, int(lens[0]), int(batch), int(T), host_views)
+
+
+def _check_packed_layer(layer, plan=None, x=None):
+    """What a layer refuses with pack=True; plan / x: also checked to be prepare_packing()'s and
+    the packed batch that goes with it."""
+    if plan is not None and not isinstance(plan, Fn.PackPlan):
+        raise ValueError("pack: pass what snns.prepare_packing() returns (SNN.forward(x, lengths, pack=True) does so itself)")
+    if plan is not None and x is not None and (x.ndim != 3 or x.shape[0] != 1 or x.shape[1] != plan.n):
+        raise ValueError(f"pack: the layer's input must be the packed batch (1, {plan.n}, features), got {tuple(x.shape)}")
+    Fn._check_packed(True if plan is None else plan, 2 if getattr(layer, "bidirectional", False) else 1, hasattr(layer, "V"),
+                     layer.hidden_size)
+    if Fn.SYNC_BN is not None and Fn.SYNC_BN["world"] > 1:
+        raise ValueError("sparch_amd: pack=True with --sync_bn is not supported")
 
 
 def _check_ragged_layer(layer, lengths=None):
@@ -694,7 +752,14 @@ class SNN(nn.Module):
     is then what the network gives for x[b:b+1, :lengths[b]] run on its own with the same initial-state rows (in train
     mode: with the same normalisation statistics, taken over the valid steps): hidden spikes are 0 on the padding, the
     readout sums over the row's own steps, firing rates are means over valid steps.  None: every row runs to `time`,
-    as the reference does."""
+    as the reference does.
+
+    pack=True (with lengths; DESIGN.md section 6, "Packed ragged batches"): the same contract, but the padded steps are
+    skipped instead of masked — the batch is packed to (sum(lengths), feat) rows, sorted by length, once; every layer runs
+    on packed tensors; out and the firing rates come back in the caller's row order (without a readout layer the spikes
+    are unpacked to (batch, time, feats) with zero tails).  x need not be zero on the padding: it is never read.
+    Differences from the masked mode: dropout masks are indexed by the position in the packed tensor, no state exists
+    for t >= lengths[b], and BatchNorm with use_bias=True is accepted."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
@@ -805,12 +870,14 @@ class SNN(nn.Module):
                     fill(w0)
                 fill(s0)
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, pack=False):
         if self.reshape:
             if x.ndim == 4:
                 x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
             else:
                 raise NotImplementedError
+        if pack:
+            return self._forward_packed(x, lengths)
         if lengths is not None:  # (the refusals come before anything else, the device check included)
             if getattr(self, "_static_states", None) is not None:
                 raise ValueError("sparch_amd: lengths inside a captured step (GraphedTrainStep) is not supported: the "
@@ -847,5 +914,48 @@ class SNN(nn.Module):
                 if wait is not None:
                     wait()  # (no-op once the first layer's call has waited)
                 rates.append(r)
+        firing_rates = torch.cat(rates) if len(rates) > 1 else rates[0]
+        return x, firing_rates
+
+    def _forward_packed(self, x, lengths):
+        """forward(x, lengths, pack=True): the batch packed once, every layer on packed tensors, the results back in the
+        caller's row order (class docstring)."""
+        if lengths is None:
+            raise ValueError("sparch_amd: pack=True needs lengths (the packed layout is made from them)")
+        if getattr(self, "_static_states", None) is not None:
+            raise ValueError("sparch_amd: pack=True inside a captured step (GraphedTrainStep) is not supported: the "
+                             "lengths, their order and their sum change with every batch")
+        for layer in self.snn:  # every refusal before the first kernel
+            _check_packed_layer(layer)
+        batch, T = x.shape[0], x.shape[1]
+        plan = prepare_packing(lengths, batch, T, x.device)
+        for layer in self.snn:  # (what depends on the batch's longest sequence: chunked recurrent launches)
+            _check_packed_layer(layer, plan)
+        Fn._require_device(x, "input")
+        tag = Fn.input_plane_of(x)
+        if tag is not None:  # input_from_counts: the bf16 plane is the data, x a placeholder without values
+            plane = Fn.pack_rows(tag[0].view(batch, T, -1), plan)
+            x = Fn.spike_placeholder(1, plan.n, x.shape[2], x.device).view(1, plan.n, x.shape[2])
+            x._sparch_input_plane = (tuple(x.shape), plane, tag[1])
+        else:
+            if x.element_size() not in (1, 2, 4):
+                x = x.float()
+            x = Fn.PackRowsFn.apply(x, plan).unsqueeze(0)
+        # the draws are the padded forward's (same generator, same order, one row per batch row); each sequence takes
+        # its own row with it
+        states = self.draw_states(batch, x.device)
+        states.wait_ready()
+        take = lambda t_: None if t_ is None else t_.index_select(0, plan.order)  # noqa: E731
+        last = self.num_layers - 1
+        rates = []
+        for i, layer in enumerate(self.snn):
+            if self.use_readout_layer and i == last:
+                x = layer(x, u0=take(states[i]), pack=plan).index_select(0, plan.inverse)
+            else:
+                inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
+                x, r = layer.forward_with_rate(x, states=tuple(take(t_) for t_ in states[i]), fp32_out=not inner, pack=plan)
+                rates.append(r)
+        if not self.use_readout_layer:
+            x = Fn.UnpackRowsFn.apply(x.reshape(plan.n, -1), plan)
         firing_rates = torch.cat(rates) if len(rates) > 1 else rates[0]
         return x, firing_rates

@@ -454,8 +454,10 @@ class StreamingSNN(_Stream):
             for i, t in enumerate(taps):
                 self._spike_tap(i, t)
 
-    def step(self, x_chunk, lengths=None):
+    def step(self, x_chunk, lengths=None, pack=False):
         """x_chunk (B,Tc,C) float32, or uint8 spike counts, on the device; any Tc >= 1."""
+        if pack:
+            raise ValueError("sparch_amd: pack=True is not supported by the streaming classes (StreamingSNN)")
         if lengths is not None:  # (a stream ends when its caller stops feeding it: DESIGN.md section 7)
             raise ValueError("sparch_amd: lengths are not supported by the streaming classes (StreamingSNN)")
         self._ensure()

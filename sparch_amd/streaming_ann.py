@@ -206,8 +206,10 @@ class StreamingANN(_Stream):
                 L.y, L.y_alt = L.y_alt, L.y
         self._parity ^= 1
 
-    def step(self, x_chunk, lengths=None):
+    def step(self, x_chunk, lengths=None, pack=False):
         """x_chunk (B,Tc,C) float32 (or uint8 counts, converted here) on the device, 4-D when net.reshape; Tc >= 1."""
+        if pack:
+            raise ValueError("sparch_amd: pack=True is not supported by the streaming classes (StreamingANN)")
         if lengths is not None:  # (DESIGN.md section 7)
             raise ValueError("sparch_amd: lengths are not supported by the streaming classes (StreamingANN)")
         self._ensure()
