@@ -665,6 +665,39 @@ int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* 
                           const float* bn_mean, const float* bn_invstd, const float* u_save,
                           const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
                           const int* lengths, const int* offsets, long long n_valid, void* stream);
+/* Per-step readout ("Per-step readout"): the `_seq` forms also give the readout's value after
+ * every step, seq (B,T,C), and take a gradient per step, g_seq (B,T,C).  seq_mode selects what a step's row is:
+ *   SPARCH_SEQ_PROB  seq[b,t,:] = softmax(u_t);                       the gradient of p_t is G_t = fp32(g_out + g_seq[t])
+ *   SPARCH_SEQ_SUM   seq[b,t,:] = sum_{t' <= t} softmax(u_t'), the accumulator of `out` after adding step t (the same
+ *                    sequential fp32 sum in time order: seq[:, T-1] == out, and row t is what
+ *                    sparch_readout_stream_fwd holds after t + 1 steps, bit for bit);  G_t = fp32(g_out + S_t) with the
+ *                    reverse running sum S_t = fp32(S_{t+1} + g_seq[t]), S_T = 0, taken sequentially in fp32 per class
+ * out, u_save, dWx and dalpha_ws are those of the plain forms (e_t = p_t (G_t - <p_t, G_t>), then the same reverse
+ * recurrence).  g_out may be NULL (counts as 0).  The `_len` forms: seq[b,t,:] is written as 0 for t >= lengths[b] (in
+ * both modes; the caller need not clear it), g_seq is not read there — whatever it holds, a NaN included — and S starts
+ * from 0 at the row's own last step.  There is no packed form.  SPARCH_EINVAL, before any device work, for seq == NULL,
+ * g_seq == NULL, seq_mode outside {0, 1}, C > 256 and whatever the plain forms refuse.                           */
+#define SPARCH_SEQ_PROB 0
+#define SPARCH_SEQ_SUM 1
+int sparch_readout_fwd_seq(int B, int T, int C, const float* Wx, const float* scale,
+                           const float* shift, const float* alpha, const float* u0, float* out,
+                           float* u_save, float* seq, int seq_mode, void* stream);
+int sparch_readout_bwd_seq(int B, int T, int C, const float* g_out, const float* g_seq, int seq_mode,
+                           const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                           const float* u_save, const float* alpha, const float* u0, float* dWx,
+                           float* dalpha_ws, void* stream);
+int sparch_readout_fwd_seq_len(int B, int T, int C, const float* Wx, const float* scale,
+                               const float* shift, const float* alpha, const float* u0, float* out,
+                               float* u_save, float* seq, int seq_mode, const int* lengths,
+                               long long n_valid, void* stream);
+int sparch_readout_bwd_seq_len(int B, int T, int C, const float* g_out, const float* g_seq, int seq_mode,
+                               const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                               const float* u_save, const float* alpha, const float* u0, float* dWx,
+                               float* dalpha_ws, const int* lengths, long long n_valid, void* stream);
+/* Time steps per LDS chunk of the readout kernels for a (T, C) problem — what the launchers above pass as `rows`:
+ * bwd 0 the forward kernels, 1 the backward; seq 0 the plain / ragged / packed forms, 1 the `_seq` forms (whose backward
+ * holds one more chunk image).  Host only, no device work; 0 for T <= 0, C <= 0 or C > 256.                     */
+int sparch_readout_chunk_steps(int T, int C, int bwd, int seq);
 
 /* ------------------------------------------------------------------------------------
  * G9  mel filterbank front-end  (replaces torchaudio.compliance.kaldi.fbank(x,

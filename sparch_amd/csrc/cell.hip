@@ -393,6 +393,16 @@ struct RoCursor {
 };
 __device__ __forceinline__ const int* ro_offsets() { return nullptr; }
 __device__ __forceinline__ const int* ro_offsets(const int* offsets) { return offsets; }
+// Per-step readout (sparch_readout_*_seq): the trailing argument of the `_seq` kernels, in the place of the packed
+// form's offsets.  mode: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM.
+struct RoSeq { float* seq; int mode; };          // forward: the per-step output (B,T,C)
+struct RoGSeq { const float* g_seq; int mode; }; // backward: the per-step incoming gradient (B,T,C)
+template <class S> __device__ __forceinline__ const int* ro_offsets(S) { return nullptr; }
+template <class S, class... A> constexpr bool ro_has = (std::is_same_v<S, A> || ...);
+template <class S, class... A> __device__ __forceinline__ S ro_seq([[maybe_unused]] A... a) {
+    if constexpr (ro_has<S, A...>) return (a, ...);
+    else return S{nullptr, 0};
+}
 // (ro_softmax_row: common.h — the streaming step's readout kernel, streamstep.hip, shares it)
 
 // STREAM (sparch_readout_stream_fwd): `u_io` (B,C) is the membrane state, read in place of u0 and written back behind
@@ -402,6 +412,10 @@ __device__ __forceinline__ const int* ro_offsets(const int* offsets) { return of
 // truncated sum over t < lengths[b], what the clip run alone gives; u_save is not written past it.
 // Offsets (sparch_readout_fwd_pk, with LEN: one more argument, `const int* offsets`): the packed layout — the row's steps
 // are rows [offsets[b], offsets[b] + lengths[b]) of Wx / u_save (N,C), and its buffer resources end at its own last step.
+// RoSeq (sparch_readout_fwd_seq / _seq_len: one more argument, `RoSeq`, never with Offsets): the chunk image also goes
+// out as seq[b, c0 + t, :] by a thread = element pass behind the sum — in PROB mode as the softmax phase left it, in SUM
+// mode after the sum phase has put its accumulator back in place of every p_t it added (the accumulator of `out`
+// itself: seq[b, t] is out after t + 1 steps).  With LEN the rows t >= lengths[b] of seq are written as 0.
 // (A trailing parameter pack: the kernels without it keep the argument list they had.)
 template <bool STREAM, bool LEN = false, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C, int rows, const float* __restrict__ Wx,
@@ -411,9 +425,11 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
                                                             const float* __restrict__ u0, float* __restrict__ out,
                                                             float* __restrict__ u_save, float* u_io,
                                                             const int* __restrict__ lengths, Offsets... pk) {
-    constexpr bool PK = sizeof...(Offsets) == 1;
+    constexpr bool PK = ro_has<const int*, Offsets...>, SEQ = ro_has<RoSeq, Offsets...>;
     static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
+    static_assert(!(SEQ && STREAM), "the per-step output belongs to the whole-sequence forms");
     [[maybe_unused]] const int* offsets = ro_offsets(pk...);
+    [[maybe_unused]] const RoSeq sq = ro_seq<RoSeq>(pk...);
     __shared__ float us[RO_FWD_FLOATS];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -430,6 +446,10 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     float acc = STREAM ? out[(size_t)b * C + cp] : 0.f;
     const __amdgpu_buffer_rsrc_t rx = PK ? ro_row(Wx, (size_t)C, offsets[b], Tb) : ro_row(Wx, (size_t)T * C, b),
                                  ru = PK ? ro_row(u_save, (size_t)C, offsets[b], Tb) : ro_row(u_save, (size_t)T * C, b);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rs = ro_row(sq.seq, (size_t)T * C, b);
+    if constexpr (SEQ && LEN) {  // thread = element: the padded tail of seq
+        for (int idx = Tb * C + tid; idx < T * C; idx += RO_NT) ro_store(0.f, rs, (unsigned)((size_t)idx * sizeof(float)));
+    }
     for (int c0 = 0; c0 < Tb; c0 += rows) {
         const int len = min(rows, Tb - c0), n = len * C;
         // thread = element: the chunk's projection -> LDS
@@ -490,19 +510,45 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
         ro_barrier();
         // thread = class: out += softmax(u_t) in time order             // snns.py:823
         if (wave_has_class) {
-            const float* p = us + cc;
+            std::conditional_t<SEQ, float, const float>* p = us + cc;
+            [[maybe_unused]] const bool put = SEQ && sq.mode == SPARCH_SEQ_SUM;  // the running sum replaces p_t
             int t0 = 0;
             for (; t0 + 8 <= len; t0 += 8) {
                 float pv[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pv[j] = p[j * CS];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc = acc + pv[j];
+                for (int j = 0; j < 8; ++j) {
+                    acc = acc + pv[j];
+                    if constexpr (SEQ) { if (put) p[j * CS] = acc; }
+                }
                 p += 8 * CS;
             }
-            for (; t0 < len; ++t0, p += CS) acc = acc + *p;
+            for (; t0 < len; ++t0, p += CS) {
+                acc = acc + *p;
+                if constexpr (SEQ) { if (put) *p = acc; }
+            }
         }
         ro_barrier();
+        if constexpr (SEQ) {
+            // thread = element: the chunk image -> seq[b, c0 ..], the staging sweep run backwards
+            RoCursor cur(tid, C);
+            for (int base = 0; base < n; base += RO_NT * RO_LPT) {
+                float v[RO_LPT];
+#pragma unroll
+                for (int k = 0; k < RO_LPT; ++k) {
+                    const int idx = base + tid + RO_NT * k;
+                    v[k] = us[idx < n ? cur.t * CS + cur.c : C];
+                    cur.next();
+                }
+#pragma unroll
+                for (int k = 0; k < RO_LPT; ++k) {
+                    const int idx = base + tid + RO_NT * k;
+                    ro_store(v[k], rs, idx < n ? (unsigned)(((size_t)c0 * C + idx) * sizeof(float)) : RO_OOB);
+                }
+            }
+            ro_barrier();  // (the next chunk's staging sweep overwrites the image)
+        }
     }
     if (act) out[(size_t)b * C + cc] = acc;
     if (STREAM && act) u_io[(size_t)b * C + cc] = u;
@@ -515,6 +561,11 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
 // Three chunk images in LDS: u (overwritten by e), u_{t-1} - u_t, and BatchNorm's xhat of the raw projection.
 // LEN (sparch_readout_bwd_len): the reverse recurrence starts at the row's last valid step; dWx past it is written as 0.
 // Offsets (sparch_readout_bwd_pk, with LEN): packed rows as in the forward; there is no tail of dWx to write.
+// RoGSeq (sparch_readout_bwd_seq / _seq_len: one more argument, `RoGSeq`, never with Offsets): the gradient of p_t is per
+// step, G_t = g + A_t, with a fourth chunk image for A: g_seq[t] as staged (PROB), or the reverse running sum
+// S_t = S_{t+1} + g_seq[t] (SUM), which a thread = class reverse pass in front of the thread = time phase puts in place of
+// g_seq[t]; S lives in a register across the chunks, which already run in reverse, and starts from 0 at the row's last
+// step — g_seq behind it is never read.  g_out may be null (g = 0).
 extern __shared__ __attribute__((aligned(16))) float ro_dyn_lds[];
 template <bool LEN, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C, int rows, const float* __restrict__ g_out,
@@ -526,9 +577,10 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                                                             const float* __restrict__ bn_mean,
                                                             const float* __restrict__ bn_invstd,
                                                             const int* __restrict__ lengths, Offsets... pk) {
-    constexpr bool PK = sizeof...(Offsets) == 1;
+    constexpr bool PK = ro_has<const int*, Offsets...>, SEQ = ro_has<RoGSeq, Offsets...>;
     static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
     [[maybe_unused]] const int* offsets = ro_offsets(pk...);
+    [[maybe_unused]] const RoGSeq sq = ro_seq<RoGSeq>(pk...);
     __shared__ float gs[RO_NT];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -537,13 +589,17 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     float* const ue = ro_dyn_lds;            // [rows][CS] u_t, then e_t
     float* const dl = ue + rows * CS;        // [rows][CS] u_{t-1} - u_t
     float* const xh = dl + rows * CS;        // [rows][CS] xhat_t
+    [[maybe_unused]] float* const ga = xh + rows * CS;  // SEQ: [rows][CS] g_seq[t], then S_t (SUM), then G_t
     const bool act = tid < C;
     const bool wave_has_class = (tid & ~63) < C;
     const int cc = act ? tid : C;
     const int cp = act ? tid : 0;
     const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;  // (neuron.h: this copy stays)
+    if constexpr (SEQ) gs[tid] = (act && g_out) ? g_out[(size_t)b * C + cp] : 0.f;
+    else
     gs[tid] = act ? g_out[(size_t)b * C + cp] : 0.f;
     float du = 0.f, acc = 0.f;
+    [[maybe_unused]] float S = 0.f;  // SEQ, SUM mode: sum of g_seq[t'] over the steps t' behind the current one
     // BatchNorm backward's column sums folded in (nullable): sum_t dWx and sum_t dWx*xhat per (row, class)
     const bool bn = bn_x != nullptr;
     float acc_dy = 0.f, acc_dyx = 0.f;
@@ -551,6 +607,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                                  rb = PK ? ro_row(bn_x, (size_t)C, offsets[b], Tb) : ro_row(bn_x, (size_t)T * C, b),
                                  rd = PK ? ro_row(dWx, (size_t)C, offsets[b], Tb) : ro_row(dWx, (size_t)T * C, b),
                                  r0 = ro_row(u0, (size_t)C, b);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rg = ro_row(sq.g_seq, (size_t)T * C, b);
     if constexpr (LEN && !PK) {  // thread = element: the padded tail of dWx
         for (int idx = Tb * C + tid; idx < T * C; idx += RO_NT) ro_store(0.f, rd, (unsigned)((size_t)idx * sizeof(float)));
     }
@@ -563,6 +620,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
             constexpr int LPT = RO_LPT / 2;
             for (int base = 0; base < n; base += RO_NT * LPT) {
                 float vu[LPT], vx[LPT];
+                [[maybe_unused]] float vg[LPT];
                 unsigned vp[LPT], v0[LPT];
 #pragma unroll
                 for (int k = 0; k < LPT; ++k) {
@@ -574,6 +632,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                     vx[k] = ro_load(rb, in ? (unsigned)(e * sizeof(float)) : RO_OOB);
                     vp[k] = __builtin_amdgcn_raw_buffer_load_b32(ru, (in && !first) ? (unsigned)((e - C) * sizeof(float)) : RO_OOB, 0, 0);
                     v0[k] = __builtin_amdgcn_raw_buffer_load_b32(r0, first ? (unsigned)(e * sizeof(float)) : RO_OOB, 0, 0);
+                    if constexpr (SEQ) vg[k] = ro_load(rg, in ? (unsigned)(e * sizeof(float)) : RO_OOB);
                 }
 #pragma unroll
                 for (int k = 0; k < LPT; ++k) {
@@ -583,22 +642,60 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                     ue[at] = vu[k];
                     dl[at] = __uint_as_float(vp[k] | v0[k]) - vu[k];   // exactly one of the two loads was in range
                     xh[at] = bn ? (vx[k] - bn_mean[cl]) * bn_invstd[cl] : 0.f;
+                    if constexpr (SEQ) ga[at] = vg[k];
                     cur.next();
                 }
             }
         }
         ro_barrier();
+        if constexpr (SEQ) {
+            // thread = class: g_seq[t] -> S_t in place, in reverse time order (one sequential fp32 sum per class)
+            if (sq.mode == SPARCH_SEQ_SUM) {
+                if (wave_has_class) {
+                    float* q = ga + (len - 1) * CS + cc;
+                    int left = len;
+                    for (; left >= 8; left -= 8) {
+                        float gv[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) gv[j] = q[-j * CS];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            S = S + gv[j];
+                            q[-j * CS] = S;
+                        }
+                        q -= 8 * CS;
+                    }
+                    for (; left > 0; --left, q -= CS) {
+                        S = S + *q;
+                        *q = S;
+                    }
+                }
+                ro_barrier();
+            }
+        }
         // thread = time: e_t in place
         for (int tl = tid; tl < len; tl += RO_NT) {
             float* row = ue + tl * CS;
             const float den = ro_softmax_row(row, C);
             float dot = 0.f;
+            if constexpr (SEQ) {
+                float* grow = ga + tl * CS;
+                for (int c = 0; c < C; ++c) {
+                    const float pc = row[c] / den;
+                    const float G = gs[c] + grow[c];
+                    row[c] = pc;
+                    grow[c] = G;
+                    dot += pc * G;
+                }
+                for (int c = 0; c < C; ++c) row[c] = row[c] * (grow[c] - dot);
+            } else {
             for (int c = 0; c < C; ++c) {
                 const float pc = row[c] / den;
                 row[c] = pc;
                 dot += pc * gs[c];
             }
             for (int c = 0; c < C; ++c) row[c] = row[c] * (gs[c] - dot);
+            }
         }
         ro_barrier();
         // thread = class: reverse recurrence (groups of 8 steps without predicates, then the ragged rest)
@@ -941,12 +1038,23 @@ extern "C" int sparch_cell_bwd(int kind, int B, int dirs, int T, int H, const fl
 }
 
 namespace {
+bool seq_mode_ok(int mode) { return mode == SPARCH_SEQ_PROB || mode == SPARCH_SEQ_SUM; }
+
+// seq: the `_seq` forms' per-step output with its mode (never with offsets), else null
 int readout_fwd(int B, int T, int C, const float* Wx, const float* scale, const float* shift, const float* alpha,
-                const float* u0, float* out, float* u_save, const int* lengths, const int* offsets, void* stream) {
+                const float* u0, float* out, float* u_save, const int* lengths, const int* offsets, void* stream,
+                const RoSeq* seq = nullptr) {
     if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
     if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    if (seq && (!seq->seq || !seq_mode_ok(seq->mode) || offsets)) return SPARCH_EINVAL;
     const int rows = ro_chunk_steps(T, C, RO_FWD_FLOATS);
-    if (offsets)
+    if (seq && lengths)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, true, RoSeq>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C, rows,
+                           Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths, *seq);
+    else if (seq)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, false, RoSeq>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C, rows,
+                           Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, (const int*)nullptr, *seq);
+    else if (offsets)
         hipLaunchKernelGGL((readout_fwd_kernel<false, true, const int*>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
                            rows, Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths, offsets);
     else if (lengths)
@@ -959,22 +1067,28 @@ int readout_fwd(int B, int T, int C, const float* Wx, const float* scale, const 
     return SPARCH_OK;
 }
 
-// offsets: none, or the packed form's `const int* offsets`
+// offsets: none, the packed form's `const int* offsets`, or the per-step form's `RoGSeq` (one chunk image more)
 template <bool LEN, class... Offsets>
 int readout_bwd(int B, int T, int C, const float* g_out, const float* bn_x, const float* bn_mean, const float* bn_invstd,
                 const float* u_save, const float* alpha, const float* u0, float* dWx, float* dalpha_ws, const int* lengths,
                 void* stream, Offsets... offsets) {
     // (dalpha uses u_{t-1}-x_t = (u_{t-1}-u_t)/(1-alpha): the projection is re-read only for BatchNorm's sums)
-    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || !g_out || !u_save || !alpha || !u0 || !dWx || !dalpha_ws)
+    constexpr bool SEQ = ro_has<RoGSeq, Offsets...>;
+    constexpr int images = SEQ ? 4 : 3;
+    if (B <= 0 || T <= 0 || C <= 0 || C > 256 || (!g_out && !SEQ) || !u_save || !alpha || !u0 || !dWx || !dalpha_ws)
         return SPARCH_EINVAL;
     if (bn_x && (!bn_mean || !bn_invstd)) return SPARCH_EINVAL;
-    const int rows = ro_chunk_steps(T, C, RO_BWD_FLOATS / 3);
+    if constexpr (SEQ) {
+        const RoGSeq sq = (offsets, ...);
+        if (!sq.g_seq || !seq_mode_ok(sq.mode)) return SPARCH_EINVAL;
+    }
+    const int rows = ro_chunk_steps(T, C, RO_BWD_FLOATS / images);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_bwd_kernel<LEN, Offsets...>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        (int)(RO_BWD_FLOATS * sizeof(float)));
     if (attr != hipSuccess) { sparch_note_hip_error((int)attr); return SPARCH_ELAUNCH; }
     hipLaunchKernelGGL((readout_bwd_kernel<LEN, Offsets...>), dim3(B), dim3(RO_NT),
-                       (size_t)3 * rows * ro_row_stride(C) * sizeof(float), (hipStream_t)stream, B, T, C, rows, g_out, u_save,
+                       (size_t)images * rows * ro_row_stride(C) * sizeof(float), (hipStream_t)stream, B, T, C, rows, g_out, u_save,
                        alpha, u0, dWx, dalpha_ws, bn_x, bn_mean, bn_invstd, lengths, offsets...);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
@@ -1033,6 +1147,50 @@ extern "C" int sparch_readout_bwd_len(int B, int T, int C, const float* g_out, c
     SPARCH_ENTER();
     if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
     return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream);
+}
+
+// The per-step forms (include/sparch_hip.h).  They stand in front of sparch_readout_bwd_pk so that its kernel stays the
+// last one this file emits: the per-symbol device-code digest sees the padding behind a kernel.
+extern "C" int sparch_readout_fwd_seq(int B, int T, int C, const float* Wx, const float* scale,
+                                      const float* shift, const float* alpha, const float* u0, float* out,
+                                      float* u_save, float* seq, int seq_mode, void* stream) {
+    SPARCH_ENTER();
+    const RoSeq sq{seq, seq_mode};
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, nullptr, nullptr, stream, &sq);
+}
+
+extern "C" int sparch_readout_fwd_seq_len(int B, int T, int C, const float* Wx, const float* scale,
+                                          const float* shift, const float* alpha, const float* u0, float* out,
+                                          float* u_save, float* seq, int seq_mode, const int* lengths,
+                                          long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
+    const RoSeq sq{seq, seq_mode};
+    return readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, nullptr, stream, &sq);
+}
+
+extern "C" int sparch_readout_bwd_seq(int B, int T, int C, const float* g_out, const float* g_seq, int seq_mode,
+                                      const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                      const float* u_save, const float* alpha, const float* u0, float* dWx,
+                                      float* dalpha_ws, void* stream) {
+    SPARCH_ENTER();
+    return readout_bwd<false>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, nullptr, stream,
+                              RoGSeq{g_seq, seq_mode});
+}
+
+extern "C" int sparch_readout_bwd_seq_len(int B, int T, int C, const float* g_out, const float* g_seq, int seq_mode,
+                                          const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                          const float* u_save, const float* alpha, const float* u0, float* dWx,
+                                          float* dalpha_ws, const int* lengths, long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!ragged_ok(1, lengths, n_valid)) return SPARCH_EINVAL;
+    return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream,
+                             RoGSeq{g_seq, seq_mode});
+}
+
+extern "C" int sparch_readout_chunk_steps(int T, int C, int bwd, int seq) {
+    if (T <= 0 || C <= 0 || C > 256) return 0;
+    return ro_chunk_steps(T, C, bwd ? RO_BWD_FLOATS / (seq ? 4 : 3) : RO_FWD_FLOATS);
 }
 
 extern "C" int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* bn_x,

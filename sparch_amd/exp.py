@@ -120,6 +120,53 @@ def parse_clip_grad(value):
     return c
 
 
+def parse_per_step_loss(value):
+    """SPARCH_PER_STEP_LOSS=w[:t0]: unset or empty -> None; else (w, t0) with the weight w a finite number > 0 and the
+    first step t0 an integer >= 0 (default 0); anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    head, sep, tail = value.strip().partition(":")
+    try:
+        w = float(head)
+        t0 = int(tail) if sep else 0
+    except ValueError:
+        w, t0 = float("nan"), 0
+    if not (0 < w < float("inf")) or t0 < 0:
+        raise ValueError(f"SPARCH_PER_STEP_LOSS={value!r}: w[:t0] with a weight w > 0 and a first step t0 >= 0 "
+                         "(an integer; default 0)")
+    return w, t0
+
+
+def _step_lengths(seq, lengths):
+    B, T = seq.shape[0], seq.shape[1]
+    if lengths is None:
+        return torch.full((B,), T, dtype=torch.long, device=seq.device)
+    return torch.as_tensor(lengths).to(device=seq.device, dtype=torch.long)
+
+
+def per_step_nll(seq_sum, y, lengths=None, t0=0):
+    """Loss on early decisions.  seq_sum (B,T,C): the readout's running sum (SNN.forward(..., per_step="sum")), y (B,)
+    labels, lengths (B,) or None (every clip has T steps).  seq_sum[b,t] / (t + 1) is a distribution over the classes
+    (a mean of softmaxes); returns the mean, over the pairs (b, t) with t0 <= t < lengths[b], of its negative log at
+    the label — 0 if there is no such pair."""
+    B, T, _ = seq_sum.shape
+    steps = torch.arange(T, device=seq_sum.device)
+    at_label = seq_sum.gather(2, y.view(B, 1, 1).expand(B, T, 1)).squeeze(2) / (steps + 1).to(seq_sum.dtype)
+    valid = (steps[None, :] >= t0) & (steps[None, :] < _step_lengths(seq_sum, lengths)[:, None])
+    nll = -torch.log(torch.where(valid, at_label, torch.ones_like(at_label)).clamp_min(torch.finfo(seq_sum.dtype).tiny))
+    return nll.sum() / valid.sum().clamp_min(1).to(seq_sum.dtype)
+
+
+def decision_steps(seq_sum, y, lengths=None):
+    """(B,) integers: per clip the earliest step t from which argmax seq_sum[b, t'] is the label for ALL t' with
+    t <= t' < lengths[b]; a clip whose last step is still wrong never settles and counts at lengths[b]."""
+    T = seq_sum.shape[1]
+    steps = torch.arange(T, device=seq_sum.device)
+    valid = steps[None, :] < _step_lengths(seq_sum, lengths)[:, None]
+    wrong = (seq_sum.argmax(dim=2) != y[:, None]) & valid
+    return (wrong.long() * (steps + 1)[None, :]).amax(dim=1)  # one past the last wrong step (0: right from the start)
+
+
 class Experiment:
     """Training / testing of spiking networks on the four speech-command datasets."""
 
@@ -158,6 +205,16 @@ class Experiment:
             if self.model_type in ["RLIF", "RadLIF"] and Fn.rec_step_path(getattr(args, "nb_hiddens", 0)):
                 raise ValueError(f"sparch_amd: SPARCH_LENGTHS=pack with recurrent layers above 1024 hidden units (got "
                                  f"{args.nb_hiddens}) is not supported (use SPARCH_LENGTHS=mask)")
+
+        # SPARCH_PER_STEP_LOSS=w[:t0]: the training loss gains w x per_step_nll on the readout's running sum from step
+        # t0 on, and validation / test log the mean decision step ("Per-step readout")
+        self.per_step_loss = parse_per_step_loss(os.environ.get("SPARCH_PER_STEP_LOSS"))
+        if self.per_step_loss is not None:
+            if mode == "pack":
+                raise ValueError("sparch_amd: SPARCH_PER_STEP_LOSS with SPARCH_LENGTHS=pack is not supported (the per-step "
+                                 "readout has no packed form; use SPARCH_LENGTHS=mask)")
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
+                raise ValueError(f"sparch_amd: SPARCH_PER_STEP_LOSS needs a spiking model (got {self.model_type})")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -425,7 +482,12 @@ class Experiment:
             yield xd, xlens, yd
 
     def _net(self, x, xlens):
-        """The network on one batch: with SPARCH_LENGTHS=mask or pack the clips' lengths go with it."""
+        """The network on one batch: with SPARCH_LENGTHS=mask or pack the clips' lengths go with it; with
+        SPARCH_PER_STEP_LOSS the readout's running sum comes back as a third value."""
+        if self.per_step_loss is not None:
+            if not getattr(self.net, "is_snn", False):
+                raise ValueError("sparch_amd: SPARCH_PER_STEP_LOSS needs a spiking model")
+            return self.net(x, lengths=None if self.lengths_mode is None else xlens, per_step="sum")
         if self.lengths_mode is None:
             return self.net(x)
         if not getattr(self.net, "is_snn", False):
@@ -447,6 +509,7 @@ class Experiment:
         if hasattr(getattr(self.train_loader, "sampler", None), "set_epoch"):
             self.train_loader.sampler.set_epoch(e)  # per-rank shards of a fresh permutation every epoch
         losses, accs, sizes = [], [], []
+        early_losses = []  # SPARCH_PER_STEP_LOSS: the per-step term of every batch (unweighted)
         epoch_spike_rate = 0
         seen = 0
         # No host round trip inside the loop: the reference's per-step `.item()` / `.cpu()`
@@ -454,9 +517,13 @@ class Experiment:
         # values, the same float64 means — and the kernels' status word is checked at the same point.
         for step, (x, xlens, y) in enumerate(self._prefetched(self.train_loader)):
             x, y = self._to_device(x, y)
-            output, firing_rates = self._net(x, xlens)
+            output, firing_rates, *seq = self._net(x, xlens)
             loss_val = self.loss_fn(output, y)
             losses.append(loss_val.detach())
+            if seq:
+                early = per_step_nll(seq[0], y, None if self.lengths_mode is None else xlens, self.per_step_loss[1])
+                early_losses.append(early.detach())
+                loss_val = loss_val + self.per_step_loss[0] * early
             if self.net.is_snn:
                 epoch_spike_rate += torch.mean(firing_rates)
                 if self.use_regularizers:
@@ -480,6 +547,9 @@ class Experiment:
         logging.info(f"Epoch {e}: lr={self.opt.param_groups[-1]['lr']}")
         logging.info(f"Epoch {e}: train loss={self._mean_over_ranks(np.mean(losses))}")
         logging.info(f"Epoch {e}: train acc={self._mean_over_ranks(np.mean(accs))}")
+        if early_losses:
+            early = torch.stack(early_losses).cpu().numpy().astype(np.float64)
+            logging.info(f"Epoch {e}: train per-step loss={self._mean_over_ranks(np.mean(early))}")
         if self.clip_grad is not None:
             s = self.opt.clip_stats()
             self.opt.reset_clip_stats()  # (per-epoch figures)
@@ -523,12 +593,16 @@ class Experiment:
 
     def _eval_epoch(self, loader, retried=False):
         losses, accs, sizes = [], [], []
+        decided = []  # SPARCH_PER_STEP_LOSS: the sum of the clips' decision steps, per batch
+        self.decision_step = None
         epoch_spike_rate = 0
         step = 0
         for step, (x, xlens, y) in enumerate(self._prefetched(loader)):
             x, y = self._to_device(x, y)
-            output, firing_rates = self._net(x, xlens)
+            output, firing_rates, *seq = self._net(x, xlens)
             losses.append(self.loss_fn(output, y).detach())
+            if seq:
+                decided.append(decision_steps(seq[0], y, None if self.lengths_mode is None else xlens).sum())
             pred = torch.argmax(output, dim=1)
             accs.append((y == pred).sum())
             sizes.append(y.shape[0])
@@ -542,6 +616,8 @@ class Experiment:
             return self._eval_epoch(loader, retried=True)
         losses = torch.stack(losses).cpu().numpy().astype(np.float64) if losses else np.zeros(0)
         accs = (torch.stack(accs).cpu().numpy().astype(np.float64) / np.asarray(sizes, np.float64)) if accs else np.zeros(0)
+        if decided:  # the mean over the clips of the epoch
+            self.decision_step = self._mean_over_ranks(float(torch.stack(decided).sum().item()) / max(sum(sizes), 1))
         if self.net.is_snn:
             epoch_spike_rate /= step  # sic (exp.py:449, 515)
         return (self._mean_over_ranks(np.mean(losses)), self._mean_over_ranks(np.mean(accs)), epoch_spike_rate)
@@ -552,6 +628,8 @@ class Experiment:
             valid_loss, valid_acc, rate = self._eval_epoch(self.valid_loader)
             logging.info(f"Epoch {e}: valid loss={valid_loss}")
             logging.info(f"Epoch {e}: valid acc={valid_acc}")
+            if self.decision_step is not None:
+                logging.info(f"Epoch {e}: valid mean decision step={self.decision_step}")
             if self.net.is_snn:
                 logging.info(f"Epoch {e}: valid mean act rate={rate}")
             self.scheduler.step(valid_acc)
@@ -572,6 +650,8 @@ class Experiment:
             test_loss, test_acc, rate = self._eval_epoch(test_loader)
             logging.info(f"Test loss={test_loss}")
             logging.info(f"Test acc={test_acc}")
+            if self.decision_step is not None:
+                logging.info(f"Test mean decision step={self.decision_step}")
             if self.net.is_snn:
                 logging.info(f"Test mean act rate={rate}")
             logging.info("\n-----------------------------\n")

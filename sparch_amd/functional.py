@@ -1157,8 +1157,23 @@ class SpikingLayerFn(torch.autograd.Function):
                 pg.get("V"), None, None, None)
 
 
+SEQ_MODES = {"prob": 0, "sum": 1}  # per-step readout: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM
+
+
+def seq_mode(per_step):
+    """per_step (None, "prob" or "sum") -> None or the C ABI's seq_mode."""
+    if per_step is None:
+        return None
+    if not isinstance(per_step, str) or per_step not in SEQ_MODES:
+        raise ValueError(f"sparch_amd: per_step must be None, 'prob' or 'sum' (got {per_step!r})")
+    return SEQ_MODES[per_step]
+
+
 class ReadoutLayerFn(torch.autograd.Function):
-    """x (B,T,K) -> out (B,C): softmax-sum readout (snns.py:793-825)."""
+    """x (B,T,K) -> out (B,C): softmax-sum readout (snns.py:793-825).
+
+    With cfg["per_step"] ("prob" / "sum"; DESIGN.md section 6, "Per-step readout") -> (out, seq): seq (B,T,C) is
+    softmax(u_t), or the running sum of `out` after every step; its gradient reaches the kernel as g_seq."""
 
     @staticmethod
     def forward(ctx, cfg, x, W, Wb, nw, nb, alpha, u0):
@@ -1174,7 +1189,19 @@ class ReadoutLayerFn(torch.autograd.Function):
         out = torch.empty(B if pack is None else pack.batch, C, dtype=torch.float32, device=x.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
         lengths = cfg.get("lengths")
-        if pack is not None:
+        mode = seq_mode(cfg.get("per_step"))
+        if mode is not None:
+            if pack is not None:
+                raise ValueError("sparch_amd: the per-step readout has no packed form (per_step with pack)")
+            seq = torch.empty(B, T, C, dtype=torch.float32, device=x.device)  # (every element is written: no clear)
+            lead = (B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out), ptr(u_save), ptr(seq), mode)
+            if lengths is None:
+                check(lib.sparch_readout_fwd_seq(*lead, _stream()), "sparch_readout_fwd_seq")
+            else:
+                check(lib.sparch_readout_fwd_seq_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()),
+                      "sparch_readout_fwd_seq_len")
+            ctx.set_materialize_grads(False)  # a loss on one of the two outputs: no zero tensor for the other
+        elif pack is not None:
             check(lib.sparch_readout_fwd_pk(pack.batch, pack.t_max, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0),
                                             ptr(out), ptr(u_save), *pack.args(), _stream()), "sparch_readout_fwd_pk")
         elif lengths is None:
@@ -1188,17 +1215,22 @@ class ReadoutLayerFn(torch.autograd.Function):
         ctx.shape = (B, T, K, C)
         ctx.nsaved = nsaved
         ctx.save_for_backward(inp.x2, W, nw, alpha, u0, u_save, Wx_raw)
-        return out
+        return out if mode is None else (out, seq)
 
     @staticmethod
-    def backward(ctx, g_out):
+    def backward(ctx, g_out, g_seq=None):
         cfg = ctx.cfg
         norm = cfg["normalization"]
         B, T, K, C = ctx.shape
         x2, W, nw, alpha, u0, u_save, Wx_raw = ctx.saved_tensors
         M = B * T
         dev = x2.device
-        g_out = _f32c(g_out)
+        mode = seq_mode(cfg.get("per_step"))
+        if g_seq is None:
+            mode = None  # nothing came back through seq: the plain kernels
+            if g_out is None:
+                g_out = torch.zeros(B, C, dtype=torch.float32, device=dev)
+        g_out = None if g_out is None else _f32c(g_out)
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         fuse = norm == "batchnorm"
         pack = cfg.get("pack")
@@ -1208,7 +1240,14 @@ class ReadoutLayerFn(torch.autograd.Function):
         lead = (B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None, ptr(ctx.nsaved[0]) if fuse else None,
                 ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
         lengths = cfg.get("lengths")
-        if pack is not None:
+        if mode is not None:
+            lead = lead[:4] + (ptr(_f32c(g_seq)), mode) + lead[4:]
+            if lengths is None:
+                check(lib.sparch_readout_bwd_seq(*lead, _stream()), "sparch_readout_bwd_seq")
+            else:
+                check(lib.sparch_readout_bwd_seq_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()),
+                      "sparch_readout_bwd_seq_len")
+        elif pack is not None:
             check(lib.sparch_readout_bwd_pk(*lead, *pack.args(), _stream()), "sparch_readout_bwd_pk")
         elif lengths is None:
             check(lib.sparch_readout_bwd(*lead, _stream()), "sparch_readout_bwd")

@@ -614,10 +614,16 @@ class ReadoutLayer(nn.Module):
             self.norm = norm
         self.drop = nn.Dropout(p=dropout)
 
-    def forward(self, x, u0=None, lengths=None, pack=None):
+    def forward(self, x, u0=None, lengths=None, pack=None, per_step=None):
         """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b].
         pack: None, or prepare_packing()'s result — x is the packed batch (1, n, feat); out and u0 hold the plan's
-        `batch` rows in its sorted order."""
+        `batch` rows in its sorted order.
+        per_step: None — returns out (batch, classes) — or "prob" / "sum" — returns (out, seq) with seq (batch, time,
+        classes) = softmax(u_t), or the running sum of `out` after step t (seq[:, -1] is out); with lengths, seq is 0
+        at t >= lengths[b].  Both are differentiable.  Not with pack."""
+        Fn.seq_mode(per_step)
+        if per_step is not None and pack is not None:
+            raise ValueError("sparch_amd: per_step with pack is not supported (the per-step readout has no packed form)")
         if lengths is not None:
             _check_ragged_layer(self, lengths)
         if pack is not None:
@@ -640,6 +646,8 @@ class ReadoutLayer(nn.Module):
             cfg["lengths"] = lengths
         if pack is not None:
             cfg["pack"] = pack
+        if per_step is not None:
+            cfg["per_step"] = per_step
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         return Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
@@ -759,7 +767,13 @@ class SNN(nn.Module):
     on packed tensors; out and the firing rates come back in the caller's row order (without a readout layer the spikes
     are unpacked to (batch, time, feats) with zero tails).  x need not be zero on the padding: it is never read.
     Differences from the masked mode: dropout masks are indexed by the position in the packed tensor, no state exists
-    for t >= lengths[b], and BatchNorm with use_bias=True is accepted."""
+    for t >= lengths[b], and BatchNorm with use_bias=True is accepted.
+
+    per_step="prob" / "sum" ("Per-step readout"; needs a readout layer, not with pack): forward
+    returns THREE values, (out, firing_rates, seq): seq (batch, time, classes) is the readout after every step —
+    softmax(u_t), or the running sum whose last step is `out` (row t is what StreamingSNN.step returns after t + 1
+    steps).  With lengths, seq[b, t] is 0 for t >= lengths[b].  A loss may use out, seq or both.  per_step=None (the
+    default): the two values above, nothing else changes."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
@@ -870,7 +884,14 @@ class SNN(nn.Module):
                     fill(w0)
                 fill(s0)
 
-    def forward(self, x, lengths=None, pack=False):
+    def forward(self, x, lengths=None, pack=False, per_step=None):
+        if per_step is not None:  # (the refusals come before anything else)
+            Fn.seq_mode(per_step)
+            if pack:
+                raise ValueError("sparch_amd: per_step with pack=True is not supported (the per-step readout has no "
+                                 "packed form)")
+            if not self.use_readout_layer:
+                raise ValueError("sparch_amd: per_step needs a readout layer (use_readout_layer=True)")
         if self.reshape:
             if x.ndim == 4:
                 x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
@@ -904,7 +925,10 @@ class SNN(nn.Module):
             if self.use_readout_layer and i == last:
                 if wait is not None:
                     wait()
-                x = layer(x, u0=states[i]) if lengths is None else layer(x, u0=states[i], lengths=lengths)
+                if per_step is not None:
+                    x, seq = layer(x, u0=states[i], lengths=lengths, per_step=per_step)
+                else:
+                    x = layer(x, u0=states[i]) if lengths is None else layer(x, u0=states[i], lengths=lengths)
             else:
                 # between two layers of ours the spikes travel as a bf16 plane: no fp32 copy (unless somebody
                 # else may look at the layer's output: forward hooks, the network's own output)
@@ -915,6 +939,8 @@ class SNN(nn.Module):
                     wait()  # (no-op once the first layer's call has waited)
                 rates.append(r)
         firing_rates = torch.cat(rates) if len(rates) > 1 else rates[0]
+        if per_step is not None:
+            return x, firing_rates, seq
         return x, firing_rates
 
     def _forward_packed(self, x, lengths):
