@@ -698,6 +698,40 @@ int sparch_readout_bwd_seq_len(int B, int T, int C, const float* g_out, const fl
  * bwd 0 the forward kernels, 1 the backward; seq 0 the plain / ragged / packed forms, 1 the `_seq` forms (whose backward
  * holds one more chunk image).  Host only, no device work; 0 for T <= 0, C <= 0 or C > 256.                     */
 int sparch_readout_chunk_steps(int T, int C, int bwd, int seq);
+/* Selectable readout ("Selectable readout"): the `_red` forms take the reduction over time.  With
+ * T_b = lengths[b] (T without lengths) and the recurrence, u_save and the layouts of the forms above:
+ *   SPARCH_RED_SOFTMAX_SUM   out = sum_{t < T_b} softmax(u_t): the entry points above, called as they are (same bits)
+ *   SPARCH_RED_SOFTMAX_MEAN  that fp32 accumulator divided once by (float)T_b;           backward: g / (float)T_b for g
+ *   SPARCH_RED_U_MAX         out[b,c] = max_{t < T_b} u_t[c], the earliest t on a tie, u0 no candidate; arg (B,C) int32 is
+ *                            that t — the step inside the row's own sequence, also in the packed layout — written by the
+ *                            forward and read by the backward, which puts g[c] into du at t = arg[b,c] and nothing else
+ *   SPARCH_RED_U_MEAN        (...((u_0 + u_1) + u_2)...) / (float)T_b, one fp32 chain;   backward: g / (float)T_b at every t
+ *   SPARCH_RED_U_LAST        u_{T_b - 1};                                                backward: g at t = T_b - 1
+ * lengths NULL: every row has T steps (offsets and n_valid are then not looked at beyond the refusals below); lengths
+ * alone: the `_len` layout; lengths and offsets: the `_pk` layout.  arg may be NULL unless red is U_MAX.  dWx behind a
+ * row's end is written as 0 (padded layout).  SPARCH_EINVAL, before any device work: red outside 0..4, arg NULL with
+ * U_MAX, offsets without lengths, n_valid < 1 with lengths, C > 256, and whatever the forms above refuse.
+ * sparch_readout_stream_fwd_red: the streaming form.  `out` carries the accumulator in and out: the un-normalised
+ * softmax sum (SOFTMAX_SUM and SOFTMAX_MEAN: the kernel of sparch_readout_stream_fwd), the running maximum (U_MAX: the
+ * caller starts it at -inf), the un-normalised sum of u_t (U_MEAN) or u itself (U_LAST).  The caller keeps the step
+ * count and divides; after the last chunk that equals sparch_readout_fwd_red over the whole sequence bit for bit.   */
+#define SPARCH_RED_SOFTMAX_SUM 0
+#define SPARCH_RED_SOFTMAX_MEAN 1
+#define SPARCH_RED_U_MAX 2
+#define SPARCH_RED_U_MEAN 3
+#define SPARCH_RED_U_LAST 4
+int sparch_readout_fwd_red(int B, int T, int C, const float* Wx, const float* scale,
+                           const float* shift, const float* alpha, const float* u0, float* out,
+                           float* u_save, int red, int* arg, const int* lengths, const int* offsets,
+                           long long n_valid, void* stream);
+int sparch_readout_bwd_red(int B, int T, int C, const float* g_out, const float* bn_x,
+                           const float* bn_mean, const float* bn_invstd, const float* u_save,
+                           const float* alpha, const float* u0, float* dWx, float* dalpha_ws, int red,
+                           const int* arg, const int* lengths, const int* offsets, long long n_valid,
+                           void* stream);
+int sparch_readout_stream_fwd_red(int B, int T, int C, const float* Wx, const float* scale,
+                                  const float* shift, const float* alpha, float* u, float* out, int red,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------
  * G9  mel filterbank front-end  (replaces torchaudio.compliance.kaldi.fbank(x,

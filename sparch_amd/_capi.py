@@ -134,6 +134,9 @@ PROTOTYPES = {
     "sparch_readout_fwd_seq_len": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P, c_longlong, P]),
     "sparch_readout_bwd_seq_len": (c_int, [c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P, P, P, P, c_longlong, P]),
     "sparch_readout_chunk_steps": (c_int, [c_int, c_int, c_int, c_int]),
+    "sparch_readout_fwd_red": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P, P, P, c_longlong, P]),
+    "sparch_readout_bwd_red": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, P, P, P, c_longlong, P]),
+    "sparch_readout_stream_fwd_red": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, c_int, P]),
     "sparch_stream_step_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P,
                                        P, P, P, P, P, c_float, P, P]),
     "sparch_stream_step_readout": (c_int, [c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),

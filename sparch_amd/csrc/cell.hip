@@ -398,6 +398,31 @@ __device__ __forceinline__ const int* ro_offsets(const int* offsets) { return of
 struct RoSeq { float* seq; int mode; };          // forward: the per-step output (B,T,C)
 struct RoGSeq { const float* g_seq; int mode; }; // backward: the per-step incoming gradient (B,T,C)
 template <class S> __device__ __forceinline__ const int* ro_offsets(S) { return nullptr; }
+template <class S> __device__ __forceinline__ const int* ro_offsets(const int* offsets, S) { return offsets; }
+// Selectable readout (sparch_readout_*_red): a trailing argument too, alone or behind the packed form's offsets.  The
+// reduction over time M (SPARCH_RED_*) is a template argument — each mode is a kernel of its own, and the kernels without
+// the argument are the softmax-sum.  arg (B,C): u_max's step of the maximum, written by the forward, read by the backward.
+template <int M> struct RoRed { int* arg; };
+template <class S> struct ro_red_of { static constexpr int value = -1; };
+template <int M> struct ro_red_of<RoRed<M>> { static constexpr int value = M; };
+template <class... A> constexpr int ro_red_mode() {
+    int m = SPARCH_RED_SOFTMAX_SUM;
+    ((m = ro_red_of<A>::value >= 0 ? ro_red_of<A>::value : m), ...);
+    return m;
+}
+template <class S> __device__ __forceinline__ int* ro_arg1(S, int* r) { return r; }
+template <int M> __device__ __forceinline__ int* ro_arg1(RoRed<M> red, int*) { return red.arg; }
+template <class... A> __device__ __forceinline__ int* ro_red_arg([[maybe_unused]] A... a) {
+    int* r = nullptr;
+    ((r = ro_arg1(a, r)), ...);
+    return r;
+}
+// the direct gradient e_t of a membrane mode at step t: gc is g (u_max, u_last) or g / T_b (u_mean)
+template <int M> __device__ __forceinline__ float ro_red_e(float gc, int t, int arg_t, int t_last) {
+    if constexpr (M == SPARCH_RED_U_MAX) return t == arg_t ? gc : 0.f;
+    else if constexpr (M == SPARCH_RED_U_LAST) return t == t_last ? gc : 0.f;
+    else return gc;
+}
 template <class S, class... A> constexpr bool ro_has = (std::is_same_v<S, A> || ...);
 template <class S, class... A> __device__ __forceinline__ S ro_seq([[maybe_unused]] A... a) {
     if constexpr (ro_has<S, A...>) return (a, ...);
@@ -416,6 +441,13 @@ template <class S, class... A> __device__ __forceinline__ S ro_seq([[maybe_unuse
 // out as seq[b, c0 + t, :] by a thread = element pass behind the sum — in PROB mode as the softmax phase left it, in SUM
 // mode after the sum phase has put its accumulator back in place of every p_t it added (the accumulator of `out`
 // itself: seq[b, t] is out after t + 1 steps).  With LEN the rows t >= lengths[b] of seq are written as 0.
+// RoRed<M> (sparch_readout_fwd_red / _stream_fwd_red: one more argument, last; never with RoSeq): the reduction over time.
+//   SOFTMAX_MEAN  the kernel above with one division of the accumulator by (float)T_b at the final store
+//   U_MAX / U_MEAN / U_LAST  the membrane modes: no softmax phase, no sum phase and neither of their barriers; the
+//       recurrence phase (thread = class) keeps the running maximum with its step (strict >: the earliest wins; u0 is no
+//       candidate), or the sequential sum of u_t, in registers, and does not write u_t back to LDS — nobody reads it.
+//   With STREAM the accumulator is carried in `out` as above: the running maximum (the caller starts it at -inf), the
+//   un-normalised sum of u_t (the caller divides by its step count), or nothing (u_last: out = u); arg is not written.
 // (A trailing parameter pack: the kernels without it keep the argument list they had.)
 template <bool STREAM, bool LEN = false, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C, int rows, const float* __restrict__ Wx,
@@ -426,10 +458,14 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
                                                             float* __restrict__ u_save, float* u_io,
                                                             const int* __restrict__ lengths, Offsets... pk) {
     constexpr bool PK = ro_has<const int*, Offsets...>, SEQ = ro_has<RoSeq, Offsets...>;
-    static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
+    constexpr int RED = ro_red_mode<Offsets...>();
+    constexpr bool MEMB = RED >= SPARCH_RED_U_MAX;  // a reduction of the membrane itself
+    static_assert(sizeof...(Offsets) <= 1 + (PK && RED != 0) && (!PK || LEN), "packed rows carry their lengths");
     static_assert(!(SEQ && STREAM), "the per-step output belongs to the whole-sequence forms");
+    static_assert(!(SEQ && RED != 0), "the per-step output is the softmax-sum's");
     [[maybe_unused]] const int* offsets = ro_offsets(pk...);
     [[maybe_unused]] const RoSeq sq = ro_seq<RoSeq>(pk...);
+    [[maybe_unused]] int* const arg = ro_red_arg(pk...);
     __shared__ float us[RO_FWD_FLOATS];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -443,7 +479,8 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
     const bool has_bn = scale != nullptr;
     const float sc = has_bn ? scale[cp] : 1.0f, sh = has_bn ? shift[cp] : 0.0f;
     float u = STREAM ? u_io[(size_t)b * C + cp] : u0[(size_t)b * C + cp];
-    float acc = STREAM ? out[(size_t)b * C + cp] : 0.f;
+    float acc = STREAM ? out[(size_t)b * C + cp] : RED == SPARCH_RED_U_MAX ? -INFINITY : 0.f;
+    [[maybe_unused]] int amax = 0;  // U_MAX: the step of acc
     const __amdgpu_buffer_rsrc_t rx = PK ? ro_row(Wx, (size_t)C, offsets[b], Tb) : ro_row(Wx, (size_t)T * C, b),
                                  ru = PK ? ro_row(u_save, (size_t)C, offsets[b], Tb) : ro_row(u_save, (size_t)T * C, b);
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rs = ro_row(sq.seq, (size_t)T * C, b);
@@ -486,21 +523,26 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     u = readout_step(u, neuron_input(x[j], false, 0.f, has_bn, sc, sh), p.al, p.oma);
-                    q[j * CS] = u;
+                    if constexpr (!MEMB) q[j * CS] = u;
                     ro_store(u, ru, go + j * gstep);
+                    if constexpr (RED == SPARCH_RED_U_MAX) { if (u > acc) { acc = u; amax = c0 + t0 + j; } }
+                    if constexpr (RED == SPARCH_RED_U_MEAN) acc = acc + u;
                 }
                 q += 8 * CS;
                 go += 8 * gstep;
             }
             for (; t0 < len; ++t0) {
                 u = readout_step(u, neuron_input(*q, false, 0.f, has_bn, sc, sh), p.al, p.oma);
-                *q = u;
+                if constexpr (!MEMB) *q = u;
                 ro_store(u, ru, go);
+                if constexpr (RED == SPARCH_RED_U_MAX) { if (u > acc) { acc = u; amax = c0 + t0; } }
+                if constexpr (RED == SPARCH_RED_U_MEAN) acc = acc + u;
                 q += CS;
                 go += gstep;
             }
         }
-        ro_barrier();
+        ro_barrier();  // (membrane modes: the chunk's only other barrier — the next staging sweep overwrites the image)
+        if constexpr (!MEMB) {
         // thread = time: softmax over classes, in place
         for (int tl = tid; tl < len; tl += RO_NT) {
             float* row = us + tl * CS;
@@ -530,6 +572,7 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
             }
         }
         ro_barrier();
+        }
         if constexpr (SEQ) {
             // thread = element: the chunk image -> seq[b, c0 ..], the staging sweep run backwards
             RoCursor cur(tid, C);
@@ -550,7 +593,10 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
             ro_barrier();  // (the next chunk's staging sweep overwrites the image)
         }
     }
+    if constexpr (RED == SPARCH_RED_U_LAST) acc = u;
+    if constexpr (!STREAM && (RED == SPARCH_RED_SOFTMAX_MEAN || RED == SPARCH_RED_U_MEAN)) acc = acc / (float)Tb;
     if (act) out[(size_t)b * C + cc] = acc;
+    if constexpr (!STREAM && RED == SPARCH_RED_U_MAX) { if (act) arg[(size_t)b * C + cc] = amax; }
     if (STREAM && act) u_io[(size_t)b * C + cc] = u;
 }
 
@@ -566,6 +612,11 @@ __global__ __launch_bounds__(RO_NT) void readout_fwd_kernel(int B, int T, int C,
 // S_t = S_{t+1} + g_seq[t] (SUM), which a thread = class reverse pass in front of the thread = time phase puts in place of
 // g_seq[t]; S lives in a register across the chunks, which already run in reverse, and starts from 0 at the row's last
 // step — g_seq behind it is never read.  g_out may be null (g = 0).
+// RoRed<M> (sparch_readout_bwd_red: one more argument, last; never with RoGSeq): SOFTMAX_MEAN is the kernel above with
+// g / (float)T_b in place of g.  The membrane modes have no thread = time phase: e_t is a select on the step (u_max: g at
+// t = arg[b,c]; u_last: g at t = T_b - 1) or the constant g / (float)T_b (u_mean), formed in the reverse recurrence from
+// registers.  The u image has no reader then and is not staged (its LDS stays allotted: the chunks are the plain
+// kernel's); u_{t-1} - u_t and xhat are staged as above, for dalpha and BatchNorm's sums.
 extern __shared__ __attribute__((aligned(16))) float ro_dyn_lds[];
 template <bool LEN, class... Offsets>
 __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C, int rows, const float* __restrict__ g_out,
@@ -578,9 +629,13 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                                                             const float* __restrict__ bn_invstd,
                                                             const int* __restrict__ lengths, Offsets... pk) {
     constexpr bool PK = ro_has<const int*, Offsets...>, SEQ = ro_has<RoGSeq, Offsets...>;
-    static_assert(sizeof...(Offsets) <= 1 && (!PK || LEN), "packed rows carry their lengths");
+    constexpr int RED = ro_red_mode<Offsets...>();
+    constexpr bool MEMB = RED >= SPARCH_RED_U_MAX;
+    static_assert(sizeof...(Offsets) <= 1 + (PK && RED != 0) && (!PK || LEN), "packed rows carry their lengths");
+    static_assert(!(SEQ && RED != 0), "the per-step gradient is the softmax-sum's");
     [[maybe_unused]] const int* offsets = ro_offsets(pk...);
     [[maybe_unused]] const RoGSeq sq = ro_seq<RoGSeq>(pk...);
+    [[maybe_unused]] const int* const arg = ro_red_arg(pk...);
     __shared__ float gs[RO_NT];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -595,6 +650,19 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     const int cc = act ? tid : C;
     const int cp = act ? tid : 0;
     const float al = clampf(alpha[cp], SP_ALPHA_LO, SP_ALPHA_HI), oma = 1.0f - al;  // (neuron.h: this copy stays)
+    [[maybe_unused]] float gc = 0.f;   // RED: this class's g, over (float)T_b in the mean modes
+    [[maybe_unused]] int arg_t = 0;    // U_MAX: the step that takes it
+    if constexpr (RED != 0) {
+        gc = act ? g_out[(size_t)b * C + cp] : 0.f;
+        if constexpr (RED == SPARCH_RED_SOFTMAX_MEAN || RED == SPARCH_RED_U_MEAN) gc = gc / (float)Tb;
+        // (through a buffer resource like the rows: with a flat load of arg, hipcc held dWx's resource in VGPRs in the
+        // <false, RoRed<U_MAX>> instantiation and wrapped every dWx store in a waterfall loop, 35 us for 22 — seen in the
+        // ISA, the reason not established; lanes past the classes read 0 and carry gc = 0)
+        if constexpr (RED == SPARCH_RED_U_MAX)
+            arg_t = (int)__builtin_amdgcn_raw_buffer_load_b32(ro_row(reinterpret_cast<const float*>(arg), (size_t)C, b),
+                                                              act ? (unsigned)(tid * sizeof(int)) : RO_OOB, 0, 0);
+        if constexpr (!MEMB) gs[tid] = gc;
+    } else
     if constexpr (SEQ) gs[tid] = (act && g_out) ? g_out[(size_t)b * C + cp] : 0.f;
     else
     gs[tid] = act ? g_out[(size_t)b * C + cp] : 0.f;
@@ -639,7 +707,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                     const int idx = base + tid + RO_NT * k;
                     const int at = idx < n ? cur.t * CS + cur.c : C;
                     const int cl = idx < n ? cur.c : 0;
-                    ue[at] = vu[k];
+                    if constexpr (!MEMB) ue[at] = vu[k];
                     dl[at] = __uint_as_float(vp[k] | v0[k]) - vu[k];   // exactly one of the two loads was in range
                     xh[at] = bn ? (vx[k] - bn_mean[cl]) * bn_invstd[cl] : 0.f;
                     if constexpr (SEQ) ga[at] = vg[k];
@@ -674,6 +742,7 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
             }
         }
         // thread = time: e_t in place
+        if constexpr (!MEMB) {
         for (int tl = tid; tl < len; tl += RO_NT) {
             float* row = ue + tl * CS;
             const float den = ro_softmax_row(row, C);
@@ -698,16 +767,23 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
             }
         }
         ro_barrier();
+        }
         // thread = class: reverse recurrence (groups of 8 steps without predicates, then the ragged rest)
         if (wave_has_class) {
             int at = (len - 1) * CS + cc;                                            // -> [t][cc] of the three images
             unsigned go = act ? (unsigned)(((size_t)(c0 + len - 1) * C + tid) * sizeof(float)) : RO_OOB;  // -> dWx[c0 + t][tid]
             const unsigned gstep = act ? (unsigned)(C * sizeof(float)) : 0u;
             int left = len;
+            [[maybe_unused]] int tt = c0 + len - 1;  // membrane modes: the step `at` stands on
             for (; left >= 8; left -= 8) {
                 float ev[8], dv[8], xv[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { ev[j] = ue[at - j * CS]; dv[j] = dl[at - j * CS]; xv[j] = xh[at - j * CS]; }
+                for (int j = 0; j < 8; ++j) {
+                    if constexpr (MEMB) ev[j] = ro_red_e<RED>(gc, tt - j, arg_t, Tb - 1);
+                    else
+                    ev[j] = ue[at - j * CS];
+                    dv[j] = dl[at - j * CS]; xv[j] = xh[at - j * CS];
+                }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     du = al * du + ev[j];
@@ -719,8 +795,11 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
                 }
                 at -= 8 * CS;
                 go -= 8 * gstep;
+                tt -= 8;
             }
             for (; left > 0; --left) {
+                if constexpr (MEMB) du = al * du + ro_red_e<RED>(gc, tt--, arg_t, Tb - 1);
+                else
                 du = al * du + ue[at];
                 const float dwx = oma * du;
                 ro_store(dwx, rd, go);
@@ -1191,6 +1270,130 @@ extern "C" int sparch_readout_bwd_seq_len(int B, int T, int C, const float* g_ou
 extern "C" int sparch_readout_chunk_steps(int T, int C, int bwd, int seq) {
     if (T <= 0 || C <= 0 || C > 256) return 0;
     return ro_chunk_steps(T, C, bwd ? RO_BWD_FLOATS / (seq ? 4 : 3) : RO_FWD_FLOATS);
+}
+
+// The selectable readout (include/sparch_hip.h), in front of sparch_readout_bwd_pk for the same reason.
+namespace {
+// the `_red` entry points' refusals, in front of everything else
+bool red_ok(int C, int red, const void* arg, const int* lengths, const int* offsets, long long n_valid) {
+    if (red < SPARCH_RED_SOFTMAX_SUM || red > SPARCH_RED_U_LAST) return false;
+    if (red == SPARCH_RED_U_MAX && !arg) return false;
+    if (offsets && !lengths) return false;
+    if (lengths && n_valid < 1) return false;
+    return C <= 256;
+}
+
+template <int M>
+int readout_fwd_red(int B, int T, int C, const float* Wx, const float* scale, const float* shift, const float* alpha,
+                    const float* u0, float* out, float* u_save, int* arg, const int* lengths, const int* offsets,
+                    void* stream) {
+    const int rows = ro_chunk_steps(T, C, RO_FWD_FLOATS);
+    const RoRed<M> red{arg};
+    if (offsets)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, true, const int*, RoRed<M>>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream,
+                           B, T, C, rows, Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths, offsets, red);
+    else if (lengths)
+        hipLaunchKernelGGL((readout_fwd_kernel<false, true, RoRed<M>>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                           rows, Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, lengths, red);
+    else
+        hipLaunchKernelGGL((readout_fwd_kernel<false, false, RoRed<M>>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                           rows, Wx, scale, shift, alpha, u0, out, u_save, (float*)nullptr, (const int*)nullptr, red);
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+template <int M>
+int readout_bwd_red(int B, int T, int C, const float* g_out, const float* bn_x, const float* bn_mean,
+                    const float* bn_invstd, const float* u_save, const float* alpha, const float* u0, float* dWx,
+                    float* dalpha_ws, const int* arg, const int* lengths, const int* offsets, void* stream) {
+    const RoRed<M> red{const_cast<int*>(arg)};  // (the backward only reads it)
+    if (offsets)
+        return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream,
+                                 offsets, red);
+    if (lengths)
+        return readout_bwd<true>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, stream,
+                                 red);
+    return readout_bwd<false>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, nullptr, stream,
+                              red);
+}
+
+template <int M>
+int readout_stream_fwd_red(int B, int T, int C, const float* Wx, const float* scale, const float* shift,
+                           const float* alpha, float* u, float* out, void* stream) {
+    hipLaunchKernelGGL((readout_fwd_kernel<true, false, RoRed<M>>), dim3(B), dim3(RO_NT), 0, (hipStream_t)stream, B, T, C,
+                       ro_chunk_steps(T, C, RO_FWD_FLOATS), Wx, scale, shift, alpha, (const float*)nullptr, out,
+                       (float*)nullptr, u, (const int*)nullptr, RoRed<M>{nullptr});
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+}  // namespace
+
+extern "C" int sparch_readout_fwd_red(int B, int T, int C, const float* Wx, const float* scale,
+                                      const float* shift, const float* alpha, const float* u0, float* out,
+                                      float* u_save, int red, int* arg, const int* lengths, const int* offsets,
+                                      long long n_valid, void* stream) {
+    SPARCH_ENTER();
+    if (!red_ok(C, red, arg, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    if (red == SPARCH_RED_SOFTMAX_SUM)  // the softmax-sum's own entry points
+        return offsets   ? sparch_readout_fwd_pk(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, offsets, n_valid, stream)
+               : lengths ? sparch_readout_fwd_len(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, lengths, n_valid, stream)
+                         : sparch_readout_fwd(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, stream);
+    if (B <= 0 || T <= 0 || C <= 0 || !Wx || !alpha || !u0 || !out) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    switch (red) {
+        case SPARCH_RED_SOFTMAX_MEAN:
+            return readout_fwd_red<SPARCH_RED_SOFTMAX_MEAN>(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, arg, lengths, offsets, stream);
+        case SPARCH_RED_U_MAX:
+            return readout_fwd_red<SPARCH_RED_U_MAX>(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, arg, lengths, offsets, stream);
+        case SPARCH_RED_U_MEAN:
+            return readout_fwd_red<SPARCH_RED_U_MEAN>(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, arg, lengths, offsets, stream);
+        default:
+            return readout_fwd_red<SPARCH_RED_U_LAST>(B, T, C, Wx, scale, shift, alpha, u0, out, u_save, arg, lengths, offsets, stream);
+    }
+}
+
+extern "C" int sparch_readout_stream_fwd_red(int B, int T, int C, const float* Wx, const float* scale,
+                                             const float* shift, const float* alpha, float* u, float* out, int red,
+                                             void* stream) {
+    SPARCH_ENTER();
+    if (red < SPARCH_RED_SOFTMAX_SUM || red > SPARCH_RED_U_LAST || C > 256) return SPARCH_EINVAL;
+    if (red == SPARCH_RED_SOFTMAX_SUM || red == SPARCH_RED_SOFTMAX_MEAN)  // (the mean's division is the caller's)
+        return sparch_readout_stream_fwd(B, T, C, Wx, scale, shift, alpha, u, out, stream);
+    if (B <= 0 || T <= 0 || C <= 0 || !Wx || !alpha || !u || !out) return SPARCH_EINVAL;
+    if ((scale == nullptr) != (shift == nullptr)) return SPARCH_EINVAL;
+    switch (red) {
+        case SPARCH_RED_U_MAX: return readout_stream_fwd_red<SPARCH_RED_U_MAX>(B, T, C, Wx, scale, shift, alpha, u, out, stream);
+        case SPARCH_RED_U_MEAN: return readout_stream_fwd_red<SPARCH_RED_U_MEAN>(B, T, C, Wx, scale, shift, alpha, u, out, stream);
+        default: return readout_stream_fwd_red<SPARCH_RED_U_LAST>(B, T, C, Wx, scale, shift, alpha, u, out, stream);
+    }
+}
+
+extern "C" int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* bn_x,
+                                     const float* bn_mean, const float* bn_invstd, const float* u_save,
+                                     const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                                     const int* lengths, const int* offsets, long long n_valid, void* stream);
+
+extern "C" int sparch_readout_bwd_red(int B, int T, int C, const float* g_out, const float* bn_x,
+                                      const float* bn_mean, const float* bn_invstd, const float* u_save,
+                                      const float* alpha, const float* u0, float* dWx, float* dalpha_ws, int red,
+                                      const int* arg, const int* lengths, const int* offsets, long long n_valid,
+                                      void* stream) {
+    SPARCH_ENTER();
+    if (!red_ok(C, red, arg, lengths, offsets, n_valid)) return SPARCH_EINVAL;
+    if (red == SPARCH_RED_SOFTMAX_SUM)
+        return offsets   ? sparch_readout_bwd_pk(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, offsets, n_valid, stream)
+               : lengths ? sparch_readout_bwd_len(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, lengths, n_valid, stream)
+                         : sparch_readout_bwd(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, stream);
+    switch (red) {
+        case SPARCH_RED_SOFTMAX_MEAN:
+            return readout_bwd_red<SPARCH_RED_SOFTMAX_MEAN>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, arg, lengths, offsets, stream);
+        case SPARCH_RED_U_MAX:
+            return readout_bwd_red<SPARCH_RED_U_MAX>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, arg, lengths, offsets, stream);
+        case SPARCH_RED_U_MEAN:
+            return readout_bwd_red<SPARCH_RED_U_MEAN>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, arg, lengths, offsets, stream);
+        default:
+            return readout_bwd_red<SPARCH_RED_U_LAST>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, arg, lengths, offsets, stream);
+    }
 }
 
 extern "C" int sparch_readout_bwd_pk(int B, int T, int C, const float* g_out, const float* bn_x,

@@ -137,6 +137,17 @@ def parse_per_step_loss(value):
     return w, t0
 
 
+def parse_readout(value):
+    """SPARCH_READOUT=<mode>: unset or empty -> None (the reference's softmax-sum, nothing changes); else one of
+    functional.READOUT_MODES; anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    name = value.strip()
+    if name not in Fn.READOUT_MODES:
+        raise ValueError(f"SPARCH_READOUT={value!r}: the values are {', '.join(Fn.READOUT_MODES)} (unset: softmax_sum)")
+    return name
+
+
 def _step_lengths(seq, lengths):
     B, T = seq.shape[0], seq.shape[1]
     if lengths is None:
@@ -215,6 +226,16 @@ class Experiment:
                                  "readout has no packed form; use SPARCH_LENGTHS=mask)")
             if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
                 raise ValueError(f"sparch_amd: SPARCH_PER_STEP_LOSS needs a spiking model (got {self.model_type})")
+
+        # SPARCH_READOUT=<mode>: the readout layer's reduction over time (SNN(readout=...); DESIGN.md section 6,
+        # "Selectable readout").  The loss stays cross-entropy on the network's output.
+        self.readout = parse_readout(os.environ.get("SPARCH_READOUT"))
+        if self.readout not in (None, "softmax_sum"):
+            if self.per_step_loss is not None:
+                raise ValueError(f"sparch_amd: SPARCH_READOUT={self.readout} with SPARCH_PER_STEP_LOSS is not supported "
+                                 "(the per-step readout is the softmax-sum's)")
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
+                raise ValueError(f"sparch_amd: SPARCH_READOUT needs a spiking model (got {self.model_type})")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -397,12 +418,15 @@ class Experiment:
                        if getattr(self.net, "is_snn", False) else "none (not a spiking model)")
                 logging.warning(f"SPARCH_SURROGATE={self.surrogate[0]} is ignored: the loaded model keeps its own "
                                 f"surrogate gradient, {own}")
+            if self.readout is not None:
+                logging.warning(f"SPARCH_READOUT={self.readout} is ignored: the loaded model keeps its own readout")
         elif self.model_type in ["LIF", "adLIF", "RLIF", "RadLIF"]:
             name, scale = self.surrogate if self.surrogate is not None else ("boxcar", None)
             self.net = SNN(input_shape=input_shape, layer_sizes=layer_sizes, neuron_type=self.model_type,
                            dropout=self.pdrop, normalization=self.normalization, use_bias=self.use_bias,
                            bidirectional=self.bidirectional, use_readout_layer=True, surrogate=name,
-                           surrogate_scale=scale).to(self.device)
+                           surrogate_scale=scale, **({} if self.readout is None else {"readout": self.readout})
+                           ).to(self.device)
             logging.info(f"\nCreated new spiking model:\n {self.net}\n")
             if self.surrogate is not None:
                 logging.info(f"Surrogate gradient: {name}" + ("" if scale is None else f", scale {scale:g}")

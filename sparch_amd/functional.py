@@ -1169,8 +1169,32 @@ def seq_mode(per_step):
     return SEQ_MODES[per_step]
 
 
+# selectable readout ("Selectable readout"): SPARCH_RED_*
+READOUT_MODES = {"softmax_sum": 0, "softmax_mean": 1, "u_max": 2, "u_mean": 3, "u_last": 4}
+
+
+def readout_mode(readout):
+    """readout (None or a name of READOUT_MODES) -> the C ABI's `red`; None is the default, "softmax_sum"."""
+    if readout is None:
+        return 0
+    if not isinstance(readout, str) or readout not in READOUT_MODES:
+        raise ValueError(f"sparch_amd: readout must be one of {', '.join(READOUT_MODES)} (got {readout!r})")
+    return READOUT_MODES[readout]
+
+
+def _readout_red_tail(red, arg, lengths, pack):
+    """The `_red` entry points' arguments behind the plain ones: red, arg, lengths, offsets, n_valid."""
+    if pack is not None:
+        len_ptr, off_ptr, n_valid = pack.args()
+        return red, ptr(arg), len_ptr, off_ptr, n_valid
+    if lengths is not None:
+        return red, ptr(arg), ptr(lengths[0]), None, int(lengths[1])
+    return red, ptr(arg), None, None, 0
+
+
 class ReadoutLayerFn(torch.autograd.Function):
-    """x (B,T,K) -> out (B,C): softmax-sum readout (snns.py:793-825).
+    """x (B,T,K) -> out (B,C): softmax-sum readout (snns.py:793-825), or with cfg["readout"] another reduction over
+    time (READOUT_MODES; the default issues exactly the calls it always did).
 
     With cfg["per_step"] ("prob" / "sum"; DESIGN.md section 6, "Per-step readout") -> (out, seq): seq (B,T,C) is
     softmax(u_t), or the running sum of `out` after every step; its gradient reaches the kernel as g_seq."""
@@ -1190,7 +1214,18 @@ class ReadoutLayerFn(torch.autograd.Function):
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
         lengths = cfg.get("lengths")
         mode = seq_mode(cfg.get("per_step"))
-        if mode is not None:
+        red = readout_mode(cfg.get("readout"))
+        if red != 0 and mode is not None:
+            raise ValueError("sparch_amd: per_step needs the default readout (softmax_sum)")
+        ctx.red_arg = None
+        if red != 0:
+            Bk, Tk = (B, T) if pack is None else (pack.batch, pack.t_max)
+            if red == READOUT_MODES["u_max"]:  # the step of each maximum: the backward reads it
+                ctx.red_arg = torch.empty(Bk, C, dtype=torch.int32, device=x.device)
+            check(lib.sparch_readout_fwd_red(Bk, Tk, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
+                                             ptr(u_save), *_readout_red_tail(red, ctx.red_arg, lengths, pack), _stream()),
+                  "sparch_readout_fwd_red")
+        elif mode is not None:
             if pack is not None:
                 raise ValueError("sparch_amd: the per-step readout has no packed form (per_step with pack)")
             seq = torch.empty(B, T, C, dtype=torch.float32, device=x.device)  # (every element is written: no clear)
@@ -1240,7 +1275,11 @@ class ReadoutLayerFn(torch.autograd.Function):
         lead = (B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None, ptr(ctx.nsaved[0]) if fuse else None,
                 ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
         lengths = cfg.get("lengths")
-        if mode is not None:
+        red = readout_mode(cfg.get("readout"))
+        if red != 0:
+            check(lib.sparch_readout_bwd_red(*lead, *_readout_red_tail(red, ctx.red_arg, lengths, pack), _stream()),
+                  "sparch_readout_bwd_red")
+        elif mode is not None:
             lead = lead[:4] + (ptr(_f32c(g_seq)), mode) + lead[4:]
             if lengths is None:
                 check(lib.sparch_readout_bwd_seq(*lead, _stream()), "sparch_readout_bwd_seq")
@@ -1298,10 +1337,11 @@ class SpikingCellFn(torch.autograd.Function):
 
 
 class ReadoutCellFn(torch.autograd.Function):
-    """The readout cell in isolation (reference `_readout_cell`, snns.py:808-825)."""
+    """The readout cell in isolation (reference `_readout_cell`, snns.py:808-825); readout: a name of READOUT_MODES."""
 
     @staticmethod
-    def forward(ctx, Wx, alpha, u0):
+    def forward(ctx, Wx, alpha, u0, readout=None):
+        red = readout_mode(readout)
         _require_device(Wx, "Wx")
         Wx = _f32c(Wx)
         B, T, C = Wx.shape
@@ -1309,8 +1349,16 @@ class ReadoutCellFn(torch.autograd.Function):
             raise ValueError(f"sparch_amd: the readout kernels handle at most 256 classes (got {C})")
         out = torch.empty(B, C, dtype=torch.float32, device=Wx.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=Wx.device)
-        check(lib.sparch_readout_fwd(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out), ptr(u_save),
-                                     _stream()), "sparch_readout_fwd")
+        ctx.red, ctx.red_arg = red, None
+        if red != 0:
+            if red == READOUT_MODES["u_max"]:
+                ctx.red_arg = torch.empty(B, C, dtype=torch.int32, device=Wx.device)
+            check(lib.sparch_readout_fwd_red(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out), ptr(u_save),
+                                             *_readout_red_tail(red, ctx.red_arg, None, None), _stream()),
+                  "sparch_readout_fwd_red")
+        else:
+            check(lib.sparch_readout_fwd(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out), ptr(u_save),
+                                         _stream()), "sparch_readout_fwd")
         ctx.dims = (B, T, C)
         ctx.save_for_backward(alpha, u0, u_save)
         return out
@@ -1321,10 +1369,16 @@ class ReadoutCellFn(torch.autograd.Function):
         B, T, C = ctx.dims
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=g_out.device)
         ws = torch.empty(1, B, C, dtype=torch.float32, device=g_out.device)
-        check(lib.sparch_readout_bwd(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save), ptr(alpha),
-                                     ptr(u0), ptr(dWx), ptr(ws), _stream()), "sparch_readout_bwd")
+        if ctx.red != 0:
+            check(lib.sparch_readout_bwd_red(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save), ptr(alpha),
+                                             ptr(u0), ptr(dWx), ptr(ws),
+                                             *_readout_red_tail(ctx.red, ctx.red_arg, None, None), _stream()),
+                  "sparch_readout_bwd_red")
+        else:
+            check(lib.sparch_readout_bwd(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save), ptr(alpha),
+                                         ptr(u0), ptr(dWx), ptr(ws), _stream()), "sparch_readout_bwd")
         (dalpha,) = _finish_param_grads(ws, B, C, [alpha], [ALPHA_LIM])
-        return dWx, dalpha, None
+        return dWx, dalpha, None, None
 
 
 class CrossEntropyFn(torch.autograd.Function):

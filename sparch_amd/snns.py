@@ -593,11 +593,17 @@ class RadLIFLayer(_SpikingLayer):
 class ReadoutLayer(nn.Module):
     """Non-spiking leaky integrator whose output is the sum over time of softmax(u_t)
     (reference ReadoutLayer, snns.py:730-825).  No dropout is applied, as in the reference
-    (the Dropout module exists at 791 but is never called)."""
+    (the Dropout module exists at 791 but is never called).
+
+    readout ("Selectable readout"): the reduction over time — "softmax_sum" (the default, the
+    reference's), "softmax_mean" (that sum over the row's number of steps), or of the membrane itself "u_max" (ties:
+    the earliest step), "u_mean", "u_last".  With lengths the row's own steps count."""
 
     def __init__(self, input_size, hidden_size, batch_size, dropout=0.0, normalization="batchnorm",
-                 use_bias=False):
+                 use_bias=False, readout="softmax_sum"):
         super().__init__()
+        Fn.readout_mode(readout)
+        self.readout = readout
         self.input_size = int(input_size)
         self.hidden_size = int(hidden_size)
         self.batch_size = batch_size
@@ -614,6 +620,10 @@ class ReadoutLayer(nn.Module):
             self.norm = norm
         self.drop = nn.Dropout(p=dropout)
 
+    def extra_repr(self):
+        name = getattr(self, "readout", "softmax_sum")
+        return "" if name == "softmax_sum" else f"readout={name}"
+
     def forward(self, x, u0=None, lengths=None, pack=None, per_step=None):
         """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b].
         pack: None, or prepare_packing()'s result — x is the packed batch (1, n, feat); out and u0 hold the plan's
@@ -622,6 +632,11 @@ class ReadoutLayer(nn.Module):
         classes) = softmax(u_t), or the running sum of `out` after step t (seq[:, -1] is out); with lengths, seq is 0
         at t >= lengths[b].  Both are differentiable.  Not with pack."""
         Fn.seq_mode(per_step)
+        readout = getattr(self, "readout", "softmax_sum")  # (a module pickled before the attribute: the default)
+        Fn.readout_mode(readout)
+        if per_step is not None and readout != "softmax_sum":
+            raise ValueError(f"sparch_amd: per_step with readout={readout!r} is not supported (the per-step readout is "
+                             "the softmax-sum's)")
         if per_step is not None and pack is not None:
             raise ValueError("sparch_amd: per_step with pack is not supported (the per-step readout has no packed form)")
         if lengths is not None:
@@ -648,6 +663,8 @@ class ReadoutLayer(nn.Module):
             cfg["pack"] = pack
         if per_step is not None:
             cfg["per_step"] = per_step
+        if readout != "softmax_sum":
+            cfg["readout"] = readout
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         return Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
@@ -655,7 +672,10 @@ class ReadoutLayer(nn.Module):
     def _readout_cell(self, Wx):
         Fn._require_device(Wx, "Wx")
         u0 = _rand_to(Wx.shape[0], Wx.shape[2], Wx.device)
-        return Fn.ReadoutCellFn.apply(Wx, self.alpha, u0)
+        readout = getattr(self, "readout", "softmax_sum")
+        if readout == "softmax_sum":
+            return Fn.ReadoutCellFn.apply(Wx, self.alpha, u0)
+        return Fn.ReadoutCellFn.apply(Wx, self.alpha, u0, readout)
 
 
 def prepare_lengths(lengths, batch, T, device):
@@ -773,12 +793,18 @@ class SNN(nn.Module):
     returns THREE values, (out, firing_rates, seq): seq (batch, time, classes) is the readout after every step —
     softmax(u_t), or the running sum whose last step is `out` (row t is what StreamingSNN.step returns after t + 1
     steps).  With lengths, seq[b, t] is 0 for t >= lengths[b].  A loss may use out, seq or both.  per_step=None (the
-    default): the two values above, nothing else changes."""
+    default): the two values above, nothing else changes.
+
+    readout="softmax_sum" (the default) / "softmax_mean" / "u_max" / "u_mean" / "u_last" (DESIGN.md section 6,
+    "Selectable readout"): the readout layer's reduction over time (ReadoutLayer); with lengths, also packed, over the
+    row's own steps.  per_step needs the default."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
-                 surrogate="boxcar", surrogate_scale=None):
+                 surrogate="boxcar", surrogate_scale=None, readout="softmax_sum"):
         super().__init__()
+        Fn.readout_mode(readout)
+        self.readout = readout
         self.surrogate, self.surrogate_scale = resolve_surrogate(surrogate, surrogate_scale)
         self.reshape = len(input_shape) > 3
         self.input_size = float(torch.prod(torch.tensor(input_shape[2:])))
@@ -816,12 +842,16 @@ class SNN(nn.Module):
         if self.use_readout_layer:
             layers.append(ReadoutLayer(
                 input_size=fan_in, hidden_size=self.layer_sizes[-1], batch_size=self.batch_size,
-                dropout=self.dropout, normalization=self.normalization, use_bias=self.use_bias))
+                dropout=self.dropout, normalization=self.normalization, use_bias=self.use_bias,
+                readout=self.readout))
         return layers
 
     def extra_repr(self):
         name = getattr(self, "surrogate", "boxcar")
-        return "" if name == "boxcar" else f"surrogate={name}, surrogate_scale={getattr(self, 'surrogate_scale', None):g}"
+        parts = [] if name == "boxcar" else [f"surrogate={name}, surrogate_scale={getattr(self, 'surrogate_scale', None):g}"]
+        if getattr(self, "readout", "softmax_sum") != "softmax_sum":
+            parts.append(f"readout={self.readout}")
+        return ", ".join(parts)
 
     def draw_states(self, batch, device, out=None):
         """Every layer's initial states for one forward, drawn from torch's global CPU generator in the
@@ -892,6 +922,10 @@ class SNN(nn.Module):
                                  "packed form)")
             if not self.use_readout_layer:
                 raise ValueError("sparch_amd: per_step needs a readout layer (use_readout_layer=True)")
+            readout = getattr(self.snn[-1], "readout", "softmax_sum")
+            if readout != "softmax_sum":
+                raise ValueError(f"sparch_amd: per_step with readout={readout!r} is not supported (the per-step readout "
+                                 "is the softmax-sum's)")
         if self.reshape:
             if x.ndim == 4:
                 x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])

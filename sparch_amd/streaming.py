@@ -171,7 +171,9 @@ class _Stream:
 class StreamingSNN(_Stream):
     """Chunked forward of a `sparch_amd.SNN` in eval mode with carried state.
 
-    step(x_chunk) returns, with a readout layer, the running softmax-sum (B,classes) after all steps seen so far
+    step(x_chunk) returns, with a readout layer, the running softmax-sum (B,classes) after all steps seen so far — or,
+    on the chunk path, the network's own readout (SNN(readout=...)) of the steps seen so far: the mean over them, the
+    running maximum, the last membrane; fused=True takes the default readout only —
     (with graph=True a static tensor that the next step overwrites), without one the chunk's spikes (B,Tc,H).
     firing_rates() is spike count / (B * steps_seen) per hidden unit, concatenated over the layers as SNN.forward
     does; the integer counts add exactly across chunks.  The spike counters are per layer, NOT per row:
@@ -191,6 +193,11 @@ class StreamingSNN(_Stream):
         if fused and any(mod.normalize and mod.normalization == "layernorm" for mod in net.snn):
             raise ValueError("StreamingSNN: fused=True does not take LayerNorm layers (a row statistic across the "
                              "workgroups of a step); use fused=False")
+        readout = self._readout_name(net)
+        Fn.readout_mode(readout)
+        if fused and readout != "softmax_sum":
+            raise ValueError(f"StreamingSNN: fused=True does not take readout={readout!r} (the one-step readout kernels "
+                             "are the softmax-sum's); use fused=False")
         self.fused = bool(fused)
         self.sparse = bool(sparse)
         self._fused_active = self.fused and Fn._prec() == 0
@@ -204,6 +211,11 @@ class StreamingSNN(_Stream):
         # layer with the chunk's spikes as they travel to the next layer (the bf16 0/1 plane); the tensor
         # is only valid during the call (graph=True: a static buffer the next replay overwrites)
         self._spike_tap = None
+
+    @staticmethod
+    def _readout_name(net):
+        """The readout layer's reduction over time (snns.ReadoutLayer; a module from before the attribute: the default)."""
+        return getattr(net.snn[-1], "readout", "softmax_sum") if net.use_readout_layer else "softmax_sum"
 
     # ------------------------------------------------------------------ caches
     def refresh(self):
@@ -234,6 +246,11 @@ class StreamingSNN(_Stream):
                 elif L.norm == "layernorm":
                     L.nw, L.nb = mod.norm.weight.detach(), mod.norm.bias.detach()
                 L.theta = None if L.readout else float(mod.threshold)
+                # readout: the reduction over time; the mean modes carry the un-normalised accumulator in `out` and the
+                # rows' step counts in `steps`, u_max the running maximum (from -inf)
+                L.red = Fn.readout_mode(self._readout_name(net)) if L.readout else 0
+                L.red_mean = L.red in (Fn.READOUT_MODES["softmax_mean"], Fn.READOUT_MODES["u_mean"])
+                L.out_init = float("-inf") if L.red == Fn.READOUT_MODES["u_max"] else 0.0
                 # the recurrent kernels own 4 columns per thread: other widths run zero-padded (as cell_forward does),
                 # and the padded state stays padded
                 L.Hs = (L.H + 3) // 4 * 4 if L.recurrent else L.H
@@ -257,11 +274,12 @@ class StreamingSNN(_Stream):
                     L.vmask_t = L.vmask.t().contiguous()  # (H_out, H_in): the NT operand of the exact spike product
                 # state buffers: kept across refresh()
                 if old is not None:
-                    for k in ("u", "w", "s", "s16", "count", "out", "binary", "s_alt", "s16_alt", "s_first"):
+                    for k in ("u", "w", "s", "s16", "count", "out", "steps", "binary", "s_alt", "s16_alt", "s_first"):
                         setattr(L, k, getattr(old[i], k, None))
                 elif L.readout:
                     L.u = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
-                    L.out = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
+                    L.out = torch.full((B, L.H), L.out_init, dtype=torch.float32, device=dev)
+                    L.steps = torch.zeros(B, 1, dtype=torch.int32, device=dev) if L.red_mean else None
                 else:
                     L.u = torch.zeros(B, L.Hs, dtype=torch.float32, device=dev)
                     L.w = torch.zeros(B, L.Hs, dtype=torch.float32, device=dev) if L.adaptive else None
@@ -317,6 +335,15 @@ class StreamingSNN(_Stream):
             if L.readout:
                 if out is not None:
                     self._put(L.out, out, "out", idx)
+                steps = st.get("steps") if isinstance(st, dict) else None
+                if steps is not None and L.steps is not None:
+                    steps = torch.as_tensor(steps).to(device=self._dev, dtype=torch.int32).reshape(-1, 1)
+                    if steps.shape[0] != (self.batch_size if idx is None else len(idx)):
+                        raise ValueError(f"StreamingSNN: steps has {steps.shape[0]} rows")
+                    if idx is None:
+                        L.steps.copy_(steps)
+                    else:
+                        L.steps.index_copy_(0, idx, steps)
                 continue
             if L.adaptive:
                 self._put(L.w, w, "w", idx, L.H)
@@ -343,18 +370,25 @@ class StreamingSNN(_Stream):
                 if not L.readout:
                     L.count.zero_()
             if ro is not None:
-                ro.out.zero_()
+                ro.out.fill_(ro.out_init)
+                if ro.steps is not None:
+                    ro.steps.zero_()
         elif ro is not None:
-            ro.out.index_fill_(0, self._rows(rows), 0.0)
+            ro.out.index_fill_(0, self._rows(rows), ro.out_init)
+            if ro.steps is not None:
+                ro.steps.index_fill_(0, self._rows(rows), 0)
         self._restart(rows)
 
     def get_state(self):
-        """A copy of the carried state: per hidden layer {"u", ["w",] "s"}, for the readout {"u", "out"} (unpadded)."""
+        """A copy of the carried state: per hidden layer {"u", ["w",] "s"}, for the readout {"u", "out"} (unpadded);
+        `out` is the accumulator as carried — in the mean readouts un-normalised, with the rows' step counts as "steps"."""
         self._ensure()
         res = []
         for L in self._layers:
             if L.readout:
                 res.append({"u": L.u.clone(), "out": L.out.clone()})
+                if L.steps is not None:
+                    res[-1]["steps"] = L.steps.clone()
             else:
                 d = {"u": L.u[:, :L.H].clone(), "s": L.s[:, :L.H].clone()}
                 if L.adaptive:
@@ -442,6 +476,14 @@ class StreamingSNN(_Stream):
                 Wx_raw, _ = inp.project(L.W, L.Wb, False, b_planes=L.w_planes)
             Wx = self._norm(L, Wx_raw)
             if L.readout:
+                if L.red != 0:
+                    check(lib.sparch_readout_stream_fwd_red(B, Tc, L.H, ptr(Wx), ptr(L.scale), ptr(L.shift),
+                                                            ptr(L.p["alpha"]), ptr(L.u), ptr(L.out), L.red, Fn._stream()),
+                          "sparch_readout_stream_fwd_red")
+                    if L.red_mean:  # accumulator / steps: the whole-sequence kernel's one division by (float)T_b
+                        L.steps += Tc
+                        return L.out / L.steps.to(torch.float32), taps
+                    return L.out, taps
                 check(lib.sparch_readout_stream_fwd(B, Tc, L.H, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(L.p["alpha"]),
                                                     ptr(L.u), ptr(L.out), Fn._stream()), "sparch_readout_stream_fwd")
                 return L.out, taps
