@@ -733,6 +733,52 @@ int sparch_readout_stream_fwd_red(int B, int T, int C, const float* Wx, const fl
                                   const float* shift, const float* alpha, float* u, float* out, int red,
                                   void* stream);
 
+/* Stateful training ("Stateful training"): the reverse pass of a chunk whose final state
+ * (u_T, w_T, s_T = 1[u_T > theta]) was handed on to the next chunk and whose initial state came from the one before.
+ * The forward is the plain one (sparch_cell_fwd / sparch_readout_fwd with fp32 saves: u_save[:, T-1], w_save[:, T-1]
+ * ARE the final membranes).  With du_t, dw_t the total gradients of u_t, w_t, k the dropout scale:
+ *   into the chunk, at the reverse pass's first step only (du_{T+1} = dw_{T+1} = 0 there), from g_uT / g_wT / g_sT,
+ *   the gradient arriving on the final state ((B,H) each, NULL = 0):
+ *     ds_T = (g_T + g_rate) k + g_sT        du_T = gate(ds_T) + g_uT        dw_T = g_wT - (1 - alpha) du_T
+ *     (g_sT is the RAW spike's: it enters behind the dropout scale, which scales the layer's output, not its state)
+ *   out of the chunk, from the carries the pass ends with, into g_u0 / g_w0 / g_s0 ((B,H) each, NULL = not wanted):
+ *     g_u0 = alpha du_1 + a dw_1            g_w0 = beta dw_1                g_s0 = -alpha du_1 + b dw_1
+ *     (LIF: the terms in dw are absent; g_wT / g_w0 are ignored)
+ * sparch_cell_bwd_st: the arguments of sparch_cell_bwd_sg, then the six above.  dirs == 1 and save_bf16 == 0 only:
+ * anything else is SPARCH_EINVAL before any device work, as are sparch_cell_bwd_sg's own refusals.
+ * sparch_readout_bwd_st: the arguments of sparch_readout_bwd, then g_uT and g_u0 ((B,C), nullable):
+ *     du_T = softmax'(u_T)^T g_out + g_uT                                   g_u0 = alpha du_1                     */
+int sparch_cell_bwd_st(int kind, int B, int dirs, int T, int H, const float* g_out,
+                       const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                       const float* alpha, const float* beta, const float* a, const float* b,
+                       const float* u0, const float* w0, const float* s0, float theta,
+                       float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                       const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
+                       const float* g_uT, const float* g_wT, const float* g_sT, float* g_u0, float* g_w0,
+                       float* g_s0, void* stream);
+/* sparch_rec_cell_bwd_st (RLIF / RadLIF): the arguments of sparch_rec_cell_bwd_sg up to surrogate_scale, then the six
+ * above ((Bp,H) each, nullable), then stream and precision.  With Vm = V with a zero diagonal and dWx_1 = (1 - alpha) du_1,
+ *     g_s0 = -alpha du_1 + b dw_1 + dWx_1 Vm^T:
+ * the kernel writes g_u0, g_w0 and the two pointwise terms of g_s0; the product is the caller's, one (Bp x H)(H x H)
+ * GEMM on dWx[:, 0, :] through the existing entry points.  dV's s_0 term is what it always was.  Whole-sequence launches
+ * only: steps_per_launch < T is SPARCH_EINVAL, as are dirs != 1, save_bf16 != 0, precision != 0 (the bf16 operand mode),
+ * H > 1024 and a grid that cannot be co-resident (no degraded mode) — each before any device work.                  */
+int sparch_rec_cell_bwd_st(int kind, int B, int dirs, int T, int H, const float* g_out,
+                           const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                           const float* alpha, const float* beta, const float* a,
+                           const float* b, const float* vpack_t, const float* u0,
+                           const float* w0, const float* s0, float theta, float p_drop,
+                           uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                           const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                           void* chan, size_t chan_bytes, uint32_t* status,
+                           int steps_per_launch, int surrogate, float surrogate_scale,
+                           const float* g_uT, const float* g_wT, const float* g_sT, float* g_u0,
+                           float* g_w0, float* g_s0, void* stream, int precision);
+int sparch_readout_bwd_st(int B, int T, int C, const float* g_out, const float* bn_x,
+                          const float* bn_mean, const float* bn_invstd, const float* u_save,
+                          const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                          const float* g_uT, float* g_u0, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * G9  mel filterbank front-end  (replaces torchaudio.compliance.kaldi.fbank(x,
  *     num_mel_bins=40) at nonspiking_datasets.py:96,194; third-party, parity unpinned).

@@ -74,6 +74,9 @@ PROTOTYPES = {
                                 c_float, c_float, c_uint64, P, P, P, P, P, P]),
     "sparch_cell_bwd_sg": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
                                    c_float, c_float, c_uint64, P, P, P, P, P, c_int, c_float, P]),
+    "sparch_cell_bwd_st": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
+                                   c_float, c_float, c_uint64, P, P, P, P, P, c_int, c_float, P, P, P, P, P, P, P]),
+    "sparch_readout_bwd_st": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
     "sparch_cell_fwd_len": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P,
                                     c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, c_longlong, P]),
     "sparch_cell_bwd_len": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P,
@@ -99,6 +102,9 @@ PROTOTYPES = {
     "sparch_rec_cell_bwd_sg": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
                                        c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_size_t, P, c_int,
                                        c_int, c_float, P, c_int]),
+    "sparch_rec_cell_bwd_st": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, P, P, P, P,
+                                       c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_size_t, P, c_int,
+                                       c_int, c_float, P, P, P, P, P, P, P, c_int]),
     "sparch_rec_cell_fwd_len": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P,
                                         c_float, c_float, c_uint64, P, P, P, P, c_int, P, P, c_longlong, P, c_size_t, P,
                                         c_int, P, c_int]),

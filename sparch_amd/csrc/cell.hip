@@ -42,10 +42,16 @@ struct CellLenArgs : CellArgs { const int* lengths; };
 // The packed entry points (`_pk`): the batch's sequences sorted by length, sequence j in rows [offsets[j], offsets[j] +
 // lengths[j]) of every (N,H) tensor (N = offsets[B]); B counts sequences and T is the longest length.
 struct CellPkArgs : CellArgs { const int* lengths; const int* offsets; };
-// The packed kernels give every sequence whole waves: a row of HQ threads is padded to the next multiple of 64 (the lanes
+// The stateful entry point (`_st`, backward only): the gradient arriving on the final state (u_T, w_T, s_T) and the
+// gradient of the initial state (u0, w0, s0) going out, each (B,H) and each nullable.
+struct CellStArgs : CellArgs {
+    const float* g_uT; const float* g_wT; const float* g_sT;
+    float* g_u0; float* g_w0; float* g_s0;
+};// The packed kernels give every sequence whole waves: a row of HQ threads is padded to the next multiple of 64 (the lanes
 // behind HQ leave at once), so that no wave straddles two sequences and a wave's length and row offset are scalars.
 __host__ __device__ constexpr int pk_row_threads(int HQ) { return (HQ + 63) / 64 * 64; }
 template <class Args> constexpr int cell_mode = std::is_same_v<Args, CellPkArgs> ? 2 : std::is_same_v<Args, CellLenArgs> ? 1 : 0;
+template <class Args> constexpr bool cell_stateful = std::is_same_v<Args, CellStArgs>;  // the stateful backward family
 
 template <int VEC>
 __device__ __forceinline__ void ldv(float (&d)[VEC], const float* p) {
@@ -272,6 +278,18 @@ __global__ __launch_bounds__(256) void cell_fwd_pipe_kernel(
 // with the smooth kernels' 256 VGPRs + AGPR copies at one wave per SIMD).
 // cell_bwd_pipe_pk_kernel / cell_bwd_pipe_pk_sg_kernel (sparch_cell_bwd_pk) are the packed ones: ROW_T(b) is the
 // sequence's own length and ROW0(r) its first packed row, and there is no tail to zero.
+// cell_bwd_pipe_st_kernel / cell_bwd_pipe_st_sg_kernel (sparch_cell_bwd_st) are the stateful ones, behind the packed
+// family below: ST_LOAD / ST_ADD / ST_TAIL take a gradient on the final state in and put the initial state's out; in
+// every other family they are empty.
+#define ST_LOAD
+#define ST_DS(t, gs)                  \
+    float ds = gs - al[e] * du_n[e]; \
+    if (ADAPT) ds = ds + pb[e] * dw_n[e];
+#define ST_DU(t, gate)                    \
+    float du = gate + al[e] * du_n[e];   \
+    if (ADAPT) du = du + pa[e] * dw_n[e];
+#define ST_ADD(t, v, g) (v)
+#define ST_TAIL
 #define ROW_THREADS(HQ) (HQ)
 #define ROW_GUARD(h)
 #define ROW0_INIT(b) 0
@@ -337,6 +355,79 @@ __global__ __launch_bounds__(256) void cell_bwd_pipe_pk_sg_kernel(CellPkArgs c, 
 #undef ROW_THREADS
 #undef ROW_GUARD
 #undef ROW0_INIT
+#undef ST_LOAD
+#undef ST_DS
+#undef ST_DU
+#undef ST_ADD
+#undef ST_TAIL
+// Stateful training ("Stateful training"): the plain family's rows, plus
+//   into the chunk, at the reverse pass's first step only (du_{T+1} = dw_{T+1} = 0 there):
+//     ds_T = (g_T + g_rate) k + g_sT,   du_T = gate(ds_T) + g_uT,   dw_T = g_wT - (1 - alpha) du_T
+//   out of the chunk, from the carries the pass ends with:
+//     g_u0 = alpha du_1 + a dw_1,   g_w0 = beta dw_1,   g_s0 = -alpha du_1 + b dw_1
+#define ROW_THREADS(HQ) (HQ)
+#define ROW_GUARD(h)
+#define ROW0_INIT(b) 0
+#define ROW_T(b) c.T
+#define ROW0(r) ((size_t)(r) * T)
+#define ROW_LEN(b) T
+#define TAIL_ZERO(t, v) (v)
+#define ST_LOAD                                                                                   \
+    float st_gu[VEC], st_gw[VEC], st_gs[VEC];                                                     \
+    _Pragma("unroll") for (int e = 0; e < VEC; ++e) st_gu[e] = st_gw[e] = st_gs[e] = 0.f;         \
+    if (c.g_uT) ldv<VEC>(st_gu, c.g_uT + (size_t)bp * H + h);                                     \
+    if (ADAPT && c.g_wT) ldv<VEC>(st_gw, c.g_wT + (size_t)bp * H + h);                            \
+    if (c.g_sT) ldv<VEC>(st_gs, c.g_sT + (size_t)bp * H + h);
+// (every step adds the carried terms as the sums S_t, U_t that ST_TAIL hands over at a boundary: a chained run's dWx is
+// then the one-chunk run's bit for bit, adaptation included — fp32 addition does not reassociate)
+#define ST_DS(t, gs)                                              \
+    float st_s = -(al[e] * du_n[e]);                              \
+    if (ADAPT) st_s = st_s + pb[e] * dw_n[e];                     \
+    float ds = (gs) + ((t) == T - 1 ? st_gs[e] : st_s);
+#define ST_DU(t, gate)                                            \
+    float st_u = al[e] * du_n[e];                                 \
+    if (ADAPT) st_u = st_u + pa[e] * dw_n[e];                     \
+    float du = (gate) + ((t) == T - 1 ? st_gu[e] : st_u);
+#define ST_ADD(t, v, g) ((t) == T - 1 ? (v) + (g) : (v))
+#define ST_TAIL                                                                                  \
+    {                                                                                             \
+        float o_u[VEC], o_w[VEC], o_s[VEC];                                                       \
+        _Pragma("unroll") for (int e = 0; e < VEC; ++e) {                                         \
+            o_u[e] = al[e] * du_n[e];                                                             \
+            o_s[e] = -o_u[e];                                                                     \
+            o_w[e] = 0.f;                                                                         \
+            if (ADAPT) {                                                                          \
+                o_u[e] = o_u[e] + pa[e] * dw_n[e];                                                \
+                o_s[e] = o_s[e] + pb[e] * dw_n[e];                                                \
+                o_w[e] = be[e] * dw_n[e];                                                         \
+            }                                                                                     \
+        }                                                                                         \
+        if (c.g_u0) stv<VEC>(c.g_u0 + (size_t)bp * H + h, o_u);                                   \
+        if (ADAPT && c.g_w0) stv<VEC>(c.g_w0 + (size_t)bp * H + h, o_w);                          \
+        if (c.g_s0) stv<VEC>(c.g_s0 + (size_t)bp * H + h, o_s);                                   \
+    }
+template <bool ADAPT, int VEC, bool BN, bool DROP, bool S16 = false>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_st_kernel(CellStArgs c)
+#define SURROGATE_GATE(ds, x) boxcar_gate(ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+template <bool ADAPT, int VEC, bool BN, bool DROP, bool S16 = false>
+__global__ __launch_bounds__(256) void cell_bwd_pipe_st_sg_kernel(CellStArgs c, SurrogateArgs sg)
+#define SURROGATE_GATE(ds, x) smooth_gate(sg.id, sg.k, ds, x)
+#include "cell_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_LEN
+#undef TAIL_ZERO
+#undef ROW_T
+#undef ROW0
+#undef ROW_THREADS
+#undef ROW_GUARD
+#undef ROW0_INIT
+#undef ST_LOAD
+#undef ST_DS
+#undef ST_DU
+#undef ST_ADD
+#undef ST_TAIL
 
 // ------------------------------------------------------------------ readout cell
 // Readout layer (snns.py:815-825): u_t = alpha u_{t-1} + (1-alpha) x_t, out = sum_t softmax_c(u_t).
@@ -397,6 +488,9 @@ __device__ __forceinline__ const int* ro_offsets(const int* offsets) { return of
 // form's offsets.  mode: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM.
 struct RoSeq { float* seq; int mode; };          // forward: the per-step output (B,T,C)
 struct RoGSeq { const float* g_seq; int mode; }; // backward: the per-step incoming gradient (B,T,C)
+// Stateful training (sparch_readout_bwd_st): the backward's trailing argument, alone.  g_uT (B,C): the gradient arriving
+// on the returned final membrane u_T, added to e_T; g_u0 (B,C), written: alpha du_1, the initial membrane's.  Each nullable.
+struct RoSt { const float* g_uT; float* g_u0; };
 template <class S> __device__ __forceinline__ const int* ro_offsets(S) { return nullptr; }
 template <class S> __device__ __forceinline__ const int* ro_offsets(const int* offsets, S) { return offsets; }
 // Selectable readout (sparch_readout_*_red): a trailing argument too, alone or behind the packed form's offsets.  The
@@ -631,8 +725,10 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
     constexpr bool PK = ro_has<const int*, Offsets...>, SEQ = ro_has<RoGSeq, Offsets...>;
     constexpr int RED = ro_red_mode<Offsets...>();
     constexpr bool MEMB = RED >= SPARCH_RED_U_MAX;
+    constexpr bool ST = ro_has<RoSt, Offsets...>;
     static_assert(sizeof...(Offsets) <= 1 + (PK && RED != 0) && (!PK || LEN), "packed rows carry their lengths");
     static_assert(!(SEQ && RED != 0), "the per-step gradient is the softmax-sum's");
+    static_assert(!ST || (sizeof...(Offsets) == 1 && !LEN), "the stateful form is the plain softmax-sum's");
     [[maybe_unused]] const int* offsets = ro_offsets(pk...);
     [[maybe_unused]] const RoGSeq sq = ro_seq<RoGSeq>(pk...);
     [[maybe_unused]] const int* const arg = ro_red_arg(pk...);
@@ -770,6 +866,10 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
         }
         // thread = class: reverse recurrence (groups of 8 steps without predicates, then the ragged rest)
         if (wave_has_class) {
+            if constexpr (ST) {  // the gradient on u_T joins e_T (this thread's own element of the image, written by it)
+                const float* g_uT = ro_seq<RoSt>(pk...).g_uT;
+                if (ch == nchunk - 1 && act && g_uT) ue[(len - 1) * CS + cc] += g_uT[(size_t)b * C + cp];
+            }
             int at = (len - 1) * CS + cc;                                            // -> [t][cc] of the three images
             unsigned go = act ? (unsigned)(((size_t)(c0 + len - 1) * C + tid) * sizeof(float)) : RO_OOB;  // -> dWx[c0 + t][tid]
             const unsigned gstep = act ? (unsigned)(C * sizeof(float)) : 0u;
@@ -818,6 +918,10 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
             dalpha_ws[((size_t)B + b) * C + cc] = acc_dy;
             dalpha_ws[((size_t)2 * B + b) * C + cc] = acc_dyx;
         }
+        if constexpr (ST) {  // du holds du_1: the initial membrane's gradient
+            float* g_u0 = ro_seq<RoSt>(pk...).g_u0;
+            if (g_u0) g_u0[(size_t)b * C + cc] = al * du;
+        }
     }
 }
 
@@ -825,6 +929,17 @@ __global__ __launch_bounds__(RO_NT) void readout_bwd_kernel(int B, int T, int C,
 template <bool ADAPT, int VEC, bool DROP, class Args>
 void launch_cell_pipe(bool bwd, const Args& c, const SurrogateArgs& sg, unsigned blocks, hipStream_t st) {
     constexpr bool LEN = cell_mode<Args> == 1, PK = cell_mode<Args> == 2;
+    if constexpr (cell_stateful<Args>) {  // the stateful backward (fp32 saves: the entry point has refused bf16 ones)
+        auto go = [&](auto bn) {
+            constexpr bool BN = decltype(bn)::value;
+            if (sg.id == SPARCH_SURROGATE_BOXCAR)
+                hipLaunchKernelGGL((cell_bwd_pipe_st_kernel<ADAPT, VEC, BN, DROP>), dim3(blocks), dim3(256), 0, st, c);
+            else
+                hipLaunchKernelGGL((cell_bwd_pipe_st_sg_kernel<ADAPT, VEC, BN, DROP>), dim3(blocks), dim3(256), 0, st, c, sg);
+        };
+        if (c.bn_x) go(std::true_type{}); else go(std::false_type{});
+        return;
+    } else
     if constexpr (LEN || PK) {
         if (bwd) {
             auto go = [&](auto s16, auto bn) {  // (bf16 saves: the box-car only — the entry point has refused the rest)
@@ -1270,6 +1385,53 @@ extern "C" int sparch_readout_bwd_seq_len(int B, int T, int C, const float* g_ou
 extern "C" int sparch_readout_chunk_steps(int T, int C, int bwd, int seq) {
     if (T <= 0 || C <= 0 || C > 256) return 0;
     return ro_chunk_steps(T, C, bwd ? RO_BWD_FLOATS / (seq ? 4 : 3) : RO_FWD_FLOATS);
+}
+
+// Stateful training (include/sparch_hip.h), in front of sparch_readout_bwd_pk for the same reason.
+// (launch_cell / launch_cell_pipe with Args = CellStArgs: the one thread-mapping rule and dispatch of every family)
+extern "C" int sparch_cell_bwd_st(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                  const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                  const float* alpha, const float* beta, const float* a, const float* b,
+                                  const float* u0, const float* w0, const float* s0, float theta,
+                                  float p_drop, uint64_t seed, float* dWx, float* dparam_ws, const float* bn_x,
+                                  const float* bn_mean, const float* bn_invstd, int surrogate, float surrogate_scale,
+                                  const float* g_uT, const float* g_wT, const float* g_sT, float* g_u0, float* g_w0,
+                                  float* g_s0, void* stream) {
+    SPARCH_ENTER();
+    if (dirs != 1 || save_bf16 != 0) return SPARCH_EINVAL;  // a carried state is causal; the final state is read from fp32 saves
+    if (!surrogate_ok(surrogate, surrogate_scale, 0)) return SPARCH_EINVAL;
+    if (kind != SPARCH_KIND_LIF && kind != SPARCH_KIND_ADLIF) return SPARCH_EINVAL;
+    if (bn_x && (!bn_mean || !bn_invstd || !aligned16(bn_x))) return SPARCH_EINVAL;
+    const bool adapt = kind == SPARCH_KIND_ADLIF;
+    if (B <= 0 || T <= 0 || H <= 0 || !g_out || !u_save || !alpha || !u0 || !s0 || !dWx || !dparam_ws) return SPARCH_EINVAL;
+    if (adapt && (!beta || !a || !b || !w0 || !w_save)) return SPARCH_EINVAL;
+    if (!(p_drop >= 0.0f && p_drop < 1.0f)) return SPARCH_EINVAL;
+    if (!ptrs_aligned({g_out, u_save, w_save, u0, w0, s0, dWx, dparam_ws, g_uT, g_wT, g_sT, g_u0, g_w0, g_s0}))
+        return SPARCH_EALIGN;
+    CellStArgs c{};
+    c.B = B; c.dirs = 1; c.T = T; c.H = H;
+    c.alpha = alpha; c.beta = beta; c.a = a; c.b = b;
+    c.u0 = u0; c.w0 = w0; c.s0 = s0;
+    c.theta = theta; c.p_drop = p_drop; c.inv_keep = 1.0f / (1.0f - p_drop); c.seed = seed;
+    c.u_save = (float*)const_cast<void*>(u_save); c.w_save = (float*)const_cast<void*>(w_save);
+    c.save16 = 0;
+    c.g_out = g_out; c.g_rate = g_rate;
+    c.g_rate_scale = 1.0f / ((float)B * (float)T);
+    c.dWx = dWx; c.dparam_ws = dparam_ws;
+    c.bn_x = bn_x; c.bn_mean = bn_mean; c.bn_invstd = bn_invstd;
+    c.g_uT = g_uT; c.g_wT = g_wT; c.g_sT = g_sT;
+    c.g_u0 = g_u0; c.g_w0 = g_w0; c.g_s0 = g_s0;
+    const SurrogateArgs sg{surrogate, surrogate_scale};
+    return adapt ? launch_cell<true>(true, c, (hipStream_t)stream, sg) : launch_cell<false>(true, c, (hipStream_t)stream, sg);
+}
+
+extern "C" int sparch_readout_bwd_st(int B, int T, int C, const float* g_out, const float* bn_x,
+                                     const float* bn_mean, const float* bn_invstd, const float* u_save,
+                                     const float* alpha, const float* u0, float* dWx, float* dalpha_ws,
+                                     const float* g_uT, float* g_u0, void* stream) {
+    SPARCH_ENTER();
+    return readout_bwd<false>(B, T, C, g_out, bn_x, bn_mean, bn_invstd, u_save, alpha, u0, dWx, dalpha_ws, nullptr, stream,
+                              RoSt{g_uT, g_u0});
 }
 
 // The selectable readout (include/sparch_hip.h), in front of sparch_readout_bwd_pk for the same reason.

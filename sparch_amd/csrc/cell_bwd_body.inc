@@ -2,7 +2,8 @@
 // signature): template parameters ADAPT, VEC, S16, BN, DROP, the argument `c` (CellArgs, CellLenArgs or CellPkArgs) and
 // the macros below.  The families: cell_bwd_pipe_kernel / cell_bwd_pipe_sg_kernel (no lengths),
 // cell_bwd_pipe_len_kernel / cell_bwd_pipe_len_sg_kernel (ragged, masked), cell_bwd_pipe_pk_kernel /
-// cell_bwd_pipe_pk_sg_kernel (ragged, packed).
+// cell_bwd_pipe_pk_sg_kernel (ragged, packed), cell_bwd_pipe_st_kernel / cell_bwd_pipe_st_sg_kernel (stateful:
+// CellStArgs, no lengths, one direction).
 //   SURROGATE_GATE(ds, x)  the surrogate gradient's gate: boxcar_gate, or smooth_gate on the `_sg` kernels' second argument
 //   ROW_LEN(b)             the row's length; TAIL_ZERO(t, v): the incoming gradient v of step t, 0 at or past that length.
 //                          T and v itself except in the `_len` family.  (From a zero gradient the carries du, dw stay zero
@@ -12,6 +13,18 @@
 //                          which ROW0_INIT(b) loads once; 0 elsewhere)
 //   ROW_THREADS(HQ)        threads per row: HQ; packed: HQ padded to whole waves, so that ROW_T and ROW0 are wave-uniform
 //                          (scalars, like c.T), and ROW_GUARD(h) retires the lanes behind the row (empty elsewhere)
+//   ST_LOAD               stateful: declares st_gu / st_gw / st_gs, the gradient arriving on the returned final state
+//                          (u_T, w_T, s_T), 0 where the pointer is null; empty elsewhere
+//   ST_DS(t, gs)           declares ds, the spike's gradient of step t: gs - alpha du_{t+1} [+ b dw_{t+1}], added in this order.
+//                          Stateful: gs + S_t with S_t = -alpha du_{t+1} [+ b dw_{t+1}] formed FIRST, and S_T = g_sT at the
+//                          reverse pass's first step (t = T - 1, where du_{T+1} = dw_{T+1} = 0) — S_t is what ST_TAIL hands
+//                          the chunk before as its g_sT, so a chunk boundary rounds exactly as an inner step does.  g_sT
+//                          enters BEHIND the dropout scale: dropout scales the output, not the state
+//   ST_DU(t, gate)         declares du: gate + alpha du_{t+1} [+ a dw_{t+1}], in this order.  Stateful: gate + U_t with
+//                          U_t = alpha du_{t+1} [+ a dw_{t+1}] formed first, U_T = g_uT
+//   ST_ADD(t, v, g)        v + g at the reverse pass's first step, else v; (v) elsewhere (dw_T: g_wT = beta dw_{T+1})
+//   ST_TAIL                stateful: stores the initial state's gradient from the last carries du_1, dw_1 —
+//                          g_u0 = alpha du_1 + a dw_1, g_w0 = beta dw_1, g_s0 = -alpha du_1 + b dw_1; empty elsewhere
 // Text, not a function: inlined from a shared __device__ function the box-car kernels came
 // out of the compiler with another schedule, and they are held to the instructions they had (DESIGN.md section 6).
 {
@@ -50,6 +63,7 @@
     if (ADAPT) ldv<VEC>(w0v, c.w0 + (size_t)bp * H + h);
     constexpr bool drop = DROP;
     const uint64_t seed = drop ? resolve_seed(c.seed) : 0;
+    ST_LOAD
 
     struct Slot { float g[VEC]; float xr[BN ? VEC : 1]; SavedVec<VEC, S16> up; SavedVec<VEC, S16> wp; };
     const float* grow = c.g_out + ROW0(b) * HO + (size_t)d * H + h;
@@ -82,11 +96,9 @@
         for (int e = 0; e < VEC; ++e) {
             const float k = drop ? keep_scale(seed, o + e, c.p_drop, c.inv_keep) : 1.0f;
             const float gs = TAIL_ZERO(t, (q.g[e] + gr[e]) * k);
-            float ds = gs - al[e] * du_n[e];
-            if (ADAPT) ds = ds + pb[e] * dw_n[e];
+            ST_DS(t, gs)
             const float xs = u_t[e] - c.theta;
-            float du = SURROGATE_GATE(ds, xs) + al[e] * du_n[e];         // snns.py:33-35
-            if (ADAPT) du = du + pa[e] * dw_n[e];
+            ST_DU(t, SURROGATE_GATE(ds, xs))                              // snns.py:33-35
             dwx[e] = oma[e] * du;
             if (BN) {  // BatchNorm backward's column sums (dy = dWx, xhat = (x - mean) * invstd)
                 acc_dy[e] += dwx[e];
@@ -95,7 +107,7 @@
             const float qq = up[e] - sp[e];
             acc_al[e] += du * (qq - u_t[e]);  // d u_t / d alpha = (q - u_t)/(1-alpha); scaled at the end
             if (ADAPT) {
-                const float dw = be[e] * dw_n[e] - dwx[e];
+                const float dw = ST_ADD(t, be[e] * dw_n[e] - dwx[e], st_gw[e]);
                 acc_be[e] += dw * wp[e];
                 acc_a[e] += dw * up[e];
                 acc_b[e] += dw * sp[e];
@@ -142,4 +154,5 @@
         stv<VEC>(ws + 4 * plane, acc_dy);
         stv<VEC>(ws + 5 * plane, acc_dyx);
     }
+    ST_TAIL
 }

@@ -14,6 +14,15 @@
 //   ROW_STORE(t)        whether step t's dWx / s_prev16 are stored: true; packed: t < row_len (a store behind a row's
 //                       end would land in the next sequence).  Such a step's incoming gradient is zero (TAIL_ZERO), its
 //                       recurrent term is its own zero dWx row times V^T: it computes and publishes zeros.
+// The stateful rec_bwd_st_kernel (RecStArgs, whole-sequence launches, fp32 operands and saves) differs in four more, empty
+// (ST_PLUS(v, g): v) elsewhere:
+//   ST_PRE_LOAD         declares st_s / st_u: at the reverse pass's first step (t = T - 1) g_sT / g_uT of the thread's four
+//                       columns, else 0.  g_sT joins the incoming gradient BEHIND the dropout scale; g_uT stands in the
+//                       place of alpha du_{T+1} (which is 0 there)
+//   ST_POST_LOAD        declares st_w: g_wT at that step, else 0 (dw_T = g_wT - (1 - alpha) du_T)
+//   ST_PLUS(v, g)       v + g
+//   ST_TAIL             stores g_u0 = alpha du_1 + a dw_1, g_w0 = beta dw_1 and the pointwise part of g_s0,
+//                       -alpha du_1 + b dw_1 (the host adds dWx_1 Vm^T)
 {
     static_assert(CW == 1 || (CW == 2 && NW == 8 && !EXT && NP == 1), "64-column workgroups: bf16 operand mode, 8 waves");
     // cross-wave reduction tiles: written before the step's first barrier, read after it by the pointwise
@@ -197,14 +206,16 @@
         float pre_ds[4], pre_aldu[4], pre_padw[4];
         auto pre_pointwise = [&]() __attribute__((always_inline)) {
             const f32x4 al = pcol[0][d][cqx], pa = pcol[2][d][cqx], pb = pcol[3][d][cqx], gr = pcol[4][d][cqx];
+            ST_PRE_LOAD
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float k = drop ? keep_scale(seed, o_out + e, a.p_drop, a.inv_keep) : 1.0f;
-                const float gs = TAIL_ZERO(t, (gv[e] + gr[e]) * k);
+                const float gs = ST_PLUS(TAIL_ZERO(t, (gv[e] + gr[e]) * k), st_s[e]);
                 pre_aldu[e] = al[e] * du_n[e];
                 float ds = gs - pre_aldu[e];
                 pre_padw[e] = ADAPT ? pa[e] * dw_n[e] : 0.f;
                 if (ADAPT) ds = ds + pb[e] * dw_n[e];
+                pre_aldu[e] = ST_PLUS(pre_aldu[e], st_u[e]);
                 pre_ds[e] = ds;
                 asm volatile("" : "+v"(pre_ds[e]), "+v"(pre_aldu[e]), "+v"(pre_padw[e]));  // not sunk behind the barrier
             }
@@ -362,6 +373,7 @@
             sp[0] = v.x; sp[1] = v.y; sp[2] = v.z; sp[3] = v.w;
         }
         const f32x4 al = pcol[0][d][cqx], be = pcol[1][d][cqx];
+        ST_POST_LOAD
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float ds = pre_ds[e] + rec[e];
@@ -370,7 +382,7 @@
             if (ADAPT) du = du + pre_padw[e];
             dwx[e] = valid ? (1.0f - al[e]) * du : 0.0f;
             du_new[e] = du;
-            dw_new[e] = ADAPT ? be[e] * dw_n[e] - dwx[e] : 0.f;
+            dw_new[e] = ADAPT ? ST_PLUS(be[e] * dw_n[e] - dwx[e], st_w[e]) : 0.f;
             spv[e] = (t > 0) ? sp[e] : 0.0f;  // binary rows only: the s0 term of dV is added by the host
         }
         PROF_STAMP(8);  // reverse-step arithmetic
@@ -507,5 +519,6 @@
             st4(ws + 6 * plane, pacc[4][tid]);
             st4(ws + 7 * plane, pacc[5][tid]);
         }
+        ST_TAIL
     }
 }

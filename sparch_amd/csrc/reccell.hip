@@ -102,6 +102,12 @@ struct RecLenArgs : RecSgArgs { const int* lengths; };
 // the packed (`_pk`) kernels: the sorted lengths and the exclusive prefix sum (B + 1,) behind them — sequence j owns rows
 // [offsets[j], offsets[j] + lengths[j]) of every (N, .) tensor; B counts sequences and T is the longest length
 struct RecPkArgs : RecLenArgs { const int* offsets; };
+// the stateful (`_st`) backward kernels: the gradient arriving on the final state (u_T, w_T, s_T) and the gradient of the
+// initial state going out, each (Bp,H) and nullable
+struct RecStArgs : RecSgArgs {
+    const float* g_uT; const float* g_wT; const float* g_sT;
+    float* g_u0; float* g_w0; float* g_s0;
+};
 
 // Diagnostic build only (-DSPARCH_REC_PROF, never shipped): per-workgroup sums of s_memtime
 // deltas for the segments of a time step, written to a private buffer no kernel reads.
@@ -507,6 +513,11 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_fwd_kernel(
 // only: S16 is never set there).
 // ROW_LEN(b) / TAIL_ZERO(t, v): see cell_bwd_body.inc — the ragged family's row length and its select on the incoming
 // gradient (a row's recurrent term is its own dWx_{t+1} row times V^T: zero over its tail like the carries).
+// ST_PRE_LOAD / ST_POST_LOAD / ST_PLUS / ST_TAIL: the stateful family's (rec_bwd_st_kernel, behind the packed one); empty here.
+#define ST_PRE_LOAD
+#define ST_POST_LOAD
+#define ST_PLUS(v, g) (v)
+#define ST_TAIL
 #define ROW_PK_INIT
 #define T_HI a.t_end
 #define T_RING T
@@ -559,6 +570,65 @@ __global__ __launch_bounds__(64 * NW, 1) void rec_bwd_pk_kernel(RecPkArgs a)
 #undef ROW_STORE
 #undef ROW_LEN
 #undef TAIL_ZERO
+#undef ST_PRE_LOAD
+#undef ST_POST_LOAD
+#undef ST_PLUS
+#undef ST_TAIL
+// the stateful family (sparch_rec_cell_bwd_st; DESIGN.md section 6, "Stateful training"): the plain family's rows, any
+// surrogate, whole-sequence launches, fp32 operands and saves.  The gradient arriving on the final state enters at the
+// reverse pass's first step only (two wave-uniform branches with their own loads: the kernel's registers have no room to
+// hold twelve values through the loop), the initial state's goes out from the last carries.
+#define ROW_PK_INIT
+#define T_HI a.t_end
+#define T_RING T
+#define RROW(r, t) ((size_t)(r) * T + (t))
+#define ROW_STORE(t) true
+#define ROW_LEN(b) T
+#define TAIL_ZERO(t, v) (v)
+#define ST_PRE_LOAD                                                                      \
+    f32x4 st_s = {0.f, 0.f, 0.f, 0.f}, st_u = st_s;                                      \
+    if (t == T - 1) {                                                                    \
+        if (a.g_sT) st_s = ld4(a.g_sT + (size_t)bpc * H + colc);                         \
+        if (a.g_uT) st_u = ld4(a.g_uT + (size_t)bpc * H + colc);                         \
+    }
+#define ST_POST_LOAD                                                                     \
+    f32x4 st_w = {0.f, 0.f, 0.f, 0.f};                                                   \
+    if (ADAPT && t == T - 1 && a.g_wT) st_w = ld4(a.g_wT + (size_t)bpc * H + colc);
+#define ST_PLUS(v, g) ((v) + (g))
+#define ST_TAIL                                                                          \
+    if (a.t_begin == 0) {                                                                \
+        const f32x4 t_al = pcol[0][d][cqx], t_be = pcol[1][d][cqx], t_a = pcol[2][d][cqx], t_b = pcol[3][d][cqx]; \
+        f32x4 o_u, o_w, o_s;                                                             \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                  \
+            o_u[e] = t_al[e] * du_n[e];                                                  \
+            o_s[e] = -o_u[e];                                                            \
+            o_w[e] = 0.f;                                                                \
+            if (ADAPT) {                                                                 \
+                o_u[e] = o_u[e] + t_a[e] * dw_n[e];                                      \
+                o_s[e] = o_s[e] + t_b[e] * dw_n[e];                                      \
+                o_w[e] = t_be[e] * dw_n[e];                                              \
+            }                                                                            \
+        }                                                                                \
+        if (a.g_u0) st4(a.g_u0 + (size_t)bp * H + col, o_u);                             \
+        if (ADAPT && a.g_w0) st4(a.g_w0 + (size_t)bp * H + col, o_w);                    \
+        if (a.g_s0) st4(a.g_s0 + (size_t)bp * H + col, o_s);                             \
+    }
+template <bool ADAPT, int KGW, int NW, bool EXT = false, int NP = 3, bool S16 = false, int CW = 1>
+__global__ __launch_bounds__(64 * NW, 1) void rec_bwd_st_kernel(RecStArgs a)
+#define SURROGATE_GATE(ds, x) any_gate(a.sg.id, a.sg.k, ds, x)
+#include "rec_bwd_body.inc"
+#undef SURROGATE_GATE
+#undef ROW_PK_INIT
+#undef T_HI
+#undef T_RING
+#undef RROW
+#undef ROW_STORE
+#undef ROW_LEN
+#undef TAIL_ZERO
+#undef ST_PRE_LOAD
+#undef ST_POST_LOAD
+#undef ST_PLUS
+#undef ST_TAIL
 
 
 // ------------------------------------------------------------------ dense recurrent cell (ANN baselines, f-4)
@@ -890,6 +960,16 @@ RecLenArgsOf<PK> with_lengths(const RecArgs& a, const SurrogateArgs sg, const in
     if constexpr (PK) g.offsets = offsets;
     return g;
 }
+// the stateful backward kernels (RecStArgs): fp32 operands, fp32 saves, 32-column workgroups, any surrogate
+using RecStKernel = KernelRef<RecStArgs>;
+RecStKernel rec_st_kernel(bool adapt, int kgw) {
+    return rec_plan::with_kgw(kgw, [&](auto k) {
+        return rec_plan::with_bool(adapt, [&](auto ad) -> RecStKernel {
+            constexpr int K = decltype(k)::value, KB = rec_kb(K), NW = rec_nw(K);
+            return kernel_with_occupancy<RecStArgs, rec_bwd_st_kernel<decltype(ad)::value, KB, NW, false, 3, false, 1>, 64 * NW>();
+        });
+    });
+}
 // the step variants (EXT): the recurrent product comes from the caller, one k-group class, no hand-off
 template <bool BWD, bool STREAM = false>
 RecKernel rec_step_kernel(bool adapt) {
@@ -931,12 +1011,15 @@ AnnKernel ann_kernel(int act, int kgw) {
 // SG (backward): `sg` names a smooth surrogate and the pass runs on the rec_bwd_sg_kernel rows of the table
 // lengths (not null): the ragged pass, on the rec_len_kernel table (`sg` is then any surrogate); PK: its packed form
 // (offsets not null), whole-sequence launches only
-template <bool BWD, bool STREAM = false, bool SG = false, bool LEN = false, bool PK = false>
+// ST (backward): the stateful pass, on the rec_st_kernel table (`sg` is any surrogate, `stx` the six state-gradient
+// pointers), whole-sequence launches only
+template <bool BWD, bool STREAM = false, bool SG = false, bool LEN = false, bool PK = false, bool ST = false>
 int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipStream_t st, const SurrogateArgs sg = {},
-            const int* lengths = nullptr, const int* offsets = nullptr) {
+            const int* lengths = nullptr, const int* offsets = nullptr, const RecStArgs* stx = nullptr) {
     static_assert(!LEN || (!STREAM && !SG), "the ragged pass has its own table");
     static_assert(!PK || LEN, "the packed pass is a ragged one");
-    if (PK && steps_per_launch < a.T) return SPARCH_EINVAL;
+    static_assert(!ST || (BWD && !STREAM && !SG && !LEN), "the stateful pass has its own table");
+    if ((PK || ST) && steps_per_launch < a.T) return SPARCH_EINVAL;
     const bool adapt = kind == SPARCH_KIND_RADLIF;
     const bool low = sparch_operand_bf16() != 0;  // the V pack must have been made in the same mode
     const int kgw = pick_kgw(a.H);
@@ -954,17 +1037,29 @@ int run_rec(int kind, RecArgs& a, size_t chan_bytes, int steps_per_launch, hipSt
     static const int cw_env = [] { const char* e = getenv("SPARCH_REC_CW"); return e ? atoi(e) : 0; }();
     rec_plan::Policy pol;
     pol.ask_occupancy = true;
-    pol.refuse_degrade = (a.save16 && !BWD) || PK;  // bf16 saves need the whole-sequence forward launch; so do packed rows
+    pol.refuse_degrade = (a.save16 && !BWD) || PK || ST;  // bf16 saves need the whole-sequence forward launch; so do packed rows and the stateful pass
     pol.has_cw2 = !STREAM && low && kgw >= 2;
     pol.cw_override = cw_env;
     const int cus = sparch_device_cus();
     const rec_plan::Plan q = rec_plan::make_plan(a.n_rt_total, a.T, a.n_ct, steps_per_launch, cus, pol, [&](unsigned grid, int cw) {
-        if constexpr (LEN) return co_resident(rec_len_kernel<BWD, PK>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
+        if constexpr (ST) return co_resident(rec_st_kernel(adapt, kgw), grid, cus);
+        else if constexpr (LEN) return co_resident(rec_len_kernel<BWD, PK>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
         else return co_resident(rec_kernel<BWD, STREAM, SG>(adapt, low, kgw, cw, a.save16 != 0), grid, cus);
     });
     if (!q.ok) return SPARCH_EINVAL;
     // whole-sequence launches only (one agreement per launch)
     a.xcd_tab = q.whole && xcd_local_enabled() ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.chan) + hb) : nullptr;
+    if constexpr (ST) {
+        if (!q.whole || q.cw != 1 || low) return SPARCH_EINVAL;
+        const RecStKernel k = rec_st_kernel(adapt, kgw);
+        return rec_plan::walk(q, true, [&](int rt0, int n_rt, int t0, int t1) {
+            a.rt_base = rt0; a.n_rt_launch = n_rt; a.t_begin = t0; a.t_end = t1;
+            RecStArgs g = *stx;
+            static_cast<RecArgs&>(g) = a;
+            g.sg = sg;
+            return launch_kernel(k, (unsigned)(q.wg_per_rt * n_rt), g, st);
+        });
+    }
     if constexpr (LEN) {
         if (PK && !q.whole) return SPARCH_EINVAL;
         const RecLenKernelOf<PK> k = rec_len_kernel<BWD, PK>(adapt, low, kgw, q.cw, a.save16 != 0);
@@ -1243,7 +1338,7 @@ int rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                       void* chan, size_t chan_bytes, uint32_t* status,
                                       int steps_per_launch, int surrogate, float surrogate_scale, void* stream,
                                       int precision, const int* lengths, long long n_valid,
-                                      const int* offsets = nullptr) {
+                                      const int* offsets = nullptr, const RecStArgs* stx = nullptr) {
     if (!surrogate_ok(surrogate, surrogate_scale, save_bf16)) return SPARCH_EINVAL;
     PrecisionScope prec_scope_(precision);
     if (!prec_scope_.ok) return SPARCH_EINVAL;
@@ -1258,6 +1353,9 @@ int rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
     r.vpack = reinterpret_cast<const u32x4*>(vpack_t);
     r.save16 = save_bf16 != 0;
     r.chan = (u64*)chan; r.status = status;
+    if (stx)
+        return run_rec<true, false, false, false, false, true>(kind, r, chan_bytes, steps_per_launch, (hipStream_t)stream,
+                                                               SurrogateArgs{surrogate, surrogate_scale}, nullptr, nullptr, stx);
     if (lengths) {
         r.g_rate_scale = 1.0f / (float)n_valid;
         if (offsets)
@@ -1319,6 +1417,34 @@ extern "C" int sparch_rec_cell_bwd_pk(int kind, int B, int dirs, int T, int H, c
     return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
                         s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
                         steps_per_launch, surrogate, surrogate_scale, stream, precision, lengths, n_valid, offsets);
+}
+extern "C" int sparch_rec_cell_bwd_st(int kind, int B, int dirs, int T, int H, const float* g_out,
+                                      const float* g_rate, const void* u_save, const void* w_save, int save_bf16,
+                                      const float* alpha, const float* beta, const float* a,
+                                      const float* b, const float* vpack_t, const float* u0,
+                                      const float* w0, const float* s0, float theta, float p_drop,
+                                      uint64_t seed, float* dWx, uint16_t* s_prev16, float* dparam_ws,
+                                      const float* bn_x, const float* bn_mean, const float* bn_invstd,
+                                      void* chan, size_t chan_bytes, uint32_t* status,
+                                      int steps_per_launch, int surrogate, float surrogate_scale,
+                                      const float* g_uT, const float* g_wT, const float* g_sT, float* g_u0,
+                                      float* g_w0, float* g_s0, void* stream, int precision) {
+    SPARCH_ENTER();
+    // a carried state is causal, the final state is read from fp32 saves, whole-sequence launches, fp32 operands, H <= 1024
+    if (dirs != 1 || save_bf16 != 0 || steps_per_launch < T || precision != 0 || H > 1024) return SPARCH_EINVAL;
+    if (!al16({g_uT, g_wT, g_sT, g_u0, g_w0, g_s0})) {
+        // (behind the sibling's SPARCH_EINVAL checks, like every SPARCH_EALIGN: run them first on the plain arguments)
+        const int rc = rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t,
+                                    u0, w0, s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd,
+                                    nullptr, 0, status, steps_per_launch, surrogate, surrogate_scale, stream, precision,
+                                    nullptr, 0);
+        return rc == SPARCH_EINVAL ? rc : SPARCH_EALIGN;
+    }
+    RecStArgs stx{};
+    stx.g_uT = g_uT; stx.g_wT = g_wT; stx.g_sT = g_sT; stx.g_u0 = g_u0; stx.g_w0 = g_w0; stx.g_s0 = g_s0;
+    return rec_cell_bwd(kind, B, dirs, T, H, g_out, g_rate, u_save, w_save, save_bf16, alpha, beta, a, b, vpack_t, u0, w0,
+                        s0, theta, p_drop, seed, dWx, s_prev16, dparam_ws, bn_x, bn_mean, bn_invstd, chan, chan_bytes, status,
+                        steps_per_launch, surrogate, surrogate_scale, stream, precision, nullptr, 0, nullptr, &stx);
 }
 extern "C" int sparch_rec_cell_bwd(int kind, int B, int dirs, int T, int H, const float* g_out,
                                    const float* g_rate, const void* u_save, const void* w_save, int save_bf16,

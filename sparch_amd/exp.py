@@ -148,6 +148,21 @@ def parse_readout(value):
     return name
 
 
+def parse_tbptt(value):
+    """SPARCH_TBPTT=K: unset or empty -> None (whole-sequence training, nothing changes); else the chunk length K, an
+    integer >= 1 (truncated BPTT: SNN.forward(state=..., return_state=True)); anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    try:
+        k = int(value.strip())
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise ValueError(f"SPARCH_TBPTT={value!r}: the chunk length in time steps, an integer >= 1 (unset: every batch is "
+                         "one whole-sequence step)")
+    return k
+
+
 def _step_lengths(seq, lengths):
     B, T = seq.shape[0], seq.shape[1]
     if lengths is None:
@@ -237,8 +252,25 @@ class Experiment:
             if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
                 raise ValueError(f"sparch_amd: SPARCH_READOUT needs a spiking model (got {self.model_type})")
 
+        # SPARCH_TBPTT=K: classic truncated BPTT — every training batch is cut into ceil(T / K) chunks, each started from
+        # the detached state the one before ended in, with one optimizer step per chunk ("Stateful
+        # training").  Validation and test are unchanged.
+        self.tbptt = parse_tbptt(os.environ.get("SPARCH_TBPTT"))
+        self._tbptt_steps = 0  # optimizer steps taken by chunks (logged per epoch)
+        if self.tbptt is not None:
+            for on, what in ((mode, f"SPARCH_LENGTHS={mode}"), (self.per_step_loss is not None, "SPARCH_PER_STEP_LOSS"),
+                             (self.readout not in (None, "softmax_sum"), f"SPARCH_READOUT={self.readout}"),
+                             (getattr(args, "bidirectional", False), "--bidirectional"), (self.sync_bn, "--sync_bn"),
+                             (self.compute_dtype == "bf16", "--compute_dtype bf16")):
+                if on:
+                    raise ValueError(f"sparch_amd: SPARCH_TBPTT with {what} is not supported")
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
+                raise ValueError(f"sparch_amd: SPARCH_TBPTT needs a spiking model (got {self.model_type})")
+
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
+        if self.tbptt is not None and self.world > 1:  # (known only now; on every rank alike, before the first collective)
+            raise ValueError("sparch_amd: SPARCH_TBPTT in a data-parallel run is not supported")
         # The HD / SC loaders (file and resident) pad each batch to its own longest clip, so ranks hold different numbers of rows
         # (B * T); the --sync_bn exchange (functional._Norm) gathers equal-sized statistics from every rank.  Refused
         # on every rank alike, before the first collective.
@@ -520,6 +552,29 @@ class Experiment:
             return self.net(x, lengths=xlens, pack=True)
         return self.net(x, lengths=xlens)
 
+    def _train_batch_tbptt(self, x, y):
+        """SPARCH_TBPTT=K: one training batch as ceil(T / K) chunks of K steps.  The first chunk starts from the usual
+        draw, each later one from the detached state the one before ended in; per chunk: forward, the loss on the
+        chunk's own output and firing rates, backward, one optimizer step.  Returns (the mean of the chunks' losses, the
+        summed output — the whole sequence's under the parameters as they moved —, the mean firing rates)."""
+        from .snns import detach_state
+        K, T = self.tbptt, x.shape[1]
+        state, total, chunk_losses, rates = None, None, [], []
+        for t0 in range(0, T, K):
+            out, fr, state = self.net(Fn.time_slice(x, t0, min(t0 + K, T)), state=state, return_state=True)
+            state = detach_state(state)
+            loss_val = self.loss_fn(out, y)
+            chunk_losses.append(loss_val.detach())
+            if self.use_regularizers:
+                loss_val = loss_val + self.reg_factor * (F.relu(self.reg_fmin - fr).sum() + F.relu(fr - self.reg_fmax).sum())
+            self.opt.zero_grad()
+            loss_val.backward()
+            self.opt.step()
+            self._tbptt_steps += 1
+            total = out.detach() if total is None else total + out.detach()
+            rates.append(fr.detach())
+        return torch.stack(chunk_losses).mean(), total, torch.stack(rates).mean(dim=0)
+
     def _mean_over_ranks(self, value):
         if self.world == 1:
             return value
@@ -541,6 +596,16 @@ class Experiment:
         # values, the same float64 means — and the kernels' status word is checked at the same point.
         for step, (x, xlens, y) in enumerate(self._prefetched(self.train_loader)):
             x, y = self._to_device(x, y)
+            if self.tbptt is not None:
+                loss_val, output, firing_rates = self._train_batch_tbptt(x, y)
+                losses.append(loss_val)
+                epoch_spike_rate += torch.mean(firing_rates)
+                accs.append((y == torch.argmax(output, dim=1)).sum())
+                sizes.append(y.shape[0])
+                seen += x.shape[0] * x.shape[1]
+                if (step + 1) % self.status_check_every == 0:
+                    self._check_kernels(e, step)
+                continue
             output, firing_rates, *seq = self._net(x, xlens)
             loss_val = self.loss_fn(output, y)
             losses.append(loss_val.detach())
@@ -571,6 +636,9 @@ class Experiment:
         logging.info(f"Epoch {e}: lr={self.opt.param_groups[-1]['lr']}")
         logging.info(f"Epoch {e}: train loss={self._mean_over_ranks(np.mean(losses))}")
         logging.info(f"Epoch {e}: train acc={self._mean_over_ranks(np.mean(accs))}")
+        if self.tbptt is not None:
+            logging.info(f"Epoch {e}: SPARCH_TBPTT={self.tbptt}: optimizer steps={self._tbptt_steps}")
+            self._tbptt_steps = 0  # (a per-epoch figure)
         if early_losses:
             early = torch.stack(early_losses).cpu().numpy().astype(np.float64)
             logging.info(f"Epoch {e}: train per-step loss={self._mean_over_ranks(np.mean(early))}")

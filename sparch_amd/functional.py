@@ -333,6 +333,20 @@ def input_plane_of(x):
     return tag[1], tag[2]
 
 
+def time_slice(x, t0, t1):
+    """Steps [t0, t1) of a network input (B,T,K) as an input of its own: a contiguous copy, or — for an input made by
+    `input_from_counts` — a placeholder that carries the same rows of the bf16 plane (chunks of a stateful run)."""
+    tag = input_plane_of(x)
+    if tag is None:
+        return x[:, t0:t1].contiguous()
+    B, T, K = x.shape
+    plane, flag = tag
+    part = plane.view(B, T, plane.shape[-1])[:, t0:t1].contiguous().view(-1, plane.shape[-1])
+    xs = spike_placeholder(B, t1 - t0, K, x.device).view(B, t1 - t0, K)
+    xs._sparch_input_plane = (tuple(xs.shape), part, flag)
+    return xs
+
+
 def split_planes(W):
     """The three exact bf16 planes of a weight matrix, (3, *W.shape) bf16 (W = p0 + p1 + p2 exactly, the
     truncation split the GEMM kernels otherwise redo in every workgroup that stages a tile of W); None where
@@ -867,6 +881,40 @@ def _check_ragged(lengths, dirs, recurrent, H):
                          "(the per-step recurrent path takes no lengths)")
 
 
+def check_stateful(kind=None, H=0, *, dirs=1, lengths=None, pack=None, per_step=None, readout=None, T=None):
+    """The refusals of stateful training (`state` / `return_state`), each before any kernel.
+    kind=None: the readout layer."""
+    if dirs != 1:
+        raise ValueError("sparch_amd: state / return_state with bidirectional=True is not supported (a carried state "
+                         "is causal: the reverse direction would start where the stream has not arrived yet)")
+    if pack is not None:  # (in front of lengths: a packed batch always comes with them)
+        raise ValueError("sparch_amd: state / return_state with pack is not supported (the packed kernels have no "
+                         "stateful form)")
+    if lengths is not None:
+        raise ValueError("sparch_amd: state / return_state with lengths is not supported (the kernels with lengths "
+                         "have no stateful form)")
+    if per_step is not None:
+        raise ValueError("sparch_amd: state / return_state with per_step is not supported (the per-step readout has "
+                         "no stateful form)")
+    if readout_mode(readout) != 0:
+        raise ValueError(f"sparch_amd: state / return_state with readout={readout!r} is not supported (chunks add up "
+                         "under the softmax-sum only)")
+    if SAVE_BF16:
+        raise ValueError("sparch_amd: state / return_state with SPARCH_SAVE_DTYPE=bf16 is not supported (the final "
+                         "state is read from the fp32 saves)")
+    if _prec() != 0:
+        raise ValueError("sparch_amd: state / return_state in the bf16 operand mode is not supported")
+    if kind is not None and KIND[kind] & 2:
+        if rec_step_path(H):
+            raise ValueError(f"sparch_amd: state / return_state with a recurrent hidden size above 1024 (got {H}) is not "
+                             "supported (the per-step recurrent path has no stateful form)")
+        L = rec_steps_per_launch(T if T is not None else 1 << 30)
+        if L < (T if T is not None else 2):
+            raise ValueError("sparch_amd: state / return_state in the degraded or chunked recurrent launch modes "
+                             f"({L} steps per launch) is not supported (the stateful recurrent backward runs whole "
+                             "sequences only)")
+
+
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
                  want_s_out=True, want_saves=True, surrogate=None, lengths=None, pack=None):
     """Run one spiking cell over the whole sequence on the device.
@@ -972,7 +1020,8 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
 
 
 def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, theta, p_drop, seed,
-                  steps_per_launch=None, bn=None, surrogate=None, lengths=None, pack=None):
+                  steps_per_launch=None, bn=None, surrogate=None, lengths=None, pack=None, state_grads=None,
+                  want_state_grads=False):
     """Reverse-time pass.  Returns dWx (B*dirs,T,H) [virtual rows, original time index],
     param grads dict (alpha[,beta,a,b][,V]) — plus, with bn = (Wx_raw (B,T,H), mean, invstd), the entry
     "bn_sums" = (dbeta, dgamma): BatchNorm backward's column sums, accumulated by the same kernel.
@@ -980,12 +1029,25 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
     `_sg` entry points with (id, scale) in front of the stream (timer labels unchanged).
     lengths: as in cell_forward — the `_len` entry points (one per family, any surrogate) take the incoming gradient of
     a row's padded steps as zero, whatever g_out holds there; dWx is exactly 0 on them.
-    pack: as in cell_forward (B = 1, T = n: g_out, dWx and bn's projection are the packed (1, n, .) tensors)."""
+    pack: as in cell_forward (B = 1, T = n: g_out, dWx and bn's projection are the packed (1, n, .) tensors).
+    state_grads / want_state_grads (stateful training): state_grads = (g_uT, g_wT, g_sT), each
+    (B,H) or None, is the gradient arriving on the chunk's final state (u_T, w_T, s_T = 1[u_T > theta]);
+    want_state_grads=True adds the entry "state" = (g_u0, g_w0, g_s0), the gradient of the initial state (g_w0 None
+    without adaptation).  Either issues sparch_cell_bwd_st (timer label unchanged); neither: the calls above."""
     sg = surrogate_args(surrogate)
     Bp = B * dirs
     dev = g_out.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    stateful = want_state_grads or (state_grads is not None and any(g is not None for g in state_grads))
+    if stateful:
+        check_stateful(kind, H, dirs=dirs, lengths=lengths, pack=pack,
+                       T=T if steps_per_launch is None or steps_per_launch >= T else None)
+        if steps_per_launch is not None and steps_per_launch < T and recurrent:
+            raise ValueError("sparch_amd: state / return_state in the degraded or chunked recurrent launch modes is not "
+                             "supported (the stateful recurrent backward runs whole sequences only)")
+        if saved[0].dtype != torch.float32:
+            raise ValueError("sparch_amd: stateful training needs fp32 saves (SPARCH_SAVE_DTYPE=bf16 is not supported)")
     _check_ragged(lengths, dirs, recurrent, H)
     _check_packed(pack, dirs, recurrent, H)
     len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
@@ -997,10 +1059,17 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         pp = {k_: (torch.nn.functional.pad(v, (0, H4 - H, 0, H4 - H)) if k_ == "V" else padh(v)) for k_, v in p.items()}
         g_p = padh(g_out.reshape(B, T, dirs, H)).reshape(B, T, dirs * H4)
         gr_p = None if g_rate is None else padh(g_rate.reshape(dirs, H)).reshape(dirs * H4)
+        st_kw = {}
+        if stateful:  # (the padding's state is zero and stays zero: its incoming gradient is zero, its outgoing one cut off)
+            st_kw = {"state_grads": tuple(padh(g) for g in (state_grads or (None, None, None))),
+                     "want_state_grads": want_state_grads}
         dWx_p, gp = cell_backward(kind, g_p, gr_p, pp, padh(u0), padh(w0), padh(s0), saved, B=B, dirs=dirs, T=T, H=H4,
                                   theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
-                                  surrogate=surrogate, lengths=lengths, pack=pack)
+                                  surrogate=surrogate, lengths=lengths, pack=pack, **st_kw)
+        state_p = gp.pop("state", None)
         grads = {k_: (v[:H, :H].contiguous() if k_ == "V" else v[:H].contiguous()) for k_, v in gp.items()}
+        if state_p is not None:
+            grads["state"] = tuple(None if g is None else g[:, :H].contiguous() for g in state_p)
         return dWx_p[..., :H].contiguous(), grads
     vpack_fwd_made = saved[2] if len(saved) > 2 else None  # backward fragments of V packed by cell_forward
     save16 = u_save.dtype == torch.bfloat16
@@ -1017,7 +1086,15 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                 ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
                 ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
                 ptr(bn_invstd))
-        if pack is not None:
+        if stateful:
+            g_in = [None if g is None else _f32c(g) for g in (state_grads or (None, None, None))]
+            g_0 = [torch.empty(B, H, dtype=torch.float32, device=dev) if (want_state_grads and (i != 1 or adaptive))
+                   else None for i in range(3)]
+            check(lib.sparch_cell_bwd_st(*lead, *sg_len, *(ptr(g) for g in g_in), *(ptr(g) for g in g_0), _stream()),
+                  "sparch_cell_bwd_st")
+            if want_state_grads:
+                grads["state"] = tuple(g_0)
+        elif pack is not None:
             check(lib.sparch_cell_bwd_pk(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_pk")
         elif lengths is not None:
             check(lib.sparch_cell_bwd_len(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_len")
@@ -1052,7 +1129,14 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
         else:
             vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
             entry = ("sparch_rec_cell_bwd_pk" if pack is not None else "sparch_rec_cell_bwd_len" if lengths is not None
+                     else "sparch_rec_cell_bwd_st" if stateful
                      else "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg")
+            sg_tail = sg_len if (lengths is not None or pack is not None) else sg
+            if stateful:
+                g_in = [None if g is None else _f32c(g) for g in (state_grads or (None, None, None))]
+                g_0 = [torch.empty(Bp, H, dtype=torch.float32, device=dev) if (want_state_grads and (i != 1 or adaptive))
+                       else None for i in range(3)]
+                sg_tail = (*sg_len, *(ptr(g) for g in g_in), *(ptr(g) for g in g_0))
             _persistent(f"rec_cell_bwd[{kind}]", entry,
                         (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
                          ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack_t), ptr(u0),
@@ -1060,7 +1144,15 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                          ptr(bn_invstd), *len_args),
                         lib.sparch_rec_chan_bytes(Bp, T, H), dev,
                         steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec(),
-                        sg=sg_len if (lengths is not None or pack is not None) else sg)
+                        sg=sg_tail)
+            if stateful and want_state_grads:
+                # g_s0's third term, (dWx_1) Vm^T: one (B' x H)(H x H) product on the first step's dWx (the kernel wrote
+                # the two pointwise terms)
+                vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
+                check(lib.sparch_vmask(H, ptr(V), ptr(vmask), _stream()), "sparch_vmask")
+                rec1, _ = gemm_nt(dWx[:, 0, :].contiguous(), vmask)  # rec1[b,i] = sum_j dWx_1[b,j] Vm[i,j]
+                g_0[2] = g_0[2] + rec1
+                grads["state"] = tuple(g_0)
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
@@ -1110,7 +1202,7 @@ class SpikingLayerFn(torch.autograd.Function):
         s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
                                                 dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
                                                 want_s_out=cfg.get("fp32_out", True),
-                                                want_saves=any(ctx.needs_input_grad),
+                                                want_saves=any(ctx.needs_input_grad) or bool(cfg.get("stateful")),
                                                 surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
                                                 **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
         if s_out is None:
@@ -1125,10 +1217,19 @@ class SpikingLayerFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # no zero tensors for unused outputs (s16 is as large as s in bf16)
         ctx.save_for_backward(inp.x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw)
         ctx.mark_non_differentiable(s16)
+        if cfg.get("stateful"):
+            # the final state: with fp32 saves the last saved step IS u_T / w_T, and s_T = 1[u_T > theta] is the raw
+            # spike, before dropout (how the kernels themselves resume); outputs of this node, so that a gradient on
+            # them reaches backward() as g_uT / g_wT / g_sT
+            # (a recurrent width that runs zero-padded saves the padded width: the state goes out unpadded)
+            u_T = saved[0][:, T - 1, :H].contiguous()
+            w_T = saved[1][:, T - 1, :H].contiguous() if saved[1] is not None else None
+            s_T = (u_T > theta).to(torch.float32)
+            return s_out, rate, s16, u_T, w_T, s_T
         return s_out, rate, s16
 
     @staticmethod
-    def backward(ctx, g_s, g_rate, _g_s16=None):
+    def backward(ctx, g_s, g_rate, _g_s16=None, g_uT=None, g_wT=None, g_sT=None):
         cfg = ctx.cfg
         kind, norm, dirs = cfg["kind"], cfg["normalization"], cfg["dirs"]
         B, T, K, H = ctx.shape
@@ -1143,18 +1244,23 @@ class SpikingLayerFn(torch.autograd.Function):
         p = {k_: v for k_, v in p.items() if v is not None}
         # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
+        st_kw = {}
+        if cfg.get("stateful"):  # (absent otherwise: the calls and their arguments are then what they always were)
+            st_kw = {"state_grads": (g_uT, g_wT, g_sT), "want_state_grads": any(ctx.needs_input_grad[11:14])}
         dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
                                 theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn,
                                 surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
-                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
+                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}), **st_kw)
         ctx.cell_saved = None
         dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
                                                   sums=pg.get("bn_sums"), w_planes=ctx.w_planes, dx_planes=True)
         dx = None if dx is None else dx.view(B, T, K)
         ctx.w_planes = ctx.inp = None
+        g_u0, g_w0, g_s0 = pg.get("state", (None, None, None))
+        need = ctx.needs_input_grad
         return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
-                pg.get("V"), None, None, None)
+                pg.get("V"), g_u0 if need[11] else None, g_w0 if need[12] else None, g_s0 if need[13] else None)
 
 
 SEQ_MODES = {"prob": 0, "sum": 1}  # per-step readout: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM
@@ -1250,6 +1356,11 @@ class ReadoutLayerFn(torch.autograd.Function):
         ctx.shape = (B, T, K, C)
         ctx.nsaved = nsaved
         ctx.save_for_backward(inp.x2, W, nw, alpha, u0, u_save, Wx_raw)
+        if cfg.get("stateful"):  # (out, u_T): the final membrane is the last saved step; its gradient comes back as g_uT
+            if red != 0 or mode is not None or pack is not None or lengths is not None:
+                raise ValueError("sparch_amd: the stateful readout is the plain softmax-sum's")
+            ctx.set_materialize_grads(False)
+            return out, u_save[:, T - 1].contiguous()
         return out if mode is None else (out, seq)
 
     @staticmethod
@@ -1260,6 +1371,9 @@ class ReadoutLayerFn(torch.autograd.Function):
         x2, W, nw, alpha, u0, u_save, Wx_raw = ctx.saved_tensors
         M = B * T
         dev = x2.device
+        stateful, g_uT, g_u0 = bool(cfg.get("stateful")), None, None
+        if stateful:  # the second output was u_T, not seq
+            g_uT, g_seq = g_seq, None
         mode = seq_mode(cfg.get("per_step"))
         if g_seq is None:
             mode = None  # nothing came back through seq: the plain kernels
@@ -1276,7 +1390,12 @@ class ReadoutLayerFn(torch.autograd.Function):
                 ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
         lengths = cfg.get("lengths")
         red = readout_mode(cfg.get("readout"))
-        if red != 0:
+        if stateful:
+            g_uT = None if g_uT is None else _f32c(g_uT)
+            if ctx.needs_input_grad[7]:
+                g_u0 = torch.empty(B, C, dtype=torch.float32, device=dev)
+            check(lib.sparch_readout_bwd_st(*lead, ptr(g_uT), ptr(g_u0), _stream()), "sparch_readout_bwd_st")
+        elif red != 0:
             check(lib.sparch_readout_bwd_red(*lead, *_readout_red_tail(red, ctx.red_arg, lengths, pack), _stream()),
                   "sparch_readout_bwd_red")
         elif mode is not None:
@@ -1303,7 +1422,7 @@ class ReadoutLayerFn(torch.autograd.Function):
                                                   sums=sums)
         dx = None if dx is None else dx.view(*ctx.shape[:3])
         ctx.inp = None
-        return None, dx, dW, dWb, dnw, dnb, dalpha, None
+        return None, dx, dW, dWb, dnw, dnb, dalpha, g_u0
 
 
 class SpikingCellFn(torch.autograd.Function):

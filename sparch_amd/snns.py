@@ -483,7 +483,8 @@ class _SpikingLayer(nn.Module):
         return p
 
     # ------------------------------------------------------------------ forward
-    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None, pack=None):
+    def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None, pack=None,
+                          return_state=False):
         """Returns (spikes (B,T,H*(1+bidir)), firing_rate (H*(1+bidir),)).  Equivalent to the
         reference forward (e.g. snns.py:663-694) followed by `.mean(dim=(0,1))` (174).
         states: (u0, w0, s0) drawn ahead of time by SNN.forward (same generator, same order);
@@ -495,7 +496,13 @@ class _SpikingLayer(nn.Module):
         lengths: None, or what prepare_lengths() returned for this batch — the layer's output is then exactly 0 on
         every row's padded steps and the firing rate is the mean over valid steps (SNN.forward has the contract).
         pack: None, or what prepare_packing() returned — x is then the PACKED batch (1, n, feat) (functional.pack_rows)
-        and so is the result; `states` hold the plan's `batch` rows in its sorted order (drawn so when not given)."""
+        and so is the result; `states` hold the plan's `batch` rows in its sorted order (drawn so when not given).
+        return_state=True (stateful training, SNN.forward has the contract): returns (spikes, firing_rate, state) with
+        state = {"u": u_T, ["w": w_T,] "s": 1[u_T > threshold]}, the raw spike before dropout; the three are nodes of the
+        graph, and the gradient of `states` comes out of the backward.  LIF / adLIF, one direction, no lengths / pack."""
+        if return_state:
+            Fn.check_stateful(self.kind, self.hidden_size, dirs=2 if self.bidirectional else 1, lengths=lengths, pack=pack,
+                              T=x.shape[1])
         if lengths is not None:
             _check_ragged_layer(self, lengths)
         if pack is not None:
@@ -535,14 +542,19 @@ class _SpikingLayer(nn.Module):
             cfg["lengths"] = lengths
         if pack is not None:
             cfg["pack"] = pack
+        if return_state:
+            cfg["stateful"] = True
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
-        s, rate, s16 = Fn.SpikingLayerFn.apply(
+        s, rate, s16, *final = Fn.SpikingLayerFn.apply(
             cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha,
             getattr(self, "beta", None), getattr(self, "a", None), getattr(self, "b", None),
             self.V.weight if hasattr(self, "V") else None, u0, w0, s0)
         # lets the next layer take the exact bf16-split GEMMs and read the spikes as a bf16 plane (half the bytes)
         _tag_spikes(s, 1.0 / (1.0 - p_drop), s16, placeholder=not fp32_out and not s.is_contiguous())
+        if return_state:
+            u_T, w_T, s_T = final
+            return s, rate, ({"u": u_T, "s": s_T} if w_T is None else {"u": u_T, "w": w_T, "s": s_T})
         return s, rate
 
     def forward(self, x):
@@ -624,16 +636,20 @@ class ReadoutLayer(nn.Module):
         name = getattr(self, "readout", "softmax_sum")
         return "" if name == "softmax_sum" else f"readout={name}"
 
-    def forward(self, x, u0=None, lengths=None, pack=None, per_step=None):
+    def forward(self, x, u0=None, lengths=None, pack=None, per_step=None, return_state=False):
         """lengths: None, or prepare_lengths()'s result — out[b] is then the sum of softmax(u_t) over t < lengths[b].
         pack: None, or prepare_packing()'s result — x is the packed batch (1, n, feat); out and u0 hold the plan's
         `batch` rows in its sorted order.
         per_step: None — returns out (batch, classes) — or "prob" / "sum" — returns (out, seq) with seq (batch, time,
         classes) = softmax(u_t), or the running sum of `out` after step t (seq[:, -1] is out); with lengths, seq is 0
-        at t >= lengths[b].  Both are differentiable.  Not with pack."""
+        at t >= lengths[b].  Both are differentiable.  Not with pack.
+        return_state=True (stateful training): returns (out, {"u": u_T}) — out is this chunk's own sum, u_T a node of the
+        graph; the default readout only, no lengths / pack / per_step."""
         Fn.seq_mode(per_step)
         readout = getattr(self, "readout", "softmax_sum")  # (a module pickled before the attribute: the default)
         Fn.readout_mode(readout)
+        if return_state:
+            Fn.check_stateful(lengths=lengths, pack=pack, per_step=per_step, readout=readout)
         if per_step is not None and readout != "softmax_sum":
             raise ValueError(f"sparch_amd: per_step with readout={readout!r} is not supported (the per-step readout is "
                              "the softmax-sum's)")
@@ -667,6 +683,10 @@ class ReadoutLayer(nn.Module):
             cfg["readout"] = readout
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
+        if return_state:
+            cfg["stateful"] = True
+            out, u_T = Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
+            return out, {"u": u_T}
         return Fn.ReadoutLayerFn.apply(cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha, u0)
 
     def _readout_cell(self, Wx):
@@ -759,6 +779,13 @@ def _check_ragged_layer(layer, lengths=None):
 
 
 _LAYER_CLASSES = {"LIF": LIFLayer, "adLIF": adLIFLayer, "RLIF": RLIFLayer, "RadLIF": RadLIFLayer}
+
+
+def detach_state(state):
+    """A state as SNN.forward(return_state=True) returns it, cut out of the graph: fed to the next chunk it gives
+    classic truncated BPTT (no gradient crosses the boundary, and the chunk's saved tensors are freed by its own
+    backward)."""
+    return [{k: v.detach() for k, v in st.items()} if isinstance(st, dict) else st.detach() for st in state]
 
 
 def _global_forward_hooks():
@@ -914,7 +941,61 @@ class SNN(nn.Module):
                     fill(w0)
                 fill(s0)
 
-    def forward(self, x, lengths=None, pack=False, per_step=None):
+    def _check_stateful(self, lengths, pack, per_step, T):
+        """Every refusal of state / return_state, before the first kernel."""
+        if getattr(self, "_static_states", None) is not None:
+            raise ValueError("sparch_amd: state / return_state inside a captured step (GraphedTrainStep) is not "
+                             "supported: the carried state changes with every chunk")
+        last = self.num_layers - 1
+        for i, layer in enumerate(self.snn):
+            if self.use_readout_layer and i == last:
+                Fn.check_stateful(lengths=lengths, pack=pack if pack else None, per_step=per_step,
+                                  readout=getattr(layer, "readout", "softmax_sum"))
+            else:
+                Fn.check_stateful(layer.kind, layer.hidden_size, dirs=2 if layer.bidirectional else 1, lengths=lengths,
+                                  pack=pack if pack else None, per_step=per_step, T=T)
+
+    def _states_from(self, state, batch, device):
+        """A caller's `state` (one dict per layer, StreamingSNN.get_state()'s format; other keys, such as its `out` and
+        `steps`, are ignored) -> the list SNN.forward runs on: (u0, w0, s0) per hidden layer, the readout's u0 last."""
+        if len(state) != len(self.snn):
+            raise ValueError(f"sparch_amd: state has {len(state)} entries for {len(self.snn)} layers")
+        last = self.num_layers - 1
+
+        def take(st, what, i, cols):
+            t = st.get(what) if isinstance(st, dict) else None
+            if not torch.is_tensor(t):
+                raise ValueError(f"sparch_amd: state[{i}] has no {what!r}")
+            if tuple(t.shape) != (batch, cols):
+                raise ValueError(f"sparch_amd: state[{i}][{what!r}] is {tuple(t.shape)}, expected {(batch, cols)}")
+            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"sparch_amd: state[{i}][{what!r}] must be a contiguous float32 tensor on {device}")
+            return t
+
+        states = []
+        for i, (layer, st) in enumerate(zip(self.snn, state)):
+            if self.use_readout_layer and i == last:
+                states.append(take(st, "u", i, layer.hidden_size))
+                continue
+            adaptive = layer.kind in ("adLIF", "RadLIF")
+            states.append((take(st, "u", i, layer.hidden_size), take(st, "w", i, layer.hidden_size) if adaptive else None,
+                           take(st, "s", i, layer.hidden_size)))
+        return states
+
+    def forward(self, x, lengths=None, pack=False, per_step=None, state=None, return_state=False):
+        """state / return_state (stateful training): `out, rates, state = net(x, state=st,
+        return_state=True)` starts every layer from `st` — a list with one entry per layer, {"u", ["w",] "s"} (batch,
+        hidden) per hidden layer and {"u"} (batch, classes) for the readout, StreamingSNN.get_state()'s format — instead
+        of drawing from the host generator, and returns the state the chunk ended in: u_T, w_T and the raw spike
+        s_T = 1[u_T > threshold] (before dropout) per hidden layer, u_T for the readout.  `out` is the chunk's own
+        softmax-sum: the caller adds chunks.  The returned tensors are nodes of the graph: kept, the gradient crosses
+        the chunk boundary exactly; through detach_state() it is classic truncated BPTT.  A `state` tensor with
+        requires_grad gets its gradient.  state=None draws as always; return_state=False returns what it always did."""
+        stateful = state is not None or return_state
+        if stateful:  # (the refusals come before anything else)
+            self._check_stateful(lengths, pack, per_step, x.shape[1])
+            if state is not None:
+                state = self._states_from(state, x.shape[0], x.device)
         if per_step is not None:  # (the refusals come before anything else)
             Fn.seq_mode(per_step)
             if pack:
@@ -951,15 +1032,21 @@ class SNN(nn.Module):
         # the round-2 kernel trace).
         last = self.num_layers - 1
         states = getattr(self, "_static_states", None)  # graph mode: refilled by draw_states_into() per step
-        if states is None:
+        if state is not None:  # a carried state: nothing is drawn
+            states = state
+        elif states is None:
             states = self.draw_states(x.shape[0], x.device)
         rates = []
+        final = []  # stateful: every layer's final state
         wait = getattr(states, "wait_ready", None)  # the states' upload runs under the first projection GEMM
         for i, layer in enumerate(self.snn):
             if self.use_readout_layer and i == last:
                 if wait is not None:
                     wait()
-                if per_step is not None:
+                if stateful:
+                    x, st = layer(x, u0=states[i], return_state=True)
+                    final.append(st)
+                elif per_step is not None:
                     x, seq = layer(x, u0=states[i], lengths=lengths, per_step=per_step)
                 else:
                     x = layer(x, u0=states[i]) if lengths is None else layer(x, u0=states[i], lengths=lengths)
@@ -967,12 +1054,19 @@ class SNN(nn.Module):
                 # between two layers of ours the spikes travel as a bf16 plane: no fp32 copy (unless somebody
                 # else may look at the layer's output: forward hooks, the network's own output)
                 inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
-                x, r = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
-                                               fp32_out=not inner, **({} if lengths is None else {"lengths": lengths}))
+                if stateful:
+                    x, r, st = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
+                                                       fp32_out=not inner, return_state=True)
+                    final.append(st)
+                else:
+                    x, r = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
+                                                   fp32_out=not inner, **({} if lengths is None else {"lengths": lengths}))
                 if wait is not None:
                     wait()  # (no-op once the first layer's call has waited)
                 rates.append(r)
         firing_rates = torch.cat(rates) if len(rates) > 1 else rates[0]
+        if return_state:
+            return x, firing_rates, final
         if per_step is not None:
             return x, firing_rates, seq
         return x, firing_rates
