@@ -1206,6 +1206,37 @@ int sparch_expand_counts_u8(long long M, int K, const uint8_t* counts, uint16_t*
 int sparch_ce_loss(int B, int C, const float* logits, const int64_t* labels, float* loss, float* dlogits,
                    void* stream);
 
+/* ---- Axonal delays (csrc/delay.hip): one learnable time shift per input feature of a layer.
+ * delay (K) fp32 is the parameter theta; the kernels take d_i = (int)rintf(min(max(theta_i, 0), max_delay)) themselves
+ * (ties to even, a NaN gives 0), 1 <= max_delay <= 255: the host never reads theta.  With len_b the row's own length
+ * (T without lengths) and x[b,-1,i] = 0:
+ *   y[b,t,i]   = x[b,t-d_i,i]   if d_i <= t < len_b,  else 0
+ *   g_x[b,t,i] = g_y[b,t+d_i,i] if t + d_i < len_b,   else 0        (what g_y holds at t >= len_b is never read)
+ *   g_delay[i] = gate_i * sum_b sum_{t=d_i}^{len_b-1} g_y[b,t,i] * x_scale * (x[b,t-d_i-1,i] - x[b,t-d_i,i]),
+ *   gate_i     = 1 if 0 <= theta_i <= max_delay else 0
+ * x, y: (B,T,K) elements of elem_size 2 or 4 bytes moved as raw bytes (the bf16 spike plane, fp32 tensors), unit stride
+ * along K, rows ldx / ldy ELEMENTS apart (>= K; batch row b starts at row b T); g_y, g_x fp32 likewise (ldg, ldgx).
+ * lengths (B) int32 or NULL (dense); offsets (B+1) int32 non-NULL: the packed layout of sparch_pack_rows — sequence j
+ * owns rows [offsets[j], offsets[j] + lengths[j]), T is the longest length, lengths are the sorted ones, and rows that
+ * do not exist are not written.  16-byte stores where K, the row strides and the base addresses are multiples of 16
+ * bytes, single elements otherwise.
+ * sparch_delay_bwd: g_x and g_delay are each optional (not both NULL).  g_delay reads x (x_elem_size 2: bf16 bit
+ * patterns; 4: fp32) and sums per-workgroup partial sums from ws (sparch_delay_bwd_workspace_bytes(B,T,K) bytes, 0 for
+ * a bad shape) in a fixed order: no atomics, the same bits on every run.
+ * sparch_delay_stream: the shift on a chunk x (B,Tc,K) of a stream; hist (B,max_delay,K) contiguous, same element
+ * type, holds the last max_delay input steps (row max_delay - 1 the newest; zeros at the start of a stream) and is
+ * advanced in place by the Tc steps of the chunk.  x, y and hist must not overlap.
+ * SPARCH_EINVAL before any device work: B, T, K < 1, max_delay outside [1, 255], a NULL pointer, a row stride < K,
+ * another element size, offsets without lengths; SPARCH_EWORKSPACE: ws too small. */
+int sparch_delay_fwd(int B, int T, int K, int elem_size, int max_delay, const float* delay, const void* x,
+                     long long ldx, void* y, long long ldy, const int* lengths, const int* offsets, void* stream);
+size_t sparch_delay_bwd_workspace_bytes(int B, int T, int K);
+int sparch_delay_bwd(int B, int T, int K, int x_elem_size, int max_delay, const float* delay, const float* g_y,
+                     long long ldg, const void* x, long long ldx, float x_scale, float* g_x, long long ldgx,
+                     float* g_delay, void* ws, size_t ws_bytes, const int* lengths, const int* offsets, void* stream);
+int sparch_delay_stream(int B, int Tc, int K, int elem_size, int max_delay, const float* delay, const void* x,
+                        long long ldx, void* y, long long ldy, void* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,11 @@ PROTOTYPES = {
     "sparch_adam_step_clip": (c_int, [c_int, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_float, P, P,
                                       P, P]),
     "sparch_scale_grads": (c_int, [c_int, P, P, P, P]),
+    "sparch_delay_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_longlong, P, c_longlong, P, P, P]),
+    "sparch_delay_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sparch_delay_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_longlong, P, c_longlong, c_float, P,
+                                 c_longlong, P, P, c_size_t, P, P, P]),
+    "sparch_delay_stream": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_longlong, P, c_longlong, P, P]),
 }
 
 

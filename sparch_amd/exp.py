@@ -163,6 +163,36 @@ def parse_tbptt(value):
     return k
 
 
+def parse_delays(value):
+    """SPARCH_DELAYS=D[:zero|uniform][:fixed][:hidden]: unset or empty -> None (no delays, nothing changes); else the
+    SNN arguments {"max_delay": D (an integer in [1, 255]), "delay_init": "zero" (default) or "uniform", "learn_delays":
+    False with `fixed`, "delay_layers": "hidden" with `hidden` (default "all")}; the options in any order, each at most
+    once; anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    head, *opts = [part.strip() for part in value.strip().split(":")]
+    try:
+        d = int(head)
+    except ValueError:
+        d = 0
+    res = {"max_delay": d, "delay_init": None, "learn_delays": True, "delay_layers": "all"}
+    ok = 1 <= d <= Fn.MAX_DELAY_CAP
+    for opt in opts:
+        if opt in ("zero", "uniform") and res["delay_init"] is None:
+            res["delay_init"] = opt
+        elif opt == "fixed" and res["learn_delays"]:
+            res["learn_delays"] = False
+        elif opt == "hidden" and res["delay_layers"] == "all":
+            res["delay_layers"] = "hidden"
+        else:
+            ok = False
+    if not ok:
+        raise ValueError(f"SPARCH_DELAYS={value!r}: D[:zero|uniform][:fixed][:hidden] with the largest delay D an integer "
+                         f"in [1, {Fn.MAX_DELAY_CAP}] time steps (unset: no delays)")
+    res["delay_init"] = res["delay_init"] or "zero"
+    return res
+
+
 def _step_lengths(seq, lengths):
     B, T = seq.shape[0], seq.shape[1]
     if lengths is None:
@@ -266,6 +296,17 @@ class Experiment:
                     raise ValueError(f"sparch_amd: SPARCH_TBPTT with {what} is not supported")
             if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
                 raise ValueError(f"sparch_amd: SPARCH_TBPTT needs a spiking model (got {self.model_type})")
+
+        # SPARCH_DELAYS=D[:zero|uniform][:fixed][:hidden]: a learnable (or fixed) axonal delay of at most D steps per
+        # input feature of every layer (or of every layer but the first) — SNN(max_delay=...); DESIGN.md section 6,
+        # "Axonal delays".  Every epoch logs each delayed layer's mean and largest delay.
+        self.delays = parse_delays(os.environ.get("SPARCH_DELAYS"))
+        if self.delays is not None:
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
+                raise ValueError(f"sparch_amd: SPARCH_DELAYS needs a spiking model (got {self.model_type})")
+            if self.tbptt is not None:
+                raise ValueError("sparch_amd: SPARCH_DELAYS with SPARCH_TBPTT is not supported (the delayed input is "
+                                 "not carried across chunks)")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -452,14 +493,20 @@ class Experiment:
                                 f"surrogate gradient, {own}")
             if self.readout is not None:
                 logging.warning(f"SPARCH_READOUT={self.readout} is ignored: the loaded model keeps its own readout")
+            if self.delays is not None:
+                logging.warning("SPARCH_DELAYS is ignored: the loaded model keeps its own delays (or none)")
         elif self.model_type in ["LIF", "adLIF", "RLIF", "RadLIF"]:
             name, scale = self.surrogate if self.surrogate is not None else ("boxcar", None)
             self.net = SNN(input_shape=input_shape, layer_sizes=layer_sizes, neuron_type=self.model_type,
                            dropout=self.pdrop, normalization=self.normalization, use_bias=self.use_bias,
                            bidirectional=self.bidirectional, use_readout_layer=True, surrogate=name,
-                           surrogate_scale=scale, **({} if self.readout is None else {"readout": self.readout})
-                           ).to(self.device)
+                           surrogate_scale=scale, **({} if self.readout is None else {"readout": self.readout}),
+                           **(self.delays or {})).to(self.device)
             logging.info(f"\nCreated new spiking model:\n {self.net}\n")
+            if self.delays is not None:
+                logging.info("Axonal delays: up to {max_delay} steps, init {delay_init}, {0}, {delay_layers} layers "
+                             "(SPARCH_DELAYS)".format("learnable" if self.delays["learn_delays"] else "fixed",
+                                                      **self.delays))
             if self.surrogate is not None:
                 logging.info(f"Surrogate gradient: {name}" + ("" if scale is None else f", scale {scale:g}")
                              + " (SPARCH_SURROGATE)")
@@ -647,6 +694,10 @@ class Experiment:
             self.opt.reset_clip_stats()  # (per-epoch figures)
             logging.info(f"Epoch {e}: grad norm max={s['max_norm']}, clipped {s['clipped']} of {s['steps']} steps, "
                          f"skipped {s['skipped']} non-finite")
+        if getattr(self.net, "max_delay", 0):  # one read-back per epoch; the forward never reads the delays on the host
+            for i, d in self.net.delay_steps().items():
+                logging.info(f"Epoch {e}: layer {i} delays: mean d={float(d.float().mean()):.3f}, max d={int(d.max())} "
+                             f"(of {self.net.max_delay})")
         if self.net.is_snn:
             epoch_spike_rate /= step  # sic: the reference divides by the last batch index (exp.py:398)
             logging.info(f"Epoch {e}: train mean act rate={epoch_spike_rate}")

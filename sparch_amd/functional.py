@@ -850,6 +850,170 @@ class UnpackRowsFn(torch.autograd.Function):
         return pack_rows(_f32c(g), ctx.plan), None
 
 
+# ----------------------------------------------------------------------------- axonal delays
+MAX_DELAY_CAP = 255  # the largest max_delay the kernels take (csrc/delay.hip)
+
+
+def check_max_delay(max_delay, zero_ok=False):
+    """max_delay as SNN and the delay kernels take it: an integer in [1, 255] ([0, 255] with zero_ok) -> int."""
+    lo = 0 if zero_ok else 1
+    if isinstance(max_delay, bool) or not isinstance(max_delay, int) or not lo <= max_delay <= MAX_DELAY_CAP:
+        raise ValueError(f"sparch_amd: max_delay must be an integer in [{lo}, {MAX_DELAY_CAP}] (got {max_delay!r})")
+    return max_delay
+
+
+def _delay_rows(x, what):
+    """x (B,T,K), 2- or 4-byte elements -> (x, row stride in elements) with unit stride along K and the rows of all
+    batch entries one stride apart (a column slice of a wider buffer is read where it lies, anything else is copied)."""
+    if x.ndim != 3 or x.element_size() not in (2, 4):
+        raise ValueError(f"{what}: a (B,T,K) tensor of 2- or 4-byte elements (got {tuple(x.shape)}, {x.dtype})")
+    B, T, K = x.shape
+    if T > 1:
+        ld = x.stride(1)
+        ok = B == 1 or x.stride(0) == T * ld
+    else:
+        ld = x.stride(0) if B > 1 else K
+        ok = True
+    if not (ok and ld >= K and (K == 1 or x.stride(2) == 1)):
+        x, ld = x.contiguous(), K
+    return x, ld
+
+
+def _check_delays(delay, K, device, what):
+    """The delay parameter as the kernels read it: K contiguous fp32 values on the tensors' device."""
+    delay = _f32c(delay)
+    if delay.numel() != K or delay.device != device:
+        raise ValueError(f"{what}: {K} delays on {device} (got {tuple(delay.shape)} on {delay.device})")
+    return delay
+
+
+def _delay_layout(B, T, lengths, pack):
+    """The kernels' index space: (sequences, steps, lengths pointer, offsets pointer).  lengths: prepare_lengths()'s
+    pair; pack: a PackPlan — the tensors are then (1, n, K) and the shift stays inside each sequence's rows."""
+    if pack is not None:
+        if B != 1 or T != pack.n:
+            raise ValueError(f"sparch_amd: a packed delay input must be (1, {pack.n}, K), got ({B}, {T}, K)")
+        return pack.batch, pack.t_max, ptr(pack.lengths), ptr(pack.offsets)
+    return B, T, (None if lengths is None else ptr(lengths[0])), None
+
+
+def delay_forward(x, delay, max_delay, lengths=None, pack=None, out=None):
+    """y[b,t,i] = x[b, t - d_i, i] for d_i <= t < len_b, else 0, with d_i = rint(clamp(delay_i, 0, max_delay)) taken on
+    the device (`sparch_delay_fwd`).  x (B,T,K): any 2- or 4-byte dtype (the bf16 spike plane, fp32), moved as raw
+    bytes.  out: a tensor to write (same dtype; every row that exists is written), else a fresh contiguous one."""
+    _require_device(x, "input")
+    D = check_max_delay(max_delay)
+    x, ldx = _delay_rows(x, "delay_forward")
+    B, T, K = x.shape
+    delay = _check_delays(delay, K, x.device, "delay_forward")
+    y = torch.empty(B, T, K, dtype=x.dtype, device=x.device) if out is None else out
+    if y.dtype != x.dtype or tuple(y.shape) != (B, T, K):
+        raise ValueError("delay_forward: out must have the input's shape and dtype")
+    y_rows, ldy = _delay_rows(y, "delay_forward")
+    if y_rows is not y:
+        raise ValueError("delay_forward: out must have unit stride along K and one row stride")
+    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    tok = timer.start("delay_fwd")
+    check(lib.sparch_delay_fwd(Bk, Tk, K, x.element_size(), D, ptr(delay), ptr(x), ldx, ptr(y), ldy, len_ptr, off_ptr,
+                               _stream()), "sparch_delay_fwd")
+    timer.stop(tok)
+    return y
+
+
+def delay_backward(g_y, delay, max_delay, x=None, x_scale=1.0, lengths=None, pack=None, need_gx=True, need_gdelay=True):
+    """The two gradients of delay_forward (`sparch_delay_bwd`) -> (g_x or None, g_delay or None), both fp32.
+    g_x[b,t,i] = g_y[b, t + d_i, i] for t + d_i < len_b, else 0.  g_delay: the finite difference of the delayed input
+    (SLAYER's rule), gate_i * sum g_y[b,t,i] * x_scale * (x[b,t-d_i-1,i] - x[b,t-d_i,i]); x is the forward's input, fp32
+    or its bf16 plane; summed in a fixed order (two runs give the same bits)."""
+    _require_device(g_y, "gradient")
+    D = check_max_delay(max_delay)
+    g_y, ldg = _delay_rows(_f32c(g_y), "delay_backward")
+    B, T, K = g_y.shape
+    delay = _check_delays(delay, K, g_y.device, "delay_backward")
+    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    g_x = torch.empty(B, T, K, dtype=torch.float32, device=g_y.device) if need_gx else None
+    g_delay = ws = None
+    nbytes, esize, ldx = 0, 4, K
+    if need_gdelay:
+        if x is None or tuple(x.shape) != (B, T, K):
+            raise ValueError("delay_backward: the delay's gradient needs the forward's input, in the gradient's shape")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        x, ldx = _delay_rows(x, "delay_backward")
+        esize = x.element_size()
+        g_delay = torch.empty(K, dtype=torch.float32, device=g_y.device)
+        nbytes = lib.sparch_delay_bwd_workspace_bytes(Bk, Tk, K)
+        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=g_y.device)
+    if not need_gx and not need_gdelay:
+        return None, None
+    tok = timer.start("delay_bwd")
+    check(lib.sparch_delay_bwd(Bk, Tk, K, esize, D, ptr(delay), ptr(g_y), ldg, ptr(x) if need_gdelay else None, ldx,
+                               float(x_scale), ptr(g_x), K, ptr(g_delay), ptr(ws), nbytes, len_ptr, off_ptr, _stream()),
+          "sparch_delay_bwd")
+    timer.stop(tok)
+    return g_x, g_delay
+
+
+def delay_stream(x, delay, max_delay, hist, out=None):
+    """The delay on a chunk x (B,Tc,K) of a stream (`sparch_delay_stream`): hist (B,max_delay,K), same dtype,
+    contiguous, holds the last max_delay input steps and is advanced in place."""
+    _require_device(x, "input")
+    D = check_max_delay(max_delay)
+    x, ldx = _delay_rows(x, "delay_stream")
+    B, Tc, K = x.shape
+    if tuple(hist.shape) != (B, D, K) or hist.dtype != x.dtype or not hist.is_contiguous() or hist.device != x.device:
+        raise ValueError(f"delay_stream: hist must be a contiguous ({B}, {D}, {K}) {x.dtype} tensor on {x.device}")
+    y = torch.empty(B, Tc, K, dtype=x.dtype, device=x.device) if out is None else out
+    y_rows, ldy = _delay_rows(y, "delay_stream")
+    if y_rows is not y or y.dtype != x.dtype or tuple(y.shape) != (B, Tc, K):
+        raise ValueError("delay_stream: out must have the input's shape and dtype, unit stride along K")
+    delay = _check_delays(delay, K, x.device, "delay_stream")
+    check(lib.sparch_delay_stream(B, Tc, K, x.element_size(), D, ptr(delay), ptr(x), ldx, ptr(y), ldy, ptr(hist),
+                                  _stream()), "sparch_delay_stream")
+    return y
+
+
+class DelayFn(torch.autograd.Function):
+    """x (B,T,K), delay (K,) -> (y, y_plane): the layer input shifted by its per-feature delays (DESIGN.md section 6,
+    "Axonal delays"), on the representation the layer's GEMMs read.  cfg: max_delay; lengths / pack as the layers take
+    them; plane: None — x itself is gathered and y_plane is None — or the (B,T,K) bf16 plane that carries x's values
+    (a spike train of ours, an input made by input_from_counts): the plane is gathered into y_plane ((B*T, ld_plane)
+    with zeros behind column K, ld_plane default K) and y is a placeholder without values, as x may be; scale: x = plane
+    * scale (the delay's gradient reads the plane)."""
+
+    @staticmethod
+    def forward(ctx, x, delay, cfg):
+        _require_device(x, "input")
+        _require_device(delay, "delay")
+        B, T, K = x.shape
+        D, plane, lengths, pack = cfg["max_delay"], cfg.get("plane"), cfg.get("lengths"), cfg.get("pack")
+        if plane is None:
+            src = x if x.element_size() in (2, 4) else x.float()
+            src = src.contiguous() if src.stride(2) != 1 else src
+            y, y16 = delay_forward(src, delay, D, lengths, pack), None
+        else:
+            ld = int(cfg.get("ld_plane", K))
+            store = (torch.empty if ld == K else torch.zeros)(B * T, ld, dtype=plane.dtype, device=plane.device)
+            delay_forward(plane, delay, D, lengths, pack, out=store.view(B, T, ld)[:, :, :K])
+            src, y, y16 = plane, spike_placeholder(B, T, K, x.device), store
+            ctx.mark_non_differentiable(y16)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(delay, src if ctx.needs_input_grad[1] else None)
+        return y, y16
+
+    @staticmethod
+    def backward(ctx, g_y, _g16=None):
+        if g_y is None:
+            return None, None, None
+        cfg = ctx.cfg
+        delay, src = ctx.saved_tensors
+        g_x, g_delay = delay_backward(g_y, delay, cfg["max_delay"], src, float(cfg.get("scale") or 1.0),
+                                      cfg.get("lengths"), cfg.get("pack"), need_gx=ctx.needs_input_grad[0],
+                                      need_gdelay=ctx.needs_input_grad[1])
+        return g_x, g_delay, None
+
+
 def _check_packed(pack, dirs, recurrent, H):
     """What the `_pk` kernels do not take."""
     if pack is None:

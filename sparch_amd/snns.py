@@ -155,6 +155,54 @@ def _spike_tag(x):
     return tag[2], tag[3]
 
 
+DELAY_INITS = ("zero", "uniform")
+DELAY_LAYERS = ("all", "hidden")
+
+
+def _refuse_stateful_delays(layer):
+    if getattr(layer, "max_delay", 0):
+        raise ValueError("sparch_amd: state / return_state with axonal delays is not supported (the last max_delay "
+                         "input steps of a chunk are not carried into the next one)")
+
+
+def _delayed_input(layer, x, lengths=None, pack=None):
+    """x as a layer with axonal delays (SNN(max_delay=...)) reads it: every input feature shifted
+    by its own delay, on the representation the layer's GEMMs read — the bf16 plane of a spike train of ours or of an
+    input made by input_from_counts (x and the result are then placeholders; the tags travel on), else x's own values.
+    A layer without delays returns x itself: nothing is launched."""
+    D = getattr(layer, "max_delay", 0)
+    if not D:
+        return x
+    Fn._require_device(x, "input")
+    if x.ndim != 3 or x.shape[2] != layer.delay.numel():
+        raise ValueError(f"sparch_amd: a layer with delays takes (batch, time, {layer.delay.numel()}) inputs, got "
+                         f"{tuple(x.shape)}")
+    cfg = {"max_delay": D}
+    if lengths is not None:
+        cfg["lengths"] = lengths
+    if pack is not None:
+        cfg["pack"] = pack
+    B, T, K = x.shape
+    scale, s16 = _spike_tag(x)
+    if scale is not None and s16 is not None:
+        cfg.update(plane=s16.view(B, T, K), scale=scale)
+        y, y16 = Fn.DelayFn.apply(x, layer.delay, cfg)
+        _tag_spikes(y, scale, y16.view(B, T, K), placeholder=True)
+        return y
+    tag = Fn.input_plane_of(x) if scale is None else None
+    if tag is not None:
+        plane, flag = tag
+        ld = plane.shape[-1]
+        cfg.update(plane=plane.view(B, T, ld)[:, :, :K], scale=1.0, ld_plane=ld)
+        y, y16 = Fn.DelayFn.apply(x, layer.delay, cfg)
+        y._sparch_input_plane = (tuple(y.shape), y16, flag)
+        return y
+    y, _ = Fn.DelayFn.apply(x, layer.delay, cfg)
+    if scale is not None:  # a spike train without its plane: the entries stay 0 or `scale`
+        _tag_spikes(y, scale, None)
+    return y
+
+
 # ---- initial-state draws.  The reference draws every layer's u0, [w0,] s0 with torch.rand from the global CPU
 # generator at each forward (snns.py:286-287, 423-425, 558-559, 700-702, 812).  The values below are the same
 # numbers from the same generator in the same order; what differs is who computes them: torch's serial loop
@@ -501,6 +549,7 @@ class _SpikingLayer(nn.Module):
         state = {"u": u_T, ["w": w_T,] "s": 1[u_T > threshold]}, the raw spike before dropout; the three are nodes of the
         graph, and the gradient of `states` comes out of the backward.  LIF / adLIF, one direction, no lengths / pack."""
         if return_state:
+            _refuse_stateful_delays(self)
             Fn.check_stateful(self.kind, self.hidden_size, dirs=2 if self.bidirectional else 1, lengths=lengths, pack=pack,
                               T=x.shape[1])
         if lengths is not None:
@@ -508,6 +557,7 @@ class _SpikingLayer(nn.Module):
         if pack is not None:
             _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
+        x = _delayed_input(self, x, lengths, pack)  # (x itself without delays)
         dirs = 2 if self.bidirectional else 1
         rows = (x.shape[0] if pack is None else pack.batch) * dirs
         if self.batch_size != rows:
@@ -649,6 +699,7 @@ class ReadoutLayer(nn.Module):
         readout = getattr(self, "readout", "softmax_sum")  # (a module pickled before the attribute: the default)
         Fn.readout_mode(readout)
         if return_state:
+            _refuse_stateful_delays(self)
             Fn.check_stateful(lengths=lengths, pack=pack, per_step=per_step, readout=readout)
         if per_step is not None and readout != "softmax_sum":
             raise ValueError(f"sparch_amd: per_step with readout={readout!r} is not supported (the per-step readout is "
@@ -660,6 +711,7 @@ class ReadoutLayer(nn.Module):
         if pack is not None:
             _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
+        x = _delayed_input(self, x, lengths, pack)  # (x itself without delays)
         if u0 is None:
             u0 = _rand_to(x.shape[0] if pack is None else pack.batch, self.hidden_size, x.device)  # snns.py:812
         is_bn = self.normalization == "batchnorm"
@@ -824,13 +876,28 @@ class SNN(nn.Module):
 
     readout="softmax_sum" (the default) / "softmax_mean" / "u_max" / "u_mean" / "u_last" (DESIGN.md section 6,
     "Selectable readout"): the readout layer's reduction over time (ReadoutLayer); with lengths, also packed, over the
-    row's own steps.  per_step needs the default."""
+    row's own steps.  per_step needs the default.
+
+    max_delay=D (1 .. 255; 0, the default: no delays, nothing registered; DESIGN.md section 6, "Axonal delays"): every
+    layer — with delay_layers="hidden" every layer but the first — owns a parameter `delay` (one entry per input
+    feature) and reads its input shifted by d_i = rint(clamp(delay_i, 0, D)) steps per feature, inside each row's own
+    length; spikes shifted past a clip's end are dropped.  delay_init="zero" / "uniform" (in [0, D]);
+    learn_delays=False keeps them fixed (no gradient).  The delay's gradient is the finite difference of the delayed
+    input.  Not with state / return_state."""
 
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
-                 surrogate="boxcar", surrogate_scale=None, readout="softmax_sum"):
+                 surrogate="boxcar", surrogate_scale=None, readout="softmax_sum", max_delay=0, delay_init="zero",
+                 learn_delays=True, delay_layers="all"):
         super().__init__()
         Fn.readout_mode(readout)
+        Fn.check_max_delay(max_delay, zero_ok=True)
+        if delay_init not in DELAY_INITS:
+            raise ValueError(f"sparch_amd: delay_init must be one of {', '.join(DELAY_INITS)} (got {delay_init!r})")
+        if delay_layers not in DELAY_LAYERS:
+            raise ValueError(f"sparch_amd: delay_layers must be one of {', '.join(DELAY_LAYERS)} (got {delay_layers!r})")
+        self.max_delay, self.delay_init, self.delay_layers = max_delay, delay_init, delay_layers
+        self.learn_delays = bool(learn_delays)
         self.readout = readout
         self.surrogate, self.surrogate_scale = resolve_surrogate(surrogate, surrogate_scale)
         self.reshape = len(input_shape) > 3
@@ -852,6 +919,31 @@ class SNN(nn.Module):
             raise ValueError(f"Invalid neuron type {neuron_type}")
 
         self.snn = self._init_layers()
+        self._init_delays()
+
+    def _init_delays(self):
+        """Axonal delays: every delayed layer gets `max_delay` and an nn.Parameter `delay`, one
+        entry per input feature.  Made after the whole network, so that under one seed every other parameter is what it
+        is without delays; max_delay = 0 registers nothing (the state_dict keys are the reference's)."""
+        if not self.max_delay:
+            return
+        for i, layer in enumerate(self.snn):
+            if i == 0 and self.delay_layers == "hidden":
+                continue
+            layer.max_delay = self.max_delay
+            init = torch.zeros(layer.input_size)
+            if self.delay_init == "uniform":
+                init.uniform_(0.0, float(self.max_delay))
+            layer.delay = nn.Parameter(init, requires_grad=self.learn_delays)
+
+    def delay_steps(self):
+        """{layer index: the integer delays d = rint(clamp(delay, 0, max_delay)) as the kernels take them (K,) int64}
+        of the delayed layers — for logging; the forward pass never reads the parameter on the host."""
+        res = {}
+        for i, layer in enumerate(self.snn):
+            if getattr(layer, "max_delay", 0):
+                res[i] = torch.round(layer.delay.detach().float().clamp(0, layer.max_delay)).long()
+        return res
 
     def _init_layers(self):
         layers = nn.ModuleList([])
@@ -878,6 +970,9 @@ class SNN(nn.Module):
         parts = [] if name == "boxcar" else [f"surrogate={name}, surrogate_scale={getattr(self, 'surrogate_scale', None):g}"]
         if getattr(self, "readout", "softmax_sum") != "softmax_sum":
             parts.append(f"readout={self.readout}")
+        if getattr(self, "max_delay", 0):
+            parts.append(f"max_delay={self.max_delay}, delay_init={self.delay_init}, learn_delays={self.learn_delays}, "
+                         f"delay_layers={self.delay_layers}")
         return ", ".join(parts)
 
     def draw_states(self, batch, device, out=None):
@@ -947,6 +1042,8 @@ class SNN(nn.Module):
             raise ValueError("sparch_amd: state / return_state inside a captured step (GraphedTrainStep) is not "
                              "supported: the carried state changes with every chunk")
         last = self.num_layers - 1
+        for layer in self.snn:
+            _refuse_stateful_delays(layer)
         for i, layer in enumerate(self.snn):
             if self.use_readout_layer and i == last:
                 Fn.check_stateful(lengths=lengths, pack=pack if pack else None, per_step=per_step,

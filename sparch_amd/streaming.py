@@ -198,6 +198,15 @@ class StreamingSNN(_Stream):
         if fused and readout != "softmax_sum":
             raise ValueError(f"StreamingSNN: fused=True does not take readout={readout!r} (the one-step readout kernels "
                              "are the softmax-sum's); use fused=False")
+        # axonal delays (SNN(max_delay=...)): the chunk path carries one history of the last max_delay input steps per
+        # delayed layer; the one-launch fused and event-driven steps and the captured chunk step do not
+        self._has_delays = any(getattr(mod, "max_delay", 0) for mod in net.snn)
+        if self._has_delays and (fused or sparse):
+            raise ValueError("StreamingSNN: fused=True / sparse=True do not take a network with axonal delays (the "
+                             "one-launch step has no delayed input); use fused=False")
+        if self._has_delays and graph:
+            raise ValueError("StreamingSNN: graph=True does not take a network with axonal delays (the captured chunk "
+                             "step covers networks without them only); use graph=False")
         self.fused = bool(fused)
         self.sparse = bool(sparse)
         self._fused_active = self.fused and Fn._prec() == 0
@@ -246,6 +255,11 @@ class StreamingSNN(_Stream):
                 elif L.norm == "layernorm":
                     L.nw, L.nb = mod.norm.weight.detach(), mod.norm.bias.detach()
                 L.theta = None if L.readout else float(mod.threshold)
+                # axonal delays: the parameter, and (a state buffer, made at the first chunk in the dtype the layer's
+                # input travels in) the last D input steps (B,D,K)
+                L.D = int(getattr(mod, "max_delay", 0))
+                L.delay = Fn._f32c(mod.delay.detach()) if L.D else None
+                L.hist = None
                 # readout: the reduction over time; the mean modes carry the un-normalised accumulator in `out` and the
                 # rows' step counts in `steps`, u_max the running maximum (from -inf)
                 L.red = Fn.readout_mode(self._readout_name(net)) if L.readout else 0
@@ -274,7 +288,8 @@ class StreamingSNN(_Stream):
                     L.vmask_t = L.vmask.t().contiguous()  # (H_out, H_in): the NT operand of the exact spike product
                 # state buffers: kept across refresh()
                 if old is not None:
-                    for k in ("u", "w", "s", "s16", "count", "out", "steps", "binary", "s_alt", "s16_alt", "s_first"):
+                    for k in ("u", "w", "s", "s16", "count", "out", "steps", "binary", "s_alt", "s16_alt", "s_first",
+                              "hist"):
                         setattr(L, k, getattr(old[i], k, None))
                 elif L.readout:
                     L.u = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
@@ -332,6 +347,17 @@ class StreamingSNN(_Stream):
         for L, st in self._entries(states):
             u, w, s, out = self._entry(st, L.readout)
             self._put(L.u, u, "u", idx, L.H)
+            hist = st.get("hist") if isinstance(st, dict) else None
+            if L.D and hist is not None:
+                n = self.batch_size if idx is None else len(idx)
+                hist = torch.as_tensor(hist).to(self._dev)
+                if tuple(hist.shape) != (n, L.D, L.K):
+                    raise ValueError(f"StreamingSNN: hist has shape {tuple(hist.shape)}, expected ({n}, {L.D}, {L.K})")
+                dst = self._hist(L, hist.dtype if idx is None else None)
+                if idx is None:
+                    dst.copy_(hist)
+                else:
+                    dst.index_copy_(0, idx, hist.to(dst.dtype))
             if L.readout:
                 if out is not None:
                     self._put(L.out, out, "out", idx)
@@ -363,6 +389,12 @@ class StreamingSNN(_Stream):
         if states is None:
             states = self.net.draw_states(n, self._dev)
             states.wait_ready()
+        for L in self._layers:  # a delayed layer's history: no input seen yet (a `hist` entry of `states` replaces it)
+            if L.hist is not None:
+                if rows is None:
+                    L.hist.zero_()
+                else:
+                    L.hist.index_fill_(0, self._rows(rows), 0)
         self._load(states, rows)
         ro = self._layers[-1] if self._layers[-1].readout else None
         if rows is None:
@@ -381,7 +413,9 @@ class StreamingSNN(_Stream):
 
     def get_state(self):
         """A copy of the carried state: per hidden layer {"u", ["w",] "s"}, for the readout {"u", "out"} (unpadded);
-        `out` is the accumulator as carried — in the mean readouts un-normalised, with the rows' step counts as "steps"."""
+        `out` is the accumulator as carried — in the mean readouts un-normalised, with the rows' step counts as "steps".
+        A layer with axonal delays adds "hist" (B, max_delay, K): its last max_delay input steps, the newest last, in the
+        dtype they travel in (bf16 for spikes and spike counts)."""
         self._ensure()
         res = []
         for L in self._layers:
@@ -394,6 +428,8 @@ class StreamingSNN(_Stream):
                 if L.adaptive:
                     d["w"] = L.w[:, :L.H].clone()
                 res.append(d)
+            if L.D:
+                res[-1]["hist"] = self._hist(L, None).clone()
         return res
 
     def firing_rates(self):
@@ -406,6 +442,33 @@ class StreamingSNN(_Stream):
         return c * (1.0 / float(self.batch_size * self.steps_seen))
 
     # ------------------------------------------------------------------ the chunk step
+    def _hist(self, L, dtype):
+        """The history buffer of a delayed layer, (B, D, K) zeros when first asked for; dtype None: as it is (fp32 if
+        no chunk has been seen).  Another dtype than before (fp32 chunks after uint8 ones) converts what is carried."""
+        if L.hist is None:
+            L.hist = torch.zeros(self.batch_size, L.D, L.K, dtype=dtype or torch.float32, device=self._dev)
+        elif dtype is not None and L.hist.dtype != dtype:
+            L.hist = L.hist.to(dtype)
+        return L.hist
+
+    def _delayed(self, L, x, s16):
+        """The chunk's input of a delayed layer, shifted (`sparch_delay_stream`; the history moves on): the network
+        input x — its values, or the bf16 plane of a chunk of spike counts — or the previous layer's spike plane."""
+        B = self.batch_size
+        if s16 is not None:
+            return x, Fn.delay_stream(s16, L.delay, L.D, self._hist(L, s16.dtype))
+        tag = Fn.input_plane_of(x)
+        if tag is None:
+            return Fn.delay_stream(x, L.delay, L.D, self._hist(L, x.dtype)), None
+        plane, flag = tag
+        Tc, ld = x.shape[1], plane.shape[-1]
+        store = (torch.empty if ld == L.K else torch.zeros)(B * Tc, ld, dtype=plane.dtype, device=self._dev)
+        Fn.delay_stream(plane.view(B, Tc, ld)[:, :, :L.K], L.delay, L.D, self._hist(L, plane.dtype),
+                        out=store.view(B, Tc, ld)[:, :, :L.K])
+        y = Fn.spike_placeholder(B, Tc, L.K, self._dev).view(B, Tc, L.K)
+        y._sparch_input_plane = (tuple(y.shape), store, flag)
+        return y, None
+
     def _rec_drive(self, L):
         """s @ Vmasked for the state the next step starts from: the exact spike product on the bf16 plane once the
         state is binary (every chunk but the first after a reset), the dense six-term product on drawn states."""
@@ -465,6 +528,8 @@ class StreamingSNN(_Stream):
         s = s16 = None
         taps = []
         for i, L in enumerate(layers):
+            if L.D:
+                x, s16 = self._delayed(L, x, s16 if i else None)
             if i == 0:
                 # the network input, as SpikingLayerFn.forward takes it: its bf16 plane when every value is bf16-exact
                 # (binned spike counts are; decided on the device), the fp32 values otherwise
