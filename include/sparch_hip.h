@@ -1237,6 +1237,36 @@ int sparch_delay_bwd(int B, int T, int K, int x_elem_size, int max_delay, const 
 int sparch_delay_stream(int B, int Tc, int K, int elem_size, int max_delay, const float* delay, const void* x,
                         long long ldx, void* y, long long ldy, void* hist, void* stream);
 
+/* ---- Spike encoders (csrc/encode.hip): real-valued features -> spike counts, on the device.
+ * x (B,T,K) fp32 contiguous; lo, scale (K) fp32; z = (x - lo[k]) * scale[k] — two fp32 roundings, never a fused
+ * multiply-add.  The outputs are those of sparch_events_gather_bin / sparch_expand_counts_u8, K' =
+ * sparch_spike_encode_width(code, K) columns wide: plane (B*T, ldp) bf16 bit patterns, 16-byte aligned, ldp % 8 == 0,
+ * ldp >= K', exact zeros behind column K'; counts uint8 and dense fp32, (B,T,K') contiguous; each may be NULL, not all
+ * three.  lengths (B) int32 or NULL: a step t >= lengths[b] emits 0 and does not advance the state.  totals (K') uint32
+ * or NULL: the spikes emitted per output column are ADDED to it.  t0 >= 0: the steps this stream has emitted before.
+ *   SPARCH_ENCODE_RATE (stochastic, no state; state may be NULL): p = z > 0 ? min(z, 1) : 0 (a NaN gives 0); one spike
+ *     iff u < p, u the 24-bit uniform of the dropout hash above on (seed, ((t0 + t) * B + b) * K + k) — a 64-bit,
+ *     time-major index: a stream cut into chunks draws the numbers the whole sequence draws.
+ *   SPARCH_ENCODE_IF (integrate and fire; state v (B,K) in [0, 1), in / out): drive = z > 0 ? min(z, 255) : 0;
+ *     v += drive; n = floor(v); v -= n; n (<= 255) is emitted.  fresh != 0: v starts at 0 and state is only written.
+ *   SPARCH_ENCODE_DELTA (send-on-delta; state ref (B,K), in / out; K' = 2K): with fresh != 0 the state starts at 0 and
+ *     local step 0 sets ref = z (0 if z is not finite) and emits nothing.  Otherwise e = z - ref,
+ *     n = min(floor(|e|), 255); column k (ON) gets n if e > 0, column K + k (OFF) gets n if e < 0; then
+ *     ref += copysign(n, e).  A z that is not finite emits nothing and leaves ref as it is.  The threshold delta
+ *     enters through scale = 1 / delta.
+ * IF and DELTA run one thread per (b, k) over the T steps with the loads of the next SPARCH_ENCODE_PREFETCH steps in
+ * flight (they do not depend on the state); RATE is one flat pass.
+ * SPARCH_EINVAL before any device work: an unknown code; B, T, K < 1; NULL x, lo or scale; all outputs NULL; NULL
+ * state for IF or DELTA; t0 < 0; ldp < K' or ldp % 8 != 0; K' > 65535.  SPARCH_EALIGN: plane not 16-byte aligned. */
+#define SPARCH_ENCODE_RATE 0
+#define SPARCH_ENCODE_IF 1
+#define SPARCH_ENCODE_DELTA 2
+#define SPARCH_ENCODE_PREFETCH 8
+int sparch_spike_encode(int code, int B, int T, int K, const float* x, const float* lo, const float* scale,
+                        float* state, int fresh, long long t0, uint64_t seed, const int* lengths, uint16_t* plane,
+                        int ldp, uint8_t* counts, float* dense, uint32_t* totals, void* stream);
+int sparch_spike_encode_width(int code, int K);  /* K for RATE and IF, 2K for DELTA; 0 for an unknown code or K < 1 */
+
 #ifdef __cplusplus
 }
 #endif

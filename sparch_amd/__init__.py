@@ -8,6 +8,7 @@ from . import _capi  # noqa: F401  (fails loudly when libsparch_hip.so is missin
 from . import optim  # noqa: F401
 from .functional import (augment_padded, bin_events, check_status, compute_dtype, fbank,  # noqa: F401
                          fbank_padded, flac_decode_padded, set_compute_dtype)
+from .encoders import SpikeEncoder, StreamingSpikeEncoder, parse_encode  # noqa: F401
 from .snns import (SNN, LIFLayer, RLIFLayer, RadLIFLayer, ReadoutLayer,  # noqa: F401
                    SpikeFunctionBoxcar, SpikeFunctionSurrogate, adLIFLayer)
 from .streaming import StreamingFbank, StreamingSNN  # noqa: F401

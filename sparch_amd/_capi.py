@@ -215,6 +215,9 @@ PROTOTYPES = {
     "sparch_delay_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_longlong, P, c_longlong, c_float, P,
                                  c_longlong, P, P, c_size_t, P, P, P]),
     "sparch_delay_stream": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_longlong, P, c_longlong, P, P]),
+    "sparch_spike_encode": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, c_int, c_longlong, c_uint64, P, P, c_int,
+                                    P, P, P, P]),
+    "sparch_spike_encode_width": (c_int, [c_int, c_int]),
 }
 
 

@@ -36,6 +36,7 @@ from . import functional as Fn
 from .functional import check_status, fbank
 from .parsers import print_model_options, print_training_options
 from .anns import ANN
+from .encoders import SpikeEncoder, _mix64, parse_encode
 from .snns import SNN, parse_surrogate
 
 logger = logging.getLogger(__name__)
@@ -193,6 +194,17 @@ def parse_delays(value):
     return res
 
 
+def check_encode_model(net, encoder):
+    """SPARCH_ENCODE with a given network (a loaded one included): a spiking network whose first layer is as wide as
+    the encoder's output — refused before the first kernel otherwise."""
+    if not getattr(net, "is_snn", False):
+        raise ValueError(f"sparch_amd: SPARCH_ENCODE needs a spiking model (got {type(net).__name__})")
+    width = int(net.snn[0].input_size)
+    if width != encoder.out_features:
+        raise ValueError(f"sparch_amd: SPARCH_ENCODE: the {encoder.code} code gives {encoder.out_features} input features, "
+                         f"the model's first layer takes {width}")
+
+
 def _step_lengths(seq, lengths):
     B, T = seq.shape[0], seq.shape[1]
     if lengths is None:
@@ -307,6 +319,18 @@ class Experiment:
             if self.tbptt is not None:
                 raise ValueError("sparch_amd: SPARCH_DELAYS with SPARCH_TBPTT is not supported (the delayed input is "
                                  "not carried across chunks)")
+
+        # SPARCH_ENCODE=code[:key=value,...]: hd / sc features are turned into spikes on the device, behind the fbank
+        # (encoders.SpikeEncoder; DESIGN.md section 6, "Spike encoders"): layer 0 reads a count plane like every other
+        # layer.  Every epoch logs the input spike density.
+        self.encode_spec = parse_encode(os.environ.get("SPARCH_ENCODE"))
+        self.encoder = None
+        if self.encode_spec is not None:
+            if getattr(args, "dataset_name", None) in _SPIKING_SETS:
+                raise ValueError(f"sparch_amd: SPARCH_ENCODE with --dataset_name {args.dataset_name}: its input is "
+                                 "already spikes (the encoders turn hd / sc features into spikes)")
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"] and not self.use_pretrained_model:
+                raise ValueError(f"sparch_amd: SPARCH_ENCODE needs a spiking model (got {self.model_type})")
 
         self.rank, self.world, self.local_rank = dp.init_from_env()
         self.is_main = self.rank == 0
@@ -441,6 +465,10 @@ class Experiment:
                                  "store's batch kernel: it needs SPARCH_EVENTS=resident and no --synthetic")
         elif self.dataset_name in _AUDIO_SETS:
             self.nb_inputs, self.nb_outputs, kind = 40, _AUDIO_SETS[self.dataset_name], "audio"
+            if self.encode_spec is not None:  # the network is built for the spikes, not the 40 features
+                self.encoder = SpikeEncoder.from_spec(self.encode_spec, self.nb_inputs)
+                self.nb_inputs = self.encoder.out_features
+                self._enc_steps = 0
         else:
             raise ValueError(f"Invalid dataset name {self.dataset_name}")
         self.input_kind = kind
@@ -486,6 +514,8 @@ class Experiment:
         if self.use_pretrained_model:
             self.net = torch.load(self.load_path, map_location=self.device, weights_only=False)  # our own file
             logging.info(f"\nLoaded model at: {self.load_path}\n {self.net}\n")
+            if self.encoder is not None:
+                check_encode_model(self.net, self.encoder)
             if self.surrogate is not None:
                 own = (f"{getattr(self.net, 'surrogate', 'boxcar')} (scale {getattr(self.net, 'surrogate_scale', None)})"
                        if getattr(self.net, "is_snn", False) else "none (not a spiking model)")
@@ -531,11 +561,14 @@ class Experiment:
             loader = getattr(self, name, None)
             if hasattr(loader, "store") and hasattr(loader, "values"):
                 loader.values = not self.net.is_snn
+        if self.encoder is not None:
+            check_encode_model(self.net, self.encoder)
+            logging.info(f"Input features are encoded as spikes on the device: {self.encoder} (SPARCH_ENCODE)")
         self.nb_params = sum(p.numel() for p in self.net.parameters() if p.requires_grad)
         logging.info(f"Total number of trainable parameters is {self.nb_params}")
 
     # ---------------------------------------------------------------------------------- epochs
-    def _to_device(self, x, y):
+    def _to_device(self, x, y, xlens=None, seed=None):
         if x.device != self.device:  # (a batch made on the device is passed on as it is, plane tag included)
             x = x.to(self.device, non_blocking=True)
         if y.device != self.device:
@@ -544,7 +577,24 @@ class Experiment:
             x = Fn.input_from_counts(x) if self.net.is_snn else x.float()
         if self.input_kind == "audio" and x.ndim == 2:  # synthetic waves; the file loaders deliver features
             x = fbank(x, num_mel_bins=40)  # (B, 16000) -> (B, 98, 40) on the device
+        if self.encoder is not None:  # SPARCH_ENCODE: features -> the count plane layer 0 reads; padded steps emit nothing
+            if xlens is not None:
+                xlens = torch.as_tensor(xlens).clamp(max=x.shape[1])
+                self._enc_steps = self._enc_steps + xlens.sum()
+            else:
+                self._enc_steps = self._enc_steps + x.shape[0] * x.shape[1]
+            x = self.encoder.encode(x, lengths=xlens, seed=seed)
         return x, y
+
+    def _log_density(self, prefix):
+        """SPARCH_ENCODE: spikes per input feature and valid step since the last call (one read-back per epoch)."""
+        if self.encoder is None:
+            return
+        spikes, steps = float(self.encoder.totals().sum()), float(self._enc_steps)
+        self._enc_steps = 0
+        density = self._mean_over_ranks(spikes / max(steps * self.encoder.out_features, 1.0))
+        logging.info(f"{prefix} input spike density={density:.6f} spikes per feature and step "
+                     f"(SPARCH_ENCODE: {self.encoder.code})")
 
     def _prefetched(self, loader):
         """The loader's batches, on the device, uploaded ONE BATCH AHEAD on a side stream (pinned source,
@@ -642,7 +692,7 @@ class Experiment:
         # (exp.py:363, 381) become device-side lists read back ONCE per epoch — the same fp32 per-batch
         # values, the same float64 means — and the kernels' status word is checked at the same point.
         for step, (x, xlens, y) in enumerate(self._prefetched(self.train_loader)):
-            x, y = self._to_device(x, y)
+            x, y = self._to_device(x, y, xlens)  # (SPARCH_ENCODE: the encoder's own seed sequence moves on per batch)
             if self.tbptt is not None:
                 loss_val, output, firing_rates = self._train_batch_tbptt(x, y)
                 losses.append(loss_val)
@@ -698,6 +748,7 @@ class Experiment:
             for i, d in self.net.delay_steps().items():
                 logging.info(f"Epoch {e}: layer {i} delays: mean d={float(d.float().mean()):.3f}, max d={int(d.max())} "
                              f"(of {self.net.max_delay})")
+        self._log_density(f"Epoch {e}: train")
         if self.net.is_snn:
             epoch_spike_rate /= step  # sic: the reference divides by the last batch index (exp.py:398)
             logging.info(f"Epoch {e}: train mean act rate={epoch_spike_rate}")
@@ -740,8 +791,11 @@ class Experiment:
         self.decision_step = None
         epoch_spike_rate = 0
         step = 0
+        # SPARCH_ENCODE: an evaluation repeats — the seed of a batch comes from the split and the batch's index
+        split = 1 if loader is self.valid_loader else 2
         for step, (x, xlens, y) in enumerate(self._prefetched(loader)):
-            x, y = self._to_device(x, y)
+            seed = None if self.encoder is None else _mix64(_mix64(self.encoder.base_seed, -1 - split), step)
+            x, y = self._to_device(x, y, xlens, seed)
             output, firing_rates, *seq = self._net(x, xlens)
             losses.append(self.loss_fn(output, y).detach())
             if seq:
@@ -773,6 +827,7 @@ class Experiment:
             logging.info(f"Epoch {e}: valid acc={valid_acc}")
             if self.decision_step is not None:
                 logging.info(f"Epoch {e}: valid mean decision step={self.decision_step}")
+            self._log_density(f"Epoch {e}: valid")
             if self.net.is_snn:
                 logging.info(f"Epoch {e}: valid mean act rate={rate}")
             self.scheduler.step(valid_acc)
@@ -795,6 +850,7 @@ class Experiment:
             logging.info(f"Test acc={test_acc}")
             if self.decision_step is not None:
                 logging.info(f"Test mean decision step={self.decision_step}")
+            self._log_density("Test")
             if self.net.is_snn:
                 logging.info(f"Test mean act rate={rate}")
             logging.info("\n-----------------------------\n")

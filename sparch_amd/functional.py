@@ -325,6 +325,23 @@ def input_from_counts(counts):
     return x
 
 
+def input_from_plane(plane, B, T, K):
+    """The network input `input_from_counts` returns, for a bf16 count plane (B*T, ldp) that is already on the device
+    (zeros behind column K, counts <= 255: the spike encoders' output): the (B,T,K) placeholder tagged with the plane
+    and the flag "exact"."""
+    _require_device(plane, "plane")
+    if plane.dtype != torch.bfloat16 or plane.ndim != 2 or plane.shape[0] != B * T or plane.shape[1] < K or \
+            plane.shape[1] % 8 or not plane.is_contiguous():
+        raise ValueError("input_from_plane: a contiguous (B*T, ldp) bf16 plane with ldp % 8 == 0 and ldp >= K")
+    key = str(plane.device)
+    one = _flag_one.get(key)
+    if one is None:
+        one = _flag_one[key] = torch.ones(4, dtype=torch.int32, device=plane.device)
+    x = spike_placeholder(B, T, K, plane.device).view(B, T, K)
+    x._sparch_input_plane = (tuple(x.shape), plane, one)
+    return x
+
+
 def input_plane_of(x):
     """(plane, flag) if x is an input made by `input_from_counts`, else None."""
     tag = getattr(x, "_sparch_input_plane", None)

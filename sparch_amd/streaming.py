@@ -562,7 +562,8 @@ class StreamingSNN(_Stream):
                 self._spike_tap(i, t)
 
     def step(self, x_chunk, lengths=None, pack=False):
-        """x_chunk (B,Tc,C) float32, or uint8 spike counts, on the device; any Tc >= 1."""
+        """x_chunk (B,Tc,C) float32, uint8 spike counts, or a tagged count plane (`input_from_counts`, a spike
+        encoder's output), on the device; any Tc >= 1."""
         if pack:
             raise ValueError("sparch_amd: pack=True is not supported by the streaming classes (StreamingSNN)")
         if lengths is not None:  # (a stream ends when its caller stops feeding it: DESIGN.md section 7)
@@ -570,8 +571,11 @@ class StreamingSNN(_Stream):
         self._ensure()
         x = self._chunk(x_chunk)
         Tc = x.shape[1]
+        # a chunk that is a tagged placeholder (input_from_counts, a spike encoder): its bf16 plane is the data and the
+        # tensor has no values to read or copy, so it takes the chunk path's eager launches whatever its length
+        tagged = Fn.input_plane_of(x) is not None
         if self._fused_active:
-            if Tc == 1:
+            if Tc == 1 and not tagged:
                 with torch.no_grad():
                     out = self._fused_step(x)
                 self.steps_seen += 1
@@ -579,11 +583,11 @@ class StreamingSNN(_Stream):
                 return out
             if self.graph:
                 self._primary_spikes()
-        if x.dtype != torch.uint8:
+        if x.dtype != torch.uint8 and not tagged:
             x = Fn._f32c(x)
         out = None
         with torch.no_grad():
-            if self.graph:
+            if self.graph and not tagged:
                 out = self._graph_step(x, Tc)
             if out is None:
                 xin = Fn.input_from_counts(x) if x.dtype == torch.uint8 else x
