@@ -401,6 +401,44 @@ int sparch_pack_rows(int B, int T, int C, int elem_size, const void* src, void* 
                      const int* lengths, const int* offsets, long long n_valid, void* stream);
 int sparch_unpack_rows(int B, int T, int C, int elem_size, const void* src, void* dst, const int* order,
                        const int* lengths, const int* offsets, long long n_valid, void* stream);
+/* Bidirectional layers on ragged batches ("Bidirectional ragged batches"): the movements in front
+ * of and behind the one-direction `_len` / `_pk` cell entry points, which then run on 2B sequences — sequence b is clip
+ * b, sequence B + b is clip b read backwards inside its own length.  lengths (B,) int32 on the device, n_valid their sum.
+ *   split     : src (B,T,C), elements of elem_size = 1, 2 or 4 bytes moved as raw bytes -> dst (2B,T,C):
+ *               dst[b,t] = src[b,t], dst[B+b,t] = src[b, lengths[b]-1-t] for t < lengths[b], zeros behind: every element
+ *               of dst is written.
+ *   split_bwd : its adjoint, fp32: g_src[b,t] = g[b,t] + g[B+b, lengths[b]-1-t] (one fp32 sum), 0 for t >= lengths[b].
+ *   join      : s16 (2B,T,H) bf16 0/1 plane -> y16 (B,T,2H): y16[b,t,:H] = s16[b,t], y16[b,t,H:] = s16[B+b,
+ *               lengths[b]-1-t], zeros behind; y32 (B,T,2H) fp32 or NULL: the same values times `scale`; the non-zero
+ *               values of every output column are ADDED to spike_count (2H,) (the caller owns and clears it; integer
+ *               atomics: the result does not depend on the order).
+ *   join_bwd  : its adjoint: g2[b,t] = g[b,t,:H] + r, g2[B+b, lengths[b]-1-t] = g[b,t,H:] + r with r =
+ *               g_rate[column] * rate_scale (g_rate (2H,) or NULL: r = 0; one fp32 product and one fp32 sum), 0 on the
+ *               tails of g2 (2B,T,H): every element is written.
+ * The `_pk` forms: the single tensors are packed (n_valid, .) by lengths (sorted descending) and offsets (B + 1,), as
+ * sparch_pack_rows makes them, T is the longest length; the doubled tensors have 2 n_valid rows, and fwd / rev (B,) int32
+ * hold, per sequence, the first row of its forward and of its reversed copy there.  There are no tails.
+ * SPARCH_EINVAL, before any device work: B, T, C / H < 1, a NULL pointer (y32 and g_rate may be NULL), n_valid < 1 or
+ * > B T, an element size other than 1, 2, 4.  Then SPARCH_EALIGN: a pointer that is not aligned to its element.  Rows
+ * move in the widest pieces (16, 4, 2, 1 bytes) that the row size and the addresses allow.                        */
+int sparch_bidir_split_len(int B, int T, int C, int elem_size, const void* src, void* dst, const int* lengths,
+                           long long n_valid, void* stream);
+int sparch_bidir_split_pk(int B, int T, int C, int elem_size, const void* src, void* dst, const int* lengths,
+                          const int* offsets, const int* fwd, const int* rev, long long n_valid, void* stream);
+int sparch_bidir_split_bwd_len(int B, int T, int C, const float* g, float* g_src, const int* lengths,
+                               long long n_valid, void* stream);
+int sparch_bidir_split_bwd_pk(int B, int T, int C, const float* g, float* g_src, const int* lengths,
+                              const int* offsets, const int* fwd, const int* rev, long long n_valid, void* stream);
+int sparch_bidir_join_len(int B, int T, int H, const uint16_t* s16, uint16_t* y16, float* y32, float scale,
+                          uint32_t* spike_count, const int* lengths, long long n_valid, void* stream);
+int sparch_bidir_join_pk(int B, int T, int H, const uint16_t* s16, uint16_t* y16, float* y32, float scale,
+                         uint32_t* spike_count, const int* lengths, const int* offsets, const int* fwd,
+                         const int* rev, long long n_valid, void* stream);
+int sparch_bidir_join_bwd_len(int B, int T, int H, const float* g, const float* g_rate, float rate_scale,
+                              float* g2, const int* lengths, long long n_valid, void* stream);
+int sparch_bidir_join_bwd_pk(int B, int T, int H, const float* g, const float* g_rate, float rate_scale,
+                             float* g2, const int* lengths, const int* offsets, const int* fwd, const int* rev,
+                             long long n_valid, void* stream);
 
 /* Recurrent kinds (RLIF, RadLIF).  V (H,H) = V.weight; the diagonal is masked inside
  * (snns.py:566/712).  The recurrent product s_{t-1}*V runs on MFMA with the V slice of

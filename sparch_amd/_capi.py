@@ -87,6 +87,14 @@ PROTOTYPES = {
                                    c_float, c_float, c_uint64, P, P, P, P, P, P, P, c_longlong, c_int, c_float, P]),
     "sparch_pack_rows": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, c_longlong, P]),
     "sparch_unpack_rows": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, c_longlong, P]),
+    "sparch_bidir_split_len": (c_int, [c_int, c_int, c_int, c_int, P, P, P, c_longlong, P]),
+    "sparch_bidir_split_pk": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_longlong, P]),
+    "sparch_bidir_split_bwd_len": (c_int, [c_int, c_int, c_int, P, P, P, c_longlong, P]),
+    "sparch_bidir_split_bwd_pk": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P, c_longlong, P]),
+    "sparch_bidir_join_len": (c_int, [c_int, c_int, c_int, P, P, P, c_float, P, P, c_longlong, P]),
+    "sparch_bidir_join_pk": (c_int, [c_int, c_int, c_int, P, P, P, c_float, P, P, P, P, P, c_longlong, P]),
+    "sparch_bidir_join_bwd_len": (c_int, [c_int, c_int, c_int, P, P, c_float, P, P, c_longlong, P]),
+    "sparch_bidir_join_bwd_pk": (c_int, [c_int, c_int, c_int, P, P, c_float, P, P, P, P, P, c_longlong, P]),
     "sparch_vpack_bytes": (c_size_t, [c_int]),
     "sparch_set_xcd_local": (c_int, [c_int]),
     "sparch_vpack": (c_int, [c_int, P, c_int, P, P, P, c_int]),

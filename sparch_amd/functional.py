@@ -1035,9 +1035,6 @@ def _check_packed(pack, dirs, recurrent, H):
     """What the `_pk` kernels do not take."""
     if pack is None:
         return
-    if dirs != 1:
-        raise ValueError("sparch_amd: pack=True with bidirectional=True is not supported (the reverse direction would "
-                         "read each sequence's packed rows backwards: a change of its own)")
     if recurrent and rec_step_path(H):
         raise ValueError(f"sparch_amd: pack=True with a recurrent hidden size above 1024 (got {H}) is not supported "
                          "(the per-step recurrent path takes no packed batches)")
@@ -1054,12 +1051,119 @@ def _check_ragged(lengths, dirs, recurrent, H):
     """What the `_len` kernels do not take."""
     if lengths is None:
         return
-    if dirs != 1:
-        raise ValueError("sparch_amd: lengths with bidirectional=True is not supported (the reverse direction would "
-                         "have to flip inside each clip's own length)")
     if recurrent and rec_step_path(H):
         raise ValueError(f"sparch_amd: lengths with a recurrent hidden size above 1024 (got {H}) is not supported "
                          "(the per-step recurrent path takes no lengths)")
+
+
+def _check_one_direction(dirs, lengths, pack):
+    """The `_len` / `_pk` cell kernels run one direction: a bidirectional layer reaches them through SpikingLayerFn, which
+    runs them on 2B sequences between bidir_split and bidir_join ("Bidirectional ragged batches")."""
+    if dirs != 1 and (lengths is not None or pack is not None):
+        raise ValueError("sparch_amd: cell_forward / cell_backward with lengths or pack take dirs=1 (a bidirectional "
+                         "layer runs them on the doubled batch: SpikingLayerFn)")
+
+
+# ----------------------------------------------------------------------------- bidirectional layers on ragged batches
+class BidirPlan(typing.NamedTuple):
+    """The doubled batch of a bidirectional layer on a packed ragged batch (snns.prepare_bidir_packing): `plan` is the
+    PackPlan of the 2B sequences — batch row b is clip b, row B + b clip b read backwards — and fwd / rev (B,) int32, in
+    the single plan's sorted order, the first row of sequence j's forward and reversed copy in the doubled packed
+    tensor.  All views of one device buffer."""
+    plan: PackPlan
+    fwd: torch.Tensor
+    rev: torch.Tensor
+
+
+def _bidir_map(cfg):
+    """(entry suffix, B, T, the map arguments behind the tensors) of the sparch_bidir_* calls under cfg: the `_len` form
+    for cfg["lengths"], the `_pk` form for cfg["pack"] with cfg["pack2"] (a BidirPlan)."""
+    pack = cfg.get("pack")
+    if pack is not None:
+        two = cfg["pack2"]
+        return "_pk", pack.batch, pack.t_max, (ptr(pack.lengths), ptr(pack.offsets), ptr(two.fwd), ptr(two.rev), int(pack.n))
+    lengths = cfg["lengths"]
+    return "_len", lengths[0].shape[0], None, (ptr(lengths[0]), int(lengths[1]))
+
+
+def _bidir_ragged(cfg):
+    """True for a bidirectional layer with lengths or pack: the layer runs on the doubled batch."""
+    return cfg["dirs"] == 2 and (cfg.get("lengths") is not None or cfg.get("pack") is not None)
+
+
+def _bidir_cell_kw(cfg):
+    """What the one-direction cell calls on the doubled batch take: the lengths twice (cfg["lengths2"] = (device int32
+    (2B,), 2 sum(L))), or the doubled batch's PackPlan."""
+    if cfg.get("pack") is not None:
+        return {"pack": cfg["pack2"].plan}
+    return {"lengths": cfg["lengths2"]}
+
+
+def _bidir_shape(x, pk, double):
+    """The doubled (or, double=False, the single) tensor's leading shape for x (B,T,.) / packed (1,n,.)."""
+    B, T = x.shape[0], x.shape[1]
+    if double:
+        return (1, 2 * T) if pk else (2 * B, T)
+    return (1, T // 2) if pk else (B // 2, T)
+
+
+def bidir_split(x, cfg):
+    """x (B,T,C), or packed (1,n,C), elements of 1, 2 or 4 bytes -> (2B,T,C) / (1,2n,C): the batch and, behind it, every
+    clip read backwards inside its own length; zeros on the tails."""
+    sfx, B, T, tail = _bidir_map(cfg)
+    x = x.contiguous()
+    C = x.shape[2]
+    out = torch.empty(*_bidir_shape(x, sfx == "_pk", True), C, dtype=x.dtype, device=x.device)
+    tok = timer.start("bidir_split")
+    check(getattr(lib, "sparch_bidir_split" + sfx)(B, T if T is not None else x.shape[1], C, x.element_size(), ptr(x),
+                                                   ptr(out), *tail, _stream()), "sparch_bidir_split" + sfx)
+    timer.stop(tok)
+    return out
+
+
+def bidir_split_backward(g, cfg):
+    """The adjoint of bidir_split on fp32: g (2B,T,C) / (1,2n,C) -> (B,T,C) / (1,n,C), exactly 0 on the tails."""
+    sfx, B, T, tail = _bidir_map(cfg)
+    g = _f32c(g)
+    C = g.shape[2]
+    out = torch.empty(*_bidir_shape(g, sfx == "_pk", False), C, dtype=torch.float32, device=g.device)
+    tok = timer.start("bidir_split_bwd")
+    check(getattr(lib, "sparch_bidir_split_bwd" + sfx)(B, T if T is not None else g.shape[1], C, ptr(g), ptr(out), *tail,
+                                                       _stream()), "sparch_bidir_split_bwd" + sfx)
+    timer.stop(tok)
+    return out
+
+
+def bidir_join(s16, cfg, scale=1.0, want_fp32=True):
+    """s16 (2B,T,H) / (1,2n,H), the bf16 0/1 plane of the doubled batch -> (s (B,T,2H) fp32 = plane * scale or None,
+    the plane (B,T,2H), count (2H,) int32 of the spikes per output column): forward columns first, the reverse
+    direction back in the clip's own time order, zeros on the tails."""
+    sfx, B, T, tail = _bidir_map(cfg)
+    H = s16.shape[2]
+    lead = _bidir_shape(s16, sfx == "_pk", False)
+    y16 = torch.empty(*lead, 2 * H, dtype=torch.bfloat16, device=s16.device)
+    y32 = torch.empty(*lead, 2 * H, dtype=torch.float32, device=s16.device) if want_fp32 else None
+    count = torch.zeros(2 * H, dtype=torch.int32, device=s16.device)
+    tok = timer.start("bidir_join")
+    check(getattr(lib, "sparch_bidir_join" + sfx)(B, T if T is not None else s16.shape[1], H, ptr(s16), ptr(y16), ptr(y32),
+                                                  float(scale), ptr(count), *tail, _stream()), "sparch_bidir_join" + sfx)
+    timer.stop(tok)
+    return y32, y16, count
+
+
+def bidir_join_backward(g, g_rate, rate_scale, cfg):
+    """The adjoint of bidir_join: g (B,T,2H) / (1,n,2H) fp32 -> (2B,T,H) / (1,2n,H), with g_rate[column] * rate_scale (the
+    firing rate's gradient; g_rate None: nothing) added on the valid steps and exactly 0 on the tails."""
+    sfx, B, T, tail = _bidir_map(cfg)
+    g = _f32c(g)
+    H = g.shape[2] // 2
+    out = torch.empty(*_bidir_shape(g, sfx == "_pk", True), H, dtype=torch.float32, device=g.device)
+    tok = timer.start("bidir_join_bwd")
+    check(getattr(lib, "sparch_bidir_join_bwd" + sfx)(B, T if T is not None else g.shape[1], H, ptr(g), ptr(g_rate),
+                                                      float(rate_scale), ptr(out), *tail, _stream()),
+          "sparch_bidir_join_bwd" + sfx)
+    timer.stop(tok)
+    return out
 
 
 def check_stateful(kind=None, H=0, *, dirs=1, lengths=None, pack=None, per_step=None, readout=None, T=None):
@@ -1118,6 +1222,7 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     dev = Wx.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    _check_one_direction(dirs, lengths, pack)
     _check_ragged(lengths, dirs, recurrent, H)
     _check_packed(pack, dirs, recurrent, H)
     len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
@@ -1229,6 +1334,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
                              "supported (the stateful recurrent backward runs whole sequences only)")
         if saved[0].dtype != torch.float32:
             raise ValueError("sparch_amd: stateful training needs fp32 saves (SPARCH_SAVE_DTYPE=bf16 is not supported)")
+    _check_one_direction(dirs, lengths, pack)
     _check_ragged(lengths, dirs, recurrent, H)
     _check_packed(pack, dirs, recurrent, H)
     len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
@@ -1380,15 +1486,26 @@ class SpikingLayerFn(torch.autograd.Function):
         p = {k_: v for k_, v in p.items() if v is not None}
         if cfg.get("states_ready") is not None:  # initial states uploaded on a side stream (snns._rand_batch)
             cfg["states_ready"]()
-        s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
-                                                dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
-                                                want_s_out=cfg.get("fp32_out", True),
-                                                want_saves=any(ctx.needs_input_grad) or bool(cfg.get("stateful")),
-                                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
-                                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
+        inv_keep = 1.0 / (1.0 - p_drop)
+        if _bidir_ragged(cfg):
+            # both directions as 2B sequences of the one-direction `_len` / `_pk` kernels: the normalised drive is
+            # split (the projection and BatchNorm's statistics ran once, on B rows, as on the padded path), the
+            # spikes are joined and counted per direction
+            Wx2 = bidir_split(Wx_in.view(B, T, H), cfg)
+            _, _, saved, s16_2 = cell_forward(kind, Wx2, scale, shift, p, u0, w0, s0, B=Wx2.shape[0], dirs=1, theta=theta,
+                                              p_drop=p_drop, seed=seed, want_s_out=False,
+                                              want_saves=any(ctx.needs_input_grad), surrogate=cfg.get("surrogate"),
+                                              **_bidir_cell_kw(cfg))
+            s_out, s16, count = bidir_join(s16_2, cfg, scale=inv_keep, want_fp32=cfg.get("fp32_out", True))
+        else:
+            s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
+                                                    dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
+                                                    want_s_out=cfg.get("fp32_out", True),
+                                                    want_saves=any(ctx.needs_input_grad) or bool(cfg.get("stateful")),
+                                                    surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
+                                                    **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
         if s_out is None:
             s_out = spike_placeholder(B, T, H * dirs, x.device)
-        inv_keep = 1.0 / (1.0 - p_drop)
         n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]  # ragged: the mean is over valid steps
         rate = count * (inv_keep / float(n_steps))  # snns.py:174 on post-dropout spikes (int32 * float -> fp32, one kernel)
         ctx.cfg, ctx.inp = cfg, inp
@@ -1423,6 +1540,25 @@ class SpikingLayerFn(torch.autograd.Function):
             g_rate = _f32c(g_rate)
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
+        if _bidir_ragged(cfg):
+            # the forward's movements, reversed: the gather (with the rate's gradient, each direction's own count over
+            # the valid steps), the one-direction cell backward on the doubled batch — without a rate gradient and
+            # without the fused BatchNorm sums, which would see 2B rows of a projection that has B — and the two
+            # directions' dWx summed in the clip's own time order; _project_backward forms BatchNorm's sums itself
+            n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]
+            g2 = bidir_join_backward(g_s, g_rate, 1.0 / float(n_steps), cfg)
+            dWx2, pg = cell_backward(kind, g2, None, p, u0, w0, s0, ctx.cell_saved, B=g2.shape[0], dirs=1, T=g2.shape[1],
+                                     H=H, theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=None,
+                                     surrogate=cfg.get("surrogate"), **_bidir_cell_kw(cfg))
+            ctx.cell_saved = None
+            dWx = bidir_split_backward(dWx2, cfg)
+            dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, 1,
+                                                      need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                      w_planes=ctx.w_planes, dx_planes=True)
+            dx = None if dx is None else dx.view(B, T, K)
+            ctx.w_planes = ctx.inp = None
+            return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
+                    pg.get("V"), None, None, None)
         # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         st_kw = {}

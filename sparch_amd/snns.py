@@ -532,7 +532,7 @@ class _SpikingLayer(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward_with_rate(self, x, states=None, states_ready=None, fp32_out=True, lengths=None, pack=None,
-                          return_state=False):
+                          return_state=False, pack2=None, lengths2=None):
         """Returns (spikes (B,T,H*(1+bidir)), firing_rate (H*(1+bidir),)).  Equivalent to the
         reference forward (e.g. snns.py:663-694) followed by `.mean(dim=(0,1))` (174).
         states: (u0, w0, s0) drawn ahead of time by SNN.forward (same generator, same order);
@@ -545,6 +545,11 @@ class _SpikingLayer(nn.Module):
         every row's padded steps and the firing rate is the mean over valid steps (SNN.forward has the contract).
         pack: None, or what prepare_packing() returned — x is then the PACKED batch (1, n, feat) (functional.pack_rows)
         and so is the result; `states` hold the plan's `batch` rows in its sorted order (drawn so when not given).
+        A bidirectional layer with lengths or pack ("Bidirectional ragged batches") reads every clip
+        backwards inside its own length: y[b, t, H:] is the reverse direction after the clip's steps lengths[b]-1 .. t.
+        Its `states` have 2 * batch rows, row batch + b the reverse direction of clip b; with pack they are in the order
+        of pack2 = prepare_bidir_packing(pack)'s doubled plan; pack2 and lengths2 = double_lengths(lengths) are made
+        here when not given.
         return_state=True (stateful training, SNN.forward has the contract): returns (spikes, firing_rate, state) with
         state = {"u": u_T, ["w": w_T,] "s": 1[u_T > threshold]}, the raw spike before dropout; the three are nodes of the
         graph, and the gradient of `states` comes out of the backward.  LIF / adLIF, one direction, no lengths / pack."""
@@ -592,6 +597,10 @@ class _SpikingLayer(nn.Module):
             cfg["lengths"] = lengths
         if pack is not None:
             cfg["pack"] = pack
+        if dirs == 2 and pack is not None:  # the doubled batch's plan (SNN.forward makes one for all its layers)
+            cfg["pack2"] = pack2 if pack2 is not None else prepare_bidir_packing(pack, x.device)
+        elif dirs == 2 and lengths is not None:  # the doubled batch's lengths
+            cfg["lengths2"] = lengths2 if lengths2 is not None else double_lengths(lengths)
         if return_state:
             cfg["stateful"] = True
         nw = self.norm.weight if self.normalize else None
@@ -804,6 +813,51 @@ def prepare_packing(lengths, batch, T, device):
                        n, int(lens[0]), int(batch), int(T), host_views)
 
 
+def double_lengths(lengths):
+    """prepare_lengths()'s result for the doubled batch of a bidirectional layer: every clip and, behind the batch, its
+    reversed copy — the lengths twice, and twice their sum."""
+    return torch.cat((lengths[0], lengths[0])), 2 * lengths[1]
+
+
+def prepare_bidir_packing(plan, device):
+    """The functional.BidirPlan of a bidirectional layer on the packed batch `plan` (prepare_packing's): the 2 * batch
+    sequences — batch row b is clip b, row batch + b clip b read backwards — get a PackPlan of their own by
+    prepare_packing's rules (stable descending order of the doubled lengths, exclusive prefix sum, inverse), and fwd /
+    rev say where in that doubled packed tensor the two copies of sequence j of `plan` start.  Made on the host from
+    plan.host and uploaded as one pinned buffer."""
+    import numpy as np
+
+    order, lens, _ = plan.host
+    B = plan.batch
+    if 2 * plan.n >= 2 ** 31:
+        raise ValueError(f"lengths: the doubled packed batch has {2 * plan.n} rows, more than the int32 offsets hold")
+    by_row = np.empty(B, np.int64)
+    by_row[order] = lens
+    twice = np.concatenate([by_row, by_row])
+    order2 = np.argsort(-twice, kind="stable")
+    lens2 = twice[order2]
+    B2 = 2 * B
+    buf = np.empty(4 * B2 + 1 + 2 * B, np.int32)
+    buf[:B2] = order2
+    buf[B2:2 * B2] = lens2
+    buf[2 * B2] = 0
+    np.cumsum(lens2, out=buf[2 * B2 + 1:3 * B2 + 1])
+    inverse2 = np.empty(B2, np.int64)
+    inverse2[order2] = np.arange(B2)
+    buf[3 * B2 + 1:4 * B2 + 1] = inverse2
+    offsets2 = buf[2 * B2:3 * B2 + 1]
+    buf[4 * B2 + 1:4 * B2 + 1 + B] = offsets2[inverse2[order]]
+    buf[4 * B2 + 1 + B:] = offsets2[inverse2[B + np.asarray(order, np.int64)]]
+    flat = torch.from_numpy(buf)
+    if torch.device(device).type != "cpu":  # (pinned and non-blocking: see prepare_lengths)
+        flat = flat.pin_memory().to(device, non_blocking=True)
+    cut = lambda a, b: flat[a:b]  # noqa: E731
+    host_views = (buf[:B2], buf[B2:2 * B2], buf[2 * B2:3 * B2 + 1])
+    plan2 = Fn.PackPlan(cut(0, B2), cut(B2, 2 * B2), cut(2 * B2, 3 * B2 + 1), cut(3 * B2 + 1, 4 * B2 + 1), 2 * plan.n,
+                        plan.t_max, B2, plan.T, host_views)
+    return Fn.BidirPlan(plan2, cut(4 * B2 + 1, 4 * B2 + 1 + B), cut(4 * B2 + 1 + B, 4 * B2 + 1 + 2 * B))
+
+
 def _check_packed_layer(layer, plan=None, x=None):
     """What a layer refuses with pack=True; plan / x: also checked to be prepare_packing()'s and
     the packed batch that goes with it."""
@@ -828,6 +882,15 @@ def _check_ragged_layer(layer, lengths=None):
                          "padded rows non-zero, and BatchNorm removes the bias anyway)")
     if Fn.SYNC_BN is not None and Fn.SYNC_BN["world"] > 1:
         raise ValueError("sparch_amd: lengths with --sync_bn is not supported")
+
+
+def _check_bidir_input(net, x, what):
+    """A bidirectional network with lengths refuses a host tensor with the other refusals, as a ValueError before the
+    first kernel: the reverse direction's flip inside each clip's own length exists as HIP kernels
+    only (csrc/bidir.hip)."""
+    if net.bidirectional and x.device.type != "cuda":
+        raise ValueError(f"sparch_amd: {what} with bidirectional=True takes an input on the HIP device (got {x.device}: the "
+                         "reverse direction flips inside each clip's own length in kernels that have no host form)")
 
 
 _LAYER_CLASSES = {"LIF": LIFLayer, "adLIF": adLIFLayer, "RLIF": RLIFLayer, "RadLIF": RadLIFLayer}
@@ -859,7 +922,10 @@ class SNN(nn.Module):
     is then what the network gives for x[b:b+1, :lengths[b]] run on its own with the same initial-state rows (in train
     mode: with the same normalisation statistics, taken over the valid steps): hidden spikes are 0 on the padding, the
     readout sums over the row's own steps, firing rates are means over valid steps.  None: every row runs to `time`,
-    as the reference does.
+    as the reference does.  With bidirectional=True ("Bidirectional ragged batches") the reverse
+    direction reads every clip backwards inside its own length — columns H: of a hidden layer's row b at step t are its
+    state after the clip's steps lengths[b]-1 .. t — and each direction's firing rate is its own mean over the valid
+    steps; also with pack=True.
 
     pack=True (with lengths; DESIGN.md section 6, "Packed ragged batches"): the same contract, but the padded steps are
     skipped instead of masked — the batch is packed to (sum(lengths), feat) rows, sorted by length, once; every layer runs
@@ -1117,6 +1183,7 @@ class SNN(nn.Module):
                                  "lengths and their sum change with every batch")
             for layer in self.snn:  # every refusal before the first kernel
                 _check_ragged_layer(layer)
+            _check_bidir_input(self, x, "lengths")
             lengths = prepare_lengths(lengths, x.shape[0], x.shape[1], x.device)  # on the device once per forward
             if x.requires_grad:  # the input's gradient is 0 on the padding (x is 0 there: the values do not change)
                 steps = torch.arange(x.shape[1], device=x.device)
@@ -1135,6 +1202,9 @@ class SNN(nn.Module):
             states = self.draw_states(x.shape[0], x.device)
         rates = []
         final = []  # stateful: every layer's final state
+        ragged_kw = {} if lengths is None else {"lengths": lengths}
+        if lengths is not None and self.bidirectional:  # the doubled batch's lengths, once for all layers
+            ragged_kw["lengths2"] = double_lengths(lengths)
         wait = getattr(states, "wait_ready", None)  # the states' upload runs under the first projection GEMM
         for i, layer in enumerate(self.snn):
             if self.use_readout_layer and i == last:
@@ -1157,7 +1227,7 @@ class SNN(nn.Module):
                     final.append(st)
                 else:
                     x, r = layer.forward_with_rate(x, states=states[i], states_ready=wait if i == 0 else None,
-                                                   fp32_out=not inner, **({} if lengths is None else {"lengths": lengths}))
+                                                   fp32_out=not inner, **ragged_kw)
                 if wait is not None:
                     wait()  # (no-op once the first layer's call has waited)
                 rates.append(r)
@@ -1182,6 +1252,7 @@ class SNN(nn.Module):
         plan = prepare_packing(lengths, batch, T, x.device)
         for layer in self.snn:  # (what depends on the batch's longest sequence: chunked recurrent launches)
             _check_packed_layer(layer, plan)
+        _check_bidir_input(self, x, "pack=True")
         Fn._require_device(x, "input")
         tag = Fn.input_plane_of(x)
         if tag is not None:  # input_from_counts: the bf16 plane is the data, x a placeholder without values
@@ -1197,6 +1268,10 @@ class SNN(nn.Module):
         states = self.draw_states(batch, x.device)
         states.wait_ready()
         take = lambda t_: None if t_ is None else t_.index_select(0, plan.order)  # noqa: E731
+        # bidirectional layers: 2 * batch state rows (row batch + b the reverse direction of clip b), in the doubled
+        # batch's own sorted order
+        plan2 = prepare_bidir_packing(plan, x.device) if self.bidirectional else None
+        take2 = lambda t_: None if t_ is None else t_.index_select(0, plan2.plan.order)  # noqa: E731
         last = self.num_layers - 1
         rates = []
         for i, layer in enumerate(self.snn):
@@ -1204,7 +1279,11 @@ class SNN(nn.Module):
                 x = layer(x, u0=take(states[i]), pack=plan).index_select(0, plan.inverse)
             else:
                 inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
-                x, r = layer.forward_with_rate(x, states=tuple(take(t_) for t_ in states[i]), fp32_out=not inner, pack=plan)
+                if layer.bidirectional:
+                    x, r = layer.forward_with_rate(x, states=tuple(take2(t_) for t_ in states[i]), fp32_out=not inner,
+                                                   pack=plan, pack2=plan2)
+                else:
+                    x, r = layer.forward_with_rate(x, states=tuple(take(t_) for t_ in states[i]), fp32_out=not inner, pack=plan)
                 rates.append(r)
         if not self.use_readout_layer:
             x = Fn.UnpackRowsFn.apply(x.reshape(plan.n, -1), plan)
