@@ -1305,6 +1305,43 @@ int sparch_spike_encode(int code, int B, int T, int K, const float* x, const flo
                         int ldp, uint8_t* counts, float* dense, uint32_t* totals, void* stream);
 int sparch_spike_encode_width(int code, int K);  /* K for RATE and IF, 2K for DELTA; 0 for an unknown code or K < 1 */
 
+/* ---- Synaptic currents (csrc/synapse.hip): a learnable exponential synapse per neuron, in front
+ * of a spiking cell.  gamma (H) fp32 is the parameter; the kernels take g_h = min(max(gamma_h, lo), hi) and
+ * oma_h = 1.0f - g_h themselves, 0 <= lo <= hi < 1.  z[b,t,h] is the cell's input as the cell kernels form it from
+ * (Wx, bias, scale, shift): Wx (+ bias), then fma(., scale, shift) where a scale is given (bias, scale, shift (H) or
+ * NULL; shift NULL with a scale: 0).  With len_b the row's own length (T without lengths) and i[b,-1,h] = i0[b,h]
+ * (i0 (B,H) or NULL: 0):
+ *   i[b,t,h]   = g_h * i[b,t-1,h] + oma_h * z[b,t,h]        0 <= t < len_b   (two products, one add, never fused)
+ *   a[b,t,h]   = g_i[b,t,h] + g_h * a[b,t+1,h],  a[b,len_b,h] = 0            (what g_i holds at t >= len_b is never read)
+ *   g_z[b,t,h] = oma_h * a[b,t,h]
+ *   g_gamma[h] = gate_h * (sum_b sum_{t<len_b} a[b,t,h] * (i[b,t-1,h] - i[b,t,h])) / oma_h,
+ *   gate_h     = 1 if lo <= gamma_h <= hi else 0
+ * All tensors fp32, (B,T,H) with unit stride along H and rows ldwx / ldi / ldg / ldgz ELEMENTS apart (>= H; batch row b
+ * starts at row b T).  lengths (B) int32 or NULL (dense): steps t >= len_b of i_out and g_z are written as zeros and
+ * do not advance the state.  offsets (B+1) int32 non-NULL: the packed layout of sparch_pack_rows — sequence j owns rows
+ * [offsets[j], offsets[j] + lengths[j]), T is the longest length, rows that do not exist are not written; i0, i_T hold
+ * the sequences in the plan's order.  16-byte accesses where H, the row strides and the base addresses are multiples of
+ * 16 bytes, single elements otherwise.
+ * sparch_synapse_fwd: i_T (B,H) or NULL receives each row's state after its last valid step; it may alias i0 (a
+ * stream's chunk step: T = the chunk's steps, the carried state advanced in place).
+ * sparch_synapse_bwd: i is the forward's i_out, i0 the forward's; g_z and g_gamma are each optional (not both NULL).
+ * g_gamma is summed from per-sequence partial sums in ws (sparch_synapse_bwd_workspace_bytes(B,T,H) bytes, 0 for a bad
+ * shape) in a fixed order: no atomics, the same bits on every run.
+ * bn_x (B,T,H) fp32, rows ldbn apart, or NULL: the layer's raw projection under BatchNorm; with it (and bn_mean,
+ * bn_invstd (H), bn_ws (2,B,H), g_z, all required then) the call also writes BatchNorm backward's per-sequence partial
+ * sums, bn_ws[0][b][h] = sum_t g_z and bn_ws[1][b][h] = sum_t g_z * ((bn_x - mean) * invstd), added from the row's last
+ * step to its first as the cell backward kernels add theirs (sparch_colsum_clamped finishes them).
+ * SPARCH_EINVAL before any device work: B, T, H < 1, a NULL required pointer, a row stride < H, offsets without
+ * lengths, lo / hi outside 0 <= lo <= hi < 1; SPARCH_EWORKSPACE: ws too small. */
+int sparch_synapse_fwd(int B, int T, int H, const float* Wx, long long ldwx, const float* bias, const float* scale,
+                       const float* shift, const float* gamma, float lo, float hi, const float* i0, float* i_out,
+                       long long ldi, float* i_T, const int* lengths, const int* offsets, void* stream);
+size_t sparch_synapse_bwd_workspace_bytes(int B, int T, int H);
+int sparch_synapse_bwd(int B, int T, int H, const float* g_i, long long ldg, const float* i, long long ldi,
+                       const float* i0, const float* gamma, float lo, float hi, float* g_z, long long ldgz,
+                       float* g_gamma, void* ws, size_t ws_bytes, const float* bn_x, long long ldbn, const float* bn_mean,
+                       const float* bn_invstd, float* bn_ws, const int* lengths, const int* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,6 +226,11 @@ PROTOTYPES = {
     "sparch_spike_encode": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, c_int, c_longlong, c_uint64, P, P, c_int,
                                     P, P, P, P]),
     "sparch_spike_encode_width": (c_int, [c_int, c_int]),
+    "sparch_synapse_fwd": (c_int, [c_int, c_int, c_int, P, c_longlong, P, P, P, P, c_float, c_float, P, P, c_longlong,
+                                   P, P, P, P]),
+    "sparch_synapse_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sparch_synapse_bwd": (c_int, [c_int, c_int, c_int, P, c_longlong, P, c_longlong, P, P, c_float, c_float, P,
+                                   c_longlong, P, P, c_size_t, P, c_longlong, P, P, P, P, P, P]),
 }
 
 

@@ -194,6 +194,39 @@ def parse_delays(value):
     return res
 
 
+def parse_synapse(value):
+    """SPARCH_SYNAPSE=lo:hi[:lo|uniform][:fixed][:hidden]: unset or empty -> None (no synapse, nothing changes); else the
+    SNN arguments {"synapse": (lo, hi) with 0 <= lo <= hi < 1, "syn_init": "uniform" (default) or "lo", "learn_synapse":
+    False with `fixed`, "synapse_layers": "hidden" with `hidden` (default "all")}; the options in any order, each at most
+    once; anything else is refused."""
+    if value is None or value.strip() == "":
+        return None
+    parts = [part.strip() for part in value.strip().split(":")]
+    ok = len(parts) >= 2
+    lo = hi = float("nan")
+    if ok:
+        try:
+            lo, hi = float(parts[0]), float(parts[1])
+        except ValueError:
+            ok = False
+    ok = ok and 0.0 <= lo <= hi < 1.0
+    res = {"synapse": (lo, hi), "syn_init": None, "learn_synapse": True, "synapse_layers": "all"}
+    for opt in parts[2:]:
+        if opt in ("lo", "uniform") and res["syn_init"] is None:
+            res["syn_init"] = opt
+        elif opt == "fixed" and res["learn_synapse"]:
+            res["learn_synapse"] = False
+        elif opt == "hidden" and res["synapse_layers"] == "all":
+            res["synapse_layers"] = "hidden"
+        else:
+            ok = False
+    if not ok:
+        raise ValueError(f"SPARCH_SYNAPSE={value!r}: lo:hi[:lo|uniform][:fixed][:hidden] with the limits of the synaptic "
+                         "decay 0 <= lo <= hi < 1 (unset: no synapse)")
+    res["syn_init"] = res["syn_init"] or "uniform"
+    return res
+
+
 def check_encode_model(net, encoder):
     """SPARCH_ENCODE with a given network (a loaded one included): a spiking network whose first layer is as wide as
     the encoder's output — refused before the first kernel otherwise."""
@@ -319,6 +352,20 @@ class Experiment:
             if self.tbptt is not None:
                 raise ValueError("sparch_amd: SPARCH_DELAYS with SPARCH_TBPTT is not supported (the delayed input is "
                                  "not carried across chunks)")
+
+        # SPARCH_SYNAPSE=lo:hi[:lo|uniform][:fixed][:hidden]: a learnable (or fixed) exponential synapse per neuron of
+        # every hidden layer (or of every one but the first) — SNN(synapse=(lo, hi)); DESIGN.md section 6, "Synaptic
+        # currents".  Every epoch logs each layer's mean and largest clamped decay.
+        self.synapse = parse_synapse(os.environ.get("SPARCH_SYNAPSE"))
+        if self.synapse is not None:
+            if self.model_type not in ["LIF", "adLIF", "RLIF", "RadLIF"]:
+                raise ValueError(f"sparch_amd: SPARCH_SYNAPSE needs a spiking model (got {self.model_type})")
+            if self.tbptt is not None:
+                raise ValueError("sparch_amd: SPARCH_SYNAPSE with SPARCH_TBPTT is not supported (the synaptic current "
+                                 "is not carried across chunks)")
+            if getattr(args, "bidirectional", False) and mode == "pack":
+                raise ValueError("sparch_amd: SPARCH_SYNAPSE with --bidirectional and SPARCH_LENGTHS=pack is not "
+                                 "supported")
 
         # SPARCH_ENCODE=code[:key=value,...]: hd / sc features are turned into spikes on the device, behind the fbank
         # (encoders.SpikeEncoder; DESIGN.md section 6, "Spike encoders"): layer 0 reads a count plane like every other
@@ -525,14 +572,21 @@ class Experiment:
                 logging.warning(f"SPARCH_READOUT={self.readout} is ignored: the loaded model keeps its own readout")
             if self.delays is not None:
                 logging.warning("SPARCH_DELAYS is ignored: the loaded model keeps its own delays (or none)")
+            if self.synapse is not None:
+                logging.warning("SPARCH_SYNAPSE is ignored: the loaded model keeps its own synapses (or none)")
         elif self.model_type in ["LIF", "adLIF", "RLIF", "RadLIF"]:
             name, scale = self.surrogate if self.surrogate is not None else ("boxcar", None)
             self.net = SNN(input_shape=input_shape, layer_sizes=layer_sizes, neuron_type=self.model_type,
                            dropout=self.pdrop, normalization=self.normalization, use_bias=self.use_bias,
                            bidirectional=self.bidirectional, use_readout_layer=True, surrogate=name,
                            surrogate_scale=scale, **({} if self.readout is None else {"readout": self.readout}),
-                           **(self.delays or {})).to(self.device)
+                           **(self.delays or {}), **(self.synapse or {})).to(self.device)
             logging.info(f"\nCreated new spiking model:\n {self.net}\n")
+            if self.synapse is not None:
+                logging.info("Synaptic currents: decay in [{0:g}, {1:g}], init {syn_init}, {2}, {synapse_layers} layers "
+                             "(SPARCH_SYNAPSE)".format(*self.synapse["synapse"],
+                                                       "learnable" if self.synapse["learn_synapse"] else "fixed",
+                                                       **self.synapse))
             if self.delays is not None:
                 logging.info("Axonal delays: up to {max_delay} steps, init {delay_init}, {0}, {delay_layers} layers "
                              "(SPARCH_DELAYS)".format("learnable" if self.delays["learn_delays"] else "fixed",
@@ -744,6 +798,10 @@ class Experiment:
             self.opt.reset_clip_stats()  # (per-epoch figures)
             logging.info(f"Epoch {e}: grad norm max={s['max_norm']}, clipped {s['clipped']} of {s['steps']} steps, "
                          f"skipped {s['skipped']} non-finite")
+        if getattr(self.net, "synapse", None) is not None:  # one read-back per epoch
+            stats = torch.stack([torch.stack((g.mean(), g.max())) for g in self.net.synapse_gammas().values()]).tolist()
+            for i, (mean, top) in zip(self.net.synapse_gammas(), stats):
+                logging.info(f"Epoch {e}: layer {i} synapse: mean gamma={mean:.4f}, max gamma={top:.4f}")
         if getattr(self.net, "max_delay", 0):  # one read-back per epoch; the forward never reads the delays on the host
             for i, d in self.net.delay_steps().items():
                 logging.info(f"Epoch {e}: layer {i} delays: mean d={float(d.float().mean()):.3f}, max d={int(d.max())} "

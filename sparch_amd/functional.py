@@ -1031,6 +1031,139 @@ class DelayFn(torch.autograd.Function):
         return g_x, g_delay, None
 
 
+# ----------------------------------------------------------------------------- synaptic currents
+def check_synapse(synapse):
+    """synapse as SNN and the synapse kernels take it: None, or (lo, hi) with 0 <= lo <= hi < 1 -> None or two floats."""
+    if synapse is None:
+        return None
+    try:
+        lo, hi = synapse
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"sparch_amd: synapse must be None or a pair (lo, hi) of numbers (got {synapse!r})") from None
+    if not 0.0 <= lo <= hi < 1.0:
+        raise ValueError(f"sparch_amd: synapse limits must satisfy 0 <= lo <= hi < 1 (got {synapse!r})")
+    return lo, hi
+
+
+def _limits(limits):
+    if limits is None:
+        raise ValueError("sparch_amd: the synapse kernels need their limits (lo, hi)")
+    return check_synapse(limits)
+
+
+def _synapse_cols(t, H, device, what, name):
+    """An (H,) per-column operand of the synapse kernels (None stays None): contiguous fp32 on the tensors' device."""
+    if t is None:
+        return None
+    t = _f32c(t)
+    if t.numel() != H or t.device != device:
+        raise ValueError(f"{what}: {name} must hold {H} values on {device} (got {tuple(t.shape)} on {t.device})")
+    return t
+
+
+def _synapse_state(t, rows, H, device, what, name):
+    if t is None:
+        return None
+    if tuple(t.shape) != (rows, H) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{what}: {name} must be a contiguous ({rows}, {H}) fp32 tensor on {device}")
+    return t
+
+
+def _synapse_out(out, B, T, H, device, what):
+    """(the tensor a synapse kernel writes, its row stride): `out` where given and usable as it lies, else a fresh one."""
+    if out is None:
+        return torch.empty(B, T, H, dtype=torch.float32, device=device), H
+    if tuple(out.shape) != (B, T, H) or out.dtype != torch.float32 or out.device != device:
+        raise ValueError(f"{what}: out must be a ({B}, {T}, {H}) fp32 tensor on {device}")
+    rows, ld = _delay_rows(out, what)
+    if rows is not out:
+        raise ValueError(f"{what}: out must have unit stride along H and one row stride")
+    return out, ld
+
+
+def synapse_forward(Wx, gamma, limits, bias=None, scale=None, shift=None, i0=None, lengths=None, pack=None,
+                    want_final=False, i_T=None, out=None):
+    """i[b,t,h] = g_h i[b,t-1,h] + (1 - g_h) z[b,t,h] for t < len_b, with g = clamp(gamma, *limits) taken on the device
+    and z the cell's input as the cell forms it from (Wx, bias, scale, shift) (`sparch_synapse_fwd`; DESIGN.md section
+    6, "Synaptic currents").  Wx (B,T,H) fp32, or packed (1,n,H) with pack; i0 (rows,H) or None (zeros).  Returns i, and
+    with want_final (or an i_T to write, which may be i0) the pair (i, i_T): every row's state after its last step.
+    out: an fp32 tensor of Wx's shape to write (unit stride along H, one row stride; every row that exists is written),
+    else a fresh contiguous one."""
+    lo, hi = _limits(limits)
+    _require_device(Wx, "input")
+    Wx, ldwx = _delay_rows(Wx if Wx.dtype == torch.float32 else Wx.float(), "synapse_forward")
+    B, T, H = Wx.shape
+    dev = Wx.device
+    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    gamma = _synapse_cols(gamma, H, dev, "synapse_forward", "gamma")
+    bias, scale, shift = (_synapse_cols(t, H, dev, "synapse_forward", n)
+                          for t, n in ((bias, "bias"), (scale, "scale"), (shift, "shift")))
+    i0 = _synapse_state(i0, Bk, H, dev, "synapse_forward", "i0")
+    if i_T is None and want_final:
+        i_T = torch.empty(Bk, H, dtype=torch.float32, device=dev)
+    i_T = _synapse_state(i_T, Bk, H, dev, "synapse_forward", "i_T")
+    i_out, ldi = _synapse_out(out, B, T, H, dev, "synapse_forward")
+    tok = timer.start("synapse_fwd")
+    check(lib.sparch_synapse_fwd(Bk, Tk, H, ptr(Wx), ldwx, ptr(bias), ptr(scale), ptr(shift), ptr(gamma), lo, hi,
+                                 ptr(i0), ptr(i_out), ldi, ptr(i_T), len_ptr, off_ptr, _stream()), "sparch_synapse_fwd")
+    timer.stop(tok)
+    return (i_out, i_T) if i_T is not None else i_out
+
+
+def synapse_backward(g_i, i, gamma, limits, i0=None, lengths=None, pack=None, need_gz=True, need_ggamma=True, out=None,
+                     bn=None):
+    """The two gradients of synapse_forward (`sparch_synapse_bwd`) -> (g_z or None, g_gamma or None), both fp32.  i is
+    the forward's result, i0 the forward's.  g_z is exactly 0 on padded steps, whatever g_i holds there; g_gamma is
+    summed in a fixed order (two runs give the same bits) and is 0 where gamma lies outside its limits.  out: a tensor
+    for g_z, as synapse_forward's.
+    bn = (Wx_raw, mean, invstd) of the layer's BatchNorm: a third result, (sum g_z, sum g_z xhat) per column — BatchNorm
+    backward's column sums, accumulated by the same kernel in the cell backward kernels' order and finished as theirs."""
+    lo, hi = _limits(limits)
+    _require_device(g_i, "gradient")
+    if not need_gz and not need_ggamma:
+        return None, None
+    g_i, ldg = _delay_rows(g_i if g_i.dtype == torch.float32 else g_i.float(), "synapse_backward")
+    B, T, H = g_i.shape
+    dev = g_i.device
+    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    gamma = _synapse_cols(gamma, H, dev, "synapse_backward", "gamma")
+    i0 = _synapse_state(i0, Bk, H, dev, "synapse_backward", "i0")
+    g_z, ldgz = _synapse_out(out, B, T, H, dev, "synapse_backward") if need_gz else (None, H)
+    g_gamma = ws = None
+    nbytes, ldi = 0, H
+    if need_ggamma:
+        if i is None or tuple(i.shape) != (B, T, H):
+            raise ValueError("synapse_backward: gamma's gradient needs the forward's result, in the gradient's shape")
+        i, ldi = _delay_rows(i if i.dtype == torch.float32 else i.float(), "synapse_backward")
+        g_gamma = torch.empty(H, dtype=torch.float32, device=dev)
+        nbytes = lib.sparch_synapse_bwd_workspace_bytes(Bk, Tk, H)
+        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
+    bn_x = bn_mean = bn_invstd = bn_ws = None
+    if bn is not None:
+        bn_x, bn_mean, bn_invstd = bn
+        if not need_gz or bn_x.numel() != B * T * H or not bn_x.is_contiguous() or bn_x.dtype != torch.float32:
+            raise ValueError("synapse_backward: bn needs g_z and the contiguous fp32 projection in the gradient's shape")
+        bn_ws = torch.empty(2, Bk, H, dtype=torch.float32, device=dev)
+    tok = timer.start("synapse_bwd")
+    check(lib.sparch_synapse_bwd(Bk, Tk, H, ptr(g_i), ldg, ptr(i) if need_ggamma else None, ldi, ptr(i0), ptr(gamma),
+                                 lo, hi, ptr(g_z), ldgz, ptr(g_gamma), ptr(ws), nbytes, ptr(bn_x), H, ptr(bn_mean),
+                                 ptr(bn_invstd), ptr(bn_ws), len_ptr, off_ptr, _stream()), "sparch_synapse_bwd")
+    timer.stop(tok)
+    if bn is not None:
+        return g_z, g_gamma, tuple(_finish_param_grads(bn_ws, Bk, H, [None, None], [(0.0, 0.0)] * 2))
+    return g_z, g_gamma
+
+
+def synapse_stream(Wx, gamma, limits, state, bias=None, scale=None, shift=None):
+    """The synapse on a chunk Wx (B,Tc,H) of a stream: state (B,H) fp32, contiguous, is the current after the last step
+    seen (zeros at the start of a stream) and is advanced in place; the same call as synapse_forward, so a stream cut
+    into chunks gives the whole sequence's bits."""
+    if state is None:
+        raise ValueError("synapse_stream: the carried state is required")
+    return synapse_forward(Wx, gamma, limits, bias, scale, shift, i0=state, i_T=state)[0]
+
+
 def _check_packed(pack, dirs, recurrent, H):
     """What the `_pk` kernels do not take."""
     if pack is None:
@@ -1466,14 +1599,35 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
 
 
 # ----------------------------------------------------------------------------- layer Functions
+def _check_synapse_layer(cfg, gamma):
+    """What a layer with a synapse does not take, before any kernel."""
+    check_synapse(cfg["synapse"])
+    if gamma is None:
+        raise ValueError("sparch_amd: a layer with a synapse needs its parameter gamma")
+    if cfg.get("stateful"):
+        raise ValueError("sparch_amd: state / return_state with a synapse is not supported (the carried state has no "
+                         "synaptic current yet)")
+    if cfg["dirs"] == 2 and cfg.get("pack") is not None:
+        raise ValueError("sparch_amd: pack=True with bidirectional=True and a synapse is not supported")
+    if cfg["dirs"] == 2 and cfg.get("lengths") is None:
+        raise ValueError("sparch_amd: a bidirectional layer with a synapse runs on the doubled batch: it needs lengths "
+                         "(snns synthesises lengths = T)")
+
+
 class SpikingLayerFn(torch.autograd.Function):
     """x (B,T,K) -> (s (B,T,H*dirs), firing_rate (H*dirs)) for LIF / adLIF / RLIF / RadLIF."""
 
     @staticmethod
-    def forward(ctx, cfg, x, W, Wb, nw, nb, alpha, beta, a, b, V, u0, w0, s0):
+    def forward(ctx, cfg, x, W, Wb, nw, nb, alpha, beta, a, b, V, u0, w0, s0, gamma=None):
         _require_device(x, "input")
         _require_device(W, "layer parameters")
         kind, dirs, theta, p_drop, seed = cfg["kind"], cfg["dirs"], cfg["theta"], cfg["p_drop"], cfg["seed"]
+        # synaptic currents (DESIGN.md section 6): cfg["synapse"] = (lo, hi) puts the filter between the projection and
+        # the cell, which then reads the current i with no scale and no shift; absent: every call below is what it was
+        syn = cfg.get("synapse")
+        ctx.has_gamma = gamma is not None
+        if syn is not None:
+            _check_synapse_layer(cfg, gamma)
         inp = _layer_input(cfg, x)
         B, T, K = x.shape
         H = W.shape[0]
@@ -1492,11 +1646,22 @@ class SpikingLayerFn(torch.autograd.Function):
             # split (the projection and BatchNorm's statistics ran once, on B rows, as on the padded path), the
             # spikes are joined and counted per direction
             Wx2 = bidir_split(Wx_in.view(B, T, H), cfg)
+            if syn is not None:  # each direction filtered causally in its own time order
+                Wx2 = ctx.syn_i = synapse_forward(Wx2, gamma, syn, scale=scale, shift=shift, **_bidir_cell_kw(cfg))
+                scale = shift = None
             _, _, saved, s16_2 = cell_forward(kind, Wx2, scale, shift, p, u0, w0, s0, B=Wx2.shape[0], dirs=1, theta=theta,
                                               p_drop=p_drop, seed=seed, want_s_out=False,
                                               want_saves=any(ctx.needs_input_grad), surrogate=cfg.get("surrogate"),
                                               **_bidir_cell_kw(cfg))
             s_out, s16, count = bidir_join(s16_2, cfg, scale=inv_keep, want_fp32=cfg.get("fp32_out", True))
+        elif syn is not None:
+            i_syn = ctx.syn_i = synapse_forward(Wx_in.view(B, T, H), gamma, syn, scale=scale, shift=shift,
+                                                lengths=cfg.get("lengths"), pack=cfg.get("pack"))
+            s_out, count, saved, s16 = cell_forward(kind, i_syn, None, None, p, u0, w0, s0, B=B, dirs=1, theta=theta,
+                                                    p_drop=p_drop, seed=seed, want_s_out=cfg.get("fp32_out", True),
+                                                    want_saves=any(ctx.needs_input_grad),
+                                                    surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
+                                                    **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
         else:
             s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
                                                     dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
@@ -1513,7 +1678,7 @@ class SpikingLayerFn(torch.autograd.Function):
         ctx.nsaved = nsaved
         ctx.cell_saved = saved
         ctx.set_materialize_grads(False)  # no zero tensors for unused outputs (s16 is as large as s in bf16)
-        ctx.save_for_backward(inp.x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw)
+        ctx.save_for_backward(inp.x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw, *([gamma] if syn is not None else []))
         ctx.mark_non_differentiable(s16)
         if cfg.get("stateful"):
             # the final state: with fp32 saves the last saved step IS u_T / w_T, and s_T = 1[u_T > theta] is the raw
@@ -1531,7 +1696,7 @@ class SpikingLayerFn(torch.autograd.Function):
         cfg = ctx.cfg
         kind, norm, dirs = cfg["kind"], cfg["normalization"], cfg["dirs"]
         B, T, K, H = ctx.shape
-        x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw = ctx.saved_tensors
+        x2, W, nw, alpha, beta, a, b, V, u0, w0, s0, Wx_raw, *gamma = ctx.saved_tensors
         dev = x2.device
         if g_s is None:
             g_s = torch.zeros(B, T, H * dirs, dtype=torch.float32, device=dev)
@@ -1540,6 +1705,37 @@ class SpikingLayerFn(torch.autograd.Function):
             g_rate = _f32c(g_rate)
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
+        syn = cfg.get("synapse")
+        g_gamma = (None,) if ctx.has_gamma else ()  # (one more gradient exactly when gamma was passed)
+        if syn is not None:
+            # the cell's backward without the fused BatchNorm sums (they would be sums over i, not over the projection)
+            # and the filter's adjoint, which makes them instead, from g_z, where the cell's kernel would have (one
+            # direction, whole 4-column pieces), in that kernel's order: at gamma = 0 the layer's gradients are the
+            # bits of the layer without a synapse.  On the doubled batch _project_backward's own pass forms them.
+            two = _bidir_ragged(cfg)
+            if two:
+                n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]
+                g_s, g_rate = bidir_join_backward(g_s, g_rate, 1.0 / float(n_steps), cfg), None
+                lay = _bidir_cell_kw(cfg)
+            else:
+                lay = {"lengths": cfg.get("lengths"), **({} if cfg.get("pack") is None else {"pack": cfg["pack"]})}
+            g_i, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=g_s.shape[0], dirs=1,
+                                    T=g_s.shape[1], H=H, theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"],
+                                    bn=None, surrogate=cfg.get("surrogate"), **lay)
+            bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0 and not two) else None
+            g_z, g_gm, *sums = synapse_backward(g_i, ctx.syn_i, gamma[0], syn, need_ggamma=ctx.needs_input_grad[14],
+                                                bn=bn, **lay)
+            ctx.cell_saved = ctx.syn_i = None
+            if two:
+                g_z = bidir_split_backward(g_z, cfg)
+            dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, g_z, 1,
+                                                      need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
+                                                      sums=sums[0] if sums else None, w_planes=ctx.w_planes,
+                                                      dx_planes=True)
+            dx = None if dx is None else dx.view(B, T, K)
+            ctx.w_planes = ctx.inp = None
+            return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
+                    pg.get("V"), None, None, None, g_gm)
         if _bidir_ragged(cfg):
             # the forward's movements, reversed: the gather (with the rate's gradient, each direction's own count over
             # the valid steps), the one-direction cell backward on the doubled batch — without a rate gradient and
@@ -1558,7 +1754,7 @@ class SpikingLayerFn(torch.autograd.Function):
             dx = None if dx is None else dx.view(B, T, K)
             ctx.w_planes = ctx.inp = None
             return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
-                    pg.get("V"), None, None, None)
+                    pg.get("V"), None, None, None, *g_gamma)
         # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
         bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
         st_kw = {}
@@ -1577,7 +1773,8 @@ class SpikingLayerFn(torch.autograd.Function):
         g_u0, g_w0, g_s0 = pg.get("state", (None, None, None))
         need = ctx.needs_input_grad
         return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
-                pg.get("V"), g_u0 if need[11] else None, g_w0 if need[12] else None, g_s0 if need[13] else None)
+                pg.get("V"), g_u0 if need[11] else None, g_w0 if need[12] else None, g_s0 if need[13] else None,
+                *g_gamma)
 
 
 SEQ_MODES = {"prob": 0, "sum": 1}  # per-step readout: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM

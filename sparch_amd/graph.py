@@ -32,6 +32,8 @@ class GraphedTrainStep:
         front_end(x) -> features (e.g. the mel filterbank), captured with the step."""
         if not getattr(net, "is_snn", False):
             raise NotImplementedError("GraphedTrainStep: spiking networks (sparch_amd.SNN)")
+        if getattr(net, "synapse", None) is not None:  # (before anything is switched to graph mode or launched)
+            raise ValueError("sparch_amd: a synapse inside a captured step (GraphedTrainStep) is not supported")
         self.net, self.opt, self.loss_fn, self.reducer = net, optimizer, loss_fn, reducer
         self.extra_loss, self.front_end = extra_loss, front_end
         self.x, self.y = x.clone(), y.clone()

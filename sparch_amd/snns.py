@@ -165,6 +165,29 @@ def _refuse_stateful_delays(layer):
                          "input steps of a chunk are not carried into the next one)")
 
 
+SYN_INITS = ("uniform", "lo")
+SYN_LAYERS = ("all", "hidden")
+
+
+def _check_synapse_call(layer, pack=None, stateful=False):
+    """What a layer with a synapse (SNN(synapse=...)) refuses, before any kernel."""
+    if stateful:
+        raise ValueError("sparch_amd: state / return_state with a synapse is not supported (the carried state has no "
+                         "synaptic current yet)")
+    if pack is not None and layer.bidirectional:
+        raise ValueError("sparch_amd: pack=True with bidirectional=True and a synapse is not supported (the doubled "
+                         "packed batch has no filtered form)")
+    if layer.bidirectional and hasattr(layer, "V") and Fn.rec_step_path(layer.hidden_size):
+        # (the doubled batch runs the kernels with lengths, also where the caller passes none: their refusal, in the
+        # caller's terms and before the projection)
+        raise ValueError(f"sparch_amd: bidirectional=True with a synapse and a recurrent hidden size above 1024 (got "
+                         f"{layer.hidden_size}) is not supported (the layer runs on the doubled batch, which the "
+                         "per-step recurrent path does not take)")
+    if layer.bidirectional and Fn.SYNC_BN is not None and Fn.SYNC_BN["world"] > 1:
+        raise ValueError("sparch_amd: bidirectional=True with a synapse and --sync_bn is not supported (the layer runs "
+                         "on the ragged route, which --sync_bn does not take)")
+
+
 def _delayed_input(layer, x, lengths=None, pack=None):
     """x as a layer with axonal delays (SNN(max_delay=...)) reads it: every input feature shifted
     by its own delay, on the representation the layer's GEMMs read — the bf16 plane of a spike train of ours or of an
@@ -557,11 +580,19 @@ class _SpikingLayer(nn.Module):
             _refuse_stateful_delays(self)
             Fn.check_stateful(self.kind, self.hidden_size, dirs=2 if self.bidirectional else 1, lengths=lengths, pack=pack,
                               T=x.shape[1])
+        synapse = getattr(self, "synapse", None)  # (a module pickled before the attribute: none)
+        if synapse is not None:
+            _check_synapse_call(self, pack=pack, stateful=return_state)
         if lengths is not None:
             _check_ragged_layer(self, lengths)
         if pack is not None:
             _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
+        if synapse is not None and self.bidirectional and lengths is None and pack is None:
+            # each direction is filtered causally in its own time order: the layer takes the doubled-batch route of
+            # the ragged batches, with every row's length T, made on the device
+            lengths = (torch.full((x.shape[0],), x.shape[1], dtype=torch.int32, device=x.device), x.shape[0] * x.shape[1])
+            lengths2 = None
         x = _delayed_input(self, x, lengths, pack)  # (x itself without delays)
         dirs = 2 if self.bidirectional else 1
         rows = (x.shape[0] if pack is None else pack.batch) * dirs
@@ -603,12 +634,16 @@ class _SpikingLayer(nn.Module):
             cfg["lengths2"] = lengths2 if lengths2 is not None else double_lengths(lengths)
         if return_state:
             cfg["stateful"] = True
+        syn_args = ()
+        if synapse is not None:  # (absent without a synapse, and gamma not passed: the call is then what it always was)
+            cfg["synapse"] = synapse
+            syn_args = (self.gamma,)
         nw = self.norm.weight if self.normalize else None
         nb = self.norm.bias if self.normalize else None
         s, rate, s16, *final = Fn.SpikingLayerFn.apply(
             cfg, x, self.W.weight, self.W.bias, nw, nb, self.alpha,
             getattr(self, "beta", None), getattr(self, "a", None), getattr(self, "b", None),
-            self.V.weight if hasattr(self, "V") else None, u0, w0, s0)
+            self.V.weight if hasattr(self, "V") else None, u0, w0, s0, *syn_args)
         # lets the next layer take the exact bf16-split GEMMs and read the spikes as a bf16 plane (half the bytes)
         _tag_spikes(s, 1.0 / (1.0 - p_drop), s16, placeholder=not fp32_out and not s.is_contiguous())
         if return_state:
@@ -954,8 +989,15 @@ class SNN(nn.Module):
     def __init__(self, input_shape, layer_sizes, neuron_type="LIF", threshold=1.0, dropout=0.0,
                  normalization="batchnorm", use_bias=False, bidirectional=False, use_readout_layer=True,
                  surrogate="boxcar", surrogate_scale=None, readout="softmax_sum", max_delay=0, delay_init="zero",
-                 learn_delays=True, delay_layers="all"):
+                 learn_delays=True, delay_layers="all", synapse=None, syn_init="uniform", learn_synapse=True,
+                 synapse_layers="all"):
         super().__init__()
+        self.synapse = Fn.check_synapse(synapse)
+        if syn_init not in SYN_INITS:
+            raise ValueError(f"sparch_amd: syn_init must be one of {', '.join(SYN_INITS)} (got {syn_init!r})")
+        if synapse_layers not in SYN_LAYERS:
+            raise ValueError(f"sparch_amd: synapse_layers must be one of {', '.join(SYN_LAYERS)} (got {synapse_layers!r})")
+        self.syn_init, self.synapse_layers, self.learn_synapse = syn_init, synapse_layers, bool(learn_synapse)
         Fn.readout_mode(readout)
         Fn.check_max_delay(max_delay, zero_ok=True)
         if delay_init not in DELAY_INITS:
@@ -986,6 +1028,31 @@ class SNN(nn.Module):
 
         self.snn = self._init_layers()
         self._init_delays()
+        self._init_synapses()
+
+    def _init_synapses(self):
+        """Synaptic currents: every hidden spiking layer — with synapse_layers="hidden" every one
+        but the first — gets `synapse` = (lo, hi) and an nn.Parameter `gamma`, one entry per neuron, U(lo, hi) or lo.
+        Made after the whole network (and its delays), so that under one seed every other parameter is what it is
+        without a synapse; synapse=None registers nothing (the state_dict keys are the reference's).  The readout layer
+        never has one."""
+        if self.synapse is None:
+            return
+        lo, hi = self.synapse
+        n_hidden = self.num_layers - 1 if self.use_readout_layer else self.num_layers
+        for i, layer in enumerate(self.snn[:n_hidden]):
+            if i == 0 and self.synapse_layers == "hidden":
+                continue
+            layer.synapse = (lo, hi)
+            init = torch.full((layer.hidden_size,), lo)
+            if self.syn_init == "uniform":
+                init.uniform_(lo, hi)
+            layer.gamma = nn.Parameter(init, requires_grad=self.learn_synapse)
+
+    def synapse_gammas(self):
+        """{layer index: the clamped gamma (H,) as the kernels take it} of the layers with a synapse — for logging."""
+        return {i: layer.gamma.detach().float().clamp(*layer.synapse)
+                for i, layer in enumerate(self.snn) if getattr(layer, "synapse", None) is not None}
 
     def _init_delays(self):
         """Axonal delays: every delayed layer gets `max_delay` and an nn.Parameter `delay`, one
@@ -1039,6 +1106,9 @@ class SNN(nn.Module):
         if getattr(self, "max_delay", 0):
             parts.append(f"max_delay={self.max_delay}, delay_init={self.delay_init}, learn_delays={self.learn_delays}, "
                          f"delay_layers={self.delay_layers}")
+        if getattr(self, "synapse", None) is not None:
+            parts.append(f"synapse=({self.synapse[0]:g}, {self.synapse[1]:g}), syn_init={self.syn_init}, "
+                         f"learn_synapse={self.learn_synapse}, synapse_layers={self.synapse_layers}")
         return ", ".join(parts)
 
     def draw_states(self, batch, device, out=None):
@@ -1155,6 +1225,12 @@ class SNN(nn.Module):
         the chunk boundary exactly; through detach_state() it is classic truncated BPTT.  A `state` tensor with
         requires_grad gets its gradient.  state=None draws as always; return_state=False returns what it always did."""
         stateful = state is not None or return_state
+        if getattr(self, "synapse", None) is not None:  # (the refusals come before anything else)
+            if getattr(self, "_static_states", None) is not None:
+                raise ValueError("sparch_amd: a synapse inside a captured step (GraphedTrainStep) is not supported")
+            for layer in self.snn:
+                if getattr(layer, "synapse", None) is not None:
+                    _check_synapse_call(layer, pack=True if pack else None, stateful=stateful)
         if stateful:  # (the refusals come before anything else)
             self._check_stateful(lengths, pack, per_step, x.shape[1])
             if state is not None:

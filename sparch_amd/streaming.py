@@ -207,6 +207,14 @@ class StreamingSNN(_Stream):
         if self._has_delays and graph:
             raise ValueError("StreamingSNN: graph=True does not take a network with axonal delays (the captured chunk "
                              "step covers networks without them only); use graph=False")
+        # synaptic currents (SNN(synapse=...)): the chunk path carries the current i (B,H) per layer; the same refusals
+        self._has_synapse = any(getattr(mod, "synapse", None) is not None for mod in net.snn)
+        if self._has_synapse and (fused or sparse):
+            raise ValueError("StreamingSNN: fused=True / sparse=True do not take a network with synaptic currents (the "
+                             "one-launch step has no filtered input); use fused=False")
+        if self._has_synapse and graph:
+            raise ValueError("StreamingSNN: graph=True does not take a network with synaptic currents (the captured chunk "
+                             "step covers networks without them only); use graph=False")
         self.fused = bool(fused)
         self.sparse = bool(sparse)
         self._fused_active = self.fused and Fn._prec() == 0
@@ -260,6 +268,14 @@ class StreamingSNN(_Stream):
                 L.D = int(getattr(mod, "max_delay", 0))
                 L.delay = Fn._f32c(mod.delay.detach()) if L.D else None
                 L.hist = None
+                # synaptic currents: the limits, the parameter and the folded BatchNorm affine, which the filter applies
+                # (the cell then reads the current with no scale and no shift); the carried current is L.i (B,H)
+                L.syn = getattr(mod, "synapse", None)
+                L.gamma = Fn._f32c(mod.gamma.detach()) if L.syn is not None else None
+                L.syn_scale, L.syn_shift = (L.scale, L.shift) if L.syn is not None else (None, None)
+                if L.syn is not None:
+                    L.scale = L.shift = None
+                L.i = None
                 # readout: the reduction over time; the mean modes carry the un-normalised accumulator in `out` and the
                 # rows' step counts in `steps`, u_max the running maximum (from -inf)
                 L.red = Fn.readout_mode(self._readout_name(net)) if L.readout else 0
@@ -289,8 +305,10 @@ class StreamingSNN(_Stream):
                 # state buffers: kept across refresh()
                 if old is not None:
                     for k in ("u", "w", "s", "s16", "count", "out", "steps", "binary", "s_alt", "s16_alt", "s_first",
-                              "hist"):
+                              "hist", "i"):
                         setattr(L, k, getattr(old[i], k, None))
+                    if L.syn is not None and L.i is None:
+                        L.i = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
                 elif L.readout:
                     L.u = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
                     L.out = torch.full((B, L.H), L.out_init, dtype=torch.float32, device=dev)
@@ -303,6 +321,8 @@ class StreamingSNN(_Stream):
                     L.count = torch.zeros(L.Hs, dtype=torch.int32, device=dev)
                     L.binary = False  # s holds 0/1 only AND s16 mirrors it (true behind every chunk step)
                     L.s_alt = L.s16_alt = L.s_first = None
+                    if L.syn is not None:
+                        L.i = torch.zeros(B, L.H, dtype=torch.float32, device=dev)
                 if self.fused and L.recurrent and L.s_alt is None:
                     # the other copy of the spike state: a fused step reads s / writes s_alt, then the host swaps the
                     # names (its padded columns are never written: they stay zero like those of s)
@@ -358,6 +378,9 @@ class StreamingSNN(_Stream):
                     dst.copy_(hist)
                 else:
                     dst.index_copy_(0, idx, hist.to(dst.dtype))
+            cur = st.get("i") if isinstance(st, dict) else None
+            if L.syn is not None and cur is not None:
+                self._put(L.i, cur, "i", idx, L.H)
             if L.readout:
                 if out is not None:
                     self._put(L.out, out, "out", idx)
@@ -395,6 +418,11 @@ class StreamingSNN(_Stream):
                     L.hist.zero_()
                 else:
                     L.hist.index_fill_(0, self._rows(rows), 0)
+            if L.i is not None:  # the synaptic current: none yet (an `i` entry of `states` replaces it)
+                if rows is None:
+                    L.i.zero_()
+                else:
+                    L.i.index_fill_(0, self._rows(rows), 0)
         self._load(states, rows)
         ro = self._layers[-1] if self._layers[-1].readout else None
         if rows is None:
@@ -430,6 +458,8 @@ class StreamingSNN(_Stream):
                 res.append(d)
             if L.D:
                 res[-1]["hist"] = self._hist(L, None).clone()
+            if L.syn is not None:
+                res[-1]["i"] = L.i.clone()
         return res
 
     def firing_rates(self):
@@ -552,6 +582,9 @@ class StreamingSNN(_Stream):
                 check(lib.sparch_readout_stream_fwd(B, Tc, L.H, ptr(Wx), ptr(L.scale), ptr(L.shift), ptr(L.p["alpha"]),
                                                     ptr(L.u), ptr(L.out), Fn._stream()), "sparch_readout_stream_fwd")
                 return L.out, taps
+            if L.syn is not None:  # the synaptic current, carried in L.i and advanced by the chunk's steps
+                Wx = Fn.synapse_stream(Wx.view(B, Tc, L.H), L.gamma, L.syn, L.i, scale=L.syn_scale,
+                                       shift=L.syn_shift).view(B * Tc, L.H)
             s, s16 = self._cell(L, Wx, Tc, want_fp32=(i + 1 == len(layers)))
             taps.append(s16)
         return s, taps
