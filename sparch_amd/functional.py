@@ -666,22 +666,17 @@ def _layer_input(cfg, x, gated=True):
     return _LayerInput(x2, None, None, flag_bf16_exact(x2))
 
 
-def _n_valid(cfg):
-    """The ragged batch's number of valid rows (cfg["lengths"] = (device int32 (B,), their sum)), or None."""
-    lengths = cfg.get("lengths")
-    return None if lengths is None else lengths[1]
-
-
-def _project(inp, W, Wb, nw, nb, cfg, dup, ln_width=None):
+def _project(inp, W, Wb, nw, nb, cfg, dup, ln_width=None, n_valid=None):
     """norm(x W^T + Wb) of a layer -> (Wx_in, scale, shift, nsaved, Wx_raw): what the cell reads (BatchNorm stays
     folded into scale / shift), what _Norm.backward needs, and the raw projection where backward needs it (else
-    None).  dup: how many directions share the rows (BatchNorm's sample count)."""
+    None).  dup: how many directions share the rows (BatchNorm's sample count); n_valid: the rows that count in it
+    (SeqLayout.n_valid; None: all)."""
     norm, training = cfg["normalization"], cfg["training"]
     Wx_raw, colstat = inp.project(W, Wb, colstat=(norm == "batchnorm" and training))
     Wx_in, scale, shift, nsaved = _Norm.forward(norm, Wx_raw, colstat, nw, nb, cfg.get("running_mean"),
                                                 cfg.get("running_var"), training, dup,
                                                 nbt=cfg.get("num_batches_tracked"), ln_width=ln_width,
-                                                n_valid=_n_valid(cfg))
+                                                n_valid=n_valid)
     return Wx_in, scale, shift, nsaved, Wx_raw if norm in ("batchnorm", "layernorm") else None
 
 
@@ -695,12 +690,12 @@ def _use_dx_planes(inp, norm, dirs, M, K, H):
 
 
 def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, need_bias, sums=None, ln_width=None,
-                      w_planes=None, dx_planes=False, raw_dx=False):
+                      w_planes=None, dx_planes=False, raw_dx=False, n_valid=None):
     """Backward of _project.  dy: the gradient of the normalised projection, (M,H) or the (B*dirs,T,H) halves of
     `dirs` directions that share the projection rows (snns.py:252-254); may be overwritten.  sums: BatchNorm's column
     sums where the cell's backward kernel made them.  w_planes: split_planes(W) for the dx product.  dx_planes: the
-    layer may take the plane kernels (_use_dx_planes decides).  Returns (dx (M,K) or None, dW, dWb or None, dnw, dnb);
-    raw_dx: the first entry is dx_raw (M,H) instead — the caller forms dx itself."""
+    layer may take the plane kernels (_use_dx_planes decides).  n_valid: as _project's.  Returns (dx (M,K) or None, dW,
+    dWb or None, dnw, dnb); raw_dx: the first entry is dx_raw (M,H) instead — the caller forms dx itself."""
     norm = cfg["normalization"]
     H, K = W.shape
     M = dy.numel() // (H * dirs)
@@ -709,7 +704,7 @@ def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, n
         B = dy.shape[0] // dirs
         dy2 = dy[B:].view(M, H) if dirs == 2 else None  # second direction: added by the same pass
         dx_raw, dnw, dnb, dxp = _Norm.backward(norm, dy[:B].view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
-                                               planes=True, dy2=dy2, keep_fp32=need_bias, n_valid=_n_valid(cfg))
+                                               planes=True, dy2=dy2, keep_fp32=need_bias, n_valid=n_valid)
         nbytes = lib.sparch_gemm_spike_tn_workspace_bytes(H, K, M, _prec())
         ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=W.device)
         dW = torch.empty(H, K, dtype=torch.float32, device=W.device)
@@ -723,7 +718,7 @@ def _project_backward(inp, W, nw, cfg, nsaved, Wx_raw, dy, dirs=1, *, need_dx, n
             halves, dy = dy, torch.empty(dy.shape[0] // 2, dy.shape[1], H, dtype=torch.float32, device=W.device)
             check(lib.sparch_add_halves(M * H, ptr(halves), ptr(dy), _stream()), "sparch_add_halves")
         dx_raw, dnw, dnb = _Norm.backward(norm, dy.view(M, H), Wx_raw, nw, nsaved, cfg["training"], sums=sums,
-                                          ln_width=ln_width, n_valid=_n_valid(cfg))
+                                          ln_width=ln_width, n_valid=n_valid)
         dW = inp.weight_grad(dx_raw)
     dWb = _colsum(dx_raw) if need_bias else None
     if raw_dx:
@@ -806,6 +801,98 @@ class PackPlan(typing.NamedTuple):
     def args(self):
         """(lengths, offsets, n_valid) as the `_pk` entry points take them."""
         return ptr(self.lengths), ptr(self.offsets), int(self.n)
+
+
+class SeqLayout(typing.NamedTuple):
+    """How the time axis of a batch lies in memory, and the only place that knows how the three layouts differ:
+    dense (B,T,.) tensors, the same with `lengths` = (device int32 (B,), their sum) masking every row's padded steps
+    (the `_len` entry points), or `pack`, a PackPlan: (1,n,.) tensors of the valid steps only (the `_pk` ones).  Built
+    once per layer pass (of_cfg) or per call of a public wrapper (its lengths= / pack= keywords).  For a bidirectional
+    layer on a ragged batch `doubled` is the layout of its 2B sequences — every clip and, behind the batch, the clip
+    read backwards — and fwd / rev say where the two copies of a packed sequence start there (BidirPlan)."""
+    lengths: typing.Optional[tuple] = None
+    pack: typing.Optional[PackPlan] = None
+    doubled: typing.Optional["SeqLayout"] = None
+    fwd: typing.Optional[torch.Tensor] = None
+    rev: typing.Optional[torch.Tensor] = None
+
+    @classmethod
+    def of(cls, lengths=None, pack=None):
+        """The layout of the lengths= / pack= keywords of the public wrappers (a dense batch: one shared record)."""
+        return _DENSE if lengths is None and pack is None else cls(lengths, pack)
+
+    @classmethod
+    def of_cfg(cls, cfg):
+        """The layout a layer Function's cfg describes: cfg["lengths"] or cfg["pack"], and for dirs == 2 the doubled
+        batch's cfg["lengths2"] (snns.double_lengths) or cfg["pack2"] (a BidirPlan).  The bidir_* movers alone also
+        take a cfg without dirs."""
+        lengths, pack, two = cfg.get("lengths"), cfg.get("pack"), cfg.get("dirs") == 2
+        if lengths is None and pack is None:
+            return _DENSE
+        if pack is not None:
+            plan2 = cfg["pack2"] if two else cfg.get("pack2")
+            return cls(None, pack) if plan2 is None else cls(None, pack, cls(None, plan2.plan), plan2.fwd, plan2.rev)
+        return cls(lengths, None, cls(cfg["lengths2"]) if two and lengths is not None else None)
+
+    @property
+    def suffix(self):
+        """What the layout appends to an entry point's name."""
+        return "_pk" if self.pack is not None else "" if self.lengths is None else "_len"
+
+    def index(self, B, T):
+        """The kernels' (sequences, steps) for tensors whose leading shape is (B, T)."""
+        return (B, T) if self.pack is None else (self.pack.batch, self.pack.t_max)
+
+    @property
+    def ragged_steps(self):
+        """The steps that exist in a ragged batch; 0 for a dense one (what the `_red` entries take)."""
+        return int(self.pack.n) if self.pack is not None else 0 if self.lengths is None else int(self.lengths[1])
+
+    def n_valid(self, B, T):
+        """The steps that exist in tensors of leading shape (B, T): the firing rate's and BatchNorm's denominator."""
+        return self.ragged_steps or B * T
+
+    @property
+    def tail(self):
+        """The arguments the cell and readout entries take for the layout: (), (lengths, n_valid) or (lengths,
+        offsets, n_valid)."""
+        if self.pack is not None:
+            return self.pack.args()
+        return () if self.lengths is None else (ptr(self.lengths[0]), int(self.lengths[1]))
+
+    @property
+    def ptrs(self):
+        """(lengths, offsets) as the entries with one form for all layouts take them (delay, synapse, `_red`): NULL for
+        what the layout does not have."""
+        if self.pack is not None:
+            return ptr(self.pack.lengths), ptr(self.pack.offsets)
+        return (None if self.lengths is None else ptr(self.lengths[0])), None
+
+    def space(self, B, T):
+        """(sequences, steps, lengths, offsets): the index space of the delay and synapse kernels for (B,T,.) tensors —
+        packed ones are (1,n,.), and the shift or the filter stays inside each sequence's rows."""
+        if self.pack is not None and (B, T) != (1, self.pack.n):
+            raise ValueError(f"sparch_amd: a packed delay input must be (1, {self.pack.n}, K), got ({B}, {T}, K)")
+        return (*self.index(B, T), *self.ptrs)
+
+    @property
+    def map_tail(self):
+        """The arguments behind the tensors of the sparch_bidir_* entries."""
+        return self.tail if self.pack is None else (*self.ptrs, ptr(self.fwd), ptr(self.rev), int(self.pack.n))
+
+    def scaled(self, B, T, num, den=1):
+        """The leading shape of a tensor with num / den times the sequences of one whose leading shape is (B, T)."""
+        return (1, T * num // den) if self.pack is not None else (B * num // den, T)
+
+    def first_steps(self, t, rows, flipped=False):
+        """t (B',T,H), or packed (1,n,H) -> (rows,H): the first step of the sequences `rows` (a slice; packed: of all
+        of them), which for a dense direction that runs backwards in time (flipped) is the last."""
+        if self.pack is not None:
+            return t.view(-1, t.shape[-1]).index_select(0, self.pack.offsets[:self.pack.batch])
+        return t[rows, t.shape[1] - 1 if flipped else 0, :]
+
+
+_DENSE = SeqLayout()
 
 
 def _pack_call(entry, src, dst, plan, C):
@@ -904,16 +991,6 @@ def _check_delays(delay, K, device, what):
     return delay
 
 
-def _delay_layout(B, T, lengths, pack):
-    """The kernels' index space: (sequences, steps, lengths pointer, offsets pointer).  lengths: prepare_lengths()'s
-    pair; pack: a PackPlan — the tensors are then (1, n, K) and the shift stays inside each sequence's rows."""
-    if pack is not None:
-        if B != 1 or T != pack.n:
-            raise ValueError(f"sparch_amd: a packed delay input must be (1, {pack.n}, K), got ({B}, {T}, K)")
-        return pack.batch, pack.t_max, ptr(pack.lengths), ptr(pack.offsets)
-    return B, T, (None if lengths is None else ptr(lengths[0])), None
-
-
 def delay_forward(x, delay, max_delay, lengths=None, pack=None, out=None):
     """y[b,t,i] = x[b, t - d_i, i] for d_i <= t < len_b, else 0, with d_i = rint(clamp(delay_i, 0, max_delay)) taken on
     the device (`sparch_delay_fwd`).  x (B,T,K): any 2- or 4-byte dtype (the bf16 spike plane, fp32), moved as raw
@@ -929,7 +1006,7 @@ def delay_forward(x, delay, max_delay, lengths=None, pack=None, out=None):
     y_rows, ldy = _delay_rows(y, "delay_forward")
     if y_rows is not y:
         raise ValueError("delay_forward: out must have unit stride along K and one row stride")
-    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    Bk, Tk, len_ptr, off_ptr = SeqLayout.of(lengths, pack).space(B, T)
     tok = timer.start("delay_fwd")
     check(lib.sparch_delay_fwd(Bk, Tk, K, x.element_size(), D, ptr(delay), ptr(x), ldx, ptr(y), ldy, len_ptr, off_ptr,
                                _stream()), "sparch_delay_fwd")
@@ -947,7 +1024,7 @@ def delay_backward(g_y, delay, max_delay, x=None, x_scale=1.0, lengths=None, pac
     g_y, ldg = _delay_rows(_f32c(g_y), "delay_backward")
     B, T, K = g_y.shape
     delay = _check_delays(delay, K, g_y.device, "delay_backward")
-    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    Bk, Tk, len_ptr, off_ptr = SeqLayout.of(lengths, pack).space(B, T)
     g_x = torch.empty(B, T, K, dtype=torch.float32, device=g_y.device) if need_gx else None
     g_delay = ws = None
     nbytes, esize, ldx = 0, 4, K
@@ -1003,7 +1080,8 @@ class DelayFn(torch.autograd.Function):
         _require_device(x, "input")
         _require_device(delay, "delay")
         B, T, K = x.shape
-        D, plane, lengths, pack = cfg["max_delay"], cfg.get("plane"), cfg.get("lengths"), cfg.get("pack")
+        D, plane, lay = cfg["max_delay"], cfg.get("plane"), SeqLayout.of_cfg(cfg)
+        lengths, pack = lay.lengths, lay.pack
         if plane is None:
             src = x if x.element_size() in (2, 4) else x.float()
             src = src.contiguous() if src.stride(2) != 1 else src
@@ -1014,7 +1092,7 @@ class DelayFn(torch.autograd.Function):
             delay_forward(plane, delay, D, lengths, pack, out=store.view(B, T, ld)[:, :, :K])
             src, y, y16 = plane, spike_placeholder(B, T, K, x.device), store
             ctx.mark_non_differentiable(y16)
-        ctx.cfg = cfg
+        ctx.cfg, ctx.lay = cfg, lay
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(delay, src if ctx.needs_input_grad[1] else None)
         return y, y16
@@ -1026,7 +1104,7 @@ class DelayFn(torch.autograd.Function):
         cfg = ctx.cfg
         delay, src = ctx.saved_tensors
         g_x, g_delay = delay_backward(g_y, delay, cfg["max_delay"], src, float(cfg.get("scale") or 1.0),
-                                      cfg.get("lengths"), cfg.get("pack"), need_gx=ctx.needs_input_grad[0],
+                                      ctx.lay.lengths, ctx.lay.pack, need_gx=ctx.needs_input_grad[0],
                                       need_gdelay=ctx.needs_input_grad[1])
         return g_x, g_delay, None
 
@@ -1095,7 +1173,7 @@ def synapse_forward(Wx, gamma, limits, bias=None, scale=None, shift=None, i0=Non
     Wx, ldwx = _delay_rows(Wx if Wx.dtype == torch.float32 else Wx.float(), "synapse_forward")
     B, T, H = Wx.shape
     dev = Wx.device
-    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    Bk, Tk, len_ptr, off_ptr = SeqLayout.of(lengths, pack).space(B, T)
     gamma = _synapse_cols(gamma, H, dev, "synapse_forward", "gamma")
     bias, scale, shift = (_synapse_cols(t, H, dev, "synapse_forward", n)
                           for t, n in ((bias, "bias"), (scale, "scale"), (shift, "shift")))
@@ -1126,7 +1204,7 @@ def synapse_backward(g_i, i, gamma, limits, i0=None, lengths=None, pack=None, ne
     g_i, ldg = _delay_rows(g_i if g_i.dtype == torch.float32 else g_i.float(), "synapse_backward")
     B, T, H = g_i.shape
     dev = g_i.device
-    Bk, Tk, len_ptr, off_ptr = _delay_layout(B, T, lengths, pack)
+    Bk, Tk, len_ptr, off_ptr = SeqLayout.of(lengths, pack).space(B, T)
     gamma = _synapse_cols(gamma, H, dev, "synapse_backward", "gamma")
     i0 = _synapse_state(i0, Bk, H, dev, "synapse_backward", "i0")
     g_z, ldgz = _synapse_out(out, B, T, H, dev, "synapse_backward") if need_gz else (None, H)
@@ -1208,62 +1286,34 @@ class BidirPlan(typing.NamedTuple):
     rev: torch.Tensor
 
 
-def _bidir_map(cfg):
-    """(entry suffix, B, T, the map arguments behind the tensors) of the sparch_bidir_* calls under cfg: the `_len` form
-    for cfg["lengths"], the `_pk` form for cfg["pack"] with cfg["pack2"] (a BidirPlan)."""
-    pack = cfg.get("pack")
-    if pack is not None:
-        two = cfg["pack2"]
-        return "_pk", pack.batch, pack.t_max, (ptr(pack.lengths), ptr(pack.offsets), ptr(two.fwd), ptr(two.rev), int(pack.n))
-    lengths = cfg["lengths"]
-    return "_len", lengths[0].shape[0], None, (ptr(lengths[0]), int(lengths[1]))
-
-
-def _bidir_ragged(cfg):
-    """True for a bidirectional layer with lengths or pack: the layer runs on the doubled batch."""
-    return cfg["dirs"] == 2 and (cfg.get("lengths") is not None or cfg.get("pack") is not None)
-
-
-def _bidir_cell_kw(cfg):
-    """What the one-direction cell calls on the doubled batch take: the lengths twice (cfg["lengths2"] = (device int32
-    (2B,), 2 sum(L))), or the doubled batch's PackPlan."""
-    if cfg.get("pack") is not None:
-        return {"pack": cfg["pack2"].plan}
-    return {"lengths": cfg["lengths2"]}
-
-
-def _bidir_shape(x, pk, double):
-    """The doubled (or, double=False, the single) tensor's leading shape for x (B,T,.) / packed (1,n,.)."""
-    B, T = x.shape[0], x.shape[1]
-    if double:
-        return (1, 2 * T) if pk else (2 * B, T)
-    return (1, T // 2) if pk else (B // 2, T)
+def _bidir_call(stem, lay, single, *args):
+    """One sparch_bidir_* mover under its timer label: `stem` + the layout's suffix, on the kernels' index space of the
+    single tensor (leading shape `single`), `args` between that and the layout's map arguments."""
+    entry = stem + lay.suffix
+    tok = timer.start(stem[len("sparch_"):])
+    check(getattr(lib, entry)(*lay.index(*single), *args, *lay.map_tail, _stream()), entry)
+    timer.stop(tok)
 
 
 def bidir_split(x, cfg):
     """x (B,T,C), or packed (1,n,C), elements of 1, 2 or 4 bytes -> (2B,T,C) / (1,2n,C): the batch and, behind it, every
-    clip read backwards inside its own length; zeros on the tails."""
-    sfx, B, T, tail = _bidir_map(cfg)
+    clip read backwards inside its own length; zeros on the tails.  cfg: a layer's cfg, or its SeqLayout."""
+    lay = cfg if isinstance(cfg, SeqLayout) else SeqLayout.of_cfg(cfg)
     x = x.contiguous()
     C = x.shape[2]
-    out = torch.empty(*_bidir_shape(x, sfx == "_pk", True), C, dtype=x.dtype, device=x.device)
-    tok = timer.start("bidir_split")
-    check(getattr(lib, "sparch_bidir_split" + sfx)(B, T if T is not None else x.shape[1], C, x.element_size(), ptr(x),
-                                                   ptr(out), *tail, _stream()), "sparch_bidir_split" + sfx)
-    timer.stop(tok)
+    out = torch.empty(*lay.scaled(*x.shape[:2], 2), C, dtype=x.dtype, device=x.device)
+    _bidir_call("sparch_bidir_split", lay, x.shape[:2], C, x.element_size(), ptr(x), ptr(out))
     return out
 
 
 def bidir_split_backward(g, cfg):
     """The adjoint of bidir_split on fp32: g (2B,T,C) / (1,2n,C) -> (B,T,C) / (1,n,C), exactly 0 on the tails."""
-    sfx, B, T, tail = _bidir_map(cfg)
+    lay = cfg if isinstance(cfg, SeqLayout) else SeqLayout.of_cfg(cfg)
     g = _f32c(g)
     C = g.shape[2]
-    out = torch.empty(*_bidir_shape(g, sfx == "_pk", False), C, dtype=torch.float32, device=g.device)
-    tok = timer.start("bidir_split_bwd")
-    check(getattr(lib, "sparch_bidir_split_bwd" + sfx)(B, T if T is not None else g.shape[1], C, ptr(g), ptr(out), *tail,
-                                                       _stream()), "sparch_bidir_split_bwd" + sfx)
-    timer.stop(tok)
+    single = lay.scaled(*g.shape[:2], 1, 2)
+    out = torch.empty(*single, C, dtype=torch.float32, device=g.device)
+    _bidir_call("sparch_bidir_split_bwd", lay, single, C, ptr(g), ptr(out))
     return out
 
 
@@ -1271,31 +1321,24 @@ def bidir_join(s16, cfg, scale=1.0, want_fp32=True):
     """s16 (2B,T,H) / (1,2n,H), the bf16 0/1 plane of the doubled batch -> (s (B,T,2H) fp32 = plane * scale or None,
     the plane (B,T,2H), count (2H,) int32 of the spikes per output column): forward columns first, the reverse
     direction back in the clip's own time order, zeros on the tails."""
-    sfx, B, T, tail = _bidir_map(cfg)
+    lay = cfg if isinstance(cfg, SeqLayout) else SeqLayout.of_cfg(cfg)
     H = s16.shape[2]
-    lead = _bidir_shape(s16, sfx == "_pk", False)
-    y16 = torch.empty(*lead, 2 * H, dtype=torch.bfloat16, device=s16.device)
-    y32 = torch.empty(*lead, 2 * H, dtype=torch.float32, device=s16.device) if want_fp32 else None
+    single = lay.scaled(*s16.shape[:2], 1, 2)
+    y16 = torch.empty(*single, 2 * H, dtype=torch.bfloat16, device=s16.device)
+    y32 = torch.empty(*single, 2 * H, dtype=torch.float32, device=s16.device) if want_fp32 else None
     count = torch.zeros(2 * H, dtype=torch.int32, device=s16.device)
-    tok = timer.start("bidir_join")
-    check(getattr(lib, "sparch_bidir_join" + sfx)(B, T if T is not None else s16.shape[1], H, ptr(s16), ptr(y16), ptr(y32),
-                                                  float(scale), ptr(count), *tail, _stream()), "sparch_bidir_join" + sfx)
-    timer.stop(tok)
+    _bidir_call("sparch_bidir_join", lay, single, H, ptr(s16), ptr(y16), ptr(y32), float(scale), ptr(count))
     return y32, y16, count
 
 
 def bidir_join_backward(g, g_rate, rate_scale, cfg):
     """The adjoint of bidir_join: g (B,T,2H) / (1,n,2H) fp32 -> (2B,T,H) / (1,2n,H), with g_rate[column] * rate_scale (the
     firing rate's gradient; g_rate None: nothing) added on the valid steps and exactly 0 on the tails."""
-    sfx, B, T, tail = _bidir_map(cfg)
+    lay = cfg if isinstance(cfg, SeqLayout) else SeqLayout.of_cfg(cfg)
     g = _f32c(g)
     H = g.shape[2] // 2
-    out = torch.empty(*_bidir_shape(g, sfx == "_pk", True), H, dtype=torch.float32, device=g.device)
-    tok = timer.start("bidir_join_bwd")
-    check(getattr(lib, "sparch_bidir_join_bwd" + sfx)(B, T if T is not None else g.shape[1], H, ptr(g), ptr(g_rate),
-                                                      float(rate_scale), ptr(out), *tail, _stream()),
-          "sparch_bidir_join_bwd" + sfx)
-    timer.stop(tok)
+    out = torch.empty(*lay.scaled(*g.shape[:2], 2), H, dtype=torch.float32, device=g.device)
+    _bidir_call("sparch_bidir_join_bwd", lay, g.shape[:2], H, ptr(g), ptr(g_rate), float(rate_scale), ptr(out))
     return out
 
 
@@ -1333,6 +1376,34 @@ def check_stateful(kind=None, H=0, *, dirs=1, lengths=None, pack=None, per_step=
                              "sequences only)")
 
 
+class _ColPad:
+    """The zero-padding of a recurrent width H to the next multiple of 4, H4 (cell_forward says why): pad / cut work on
+    the last axis, which holds `groups` blocks of H (H4) columns; None stays None."""
+
+    def __init__(self, H):
+        self.H, self.H4 = H, (H + 3) // 4 * 4
+
+    def pad(self, t, groups=1):
+        if t is None:
+            return None
+        lead = t.shape[:-1]
+        return torch.nn.functional.pad(t.reshape(*lead, groups, self.H), (0, self.H4 - self.H)).reshape(*lead, groups * self.H4)
+
+    def cut(self, t, groups=1):
+        if t is None:
+            return None
+        lead = t.shape[:-1]
+        return t.reshape(*lead, groups, self.H4)[..., :self.H].reshape(*lead, groups * self.H).contiguous()
+
+    def pad_params(self, p):
+        """The cell's parameters: V (H,H) grows on both axes."""
+        d = self.H4 - self.H
+        return {n: (torch.nn.functional.pad(v, (0, d, 0, d)) if n == "V" else self.pad(v)) for n, v in p.items()}
+
+    def cut_params(self, grads):
+        return {n: (v[:self.H, :self.H].contiguous() if n == "V" else self.cut(v)) for n, v in grads.items()}
+
+
 def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_drop, seed, steps_per_launch=None,
                  want_s_out=True, want_saves=True, surrogate=None, lengths=None, pack=None):
     """Run one spiking cell over the whole sequence on the device.
@@ -1355,17 +1426,27 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     dev = Wx.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    lay = SeqLayout.of(lengths, pack)
     _check_one_direction(dirs, lengths, pack)
     _check_ragged(lengths, dirs, recurrent, H)
     _check_packed(pack, dirs, recurrent, H)
-    len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
+    if recurrent and H % 4 != 0:
+        # The recurrent kernels own 4 columns per thread.  Any other width (the reference takes any nb_hiddens,
+        # snns.py:608-661) runs zero-padded to the next multiple of 4: a padded neuron has no input, no
+        # recurrent weights and u0 = 0, so it never spikes and feeds nothing; outputs are sliced back.
+        cols = _ColPad(H)
+        s_p, count_p, saved_p, s16_p = cell_forward(kind, cols.pad(Wx), cols.pad(scale), cols.pad(shift), cols.pad_params(p),
+                                                    cols.pad(u0), cols.pad(w0), cols.pad(s0), B=B, dirs=dirs, theta=theta,
+                                                    p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch,
+                                                    want_s_out=want_s_out, surrogate=surrogate, lengths=lengths, pack=pack)
+        return cols.cut(s_p, dirs), cols.cut(count_p, dirs), saved_p, cols.cut(s16_p, dirs)
     # the same spikes as a bf16 0/1 plane for the GEMMs of the next layer (rows must stay 16-byte aligned)
     s16 = torch.empty(B, T, H * dirs, dtype=torch.bfloat16, device=dev)
     s_out = torch.empty(B, T, H * dirs, dtype=torch.float32, device=dev) if want_s_out else None
-    L = steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T)
+    steps = lambda T_: steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T_)  # noqa: E731
     # bf16 saves: the recurrent kernels take them for whole-sequence launches only (a chunked forward resumes
     # from the saved state, which must then be exact)
-    save16 = SAVE_BF16 and H % 4 == 0 and (not recurrent or (L >= T and not rec_step_path(H)))
+    save16 = SAVE_BF16 and H % 4 == 0 and (not recurrent or (steps(T) >= T and not rec_step_path(H)))
     if surrogate_args(surrogate) is not None:
         save16 = False
     sdt = torch.bfloat16 if save16 else torch.float32
@@ -1373,69 +1454,48 @@ def cell_forward(kind, Wx, scale, shift, p, u0, w0, s0, *, B, dirs, theta, p_dro
     u_save = torch.empty(Bp, T, H, dtype=sdt, device=dev) if want_saves else None
     w_save = torch.empty(Bp, T, H, dtype=sdt, device=dev) if (adaptive and want_saves) else None
     count = torch.zeros(H * dirs, dtype=torch.int32, device=dev)
-    if not recurrent:
-        tok = timer.start(f"cell_fwd[{kind}]")
-        entry = "sparch_cell_fwd_pk" if pack is not None else "sparch_cell_fwd" if lengths is None else "sparch_cell_fwd_len"
-        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them)
-            B, T, len_args = pack.batch, pack.t_max, pack.args()
-        check(getattr(lib, entry)(k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]),
-                                  ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0), ptr(w0),
-                                  ptr(s0), theta, p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save),
-                                  int(save16), ptr(count), *len_args, _stream()), entry)
-        timer.stop(tok)
-    else:
-        if H % 4 != 0:
-            # The recurrent kernels own 4 columns per thread.  Any other width (the reference takes any nb_hiddens,
-            # snns.py:608-661) runs zero-padded to the next multiple of 4: a padded neuron has no input, no
-            # recurrent weights and u0 = 0, so it never spikes and feeds nothing; outputs are sliced back.
-            H4 = (H + 3) // 4 * 4
-            padh = lambda t_: None if t_ is None else torch.nn.functional.pad(t_, (0, H4 - H))  # noqa: E731
-            pp = {k_: (torch.nn.functional.pad(v, (0, H4 - H, 0, H4 - H)) if k_ == "V" else padh(v)) for k_, v in p.items()}
-            s_p, count_p, saved_p, s16_p = cell_forward(kind, padh(Wx), padh(scale), padh(shift), pp, padh(u0), padh(w0),
-                                                        padh(s0), B=B, dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
-                                                        steps_per_launch=steps_per_launch, want_s_out=want_s_out,
-                                                        surrogate=surrogate, lengths=lengths, pack=pack)
-            cut = lambda t_: None if t_ is None else t_.view(B, T, dirs, H4)[..., :H].reshape(B, T, dirs * H).contiguous()  # noqa: E731
-            return (cut(s_p), count_p.view(dirs, H4)[:, :H].reshape(-1).contiguous(), saved_p, cut(s16_p))
-        V = p["V"]
-        if rec_step_path(H):
-            # One launch per time step, the recurrent product s_{t-1} @ V between the steps on the exact
-            # spike GEMM (3 bf16 planes of V, fp32 accumulate): same arithmetic as the persistent kernel.
-            vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
-            check(lib.sparch_vmask(H, ptr(V), ptr(vmask), _stream()), "sparch_vmask")
-            vmask_t = vmask.t().contiguous()              # (H_out, H_in): the NT operand
-            rec = gemm_nn(s0, vmask)                      # t = 0: s0 is uniform noise, not binary
-            s_step = torch.empty(Bp, H, dtype=torch.bfloat16, device=dev)
-            tok = timer.start(f"rec_cell_fwd_steps[{kind}]")
-            for t in range(T):
-                if t > 0:
-                    rec, _ = gemm_nt(s_step, vmask_t, spike_scale=1.0, a16=s_step)
-                check(lib.sparch_rec_cell_step_fwd(k, B, dirs, T, H, t, ptr(Wx), ptr(scale), ptr(shift),
-                                                   ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
-                                                   ptr(p.get("b")), ptr(rec), ptr(u0), ptr(w0), ptr(s0), theta,
-                                                   p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save),
-                                                   ptr(count), ptr(s_step), _stream()), "sparch_rec_cell_step_fwd")
-            timer.stop(tok)
-            return s_out, count, (u_save, w_save), s16
-        # forward fragments, backward fragments (kept for cell_backward) and the masked copy: one launch
-        vpack = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=dev)
-        vpack_t = torch.empty_like(vpack)
+    if recurrent and rec_step_path(H):
+        # One launch per time step, the recurrent product s_{t-1} @ V between the steps on the exact
+        # spike GEMM (3 bf16 planes of V, fp32 accumulate): same arithmetic as the persistent kernel.
         vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
-        check(lib.sparch_vpack_both(H, ptr(V), ptr(vpack), ptr(vpack_t), ptr(vmask), _stream(), _prec()), "sparch_vpack_both")
-        # t = 0 drive: s0 is uniform noise, not binary (snns.py:559/702): a (B', H, H) dense product, split-K so
-        # that its 16 output tiles become a full grid (38 -> ~15 us at B' = 256, H = 1024)
-        rec0 = _gemm_small(s0, vmask, nn=True)
-        entry = "sparch_rec_cell_fwd_pk" if pack is not None else "sparch_rec_cell_fwd" if lengths is None else "sparch_rec_cell_fwd_len"
-        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them; whole sequences only)
-            B, T, Bp, len_args = pack.batch, pack.t_max, pack.batch, pack.args()
-            L = steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T)
-        _persistent(f"rec_cell_fwd[{kind}]", entry,
-                    (k, B, dirs, T, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]), ptr(p.get("beta")),
-                     ptr(p.get("a")), ptr(p.get("b")), ptr(vpack), ptr(rec0), ptr(u0), ptr(w0), ptr(s0), theta, p_drop,
-                     seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16), ptr(count), *len_args),
-                    lib.sparch_rec_chan_bytes(Bp, T, H), dev, L, _prec())
-        return s_out, count, (u_save, w_save, vpack_t), s16
-    return s_out, count, (u_save, w_save), s16
+        check(lib.sparch_vmask(H, ptr(p["V"]), ptr(vmask), _stream()), "sparch_vmask")
+        vmask_t = vmask.t().contiguous()              # (H_out, H_in): the NT operand
+        rec = gemm_nn(s0, vmask)                      # t = 0: s0 is uniform noise, not binary
+        s_step = torch.empty(Bp, H, dtype=torch.bfloat16, device=dev)
+        tok = timer.start(f"rec_cell_fwd_steps[{kind}]")
+        for t in range(T):
+            if t > 0:
+                rec, _ = gemm_nt(s_step, vmask_t, spike_scale=1.0, a16=s_step)
+            check(lib.sparch_rec_cell_step_fwd(k, B, dirs, T, H, t, ptr(Wx), ptr(scale), ptr(shift),
+                                               ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
+                                               ptr(p.get("b")), ptr(rec), ptr(u0), ptr(w0), ptr(s0), theta,
+                                               p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save),
+                                               ptr(count), ptr(s_step), _stream()), "sparch_rec_cell_step_fwd")
+        timer.stop(tok)
+        return s_out, count, (u_save, w_save), s16
+    # both families: the kernels' sequences and steps and the drive in front, the states and results behind
+    Bk, Tk = lay.index(B, T)
+    lead = (k, Bk, dirs, Tk, H, ptr(Wx), ptr(scale), ptr(shift), ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")),
+            ptr(p.get("b")))
+    rest = (ptr(u0), ptr(w0), ptr(s0), theta, p_drop, seed, ptr(s_out), ptr(s16), ptr(u_save), ptr(w_save), int(save16),
+            ptr(count), *lay.tail)
+    if not recurrent:
+        entry = "sparch_cell_fwd" + lay.suffix
+        tok = timer.start(f"cell_fwd[{kind}]")
+        check(getattr(lib, entry)(*lead, *rest, _stream()), entry)
+        timer.stop(tok)
+        return s_out, count, (u_save, w_save), s16
+    # forward fragments, backward fragments (kept for cell_backward) and the masked copy: one launch
+    vpack = torch.empty(lib.sparch_vpack_bytes(H) // 4, dtype=torch.float32, device=dev)
+    vpack_t = torch.empty_like(vpack)
+    vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
+    check(lib.sparch_vpack_both(H, ptr(p["V"]), ptr(vpack), ptr(vpack_t), ptr(vmask), _stream(), _prec()), "sparch_vpack_both")
+    # t = 0 drive: s0 is uniform noise, not binary (snns.py:559/702): a (B', H, H) dense product, split-K so
+    # that its 16 output tiles become a full grid (38 -> ~15 us at B' = 256, H = 1024)
+    rec0 = _gemm_small(s0, vmask, nn=True)
+    _persistent(f"rec_cell_fwd[{kind}]", "sparch_rec_cell_fwd" + lay.suffix, (*lead, ptr(vpack), ptr(rec0), *rest),
+                lib.sparch_rec_chan_bytes(Bk * dirs, Tk, H), dev, steps(Tk), _prec())
+    return s_out, count, (u_save, w_save, vpack_t), s16
 
 
 def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, theta, p_drop, seed,
@@ -1458,6 +1518,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
     dev = g_out.device
     k = KIND[kind]
     adaptive, recurrent = bool(k & 1), bool(k & 2)
+    lay = SeqLayout.of(lengths, pack)
     stateful = want_state_grads or (state_grads is not None and any(g is not None for g in state_grads))
     if stateful:
         check_stateful(kind, H, dirs=dirs, lengths=lengths, pack=pack,
@@ -1470,58 +1531,52 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
     _check_one_direction(dirs, lengths, pack)
     _check_ragged(lengths, dirs, recurrent, H)
     _check_packed(pack, dirs, recurrent, H)
-    len_args = () if lengths is None else (ptr(lengths[0]), int(lengths[1]))
-    sg_len = sg if sg is not None else (SURROGATES["boxcar"], 0.0)
     u_save, w_save = saved[0], saved[1]
     if recurrent and u_save.shape[-1] != H:  # forward ran zero-padded to a multiple of 4 columns (see cell_forward)
-        H4 = u_save.shape[-1]
-        padh = lambda t_: None if t_ is None else torch.nn.functional.pad(t_, (0, H4 - H))  # noqa: E731
-        pp = {k_: (torch.nn.functional.pad(v, (0, H4 - H, 0, H4 - H)) if k_ == "V" else padh(v)) for k_, v in p.items()}
-        g_p = padh(g_out.reshape(B, T, dirs, H)).reshape(B, T, dirs * H4)
-        gr_p = None if g_rate is None else padh(g_rate.reshape(dirs, H)).reshape(dirs * H4)
+        cols = _ColPad(H)
         st_kw = {}
         if stateful:  # (the padding's state is zero and stays zero: its incoming gradient is zero, its outgoing one cut off)
-            st_kw = {"state_grads": tuple(padh(g) for g in (state_grads or (None, None, None))),
+            st_kw = {"state_grads": tuple(cols.pad(g) for g in (state_grads or (None, None, None))),
                      "want_state_grads": want_state_grads}
-        dWx_p, gp = cell_backward(kind, g_p, gr_p, pp, padh(u0), padh(w0), padh(s0), saved, B=B, dirs=dirs, T=T, H=H4,
-                                  theta=theta, p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
+        dWx_p, gp = cell_backward(kind, cols.pad(g_out, dirs), cols.pad(g_rate, dirs), cols.pad_params(p), cols.pad(u0),
+                                  cols.pad(w0), cols.pad(s0), saved, B=B, dirs=dirs, T=T, H=cols.H4, theta=theta,
+                                  p_drop=p_drop, seed=seed, steps_per_launch=steps_per_launch, bn=None,
                                   surrogate=surrogate, lengths=lengths, pack=pack, **st_kw)
         state_p = gp.pop("state", None)
-        grads = {k_: (v[:H, :H].contiguous() if k_ == "V" else v[:H].contiguous()) for k_, v in gp.items()}
+        grads = cols.cut_params(gp)
         if state_p is not None:
-            grads["state"] = tuple(None if g is None else g[:, :H].contiguous() for g in state_p)
-        return dWx_p[..., :H].contiguous(), grads
+            grads["state"] = tuple(cols.cut(g) for g in state_p)
+        return cols.cut(dWx_p), grads
     vpack_fwd_made = saved[2] if len(saved) > 2 else None  # backward fragments of V packed by cell_forward
     save16 = u_save.dtype == torch.bfloat16
     dWx = torch.empty(Bp, T, H, dtype=torch.float32, device=dev)
     n_base = 6 if recurrent else 4
-    if pack is not None:  # (the kernels' B and T; the partial sums are per sequence)
-        B, T, Bp, len_args = pack.batch, pack.t_max, pack.batch, pack.args()
-    ws = torch.empty(n_base + (2 if bn is not None else 0), Bp, H, dtype=torch.float32, device=dev)
+    Bk, Tk = lay.index(B, T)  # (the kernels' B and T; the partial sums are per sequence)
+    rows = Bk * dirs
+    ws = torch.empty(n_base + (2 if bn is not None else 0), rows, H, dtype=torch.float32, device=dev)
     bn_x, bn_mean, bn_invstd = bn if bn is not None else (None, None, None)
     grads = {}
+    # which backward entry of either family, and what it takes behind the layout's arguments: the stateful form the
+    # surrogate and the two state gradients, a ragged layout the surrogate (one entry for all of them), dense the
+    # box-car's entry nothing and the smooth ones' `_sg` theirs
+    sg_any = sg if sg is not None else (SURROGATES["boxcar"], 0.0)
+    if stateful:
+        g_in = [None if g is None else _f32c(g) for g in (state_grads or (None, None, None))]
+        g_0 = [torch.empty(rows, H, dtype=torch.float32, device=dev) if (want_state_grads and (i != 1 or adaptive))
+               else None for i in range(3)]
+        variant, extra = "_st", (*sg_any, *(ptr(g) for g in g_in), *(ptr(g) for g in g_0))
+    elif lay.suffix:
+        variant, extra = lay.suffix, sg_any
+    else:
+        variant, extra = ("", ()) if sg is None else ("_sg", sg)
+    lead = (k, Bk, dirs, Tk, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16), ptr(p["alpha"]),
+            ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")))
+    rest = (ptr(u0), ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx))
+    bn_ptrs = (ptr(bn_x), ptr(bn_mean), ptr(bn_invstd))
     if not recurrent:
+        entry = "sparch_cell_bwd" + variant
         tok = timer.start(f"cell_bwd[{kind}]")
-        lead = (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
-                ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(u0),
-                ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(ws), ptr(bn_x), ptr(bn_mean),
-                ptr(bn_invstd))
-        if stateful:
-            g_in = [None if g is None else _f32c(g) for g in (state_grads or (None, None, None))]
-            g_0 = [torch.empty(B, H, dtype=torch.float32, device=dev) if (want_state_grads and (i != 1 or adaptive))
-                   else None for i in range(3)]
-            check(lib.sparch_cell_bwd_st(*lead, *sg_len, *(ptr(g) for g in g_in), *(ptr(g) for g in g_0), _stream()),
-                  "sparch_cell_bwd_st")
-            if want_state_grads:
-                grads["state"] = tuple(g_0)
-        elif pack is not None:
-            check(lib.sparch_cell_bwd_pk(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_pk")
-        elif lengths is not None:
-            check(lib.sparch_cell_bwd_len(*lead, *len_args, *sg_len, _stream()), "sparch_cell_bwd_len")
-        elif sg is None:
-            check(lib.sparch_cell_bwd(*lead, _stream()), "sparch_cell_bwd")
-        else:
-            check(lib.sparch_cell_bwd_sg(*lead, *sg, _stream()), "sparch_cell_bwd_sg")
+        check(getattr(lib, entry)(*lead, *rest, ptr(ws), *bn_ptrs, *lay.tail, *extra, _stream()), entry)
         timer.stop(tok)
     else:
         V = p["V"]
@@ -1532,66 +1587,49 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
             check(lib.sparch_vmask(H, ptr(V), ptr(vmask), _stream()), "sparch_vmask")
             dwx_step = torch.empty(Bp, H, dtype=torch.float32, device=dev)
             rec = None
+            entry = "sparch_rec_cell_step_bwd" + ("" if sg is None else "_sg")
             tok = timer.start(f"rec_cell_bwd_steps[{kind}]")
             for t in range(T - 1, -1, -1):
                 if t + 1 < T:
                     rec, _ = gemm_nt(dwx_step, vmask)     # rec[b,i] = sum_j dWx[b,j] Vm[i,j]
-                lead = (k, B, dirs, T, H, t, ptr(g_out), ptr(g_rate), ptr(u_save),
-                        ptr(w_save), ptr(p["alpha"]), ptr(p.get("beta")),
-                        ptr(p.get("a")), ptr(p.get("b")), ptr(rec), ptr(u0), ptr(w0),
-                        ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws),
-                        ptr(bn_x), ptr(bn_mean), ptr(bn_invstd), ptr(dwx_step))
-                if sg is None:
-                    check(lib.sparch_rec_cell_step_bwd(*lead, _stream()), "sparch_rec_cell_step_bwd")
-                else:
-                    check(lib.sparch_rec_cell_step_bwd_sg(*lead, *sg, _stream()), "sparch_rec_cell_step_bwd_sg")
+                check(getattr(lib, entry)(k, B, dirs, T, H, t, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save),
+                                          ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(rec),
+                                          *rest, ptr(s_prev), ptr(ws), *bn_ptrs, ptr(dwx_step), *(sg or ()), _stream()),
+                      entry)
             timer.stop(tok)
         else:
             vpack_t = vpack_fwd_made if vpack_fwd_made is not None else _vpack(H, V, 1)
-            entry = ("sparch_rec_cell_bwd_pk" if pack is not None else "sparch_rec_cell_bwd_len" if lengths is not None
-                     else "sparch_rec_cell_bwd_st" if stateful
-                     else "sparch_rec_cell_bwd" if sg is None else "sparch_rec_cell_bwd_sg")
-            sg_tail = sg_len if (lengths is not None or pack is not None) else sg
-            if stateful:
-                g_in = [None if g is None else _f32c(g) for g in (state_grads or (None, None, None))]
-                g_0 = [torch.empty(Bp, H, dtype=torch.float32, device=dev) if (want_state_grads and (i != 1 or adaptive))
-                       else None for i in range(3)]
-                sg_tail = (*sg_len, *(ptr(g) for g in g_in), *(ptr(g) for g in g_0))
-            _persistent(f"rec_cell_bwd[{kind}]", entry,
-                        (k, B, dirs, T, H, ptr(g_out), ptr(g_rate), ptr(u_save), ptr(w_save), int(save16),
-                         ptr(p["alpha"]), ptr(p.get("beta")), ptr(p.get("a")), ptr(p.get("b")), ptr(vpack_t), ptr(u0),
-                         ptr(w0), ptr(s0), theta, p_drop, seed, ptr(dWx), ptr(s_prev), ptr(ws), ptr(bn_x), ptr(bn_mean),
-                         ptr(bn_invstd), *len_args),
-                        lib.sparch_rec_chan_bytes(Bp, T, H), dev,
-                        steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(T), _prec(),
-                        sg=sg_tail)
-            if stateful and want_state_grads:
+            _persistent(f"rec_cell_bwd[{kind}]", "sparch_rec_cell_bwd" + variant,
+                        (*lead, ptr(vpack_t), *rest, ptr(s_prev), ptr(ws), *bn_ptrs, *lay.tail),
+                        lib.sparch_rec_chan_bytes(rows, Tk, H), dev,
+                        steps_per_launch if steps_per_launch is not None else rec_steps_per_launch(Tk), _prec(),
+                        sg=extra)
+            if want_state_grads:
                 # g_s0's third term, (dWx_1) Vm^T: one (B' x H)(H x H) product on the first step's dWx (the kernel wrote
                 # the two pointwise terms)
                 vmask = torch.empty(H, H, dtype=torch.float32, device=dev)
                 check(lib.sparch_vmask(H, ptr(V), ptr(vmask), _stream()), "sparch_vmask")
                 rec1, _ = gemm_nt(dWx[:, 0, :].contiguous(), vmask)  # rec1[b,i] = sum_j dWx_1[b,j] Vm[i,j]
                 g_0[2] = g_0[2] + rec1
-                grads["state"] = tuple(g_0)
         # dV = sum_t s_{t-1}^T (1-alpha) du_t with the diagonal zeroed (mask at snns.py:566/712):
         # binary rows t >= 1 on the exact bf16-split path, plus the t = 0 term with the non-binary s0
         # (cell step 0 sits at original time 0 for the forward direction, T-1 for the flipped one)
         dV = gemm_tn(s_prev.view(-1, H), dWx.view(-1, H), zero_diag=True, spike_side=0, spike16=True)
         for dd in range(dirs):  # s_prev rows of cell step 0 are zero: add the s0 term
-            rows = slice(dd * B, (dd + 1) * B)
-            first = (dWx[rows, (T - 1) if dd else 0, :] if pack is None  # (packed: every sequence's first row)
-                     else dWx.view(-1, H).index_select(0, pack.offsets[:pack.batch]))
-            gemm_tn(s0[rows], first, zero_diag=True, out=dV)
+            r0 = slice(dd * Bk, (dd + 1) * Bk)
+            gemm_tn(s0[r0], lay.first_steps(dWx, r0, flipped=bool(dd)), zero_diag=True, out=dV)
         grads["V"] = dV
+    if want_state_grads:
+        grads["state"] = tuple(g_0)
     names = ["alpha"] + (["beta", "a", "b"] if adaptive else [])
     lims = [ALPHA_LIM] + ([BETA_LIM, A_LIM, B_LIM] if adaptive else [])
     if bn is None:
-        outs = _finish_param_grads(ws, Bp, H, [p[n] for n in names], lims)
+        outs = _finish_param_grads(ws, rows, H, [p[n] for n in names], lims)
     else:
         # one launch for the parameter planes and the two BatchNorm planes behind them (no clamp gate there; the
         # planes in between, if any, are summed too and dropped)
         n_all = n_base + 2
-        outs = _finish_param_grads(ws, Bp, H, [p[n] for n in names] + [None] * (n_all - len(names)),
+        outs = _finish_param_grads(ws, rows, H, [p[n] for n in names] + [None] * (n_all - len(names)),
                                    lims + [(0.0, 0.0)] * (n_all - len(names)))
         grads["bn_sums"] = (outs[n_base], outs[n_base + 1])
     grads.update(dict(zip(names, outs)))
@@ -1599,7 +1637,7 @@ def cell_backward(kind, g_out, g_rate, p, u0, w0, s0, saved, *, B, dirs, T, H, t
 
 
 # ----------------------------------------------------------------------------- layer Functions
-def _check_synapse_layer(cfg, gamma):
+def _check_synapse_layer(cfg, gamma, lay):
     """What a layer with a synapse does not take, before any kernel."""
     check_synapse(cfg["synapse"])
     if gamma is None:
@@ -1607,9 +1645,9 @@ def _check_synapse_layer(cfg, gamma):
     if cfg.get("stateful"):
         raise ValueError("sparch_amd: state / return_state with a synapse is not supported (the carried state has no "
                          "synaptic current yet)")
-    if cfg["dirs"] == 2 and cfg.get("pack") is not None:
+    if cfg["dirs"] == 2 and lay.pack is not None:
         raise ValueError("sparch_amd: pack=True with bidirectional=True and a synapse is not supported")
-    if cfg["dirs"] == 2 and cfg.get("lengths") is None:
+    if cfg["dirs"] == 2 and lay.lengths is None:
         raise ValueError("sparch_amd: a bidirectional layer with a synapse runs on the doubled batch: it needs lengths "
                          "(snns synthesises lengths = T)")
 
@@ -1626,8 +1664,12 @@ class SpikingLayerFn(torch.autograd.Function):
         # the cell, which then reads the current i with no scale and no shift; absent: every call below is what it was
         syn = cfg.get("synapse")
         ctx.has_gamma = gamma is not None
+        # the layout of the time axis; a bidirectional layer on a ragged one runs its cell on the doubled batch
+        lay = SeqLayout.of_cfg(cfg)
+        two, fp32_out = lay.doubled is not None, cfg.get("fp32_out", True)
+        cell_lay = lay.doubled if two else lay
         if syn is not None:
-            _check_synapse_layer(cfg, gamma)
+            _check_synapse_layer(cfg, gamma, lay)
         inp = _layer_input(cfg, x)
         B, T, K = x.shape
         H = W.shape[0]
@@ -1635,45 +1677,36 @@ class SpikingLayerFn(torch.autograd.Function):
         # converts W on the fly: every workgroup streams all of W, and 4 MB of fp32 stay resident in the XCD's 4 MB
         # L2 where 6 MB of planes do not (0.42 against 0.61 GB of L2 misses per launch, 1.8 % faster)
         ctx.w_planes = split_planes(W) if (ctx.needs_input_grad[1] and K % 32 == 0 and H >= 128) else None
-        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, dirs)  # snns.py:261, 264-266
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, dirs,
+                                                       n_valid=lay.n_valid(B, T))  # snns.py:261, 264-266
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
         if cfg.get("states_ready") is not None:  # initial states uploaded on a side stream (snns._rand_batch)
             cfg["states_ready"]()
         inv_keep = 1.0 / (1.0 - p_drop)
-        if _bidir_ragged(cfg):
+        drive = Wx_in.view(B, T, H)
+        if two:
             # both directions as 2B sequences of the one-direction `_len` / `_pk` kernels: the normalised drive is
             # split (the projection and BatchNorm's statistics ran once, on B rows, as on the padded path), the
             # spikes are joined and counted per direction
-            Wx2 = bidir_split(Wx_in.view(B, T, H), cfg)
-            if syn is not None:  # each direction filtered causally in its own time order
-                Wx2 = ctx.syn_i = synapse_forward(Wx2, gamma, syn, scale=scale, shift=shift, **_bidir_cell_kw(cfg))
-                scale = shift = None
-            _, _, saved, s16_2 = cell_forward(kind, Wx2, scale, shift, p, u0, w0, s0, B=Wx2.shape[0], dirs=1, theta=theta,
-                                              p_drop=p_drop, seed=seed, want_s_out=False,
-                                              want_saves=any(ctx.needs_input_grad), surrogate=cfg.get("surrogate"),
-                                              **_bidir_cell_kw(cfg))
-            s_out, s16, count = bidir_join(s16_2, cfg, scale=inv_keep, want_fp32=cfg.get("fp32_out", True))
-        elif syn is not None:
-            i_syn = ctx.syn_i = synapse_forward(Wx_in.view(B, T, H), gamma, syn, scale=scale, shift=shift,
-                                                lengths=cfg.get("lengths"), pack=cfg.get("pack"))
-            s_out, count, saved, s16 = cell_forward(kind, i_syn, None, None, p, u0, w0, s0, B=B, dirs=1, theta=theta,
-                                                    p_drop=p_drop, seed=seed, want_s_out=cfg.get("fp32_out", True),
-                                                    want_saves=any(ctx.needs_input_grad),
-                                                    surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
-                                                    **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
-        else:
-            s_out, count, saved, s16 = cell_forward(kind, Wx_in.view(B, T, H), scale, shift, p, u0, w0, s0, B=B,
-                                                    dirs=dirs, theta=theta, p_drop=p_drop, seed=seed,
-                                                    want_s_out=cfg.get("fp32_out", True),
-                                                    want_saves=any(ctx.needs_input_grad) or bool(cfg.get("stateful")),
-                                                    surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
-                                                    **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}))
+            drive = bidir_split(drive, lay)
+        if syn is not None:  # the cell reads the current, no scale, no shift; each direction filtered in its own order
+            drive = ctx.syn_i = synapse_forward(drive, gamma, syn, scale=scale, shift=shift, lengths=cell_lay.lengths,
+                                                pack=cell_lay.pack)
+            scale = shift = None
+        s_out, count, saved, s16 = cell_forward(kind, drive, scale, shift, p, u0, w0, s0, B=drive.shape[0],
+                                                dirs=1 if two else dirs, theta=theta, p_drop=p_drop, seed=seed,
+                                                want_s_out=fp32_out and not two,
+                                                want_saves=any(ctx.needs_input_grad) or bool(cfg.get("stateful")),
+                                                surrogate=cfg.get("surrogate"), lengths=cell_lay.lengths,
+                                                pack=cell_lay.pack)
+        if two:
+            s_out, s16, count = bidir_join(s16, lay, scale=inv_keep, want_fp32=fp32_out)
         if s_out is None:
             s_out = spike_placeholder(B, T, H * dirs, x.device)
-        n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]  # ragged: the mean is over valid steps
-        rate = count * (inv_keep / float(n_steps))  # snns.py:174 on post-dropout spikes (int32 * float -> fp32, one kernel)
-        ctx.cfg, ctx.inp = cfg, inp
+        # snns.py:174 on post-dropout spikes, ragged: the mean over valid steps (int32 * float -> fp32, one kernel)
+        rate = count * (inv_keep / float(lay.n_valid(B, T)))
+        ctx.cfg, ctx.inp, ctx.lay = cfg, inp, lay
         ctx.shape = (B, T, K, H)
         ctx.nsaved = nsaved
         ctx.cell_saved = saved
@@ -1705,76 +1738,46 @@ class SpikingLayerFn(torch.autograd.Function):
             g_rate = _f32c(g_rate)
         p = {"alpha": alpha, "beta": beta, "a": a, "b": b, "V": V}
         p = {k_: v for k_, v in p.items() if v is not None}
-        syn = cfg.get("synapse")
-        g_gamma = (None,) if ctx.has_gamma else ()  # (one more gradient exactly when gamma was passed)
-        if syn is not None:
-            # the cell's backward without the fused BatchNorm sums (they would be sums over i, not over the projection)
-            # and the filter's adjoint, which makes them instead, from g_z, where the cell's kernel would have (one
-            # direction, whole 4-column pieces), in that kernel's order: at gamma = 0 the layer's gradients are the
-            # bits of the layer without a synapse.  On the doubled batch _project_backward's own pass forms them.
-            two = _bidir_ragged(cfg)
-            if two:
-                n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]
-                g_s, g_rate = bidir_join_backward(g_s, g_rate, 1.0 / float(n_steps), cfg), None
-                lay = _bidir_cell_kw(cfg)
-            else:
-                lay = {"lengths": cfg.get("lengths"), **({} if cfg.get("pack") is None else {"pack": cfg["pack"]})}
-            g_i, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=g_s.shape[0], dirs=1,
-                                    T=g_s.shape[1], H=H, theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"],
-                                    bn=None, surrogate=cfg.get("surrogate"), **lay)
-            bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0 and not two) else None
-            g_z, g_gm, *sums = synapse_backward(g_i, ctx.syn_i, gamma[0], syn, need_ggamma=ctx.needs_input_grad[14],
-                                                bn=bn, **lay)
-            ctx.cell_saved = ctx.syn_i = None
-            if two:
-                g_z = bidir_split_backward(g_z, cfg)
-            dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, g_z, 1,
-                                                      need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
-                                                      sums=sums[0] if sums else None, w_planes=ctx.w_planes,
-                                                      dx_planes=True)
-            dx = None if dx is None else dx.view(B, T, K)
-            ctx.w_planes = ctx.inp = None
-            return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
-                    pg.get("V"), None, None, None, g_gm)
-        if _bidir_ragged(cfg):
-            # the forward's movements, reversed: the gather (with the rate's gradient, each direction's own count over
-            # the valid steps), the one-direction cell backward on the doubled batch — without a rate gradient and
-            # without the fused BatchNorm sums, which would see 2B rows of a projection that has B — and the two
-            # directions' dWx summed in the clip's own time order; _project_backward forms BatchNorm's sums itself
-            n_steps = B * T if cfg.get("lengths") is None else cfg["lengths"][1]
-            g2 = bidir_join_backward(g_s, g_rate, 1.0 / float(n_steps), cfg)
-            dWx2, pg = cell_backward(kind, g2, None, p, u0, w0, s0, ctx.cell_saved, B=g2.shape[0], dirs=1, T=g2.shape[1],
-                                     H=H, theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=None,
-                                     surrogate=cfg.get("surrogate"), **_bidir_cell_kw(cfg))
-            ctx.cell_saved = None
-            dWx = bidir_split_backward(dWx2, cfg)
-            dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, 1,
-                                                      need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
-                                                      w_planes=ctx.w_planes, dx_planes=True)
-            dx = None if dx is None else dx.view(B, T, K)
-            ctx.w_planes = ctx.inp = None
-            return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
-                    pg.get("V"), None, None, None, *g_gamma)
-        # BatchNorm backward's column sums (dbeta, dgamma) come out of the cell's backward kernel
-        bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0) else None
+        syn, lay = cfg.get("synapse"), ctx.lay
+        two = lay.doubled is not None
+        cell_lay = lay.doubled if two else lay
+        n_valid = lay.n_valid(B, T)
+        # BatchNorm backward's column sums (dbeta, dgamma): out of the cell's backward kernel; with a synapse out of the
+        # filter's adjoint instead (they are sums over g_z, not over the current's gradient), made where the cell's
+        # kernel would have (one direction, whole 4-column pieces) in that kernel's order — at gamma = 0 the layer's
+        # gradients are the bits of the layer without a synapse; on the doubled batch, which has 2B rows of a
+        # projection that has B, _project_backward's own pass forms them
+        bn = (Wx_raw, ctx.nsaved[0], ctx.nsaved[1]) if (norm == "batchnorm" and H % 4 == 0 and not two) else None
         st_kw = {}
         if cfg.get("stateful"):  # (absent otherwise: the calls and their arguments are then what they always were)
             st_kw = {"state_grads": (g_uT, g_wT, g_sT), "want_state_grads": any(ctx.needs_input_grad[11:14])}
-        dWx, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=B, dirs=dirs, T=T, H=H,
-                                theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"], bn=bn,
-                                surrogate=cfg.get("surrogate"), lengths=cfg.get("lengths"),
-                                **({} if cfg.get("pack") is None else {"pack": cfg["pack"]}), **st_kw)
-        ctx.cell_saved = None
-        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx, dirs,
+        if two:
+            # the forward's movements, reversed: the gather (with the rate's gradient, each direction's own count over
+            # the valid steps), the one-direction cell backward on the doubled batch, and below the two directions'
+            # dWx summed in the clip's own time order
+            g_s, g_rate = bidir_join_backward(g_s, g_rate, 1.0 / float(n_valid), lay), None
+        g, pg = cell_backward(kind, g_s, g_rate, p, u0, w0, s0, ctx.cell_saved, B=g_s.shape[0], dirs=1 if two else dirs,
+                              T=g_s.shape[1], H=H, theta=cfg["theta"], p_drop=cfg["p_drop"], seed=cfg["seed"],
+                              bn=None if syn is not None else bn, surrogate=cfg.get("surrogate"), lengths=cell_lay.lengths,
+                              pack=cell_lay.pack, **st_kw)
+        sums, g_gm = pg.get("bn_sums"), None
+        if syn is not None:
+            g, g_gm, *sums = synapse_backward(g, ctx.syn_i, gamma[0], syn, need_ggamma=ctx.needs_input_grad[14], bn=bn,
+                                              lengths=cell_lay.lengths, pack=cell_lay.pack)
+            sums = sums[0] if sums else None
+        ctx.cell_saved = ctx.syn_i = None
+        if two:
+            g = bidir_split_backward(g, lay)
+        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, g, 1 if two else dirs,
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
-                                                  sums=pg.get("bn_sums"), w_planes=ctx.w_planes, dx_planes=True)
+                                                  sums=sums, w_planes=ctx.w_planes, dx_planes=True, n_valid=n_valid)
         dx = None if dx is None else dx.view(B, T, K)
         ctx.w_planes = ctx.inp = None
         g_u0, g_w0, g_s0 = pg.get("state", (None, None, None))
         need = ctx.needs_input_grad
         return (None, dx, dW, dWb, dnw, dnb, pg.get("alpha"), pg.get("beta"), pg.get("a"), pg.get("b"),
                 pg.get("V"), g_u0 if need[11] else None, g_w0 if need[12] else None, g_s0 if need[13] else None,
-                *g_gamma)
+                *((g_gm,) if ctx.has_gamma else ()))  # (one more gradient exactly when gamma was passed)
 
 
 SEQ_MODES = {"prob": 0, "sum": 1}  # per-step readout: SPARCH_SEQ_PROB / SPARCH_SEQ_SUM
@@ -1802,14 +1805,24 @@ def readout_mode(readout):
     return READOUT_MODES[readout]
 
 
-def _readout_red_tail(red, arg, lengths, pack):
-    """The `_red` entry points' arguments behind the plain ones: red, arg, lengths, offsets, n_valid."""
+def _check_per_step(pack):
     if pack is not None:
-        len_ptr, off_ptr, n_valid = pack.args()
-        return red, ptr(arg), len_ptr, off_ptr, n_valid
-    if lengths is not None:
-        return red, ptr(arg), ptr(lengths[0]), None, int(lengths[1])
-    return red, ptr(arg), None, None, 0
+        raise ValueError("sparch_amd: the per-step readout has no packed form (per_step with pack)")
+
+
+def _readout_variant(lay, red, mode, red_arg=None, state=None):
+    """Which of the readout's entry points a pass runs, forward and backward alike: (the suffix behind
+    sparch_readout_fwd / sparch_readout_bwd, the arguments behind the plain ones).  state: the stateful backward's
+    (g_uT, g_u0) pointers; red: a reduction other than the softmax-sum (one entry for every layout) with red_arg, the
+    tensor of u_max's steps; mode: the per-step form (its seq tensor and mode sit further in front, with the caller)."""
+    if state is not None:
+        return "_st", state
+    if red != 0:
+        return "_red", (red, ptr(red_arg), *lay.ptrs, lay.ragged_steps)
+    if mode is not None:
+        _check_per_step(lay.pack)
+        return "_seq" + lay.suffix, lay.tail
+    return lay.suffix, lay.tail
 
 
 class ReadoutLayerFn(torch.autograd.Function):
@@ -1828,50 +1841,34 @@ class ReadoutLayerFn(torch.autograd.Function):
         if C > 256:
             raise ValueError(f"sparch_amd: the readout kernels handle at most 256 classes (got {C})")
         inp = _layer_input(cfg, x, gated=False)
-        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1)  # snns.py:796, 799-801
-        pack = cfg.get("pack")  # a PackPlan: x is the packed (1, n, K) batch, out and u0 hold the plan's sorted rows
-        out = torch.empty(B if pack is None else pack.batch, C, dtype=torch.float32, device=x.device)
+        lay = SeqLayout.of_cfg(cfg)  # (packed: x is the (1, n, K) batch, out and u0 hold the plan's sorted rows)
+        Wx_in, scale, shift, nsaved, Wx_raw = _project(inp, W, Wb, nw, nb, cfg, 1,
+                                                       n_valid=lay.n_valid(B, T))  # snns.py:796, 799-801
+        Bk, Tk = lay.index(B, T)
+        out = torch.empty(Bk, C, dtype=torch.float32, device=x.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
-        lengths = cfg.get("lengths")
         mode = seq_mode(cfg.get("per_step"))
         red = readout_mode(cfg.get("readout"))
         if red != 0 and mode is not None:
             raise ValueError("sparch_amd: per_step needs the default readout (softmax_sum)")
         ctx.red_arg = None
-        if red != 0:
-            Bk, Tk = (B, T) if pack is None else (pack.batch, pack.t_max)
-            if red == READOUT_MODES["u_max"]:  # the step of each maximum: the backward reads it
-                ctx.red_arg = torch.empty(Bk, C, dtype=torch.int32, device=x.device)
-            check(lib.sparch_readout_fwd_red(Bk, Tk, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
-                                             ptr(u_save), *_readout_red_tail(red, ctx.red_arg, lengths, pack), _stream()),
-                  "sparch_readout_fwd_red")
-        elif mode is not None:
-            if pack is not None:
-                raise ValueError("sparch_amd: the per-step readout has no packed form (per_step with pack)")
+        if red == READOUT_MODES["u_max"]:  # the step of each maximum: the backward reads it
+            ctx.red_arg = torch.empty(Bk, C, dtype=torch.int32, device=x.device)
+        variant, extra = _readout_variant(lay, red, mode, ctx.red_arg)
+        seq_args = ()
+        if mode is not None:
             seq = torch.empty(B, T, C, dtype=torch.float32, device=x.device)  # (every element is written: no clear)
-            lead = (B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out), ptr(u_save), ptr(seq), mode)
-            if lengths is None:
-                check(lib.sparch_readout_fwd_seq(*lead, _stream()), "sparch_readout_fwd_seq")
-            else:
-                check(lib.sparch_readout_fwd_seq_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()),
-                      "sparch_readout_fwd_seq_len")
+            seq_args = (ptr(seq), mode)
             ctx.set_materialize_grads(False)  # a loss on one of the two outputs: no zero tensor for the other
-        elif pack is not None:
-            check(lib.sparch_readout_fwd_pk(pack.batch, pack.t_max, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0),
-                                            ptr(out), ptr(u_save), *pack.args(), _stream()), "sparch_readout_fwd_pk")
-        elif lengths is None:
-            check(lib.sparch_readout_fwd(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
-                                         ptr(u_save), _stream()), "sparch_readout_fwd")
-        else:  # ragged: each row's truncated sum over its own steps
-            check(lib.sparch_readout_fwd_len(B, T, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
-                                             ptr(u_save), ptr(lengths[0]), int(lengths[1]), _stream()),
-                  "sparch_readout_fwd_len")
-        ctx.cfg, ctx.inp = cfg, inp
+        entry = "sparch_readout_fwd" + variant
+        check(getattr(lib, entry)(Bk, Tk, C, ptr(Wx_in), ptr(scale), ptr(shift), ptr(alpha), ptr(u0), ptr(out),
+                                  ptr(u_save), *seq_args, *extra, _stream()), entry)
+        ctx.cfg, ctx.inp, ctx.lay = cfg, inp, lay
         ctx.shape = (B, T, K, C)
         ctx.nsaved = nsaved
         ctx.save_for_backward(inp.x2, W, nw, alpha, u0, u_save, Wx_raw)
         if cfg.get("stateful"):  # (out, u_T): the final membrane is the last saved step; its gradient comes back as g_uT
-            if red != 0 or mode is not None or pack is not None or lengths is not None:
+            if variant:
                 raise ValueError("sparch_amd: the stateful readout is the plain softmax-sum's")
             ctx.set_materialize_grads(False)
             return out, u_save[:, T - 1].contiguous()
@@ -1879,61 +1876,42 @@ class ReadoutLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_seq=None):
-        cfg = ctx.cfg
+        cfg, lay = ctx.cfg, ctx.lay
         norm = cfg["normalization"]
         B, T, K, C = ctx.shape
         x2, W, nw, alpha, u0, u_save, Wx_raw = ctx.saved_tensors
-        M = B * T
         dev = x2.device
-        stateful, g_uT, g_u0 = bool(cfg.get("stateful")), None, None
-        if stateful:  # the second output was u_T, not seq
-            g_uT, g_seq = g_seq, None
+        state, g_u0 = None, None
         mode = seq_mode(cfg.get("per_step"))
         if g_seq is None:
             mode = None  # nothing came back through seq: the plain kernels
-            if g_out is None:
-                g_out = torch.zeros(B, C, dtype=torch.float32, device=dev)
-        g_out = None if g_out is None else _f32c(g_out)
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         fuse = norm == "batchnorm"
-        pack = cfg.get("pack")
-        if pack is not None:  # (the kernels' B and T: the sequences and the longest of them)
-            B, T = pack.batch, pack.t_max
-        ws = torch.empty(3 if fuse else 1, B, C, dtype=torch.float32, device=dev)
-        lead = (B, T, C, ptr(g_out), ptr(Wx_raw) if fuse else None, ptr(ctx.nsaved[0]) if fuse else None,
-                ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save), ptr(alpha), ptr(u0), ptr(dWx), ptr(ws))
-        lengths = cfg.get("lengths")
-        red = readout_mode(cfg.get("readout"))
-        if stateful:
-            g_uT = None if g_uT is None else _f32c(g_uT)
+        Bk, Tk = lay.index(B, T)  # (the kernels' B and T: packed, the sequences and the longest of them)
+        if cfg.get("stateful"):  # the second output was u_T, not seq
+            g_uT, mode = (None if g_seq is None else _f32c(g_seq)), None
             if ctx.needs_input_grad[7]:
-                g_u0 = torch.empty(B, C, dtype=torch.float32, device=dev)
-            check(lib.sparch_readout_bwd_st(*lead, ptr(g_uT), ptr(g_u0), _stream()), "sparch_readout_bwd_st")
-        elif red != 0:
-            check(lib.sparch_readout_bwd_red(*lead, *_readout_red_tail(red, ctx.red_arg, lengths, pack), _stream()),
-                  "sparch_readout_bwd_red")
-        elif mode is not None:
-            lead = lead[:4] + (ptr(_f32c(g_seq)), mode) + lead[4:]
-            if lengths is None:
-                check(lib.sparch_readout_bwd_seq(*lead, _stream()), "sparch_readout_bwd_seq")
-            else:
-                check(lib.sparch_readout_bwd_seq_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()),
-                      "sparch_readout_bwd_seq_len")
-        elif pack is not None:
-            check(lib.sparch_readout_bwd_pk(*lead, *pack.args(), _stream()), "sparch_readout_bwd_pk")
-        elif lengths is None:
-            check(lib.sparch_readout_bwd(*lead, _stream()), "sparch_readout_bwd")
-        else:
-            check(lib.sparch_readout_bwd_len(*lead, ptr(lengths[0]), int(lengths[1]), _stream()), "sparch_readout_bwd_len")
+                g_u0 = torch.empty(Bk, C, dtype=torch.float32, device=dev)
+            state = (ptr(g_uT), ptr(g_u0))
+        if g_out is None and mode is None:
+            g_out = torch.zeros(B, C, dtype=torch.float32, device=dev)
+        g_out = None if g_out is None else _f32c(g_out)
+        ws = torch.empty(3 if fuse else 1, Bk, C, dtype=torch.float32, device=dev)
+        variant, extra = _readout_variant(lay, readout_mode(cfg.get("readout")), mode, ctx.red_arg, state)
+        seq_args = () if mode is None else (ptr(_f32c(g_seq)), mode)
+        entry = "sparch_readout_bwd" + variant
+        check(getattr(lib, entry)(Bk, Tk, C, ptr(g_out), *seq_args, ptr(Wx_raw) if fuse else None,
+                                  ptr(ctx.nsaved[0]) if fuse else None, ptr(ctx.nsaved[1]) if fuse else None, ptr(u_save),
+                                  ptr(alpha), ptr(u0), ptr(dWx), ptr(ws), *extra, _stream()), entry)
         if fuse:  # dalpha and BatchNorm's two column sums: one launch
-            dalpha, s1, s2 = _finish_param_grads(ws, B, C, [alpha, None, None], [ALPHA_LIM, (0.0, 0.0), (0.0, 0.0)])
+            dalpha, s1, s2 = _finish_param_grads(ws, Bk, C, [alpha, None, None], [ALPHA_LIM, (0.0, 0.0), (0.0, 0.0)])
             sums = (s1, s2)
         else:
-            (dalpha,) = _finish_param_grads(ws, B, C, [alpha], [ALPHA_LIM])
+            (dalpha,) = _finish_param_grads(ws, Bk, C, [alpha], [ALPHA_LIM])
             sums = None
-        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx.view(M, C),
+        dx, dW, dWb, dnw, dnb = _project_backward(ctx.inp, W, nw, cfg, ctx.nsaved, Wx_raw, dWx.view(B * T, C),
                                                   need_dx=ctx.needs_input_grad[1], need_bias=ctx.needs_input_grad[3],
-                                                  sums=sums)
+                                                  sums=sums, n_valid=lay.n_valid(B, T))
         dx = None if dx is None else dx.view(*ctx.shape[:3])
         ctx.inp = None
         return None, dx, dW, dWb, dnw, dnb, dalpha, g_u0
@@ -1983,15 +1961,11 @@ class ReadoutCellFn(torch.autograd.Function):
         out = torch.empty(B, C, dtype=torch.float32, device=Wx.device)
         u_save = torch.empty(B, T, C, dtype=torch.float32, device=Wx.device)
         ctx.red, ctx.red_arg = red, None
-        if red != 0:
-            if red == READOUT_MODES["u_max"]:
-                ctx.red_arg = torch.empty(B, C, dtype=torch.int32, device=Wx.device)
-            check(lib.sparch_readout_fwd_red(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out), ptr(u_save),
-                                             *_readout_red_tail(red, ctx.red_arg, None, None), _stream()),
-                  "sparch_readout_fwd_red")
-        else:
-            check(lib.sparch_readout_fwd(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out), ptr(u_save),
-                                         _stream()), "sparch_readout_fwd")
+        if red == READOUT_MODES["u_max"]:
+            ctx.red_arg = torch.empty(B, C, dtype=torch.int32, device=Wx.device)
+        variant, extra = _readout_variant(_DENSE, red, None, ctx.red_arg)
+        check(getattr(lib, "sparch_readout_fwd" + variant)(B, T, C, ptr(Wx), None, None, ptr(alpha), ptr(u0), ptr(out),
+                                                           ptr(u_save), *extra, _stream()), "sparch_readout_fwd" + variant)
         ctx.dims = (B, T, C)
         ctx.save_for_backward(alpha, u0, u_save)
         return out
@@ -2002,14 +1976,10 @@ class ReadoutCellFn(torch.autograd.Function):
         B, T, C = ctx.dims
         dWx = torch.empty(B, T, C, dtype=torch.float32, device=g_out.device)
         ws = torch.empty(1, B, C, dtype=torch.float32, device=g_out.device)
-        if ctx.red != 0:
-            check(lib.sparch_readout_bwd_red(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save), ptr(alpha),
-                                             ptr(u0), ptr(dWx), ptr(ws),
-                                             *_readout_red_tail(ctx.red, ctx.red_arg, None, None), _stream()),
-                  "sparch_readout_bwd_red")
-        else:
-            check(lib.sparch_readout_bwd(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save), ptr(alpha),
-                                         ptr(u0), ptr(dWx), ptr(ws), _stream()), "sparch_readout_bwd")
+        variant, extra = _readout_variant(_DENSE, ctx.red, None, ctx.red_arg)
+        check(getattr(lib, "sparch_readout_bwd" + variant)(B, T, C, ptr(_f32c(g_out)), None, None, None, ptr(u_save),
+                                                           ptr(alpha), ptr(u0), ptr(dWx), ptr(ws), *extra, _stream()),
+              "sparch_readout_bwd" + variant)
         (dalpha,) = _finish_param_grads(ws, B, C, [alpha], [ALPHA_LIM])
         return dWx, dalpha, None, None
 

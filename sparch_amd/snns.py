@@ -188,6 +188,23 @@ def _check_synapse_call(layer, pack=None, stateful=False):
                          "on the ragged route, which --sync_bn does not take)")
 
 
+def _layout_cfg(x, lengths, pack, dirs=1, lengths2=None, pack2=None):
+    """(the cfg entries that tell a layer Function how the batch's time axis lies in memory — functional.SeqLayout.of_cfg
+    reads them; absent for a dense batch — and the rows of the layer's per-sequence tensors).  dirs == 2: with the
+    doubled batch's lengths2 = double_lengths(lengths) / pack2 = prepare_bidir_packing(pack), made here when not given
+    (SNN.forward makes them once for all its layers)."""
+    cfg = {}
+    if lengths is not None:
+        cfg["lengths"] = lengths
+    if pack is not None:
+        cfg["pack"] = pack
+    if dirs == 2 and pack is not None:
+        cfg["pack2"] = pack2 if pack2 is not None else prepare_bidir_packing(pack, x.device)
+    elif dirs == 2 and lengths is not None:
+        cfg["lengths2"] = lengths2 if lengths2 is not None else double_lengths(lengths)
+    return cfg, Fn.SeqLayout.of(lengths, pack).index(x.shape[0], x.shape[1])[0] * dirs
+
+
 def _delayed_input(layer, x, lengths=None, pack=None):
     """x as a layer with axonal delays (SNN(max_delay=...)) reads it: every input feature shifted
     by its own delay, on the representation the layer's GEMMs read — the bf16 plane of a spike train of ours or of an
@@ -200,11 +217,7 @@ def _delayed_input(layer, x, lengths=None, pack=None):
     if x.ndim != 3 or x.shape[2] != layer.delay.numel():
         raise ValueError(f"sparch_amd: a layer with delays takes (batch, time, {layer.delay.numel()}) inputs, got "
                          f"{tuple(x.shape)}")
-    cfg = {"max_delay": D}
-    if lengths is not None:
-        cfg["lengths"] = lengths
-    if pack is not None:
-        cfg["pack"] = pack
+    cfg = dict(_layout_cfg(x, lengths, pack)[0], max_delay=D)
     B, T, K = x.shape
     scale, s16 = _spike_tag(x)
     if scale is not None and s16 is not None:
@@ -595,7 +608,7 @@ class _SpikingLayer(nn.Module):
             lengths2 = None
         x = _delayed_input(self, x, lengths, pack)  # (x itself without delays)
         dirs = 2 if self.bidirectional else 1
-        rows = (x.shape[0] if pack is None else pack.batch) * dirs
+        layout_cfg, rows = _layout_cfg(x, lengths, pack, dirs, lengths2, pack2)
         if self.batch_size != rows:
             self.batch_size = rows
         u0, w0, s0 = states if states is not None else self._draw_states(rows, x.device)
@@ -624,14 +637,7 @@ class _SpikingLayer(nn.Module):
             # the backward's surrogate: None = the reference's box-car, else ("name", scale) — fp32 saves then
             "surrogate": self._surrogate(),
         }
-        if lengths is not None:  # (absent without lengths: the calls and their arguments are then what they always were)
-            cfg["lengths"] = lengths
-        if pack is not None:
-            cfg["pack"] = pack
-        if dirs == 2 and pack is not None:  # the doubled batch's plan (SNN.forward makes one for all its layers)
-            cfg["pack2"] = pack2 if pack2 is not None else prepare_bidir_packing(pack, x.device)
-        elif dirs == 2 and lengths is not None:  # the doubled batch's lengths
-            cfg["lengths2"] = lengths2 if lengths2 is not None else double_lengths(lengths)
+        cfg.update(layout_cfg)
         if return_state:
             cfg["stateful"] = True
         syn_args = ()
@@ -756,8 +762,9 @@ class ReadoutLayer(nn.Module):
             _check_packed_layer(self, pack, x)
         Fn._require_device(x, "input")
         x = _delayed_input(self, x, lengths, pack)  # (x itself without delays)
+        layout_cfg, rows = _layout_cfg(x, lengths, pack)
         if u0 is None:
-            u0 = _rand_to(x.shape[0] if pack is None else pack.batch, self.hidden_size, x.device)  # snns.py:812
+            u0 = _rand_to(rows, self.hidden_size, x.device)  # snns.py:812
         is_bn = self.normalization == "batchnorm"
         in_scale, in_s16 = _spike_tag(x)
         cfg = {
@@ -769,10 +776,7 @@ class ReadoutLayer(nn.Module):
             "in_spike16": in_s16,  # the same spikes as a bf16 plane
             "num_batches_tracked": self.norm.num_batches_tracked if (is_bn and self.training) else None,
         }
-        if lengths is not None:
-            cfg["lengths"] = lengths
-        if pack is not None:
-            cfg["pack"] = pack
+        cfg.update(layout_cfg)
         if per_step is not None:
             cfg["per_step"] = per_step
         if readout != "softmax_sum":
@@ -1286,13 +1290,12 @@ class SNN(nn.Module):
             if self.use_readout_layer and i == last:
                 if wait is not None:
                     wait()
+                x = layer(x, u0=states[i], lengths=lengths, per_step=per_step, return_state=stateful)
                 if stateful:
-                    x, st = layer(x, u0=states[i], return_state=True)
+                    x, st = x
                     final.append(st)
                 elif per_step is not None:
-                    x, seq = layer(x, u0=states[i], lengths=lengths, per_step=per_step)
-                else:
-                    x = layer(x, u0=states[i]) if lengths is None else layer(x, u0=states[i], lengths=lengths)
+                    x, seq = x
             else:
                 # between two layers of ours the spikes travel as a bf16 plane: no fp32 copy (unless somebody
                 # else may look at the layer's output: forward hooks, the network's own output)
@@ -1355,11 +1358,9 @@ class SNN(nn.Module):
                 x = layer(x, u0=take(states[i]), pack=plan).index_select(0, plan.inverse)
             else:
                 inner = i + 1 < len(self.snn) and not layer._forward_hooks and not _global_forward_hooks()
-                if layer.bidirectional:
-                    x, r = layer.forward_with_rate(x, states=tuple(take2(t_) for t_ in states[i]), fp32_out=not inner,
-                                                   pack=plan, pack2=plan2)
-                else:
-                    x, r = layer.forward_with_rate(x, states=tuple(take(t_) for t_ in states[i]), fp32_out=not inner, pack=plan)
+                rows_of = take2 if layer.bidirectional else take
+                x, r = layer.forward_with_rate(x, states=tuple(rows_of(t_) for t_ in states[i]), fp32_out=not inner,
+                                               pack=plan, pack2=plan2)
                 rates.append(r)
         if not self.use_readout_layer:
             x = Fn.UnpackRowsFn.apply(x.reshape(plan.n, -1), plan)

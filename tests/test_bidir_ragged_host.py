@@ -290,8 +290,3 @@ def test_baselines_and_streams_still_refuse(monkeypatch, tmp_path):
     with pytest.raises(AttributeError) as err:
         exp.Experiment(args())
     assert "bidirectional" not in str(err.value)
-
-
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []

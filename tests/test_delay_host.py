@@ -18,6 +18,7 @@ import torch
 
 from tests.entry_probes import Entry, P, ptrs
 from tests.kit import EINVAL, EWORKSPACE
+from tools.layer_call_trace import calls as _calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE = [("B", 2), ("T", 3), ("K", 8)]
@@ -167,9 +168,9 @@ def _traced(kind="LIF", source="dense", train=True, **kw):
     from tools import layer_call_trace as lct
     from sparch_amd import functional as Fn, snns
     B, T, K, H, C = 4, 3, 32, 128, 5
-    rec = lct._Recorder()
-    with lct._tracing(rec):
-        rec.new_case("case")
+    grads = {}
+
+    def run(lct):
         torch.manual_seed(0)
         net = snns.SNN((B, None, K), [H, H, C], neuron_type=kind, **kw)
         net.train(train)
@@ -185,14 +186,9 @@ def _traced(kind="LIF", source="dense", train=True, **kw):
                 rates.append(r)
         if train:
             lct._backward(x, *rates)
-            grads = {n: p.grad for n, p in net.named_parameters()}
-        else:
-            grads = {}
-    return rec.lines[1:], grads
+            grads.update({n: p.grad for n, p in net.named_parameters()})
 
-
-def _calls(lines, name):
-    return [ln for ln in lines if ln.startswith(name + "(")]
+    return lct.traced(run)[1:], grads
 
 
 def test_without_delays_the_calls_are_what_they_were():

@@ -267,8 +267,3 @@ def test_baselines_and_streams_refuse_packed_batches():
         for cls in (streaming.StreamingSNN, streaming_ann.StreamingANN):
             with pytest.raises(ValueError, match="streaming"):
                 cls.step(object.__new__(cls), X, **kw)
-
-
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []

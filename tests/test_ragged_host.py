@@ -13,6 +13,7 @@ import torch
 
 from tests.entry_probes import KIND, MIS, WS, Entry, P, T, head, ptrs
 from tests.kit import EALIGN, EINVAL, EWORKSPACE
+from tools.layer_call_trace import traced
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEN = [("lengths", P), ("n_valid", 5)]
@@ -171,15 +172,6 @@ def test_experiment_refuses_a_bad_value_before_anything_else(monkeypatch, tmp_pa
 
 
 # ------------------------------------------------------------------------------------------------ the calls issued
-def traced(run):
-    from tools import layer_call_trace as lct
-    rec = lct._Recorder()
-    with lct._tracing(rec):
-        rec.new_case("case")
-        run(lct)
-    return rec.lines
-
-
 def layer_case(kind, lengths, norm="batchnorm"):
     def run(lct):
         x, xcfg = lct._input("dense", 4, 3, 32, True)
@@ -187,11 +179,6 @@ def layer_case(kind, lengths, norm="batchnorm"):
         s, rate, _ = lct._spiking(x, cfg, kind, norm, 1, 128)
         lct._backward(s, rate)
     return run
-
-
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []
 
 
 @pytest.mark.parametrize("kind,fwd,bwd", [("adLIF", "sparch_cell_fwd", "sparch_cell_bwd"),

@@ -207,11 +207,6 @@ def test_every_python_refusal_is_a_value_error():
     assert Fn.readout_mode(None) == 0 and [Fn.readout_mode(m) for m in rm.MODES] == [0, 1, 2, 3, 4]
 
 
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []
-
-
 def test_a_network_pickled_without_the_attribute_is_the_default():
     """What torch.save(net) wrote before the argument existed: no `readout` in any __dict__."""
     net = _net().eval()

@@ -179,11 +179,6 @@ def test_every_python_refusal_is_a_value_error():
     assert Fn.seq_mode(None) is None and Fn.seq_mode("prob") == 0 and Fn.seq_mode("sum") == 1
 
 
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []
-
-
 # ------------------------------------------------------------------------------------------------ SPARCH_PER_STEP_LOSS
 def test_sparch_per_step_loss_parsing():
     from sparch_amd import exp

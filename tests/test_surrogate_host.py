@@ -27,6 +27,7 @@ from tests import spiking_numpy as sn
 from tests import surrogate_numpy as sg
 from tests.entry_probes import KIND, MIS, NAN, RLIF, WS, Entry, P, T, head, ptrs
 from tests.kit import EALIGN, EINVAL, EWORKSPACE, F32, F64
+from tools.layer_call_trace import traced
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
@@ -316,15 +317,6 @@ def test_sg_entries_refuse_before_any_device_work(e):
 
 
 # ------------------------------------------------------------------------------------------------ the calls issued
-def traced(run):
-    from tools import layer_call_trace as lct
-    rec = lct._Recorder()
-    with lct._tracing(rec):
-        rec.new_case("case")
-        run(lct)
-    return rec.lines
-
-
 def layer_case(kind, sgate, **kw):
     def run(lct):
         with lct._env(**kw.get("env", {})):         # (the tracer clears the switches around the cases: set inside)
@@ -392,8 +384,3 @@ def test_a_smooth_layer_keeps_fp32_saves():
     assert fwd(smooth).count("bf16[4,3,128]") == 1      # the spike plane only: the saves are fp32
     bwd = next(ln for ln in smooth if ln.startswith("sparch_cell_bwd_sg("))
     assert ", 2, 5.0, NULL)" in bwd and lct.DTYPE[torch.float32] == "f32"
-
-
-def test_the_committed_trace_is_unchanged():
-    from tools import layer_call_trace as lct
-    assert lct.difference(lct.trace()) == []

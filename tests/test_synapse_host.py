@@ -20,6 +20,7 @@ import torch
 
 from tests.entry_probes import Entry, P, ptrs
 from tests.kit import EINVAL, EWORKSPACE
+from tools.layer_call_trace import calls as _calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE = [("B", 2), ("T", 3), ("H", 8)]
@@ -157,9 +158,9 @@ def _traced(kind="LIF", train=True, norm="batchnorm", bidirectional=False, lengt
     from sparch_amd import snns
     B, T, K, H, C = 4, 3, 32, 128, 5
     dirs = 2 if bidirectional else 1
-    rec = lct._Recorder()
-    with lct._tracing(rec):
-        rec.new_case("case")
+    grads = {}
+
+    def run(lct):
         torch.manual_seed(0)
         net = snns.SNN((B, None, K), [H, H, C], neuron_type=kind, normalization=norm, bidirectional=bidirectional, **kw)
         net.train(train)
@@ -177,14 +178,9 @@ def _traced(kind="LIF", train=True, norm="batchnorm", bidirectional=False, lengt
                 rates.append(r)
         if train:
             lct._backward(x, *rates)
-            grads = {n: p.grad for n, p in net.named_parameters()}
-        else:
-            grads = {}
-    return rec.lines[1:], grads
+            grads.update({n: p.grad for n, p in net.named_parameters()})
 
-
-def _calls(lines, name):
-    return [ln for ln in lines if ln.startswith(name + "(")]
+    return lct.traced(run)[1:], grads
 
 
 def _index(lines, name):

@@ -3,13 +3,15 @@
 
     python tools/layer_call_trace.py            print the trace
     python tools/layer_call_trace.py --check    unified diff against tests/golden/layer_call_trace.txt.gz (exit 1 if any)
-    python tools/layer_call_trace.py --write    regenerate that file (3 447 lines of text, kept gzipped: 26 KB)
+    python tools/layer_call_trace.py --write    regenerate that file (7 003 lines of text in 214 cases, kept gzipped: 60 KB)
 
 Nothing runs on a device: the layer Functions are driven forward and backward on CPU tensors while
   * `functional.lib` / `streaming.lib` are a stand-in that logs every launching `sparch_*` call and returns 0, forwards
     the pure host queries (every `*_bytes` function) to the real library and answers `sparch_device_cus` with 256,
-  * `ptr` hands the stand-in the tensor instead of its address, `_stream()` is None, `_require_device` lets CPU
-    tensors through, and `functional.timer` logs the labels it is started with (bench.py keys its roofline on them).
+  * `ptr` hands the stand-in the tensor instead of its address, `_stream()` is None, `_require_device` and
+    `snns._check_bidir_input` let CPU tensors through, SNN.forward draws its initial states with torch.rand
+    (`snns._fast_rand_ok` is False), and `functional.timer` logs the labels it is started with (bench.py keys its
+    roofline on them).
 A line holds the entry point and every argument in the order of `_capi.PROTOTYPES`, which also tells pointers from
 numbers.  A pointer is NULL or `dtype[shape]/(strides)#n+offset`: strides only when not contiguous, n the number of the
 tensor's allocation in order of first appearance within the case (two arguments with one n alias), never an address.
@@ -20,7 +22,10 @@ file is the same on every machine, and a change to the host code that leaves it 
 same operands.
 
 Values are never looked at, so every case uses the smallest shape at which its branch is taken.  SyncBN needs a process
-group and is not traced."""
+group and is not traced.  The first 123 cases (3 447 lines) are the dense layer passes; the 91 behind them are what the
+spiking layer path gained since: `lengths` / packed / bidirectional-ragged layouts, smooth surrogates, stateful
+training, the selectable and per-step readouts, axonal delays, synaptic currents and the row movers.  New cases go to
+the end, so that the text in front of them stays byte for byte what it was."""
 import contextlib
 import ctypes
 import difflib
@@ -185,6 +190,10 @@ def _tracing(rec):
             patch(mod, "ptr", lambda t: t)
         patch(Fn, "_stream", lambda: None)
         patch(Fn, "_require_device", lambda t, what: None)
+        patch(snns, "_check_bidir_input", lambda net, x, what: None)
+        # SNN.forward's own state draws stay with torch.rand: the host routine behind the fast draw is a library call,
+        # and its one-time self-check would see the stand-in (and switch the fast draw off for the whole process)
+        patch(snns, "_fast_rand_ok", False)
         patch(Fn, "timer", _Timer(rec))
         patch(torch, "empty", empty)
         patch(torch, "empty_like", empty_like)
@@ -225,9 +234,10 @@ def _input(source, B, T, K, x_grad=False):
     return _p(B, T, K, grad=x_grad), {}
 
 
-def _spiking(x, xcfg, kind, norm, dirs, H, train=True, bias=False, fp32_out=True):
-    """One SpikingLayerFn.apply -> (s, rate, the next layer's description of s)."""
+def _spiking(x, xcfg, kind, norm, dirs, H, train=True, bias=False, fp32_out=True, rows=None):
+    """One SpikingLayerFn.apply -> (s, rate, the next layer's description of s).  rows: the sequences of a packed x."""
     B, T, K = x.shape
+    B = rows or B
     adaptive, rec = kind in ("adLIF", "RadLIF"), kind in ("RLIF", "RadLIF")
     g = train
     nw, nb = _norm_params(norm, H, g)
@@ -243,13 +253,14 @@ def _spiking(x, xcfg, kind, norm, dirs, H, train=True, bias=False, fp32_out=True
     return s, rate, {"in_spike_scale": 1.0, "in_spike16": s16 if s16.numel() else None}
 
 
-def _readout(x, xcfg, norm, C, train=True, bias=False):
+def _readout(x, xcfg, norm, C, train=True, bias=False, extra=None, rows=None, u0_grad=False):
     B, T, K = x.shape
     nw, nb = _norm_params(norm, C, train)
     cfg = dict(_norm_cfg(norm, C, train), in_spike_scale=None, in_spike16=None)
     cfg.update({k: v for k, v in xcfg.items() if k in cfg})
+    cfg.update(extra or {})
     return Fn.ReadoutLayerFn.apply(cfg, x, _p(C, K, grad=train), _p(C, grad=train) if bias else None, nw, nb,
-                                   _p(C, grad=train), torch.zeros(B, C))
+                                   _p(C, grad=train), _p(rows or B, C, grad=u0_grad))
 
 
 def _backward(*outs):
@@ -364,6 +375,80 @@ def case_streaming(kind, norm, H, fp32_last=False):
     st.reset(states=states + ([] if fp32_last else [torch.zeros(B, C)]))
     st.step(torch.zeros(B, Tc, K))
     st.step(torch.zeros(B, Tc, K, dtype=torch.uint8))
+
+
+# ---------------------------------------------------------- ragged layouts, and what the layer path gained with them
+LENGTHS = (3, 1, 2, 3)  # at B = 4, T = 3: a full row, a one-step row, and a sum (9) that is not B * T
+SMOOTH = ("fast_sigmoid", 5.0)
+
+
+def _layout(layout, dirs=1, B=4, T=3):
+    """(the cfg entries of a layout the way snns.py assembles them, the leading shape of x, the sequences)."""
+    if layout == "dense":
+        return {}, (B, T), B
+    if layout == "lengths":
+        lengths = snns.prepare_lengths(torch.tensor(LENGTHS), B, T, "cpu")
+        return dict(lengths=lengths, **({"lengths2": snns.double_lengths(lengths)} if dirs == 2 else {})), (B, T), B
+    plan = snns.prepare_packing(torch.tensor(LENGTHS), B, T, "cpu")
+    return dict(pack=plan, **({"pack2": snns.prepare_bidir_packing(plan, "cpu")} if dirs == 2 else {})), (1, plan.n), B
+
+
+def case_layout(kind, norm, dirs, layout, K=32, H=128, x_grad=False, source="dense", **extra):
+    """SpikingLayerFn on a ragged layout; extra: further cfg entries (surrogate)."""
+    lay, (Bx, Tx), rows = _layout(layout, dirs)
+    x, xcfg = _input(source, Bx, Tx, K, x_grad)
+    s, rate, _ = _spiking(x, dict(xcfg, **lay, **extra), kind, norm, dirs, H, rows=rows)
+    _backward(s, rate)
+
+
+def case_readout_layout(norm, layout, K=32, C=5, only=None, **extra):
+    """ReadoutLayerFn on a layout; extra: readout / per_step; only: the one output ("out" / "seq") that gets a gradient."""
+    lay, (Bx, Tx), rows = _layout(layout)
+    x, xcfg = _input("dense", Bx, Tx, K, True)
+    res = _readout(x, xcfg, norm, C, extra=dict(lay, **extra), rows=rows, u0_grad=bool(extra.get("stateful")))
+    if only is not None:
+        res = res[("out", "seq").index(only)]
+    _backward(*(res if isinstance(res, tuple) else (res,)))
+
+
+def _tensors(res):
+    for r in res if isinstance(res, (tuple, list)) else (res,):
+        if isinstance(r, dict):
+            yield from r.values()
+        elif isinstance(r, (tuple, list)):
+            yield from _tensors(r)
+        else:
+            yield r
+
+
+def case_net(kind, norm, sizes=(128, 128, 5), K=32, source="dense", x_grad=False, lengths=False, train=True, fw=None,
+             **net_kw):
+    """Whole SNN.forward (states drawn by the network), backward through everything it returned."""
+    B, T = 4, 3
+    net = snns.SNN((B, None, K), list(sizes), neuron_type=kind, normalization=norm, **net_kw).train(train)
+    fw = dict(fw or {}, **({"lengths": torch.tensor(LENGTHS)} if lengths else {}))
+    with contextlib.ExitStack() as stack:
+        if not train:
+            stack.enter_context(torch.no_grad())
+        res = net(_input(source, B, T, K, x_grad)[0], **fw)
+        if train:
+            _backward(*_tensors(res))
+
+
+def case_stateful(kind, sizes=(128, 128, 5), K=32, only_state=False):
+    """return_state=True, then the next chunk from that state; only_state: the gradient arrives on the final state
+    alone."""
+    B, T = 4, 3
+    net = snns.SNN((B, None, K), list(sizes), neuron_type=kind, normalization="batchnorm").train()
+    first = net(torch.zeros(B, T, K), return_state=True)
+    second = net(torch.zeros(B, T, K), state=first[2], return_state=True)
+    _backward(*_tensors(second[2] if only_state else (first[:2], second)))
+
+
+def case_row_movers(C=8):
+    plan = _layout("pack")[0]["pack"]
+    xp = Fn.PackRowsFn.apply(_p(4, 3, C), plan)
+    _backward(xp, Fn.UnpackRowsFn.apply(_p(plan.n, C), plan))
 
 
 @contextlib.contextmanager
@@ -496,6 +581,118 @@ def _cases():
     add("streaming RLIF none, no readout, 4x(3+3)x32->6->6", case_streaming, "RLIF", "none", 6, fp32_last=True)
     add_sw("SPARCH_REC_STEP_PATH=1 streaming RadLIF batchnorm 4x(3+3)x32->128->128->5",
            lambda: _env(SPARCH_REC_STEP_PATH="1"), case_streaming, "RadLIF", "batchnorm", 128)
+
+    # ---- everything below: what the spiking layer path gained since (ragged layouts, surrogates, stateful training,
+    # readouts, delays, synapses, the row movers); lengths (3, 1, 2, 3) throughout
+    n = 0
+    for kind in kinds:  # SpikingLayerFn: every kind x layout x dirs; each normalisation meets each layout
+        for layout in ("lengths", "pack"):
+            for dirs in (1, 2):
+                norm, x_grad = norms[n % 3], bool(n & 4)
+                n += 1
+                add(f"spiking {kind} {norm} dirs={dirs} x_grad={int(x_grad)} {layout} 4x3x32->128", case_layout, kind,
+                    norm, dirs, layout, x_grad=x_grad)
+    for kind, norm, dirs, layout in (("LIF", "batchnorm", 1, "lengths"), ("adLIF", "layernorm", 2, "pack"),
+                                     ("RadLIF", "none", 2, "lengths"), ("RLIF", "batchnorm", 1, "pack")):
+        add(f"spiking {kind} {norm} dirs={dirs} {layout} 4x3x12->8", case_layout, kind, norm, dirs, layout, K=12, H=8,
+            x_grad=True)
+    for kind, dirs, layout in (("RLIF", 1, "lengths"), ("RadLIF", 2, "lengths"), ("RLIF", 2, "pack"), ("RadLIF", 1, "pack")):
+        add(f"spiking {kind} batchnorm dirs={dirs} {layout} 4x3x12->6", case_layout, kind, "batchnorm", dirs, layout,
+            K=12, H=6, x_grad=True)
+    add("spiking LIF batchnorm dirs=1 counts lengths 4x3x32->128", case_layout, "LIF", "batchnorm", 1, "lengths",
+        source="counts")
+    for kind, norm, bidir, fw in (("LIF", "batchnorm", False, {}), ("RadLIF", "layernorm", False, {"pack": True}),
+                                  ("adLIF", "batchnorm", True, {}), ("RLIF", "none", True, {"pack": True})):
+        add(f"net {kind} {norm} bidirectional={int(bidir)} {'pack' if fw else 'lengths'} 4x3x32->128->128->5", case_net,
+            kind, norm, bidirectional=bidir, lengths=True, fw=fw)
+    add("net RadLIF batchnorm bidirectional=1 lengths 4x3x12->6->6->5", case_net, "RadLIF", "batchnorm", sizes=(6, 6, 5),
+        K=12, bidirectional=True, lengths=True, x_grad=True)
+    add("net LIF batchnorm pack, no readout, counts 4x3x32->128->128", case_net, "LIF", "batchnorm", sizes=(128, 128),
+        source="counts", lengths=True, fw={"pack": True}, use_readout_layer=False)
+
+    # a smooth surrogate: the `_sg` backward entries, and the `_len` / `_pk` ones with its id and scale
+    for kind in ("LIF", "RLIF"):
+        for layout in ("dense", "lengths", "pack"):
+            add(f"surrogate fast_sigmoid spiking {kind} batchnorm dirs=1 {layout} 4x3x32->128", case_layout, kind,
+                "batchnorm", 1, layout, x_grad=True, surrogate=SMOOTH)
+    add("surrogate fast_sigmoid spiking adLIF none dirs=2 dense 4x3x12->8", case_layout, "adLIF", "none", 2, "dense",
+        K=12, H=8, surrogate=SMOOTH)
+    add("surrogate fast_sigmoid spiking RadLIF batchnorm dirs=2 lengths 4x3x12->6", case_layout, "RadLIF", "batchnorm",
+        2, "lengths", K=12, H=6, surrogate=SMOOTH)
+    add_sw("SPARCH_REC_STEP_PATH=1 surrogate fast_sigmoid spiking RLIF batchnorm dirs=1 dense 4x3x32->128",
+           lambda: _env(SPARCH_REC_STEP_PATH="1"), case_layout, "RLIF", "batchnorm", 1, "dense", surrogate=SMOOTH)
+    add("surrogate triangle net RadLIF layernorm lengths 4x3x32->128->128->5", case_net, "RadLIF", "layernorm",
+        lengths=True, surrogate="triangle")
+
+    # stateful training: return_state=True, then state=
+    for kind in ("LIF", "adLIF", "RLIF"):
+        add(f"stateful net {kind} batchnorm 4x3x32->128->128->5", case_stateful, kind)
+    for kind in ("RLIF", "RadLIF"):
+        add(f"stateful net {kind} batchnorm 4x3x12->6->6->5", case_stateful, kind, sizes=(6, 6, 5), K=12)
+    add("stateful net adLIF batchnorm, gradient on the final state only, 4x3x12->8->8->5", case_stateful, "adLIF",
+        sizes=(8, 8, 5), K=12, only_state=True)
+    add("stateful net RLIF batchnorm, gradient on the final state only, 4x3x12->6->6->5", case_stateful, "RLIF",
+        sizes=(6, 6, 5), K=12, only_state=True)
+    add("stateful readout none, gradient on u0, 4x3x32->5", case_readout_layout, "none", "dense", stateful=True)
+
+    # the readout: every reduction x layout, the per-step forms, a gradient on one output only
+    for i, mode in enumerate(Fn.READOUT_MODES):
+        for j, layout in enumerate(("dense", "lengths", "pack")):
+            add(f"readout={mode} {norms[(i + j) % 3]} {layout} 4x3x32->5", case_readout_layout, norms[(i + j) % 3],
+                layout, readout=mode)
+    for i, per_step in enumerate(Fn.SEQ_MODES):
+        for j, layout in enumerate(("dense", "lengths")):
+            add(f"per_step={per_step} {norms[(1 + i + j) % 3]} {layout} 4x3x32->5", case_readout_layout,
+                norms[(1 + i + j) % 3], layout, per_step=per_step)
+    add("per_step=prob batchnorm lengths, gradient on seq only, 4x3x32->5", case_readout_layout, "batchnorm", "lengths",
+        per_step="prob", only="seq")
+    add("per_step=sum none dense, gradient on out only, 4x3x32->5", case_readout_layout, "none", "dense",
+        per_step="sum", only="out")
+    add("per_step=prob net LIF batchnorm lengths 4x3x32->128->128->5", case_net, "LIF", "batchnorm", lengths=True,
+        fw={"per_step": "prob"})
+    add("readout=u_max net adLIF layernorm pack 4x3x12->8->8->5", case_net, "adLIF", "layernorm", sizes=(8, 8, 5), K=12,
+        lengths=True, fw={"pack": True}, readout="u_max")
+
+    # axonal delays: on dense fp32 input, on a spike plane of ours (the second layer), on byte input
+    add("delays net LIF batchnorm dense 4x3x32->128->128->5", case_net, "LIF", "batchnorm", max_delay=2)
+    add("delays net adLIF none dense x_grad=1 4x3x12->8->8->5", case_net, "adLIF", "none", sizes=(8, 8, 5), K=12,
+        x_grad=True, max_delay=2)
+    add("delays net RLIF layernorm counts 4x3x32->128->128->5", case_net, "RLIF", "layernorm", source="counts",
+        max_delay=2)
+    add("delays (fixed) net LIF batchnorm dense 4x3x32->128->128->5", case_net, "LIF", "batchnorm", max_delay=2,
+        learn_delays=False)
+    add("delays (hidden) net LIF batchnorm eval 4x3x32->128->128->5", case_net, "LIF", "batchnorm", train=False,
+        max_delay=2, delay_layers="hidden")
+    add("delays net RadLIF batchnorm lengths 4x3x32->128->128->5", case_net, "RadLIF", "batchnorm", lengths=True,
+        max_delay=2)
+    add("delays net LIF layernorm bidirectional=1 pack 4x3x32->128->128->5", case_net, "LIF", "layernorm", lengths=True,
+        fw={"pack": True}, bidirectional=True, max_delay=2)
+    add("delays net adLIF batchnorm counts pack 4x3x32->128->128->5", case_net, "adLIF", "batchnorm", source="counts",
+        lengths=True, fw={"pack": True}, max_delay=2)
+
+    # synaptic currents
+    syn = (0.0, 0.9)
+    add("synapse net LIF batchnorm dense 4x3x32->128->128->5", case_net, "LIF", "batchnorm", synapse=syn)
+    add("synapse net RadLIF layernorm lengths 4x3x32->128->128->5", case_net, "RadLIF", "layernorm", lengths=True,
+        synapse=syn)
+    add("synapse net adLIF batchnorm pack 4x3x32->128->128->5", case_net, "adLIF", "batchnorm", lengths=True,
+        fw={"pack": True}, synapse=syn)
+    add("synapse net RLIF batchnorm lengths 4x3x12->6->6->5", case_net, "RLIF", "batchnorm", sizes=(6, 6, 5), K=12,
+        lengths=True, synapse=syn)
+    add("synapse net LIF batchnorm bidirectional=1 dense 4x3x32->128->128->5", case_net, "LIF", "batchnorm",
+        bidirectional=True, synapse=syn)
+    add("synapse net RadLIF none bidirectional=1 lengths 4x3x32->128->128->5", case_net, "RadLIF", "none",
+        bidirectional=True, lengths=True, synapse=syn)
+    add("synapse (fixed, hidden) net LIF batchnorm dense 4x3x32->128->128->5", case_net, "LIF", "batchnorm", synapse=syn,
+        learn_synapse=False, synapse_layers="hidden")
+    add("synapse net adLIF layernorm eval 4x3x12->8->8->5", case_net, "adLIF", "layernorm", sizes=(8, 8, 5), K=12,
+        train=False, synapse=syn)
+    add("synapse and delays net LIF batchnorm lengths 4x3x32->128->128->5", case_net, "LIF", "batchnorm", lengths=True,
+        synapse=syn, max_delay=2)
+
+    add("row movers 4x3x8", case_row_movers)
+    add("spiking LIF batchnorm dirs=1, spikes that arrive without their plane, lengths 4x3x32->128", case_layout, "LIF",
+        "batchnorm", 1, "lengths", x_grad=True, in_spike_scale=1.0)
     return out
 
 
@@ -507,6 +704,20 @@ def trace():
             rec.new_case(name)
             run()
     return "\n".join(rec.lines) + "\n"
+
+
+def traced(run):
+    """The lines of one case of the caller's: run(this module) under the tracer (the `*_host.py` tests)."""
+    rec = _Recorder()
+    with _tracing(rec):
+        rec.new_case("case")
+        run(sys.modules[__name__])
+    return rec.lines
+
+
+def calls(lines, name):
+    """The lines of `lines` that call the entry point `name`."""
+    return [ln for ln in lines if ln.startswith(name + "(")]
 
 
 def recorded():
