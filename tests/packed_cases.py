@@ -138,11 +138,13 @@ class injected_states:
         self.mod._rand_to = self.old
 
 
-def packed_drop_masks(lengths, p_drop, seeds, widths):
+def packed_drop_masks(lengths, p_drop, seeds, widths, T=NT, run_widths=None):
     """The hidden layers' dropout multipliers of a packed forward as padded (B,T,H) tensors in the caller's row order:
-    the mask of tests/dropout_numpy.py on the packed element index, zero on the padding."""
+    the mask of tests/dropout_numpy.py on the packed element index, zero on the padding.  run_widths: the widths the
+    layers run at where they differ (a recurrent width that is not a multiple of 4 runs zero-padded to the next one, and
+    the mask's index is that tensor's: tests/dropout_numpy.py keep_mask_padded)."""
     masks = []
-    for seed, H in zip(seeds, widths):
-        flat = keep_mask(seed, (int(np.sum(lengths)), H), p_drop)
-        masks.append(torch.from_numpy(pn.unpack(flat, lengths, NT)))
+    for seed, H, Hp in zip(seeds, widths, run_widths or widths):
+        flat = keep_mask(seed, (int(np.sum(lengths)), Hp), p_drop)[:, :H]
+        masks.append(torch.from_numpy(pn.unpack(np.ascontiguousarray(flat), lengths, T)))
     return masks
