@@ -246,6 +246,12 @@ int sparch_bn_finalize(int H, int M, int n_tiles, int dup, const float* colstat_
                        float* scale, float* shift, float* save_mean, float* save_invstd,
                        const uint32_t* skip_if_nonzero, int64_t* num_batches_tracked, void* stream);
 
+/* Statistics partials of a projection with few rows, for sparch_bn_finalize with n_tiles = 3: the fp64 column sums
+ * of x and of x*x over the M rows of the contiguous (M,H) x, each as three fp32 terms (hi, mid, lo), written as
+ * colstat_ws[2][3][H].  The GEMM epilogue's fp32 partials lose log2((mean^2 + var) / var) bits of the variance; these
+ * lose none.  Rows that are exactly zero (the padding of a ragged batch) add nothing, as in the epilogue's.          */
+int sparch_bn_colstat_exact(int M, int H, const float* x, float* colstat_ws, void* stream);
+
 /* Column sums of dy and dy*xhat over M rows (xhat = (x-mean)*invstd), partials in ws
  * (2 * ceil(M/256) * H floats), finished into dgamma[H], dbeta[H].                   */
 size_t sparch_bn_bwd_workspace_bytes(int M, int H);

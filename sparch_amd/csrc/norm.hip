@@ -89,6 +89,45 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(int H, int M, int n_ti
     if (save_invstd) save_invstd[h] = invstd;
 }
 
+// ---------------------------------------------------------------- BatchNorm statistics of few rows
+// The GEMM epilogue's partials are fp32 sums of x and x*x; var = E[x^2] - mean^2 from them loses log2(R) bits,
+// R = (mean^2 + var) / var.  The non-spiking readout normalises sums of softmax outputs over the batch alone
+// (positive, nearly equal from clip to clip: R up to 3e4 measured), and its variance came out with a relative error
+// of 1e-3.  Where the projection has few rows, this kernel reads it again and writes the fp64 column sums of x and
+// x*x (x*x is exact in fp64; fixed summation order) as three fp32 terms each, hi + mid + lo = 72 bits: three "tile
+// rows" in the layout bn_finalize_kernel sums in fp64, which then forms the same difference in full fp64.
+__global__ __launch_bounds__(256) void colstat_exact_kernel(int M, int H, const float* __restrict__ x,
+                                                            float* __restrict__ ws) {
+    __shared__ double red[2][CS_LANES][CS_COLS];
+    const int c = threadIdx.x & (CS_COLS - 1), q = threadIdx.x / CS_COLS;
+    const int h = blockIdx.x * CS_COLS + c;
+    double s = 0.0, ss = 0.0;
+    if (h < H)
+        for (int r = q; r < M; r += CS_LANES) {
+            const double v = (double)x[(size_t)r * H + h];
+            s += v;
+            ss += v * v;
+        }
+    red[0][q][c] = s;
+    red[1][q][c] = ss;
+    __syncthreads();
+    if (q != 0 || h >= H) return;
+    double tot[2] = {0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < CS_LANES; ++i) { tot[0] += red[0][i][c]; tot[1] += red[1][i][c]; }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        double v = tot[k];
+        float* out = ws + (size_t)k * 3 * H + h;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float t = (float)v;
+            out[(size_t)j * H] = t;
+            v -= (double)t;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- column reductions
 // Partial sums over RB rows for 256 columns per block (4 waves x 64 lanes x float4... here
 // one column per lane-slot of a float4).  MODE 0: sum x.  MODE 1: (sum dy, sum dy*xhat) with
@@ -411,6 +450,15 @@ extern "C" int sparch_bn_finalize(int H, int M, int n_tiles, int dup, const floa
                        n_tiles, dup, colstat_ws, gamma, beta, running_mean, running_var, momentum, eps,
                        training, scale, shift, save_mean, save_invstd, skip_if_nonzero,
                        reinterpret_cast<long long*>(num_batches_tracked));
+    SPARCH_CHECK_LAUNCH();
+    return SPARCH_OK;
+}
+
+extern "C" int sparch_bn_colstat_exact(int M, int H, const float* x, float* colstat_ws, void* stream) {
+    SPARCH_ENTER();
+    if (M <= 0 || H <= 0 || !x || !colstat_ws) return SPARCH_EINVAL;
+    hipLaunchKernelGGL(colstat_exact_kernel, dim3(cdiv(H, CS_COLS)), dim3(256), 0, (hipStream_t)stream, M, H, x,
+                       colstat_ws);
     SPARCH_CHECK_LAUNCH();
     return SPARCH_OK;
 }

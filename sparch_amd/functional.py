@@ -83,6 +83,11 @@ BN_MOMENTUM = 0.05  # snns.py:240
 # parameters' own gradients stay local sums (the gradient all-reduce averages them like every other one).
 SYNC_BN = None
 NORM_EPS = 1e-5
+# BatchNorm over at most this many rows takes its statistics from exact column sums of the projection
+# (sparch_bn_colstat_exact) instead of the GEMM epilogue's fp32 partials, whose E[x^2] - mean^2 loses
+# log2((mean^2 + var) / var) bits: the baselines' readout normalises softmax sums over the batch alone, where that
+# ratio reaches 3e4.  Above it the second read of the projection would cost what the epilogue saves.
+BN_EXACT_ROWS = 1024
 
 ALPHA_LIM = (0.8187307530779818, 0.9607894391523232)  # exp(-1/5), exp(-1/25)   snns.py:229
 BETA_LIM = (0.9672161004820059, 0.9917012926388759)  # exp(-1/30), exp(-1/120)  snns.py:357
@@ -534,6 +539,9 @@ class _Norm:
             mean = torch.empty(H, dtype=torch.float32, device=dev)
             invstd = torch.empty(H, dtype=torch.float32, device=dev)
             n_tiles, rows = (M + 127) // 128, (M if n_valid is None else n_valid)
+            if training and M <= BN_EXACT_ROWS and Wx_raw.is_contiguous():
+                colstat, n_tiles = torch.empty(2 * 3 * H, dtype=torch.float32, device=dev), 3
+                check(lib.sparch_bn_colstat_exact(M, H, ptr(Wx_raw), ptr(colstat), _stream()), "sparch_bn_colstat_exact")
             if training and SYNC_BN is not None and SYNC_BN["world"] > 1:
                 import torch.distributed as dist
 

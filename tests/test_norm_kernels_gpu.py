@@ -7,6 +7,8 @@ with its fp64 restatement in tests/norm_numpy.py (itself pinned to torch fp64 by
                                    v < 0 clamp, error codes
                                 b: the GEMM epilogue's partials of columns with mean/std up to 100 (the variance
                                    comes from sum(v^2)/M - mean^2, which cancels there), both DENSE_GEMM settings
+  sparch_bn_colstat_exact       b: the fp64 column sums in three fp32 terms, columns with mean/std up to 1000, through
+                                   sparch_bn_finalize: the variance to u * var
   sparch_bn_bwd_reduce          c: colpartial_kernel<1>: vector and scalar column tails, ragged row blocks
   sparch_bn_bwd_apply_planes    d: odd M, a striding grid, dy2 / dx NULL or not; against sparch_bn_bwd_apply
   sparch_layernorm_fwd / _bwd   e: H < 64, H % 64 != 0, Hn < H, M % 4 != 0, offset rows, dx aliasing dy
@@ -320,8 +322,58 @@ def test_gemm_colstats_and_finalize_of_off_centre_columns(M, K, H, dense, monkey
     np.testing.assert_allclose(N(o["invstd"]), 1.0 / np.sqrt(var_got + EPS), rtol=1e-6)
 
 
+@pytest.mark.parametrize("M,H", [(1, 17), (2, 1), (9, 130), (17, 36), (33, 260), (130, 16), (1024, 20)])
+def test_exact_colstats_and_finalize_of_off_centre_columns(M, H, record_property):
+    """sparch_bn_colstat_exact: the fp64 column sums of x and x * x as three fp32 terms each, which sparch_bn_finalize
+    sums as three tile rows.  Columns with mean / std = 0, 10, 100, 1000 (the baselines' readout reaches 180).  M: one
+    row, fewer rows than the 16 row-lanes, more, a multiple of them and not; H: one column, a ragged last block of 16.
+
+    The three terms of a sum add up to it exactly in fp64 (24 + 24 + 24 >= 53 bits), and the fp64 sums differ from
+    numpy's only by the order of at most M additions: 2^-53 M sum|terms|.  The variance finalize forms from them is a
+    difference in fp64 of two numbers that large, then one rounding to fp32:
+        |var_got - var| <= u var + 2^-52 M (E[v^2] + 2 |mean| E|v|)
+    so at mean / std = 1000 and M = 1024 the relative error stays at u, where the epilogue's partials give 1.4e-3 at
+    mean / std = 100 (test_gemm_colstats_and_finalize_of_off_centre_columns)."""
+    c = _capi()
+    rng = np.random.default_rng(100 * M + H)
+    ratios = np.array([0.0, 10.0, 100.0, 1000.0])[np.arange(H) % 4]
+    v = rng.standard_normal((M, H))
+    if M > 1:
+        v = (v - v.mean(0)) / v.std(0) * rng.uniform(0.05, 2.0, H)
+        v = v + ratios * v.std(0)
+    x = embed(D(v, F32))
+    v = N(x).astype(np.float64)
+    ws = embed(nan_(6, H))
+    assert c.lib.sparch_bn_colstat_exact(M, H, c.ptr(x), c.ptr(ws), None) == 0
+    got = N(ws).astype(np.float64).reshape(2, 3, H)
+    x.check("x")
+    ws.check("colstat_ws")
+    order = 2.0 ** -53 * M
+    within(got[0].sum(0), v.sum(0), order * np.abs(v).sum(0) + 1e-300, "column sum")
+    within(got[1].sum(0), (v * v).sum(0), order * (v * v).sum(0) + 1e-300, "column sum of squares")
+    assert (np.abs(got[:, 1]) <= 2 * U * np.abs(got[:, 0])).all() and (np.abs(got[:, 2]) <= 2 * U * np.abs(got[:, 1])).all()
+    for bad in ((0, H, c.ptr(x), c.ptr(ws)), (M, 0, c.ptr(x), c.ptr(ws)), (M, H, None, c.ptr(ws)), (M, H, c.ptr(x), None)):
+        assert c.lib.sparch_bn_colstat_exact(*bad, None) == EINVAL
+    if M == 1:          # one value per column: finalize refuses, as nn.BatchNorm1d does
+        return
+    o = {k: nan_(H) for k in ("scale", "shift", "mean", "invstd")}
+    rm, rv = torch.zeros(H, device=DEV), torch.zeros(H, device=DEV)
+    gd, bd = D(np.ones(H), F32), D(np.zeros(H), F32)
+    c.check(c.lib.sparch_bn_finalize(H, M, 3, 1, c.ptr(ws), c.ptr(gd), c.ptr(bd), c.ptr(rm), c.ptr(rv), 1.0, EPS, 1,
+                                     c.ptr(o["scale"]), c.ptr(o["shift"]), c.ptr(o["mean"]), c.ptr(o["invstd"]), None,
+                                     None, None), "sparch_bn_finalize")
+    mean, var = v.mean(0), v.var(0)
+    var_got = N(rv).astype(np.float64) * ((M - 1.0) / M)
+    e1, e2 = np.abs(v).mean(0), (v * v).mean(0)
+    within(N(o["mean"]), mean, U * np.abs(mean) + 2.0 ** -52 * M * e1 + 1e-300, "mean")
+    f = within(var_got, var, U * var + 2.0 ** -52 * M * (e2 + 2 * np.abs(mean) * e1), "variance")
+    record_property("var_err_over_bound", f)
+    record_property("var_relerr", float((np.abs(var_got - var) / var).max()))
+    np.testing.assert_allclose(N(o["invstd"]), 1.0 / np.sqrt(var_got + EPS), rtol=1e-6)
+
+
 # ================================================================================== c. bn_bwd_reduce, f. colsum
-PAIRS = [(1, 1), (3, 3), (255, 4), (256, 30), (257, 252), (513, 256), (513, 260), (257, 1028), (1, 260), (255, 1028),
+PAIRS =[(1, 1), (3, 3), (255, 4), (256, 30), (257, 252), (513, 256), (513, 260), (257, 1028), (1, 260), (255, 1028),
          (3, 30), (256, 3)]
 assert {m for m, _ in PAIRS} == {1, 3, 255, 256, 257, 513} and {h for _, h in PAIRS} == {1, 3, 4, 30, 252, 256, 260, 1028}
 
